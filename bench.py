@@ -3,13 +3,19 @@
 of the HIP generator on 10 s x batch-32 utterances per GPU (BASELINE.json metric,
 configs[2] workload: "Batch-32 VCTK val-set resynthesis only").
 
-    python bench.py [--gpus N --steps K --warmup W]          (N > 1: spawns N ranks itself)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   (N > 1: spawns N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the generator over one batch of 32 synthetic 10 s utterances
 per rank (inputs resident in HBM), followed -- for N > 1 -- by the path's single RCCL
 all-gather of the decoded waveforms.  Weak scaling: per-GPU work is fixed.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with the
+roofline figure of those same steps).  --full adds the other legs: strong scaling, the
+D2H-inclusive figure, B = 1 latency, split-bf16, the full pipeline, the CPU baseline and
+the in-run parity check against the oracle (each of them can be left out with its --no-* option).
+--dump-outputs DIR writes the waveforms of the last timed step as DIR/waveforms.npy.
 """
 import argparse
 import json
@@ -637,6 +643,23 @@ def hbm_traffic(B, T):
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(path, wav, seed=0):
+    """--dump-outputs: the waveforms a caller of the timed step receives, from the last timed step ([B,1,L] at N = 1, the
+    all-gathered [N*B,1,L] at N > 1), as <path>/waveforms.npy in float32.  Above DUMP_LIMIT_BYTES: a fixed, seeded sample
+    of whole utterances in ascending order, the same rows at every run of the same shape."""
+    os.makedirs(path, exist_ok=True)
+    w = wav.detach().float().cpu().numpy()
+    if w.nbytes > DUMP_LIMIT_BYTES:
+        rows = max(1, DUMP_LIMIT_BYTES // w[0].nbytes)
+        w = w[np.sort(np.random.RandomState(seed).choice(w.shape[0], rows, replace=False))]
+    if w.nbytes > DUMP_LIMIT_BYTES:  # one utterance longer than the limit: its leading samples
+        w = w[..., :DUMP_LIMIT_BYTES // (w.itemsize * w[..., 0].size)]
+    np.save(os.path.join(path, "waveforms.npy"), np.ascontiguousarray(w))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--cpu-node-worker":
         return cpu_node_worker(sys.argv[2:])
@@ -646,6 +669,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=500)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the waveforms of the last one as DIR/waveforms.npy (float32; a fixed, "
+                         "seeded sample of whole utterances above 64 MB); the inputs are seeded, the same at every run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: strong scaling, D2H-inclusive, B = 1 latency, split-bf16, "
+                         "full pipeline, CPU baseline and in-run parity against the oracle (the --no-* options skip single legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-split-bf16", action="store_true", help="skip the extra split-bf16 leg (N=1 only)")
     ap.add_argument("--no-pipeline", action="store_true", help="skip the full-pipeline leg (N=1 only)")
@@ -774,11 +803,13 @@ def main():
 
     audio_sec_per_step = world * B * T * hop / 16000.0
     value = audio_sec_per_step * a.steps / dt
-    y_head = y[:8].cpu() if rank == 0 else None  # the timed loop's last fp32 batch, for the in-run parity figure
+    y_head = y[:8].cpu() if rank == 0 and a.full else None  # the timed loop's last fp32 batch, for the in-run parity figure
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, gathered if dist is not None else y)  # what a caller of the step receives
 
     # strong-scaling figure (every rank takes part; rank 0 reports): a fixed ragged job list at every N
     strong = None
-    if not a.no_strong:
+    if a.full and not a.no_strong:
         try:
             strong = strong_leg(synth, g, dev, rank, world, dist, fake)
         except Exception as e:  # noqa: BLE001
@@ -831,31 +862,31 @@ def main():
                                       "frac": round(gbps / HBM_PEAK_GBPS, 4)}
         if strong is not None:
             out["strong"] = strong
-        # the extra legs never decide whether the headline line gets printed
-        if n_gpus == 1 and not fake and not a.no_d2h:
+        # the extra legs (--full only) never decide whether the headline line gets printed
+        if a.full and n_gpus == 1 and not fake and not a.no_d2h:
             try:
                 out["d2h_inclusive"] = d2h_leg(g, d_code, d_f0, d_spkr, a.steps, audio_sec_per_step)
             except Exception as e:  # noqa: BLE001
                 out["d2h_inclusive"] = {"error": f"{type(e).__name__}: {e}"}
-        if n_gpus == 1 and not fake and not a.no_latency:
+        if a.full and n_gpus == 1 and not fake and not a.no_latency:
             try:
                 out["latency"] = latency_leg(synth, g, dev)
             except Exception as e:  # noqa: BLE001
                 out["latency"] = {"error": f"{type(e).__name__}: {e}"}
-        if not a.no_split_bf16 and n_gpus == 1 and not fake:
+        if a.full and not a.no_split_bf16 and n_gpus == 1 and not fake:
             try:
                 out["split_bf16"] = split_bf16_leg(synth, sd, dev, d_code, d_f0, d_spkr, y, a.steps,
                                                    audio_sec_per_step, flops_step)
             except Exception as e:  # noqa: BLE001
                 out["split_bf16"] = {"error": f"{type(e).__name__}: {e}"}
-        if not a.no_pipeline and n_gpus == 1 and not fake:
+        if a.full and not a.no_pipeline and n_gpus == 1 and not fake:
             try:
                 out["pipeline"] = pipeline_leg(synth, dev, g)
             except Exception as e:  # noqa: BLE001
                 out["pipeline"] = {"error": f"{type(e).__name__}: {e}"}
         y_split = out["split_bf16"].pop("_y_head", None) if isinstance(out.get("split_bf16"), dict) else None
         parity_failed = None
-        if not a.no_cpu_baseline and n_gpus == 1:
+        if a.full and not a.no_cpu_baseline and n_gpus == 1:
             try:
                 out["cpu_baseline"], ref_waves = cpu_baseline(synth, sd, torch.from_numpy(code), torch.from_numpy(f0),
                                                               torch.from_numpy(spkr))
@@ -869,7 +900,7 @@ def main():
                                      f"rel {pr['rel']:.3e} (tol {PARITY_TOL_REL})")
             except Exception as e:  # noqa: BLE001
                 out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
-        elif not a.no_cpu_baseline and not fake:
+        elif a.full and not a.no_cpu_baseline and not fake:
             # N > 1: no CPU timing (rank 0, N = 1 only), but rank 0's timed batch is still checked against the oracle in the same run
             try:
                 from oracle import generator_ref as gr

@@ -18,7 +18,7 @@ def test_bench_two_ranks_gloo_dry_run():
     env = dict(os.environ, DISSC_BENCH_FAKE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--frames", "20"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--frames", "20", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -60,6 +60,51 @@ def test_bench_refuses_world_size_mismatch():
            "--batch", "1", "--frames", "10"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode != 0 and "--gpus 2" in (r.stdout + r.stderr)
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the extra legs; --dump-outputs writes the waveforms of the
+    last timed step, the same bits at every run with the same arguments (seeded inputs).  N = 1 and N = 2 (all-gathered)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["DISSC_BENCH_FAKE"] = "1"
+    for gpus in (1, 1, 2):
+        d = tmp_path / f"out{gpus}"
+        first = np.load(d / "waveforms.npy") if d.exists() else None
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "4", "--warmup", "1",
+               "--batch", "3", "--frames", "10", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == 4 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["n_gpus"] == gpus
+        assert j["unit"] == "audio-sec/sec" and j["higher_is_better"] is True and j["dtype"] == "f32" and j["metric"]
+        assert not {"strong", "cpu_baseline", "parity", "latency", "pipeline", "split_bf16", "d2h_inclusive"} & set(j), sorted(j)
+        w = np.load(d / "waveforms.npy")
+        assert w.dtype == np.float32 and w.shape == (gpus * 3, 1, 3200) and np.isfinite(w).all()
+        if first is not None:
+            assert np.array_equal(w, first)
+
+
+def test_dump_outputs_samples_large_outputs():
+    """above 64 MB --dump-outputs keeps a fixed, seeded sample of whole utterances (ascending), at most 64 MB"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import torch
+
+    import bench
+    import tempfile
+    wav = torch.arange(120 * 160000, dtype=torch.float32).reshape(120, 1, 160000)  # 76.8 MB
+    got = []
+    for _ in range(2):
+        with tempfile.TemporaryDirectory() as d:
+            bench.dump_outputs(d, wav)
+            got.append(np.load(os.path.join(d, "waveforms.npy")))
+    w = got[0]
+    assert w.dtype == np.float32 and w.nbytes <= bench.DUMP_LIMIT_BYTES and w.shape[1:] == (1, 160000) and w.shape[0] >= 100
+    rows = w[:, 0, 0].astype(np.int64) // 160000
+    assert (np.diff(rows) > 0).all() and np.array_equal(w, wav.numpy()[rows]) and np.array_equal(w, got[1])
 
 
 def test_cpu_baseline_and_in_run_parity_figure():

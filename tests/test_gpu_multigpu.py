@@ -46,7 +46,7 @@ def _torchrun(n, script, args):
 @pytest.fixture(scope="module")
 def bench2():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--no-split-bf16", "--no-pipeline", "--no-d2h"],
+                        "--full", "--no-split-bf16", "--no-pipeline", "--no-d2h"],
                        env=_clean_env(NCCL_DEBUG="VERSION"), capture_output=True, text=True, timeout=1800, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

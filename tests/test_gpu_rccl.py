@@ -104,7 +104,7 @@ def test_sr_inference_on_rccl_world_size_one_matches_no_process_group(tmp_path):
 def test_bench_on_rccl_world_size_one():
     """bench.py with the process group forced: the weak-scaling step's all-gather and the strong leg's exchange run on
     RCCL; the line names every collective."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-split-bf16", "--no-pipeline", "--no-d2h"],
                        env=_env(DISSC_FORCE_DIST="1", MASTER_PORT=str(_free_port())), capture_output=True, text=True,
                        timeout=900, cwd=ROOT)
@@ -122,7 +122,7 @@ def test_bench_two_ranks_sharing_this_gpu():
     """bench.py --gpus 2 on the HIP path with both ranks on this box's one GPU (gloo stages the device tensors through
     the host; RCCL needs one GPU per rank): the weak-scaling step with its all-gather, and the strong-scaling leg with
     the job list really split over two ranks -- per-rank compute times, one collective, LPT imbalance close to 1."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-split-bf16", "--no-pipeline", "--no-d2h"],
                        env=_env(DISSC_BENCH_BACKEND="gloo"), capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
