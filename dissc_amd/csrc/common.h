@@ -327,6 +327,7 @@ int make_convT(const float* w, const float* bias, int Cin, int Cout, int k, int 
                std::vector<DevConv>& groups);
 int set_affine(DevConv& dc, const float* scale, const float* shift, int n);  // host pointers
 void free_conv(DevConv& dc);
+// dispatches on dc.wino: the transform-domain layers run through run_wino / run_wino8
 int run_conv(const DevConv& dc, const float* x, float* out, const float* res, float* acc,
              const int32_t* lengths, int len_default, int len_mul, int B, int C_x, int ldx, int ldo,
              int Lmax, float slope, int epi, float mrf_div, hipStream_t stream, float out_slope = 0.f, int dma_in = 0);
@@ -340,7 +341,6 @@ int run_conv_ex(const DevConv& dc, const float* x, float* out, const float* res,
 
 // Toom-Cook F(4,3) form of the wide ResBlock convs (conv_wino.hip)
 bool wino_supported(int Cout, int Cin, int KS, int dil);
-bool wino_wanted(int C, int KS);
 int make_wino(const float* w, const float* bias, int C, int KS, int dil, DevConv& dc);
 double wino_executed_macs_per_t(int C, int KS);
 int run_wino(const DevConv& dc, const float* x, float* out, const float* res, float* acc, const int32_t* lengths,
@@ -349,9 +349,7 @@ int run_wino(const DevConv& dc, const float* x, float* out, const float* res, fl
 
 // Toom-Cook F(6,3) form on 8-wave workgroups (conv_wino8.hip): the k = 7 / 11 ResBlock convs of the C >= 64 stages
 bool wino8_supported(int Cout, int Cin, int KS, int dil);
-bool wino8_wanted(int C, int KS, int dil);
 bool wino8_r4_supported(int C, int KS, int dil);
-int wino8_taps(int C, int KS, int dil);  // 3 or 4: the generator's policy for a wino8 layer
 int make_wino8(const float* w, const float* bias, int C, int KS, int dil, DevConv& dc, int R = 3);  // sets dc.wino = 2, dc.wr = R
 double wino8_executed_macs_per_t(int C, int KS, int R);
 int run_wino8(const DevConv& dc, const float* x, float* out, const float* res, float* acc, const int32_t* lengths,
@@ -367,7 +365,7 @@ struct DevPairW {
   int C = 0, KS = 0, dil = 1;
   int form = 0;  // 0: respair_wino_kernel (F(4,3), Y exchanged through LDS); 1: respair32_f23_kernel (F(2,3), register-only)
 };
-// register-only F(2,3) pairs of the 32-channel stage, k = 11 (respair_f23.hip)
+// register-only F(2,3) pairs of the 16- and 32-channel stages, k = 11 (respair_f23.hip, respair16_f23.hip)
 bool pair_f23_supported(int C, int KS, int dil);
 int pack_pair_f23(const float* w, float** dev, int C, int KS);
 int launch_pair_f23(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
@@ -378,8 +376,8 @@ int pack_pairw43(const float* w, int C, int KS, float** dev);
 int launch_pairw43(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default, int len_mul,
                    int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream);
 bool pairw_supported(int C, int KS, int dil);
-bool pairw_wanted(int C, int KS, int dil);  // the generator's policy ("pair_wino" option)
-int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, DevPairW& pw);
+// f23: the F(2,3) form (pair_f23_supported), else the F(4,3) one (pairw_supported)
+int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, bool f23, DevPairW& pw);
 void free_pairw(DevPairW& pw);
 int launch_respair_wino(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
                         int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream);
@@ -398,7 +396,6 @@ int launch_resblock_bf3(int C, const float* x, float* acc, const float* wpack, c
                         const int32_t* lengths, int len_default, int len_mul, int KS, const int* dil,
                         int B, int Lmax, int ld, float slope, int epi, float mrf_div, int m0, int m1,
                         hipStream_t stream);
-bool resblock_bf3_pairs(int C);  // run the block as three pair launches (wide halos, little LDS)
 
 // HuBERT's stride-2, k = 3 feature convs in polyphase Toom-Cook form (conv_s2tc.hip)
 struct DevS2tc {

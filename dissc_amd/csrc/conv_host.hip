@@ -160,6 +160,14 @@ int run_conv_ex(const DevConv& dc, const float* x, float* out, const float* res,
 int run_conv(const DevConv& dc, const float* x, float* out, const float* res, float* acc,
              const int32_t* lengths, int len_default, int len_mul, int B, int C_x, int ldx, int ldo,
              int Lmax, float slope, int epi, float mrf_div, hipStream_t stream, float out_slope, int dma_in) {
+  if (dc.wino) {  // transform-domain layers: no activated store (EPI_STORE_ACT, out_slope), no LDS-DMA input
+    if (epi == EPI_STORE_ACT || dma_in || C_x != dc.CIN) {
+      set_error("run_conv: transform-domain layer (C = %d, k = %d): no EPI_STORE_ACT, no dma_in, C_x must be C (%d)", dc.M, dc.KS, C_x);
+      return DISSC_EINVAL;
+    }
+    return (dc.wino == 2 ? run_wino8 : run_wino)(dc, x, out, res, acc, lengths, len_default, len_mul, B, ldx, ldo, Lmax, slope, epi,
+                                                 mrf_div, stream);
+  }
   ConvIO io;
   io.lengths_in = lengths; io.len_default = len_default; io.len_mul = len_mul;
   return run_conv_ex(dc, x, out, res, acc, io, B, C_x, ldx, ldo, Lmax, slope, epi, mrf_div, stream, out_slope, dma_in);

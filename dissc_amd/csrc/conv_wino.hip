@@ -38,11 +38,6 @@
 
 namespace dissc {
 
-// option "wino" (Options::wino, default 1): "wino" option: 1 = wide ResBlock convs through conv_wino_kernel (read at dissc_gen_create);
-                         // 2 = the stand-alone dissc_conv1d entry uses it too (tests)
-// option "wino_min_c" (Options::wino_min_c, default 64): "wino_min_c" option: narrowest stage that uses it
-// option "wino_c64_kmin" (Options::wino_c64_kmin, default 3): "wino_c64_kmin" option: smallest kernel size that uses it in a 64-channel stage (in the generator k = 3 /
-                         // 7 gain 2 % per forward there; in isolation they are break-even against the DMA-staged direct pair)
 // option "wino_small" (Options::wino_small, default 96): "wino_small" option: launches with fewer 64 x 64-tile workgroups than this use 32 x 32 wave tiles
 // option "kernel_dbg": diagnostics: knock-outs, bit 0 transform, 1 MFMAs, 2 epilogue, 3 staging
 
@@ -611,13 +606,6 @@ __global__ void __launch_bounds__(768, DISSC_WINO_LB) conv_wino_kernel(const Win
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// the generator's policy (per ResBlock): which (C, k) run in the transform domain
-bool wino_wanted(int C, int KS) {
-  if (!opts().wino || C < opts().wino_min_c) return false;
-  if (C < 128 && KS < opts().wino_c64_kmin) return false;
-  return wino_supported(C, C, KS, 1);
-}
-
 bool wino_supported(int Cout, int Cin, int KS, int dil) {
   // C in {64, 128, 256, 512}: every launch variant (large tiles and the small-grid RH = 2 / TW = 1 one, whose row-tile
   // count C / 64 must divide the 8 XCDs) exists for these; C = 1024 would only fail at forward time on short batches

@@ -35,13 +35,6 @@
 
 namespace dissc {
 
-// option "wino8" (Options::wino8, default 1): "wino8" option (read at dissc_gen_create): 1 (default) = the k = 7 / 11 ResBlock convs the "wino8_mask" names use
-                      // this kernel instead of conv_wino's F(4,3) form; 0 = none; 2 = the stand-alone dissc_conv1d entry uses it too
-                      // (tests).  Per launch it is 3-17 % faster than the F(4,3) form on 26 of the 36 (C, k, d, epilogue) shapes of the
-                      // generator (tools/wino8_gate.py) and 4-9 % slower on the d = 1 shapes of the 128-channel stage (864 workgroups
-                      // = 3.4 rounds of 256 CUs where the F(4,3) tiles make exactly 5.0): the default mask leaves that stage alone.
-                      // Whole forward, same box, two runs each: 35.17 / 35.27 -> 34.84 / 34.91 ms (1.0 %), executed-FLOP utilisation
-                      // 0.62 -> 0.60 (11 % fewer products on those layers in 1 % less time), in-run parity rms 5.5e-7 -> 6.5e-7.
 // option "kernel_dbg": diagnostics: knock-outs, bit 0 transform, 1 MFMAs, 2 epilogue
 // option "wino8_c64_wide" (Options::wino8_c64_wide, default 3): "wino8_c64_wide" option, C = 64 instances: 1 = 64 x 128 tiles (768 outputs), 0 = 64 x 64, 2 = 64 x 64 built for TWO
                            // workgroups per CU (<= 128 registers, <= 80 KB LDS: their phases overlap; +3-9 % on k = 11, mixed on
@@ -679,31 +672,7 @@ bool wino8_supported(int Cout, int Cin, int KS, int dil) {
          (dil == 1 || dil == 3 || dil == 5);
 }
 
-// Which form a ResBlock conv of the C >= 64 stages takes is decided per SHAPE (stage width class, kernel size, dilation), from the
-// per-launch measurements of tools/wino8_gate.py and same-box forward A/Bs (tools/opt_ab.sh): bit 9 cls + 3 ki + di with
-// cls = 0 / 1 / 2 for C = 64 / 128 / >= 256, ki = 0 / 1 / 2 for k = 3 / 7 / 11, di = 0 / 1 / 2 for dilation 1 / 3 / 5 -- in octal
-// three digits per class (k = 11, k = 7, k = 3 from the left), each digit = the dilations d5 d3 d1.
-static int w8_shape_bit(int C, int KS, int dil) {
-  const int cls = C >= 256 ? 2 : C >= 128 ? 1 : 0;
-  return 9 * cls + 3 * (KS == 11 ? 2 : KS == 7 ? 1 : 0) + (dil == 1 ? 0 : dil == 3 ? 1 : 2);
-}
-// option "wino8_mask" (Options::wino8_mask, default 0770770771): "wino8_mask" option: the shapes that run on conv_wino8_kernel (the others stay on conv_wino's F(4,3)) --
-                                // default: every k = 7 / 11 shape, and k = 3, d = 1 at C = 64 (as F(6,3) on the two-per-CU tiles: 4 of the
-                                // 6 launches of that chain, forward 33.47 -> 33.16 ms; the other k = 3 shapes measured neutral)
-bool wino8_wanted(int C, int KS, int dil) {
-  if (!opts().wino8 || !opts().wino || C < opts().wino_min_c || !wino8_supported(C, C, KS, dil)) return false;
-  return (opts().wino8_mask >> w8_shape_bit(C, KS, dil)) & 1;
-}
-
-// option "wino8_r4" (Options::wino8_r4, default 1): "wino8_r4" option (read at dissc_gen_create): 1 = the layers "wino8_r4_mask" names run the eight points as
-                           // F(5,4) (k = 7: 2 sub-filters of 4 taps, k = 11: 3) instead of F(6,3); 2 = dissc_conv1d too (tests); 0 = never
-// option "wino8_r4_mask" (Options::wino8_r4_mask, default 0770770010): "wino8_r4_mask" option, same bit layout as wino8_mask (k = 3 bits ignored) -- default: every k = 7 / 11
-                                   // shape of the C >= 128 stages, and k = 7, d = 1 at C = 64 (the rest of that stage is faster as F(6,3))
 bool wino8_r4_supported(int C, int KS, int dil) { return wino8_supported(C, C, KS, dil) && (KS == 7 || KS == 11); }
-int wino8_taps(int C, int KS, int dil) {  // taps per sub-filter the generator's policy picks for a wino8 layer
-  if (!opts().wino8_r4 || !wino8_r4_supported(C, KS, dil)) return 3;
-  return ((opts().wino8_r4_mask >> w8_shape_bit(C, KS, dil)) & 1) ? 4 : 3;
-}
 
 // w: [C][C][KS] -> U[p][co][ci][j] = sum_i G[p][i] w[co][ci][j + NS i], packed in A-fragment order (make_wino's, 8 points);
 // R = taps per sub-filter (3: F(6,3), 4: F(5,4)), NS = ceil(KS / R)

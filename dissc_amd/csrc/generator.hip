@@ -50,9 +50,156 @@ using namespace dissc;
                                   // 1.3-1.8 ms MORE per forward than the plain three-stream launches (tools/graph_ab.py)
 // option "graph_frames" (Options::graph_frames, default 2048): "graph_frames" option: largest B * Tmax that is graphed
 [[maybe_unused]] static int g_graph_hits = 0, g_graph_captures = 0;  // diagnostics (dissc_get_option)
-// option "pair_dma" (Options::pair_dma, default 1): "pair_dma" option: wide residual pairs hand their intermediate over in the EPI_STORE_ACT layout
 // option "multistream" (Options::multistream, default 1): "multistream" option: concurrent ResBlock chains (read at create)
 // option "par_ups" (Options::par_ups, default 1): "par_ups" option: ConvTranspose phase groups on concurrent streams
+
+// ---- the ResBlock plan -------------------------------------------------------------------------------------------------------
+// Each ResBlock is a chain of three residual pairs x = x + conv_1(lrelu(conv_d(lrelu(x)))).  Which kernels run a chain and its
+// pairs is decided ONCE per handle, by plan_chain() under the handle's options when it is created: packing follows the plan, and
+// the plan is all that the forward and the executed-FLOP count read.  The policy below is the only code that reads the form
+// options (wino, wino8*, pair_*, bf3_pairs) and the handle's precision; the kernel files only say which instances exist
+// (*_supported).
+enum class ChainForm : uint8_t {
+  pairs,      // three pair launches or launch pairs, each in its own PairForm
+  bf3_block,  // split-bf16: the whole block in one launch (resblock_bf3.hip)
+  bf3_pairs,  // split-bf16: the block as three pair launches of the same kernel
+};
+enum class PairForm : uint8_t {
+  direct,      // two direct convs, t through the chain's TMP buffer
+  direct_dma,  // ... the first stores lrelu(t) with zero tails (EPI_STORE_ACT): the second stages its windows by LDS-DMA
+  td,          // two transform-domain convs (PairPlan::conv)
+  fused,       // one launch, direct, t in LDS (respair.hip)
+  fused_td,    // one launch, both convs in the transform domain (PairPlan::f23)
+};
+enum class ConvForm : uint8_t { direct, f43, f63, f54 };  // f43: conv_wino.hip; f63 / f54: conv_wino8.hip with 3 / 4-tap sub-filters
+struct PairPlan {
+  PairForm form = PairForm::direct;
+  ConvForm conv[2] = {ConvForm::direct, ConvForm::direct};  // conv_d, conv_1
+  bool f23 = false;  // fused_td: the register-only F(2,3) kernels (respair_f23.hip); else F(4,3) (respair_wino.hip, experimental)
+};
+struct ChainPlan {
+  ChainForm form = ChainForm::pairs;
+  PairPlan pair[3];
+};
+
+// option "wino" (Options::wino, default 1): 1 = the ResBlock convs of the stages with C >= wino_min_c (64; at C = 64 those with
+//   k >= wino_c64_kmin = 3: k = 3 / 7 gain 2 % per forward there, in isolation break-even against the DMA-staged direct pair) run
+//   in the Toom-Cook transform domain; 0 = all direct (and no fused transform-domain pairs either); 2 = dissc_conv1d too (tests)
+static bool wino_wanted(int C, int KS) {
+  if (!opts().wino || C < Options::wino_min_c) return false;
+  if (C < 128 && KS < Options::wino_c64_kmin) return false;
+  return wino_supported(C, C, KS, 1);
+}
+
+// option "wino8" (Options::wino8, default 1): 1 = the transform-domain convs "wino8_mask" names run on conv_wino8.hip's eight
+//   points instead of conv_wino's F(4,3) form; 0 = none; 2 = dissc_conv1d too (tests).  Per launch 3-17 % faster than F(4,3) on 26
+//   of the 36 (C, k, d, epilogue) shapes of the generator (tools/wino8_gate.py), 4-9 % slower on the d = 1 shapes of the
+//   128-channel stage (864 workgroups = 3.4 rounds of 256 CUs where the F(4,3) tiles make exactly 5.0): the default mask leaves
+//   that stage alone.  Whole forward 35.17 / 35.27 -> 34.84 / 34.91 ms, in-run parity rms 5.5e-7 -> 6.5e-7.
+// option "wino8_mask" (Options::wino8_mask, default 0770770771): one bit per SHAPE, from per-launch measurements and same-box
+//   forward A/Bs (tools/opt_ab.sh): bit 9 cls + 3 ki + di with cls = 0 / 1 / 2 for C = 64 / 128 / >= 256, ki = 0 / 1 / 2 for
+//   k = 3 / 7 / 11, di = 0 / 1 / 2 for dilation 1 / 3 / 5 -- in octal three digits per class (k = 11, k = 7, k = 3 from the left),
+//   each digit = the dilations d5 d3 d1.  Default: every k = 7 / 11 shape, and k = 3, d = 1 at C = 64 (F(6,3) on the two-per-CU
+//   tiles: forward 33.47 -> 33.16 ms; the other k = 3 shapes measured neutral).
+// option "wino8_r4" (Options::wino8_r4, default 1): 1 = the shapes "wino8_r4_mask" (same layout, k = 3 bits ignored; default every
+//   k = 7 / 11 shape of the C >= 128 stages and k = 7, d = 1 at C = 64) run as F(5,4) instead of F(6,3); 2 = dissc_conv1d too
+//   (tests); 0 = never
+static int w8_shape_bit(int C, int KS, int dil) {
+  const int cls = C >= 256 ? 2 : C >= 128 ? 1 : 0;
+  return 9 * cls + 3 * (KS == 11 ? 2 : KS == 7 ? 1 : 0) + (dil == 1 ? 0 : dil == 3 ? 1 : 2);
+}
+static ConvForm td_conv_form(int C, int KS, int dil) {
+  if (!opts().wino8 || !wino8_supported(C, C, KS, dil) || !((opts().wino8_mask >> w8_shape_bit(C, KS, dil)) & 1))
+    return ConvForm::f43;
+  const bool r4 = opts().wino8_r4 && wino8_r4_supported(C, KS, dil) && ((opts().wino8_r4_mask >> w8_shape_bit(C, KS, dil)) & 1);
+  return r4 ? ConvForm::f54 : ConvForm::f63;
+}
+
+// option "pair_f23" (Options::pair_f23, default 3), a bit mask: 1 = the C = 32, k = 11 pairs run as register-only F(2,3)
+//   (respair_f23.hip; per launch 857 / 894 / 924 us at d = 1 / 3 / 5 against 1 042 / 1 037 / 1 052 for the direct pair,
+//   B = 32 x 10 s), 2 = the C = 16, k = 11 pairs (respair16_f23.hip: 525 against 604 us at d = 1); 4 / 8 = the k = 3 pairs of the
+//   two stages (C = 32: 365 against 417 us, C = 16: 262 against 263; forward 33.11 -> 33.09 ms: off).  Also picks the form of
+//   dissc_respair1d's mode 3.
+static bool pair_f23_wanted(int C, int KS, int dil) {
+  return pair_f23_supported(C, KS, dil) && (opts().pair_f23 & ((C == 32 ? 1 : 2) << (KS == 3 ? 2 : 0)));
+}
+// option "pair_wino" (Options::pair_wino, default 0; experimental builds): 1 = the pairs respair_wino.hip's F(4,3) kernel measured
+//   faster for (tools/pair_gate.py, B = 32 x 10 s: C = 32, k = 11, d = 1 / 3: 895 / 988 us against 1 042 / 1 047 for the direct
+//   fused pair; C = 64, k = 3, d = 1: 624 against 658 for two conv_wino launches) run on it; 2 = every shape with an instance
+//   (tests); 0 = none.  Off: its gate failed (whole forward 35.36 against 35.42 ms, executed-FLOP utilisation 0.619 -> 0.602).
+static bool pairw_wanted(int C, int KS, int dil) {
+  if (pair_f23_wanted(C, KS, dil)) return true;
+  if (!opts().pair_wino || !pairw_supported(C, KS, dil)) return false;
+  if (opts().pair_wino >= 2) return true;
+  if (C == 32) return KS == 11 && dil <= 3;
+  return C == 64 && KS == 3 && dil == 1;
+}
+
+// bf3_pairs (a constant now, Options::bf3_pairs = -1): split-bf16 blocks of >= 64 channels run as three pair launches.  With 64
+// channels the LDS holds 256-column windows only, and the 120-column halo of a whole 11-tap block would be recomputed ~2x; a
+// pair's halo is 10-30 columns, at the price of two more read+write passes of x_k per block.
+static bool bf3_pairs_wanted(int C) { return Options::bf3_pairs < 0 ? C >= 64 : Options::bf3_pairs != 0; }
+
+// option "pair_max_c" (Options::pair_max_c, default 32): widest stage whose pairs run as one launch each (0 = off)
+// option "pair_dma" (Options::pair_dma, default 1): the direct pairs of the wide stages hand t over in the EPI_STORE_ACT layout
+static ChainPlan plan_chain(int C, int KS, const int* dil, int prec) {
+  ChainPlan cp;
+  if (prec == 1 && resblock_bf3_supported(C, KS, dil)) {
+    cp.form = bf3_pairs_wanted(C) ? ChainForm::bf3_pairs : ChainForm::bf3_block;
+    return cp;
+  }
+  // the direct fused pair needs fp32 weights in its layout (16x16x4 at C = 16, 32x32x2 at C = 32: make_conv's choice)
+  bool fused = prec == 0 && (C < 32 || opts().use_mfma32) && C <= opts().pair_max_c;
+  for (int m = 0; m < 3; ++m) fused = fused && respair_supported(C, KS, dil[m]);
+  for (int m = 0; m < 3; ++m) {
+    PairPlan& p = cp.pair[m];
+    const int d = dil[m];
+    const bool td = prec == 0 && wino_wanted(C, KS) && wino_supported(C, C, KS, d);
+    // a fused transform-domain pair writes a new x_k: at C = 64 (where the other pairs update x_k in place) and in a chain whose
+    // pairs do not all fuse, only the first pair of the chain takes it
+    const bool fuse_td =
+        prec == 0 && opts().wino && pairw_wanted(C, KS, d) && (C > 32 ? td : C <= opts().pair_max_c) && (fused || m == 0);
+    if (fuse_td) {
+      p.form = PairForm::fused_td;
+      p.f23 = pair_f23_wanted(C, KS, d);
+    } else if (fused) {
+      p.form = PairForm::fused;
+    } else if (td) {
+      p.form = PairForm::td;
+      p.conv[0] = td_conv_form(C, KS, d);
+      p.conv[1] = td_conv_form(C, KS, 1);
+    } else if (opts().pair_dma && prec == 0 && opts().use_mfma32 && C >= 32 && C % KC == 0) {  // both convs on the 32x32x2 kernel, fp32
+      p.form = PairForm::direct_dma;
+    }
+  }
+  return cp;
+}
+
+// multiply-adds per output position of one pair: algorithmic, or what the matrix pipe executes
+static double pair_macs(const PairPlan& p, int C, int KS, bool executed) {
+  const double direct = (double)C * C * KS;
+  auto conv = [&](ConvForm f) {
+    return f == ConvForm::f43 ? wino_executed_macs_per_t(C, KS)
+         : f == ConvForm::f63 ? wino8_executed_macs_per_t(C, KS, 3)
+         : f == ConvForm::f54 ? wino8_executed_macs_per_t(C, KS, 4) : direct;
+  };
+  if (executed && p.form == PairForm::fused_td)  // F(2,3): 4 products per 2 outputs and sub-filter
+    return p.f23 ? 2.0 * C * C * 2.0 * ((KS + 2) / 3) : 2.0 * wino_executed_macs_per_t(C, KS);
+  return executed ? conv(p.conv[0]) + conv(p.conv[1]) : direct + direct;
+}
+
+// a transform-domain or direct conv of a pair, packed for its form
+static int make_pair_conv(ConvForm f, const float* w, const float* b, int C, int KS, int dil, DevConv& dc) {
+  switch (f) {
+    case ConvForm::f43: return make_wino(w, b, C, KS, dil, dc);
+    case ConvForm::f63: return make_wino8(w, b, C, KS, dil, dc, 3);
+    case ConvForm::f54: return make_wino8(w, b, C, KS, dil, dc, 4);
+    default: return make_conv(w, b, C, C, KS, dil, dc);
+  }
+}
+
+// The MRF epilogue of chain j's last launch: xs = r_0; xs += r_j; x = (xs + r_last) / nk
+static int mrf_epi(int j, int nk) { return j == nk - 1 ? EPI_MRF_DIV : j == 0 ? EPI_MRF_SET : EPI_MRF_ADD; }
 
 // The side streams of the concurrent ResBlock chains are shared by every generator handle of a
 // device (created on first use, kept for the life of the process): HIP multiplexes streams onto a
@@ -81,10 +228,10 @@ struct dissc_gen {
   int hop = 1;
   DevConv conv_pre;
   std::vector<std::vector<DevConv>> ups;  // per stage: one conv per phase group
-  std::vector<DevConv> rb1, rb2;  // [stage*nk*3 + j*3 + m]
-  std::vector<DevPairW> pw;       // same index: the pair as ONE transform-domain launch (respair_wino.hip), w1 == nullptr if not
-  std::vector<float*> fused_w, fused_b;  // [stage*nk + j]: 6 packed convs / biases of a split-bf16 fused ResBlock
-  std::vector<char> fused_bf3;           // ... (resblock_bf3.hip; precision = 1 only)
+  std::vector<ChainPlan> plan;     // [stage*nk + j]: the kernel forms of ResBlock j of the stage
+  std::vector<DevConv> rb1, rb2;  // [stage*nk*3 + j*3 + m]: conv_d / conv_1 of pair m (forms direct, direct_dma, td, fused)
+  std::vector<DevPairW> pw;       // same index: the pair as ONE transform-domain launch (form fused_td)
+  std::vector<float*> fused_w, fused_b;  // [stage*nk + j]: 6 packed convs / biases of a split-bf16 ResBlock (bf3_* chains)
   float* post_w = nullptr;
   float* post_b = nullptr;
   int post_C = 0, post_KS = 0;
@@ -306,12 +453,12 @@ int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, s
   int ch = c0, mul = 1;
   g->ups.resize(cfg->num_upsamples);
   const int nk = cfg->num_kernels;
+  g->plan.resize((size_t)cfg->num_upsamples * nk);
   g->rb1.resize((size_t)cfg->num_upsamples * nk * 3);
   g->rb2.resize((size_t)cfg->num_upsamples * nk * 3);
   g->pw.resize((size_t)cfg->num_upsamples * nk * 3);
   g->fused_w.assign((size_t)cfg->num_upsamples * nk, nullptr);
   g->fused_b.assign((size_t)cfg->num_upsamples * nk, nullptr);
-  g->fused_bf3.assign((size_t)cfg->num_upsamples * nk, 0);
   for (int i = 0; i < cfg->num_upsamples; ++i) {
     const int s = cfg->upsample_rates[i], k = cfg->upsample_kernel_sizes[i];
     if (s < 1 || k < s || (k - s) % 2 != 0) {  // L_out = s * L_in needs k - s even
@@ -335,60 +482,36 @@ int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, s
         set_error("dissc_gen_create: even resblock kernel size %d unsupported", rk);
         return fail(DISSC_EINVAL);
       }
-      const bool bf3 = prec == 1 && resblock_bf3_supported(ch, rk, cfg->resblock_dilations[j]);
-      std::vector<float> fw, fb;
-      const float* w6[6];
-      for (int m = 0; m < 3; ++m) {
-        const int d = cfg->resblock_dilations[j][m];
-        const size_t idx = ((size_t)i * nk + j) * 3 + m;
-        snprintf(name, sizeof(name), "resblocks.%d.convs1.%d.weight", i * nk + j, m);
-        if ((rc = get(name, {ch, ch, rk}, &w))) return fail(rc);
-        snprintf(name, sizeof(name), "resblocks.%d.convs1.%d.bias", i * nk + j, m);
-        if ((rc = get(name, {ch}, &b))) return fail(rc);
-        const bool wino = prec == 0 && wino_wanted(ch, rk) && wino_supported(ch, ch, rk, d);
-        const bool w8 = wino && wino8_wanted(ch, rk, d);  // the eight-point forms on 8-wave workgroups (per shape: conv_wino8.hip)
-        {
-          const int taps1 = w8 ? wino8_taps(ch, rk, d) : 0;
-          tasks.push_back([=]() {
-            return w8 ? make_wino8(w, b, ch, rk, d, g->rb1[idx], taps1)
-                      : wino ? make_wino(w, b, ch, rk, d, g->rb1[idx]) : make_conv(w, b, ch, ch, rk, d, g->rb1[idx]);
-          });
-        }
-        const float* w1c = w;
-        const float* b1c = b;
-        if (bf3) {
-          w6[2 * m] = w;
-          fb.insert(fb.end(), b, b + ch);
-        }
-        snprintf(name, sizeof(name), "resblocks.%d.convs2.%d.weight", i * nk + j, m);
-        if ((rc = get(name, {ch, ch, rk}, &w))) return fail(rc);
-        snprintf(name, sizeof(name), "resblocks.%d.convs2.%d.bias", i * nk + j, m);
-        if ((rc = get(name, {ch}, &b))) return fail(rc);
-        const bool wino2 = wino;
-        const bool w82 = wino && wino8_wanted(ch, rk, 1);
-        {
-          const int taps2 = w82 ? wino8_taps(ch, rk, 1) : 0;
-          tasks.push_back([=]() {
-            return w82 ? make_wino8(w, b, ch, rk, 1, g->rb2[idx], taps2)
-                       : wino2 ? make_wino(w, b, ch, rk, 1, g->rb2[idx]) : make_conv(w, b, ch, ch, rk, 1, g->rb2[idx]);
-          });
-        }
-        // the whole pair as one transform-domain launch (respair_wino.hip): C = 32, k = 7 / 11 and C = 64, k = 3
-        // (C = 64: only a chain's FIRST pair -- the later ones update x_k in place, which a fused pair cannot)
-        if (prec == 0 && opts().wino && pairw_wanted(ch, rk, d) && (ch > 32 ? (wino && m == 0) : ch <= opts().pair_max_c))
-          tasks.push_back([=]() { return make_pairw(w1c, b1c, w, b, ch, rk, d, g->pw[idx]); });
-        if (bf3) {
-          w6[2 * m + 1] = w;
-          fb.insert(fb.end(), b, b + ch);
-        }
+      const int* dl = cfg->resblock_dilations[j];
+      const size_t cj = (size_t)i * nk + j;
+      const ChainPlan& cp = g->plan[cj] = plan_chain(ch, rk, dl, prec);
+      const float* w6[6];  // conv_d / conv_1 of the three pairs
+      const float* b6[6];
+      for (int l = 0; l < 6; ++l) {
+        snprintf(name, sizeof(name), "resblocks.%d.convs%d.%d.weight", (int)cj, 1 + l % 2, l / 2);
+        if ((rc = get(name, {ch, ch, rk}, &w6[l]))) return fail(rc);
+        snprintf(name, sizeof(name), "resblocks.%d.convs%d.%d.bias", (int)cj, 1 + l % 2, l / 2);
+        if ((rc = get(name, {ch}, &b6[l]))) return fail(rc);
       }
-      if (bf3) {
+      if (cp.form != ChainForm::pairs) {  // split-bf16: the six convs packed together
+        std::vector<float> fw, fb;
         pack_resblock_bf3(ch, rk, w6, fw);
-        g->fused_bf3[(size_t)i * nk + j] = 1;
+        for (const float* bl : b6) fb.insert(fb.end(), bl, bl + ch);
+        if ((rc = upload(fw, &g->fused_w[cj]))) return fail(rc);
+        if ((rc = upload(fb, &g->fused_b[cj]))) return fail(rc);
+        continue;
       }
-      if (bf3) {
-        if ((rc = upload(fw, &g->fused_w[(size_t)i * nk + j]))) return fail(rc);
-        if ((rc = upload(fb, &g->fused_b[(size_t)i * nk + j]))) return fail(rc);
+      for (int m = 0; m < 3; ++m) {
+        const PairPlan p = cp.pair[m];
+        const size_t idx = cj * 3 + m;
+        const int d = dl[m];
+        const float *w1 = w6[2 * m], *b1 = b6[2 * m], *w2 = w6[2 * m + 1], *b2 = b6[2 * m + 1];
+        if (p.form == PairForm::fused_td) {
+          tasks.push_back([=]() { return make_pairw(w1, b1, w2, b2, ch, rk, d, p.f23, g->pw[idx]); });
+        } else {
+          tasks.push_back([=]() { return make_pair_conv(p.conv[0], w1, b1, ch, rk, d, g->rb1[idx]); });
+          tasks.push_back([=]() { return make_pair_conv(p.conv[1], w2, b2, ch, rk, 1, g->rb2[idx]); });
+        }
       }
     }
   }
@@ -445,46 +568,25 @@ size_t dissc_gen_workspace_bytes(dissc_gen_t g, int B, int Tmax) {
   return (size_t)(2 + 2 * g->cfg.num_kernels) * gen_buf_floats(g, B, Tmax) * sizeof(float) + 256;
 }
 
-double dissc_gen_flops(dissc_gen_t g, int64_t frames) {
-  if (!g) return 0;
+// multiply-adds per input frame: algorithmic, or (executed) what the matrix pipe executes -- the transform-domain forms do fewer
+static double gen_macs(const dissc_gen* g, bool executed) {
   double macs = g->conv_pre.macs_per_t;
   int mul = 1;
   const int nk = g->cfg.num_kernels;
   for (int i = 0; i < g->cfg.num_upsamples; ++i) {
     for (auto& c : g->ups[i]) macs += c.macs_per_t * mul;
     mul = g->stage_mul[i];
-    for (int j = 0; j < nk * 3; ++j)
-      macs += (g->rb1[(size_t)i * nk * 3 + j].macs_per_t + g->rb2[(size_t)i * nk * 3 + j].macs_per_t) * mul;
+    for (int j = 0; j < nk; ++j)
+      for (const PairPlan& p : g->plan[(size_t)i * nk + j].pair)
+        macs += pair_macs(p, g->stage_C[i], g->cfg.resblock_kernel_sizes[j], executed) * mul;
   }
   macs += (double)g->post_C * g->post_KS * mul;
-  return 2.0 * macs * (double)frames;
+  return macs;
 }
 
-// multiply-adds the matrix pipe actually executes: the layers that run in the Toom-Cook transform domain (conv_wino.hip)
-// do 6 ceil(k / 3) / 4 products per output and channel pair instead of k
-double dissc_gen_flops_executed(dissc_gen_t g, int64_t frames) {
-  if (!g) return 0;
-  double macs = g->conv_pre.macs_per_t;
-  int mul = 1;
-  const int nk = g->cfg.num_kernels;
-  auto ex = [](const DevConv& c) {
-    return c.wino == 2 ? wino8_executed_macs_per_t(c.M, c.KS, c.wr) : c.wino ? wino_executed_macs_per_t(c.M, c.KS) : c.macs_per_t;
-  };
-  for (int i = 0; i < g->cfg.num_upsamples; ++i) {
-    for (auto& c : g->ups[i]) macs += c.macs_per_t * mul;
-    mul = g->stage_mul[i];
-    for (int j = 0; j < nk * 3; ++j) {
-      const size_t idx = (size_t)i * nk * 3 + j;
-      if (g->pw[idx].w1)  // the pair runs as one transform-domain launch (respair_wino.hip)
-        macs += (g->pw[idx].form == 1 ? 2.0 * g->pw[idx].C * g->pw[idx].C * 2.0 * ((g->pw[idx].KS + 2) / 3)   // F(2,3): 4 products per 2 outputs and sub-filter
-                                      : 2.0 * wino_executed_macs_per_t(g->pw[idx].C, g->pw[idx].KS)) * mul;
-      else
-        macs += (ex(g->rb1[idx]) + ex(g->rb2[idx])) * mul;
-    }
-  }
-  macs += (double)g->post_C * g->post_KS * mul;
-  return 2.0 * macs * (double)frames;
-}
+double dissc_gen_flops(dissc_gen_t g, int64_t frames) { return g ? 2.0 * gen_macs(g, false) * (double)frames : 0; }
+
+double dissc_gen_flops_executed(dissc_gen_t g, int64_t frames) { return g ? 2.0 * gen_macs(g, true) * (double)frames : 0; }
 
 static int gen_forward_body(dissc_gen_t g, const int64_t* code, const float* f0, const int64_t* spkr,
                             const int32_t* lengths, int B, int Tmax, float* wav_out, void* workspace,
@@ -623,104 +725,58 @@ static int gen_forward_body(dissc_gen_t g, const int64_t* code, const float* f0,
     for (int j = 0; j < nk; ++j) {
       hipStream_t sj = (multi && j > 0) ? g->aux[j] : stream;
       if (multi && j > 0) DISSC_HIP_CHECK(hipStreamWaitEvent(sj, g->ev_x, 0));
-      if (g->fused_w[(size_t)i * nk + j]) {  // narrow stage: the whole ResBlock in one launch
-        const int epi = (j == 0) ? (nk == 1 ? EPI_MRF_DIV : EPI_MRF_SET)
-                                 : (j == nk - 1 ? EPI_MRF_DIV : EPI_MRF_ADD);
-        const bool pairs = g->fused_bf3[(size_t)i * nk + j] && resblock_bf3_pairs(ch);
-        // the MRF update is inside the launch: a whole-block launch has to wait for the previous chain
-        if (multi && j > 0 && !pairs) DISSC_HIP_CHECK(hipStreamWaitEvent(sj, g->ev_fin[j - 1], 0));
-        const float* fw = g->fused_w[(size_t)i * nk + j];
-        const float* fb = g->fused_b[(size_t)i * nk + j];
-        const int rk = c.resblock_kernel_sizes[j];
-        const int* dl = c.resblock_dilations[j];
-        if (!pairs) {
-          rc = launch_resblock_bf3(ch, X, ACC, fw, fb, lengths, L, mul, rk, dl, B, L, ld, 0.1f, epi, (float)nk, 0, 3, sj);
-        } else {  // X -> XK -> TMP -> MRF update of ACC, one launch per residual pair
-          float* xk = multi ? XKj[j] : XKj[0];
-          float* tm = multi ? TMPj[j] : TMPj[0];
-          rc = launch_resblock_bf3(ch, X, xk, fw, fb, lengths, L, mul, rk, dl, B, L, ld, 0.1f, EPI_STORE, 1.f, 0, 1, sj);
-          if (!rc)
-            rc = launch_resblock_bf3(ch, xk, tm, fw, fb, lengths, L, mul, rk, dl, B, L, ld, 0.1f, EPI_STORE, 1.f, 1, 2, sj);
-          if (!rc && multi && j > 0) DISSC_HIP_CHECK(hipStreamWaitEvent(sj, g->ev_fin[j - 1], 0));  // only the last pair
-          if (!rc)
-            rc = launch_resblock_bf3(ch, tm, ACC, fw, fb, lengths, L, mul, rk, dl, B, L, ld, 0.1f, epi, (float)nk, 2, 3, sj);
-        }
-        if (rc) return rc;
+      const size_t cj = (size_t)i * nk + j;
+      const ChainPlan& cp = g->plan[cj];
+      const int rk = c.resblock_kernel_sizes[j];
+      const int* dl = c.resblock_dilations[j];
+      const float* fw = g->fused_w[cj];
+      const float* fb = g->fused_b[cj];
+      float* TMPc = multi ? TMPj[j] : TMPj[0];
+      float* XKc = multi ? XKj[j] : XKj[0];
+      const int mrf = mrf_epi(j, nk);
+      // the chains run concurrently up to the MRF update: the one launch of a chain that updates ACC waits for the previous chain
+      auto acc_turn = [&]() -> int {
+        if (multi && j > 0) DISSC_HIP_CHECK(hipStreamWaitEvent(sj, g->ev_fin[j - 1], 0));
+        return DISSC_OK;
+      };
+      if (cp.form == ChainForm::bf3_block) {  // the whole ResBlock in one launch
+        if ((rc = acc_turn()) ||
+            (rc = launch_resblock_bf3(ch, X, ACC, fw, fb, lengths, L, mul, rk, dl, B, L, ld, 0.1f, mrf, (float)nk, 0, 3, sj)))
+          return rc;
         if (multi) DISSC_HIP_CHECK(hipEventRecord(g->ev_fin[j], sj));
         continue;
       }
-      float* TMPc = multi ? TMPj[j] : TMPj[0];
-      float* XKc = multi ? XKj[j] : XKj[0];
-      {
-        // narrow stages in exact fp32: each residual pair is ONE launch (respair.hip), ping-ponging
-        // X -> XK -> TMP -> MRF update of ACC (a pair cannot run in place: neighbours read its halo)
-        const size_t i0 = ((size_t)i * nk + j) * 3;
-        bool pairs = !g->rb1[i0].prec && g->rb1[i0].m32 == (ch >= 32 ? 1 : 0);
-        for (int m = 0; m < 3 && pairs; ++m)
-          pairs = respair_supported(ch, g->rb1[i0 + m].KS, g->rb1[i0 + m].dil);
-        if (pairs) {
-          const float* src[3] = {X, XKc, TMPc};
-          float* dst[3] = {XKc, TMPc, nullptr};
-          for (int m = 0; m < 3; ++m) {
-            int epi = EPI_RES;
-            if (m == 2) {
-              epi = (j == 0) ? (nk == 1 ? EPI_MRF_DIV : EPI_MRF_SET) : (j == nk - 1 ? EPI_MRF_DIV : EPI_MRF_ADD);
-              if (multi && j > 0) DISSC_HIP_CHECK(hipStreamWaitEvent(sj, g->ev_fin[j - 1], 0));
-            }
-            if (g->pw[i0 + m].w1)
-              rc = launch_respair_wino(g->pw[i0 + m], src[m], dst[m], ACC, lengths, L, mul, B, L, ld, 0.1f, epi, (float)nk, sj);
-            else
-              rc = launch_respair(g->rb1[i0 + m], g->rb2[i0 + m], src[m], dst[m], ACC, lengths, L, mul, B, L, ld, 0.1f, epi,
-                                  (float)nk, sj);
-            if (rc) return rc;
-          }
-          if (multi) DISSC_HIP_CHECK(hipEventRecord(g->ev_fin[j], sj));
-          continue;
-        }
-      }
+      const float* x = X;  // the chain's running x_k: X -> XK -> TMP -> MRF update of ACC where pairs are one launch each
       for (int m = 0; m < 3; ++m) {
-        const size_t idx = ((size_t)i * nk + j) * 3 + m;
-        const float* xin = (m == 0) ? X : XKc;
-        if (m == 0 && g->pw[idx].w1) {
-          // the chain's first pair as ONE transform-domain launch (respair_wino.hip): X -> XK, t never leaves LDS
-          if ((rc = launch_respair_wino(g->pw[idx], xin, XKc, ACC, lengths, L, mul, B, L, ld, 0.1f, EPI_RES, (float)nk, sj)))
+        const size_t idx = cj * 3 + m;
+        const bool last = m == 2;
+        float* nxt = x == XKc ? TMPc : XKc;  // (a one-launch pair cannot run in place: its neighbours read the halo)
+        const PairForm pf = cp.pair[m].form;
+        if (cp.form == ChainForm::bf3_pairs) {
+          if (last && (rc = acc_turn())) return rc;
+          rc = launch_resblock_bf3(ch, x, last ? ACC : nxt, fw, fb, lengths, L, mul, rk, dl, B, L, ld, 0.1f, last ? mrf : EPI_STORE,
+                                   last ? (float)nk : 1.f, m, m + 1, sj);
+          x = nxt;
+        } else if (pf == PairForm::fused || pf == PairForm::fused_td) {
+          if (last && (rc = acc_turn())) return rc;
+          float* out = last ? nullptr : nxt;
+          const int epi = last ? mrf : EPI_RES;
+          rc = pf == PairForm::fused_td
+                   ? launch_respair_wino(g->pw[idx], x, out, ACC, lengths, L, mul, B, L, ld, 0.1f, epi, (float)nk, sj)
+                   : launch_respair(g->rb1[idx], g->rb2[idx], x, out, ACC, lengths, L, mul, B, L, ld, 0.1f, epi, (float)nk, sj);
+          x = nxt;
+        } else {  // two conv launches, t through TMP, x_k updated in place
+          const bool dma = pf == PairForm::direct_dma;
+          const int ldt = dma ? (int)round_up((size_t)L + ZERO_TAIL, 4) : ld;
+          if ((rc = run_conv(g->rb1[idx], x, TMPc, nullptr, nullptr, lengths, L, mul, B, ch, ld, ldt, L, 0.1f,
+                             dma ? EPI_STORE_ACT : EPI_STORE, 1.f, sj, 0.1f, 0)))
             return rc;
-          continue;
+          if (last && (rc = acc_turn())) return rc;
+          rc = run_conv(g->rb2[idx], TMPc, XKc, x, ACC, lengths, L, mul, B, ch, ldt, ld, L, dma ? 1.0f : 0.1f, last ? mrf : EPI_RES,
+                        (float)nk, sj, 0.f, dma ? 1 : 0);
+          x = XKc;
         }
-        if (g->rb1[idx].wino && g->rb2[idx].wino) {
-          // Toom-Cook F(4,3) form (conv_wino.hip): t = conv_d(lrelu(x)); x = x + conv_1(lrelu(t)) / MRF update
-          // per conv: the eight-point forms on 8 waves (conv_wino8.hip) or F(4,3) on 12 (conv_wino.hip)
-          auto runw = g->rb1[idx].wino == 2 ? run_wino8 : run_wino;
-          auto runw2 = g->rb2[idx].wino == 2 ? run_wino8 : run_wino;
-          if ((rc = runw(g->rb1[idx], xin, TMPc, nullptr, nullptr, lengths, L, mul, B, ld, ld, L, 0.1f, EPI_STORE, 1.f, sj)))
-            return rc;
-          int epiw = EPI_RES;
-          if (m == 2) {
-            epiw = (j == 0) ? (nk == 1 ? EPI_MRF_DIV : EPI_MRF_SET) : (j == nk - 1 ? EPI_MRF_DIV : EPI_MRF_ADD);
-            if (multi && j > 0) DISSC_HIP_CHECK(hipStreamWaitEvent(sj, g->ev_fin[j - 1], 0));
-          }
-          if ((rc = runw2(g->rb2[idx], TMPc, XKc, xin, ACC, lengths, L, mul, B, ld, ld, L, 0.1f, epiw, (float)nk, sj)))
-            return rc;
-          continue;
-        }
-        // wide stages: the first conv stores lrelu(t) with zero tails (EPI_STORE_ACT) so that the second one -- the only
-        // reader of t -- stages its windows by LDS-DMA: no staging registers, no masks, one more wave per SIMD
-        const bool dma2 = opts().pair_dma && g->rb1[idx].m32 && g->rb2[idx].m32 && !g->rb1[idx].prec && !g->rb2[idx].prec &&
-                          ch % KC == 0;
-        const int ldt = dma2 ? (int)round_up((size_t)L + ZERO_TAIL, 4) : ld;
-        if ((rc = run_conv(g->rb1[idx], xin, TMPc, nullptr, nullptr, lengths, L, mul, B, ch, ld, ldt,
-                           L, 0.1f, dma2 ? EPI_STORE_ACT : EPI_STORE, 1.f, sj, 0.1f, 0)))
-          return rc;
-        int epi = EPI_RES;
-        if (m == 2) {
-          epi = (j == 0) ? (nk == 1 ? EPI_MRF_DIV : EPI_MRF_SET)
-                         : (j == nk - 1 ? EPI_MRF_DIV : EPI_MRF_ADD);
-          // xs = r0; xs += r1; x = (xs + r2)/3: only the chains' LAST convs are ordered
-          if (multi && j > 0) DISSC_HIP_CHECK(hipStreamWaitEvent(sj, g->ev_fin[j - 1], 0));
-        }
-        if ((rc = run_conv(g->rb2[idx], TMPc, XKc, xin, ACC, lengths, L, mul, B, ch, ldt, ld, L, dma2 ? 1.0f : 0.1f,
-                           epi, (float)nk, sj, 0.f, dma2 ? 1 : 0)))
-          return rc;
+        if (rc) return rc;
       }
       if (multi) DISSC_HIP_CHECK(hipEventRecord(g->ev_fin[j], sj));
     }
@@ -762,21 +818,15 @@ int dissc_conv1d(const float* x, const float* w_host, const float* bias_host, fl
     set_error("dissc_conv1d: bad argument");
     return DISSC_EINVAL;
   }
+  // "wino" / "wino8" / "wino8_r4" = 2: this entry takes the transform-domain forms too (tests)
   DevConv dc;
-  const bool use8 = opts().wino8 >= 2 && wino8_supported(Cout, Cin, k, dilation);  // "wino8" = 2: the stand-alone entry uses it (tests)
-  if (use8 || (opts().wino >= 2 && wino_supported(Cout, Cin, k, dilation))) {  // "wino" = 2: likewise for the F(4,3) form
-    const int taps = opts().wino8_r4 >= 2 && wino8_r4_supported(Cout, k, dilation) ? 4 : 3;  // "wino8_r4" = 2: F(5,4) (tests)
-    int rc = use8 ? make_wino8(w_host, bias_host, Cout, k, dilation, dc, taps) : make_wino(w_host, bias_host, Cout, k, dilation, dc);
-    if (rc) return rc;
-    rc = (use8 ? run_wino8 : run_wino)(dc, x, y, nullptr, nullptr, lengths, Lmax, 1, B, ldx, ldo, Lmax, in_slope, EPI_STORE, 1.f,
-                                       (hipStream_t)stream);
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    free_conv(dc);
-    if (rc) return rc;
-    DISSC_HIP_CHECK(e);
-    return DISSC_OK;
-  }
-  int rc = make_conv(w_host, bias_host, Cout, Cin, k, dilation, dc);
+  int rc;
+  if (opts().wino8 >= 2 && wino8_supported(Cout, Cin, k, dilation))
+    rc = make_wino8(w_host, bias_host, Cout, k, dilation, dc, opts().wino8_r4 >= 2 && wino8_r4_supported(Cout, k, dilation) ? 4 : 3);
+  else if (opts().wino >= 2 && wino_supported(Cout, Cin, k, dilation))
+    rc = make_wino(w_host, bias_host, Cout, k, dilation, dc);
+  else
+    rc = make_conv(w_host, bias_host, Cout, Cin, k, dilation, dc);
   if (rc) return rc;
   return conv_once(dc, x, y, lengths, B, ldx, ldo, Lmax, in_slope, (hipStream_t)stream);
 }
@@ -790,13 +840,11 @@ static int pair_run(int mode, const DevConv& c1, const DevConv& c2, const DevPai
   int rc;
   switch (mode) {
     case 0:
+    case 2:
       if ((rc = run_conv(c1, x, tmp, nullptr, nullptr, lengths, Lmax, 1, B, C, ld, ld, Lmax, slope, EPI_STORE, 1.f, st))) return rc;
       return run_conv(c2, tmp, y, x, acc, lengths, Lmax, 1, B, C, ld, ld, Lmax, slope, epi, mrf_div, st);
     case 1:
       return launch_respair(c1, c2, x, y, acc, lengths, Lmax, 1, B, Lmax, ld, slope, epi, mrf_div, st);
-    case 2:
-      if ((rc = run_wino(c1, x, tmp, nullptr, nullptr, lengths, Lmax, 1, B, ld, ld, Lmax, slope, EPI_STORE, 1.f, st))) return rc;
-      return run_wino(c2, tmp, y, x, acc, lengths, Lmax, 1, B, ld, ld, Lmax, slope, epi, mrf_div, st);
     case 3:
       return launch_respair_wino(pw, x, y, acc, lengths, Lmax, 1, B, Lmax, ld, slope, epi, mrf_div, st);
     default:
@@ -816,7 +864,7 @@ static int pair_make(int mode, const float* w1, const float* b1, const float* w2
     if ((rc = make_wino(w1, b1, C, k, d, c1))) return rc;
     return make_wino(w2, b2, C, k, 1, c2);
   }
-  if (mode == 3) return make_pairw(w1, b1, w2, b2, C, k, d, pw);
+  if (mode == 3) return make_pairw(w1, b1, w2, b2, C, k, d, pair_f23_wanted(C, k, d), pw);
   if ((rc = make_conv(w1, b1, C, C, k, d, c1))) return rc;
   return make_conv(w2, b2, C, C, k, 1, c2);
 }
@@ -1004,11 +1052,7 @@ int dissc_conv_bench(int B, int Cin, int Cout, int k, int dilation, int L, int e
   DISSC_HIP_CHECK(hipEventCreate(&e1));
   const int saved_cls = (flags >> 16) & 0xf;
   if (flags & 0x8000) conv_set_cfg(saved_cls, (flags >> 8) & 0x3f);
-  auto once = [&]() {
-    return w8 ? run_wino8(dc, x, y, r, a, nullptr, L, 1, B, ld, ld, L, (flags & 1) ? 1.0f : 0.1f, epi, 3.f, nullptr)
-         : wino ? run_wino(dc, x, y, r, a, nullptr, L, 1, B, ld, ld, L, (flags & 1) ? 1.0f : 0.1f, epi, 3.f, nullptr)
-                : run_conv(dc, x, y, r, a, nullptr, L, 1, B, Cin, ld, ld, L, (flags & 1) ? 1.0f : 0.1f, epi, 3.f, nullptr);
-  };
+  auto once = [&]() { return run_conv(dc, x, y, r, a, nullptr, L, 1, B, Cin, ld, ld, L, (flags & 1) ? 1.0f : 0.1f, epi, 3.f, nullptr); };
   for (int it = 0; it < 2 && !rc; ++it) rc = once();
   DISSC_HIP_CHECK(hipEventRecord(e0, nullptr));
   for (int it = 0; it < iters && !rc; ++it) rc = once();

@@ -1,4 +1,4 @@
-// Host side of the one-launch residual pairs in the Toom-Cook transform domain: which shapes take which form, packing, dispatch.
+// Host side of the one-launch residual pairs in the Toom-Cook transform domain: which shapes have an instance, packing, dispatch.
 //   form 1: the register-only F(2,3) pairs (respair_f23.hip, respair16_f23.hip) -- the default for k = 11 at C = 32 / 16;
 //   form 0: the F(4,3) pair kernel with the Y exchange through LDS (experimental/csrc/respair_wino.hip: its gate FAILED in round 4,
 //           it is in DISSC_EXPERIMENTAL=1 builds only; experimental_stubs.hip answers for it otherwise).
@@ -24,28 +24,12 @@ bool pairw_supported(int C, int KS, int dil) {
   return false;
 }
 
-// ... and the ones the generator uses it for with "pair_wino" = 1: where it measured faster than what it replaces
-// (tools/pair_gate.py, B = 32 x 10 s, one MI355X: C = 32, k = 11: 895 / 988 us against 1 042 / 1 047 for the direct fused
-// pair at d = 1 / 3, break-even at d = 5 and slower with the MRF epilogue that pair always has; C = 64, k = 3, d = 1:
-// 624 against 658 for two conv_wino launches, break-even at d = 3 / 5; C = 32, k = 7: 884-963 against 732: never).
-// The verdict's gates (C = 32, k = 11, d = 1 pair <= 720 us where the direct pair takes 921; C = 64, k = 3 pair <= 520 us)
-// were NOT met: knock-outs (tools/pair_ko.py) put a k = 11 tile at MFMAs 476 + input transforms 100 + the two A^T
-// exchanges 125 + skeleton (staging, barriers, weight loads, launch) 197 us, nothing overlapping -- one workgroup fills
-// the CU and fp32 VALU work shares the MFMA datapath.  "pair_wino" = 2 takes every supported shape (tests).
-bool pairw_wanted(int C, int KS, int dil) {
-  if (opts().pair_f23 && pair_f23_supported(C, KS, dil)) return true;  // (make_pairw then builds the register-only F(2,3) form)
-  if (!opts().pair_wino || !pairw_supported(C, KS, dil)) return false;
-  if (opts().pair_wino >= 2) return true;
-  if (C == 32) return KS == 11 && dil <= 3;
-  return C == 64 && KS == 3 && dil == 1;
-}
-
 // w: [C][C][KS] -> U[p][co][ci][j] = sum_i G[p][i] w[co][ci][j + NS i] in the order the kernel's lanes hold them:
 // [point][mi][tap j][8-channel sub-chunk][lane][k-step e] = U_p[32 mi + (lane & 31)][8 ksub + 2 e + (lane >> 5)][j]
 
-int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, DevPairW& pw) {
-  pw.form = (opts().pair_f23 && pair_f23_supported(C, KS, dil)) ? 1 : 0;
-  if (!pw.form && !pairw_supported(C, KS, dil)) {
+int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, bool f23, DevPairW& pw) {
+  pw.form = f23 ? 1 : 0;
+  if (f23 ? !pair_f23_supported(C, KS, dil) : !pairw_supported(C, KS, dil)) {
     set_error("make_pairw: no instance for C = %d, k = %d, dilation %d", C, KS, dil);
     return DISSC_EINVAL;
   }

@@ -344,12 +344,6 @@ static inline float bf16_to_f32_host(uint16_t h) {
 
 // option "fused_variant" (Options::bf3_variant, default 0): "fused_variant" in precision mode: 0 = 512-column window, 1 = 1024
 
-// option "bf3_pairs" (Options::bf3_pairs, default -1): "bf3_pairs": -1 = by channel count (below), 0 = whole blocks, 1 = always pairs
-// One launch per residual pair instead of per block?  With 64 channels the LDS holds 256-column
-// windows only, and the 120-column halo of a whole 11-tap block would be recomputed ~2x; a pair's
-// halo is 10-30 columns, at the price of two more read+write passes of x_k per block.
-bool resblock_bf3_pairs(int C) { return opts().bf3_pairs < 0 ? C >= 64 : opts().bf3_pairs != 0; }
-
 bool resblock_bf3_supported(int C, int KS, const int* dil) {
   if (C != 16 && C != 32 && C != 64) return false;
   // (C = 64 leaves room for 256-column windows only; with 11 taps the halo is 120 of them and the

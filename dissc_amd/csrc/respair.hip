@@ -461,10 +461,8 @@ static int launch_pair16(const PairArgs& a, int B, int Lmax, hipStream_t stream)
 
 // option "pair_lds" (Options::pair_lds_mode, default 1): "pair_lds" option: LDS layout of respair32 (see LM)
 // option "pair_pad_lds" (Options::pair_pad_lds, default 0): diagnostics: extra dynamic LDS bytes per workgroup (lowers occupancy)
-// option "pair_max_c" (Options::pair_max_c, default 32): "pair_max_c" option: widest stage run as fused residual pairs (0 = off)
 
 bool respair_supported(int C, int KS, int dil) {
-  if (C > opts().pair_max_c) return false;
   if (C != 16 && C != 32) return false;
   return (KS == 3 || KS == 7 || KS == 11) && (dil == 1 || dil == 3 || dil == 5);
 }

@@ -25,11 +25,6 @@
 
 namespace dissc {
 
-// option "pair_f23" (Options::pair_f23, default 3): "pair_f23" option (read at dissc_gen_create), a bit mask: 1 = the C = 32, k = 11 pairs run on this kernel -- per launch
-                     // 857 / 894 / 924 us at d = 1 / 3 / 5 against 1 042 / 1 037 / 1 052 for the direct pair (B = 32 x 10 s) --, 2 = the
-                     // C = 16, k = 11 pairs on respair16_f23.hip (525 against 604 us at d = 1); default both.  4 / 8 = the k = 3 pairs of
-                     // the two stages (C = 32: 365 against 417 us, C = 16: 262 against 263; forward 33.11 -> 33.09 ms: off)
-
 template <int KS_, int DIL>
 struct F23Geo {
   static constexpr int KS = KS_, NS = (KS_ + 2) / 3, C = 32, NW = 4;
@@ -280,12 +275,10 @@ __global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairFArgs a
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// "pair_f23" is a bit mask: 1 = the 32-channel stage (this file), 2 = the 16-channel stage (respair16_f23.hip)
-// (bits 2 / 3: the k = 3 pairs of the two stages -- one sub-filter, 2 products per output instead of 3)
+// the 32-channel stage (this file) and the 16-channel one (respair16_f23.hip); k = 3 (one sub-filter, 2 products per output
+// instead of 3) in DISSC_EXPERIMENTAL=1 builds only
 bool pair_f23_supported(int C, int KS, int dil) {
-  if (!((KS == 11 || (KS == 3 && DISSC_EXPERIMENTAL)) && (dil == 1 || dil == 3 || dil == 5))) return false;
-  const int sh = KS == 3 ? 2 : 0;
-  return (C == 32 && (opts().pair_f23 & (1 << sh))) || (C == 16 && (opts().pair_f23 & (2 << sh)));
+  return (C == 16 || C == 32) && (KS == 11 || (KS == 3 && DISSC_EXPERIMENTAL)) && (dil == 1 || dil == 3 || dil == 5);
 }
 
 // w: [32][32][11] -> U_p[co][ci][j] = sum_i G[p][i] w[co][ci][j + 4 i] in A-fragment order [chunk][sub-filter][point][half][lane][4]

@@ -33,12 +33,6 @@
 
 namespace dissc {
 
-// option "pair_wino" (Options::pair_wino, default 0): "pair_wino" option (read at dissc_gen_create): 0 (default) = not used (respair32 direct / two conv_wino
-                      // launches); 1 = the shapes pairw_wanted() names run as fused transform-domain pairs, 2 = every shape
-                      // with an instance.  Off by default: the gate experiment failed (below) -- per launch the winning
-                      // shapes are 6-15 % faster, in the whole forward (three chains overlapping on their streams) that
-                      // is 35.36 against 35.42 ms, while the executed-FLOP utilisation falls from 0.619 to 0.602.
-
 struct PairWArgs {
   const float* x;     // [B][C][ld] pair input x_k
   float* out;         // EPI_RES: x_k' (may not alias x: neighbouring workgroups still read x's halo)

@@ -146,9 +146,8 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  * Options marked [experimental] select kernels whose gates failed; they are only in libraries built with
  * DISSC_EXPERIMENTAL=1 (dissc_get_option("experimental") == 1) and are refused or ignored otherwise.
  *   multistream (1)      generator: the ResBlocks of a stage run as concurrent chains on HIP streams (two side
- *                        streams per device, shared by all generator handles of the process)
- *   stream_prio (1)      ... and the longer chains get higher HIP stream priority
- *   par_ups (1)          ... and the phase groups of a ConvTranspose layer run concurrently on the same streams
+ *                        streams per device, shared by all generator handles of the process; the longer chains at higher
+ *                        stream priority, the phase groups of a ConvTranspose layer concurrently on the same streams)
  *   precision (0)        0 = exact fp32 MFMA everywhere (default, bench.py's headline); 1 = split-bf16 GENERATOR
  *                        ("bf16x3": hi*hi + hi*lo + lo*hi on the bf16 matrix cores, fp32 accumulate; conv_bf3.hip,
  *                        resblock_bf3.hip) -- ~2^-17 product error, waveform RMS ~4e-6 vs the reference (bar 1e-4),
@@ -157,8 +156,10 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *   conv_cfg_bm{16,32,64,128,256} / conv32_cfg_bm{32,64,128,256}
  *                        tile-shape id per GEMM-M class (tables in conv_mfma.hip / conv_mfma32.hip)
  *   small_grid (1)       launches with fewer than value x 256 workgroups step down to smaller conv tiles (0 = never)
- *   lin_tile (2)         1x1 convs: 16-channel chunks staged per barrier (2 or 4)
- *   cpb2 (0)             k <= value convs stage 32 channels per barrier
+ *   lin128 (1)           HuBERT's linears on lin_gemm.hip's 256 x 128 tiles (0: conv_mfma32_kernel's 256 x 64 instances)
+ *   conv2s128 (1)        HuBERT's stride-2, k = 3 feature convs on lin_gemm.hip's tiles (0: conv_mfma32_kernel; 2: 32 channels
+ *                        per barrier)
+ *   kernel_dbg (0)       diagnostics only: knock-outs inside the kernels (bit meanings in their sources); wrong results when set
  *   pair_max_c (32)      widest fp32 stage whose residual pairs (conv_d -> conv_1 -> +x) run as ONE launch each
  *                        (respair.hip; 0 = every conv its own launch; results are bit-identical either way)
  *   pair_f23 (3)         read at dissc_gen_create, a bit mask: 1 = the k = 11 residual pairs of the 32-channel stage, 2 = those of the
@@ -166,6 +167,8 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *                        output instead of 11, no LDS exchange; forward 1.5 % faster; not bit-identical to the direct pairs, error no
  *                        larger); 4 / 8 = their k = 3 pairs too (2 products per output instead of 3: per launch -12 % at C = 32, 0 at
  *                        C = 16, nothing in the forward -- off); 0 = the direct pairs of respair.hip
+ *   pair_dma (1)         read at dissc_gen_create: the two-launch direct residual pairs of the >= 32-channel stages hand their
+ *                        intermediate over activated with zero tails, and the second conv stages its windows by LDS-DMA
  *   wino8 (1)            read at dissc_gen_create: 1 = the ResBlock convs selected by wino8_mask run on conv_wino8.hip's
  *                        8-wave workgroups (eight Toom-Cook points: F(6,3), 8 ceil(k / 3) / 6 products per output, or F(5,4) with
  *                        4-tap sub-filters, 8 ceil(k / 4) / 5 -- forward 4 % faster than with F(4,3) everywhere, per-layer rounding
@@ -181,10 +184,9 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *                        the first pair of the C = 64, k = 3 chain) run as ONE launch with both convs in the Toom-Cook
  *                        transform domain and the intermediate in LDS (respair_wino.hip); 2 = every shape with an instance
  *                        (C = 32: k = 7 / 11; C = 64: k = 3, first pair of a chain); 0 = none
- *   pairw_chv (2)        respair_wino.hip: 2 = one 12-wave workgroup per CU, 1 = two 6-wave workgroups with half the tile
- *   bf3_pairs (-1)       split-bf16 fused ResBlocks as three launches of one residual pair each: -1 = for >= 64
- *                        channels only, 0 = never, 1 = always
- *   fused_variant (0)    split-bf16 fused ResBlocks: 0 = 512-column windows, 1 = 1024
+ *   pairw_chv (2)        [experimental] respair_wino.hip: 2 = one 12-wave workgroup per CU, 1 = two 6-wave workgroups with half the tile
+ *   graphs (0)           [experimental] generator forwards of B * Tmax <= graph_frames (2048) are captured once into a hipGraph
+ *                        and replayed (off: slower than the plain three-stream launches on ROCm 7.2)
  *   wino (1)             read at dissc_gen_create: 1 = ResBlock convs with C >= wino_min_c (64; at C = 64 those with k >=
  *                        wino_c64_kmin = 3) run in the Toom-Cook F(4,3) transform domain (conv_wino.hip), 0 = all direct,
  *                        2 = dissc_conv1d uses it too (tests)
@@ -194,11 +196,9 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *                        Toom-Cook form (conv_s2tc.hip: 15 / 7 instead of 3 MFMA products per output; opt-in: its gate failed --
  *                        6 % faster per launch, 2.35x the direct form's rounding error); 0 = direct implicit GEMM (default).
  *                        s2tc_xmode (0): 0 = row tiles pinned to XCDs, 1 = the row tiles of a time tile share an XCD
- *   attn_fused (1)       HuBERT attention as one fused kernel (0: batched GEMM -> softmax -> batched GEMM)
  *   hubert_split (1)     dissc_hubert_forward runs a batch of >= 16 utterances as 2-4 parts on streams of their own, which
  *                        fill the partly filled last workgroup rounds of each other's launches (0 never, 1 unless the
  *                        whole batch fills whole rounds by itself, N >= 2 always N parts); the units do not depend on it
- *   mfast (0)            M-fastest block order for convs with many M tiles
  *   xcd_order (11)       XCD-aware workgroup order of the 32x32x2 implicit-GEMM launches with >= 2 M tiles (bit 0: 1x1 convs =
  *                        HuBERT's linears, bit 1: stride-2 convs = its feature extractor, bit 2: every other instance): a 1-D
  *                        grid whose ids are dealt in sweeps over groups of M tiles (weight slabs that fit one XCD's L2 together),
