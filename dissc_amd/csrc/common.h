@@ -42,7 +42,7 @@ void set_error(const char* fmt, ...);
   X(kernel_dbg, 0, "kernel_dbg") \
   X(wino_sv, 1, "wino_sv") \
   X(wino8_c64_wide, 3, "wino8_c64_wide") \
-  X(wino8_mask, 0770770771, "wino8_mask") \
+  X(wino8_mask, 0450770550, "wino8_mask") \
   X(wino8_r4_mask, 0770770010, "wino8_r4_mask") \
   X(wino8_r4, 1, "wino8_r4") \
   X(wino8, 1, "wino8") \

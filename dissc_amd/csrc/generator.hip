@@ -96,11 +96,13 @@ static bool wino_wanted(int C, int KS) {
 //   of the 36 (C, k, d, epilogue) shapes of the generator (tools/wino8_gate.py), 4-9 % slower on the d = 1 shapes of the
 //   128-channel stage (864 workgroups = 3.4 rounds of 256 CUs where the F(4,3) tiles make exactly 5.0): the default mask leaves
 //   that stage alone.  Whole forward 35.17 / 35.27 -> 34.84 / 34.91 ms, in-run parity rms 5.5e-7 -> 6.5e-7.
-// option "wino8_mask" (Options::wino8_mask, default 0770770771): one bit per SHAPE, from per-launch measurements and same-box
+// option "wino8_mask" (Options::wino8_mask, default 0450770550): one bit per SHAPE, from per-launch measurements and same-box
 //   forward A/Bs (tools/opt_ab.sh): bit 9 cls + 3 ki + di with cls = 0 / 1 / 2 for C = 64 / 128 / >= 256, ki = 0 / 1 / 2 for
 //   k = 3 / 7 / 11, di = 0 / 1 / 2 for dilation 1 / 3 / 5 -- in octal three digits per class (k = 11, k = 7, k = 3 from the left),
-//   each digit = the dilations d5 d3 d1.  Default: every k = 7 / 11 shape, and k = 3, d = 1 at C = 64 (F(6,3) on the two-per-CU
-//   tiles: forward 33.47 -> 33.16 ms; the other k = 3 shapes measured neutral).
+//   each digit = the dilations d5 d3 d1.  Speed alone picked every k = 7 / 11 shape and k = 3, d = 1 at C = 64 (0770770771);
+//   on trained-like weights and inputs (tests/test_gpu_trained_like.py, profiles/trained_like_error.md) seven of those shapes
+//   rounded above 3x the direct kernel's rms error in their eight-point form and stay on F(4,3): C >= 256 k = 7 d = 3 and
+//   k = 11 d = 1 / 3 (F(5,4)), C = 64 k = 3 d = 1, k = 7 d = 3 and k = 11 d = 3 (F(6,3)).
 // option "wino8_r4" (Options::wino8_r4, default 1): 1 = the shapes "wino8_r4_mask" (same layout, k = 3 bits ignored; default every
 //   k = 7 / 11 shape of the C >= 128 stages and k = 7, d = 1 at C = 64) run as F(5,4) instead of F(6,3); 2 = dissc_conv1d too
 //   (tests); 0 = never

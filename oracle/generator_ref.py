@@ -11,6 +11,8 @@ Follows, function by function:
   embed_concat          <- CodeGenerator.forward, reference sr/models.py:179-215
   generator_forward     <- Generator.forward, reference sr/models.py:98-114
   resblock1             <- ResBlock1.forward, reference sr/models.py:34-41
+  to_double             <- (none) folded weights cast to float64: code_generator / generator_forward then run in
+                           float64, so a comparison against them measures arithmetic error only, not folding
   wav_postprocess       <- generate()/inference(), reference
                            sr/inference.py:73-75,205-206
 """
@@ -47,6 +49,11 @@ def fold_state_dict(sd):
     return out
 
 
+def to_double(folded):
+    """fold_state_dict's fp32 tensors cast to float64 (the fold itself stays fp32, exactly as the reference's)"""
+    return {k: (v.double() if v.is_floating_point() else v) for k, v in folded.items()}
+
+
 def get_padding(kernel_size, dilation=1):
     # reference sr/utils.py:44-45
     return int((kernel_size * dilation - dilation) / 2)
@@ -72,27 +79,36 @@ def embed_concat(w, code, f0, spkr):
     elif f0.shape[-1] != x.shape[-1]:
         f0 = upsample(f0, x.shape[-1])
     T = x.shape[-1]
-    x = torch.cat([x, f0], dim=1)
+    x = torch.cat([x, f0.to(x.dtype)], dim=1)
     s = F.embedding(spkr, w["spkr.weight"]).transpose(1, 2)  # [1,128,1]
     x = torch.cat([x, s.expand(-1, -1, T)], dim=1)
     return x
 
 
-def resblock1(w, prefix, x, k, dilations=(1, 3, 5)):
+def resblock1(w, prefix, x, k, dilations=(1, 3, 5), conv_taps=None):
+    """``conv_taps`` (dict) receives the input of every conv after its leaky ReLU as "<prefix>.convs{1,2}.<m>" and the
+    pre-activation value as "<prefix>.convs{1,2}.<m>.x" (for convs1.<m>: the residual stream entering pair m)."""
     for m, d in enumerate(dilations):
         xt = F.leaky_relu(x, LRELU_SLOPE)
+        if conv_taps is not None:
+            conv_taps[f"{prefix}.convs1.{m}.x"], conv_taps[f"{prefix}.convs1.{m}"] = x, xt
         xt = F.conv1d(xt, w[f"{prefix}.convs1.{m}.weight"], w[f"{prefix}.convs1.{m}.bias"],
                       padding=get_padding(k, d), dilation=d)
+        if conv_taps is not None:
+            conv_taps[f"{prefix}.convs2.{m}.x"] = xt
         xt = F.leaky_relu(xt, LRELU_SLOPE)
+        if conv_taps is not None:
+            conv_taps[f"{prefix}.convs2.{m}"] = xt
         xt = F.conv1d(xt, w[f"{prefix}.convs2.{m}.weight"], w[f"{prefix}.convs2.{m}.bias"],
                       padding=get_padding(k, 1))
         x = xt + x
     return x
 
 
-def generator_forward(w, h, x, taps=None):
+def generator_forward(w, h, x, taps=None, conv_taps=None, pre_tanh=None):
     """x [1,in_dim,T] -> wav [1,1,T*prod(upsample_rates)].  ``taps`` (dict)
-    receives the per-stage activations when given."""
+    receives the per-stage activations when given, ``conv_taps`` the ResBlock
+    conv inputs (resblock1), ``pre_tanh`` (dict) the conv_post output as "y"."""
     nk = len(h["resblock_kernel_sizes"])
     x = F.conv1d(x, w["conv_pre.weight"], w["conv_pre.bias"], padding=3)
     if taps is not None:
@@ -105,33 +121,37 @@ def generator_forward(w, h, x, taps=None):
             taps[f"up{i}"] = x
         xs = None
         for j, (rk, rd) in enumerate(zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])):
-            r = resblock1(w, f"resblocks.{i * nk + j}", x, rk, tuple(rd))
+            r = resblock1(w, f"resblocks.{i * nk + j}", x, rk, tuple(rd), conv_taps)
             xs = r if xs is None else xs + r
         x = xs / nk
         if taps is not None:
             taps[f"mrf{i}"] = x
     x = F.leaky_relu(x)  # default slope 0.01 (reference sr/models.py:110)
     x = F.conv1d(x, w["conv_post.weight"], w["conv_post.bias"], padding=3)
+    if pre_tanh is not None:
+        pre_tanh["y"] = x
     return torch.tanh(x)
 
 
 @torch.no_grad()
-def code_generator(w, h, code, f0, spkr, lengths=None, taps=None):
+def code_generator(w, h, code, f0, spkr, lengths=None, taps=None, conv_taps=None):
     """Batched front end with the reference's semantics: every utterance is run
     alone at its true length (the reference never batches), outputs are right
-    padded with zeros.  code [B,T] i64, f0 [B,1,T], spkr [B,1] -> [B,1,hop*T]."""
+    padded with zeros.  code [B,T] i64, f0 [B,1,T], spkr [B,1] -> [B,1,hop*T].
+    Runs in the dtype of the weights (fp32: fold_state_dict; float64: to_double);
+    the output follows it.  ``taps`` / ``conv_taps``: of utterance 0."""
     code = torch.as_tensor(code)
     f0 = torch.as_tensor(f0)
     spkr = torch.as_tensor(spkr)
     B, T = code.shape
     hop = int(np.prod(h["upsample_rates"]))
-    out = torch.zeros(B, 1, hop * T)
+    out = torch.zeros(B, 1, hop * T, dtype=w["conv_pre.weight"].dtype)
     for b in range(B):
         n = T if lengths is None else int(lengths[b])
         if n == 0:
             continue
         x = embed_concat(w, code[b:b + 1, :n], f0[b:b + 1, :, :n], spkr[b:b + 1])
-        y = generator_forward(w, h, x, taps if (taps is not None and b == 0) else None)
+        y = generator_forward(w, h, x, taps if b == 0 else None, conv_taps if b == 0 else None)
         out[b, :, : hop * n] = y[0]
     return out
 

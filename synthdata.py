@@ -56,8 +56,51 @@ def _wn_conv(rs, sd, name, shape, fan_in, gain, g_dim0):
     sd[name + ".weight_v"] = _t(v)
 
 
-def synth_generator_state_dict(h=None, seed=0):
-    """State dict with the reference's 293 keys."""
+# kind="trained_like": heavy-tailed statistics in the spirit of trained HiFi-GAN checkpoints (frozen; tuned until the checks of
+# tests/test_trained_like_cpu.py hold): per-channel gains log-normal with sigma TL_GAIN_SIGMA (~40 dB of spread) and TL_OUTLIERS
+# (2-4) channels per layer at TL_OUTLIER_GAIN x, renormalised so the layer's RMS gain is the iid value; directions Student-t with
+# TL_T_DOF degrees of freedom; biases TL_BIAS_STD * N(0,1); TL_MASSIVE_DIMS embedding dimensions at TL_MASSIVE_SCALE x; conv_post
+# at RMS gain TL_POST_GAIN (iid: 0.35) so the waveform stays off tanh saturation (pre-tanh RMS 0.24 / 0.36 at T = 99 / 33).
+TL_GAIN_SIGMA = 1.2
+TL_OUTLIERS = (2, 4)
+TL_OUTLIER_GAIN = 30.0
+TL_T_DOF = 3.0
+TL_BIAS_STD = 0.3
+TL_MASSIVE_DIMS = 3
+TL_MASSIVE_SCALE = 10.0
+TL_POST_GAIN = 0.12
+
+
+def _wn_conv_trained_like(rs, sd, name, shape, fan_in, gain, g_dim0):
+    """weight_v ~ Student-t(TL_T_DOF); weight_g = a per-channel gain (log-normal x outliers), RMS-renormalised to
+    gain / sqrt(fan_in) * sqrt(numel / g_dim0) (the iid layer's RMS)."""
+    v = rs.standard_t(TL_T_DOF, size=shape)
+    per = np.sqrt(np.prod(shape[1:]))
+    c = np.exp(TL_GAIN_SIGMA * rs.standard_normal(shape[0]))
+    if shape[0] >= 16:
+        n_out = rs.randint(TL_OUTLIERS[0], TL_OUTLIERS[1] + 1)
+        c[rs.choice(shape[0], n_out, replace=False)] = TL_OUTLIER_GAIN * np.median(c)
+    c /= np.sqrt(np.mean(c ** 2))
+    g = (gain / np.sqrt(fan_in)) * per * c
+    sd[name + ".weight_g"] = _t(g.reshape((shape[0],) + (1,) * (len(shape) - 1)))
+    sd[name + ".weight_v"] = _t(v)
+
+
+def _embedding_trained_like(rs, n, dim):
+    e = rs.standard_normal((n, dim))
+    e[:, rs.choice(dim, TL_MASSIVE_DIMS, replace=False)] *= TL_MASSIVE_SCALE
+    return e
+
+
+def synth_generator_state_dict(h=None, seed=0, kind="iid"):
+    """State dict with the reference's 293 keys.
+
+    kind "iid": N(0,1) directions, per-channel gains N(1, 0.1), biases 0.1 N(0,1) (every existing fixture);
+    "trained_like": the heavy-tailed statistics above (same keys, layouts and per-layer RMS gains)."""
+    if kind == "trained_like":
+        return _synth_generator_state_dict_trained_like(h, seed)
+    if kind != "iid":
+        raise ValueError(f"kind {kind!r}: 'iid' or 'trained_like'")
     h = h or VCTK_CONFIG
     rs = np.random.RandomState(seed)
     sd = OrderedDict()
@@ -90,9 +133,57 @@ def synth_generator_state_dict(h=None, seed=0):
     return sd
 
 
-def synth_generator_inputs(B, T, seed=1234, ragged=False, n_spk=108, n_codes=100):
+def _synth_generator_state_dict_trained_like(h, seed):
+    h = h or VCTK_CONFIG
+    rs = np.random.RandomState(seed)
+    sd = OrderedDict()
+    c0 = h["upsample_initial_channel"]
+    in_dim = h.get("model_in_dim", 128)
+    sd["conv_pre.bias"] = _t(TL_BIAS_STD * rs.standard_normal(c0))
+    _wn_conv_trained_like(rs, sd, "conv_pre", (c0, in_dim, 7), in_dim * 7, 1.0, c0)
+    for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
+        cin, cout = c0 // 2 ** i, c0 // 2 ** (i + 1)
+        sd[f"ups.{i}.bias"] = _t(TL_BIAS_STD * rs.standard_normal(cout))
+        _wn_conv_trained_like(rs, sd, f"ups.{i}", (cin, cout, k), cin * k / u, 1.4, cin)
+    nk = len(h["resblock_kernel_sizes"])
+    for i in range(len(h["upsample_rates"])):
+        ch = c0 // 2 ** (i + 1)
+        for j, k in enumerate(h["resblock_kernel_sizes"]):
+            idx = i * nk + j
+            for grp, gain in (("convs1", 1.4), ("convs2", 0.6)):
+                for m in range(3):
+                    name = f"resblocks.{idx}.{grp}.{m}"
+                    sd[name + ".bias"] = _t(TL_BIAS_STD * rs.standard_normal(ch))
+                    _wn_conv_trained_like(rs, sd, name, (ch, ch, k), ch * k, gain, ch)
+    ch = c0 // 2 ** len(h["upsample_rates"])
+    sd["conv_post.bias"] = _t(0.05 * rs.standard_normal(1))
+    _wn_conv_trained_like(rs, sd, "conv_post", (1, ch, 7), ch * 7, TL_POST_GAIN, 1)
+    sd["dict.weight"] = _t(_embedding_trained_like(rs, h["num_embeddings"], h["embedding_dim"]))
+    sd["spkr.weight"] = _t(_embedding_trained_like(rs, 200, h["embedding_dim"]))
+    return sd
+
+
+# kind="trained_like" inputs (frozen, as above): f0 z-scores with TL_F0_PEAKS frames per utterance pushed to |6|, unvoiced runs of
+# mean TL_UNVOICED_RUN frames (TL_UNVOICED_P of the runs), code runs of mean TL_CODE_RUN frames, and leading / trailing silence
+# (code TL_SILENCE_CODE, f0 exactly 0) over TL_SILENCE_FRAC of the frames at each end.
+TL_F0_PEAKS = 2
+TL_UNVOICED_RUN = 25.0
+TL_UNVOICED_P = 0.4
+TL_CODE_RUN = 8.0
+TL_SILENCE_CODE = 0
+TL_SILENCE_FRAC = 0.15
+
+
+def synth_generator_inputs(B, T, seed=1234, ragged=False, n_spk=108, n_codes=100, kind="iid"):
     """runs of a uniform symbol (geometric, mean 2.5 frames),
-    f0 ~ N(0,1) with ~35% exact-zero unvoiced runs, spkr uniform."""
+    f0 ~ N(0,1) with ~35% exact-zero unvoiced runs, spkr uniform.
+
+    kind "trained_like": the harsher inputs above (long code runs, long exact-zero unvoiced runs, f0 peaks at |6|, silence at
+    both ends of every utterance)."""
+    if kind == "trained_like":
+        return _synth_generator_inputs_trained_like(B, T, seed, ragged, n_spk, n_codes)
+    if kind != "iid":
+        raise ValueError(f"kind {kind!r}: 'iid' or 'trained_like'")
     rs = np.random.RandomState(seed)
     code = np.zeros((B, T), dtype=np.int64)
     f0 = np.zeros((B, 1, T), dtype=np.float32)
@@ -115,6 +206,39 @@ def synth_generator_inputs(B, T, seed=1234, ragged=False, n_spk=108, n_codes=100
         lengths[0] = T
     else:
         lengths = np.full(B, T, dtype=np.int32)
+    return code, f0, spkr, lengths
+
+
+def _synth_generator_inputs_trained_like(B, T, seed, ragged, n_spk, n_codes):
+    rs = np.random.RandomState(seed)
+    code = np.zeros((B, T), dtype=np.int64)
+    f0 = np.zeros((B, 1, T), dtype=np.float32)
+    lengths = np.full(B, T, dtype=np.int32)
+    if ragged:
+        lengths = rs.randint(max(1, T // 2), T + 1, size=B).astype(np.int32)
+        lengths[0] = T
+    for b in range(B):
+        n = int(lengths[b])
+        t = 0
+        while t < T:
+            run = rs.geometric(1 / TL_CODE_RUN)
+            code[b, t:t + run] = rs.randint(0, n_codes)
+            t += run
+        f0[b, 0] = rs.standard_normal(T)
+        t = 0
+        while t < T:
+            run = rs.geometric(1 / TL_UNVOICED_RUN)
+            if rs.rand() < TL_UNVOICED_P:
+                f0[b, 0, t:t + run] = 0.0
+            t += run
+        s = int(round(TL_SILENCE_FRAC * n))  # silence at both ends of the utterance's own length
+        peaks = rs.randint(s, max(s + 1, n - s), size=TL_F0_PEAKS)  # inside the voiced part
+        f0[b, 0, peaks] = 6.0 * rs.choice([-1.0, 1.0], size=TL_F0_PEAKS)
+        if s > 0:
+            for sl in (slice(0, s), slice(n - s, n)):
+                code[b, sl] = TL_SILENCE_CODE
+                f0[b, 0, sl] = 0.0
+    spkr = rs.randint(0, n_spk, size=(B, 1)).astype(np.int64)
     return code, f0, spkr, lengths
 
 

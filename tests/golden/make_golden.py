@@ -96,6 +96,33 @@ def make_generator():
     print("gen_vctk.npz", len(out), "arrays")
 
 
+def make_generator_trained_like():
+    """synthdata's kind="trained_like" checkpoint (seed 0) in the reference CodeGenerator -> gen_vctk_trainedlike.npz: the waveforms
+    of trained-like inputs at T = 33 / 99 (seeds 100 + T, as make_generator's), fp32, and again with the folded module cast to
+    float64 (.double() after remove_weight_norm: the fold stays fp32, as oracle.generator_ref.to_double does).  Outputs only: the
+    weights and inputs come from the seeds."""
+    ref_models, ref_utils = _import_ref_sr()
+    h = ref_utils.AttrDict(json.load(open(os.path.join(REF, "sr/configs/VCTK/hubert100_lut.json"))))
+    g = ref_models.CodeGenerator(h)
+    g.load_state_dict(synth.synth_generator_state_dict(seed=0, kind="trained_like"), strict=True)
+    g.eval()
+    g.remove_weight_norm()
+    out = {}
+    for T in (33, 99):
+        code, f0, spkr, _ = synth.synth_generator_inputs(1, T, seed=100 + T, kind="trained_like")
+        with torch.no_grad():
+            out[f"T{T}/wav"] = g(code=torch.from_numpy(code), f0=torch.from_numpy(f0), spkr=torch.from_numpy(spkr)).numpy()
+    g.double()
+    for T in (33, 99):
+        code, f0, spkr, _ = synth.synth_generator_inputs(1, T, seed=100 + T, kind="trained_like")
+        with torch.no_grad():
+            y = g(code=torch.from_numpy(code), f0=torch.from_numpy(f0).double(), spkr=torch.from_numpy(spkr))
+        assert y.dtype == torch.float64
+        out[f"T{T}/wav64"] = y.numpy()
+    np.savez_compressed(os.path.join(OUT, "gen_vctk_trainedlike.npz"), **out)
+    print("gen_vctk_trainedlike.npz", {k: v.dtype.name for k, v in out.items()})
+
+
 def _import_ref_root():
     """reference infer.py imports root utils.py -> `from tensorflow import summary`
     (reference utils.py:2); tensorflow is not installed, a stub module is enough."""
@@ -662,7 +689,7 @@ def make_upsample():
 
 
 TARGETS = {"upsample": make_upsample, "train": make_train, "prep_dataset": make_prep_dataset, "hubert": make_hubert, "sr_inference": make_sr_inference,
-           "generator": make_generator, "predictors": make_predictors}
+           "generator": make_generator, "generator_trained_like": make_generator_trained_like, "predictors": make_predictors}
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(TARGETS)

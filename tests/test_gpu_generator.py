@@ -410,9 +410,10 @@ def test_precision_option_leaves_predictors_and_units_exact():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
-def _generator_with(lib, synth, **options):
+def _generator_with(lib, synth, state_dict=None, precision=None, **options):
     """an instance whose native handle is CREATED under the given options (a handle snapshots the options when it is created and
-    never looks at the process-wide defaults again: include/dissc_hip.h); the defaults are restored afterwards"""
+    never looks at the process-wide defaults again: include/dissc_hip.h); the defaults are restored afterwards.  state_dict:
+    the checkpoint to load (default: synth_generator_state_dict(seed=0))"""
     import dissc_amd
     saved = {}
     try:
@@ -421,8 +422,8 @@ def _generator_with(lib, synth, **options):
             assert lib.dissc_get_option(k.encode(), ctypes.byref(cur)) == 0, k
             saved[k] = cur.value
             assert lib.dissc_set_option(k.encode(), v) == 0
-        gd = dissc_amd.CodeGenerator(synth.VCTK_CONFIG).to("cuda:0")
-        gd.load_state_dict(synth.synth_generator_state_dict(seed=0))
+        gd = dissc_amd.CodeGenerator(synth.VCTK_CONFIG, precision=precision).to("cuda:0")
+        gd.load_state_dict(synth.synth_generator_state_dict(seed=0) if state_dict is None else state_dict)
         gd.eval().remove_weight_norm()
         c1, f1, s1, _ = synth.synth_generator_inputs(1, 3, seed=1)
         gd(code=torch.from_numpy(c1), f0=torch.from_numpy(f1), spkr=torch.from_numpy(s1))  # the native handle is built here

@@ -1,0 +1,516 @@
+"""Generator parity on trained-like weights and inputs (synthdata kind="trained_like": per-channel gains over decades, outlier
+channels, Student-t directions, f0 peaks, exact silence next to loud onsets).  The rounding error of a Toom-Cook form scales with
+the largest value of a tile after its input transform and spreads over the whole tile, so the bars measured on benign data are
+re-checked here, per layer and on the whole generator, against the float64 oracle (oracle.generator_ref.to_double).
+
+Per layer (every ResBlock conv / residual pair of the VCTK config, through every form with an instance for its shape):
+  e_rms  RMS error over the valid outputs against a float64 conv of the same fp32 weights and inputs
+  e_ch   the worst output channel's RMS error over that channel's reference RMS (floor: 1e-3 of the layer's RMS)
+  leak   on the adversarial rows, the largest |error| at outputs whose receptive field holds no loud sample, in units of
+         (loud level x sum|w| x 2^-24): a wrong tile or halo gives ~2^24, which no averaging hides
+Inputs: (a) the float64 oracle's tap of the layer on a trained-like T = 99 utterance; (b) rows built from the tap's own channel
+statistics: bursts after exact silence with their edges at every offset modulo the forms' tile widths (x dilation), isolated
+spikes at 100x the channel RMS, ragged lengths (1, tile +- 1, the kernels' work tiles +- 1, long); NaN beyond every length.
+Run with -s for one line per (layer, form)."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import is_experimental_build
+from test_gpu_generator import FP32_GUARD_RMS, NORTH_STAR_RMS, _generator_with, _rms, _run_conv
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+U = 2.0 ** -24
+SLOPE = 0.1
+STAGES = (256, 128, 64, 32, 16)
+KS = (3, 7, 11)
+DILS = (1, 3, 5)
+BURST_STEP = 211  # burst starts advance by a prime: their residues cover every tile width x dilation (widths 2..6, d 1..5)
+BURST_LEN = 37
+
+# bars: ceilings, tightened to ~2x of the measured worst case where that is below them (profiles/trained_like_error.md)
+DIRECT_VS_CPU = 4.0    # direct GPU kernel e_rms <= this x CPU fp32 F.conv1d's (measured <= 2.96 over (a) + (b))
+TD_RMS = 3.0           # the plan's transform-domain e_rms <= this x the direct GPU kernel's, same input (measured <= 2.98)
+TD_CH = 10.0           # transform-domain e_ch <= this x the direct GPU kernel's (measured <= 5.03)
+LEAK = 4.0             # transform-domain leak <= this (ceiling 64; measured <= 1.79, a wrong tile or halo: ~1e5)
+GUARD_FACTOR = 3.0     # fp32 guard: error vs float64 <= max(FP32_GUARD_RMS, this x the fp32 oracle's own)
+
+
+@pytest.fixture(scope="module")
+def tl():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from dissc_amd import _lib
+    from oracle import generator_ref as gr
+    import synthdata as synth
+    sd = synth.synth_generator_state_dict(seed=0, kind="trained_like")
+    folded = gr.fold_state_dict(sd)
+    w64 = gr.to_double(folded)
+    code, f0, spkr, _ = synth.synth_generator_inputs(1, 99, seed=199, kind="trained_like")
+    x = gr.embed_concat(w64, torch.from_numpy(code), torch.from_numpy(f0), torch.from_numpy(spkr))
+    taps, conv_taps = {}, {}
+    gr.generator_forward(w64, synth.VCTK_CONFIG, x, taps=taps, conv_taps=conv_taps)
+    # the pre-activation inputs (the kernels apply the leaky ReLU on load), as the fp32 data a kernel is fed
+    inp = {k[:-2]: v[0].float() for k, v in conv_taps.items() if k.endswith(".x")}
+    inp["conv_pre"] = x[0].float()
+    for i in range(5):
+        inp[f"ups.{i}"] = (taps["conv_pre"] if i == 0 else taps[f"mrf{i - 1}"])[0].float()
+    return dict(lib=_lib.lib, _lib=_lib, gr=gr, synth=synth, sd=sd, folded=folded, inp=inp, experimental=is_experimental_build())
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# inputs (b) and metrics
+# ------------------------------------------------------------------------------------------------------------------------
+def _adversarial_rows(tap, tiles, seed):
+    """tap [C, n] fp32 -> list of (row [C, len] fp32, loud mask [len] bool or None); tiles: the tile widths x dilation in use"""
+    rs = np.random.RandomState(seed)
+    C, n = tap.shape
+    ch_rms = tap.double().pow(2).mean(1).sqrt().float()
+    rows = []
+    # bursts of the tap's own columns after exact silence; start (and end) residues cover every offset modulo each tile
+    nb = max(tiles)
+    r = torch.zeros(C, 64 + nb * BURST_STEP)
+    loud = np.zeros(r.shape[1], bool)
+    for i in range(nb):
+        s = 64 + i * BURST_STEP
+        c0 = rs.randint(0, max(1, n - BURST_LEN))
+        seg = tap[:, c0:c0 + BURST_LEN]
+        r[:, s:s + seg.shape[1]] = seg
+        loud[s:s + seg.shape[1]] = True
+    rows.append((r, loud))
+    # isolated spikes at 100x each channel's RMS on a random third of the channels, on silence
+    r = torch.zeros(C, 64 + 16 * BURST_STEP)
+    loud = np.zeros(r.shape[1], bool)
+    for i in range(16):
+        s = 64 + i * BURST_STEP + rs.randint(0, 7)
+        chans = rs.choice(C, max(1, C // 3), replace=False)
+        r[chans, s] = 100.0 * ch_rms[chans] * torch.from_numpy(rs.choice([-1.0, 1.0], len(chans))).float()
+        loud[s] = True
+    rows.append((r, loud))
+    # ragged lengths on the tap's columns: 1, tile +- 1, the work tiles of the kernels (300..512 outputs) +- 1, long
+    lens = {1, 315, 316, 383, 384, 385, 499, 500, 501, 509, n}
+    for t in tiles:
+        lens |= {t - 1, t, t + 1, 2 * t + 1}
+    for ln in sorted(lens):
+        c0 = rs.randint(0, max(1, n - ln + 1))
+        seg = tap[:, c0:c0 + ln]
+        if seg.shape[1] < ln:  # (the tap is shorter: wrap around)
+            seg = tap[:, np.arange(c0, c0 + ln) % n]
+        rows.append((seg.clone(), None))
+    return rows
+
+
+def _batch(rows):
+    L = max(r.shape[1] for r, _ in rows)
+    L = (L + 3) // 4 * 4
+    x = torch.zeros(len(rows), rows[0][0].shape[0], L)
+    for i, (r, _) in enumerate(rows):
+        x[i, :, :r.shape[1]] = r
+    return x, [r.shape[1] for r, _ in rows]
+
+
+def _quiet(loud, pad):
+    """outputs whose receptive field [t - pad, t + pad] holds no loud sample"""
+    c = np.concatenate([[0], np.cumsum(loud)])
+    n = len(loud)
+    t = np.arange(n)
+    return (c[np.minimum(t + pad + 1, n)] - c[np.maximum(t - pad, 0)]) == 0
+
+
+class _Acc:
+    """e_rms / e_ch accumulated over rows; leak over the rows with a loud mask"""
+
+    def __init__(self, C):
+        self.e2 = torch.zeros(C, dtype=torch.float64)
+        self.r2 = torch.zeros(C, dtype=torch.float64)
+        self.n = 0
+        self.leak = 0.0
+
+    def add(self, y, ref, loud=None, pad=0, unit=None):
+        e = y.double() - ref
+        self.e2 += e.pow(2).sum(1)
+        self.r2 += ref.pow(2).sum(1)
+        self.n += ref.shape[1]
+        if loud is not None:
+            q = torch.from_numpy(_quiet(loud, pad))
+            if q.any():
+                self.leak = max(self.leak, float((e[:, q].abs() / unit[:, None]).max()))
+
+    def metrics(self):
+        layer = float((self.r2.sum() / (self.n * len(self.r2))).sqrt())
+        ch_ref = (self.r2 / self.n).sqrt().clamp(min=1e-3 * layer)
+        return dict(e_rms=float((self.e2.sum() / (self.n * len(self.e2))).sqrt()),
+                    e_ch=float(((self.e2 / self.n).sqrt() / ch_ref).max()), leak=self.leak, rms=layer, n=self.n)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# per-layer: the ResBlock convs of the C >= 64 stages through dissc_conv1d
+# ------------------------------------------------------------------------------------------------------------------------
+def _conv_forms(C, k, d, experimental):
+    """(name, wino, wino8, wino8_r4, tile width) of every form dissc_conv1d has an instance for (conv_wino8.hip's
+    wino8_supported / wino8_r4_supported, conv_wino.hip's wino_supported)"""
+    forms = [("direct", 0, 0, 0, 4), ("F(4,3)", 2, 0, 0, 4)]
+    if k in (7, 11) or experimental or (C == 64 and d == 1):
+        forms.append(("F(6,3)", 1, 2, 0, 6))
+    if k in (7, 11):
+        forms.append(("F(5,4)", 1, 2, 2, 5))
+    return forms
+
+
+def _with_options(lib, opts, fn):
+    saved = {}
+    try:
+        for key, v in opts.items():
+            cur = ctypes.c_int(0)
+            assert lib.dissc_get_option(key.encode(), ctypes.byref(cur)) == 0
+            saved[key] = cur.value
+            assert lib.dissc_set_option(key.encode(), v) == 0
+        return fn()
+    finally:
+        for key, v in saved.items():
+            lib.dissc_set_option(key.encode(), v)
+
+
+def _ref_conv(x, w, b, k, d, slope, dtype):
+    return F.conv1d(F.leaky_relu(x.to(dtype)[None], slope), w.to(dtype), b.to(dtype), padding=(k - 1) * d // 2, dilation=d)[0]
+
+
+def _report(name, form, ma, mb, ratios=""):
+    print(f"TL {name:24s} {form:8s} (a) e_rms {ma['e_rms']:.3e} e_ch {ma['e_ch']:.3e} | (b) e_rms {mb['e_rms']:.3e} "
+          f"e_ch {mb['e_ch']:.3e} leak {mb['leak']:.3g} {ratios}")
+
+
+@pytest.mark.parametrize("stage,j", [(i, j) for i in range(3) for j in range(3)])
+def test_trained_like_resblock_convs(tl, stage, j):
+    """every ResBlock conv of the 256 / 128 / 64-channel stages (convs1 at d = 1 / 3 / 5, convs2 at d = 1) through the direct
+    kernel and every transform-domain form with an instance for its shape"""
+    lib, folded = tl["lib"], tl["folded"]
+    C, k = STAGES[stage], KS[j]
+    bad = []
+    for grp in (1, 2):
+        for m in range(3):
+            d = DILS[m] if grp == 1 else 1
+            name = f"resblocks.{3 * stage + j}.convs{grp}.{m}"
+            w, b = folded[name + ".weight"], folded[name + ".bias"]
+            forms = _conv_forms(C, k, d, tl["experimental"])
+            tap = tl["inp"][name]
+            adv = _adversarial_rows(tap, [f[4] * d for f in forms], seed=1000 * stage + 100 * j + 10 * grp + m)
+            rows = [(tap, None)] + adv
+            x, lens = _batch(rows)
+            pad = (k - 1) * d // 2
+            unit = F.leaky_relu(x, SLOPE).abs().amax((1, 2))  # loud level per row
+            wsum = w.double().abs().sum((1, 2))
+            refs = [_ref_conv(x[i, :, :n], w, b, k, d, SLOPE, torch.float64) for i, n in enumerate(lens)]
+            cpu = [_ref_conv(x[i, :, :n], w, b, k, d, SLOPE, torch.float32) for i, n in enumerate(lens)]
+            res, outs = {}, {}
+            for form, wo, w8, r4, _tile in [("cpu", 0, 0, 0, 0)] + forms:
+                acc_a, acc_b = _Acc(C), _Acc(C)
+                if form == "cpu":
+                    y = cpu
+                else:
+                    yb = _with_options(lib, dict(wino=wo, wino8=w8, wino8_r4=r4),
+                                       lambda: _run_conv(dict(lib=lib, _lib=tl["_lib"]), x, w, b, lens, k, d, SLOPE))
+                    outs[form] = yb
+                    for i, n in enumerate(lens):
+                        assert (yb[i, :, n:] == -7.0).all(), (name, form, i, "wrote beyond the utterance")
+                        assert torch.isfinite(yb[i, :, :n]).all(), (name, form, i)
+                    y = [yb[i, :, :n] for i, n in enumerate(lens)]
+                for i, (r, loud) in enumerate(rows):
+                    if i == 0:
+                        acc_a.add(y[i], refs[i])
+                    else:
+                        acc_b.add(y[i], refs[i], loud, pad, float(unit[i]) * wsum * U)
+                res[form] = (acc_a.metrics(), acc_b.metrics())
+            bad += _check(name, [f[0] for f in forms], res, _plan_conv_form(lib, C, k, d))
+            for form, *_ in forms[1:]:
+                assert not torch.equal(outs[form], outs["direct"]), (name, form, "the form did not run")
+            if "F(6,3)" in outs and "F(5,4)" in outs:
+                assert not torch.equal(outs["F(6,3)"], outs["F(5,4)"]), (name, "F(5,4) did not run")
+    assert not bad, bad
+
+
+def _check(name, forms, res, plan_form):
+    """the bars of one layer; returns the broken ones (every layer and form is measured before a test fails).  plan_form: the
+    form the default plan runs this layer in -- a transform-domain form above TD_RMS x the direct kernel's e_rms must not be it
+    (generator.hip falls back to a safer form there); the e_ch and leak bars hold for every form"""
+    bad = []
+    (ca, cb), (da, db) = res["cpu"], res["direct"]
+    _report(name, "cpu-fp32", ca, cb)
+    # the direct kernel against CPU fp32 over all valid outputs of the layer's inputs, (a) and (b) together
+    e_dir = ((da["e_rms"] ** 2 * da["n"] + db["e_rms"] ** 2 * db["n"]) / (da["n"] + db["n"])) ** 0.5
+    e_cpu = ((ca["e_rms"] ** 2 * ca["n"] + cb["e_rms"] ** 2 * cb["n"]) / (ca["n"] + cb["n"])) ** 0.5
+    _report(name, "direct", da, db, f"direct/cpu {da['e_rms'] / ca['e_rms']:.2f} {db['e_rms'] / cb['e_rms']:.2f} "
+                                    f"all {e_dir / e_cpu:.2f}")
+    if e_dir > DIRECT_VS_CPU * e_cpu:
+        bad.append((name, "direct", "e_rms vs CPU fp32", e_dir / e_cpu))
+    for form in forms[1:]:
+        fa, fb = res[form]
+        ra, rb = fa["e_rms"] / da["e_rms"], fb["e_rms"] / db["e_rms"]
+        ha, hb = fa["e_ch"] / da["e_ch"], fb["e_ch"] / db["e_ch"]
+        tag = " [plan]" if form == plan_form else ""
+        _report(name, form, fa, fb, f"x direct: e_rms {ra:.2f} {rb:.2f} e_ch {ha:.2f} {hb:.2f}{tag}")
+        if max(ra, rb) > TD_RMS and form == plan_form:
+            bad.append((name, form, "e_rms x direct", ra, rb))
+        if max(ha, hb) > TD_CH:
+            bad.append((name, form, "e_ch x direct", ha, hb))
+        if fb["leak"] > LEAK:
+            bad.append((name, form, "leak", fb["leak"]))
+    return bad
+
+
+def _plan_conv_form(lib, C, k, d):
+    """generator.hip td_conv_form under the current option defaults (the ResBlock convs of the C >= 64 stages)"""
+    opt = {}
+    for key in ("wino", "wino8", "wino8_mask", "wino8_r4", "wino8_r4_mask"):
+        v = ctypes.c_int(0)
+        assert lib.dissc_get_option(key.encode(), ctypes.byref(v)) == 0
+        opt[key] = v.value
+    if not opt["wino"]:
+        return "direct"
+    bit = 9 * (2 if C >= 256 else 1 if C >= 128 else 0) + 3 * KS.index(k) + DILS.index(d)
+    if not opt["wino8"] or not (opt["wino8_mask"] >> bit) & 1 or not (k in (7, 11) or (C == 64 and d == 1)):
+        return "F(4,3)"
+    return "F(5,4)" if opt["wino8_r4"] and k in (7, 11) and (opt["wino8_r4_mask"] >> bit) & 1 else "F(6,3)"
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# per-layer: the residual pairs of the 32 / 16-channel stages through dissc_respair1d
+# ------------------------------------------------------------------------------------------------------------------------
+def _pair(tl, mode, x, w1, b1, w2, b2, lengths, k, d, epi=1, acc=None):
+    lib = tl["lib"]
+    B, C, ld = x.shape
+    xd = x.to(DEV)
+    for i, n in enumerate(lengths):
+        xd[i, :, n:] = float("nan")  # never read
+    y = torch.full_like(xd, -7.0)
+    ln = torch.as_tensor(lengths, dtype=torch.int32, device=DEV)
+    a = None if acc is None else acc.to(DEV).clone()
+    tl["_lib"].check(lib.dissc_respair1d(xd.data_ptr(), w1.contiguous().data_ptr(), b1.contiguous().data_ptr(),
+                                         w2.contiguous().data_ptr(), b2.contiguous().data_ptr(), y.data_ptr(),
+                                         None if a is None else a.data_ptr(), ln.data_ptr(), B, C, k, d, ld, int(max(lengths)),
+                                         ctypes.c_float(SLOPE), epi, ctypes.c_float(3.0), mode, None), f"dissc_respair1d {mode}")
+    return (y if epi == 1 else a).cpu()
+
+
+def _ref_pair(x, w1, b1, w2, b2, k, d, dtype):
+    x = x.to(dtype)[None]
+    t = F.conv1d(F.leaky_relu(x, SLOPE), w1.to(dtype), b1.to(dtype), padding=(k - 1) * d // 2, dilation=d)
+    return (x + F.conv1d(F.leaky_relu(t, SLOPE), w2.to(dtype), b2.to(dtype), padding=(k - 1) // 2))[0]
+
+
+@pytest.mark.parametrize("stage,j", [(i, j) for i in (3, 4) for j in range(3)])
+def test_trained_like_residual_pairs(tl, stage, j):
+    """every residual pair of the 32 / 16-channel stages: two direct launches (mode 0), the fused direct pair (mode 1) and,
+    for k = 11, the register-only F(2,3) pair (mode 3); the MRF epilogues (2: store, 3: accumulate, 4: accumulate / 3) on the
+    last pair of the chain"""
+    folded = tl["folded"]
+    C, k = STAGES[stage], KS[j]
+    bad = []
+    for m in range(3):
+        d = DILS[m]
+        p = f"resblocks.{3 * stage + j}"
+        w1, b1 = folded[f"{p}.convs1.{m}.weight"], folded[f"{p}.convs1.{m}.bias"]
+        w2, b2 = folded[f"{p}.convs2.{m}.weight"], folded[f"{p}.convs2.{m}.bias"]
+        forms = [("direct", 0, 4), ("fused", 1, 4)] + ([("F(2,3)", 3, 2)] if k == 11 else [])
+        tap = tl["inp"][f"{p}.convs1.{m}"]
+        adv = _adversarial_rows(tap, [2 * d, 4 * d, 6 * d], seed=1000 * stage + 100 * j + m)
+        rows = [(tap, None)] + adv
+        x, lens = _batch(rows)
+        pad = (k - 1) * d // 2 + (k - 1) // 2
+        unit = F.leaky_relu(x, SLOPE).abs().amax((1, 2))
+        s1 = float(w1.double().abs().sum((1, 2)).max())
+        wsum = w2.double().abs().sum((1, 2)) * s1  # the gain of the pair's path from a loud input, per output channel
+        refs = [_ref_pair(x[i, :, :n], w1, b1, w2, b2, k, d, torch.float64) for i, n in enumerate(lens)]
+        cpu = [_ref_pair(x[i, :, :n], w1, b1, w2, b2, k, d, torch.float32) for i, n in enumerate(lens)]
+        res, outs = {}, {}
+        for form, mode, _tile in [("cpu", -1, 0)] + forms:
+            acc_a, acc_b = _Acc(C), _Acc(C)
+            if form == "cpu":
+                y = cpu
+            else:
+                yb = _pair(tl, mode, x, w1, b1, w2, b2, lens, k, d)
+                outs[form] = yb
+                for i, n in enumerate(lens):
+                    assert (yb[i, :, n:] == -7.0).all(), (p, m, form, i, "wrote beyond the utterance")
+                    assert torch.isfinite(yb[i, :, :n]).all(), (p, m, form, i)
+                y = [yb[i, :, :n] for i, n in enumerate(lens)]
+                if m == 2:  # the MRF epilogues of the chain's last pair: exactly the pair's output stored / accumulated
+                    acc0 = torch.rand(x.shape, generator=torch.Generator().manual_seed(m))
+                    for epi in (2, 3, 4):
+                        a = _pair(tl, mode, x, w1, b1, w2, b2, lens, k, d, epi=epi, acc=acc0)
+                        for i, n in enumerate(lens):
+                            want = yb[i, :, :n] if epi == 2 else acc0[i, :, :n] + yb[i, :, :n]
+                            if epi == 4:
+                                want = want / 3.0
+                            assert torch.equal(a[i, :, :n], want), (p, form, epi, i)
+                            assert torch.equal(a[i, :, n:], acc0[i, :, n:]), (p, form, epi, i)
+            for i, (r, loud) in enumerate(rows):
+                if i == 0:
+                    acc_a.add(y[i], refs[i])
+                else:
+                    acc_b.add(y[i], refs[i], loud, pad, float(unit[i]) * wsum * U)
+            res[form] = (acc_a.metrics(), acc_b.metrics())
+        # the default plan: F(2,3) for the k = 11 pairs ("pair_f23" = 3), the fused direct pair otherwise
+        bad += _check(f"{p}.pair{m}", [f[0] for f in forms], res, "F(2,3)" if k == 11 else "fused")
+        if k == 11:
+            assert not torch.equal(outs["F(2,3)"], outs["direct"])
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("name", ["conv_pre"] + [f"ups.{i}" for i in range(5)])
+def test_trained_like_outer_layers_on_the_direct_kernels(tl, name):
+    """conv_pre (no activation on its input) and the five ConvTranspose1d layers on their float64-oracle inputs, direct
+    kernels: e_rms within 4x of CPU fp32.  (conv_post runs on its own fused kernel with the tanh, gen_misc.hip, which has no
+    stand-alone entry: the whole-generator tests below cover it.)"""
+    h = tl["synth"].VCTK_CONFIG
+    w, b = tl["folded"][name + ".weight"], tl["folded"][name + ".bias"]
+    tap = tl["inp"][name]
+    n = tap.shape[1]
+    lens = [n, max(1, n // 3), 1]
+    x = torch.stack([tap, torch.roll(tap, n // 2, 1), tap])
+    if name.startswith("ups"):
+        i = int(name[4:])
+        u, k = h["upsample_rates"][i], h["upsample_kernel_sizes"][i]
+        y = _run_conv(tl, x, w, b, lens, k, 1, SLOPE, transpose=True, stride=u)
+
+        def f(xi, dtype):
+            return F.conv_transpose1d(F.leaky_relu(xi.to(dtype)[None], SLOPE), w.to(dtype), b.to(dtype), stride=u,
+                                      padding=(k - u) // 2)[0]
+    else:
+        u, k, slope = 1, w.shape[2], 1.0
+        y = _run_conv(tl, x, w, b, lens, k, 1, slope)
+
+        def f(xi, dtype):
+            return _ref_conv(xi, w, b, k, 1, slope, dtype)
+    acc_g, acc_c = _Acc(y.shape[1]), _Acc(y.shape[1])
+    for i, ln in enumerate(lens):
+        ref = f(x[i, :, :ln], torch.float64)
+        acc_g.add(y[i, :, :ln * u], ref)
+        acc_c.add(f(x[i, :, :ln], torch.float32), ref)
+        assert (y[i, :, ln * u:] == -7.0).all(), (name, i)
+    mg, mc = acc_g.metrics(), acc_c.metrics()
+    print(f"TL {name:24s} direct   e_rms {mg['e_rms']:.3e} e_ch {mg['e_ch']:.3e} | cpu-fp32 e_rms {mc['e_rms']:.3e} "
+          f"e_ch {mc['e_ch']:.3e} direct/cpu {mg['e_rms'] / mc['e_rms']:.2f}")
+    assert mg["e_rms"] <= DIRECT_VS_CPU * mc["e_rms"], (name, mg, mc)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# whole generator under every plan
+# ------------------------------------------------------------------------------------------------------------------------
+PLANS = {
+    "default": {},
+    "f43": dict(wino8=0),
+    "f63": dict(wino8=1, wino8_r4=0, wino8_mask=0o777777777),
+    "f54": dict(wino8=1, wino8_r4=1, wino8_mask=0o777777777, wino8_r4_mask=0o777777777),
+    "direct": dict(wino=0),
+    "pair_direct": dict(pair_f23=0),
+    "split_bf16": dict(precision="split_bf16"),
+}
+
+
+@pytest.fixture(scope="module")
+def plans(tl):
+    out = {}
+    for name, opts in PLANS.items():
+        opts = dict(opts)
+        prec = opts.pop("precision", None)
+        out[name] = _generator_with(tl["lib"], tl["synth"], state_dict=tl["sd"], precision=prec, **opts)
+    return out
+
+
+def _run(g, code, f0, spkr, lengths=None):
+    kw = dict(code=torch.from_numpy(code), f0=torch.from_numpy(f0), spkr=torch.from_numpy(spkr))
+    if lengths is not None:
+        kw["lengths"] = torch.from_numpy(lengths)
+    return g(**kw).cpu()
+
+
+def _bars(plan, e, ref_rms, e32o, tag, discriminate=True):
+    """north star for every plan; the fp32 guard for the fp32 plans -- and split-bf16 must fail it (discriminate: False for
+    clips of a few hundred samples, where the RMS of split-bf16's error does not yet separate from the guard's floor)"""
+    guard = max(FP32_GUARD_RMS, GUARD_FACTOR * e32o)
+    print(f"TLGEN {tag} {plan:12s} rms {e:.3e} (fp32 oracle {e32o:.3e}, guard {guard:.2e}, signal {ref_rms:.3f})")
+    assert e <= NORTH_STAR_RMS and e <= 1e-3 * ref_rms, (tag, plan, e)
+    if plan == "split_bf16":
+        assert e > guard or not discriminate, (tag, "the fp32 guard no longer rejects split-bf16", e, guard)
+    else:
+        assert e <= guard, (tag, plan, e, guard)
+
+
+@pytest.mark.parametrize("T", [33, 99])
+def test_trained_like_generator_matches_reference_fixture(tl, plans, golden_dir, T):
+    import os
+    gold = np.load(os.path.join(golden_dir, "gen_vctk_trainedlike.npz"))
+    code, f0, spkr, _ = tl["synth"].synth_generator_inputs(1, T, seed=100 + T, kind="trained_like")
+    ref64, ref32 = gold[f"T{T}/wav64"], gold[f"T{T}/wav"]
+    e32o = _rms(ref32 - ref64)
+    for name, g in plans.items():
+        y = _run(g, code, f0, spkr).numpy()
+        assert y.shape == ref64.shape and np.isfinite(y).all()
+        _bars(name, _rms(y - ref64), _rms(ref64), e32o, f"T={T}")
+
+
+def test_trained_like_ragged_batch(tl, plans):
+    """B = 6 with a 0- and a 1-frame row, inputs poisoned beyond every length: each row against the float64 oracle, zeros
+    beyond it, and bit-identical when decoded alone"""
+    gr, synth = tl["gr"], tl["synth"]
+    code, f0, spkr, lengths = synth.synth_generator_inputs(6, 41, seed=21, ragged=True, kind="trained_like")
+    lengths = lengths.copy()
+    lengths[1], lengths[2], lengths[4] = 0, 1, 41
+    code2, f02 = code.copy(), f0.copy()
+    for b in range(6):
+        code2[b, lengths[b]:] = 99
+        f02[b, 0, lengths[b]:] = 1e9
+    w64 = gr.to_double(tl["folded"])
+    refs = {}
+    for b in range(6):
+        n = int(lengths[b])
+        if n:
+            args = (code[b:b + 1, :n], f0[b:b + 1, :, :n], spkr[b:b + 1])
+            refs[b] = (gr.code_generator(w64, synth.VCTK_CONFIG, *args).numpy(),
+                       gr.code_generator(tl["folded"], synth.VCTK_CONFIG, *args).numpy())
+    for name, g in plans.items():
+        y = _run(g, code2, f02, spkr, lengths).numpy()
+        assert y.shape == (6, 1, 320 * 41) and np.isfinite(y).all()
+        for b in range(6):
+            n = int(lengths[b]) * 320
+            assert not y[b, :, n:].any(), (name, b, "wrote beyond the row")
+            if b in refs:
+                r64, r32 = refs[b]
+                _bars(name, _rms(y[b:b + 1, :, :n] - r64), max(_rms(r64), 1e-1), _rms(r32 - r64), f"ragged b={b} n={n // 320}",
+                      discriminate=n >= 20 * 320)
+        for b in (0, 2, 3):
+            n = int(lengths[b])
+            one = _run(g, code2[b:b + 1, :n], f02[b:b + 1, :, :n], spkr[b:b + 1]).numpy()
+            assert np.array_equal(one[0], y[b, :, :320 * n]), (name, b)
+
+
+@pytest.fixture(scope="module")
+def full_case(tl):
+    gr, synth = tl["gr"], tl["synth"]
+    code, f0, spkr, _ = synth.synth_generator_inputs(32, 500, seed=1234, kind="trained_like")
+    w64 = gr.to_double(tl["folded"])
+    refs = {}
+    for b in (0, 3, 8, 13, 17, 22, 26, 31):  # the oracle on 8 of the 32 utterances
+        args = (code[b:b + 1], f0[b:b + 1], spkr[b:b + 1])
+        refs[b] = (gr.code_generator(w64, synth.VCTK_CONFIG, *args).numpy(),
+                   gr.code_generator(tl["folded"], synth.VCTK_CONFIG, *args).numpy())
+    return code, f0, spkr, refs
+
+
+@pytest.mark.parametrize("plan", list(PLANS))
+def test_trained_like_generator_full_size(tl, plans, full_case, plan):
+    """B = 32 x T = 500 under each plan: 8 utterances against the float64 oracle, batch independence for 3"""
+    code, f0, spkr, refs = full_case
+    g = plans[plan]
+    y = _run(g, code, f0, spkr).numpy()
+    assert y.shape == (32, 1, 160000) and np.isfinite(y).all() and np.abs(y).max() <= 1.0
+    for b, (r64, r32) in refs.items():
+        _bars(plan, _rms(y[b:b + 1] - r64), _rms(r64), _rms(r32 - r64), f"B=32xT=500 b={b}")
+    for b in (7, 19, 30):
+        one = _run(g, code[b:b + 1], f0[b:b + 1], spkr[b:b + 1]).numpy()
+        assert np.array_equal(one[0], y[b]), (plan, b)
