@@ -95,6 +95,8 @@ def _load():
     L.dissc_kmeans_assign.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.dissc_mfma_peak.argtypes = [i32, ctypes.POINTER(ctypes.c_float)]
     L.dissc_erf_check.argtypes = [vp, vp, i32, vp]
+    L.dissc_attention.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
+    L.dissc_layernorm_cf.argtypes = [vp, vp, vp, vp, i32, i32, i32, ctypes.c_float, vp, vp]
     L.dissc_set_option.argtypes = [ctypes.c_char_p, i32]
     L.dissc_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     L.dissc_conv_bench.argtypes = [i32] * 9 + [ctypes.POINTER(ctypes.c_float)]

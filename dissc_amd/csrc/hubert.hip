@@ -180,6 +180,11 @@ __global__ void __launch_bounds__(256) conv0_apply_kernel(const float* __restric
 // ---- LayerNorm over channels of a channels-first tensor (optionally of x + r) ----------------
 // One block = 64 time steps x all C channels; 16 waves each keep C/16 channels of their 64
 // columns in registers (single pass over HBM), partial moments are combined through LDS.
+// The moments are taken of the row minus one of its own values, p (the median of three channels; the shift is exact for rows near
+// a common offset), and the output subtracts the mean as c = p + mean_s plus the rounding residual of that sum: a constant row
+// gives beta exactly, and a row at an offset of 1e3 .. 1e4 keeps its mean (the plain fp32 sum of 768 values near 1e4 lost it:
+// 1e-3 relative error against torch's 3e-4, and 2 away from beta on a constant row of 5679).  A pivot at an outlier would put
+// C |p| into the sums (7x torch's error on a row whose pivot channel was at 1e3): hence the median.
 constexpr int LN_WAVES = 16;
 constexpr int LN_MAXC = 48;  // channels per wave held in registers (C <= 768)
 __global__ void __launch_bounds__(64 * LN_WAVES) ln_cf_kernel(const float* __restrict__ x,
@@ -195,6 +200,17 @@ __global__ void __launch_bounds__(64 * LN_WAVES) ln_cf_kernel(const float* __res
   const bool ok = t < lens[b];
   const int cpw = C / LN_WAVES;  // host guarantees C % 16 == 0 and cpw <= LN_MAXC
   const size_t base = (size_t)b * C * ld + (size_t)(wv * cpw) * ld + t;
+  float piv = 0.f;
+  if (ok) {  // the median of channels 0, C/2 and C-1: an outlier channel (a massive dimension) is not picked unless two of them are
+    const size_t b0 = (size_t)b * C * ld + t, b1 = b0 + (size_t)(C / 2) * ld, b2 = b0 + (size_t)(C - 1) * ld;
+    float p0 = x[b0], p1 = x[b1], p2 = x[b2];
+    if (r) {
+      p0 += r[b0];
+      p1 += r[b1];
+      p2 += r[b2];
+    }
+    piv = fmaxf(fminf(p0, p1), fminf(fmaxf(p0, p1), p2));
+  }
   float v[LN_MAXC];
   float s = 0.f;
 #pragma unroll
@@ -204,19 +220,21 @@ __global__ void __launch_bounds__(64 * LN_WAVES) ln_cf_kernel(const float* __res
       v[i] = x[base + (size_t)i * ld];
       if (r) v[i] += r[base + (size_t)i * ld];
     }
-    s += v[i];
+    if (i < cpw) s += v[i] - piv;
   }
   red[wv][lane] = s;
   __syncthreads();
   float tot = 0.f;
 #pragma unroll
   for (int w = 0; w < LN_WAVES; ++w) tot += red[w][lane];
-  const float mean = tot / (float)C;
+  const float mean_s = tot / (float)C;           // mean of the shifted row
+  const float mc = piv + mean_s;                  // the mean ...
+  const float mr = (piv - mc) + mean_s;           // ... and the rounding residual of that sum
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAXC; ++i)
     if (i < cpw) {
-      const float d = v[i] - mean;
+      const float d = (v[i] - piv) - mean_s;
       q = fmaf(d, d, q);
     }
   __syncthreads();
@@ -231,7 +249,7 @@ __global__ void __launch_bounds__(64 * LN_WAVES) ln_cf_kernel(const float* __res
   for (int i = 0; i < LN_MAXC; ++i)
     if (i < cpw) {
       const int c = wv * cpw + i;
-      y[base + (size_t)i * ld] = (v[i] - mean) * rstd * gamma[c] + beta[c];
+      y[base + (size_t)i * ld] = ((v[i] - mc) - mr) * rstd * gamma[c] + beta[c];
     }
 }
 
@@ -1078,4 +1096,27 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
   return DISSC_OK;
 }
 
+// Diagnostics: the encoder's fused attention (attn.hip) and its LayerNorm on their own, on caller-made inputs (device pointers,
+// asynchronous on `stream`).  The forward path does not use these entries.
+int dissc_attention(const float* qkv, const int32_t* lens, int B, int Tmax, int D, int ld, float* out, void* stream) {
+  if (!qkv || !lens || !out || B <= 0 || Tmax <= 0 || D <= 0 || D % 64 != 0 || ld < Tmax || ld % 4 != 0) {
+    set_error("dissc_attention: bad argument (D %% 64 == 0, Tmax <= ld, ld %% 4 == 0)");
+    return DISSC_EINVAL;
+  }
+  return launch_attn_fused(qkv, lens, D, 64, ld, out, Tmax, D / 64, B, (hipStream_t)stream);
+}
+
+int dissc_layernorm_cf(const float* x, const float* gamma, const float* beta, const int32_t* lens, int B, int C, int ld, float eps,
+                       float* y, void* stream) {
+  if (!x || !gamma || !beta || !lens || !y || B <= 0 || ld <= 0 || C <= 0 || C % LN_WAVES != 0 || C / LN_WAVES > LN_MAXC) {
+    set_error("dissc_layernorm_cf: bad argument (C %% %d == 0, C <= %d)", LN_WAVES, LN_WAVES * LN_MAXC);
+    return DISSC_EINVAL;
+  }
+  hipLaunchKernelGGL(ln_cf_kernel, dim3((ld + 63) / 64, B), dim3(64 * LN_WAVES), 0, (hipStream_t)stream, x, (const float*)nullptr, gamma,
+                     beta, lens, C, ld, eps, y);
+  DISSC_HIP_CHECK(hipGetLastError());
+  return DISSC_OK;
+}
+
 }  // extern "C"
+

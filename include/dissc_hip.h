@@ -326,6 +326,17 @@ int dissc_mfma_peak(int iters, float* tflops);
 /* Diagnostics: y[i] = erf(x[i]) as the GELU epilogues evaluate it (branch-free, < 1 ulp; HuBERT's exact-erf GELU,
  * arch per HF:154-213,371-445 [3P]); x, y: device f32 [n]. */
 int dissc_erf_check(const float* x, float* y, int n, void* stream);
+/* Diagnostics: the encoder's fused self-attention (exact softmax, fp32; the launch dissc_hubert_forward makes) on its own.
+ * qkv f32 [B][3D][ld] channels-first (rows Q | K | V; head h owns rows 64h .. 64h + 63 of each; Q already scaled by 1/8, as the
+ * forward's qkv GEMM leaves it), lens i32 [B] frames per utterance (each <= Tmax <= ld, ld % 4 == 0), H = D / 64 heads
+ * -> out f32 [B][D][ld]: columns t < lens[b] written, the rest untouched.  Device pointers; asynchronous on `stream`. */
+int dissc_attention(const float* qkv, const int32_t* lens, int B, int Tmax, int D, int ld, float* out, void* stream);
+/* Diagnostics: the encoder's LayerNorm over the channels of a channels-first tensor (fp32, moments of the row shifted by one
+ * of its own values; the launch the forward makes 14 times): x f32 [B][C][ld] (C % 16 == 0, C <= 768), gamma / beta f32 [C],
+ * lens i32 [B] (each <= ld) -> y f32 [B][C][ld]: columns t < lens[b] written, the rest untouched.  Device pointers;
+ * asynchronous on `stream`. */
+int dissc_layernorm_cf(const float* x, const float* gamma, const float* beta, const int32_t* lens, int B, int C, int ld, float eps,
+                       float* y, void* stream);
 /* Diagnostics: ms[0] a pure-MFMA kernel alone, ms[1] a pure-fp32-VALU kernel alone, ms[2] both
  * at once on two streams (do the two pipes overlap on this part?). */
 int dissc_pipe_overlap(int mfma_iters, int valu_iters, float* ms);

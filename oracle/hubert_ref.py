@@ -73,8 +73,9 @@ def pos_conv_weight(sd):
     return torch._weight_norm(sd["encoder.pos_conv.0.weight_v"], sd["encoder.pos_conv.0.weight_g"], 2)
 
 
-def encoder(sd, feats, n_layers=6, n_heads=12):
-    """feats [B,512,T] -> layer-``n_layers`` output [B,T,768]"""
+def encoder(sd, feats, n_layers=6, n_heads=12, taps=None, logits=None):
+    """feats [B,512,T] -> layer-``n_layers`` output [B,T,768]; ``taps`` (a list) gets every layer's output (HF's
+    hidden_states[1..n_layers]), ``logits`` (a list) every layer's largest |attention logit| per head [n_heads]"""
     x = feats.transpose(1, 2)
     x = F.layer_norm(x, (x.shape[-1],), sd["layer_norm.weight"], sd["layer_norm.bias"], EPS)
     x = F.linear(x, sd["post_extract_proj.weight"], sd["post_extract_proj.bias"])
@@ -90,13 +91,18 @@ def encoder(sd, feats, n_layers=6, n_heads=12):
         k = F.linear(x, sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.k_proj.bias"])
         v = F.linear(x, sd[p + "self_attn.v_proj.weight"], sd[p + "self_attn.v_proj.bias"])
         q, k, v = (t.view(B, T, n_heads, hd).transpose(1, 2) for t in (q, k, v))
-        a = torch.softmax(q @ k.transpose(-1, -2), dim=-1) @ v
+        s = q @ k.transpose(-1, -2)
+        if logits is not None:
+            logits.append(s.abs().amax((0, 2, 3)))
+        a = torch.softmax(s, dim=-1) @ v
         a = a.transpose(1, 2).reshape(B, T, D)
         a = F.linear(a, sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"])
         x = F.layer_norm(x + a, (D,), sd[p + "self_attn_layer_norm.weight"], sd[p + "self_attn_layer_norm.bias"], EPS)
         h = F.gelu(F.linear(x, sd[p + "fc1.weight"], sd[p + "fc1.bias"]))
         h = F.linear(h, sd[p + "fc2.weight"], sd[p + "fc2.bias"])
         x = F.layer_norm(x + h, (D,), sd[p + "final_layer_norm.weight"], sd[p + "final_layer_norm.bias"], EPS)
+        if taps is not None:
+            taps.append(x)
     return x
 
 
@@ -154,11 +160,11 @@ def unit_flip_allowed(x_ref, centers, eps_l2=None, eps_rel=FEAT_EPS_L2_REL):
     return allowed.numpy(), int((allowed.sum(1) > 1).sum())
 
 
-def check_units(units, units_ref, x_ref, centers, x_dev=None, tag="units", max_mismatch=1):
+def check_units(units, units_ref, x_ref, centers, x_dev=None, tag="units", max_mismatch=1, eps_rel=FEAT_EPS_L2_REL):
     """Assert: every frame where ``units`` differs from the reference's is explained by the feature error (measured when
-    ``x_dev`` is given, else the asserted FEAT_EPS_L2_REL bound) -- and the unit chosen instead is one of the explicable
+    ``x_dev`` is given, else the asserted ``eps_rel`` bound) -- and the unit chosen instead is one of the explicable
     ones -- and no more than ``max_mismatch`` frames of the utterance differ at all (measured on every golden: 0; None: unbounded,
-    for constructed ties).
+    for constructed ties).  ``eps_rel``: the per-frame relative l2 feature error asserted (and assumed without ``x_dev``).
     Returns (n_mismatch, n_ambiguous)."""
     import numpy as np
     x_ref = torch.as_tensor(x_ref)
@@ -166,8 +172,8 @@ def check_units(units, units_ref, x_ref, centers, x_dev=None, tag="units", max_m
     if x_dev is not None:
         eps = (torch.as_tensor(x_dev).double() - x_ref.double()).norm(dim=1)
         rel = eps / x_ref.double().norm(dim=1).clamp_min(1e-30)
-        assert float(rel.max()) <= FEAT_EPS_L2_REL, f"{tag}: per-frame feature error {float(rel.max()):.3e} > {FEAT_EPS_L2_REL}"
-    allowed, n_amb = unit_flip_allowed(x_ref, centers, eps)
+        assert float(rel.max()) <= eps_rel, f"{tag}: per-frame feature error {float(rel.max()):.3e} > {eps_rel}"
+    allowed, n_amb = unit_flip_allowed(x_ref, centers, eps, eps_rel=eps_rel)
     units, units_ref = np.asarray(units).reshape(-1), np.asarray(units_ref).reshape(-1)
     assert units.shape == units_ref.shape == (allowed.shape[0],)
     ok = allowed[np.arange(len(units)), units]
@@ -181,10 +187,17 @@ def check_units(units, units_ref, x_ref, centers, x_dev=None, tag="units", max_m
 
 
 @torch.no_grad()
-def encode(sd, centers, wav, n_layers=6):
-    """One utterance like the reference (B=1, data/encode.py:32): wav [1,N] -> (units [T], dense [T,768])"""
-    dense = encoder(sd, conv_feature_extractor(sd, wav), n_layers)[0]
-    return kmeans_assign(dense, centers), dense
+def encode(sd, centers, wav, n_layers=6, taps=None, logits=None):
+    """One utterance like the reference (B=1, data/encode.py:32): wav [1,N] -> (units [T], dense [T,768]), in the dtype of
+    ``sd`` (to_double: the float64 oracle); ``taps``, ``logits``: see encoder"""
+    wav = torch.as_tensor(wav).to(next(iter(sd.values())).dtype)
+    dense = encoder(sd, conv_feature_extractor(sd, wav), n_layers, taps=taps, logits=logits)[0]
+    return kmeans_assign(dense, torch.as_tensor(centers).to(dense.dtype)), dense
+
+
+def to_double(sd):
+    """the float64 oracle's weights: the fp32 checkpoint's values, widened"""
+    return {k: v.double() for k, v in sd.items()}
 
 
 def fairseq_to_hf(sd):

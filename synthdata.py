@@ -331,7 +331,13 @@ def synth_unit_sequences(n, T_lo=60, T_hi=500, seed=99, n_codes=100):
 # ----------------------------------------------------------------------------------------------
 # HuBERT-base (fairseq checkpoint key names) + k-means centroids
 # ----------------------------------------------------------------------------------------------
-def synth_hubert_state_dict(n_layers=6, seed=3):
+def synth_hubert_state_dict(n_layers=6, seed=3, kind="iid"):
+    """fairseq HuBERT-base keys.  kind "iid": N(0,1) weights at unit RMS gain (q / k gain 1.5), LayerNorm gains N(1, 0.1) (every
+    existing fixture); "trained_like": the heavy-tailed statistics of the HT_* constants below (same keys and layouts)."""
+    if kind == "trained_like":
+        return _synth_hubert_state_dict_trained_like(n_layers, seed)
+    if kind != "iid":
+        raise ValueError(f"kind {kind!r}: 'iid' or 'trained_like'")
     rs = np.random.RandomState(seed)
     sd = OrderedDict()
     convs = [(512, 1, 10)] + [(512, 512, 3)] * 4 + [(512, 512, 2)] * 2
@@ -367,11 +373,182 @@ def synth_hubert_state_dict(n_layers=6, seed=3):
     return sd
 
 
+# kind="trained_like" HuBERT (frozen; tuned until the checks of tests/test_trained_like_hubert_cpu.py hold):
+#  * feature convs: Student-t(HT_T_DOF) directions, per-output-channel gains log-normal with sigma HT_GAIN_SIGMA, HT_OUTLIERS channels
+#    at HT_OUTLIER_GAIN x the median gain and HT_DEAD_FRAC all-zero (dead) channels, RMS-renormalised to the iid layer's gain;
+#    GroupNorm gamma log-normal (sigma HT_GN_SIGMA) with HT_GN_NEAR_ZERO gammas at HT_GN_ZERO_GAMMA, beta HT_GN_BETA_STD * N(0,1);
+#  * massive activations: HT_MASSIVE residual dimensions whose beta is HT_MASSIVE_BETA (signs random) in every encoder LayerNorm and
+#    whose out_proj / fc2 bias is HT_MASSIVE_BIAS_FRAC x that beta, so |x| stays at 1e2 .. 1e3 after every LayerNorm; the other
+#    dimensions' gamma is log-normal (sigma HT_LN_SIGMA), and x HT_LN_GAMMA in the LayerNorms of the layers: there the massive
+#    dimensions dominate the LayerNorm's variance and would otherwise squash the rest to ~1e-2.  Every projection reading the residual stream sees the massive
+#    dimensions' columns scaled by HT_MASSIVE_COL (they act as a bias, as in trained models);
+#  * attention: per-head q / k gains geometric over HT_QK_GAIN (order shuffled), so the largest |logit| spans ~1 .. ~80 over the
+#    heads; head HT_SINK_HEAD of every layer is a sink whose query is dominated by a bias of norm HT_SINK_QBIAS (every query picks the
+#    same few keys);
+#  * fc1 / fc2: Student-t rows; pos_conv weight_g spread over HT_POS_DECADES decades across the 128 kernel positions.
+HT_T_DOF = 3.0
+HT_GAIN_SIGMA = 1.0
+HT_OUTLIERS = 3
+HT_OUTLIER_GAIN = 30.0
+HT_DEAD_FRAC = 0.05
+HT_GN_SIGMA = 0.5
+HT_GN_NEAR_ZERO = 4
+HT_GN_ZERO_GAMMA = 1e-3
+HT_GN_BETA_STD = 0.5
+HT_MASSIVE = 4
+HT_MASSIVE_BETA = (150.0, 300.0, 600.0, 1000.0)
+HT_MASSIVE_BIAS_FRAC = 0.5
+HT_MASSIVE_COL = 0.001
+HT_LN_GAMMA = 40.0
+HT_LN_SIGMA = 0.3
+HT_QK_GAIN = (0.4, 4.0)
+HT_SINK_HEAD = 11
+HT_SINK_QBIAS = 60.0
+HT_POS_DECADES = 3.0
+
+
+def hubert_massive_dims(seed=3):
+    """the residual dimensions kind="trained_like" makes massive (a function of the seed only)"""
+    return np.sort(np.random.RandomState(seed + 1000).choice(768, HT_MASSIVE, replace=False))
+
+
+def _t_rows(rs, co, ci, gain, shape=None):
+    """Student-t directions at the iid RMS gain gain / sqrt(fan_in)"""
+    w = rs.standard_t(HT_T_DOF, size=shape or (co, ci))
+    return w * (gain / np.sqrt(ci) / np.sqrt(np.mean(w ** 2)))
+
+
+def _synth_hubert_state_dict_trained_like(n_layers, seed):
+    rs = np.random.RandomState(seed)
+    sd = OrderedDict()
+    convs = [(512, 1, 10)] + [(512, 512, 3)] * 4 + [(512, 512, 2)] * 2
+    for i, (co, ci, k) in enumerate(convs):
+        w = rs.standard_t(HT_T_DOF, size=(co, ci, k))
+        w /= np.sqrt((w.reshape(co, -1) ** 2).mean(1))[:, None, None]
+        c = np.exp(HT_GAIN_SIGMA * rs.standard_normal(co))
+        c[rs.choice(co, HT_OUTLIERS, replace=False)] = HT_OUTLIER_GAIN * np.median(c)
+        c[rs.choice(co, int(round(HT_DEAD_FRAC * co)), replace=False)] = 0.0
+        c /= np.sqrt(np.mean(c ** 2))
+        sd[f"feature_extractor.conv_layers.{i}.0.weight"] = _t(w * (c * 1.6 / np.sqrt(ci * k))[:, None, None])
+    g = np.exp(HT_GN_SIGMA * rs.standard_normal(512))
+    g[rs.choice(512, HT_GN_NEAR_ZERO, replace=False)] = HT_GN_ZERO_GAMMA
+    sd["feature_extractor.conv_layers.0.2.weight"] = _t(g)
+    sd["feature_extractor.conv_layers.0.2.bias"] = _t(HT_GN_BETA_STD * rs.standard_normal(512))
+    mdims = hubert_massive_dims(seed)
+    mbeta = np.asarray(HT_MASSIVE_BETA) * rs.choice([-1.0, 1.0], size=HT_MASSIVE)
+
+    def ln(name, c, massive, gain=HT_LN_GAMMA):
+        gm = np.exp(HT_LN_SIGMA * rs.standard_normal(c))
+        bt = 0.05 * rs.standard_normal(c)
+        if massive:
+            gm *= gain
+            gm[mdims] = 1.0
+            bt[mdims] = mbeta
+        sd[name + ".weight"] = _t(gm)
+        sd[name + ".bias"] = _t(bt)
+
+    def lin(name, co, ci, gain=1.0, reads_x=True, massive_bias=False):
+        w = _t_rows(rs, co, ci, gain)
+        if reads_x and ci == 768:
+            w[:, mdims] *= HT_MASSIVE_COL
+        b = 0.05 * rs.standard_normal(co)
+        if massive_bias:
+            b[mdims] = HT_MASSIVE_BIAS_FRAC * mbeta
+        sd[name + ".weight"] = _t(w)
+        sd[name + ".bias"] = _t(b)
+        return w, b
+
+    ln("layer_norm", 512, False)
+    lin("post_extract_proj", 768, 512, reads_x=False)
+    v = rs.standard_normal((768, 48, 128))
+    spread = 10.0 ** (HT_POS_DECADES * (rs.rand(128) - 0.5))
+    spread /= np.sqrt(np.mean(spread ** 2))
+    sd["encoder.pos_conv.0.weight_v"] = _t(v)
+    sd["encoder.pos_conv.0.weight_g"] = _t(np.sqrt((v ** 2).sum((0, 1), keepdims=True)) * 1.2 / np.sqrt(48 * 128)
+                                           * spread[None, None, :])
+    sd["encoder.pos_conv.0.bias"] = _t(0.1 * rs.standard_normal(768))
+    ln("encoder.layer_norm", 768, True, gain=1.0)  # its input has no massive dimensions yet
+    for i in range(n_layers):
+        p = f"encoder.layers.{i}."
+        hg = np.exp(np.linspace(np.log(HT_QK_GAIN[0]), np.log(HT_QK_GAIN[1]), 12))[rs.permutation(12)]
+        for n in ("q_proj", "k_proj"):
+            w, b = lin(p + "self_attn." + n, 768, 768)
+            w *= np.repeat(hg, 64)[:, None]
+            if n == "q_proj":
+                u = rs.standard_normal(64)
+                b[HT_SINK_HEAD * 64:(HT_SINK_HEAD + 1) * 64] = HT_SINK_QBIAS * u / np.linalg.norm(u)
+            sd[p + "self_attn." + n + ".weight"] = _t(w)
+            sd[p + "self_attn." + n + ".bias"] = _t(b)
+        lin(p + "self_attn.v_proj", 768, 768)
+        lin(p + "self_attn.out_proj", 768, 768, massive_bias=True)
+        ln(p + "self_attn_layer_norm", 768, True)
+        lin(p + "fc1", 3072, 768)
+        lin(p + "fc2", 768, 3072, reads_x=False, massive_bias=True)
+        ln(p + "final_layer_norm", 768, True)
+    return sd
+
+
 def synth_kmeans_centers(k=100, dim=768, seed=4):
     return _t(np.random.RandomState(seed).standard_normal((k, dim)) * 0.7)
 
 
-def synth_waveform(n, seed=0):
+# kind="speech_like" waveforms (frozen): a harmonic-plus-noise source (f0 WF_F0 Hz with a slow glide, WF_HARMONICS harmonics at
+# 1/k, noise WF_NOISE of the harmonic RMS) under a syllabic envelope (WF_SYLLABLE_HZ) spanning WF_ENV_DB dB, peak WF_PEAK; exact
+# digital silence over WF_EDGE_S seconds at both ends and one gap in the middle (WF_GAP_S seconds, or a third of a short
+# utterance); WF_BURSTS short bursts driven into clipping at +-32767/32768; int16-quantised (k / 32768).  kind "speech_dc": the same
+# plus a DC offset of WF_DC (silence included); kind "dither": 1-LSB dither only (samples in {-1, 0, 1} / 32768).
+WF_F0 = (90.0, 240.0)
+WF_HARMONICS = 12
+WF_NOISE = 0.3
+WF_SYLLABLE_HZ = 4.0
+WF_ENV_DB = 40.0
+WF_PEAK = 0.3
+WF_EDGE_S = 0.15
+WF_GAP_S = 1.0
+WF_BURSTS = 2
+WF_DC = 0.05
+
+
+def _speech_like(n, rs):
+    t = np.arange(n) / 16000.0
+    f0 = WF_F0[0] + (WF_F0[1] - WF_F0[0]) * rs.rand()
+    f = f0 * (1.0 + 0.15 * np.sin(2 * np.pi * (0.3 + 0.4 * rs.rand()) * t + 2 * np.pi * rs.rand()))
+    ph = 2 * np.pi * np.cumsum(f) / 16000.0
+    x = sum(np.sin(k * ph + 2 * np.pi * rs.rand()) / k for k in range(1, WF_HARMONICS + 1))
+    x = x / np.sqrt(np.mean(x ** 2)) + WF_NOISE * rs.standard_normal(n)
+    env_db = -WF_ENV_DB * 0.5 * (1.0 - np.cos(2 * np.pi * WF_SYLLABLE_HZ * t + 2 * np.pi * rs.rand()))
+    x = WF_PEAK * x * 10.0 ** (env_db / 20.0) / 3.0
+    for _ in range(WF_BURSTS):
+        a = rs.randint(0, max(1, n - 800))
+        x[a:a + 800] *= 40.0
+    edge = min(int(WF_EDGE_S * 16000), n // 8)
+    gap = int(WF_GAP_S * 16000) if n >= 3 * int(WF_GAP_S * 16000) else n // 3
+    x[:edge] = 0.0
+    x[n - edge:] = 0.0
+    g0 = (n - gap) // 2
+    x[g0:g0 + gap] = 0.0
+    return x
+
+
+def synth_waveform(n, seed=0, kind="iid"):
+    """kind "iid": N(0,0.1) noise + a few tones, clipped to [-1,1] (every existing fixture); "speech_like",
+    "speech_dc", "dither": the int16-quantised waveforms above."""
+    if kind == "iid":
+        return _synth_waveform_iid(n, seed)
+    rs = np.random.RandomState(seed)
+    if kind == "dither":
+        q = rs.randint(-1, 2, size=n).astype(np.float64)
+    elif kind in ("speech_like", "speech_dc"):
+        x = _speech_like(n, rs)
+        if kind == "speech_dc":
+            x = x + WF_DC
+        q = np.clip(np.round(x * 32768.0), -32767, 32767)
+    else:
+        raise ValueError(f"kind {kind!r}: 'iid', 'speech_like', 'speech_dc' or 'dither'")
+    return (q / 32768.0).astype(np.float32)
+
+
+def _synth_waveform_iid(n, seed):
     """N(0,0.1) noise + a few tones, clipped to [-1,1]"""
     rs = np.random.RandomState(seed)
     t = np.arange(n) / 16000.0

@@ -467,6 +467,57 @@ def make_hubert():
     print("hubert.npz", {k: v.shape for k, v in out.items() if k.endswith("units")})
 
 
+# hubert_trained_like: the fixture's utterances (kind, samples, seed) and the ones the k-means centres are fitted on
+HUBERT_TL_UTTS = (("speech_like", 32000, 31), ("speech_dc", 16000, 32), ("dither", 8000, 33))
+HUBERT_TL_FIT = tuple(("speech_like" if i % 3 else "speech_dc", 48000 + 16000 * i, 40 + i) for i in range(6))
+HUBERT_TL_KEEP = 5  # frames per utterance whose hidden states are stored (evenly spaced, both ends included): 1 MiB bounds the file
+
+
+def make_hubert_trained_like():
+    """synthdata's kind="trained_like" HuBERT (seed 3, 6 layers) -> hubert_trainedlike.npz:
+    * centres: K = 100, sklearn KMeans (random_state 0, n_init 1) fitted on the float64 oracle's layer-6 features of the
+      HUBERT_TL_FIT utterances (as km100 was fitted on HuBERT features: near-ties are frequent).  Stored, never refitted: the
+      fit is not bit-stable across sklearn builds;
+    * per HUBERT_TL_UTTS utterance u: HF HubertModel hidden_states[1..6] in fp32 (u/hs32 [6, F, 768]) and with the module in
+      float64 (.double(); stored as u/hs64d = hs64 - hs32 in fp32, which keeps ~1e-14 of the float64 value) at the frames u/frames
+      [F]; u/units: sklearn's fp32 predict on the fp32 layer-6 features of every frame."""
+    from sklearn.cluster import KMeans
+    from transformers import HubertConfig, HubertModel
+    from oracle import hubert_ref
+    sd = synth.synth_hubert_state_dict(6, kind="trained_like")
+    sd64 = hubert_ref.to_double(sd)
+    fit = []
+    for kind, n, seed in HUBERT_TL_FIT:
+        wav = torch.from_numpy(synth.synth_waveform(n, seed=seed, kind=kind))[None]
+        fit.append(hubert_ref.encode(sd64, torch.zeros(1, 768), wav)[1].numpy())
+    km = KMeans(n_clusters=100, n_init=1, random_state=0).fit(np.concatenate(fit))
+    centers = km.cluster_centers_.astype(np.float32)
+    km.cluster_centers_ = centers
+    m = HubertModel(HubertConfig(num_hidden_layers=6)).eval()
+    missing, unexpected = m.load_state_dict(hubert_ref.fairseq_to_hf(sd), strict=False)
+    assert not unexpected and all("masked_spec_embed" in k for k in missing), (missing, unexpected)
+    m64 = HubertModel(HubertConfig(num_hidden_layers=6)).eval()
+    m64.load_state_dict(hubert_ref.fairseq_to_hf(sd), strict=False)
+    m64.double()
+    out = {"centers": centers}
+    for kind, n, seed in HUBERT_TL_UTTS:
+        wav = torch.from_numpy(synth.synth_waveform(n, seed=seed, kind=kind))[None]
+        with torch.no_grad():
+            h32 = m(wav, output_hidden_states=True).hidden_states
+            h64 = m64(wav.double(), output_hidden_states=True).hidden_states
+        T = h32[6].shape[1]
+        frames = np.unique(np.linspace(0, T - 1, HUBERT_TL_KEEP).round().astype(np.int64))
+        hs32 = np.stack([h32[L][0].numpy()[frames] for L in range(1, 7)])
+        hs64 = np.stack([h64[L][0].numpy()[frames] for L in range(1, 7)])
+        assert hs64.dtype == np.float64
+        out[f"{kind}/frames"] = frames
+        out[f"{kind}/hs32"] = hs32
+        out[f"{kind}/hs64d"] = (hs64 - hs32).astype(np.float32)
+        out[f"{kind}/units"] = km.predict(h32[6][0].numpy().astype(np.float32)).astype(np.int64)
+    np.savez_compressed(os.path.join(OUT, "hubert_trainedlike.npz"), **out)
+    print("hubert_trainedlike.npz", {k: v.shape for k, v in out.items()})
+
+
 def synth_units_jsonl(seed=7, n_spk=5, utts_per_spk=6):
     """Encoded-dataset lines the way data/encode.py writes them: f0 in Hz as float32 values,
     exact 0.0 on unvoiced frames; one speaker is entirely unvoiced in one utterance."""
@@ -688,7 +739,8 @@ def make_upsample():
     print("gen_upsample.npz", {k: v.shape for k, v in out.items() if k.endswith("wav")})
 
 
-TARGETS = {"upsample": make_upsample, "train": make_train, "prep_dataset": make_prep_dataset, "hubert": make_hubert, "sr_inference": make_sr_inference,
+TARGETS = {"upsample": make_upsample, "train": make_train, "prep_dataset": make_prep_dataset, "hubert": make_hubert,
+           "hubert_trained_like": make_hubert_trained_like, "sr_inference": make_sr_inference,
            "generator": make_generator, "generator_trained_like": make_generator_trained_like, "predictors": make_predictors}
 
 if __name__ == "__main__":
