@@ -83,7 +83,6 @@ struct Options {
   static constexpr int conv_pad_lds = 0;  // extra LDS bytes per workgroup (occupancy experiments)
   static constexpr int c64_wide = 1;  // 64 x 256 tile for the DMA-staged second convs of the C = 64 stage
   static constexpr int conv2_dma = 1;  // stride-2 valid convs of the 256 x 64 kernel stage by global_load_lds
-  static constexpr int mfast = 0;  // blockIdx.x walks the M tiles (measured neutral)
   static constexpr int wino_min_c = 64;  // narrowest stage on the transform-domain kernels
   static constexpr int wino_c64_kmin = 3;  // smallest kernel size of the C = 64 stage on them
   static constexpr int wino_small = 96;  // workgroups below which conv_wino steps down to 32 x 32 wave tiles
@@ -229,7 +228,6 @@ struct ConvArgs {
   int mt_per_group;     // M tiles (blockIdx.y) per group
   int nsub_group;       // 16-row subtiles per group in the packed weights / bias arrays
   int act;              // 0 none, 1 exact GELU on (conv + bias) before any residual
-  int mfast;            // 1: blockIdx.x walks the M tiles (XCD i keeps M tiles i, i+8, ... of the weights in its L2)
   int xcd;              // 1: 1-D grid in XCD order -- workgroup id i runs on XCD i % 8 and takes M tile (i / 8) % MT of time tile
                         //    i % 8 + 8 * ((i / 8) / MT): the M tiles that read one input window follow each other on ONE XCD (one L2)
   int xcd_ntile, xcd_nb;  // time tiles per utterance / utterances of that enumeration

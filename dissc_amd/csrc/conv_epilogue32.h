@@ -2,12 +2,12 @@
 // the 32x32 MFMA C/D layout -> bias / affine / activation / residual / MRF update -> HBM.
 #pragma once
 #include "common.h"
+#include "ragged_epi.h"
 
 namespace dissc {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 __device__ __forceinline__ float gelu_exact(float v) { return 0.5f * v * (1.f + erf_1ulp(v * 0.70710678118654752440f)); }
 
 // EPI_STORE_ACT: zeros for the columns tcol .. tcol+3 of one row that lie in [olen, olen + ZERO_TAIL) or [ldo - ZERO_TAIL, ldo)
@@ -139,43 +139,9 @@ __device__ __forceinline__ void conv_epilogue32(const ConvArgs& a, f32x16 (&acc)
           continue;
         }
         if (nv >= 4) {
-          if (epi == EPI_STORE) {
-            *reinterpret_cast<f32x4*>(a.out + idx) = v;
-          } else {
-            const f32x4 rs = *reinterpret_cast<const f32x4*>(a.res + idx);
-            v[0] += rs[0]; v[1] += rs[1]; v[2] += rs[2]; v[3] += rs[3];
-            if (epi == EPI_RES) {
-              *reinterpret_cast<f32x4*>(a.out + idx) = v;
-            } else if (epi == EPI_MRF_SET) {
-              *reinterpret_cast<f32x4*>(a.acc + idx) = v;
-            } else {
-              const f32x4 ac = *reinterpret_cast<const f32x4*>(a.acc + idx);
-              v[0] = ac[0] + v[0]; v[1] = ac[1] + v[1]; v[2] = ac[2] + v[2]; v[3] = ac[3] + v[3];
-              if (epi == EPI_MRF_DIV) {
-                v[0] = __fdiv_rn(v[0], a.mrf_div); v[1] = __fdiv_rn(v[1], a.mrf_div);
-                v[2] = __fdiv_rn(v[2], a.mrf_div); v[3] = __fdiv_rn(v[3], a.mrf_div);
-              }
-              *reinterpret_cast<f32x4*>(a.acc + idx) = v;
-            }
-          }
+          epi_store4(epi, a.out, a.acc, a.res, idx, v, a.mrf_div);
         } else {
-          for (int e = 0; e < nv; ++e) {
-            float x = v[e];
-            if (epi == EPI_STORE) {
-              a.out[idx + e] = x;
-            } else {
-              x += a.res[idx + e];
-              if (epi == EPI_RES) {
-                a.out[idx + e] = x;
-              } else if (epi == EPI_MRF_SET) {
-                a.acc[idx + e] = x;
-              } else {
-                x = a.acc[idx + e] + x;
-                if (epi == EPI_MRF_DIV) x = __fdiv_rn(x, a.mrf_div);
-                a.acc[idx + e] = x;
-              }
-            }
-          }
+          for (int e = 0; e < nv; ++e) epi_store1(epi, a.out, a.acc, a.res, idx + e, v[e], a.mrf_div);
         }
       }
     }

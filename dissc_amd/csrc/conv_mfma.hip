@@ -19,10 +19,9 @@
 // Replaces the MIOpen/cuDNN conv1d / conv_transpose1d calls behind reference
 // sr/models.py:34-41 (ResBlock1), :99-102 (conv_pre, ups).
 #include "common.h"
+#include "ragged_epi.h"
 
 namespace dissc {
-
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 __device__ __forceinline__ float gelu_exact(float v) { return 0.5f * v * (1.f + erf_1ulp(v * 0.70710678118654752440f)); }
 
@@ -233,43 +232,9 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_mfma_kernel(const ConvAr
       const size_t idx = ob + (size_t)(grp * a.M + row) * a.ldo + tcol;
       const int nv = olen - tcol;  // >= 1
       if (nv >= 4) {
-        if (epi == EPI_STORE) {
-          *reinterpret_cast<f32x4*>(a.out + idx) = v;
-        } else {
-          const f32x4 rs = *reinterpret_cast<const f32x4*>(a.res + idx);
-          v[0] += rs[0]; v[1] += rs[1]; v[2] += rs[2]; v[3] += rs[3];
-          if (epi == EPI_RES) {
-            *reinterpret_cast<f32x4*>(a.out + idx) = v;
-          } else if (epi == EPI_MRF_SET) {
-            *reinterpret_cast<f32x4*>(a.acc + idx) = v;
-          } else {
-            const f32x4 ac = *reinterpret_cast<const f32x4*>(a.acc + idx);
-            v[0] = ac[0] + v[0]; v[1] = ac[1] + v[1]; v[2] = ac[2] + v[2]; v[3] = ac[3] + v[3];
-            if (epi == EPI_MRF_DIV) {
-              v[0] = __fdiv_rn(v[0], a.mrf_div); v[1] = __fdiv_rn(v[1], a.mrf_div);
-              v[2] = __fdiv_rn(v[2], a.mrf_div); v[3] = __fdiv_rn(v[3], a.mrf_div);
-            }
-            *reinterpret_cast<f32x4*>(a.acc + idx) = v;
-          }
-        }
+        epi_store4(epi, a.out, a.acc, a.res, idx, v, a.mrf_div);
       } else {
-        for (int e = 0; e < nv; ++e) {
-          float x = v[e];
-          if (epi == EPI_STORE) {
-            a.out[idx + e] = x;
-          } else {
-            x += a.res[idx + e];
-            if (epi == EPI_RES) {
-              a.out[idx + e] = x;
-            } else if (epi == EPI_MRF_SET) {
-              a.acc[idx + e] = x;
-            } else {
-              x = a.acc[idx + e] + x;
-              if (epi == EPI_MRF_DIV) x = __fdiv_rn(x, a.mrf_div);
-              a.acc[idx + e] = x;
-            }
-          }
-        }
+        for (int e = 0; e < nv; ++e) epi_store1(epi, a.out, a.acc, a.res, idx + e, v[e], a.mrf_div);
       }
     }
   }
@@ -399,7 +364,6 @@ int launch_conv(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_t 
     return DISSC_EINVAL;
   }
   if (a.m32) return launch_conv32(a, B, Lmax_out, stride, stream);
-  // (the 16x16x4 kernel ignores a.mfast)
   const int cfg = conv_cfg(a.M);
   if (stride == 2 && span <= MAX_TAP_SPAN && a.up == 1) {
     // HuBERT feature convs (512 -> 512, k3/k2 s2): only the 256x64 tile is instantiated

@@ -35,63 +35,8 @@ __global__ void __launch_bounds__(64 * WM * WN, DMA ? DISSC_LB32_DMA : DISSC_LB3
   constexpr int SV = (KCB * (XW_MAX / 4) + NT - 1) / NT;  // float4 staging slots per thread
   extern __shared__ __attribute__((aligned(16))) float xs[];  // 2 x [KCB][XW] | NW x [8][32*NI+4] (epilogue)
 
-  int b = blockIdx.z;
-  int bx = a.mfast ? blockIdx.y : blockIdx.x;  // time tile
-  int by = a.mfast ? blockIdx.x : blockIdx.y;  // (group, M tile)
-  int ntile_g = a.mfast ? gridDim.y : gridDim.x, nb_g = gridDim.z;
-  if (a.xcd) {
-    // XCD order (1-D grid): the hardware deals workgroup ids round-robin over the 8 XCDs, each with its own 4 MB L2.
-    // The ids are cut into SWEEPS over all time tiles, one per group of xcd_mg M tiles (weight slabs that fit the L2
-    // together); inside a sweep the xcd_mg M tiles of one time tile -- which read the same input window -- take
-    // consecutive slots of ONE XCD.  So a window crosses the fabric once per sweep (not once per M tile) and a weight
-    // slab once per XCD (not once per utterance).
-    const int mt = a.mt_per_group * a.groups, mg = a.xcd_mg;
-    const int sweep = blockIdx.x / a.xcd_span, r = blockIdx.x - sweep * a.xcd_span;
-    const int s = r >> 3, sq = s / mg;
-    const int tt = (r & 7) + 8 * sq;
-    by = sweep * mg + (s - sq * mg);
-    ntile_g = a.xcd_ntile;
-    nb_g = a.xcd_nb;
-    if (tt >= ntile_g * nb_g || by >= mt) return;
-    b = tt / ntile_g;
-    bx = tt - b * ntile_g;
-  }
-  if (a.ragged_enum) {
-    // Ragged batch: (time tile, utterance) pairs are re-dealt so that only the tiles that EXIST are enumerated --
-    // utterance 0's ceil(olen_0 / BN) tiles, then utterance 1's, ... -- and the workgroups left over all sit at the END of
-    // the dispatch order (z slowest) and return at once, instead of lying between the real ones (conv_wino.hip has the
-    // measurements).  Every wave finds its pair by a prefix sum of the tile counts over its lanes.  Not for
-    // EPI_STORE_ACT, whose tiles beyond an utterance's end still have zero tails to write.
-    const int ntile = ntile_g;
-    const int lin = b * ntile + bx;
-    const int lane_ = threadIdx.x & 63;
-    const int nb = nb_g;
-    int base = 0;
-    b = -1;
-    for (int b0 = 0; b0 < nb; b0 += 64) {
-      int l = 0;
-      if (b0 + lane_ < nb)
-        l = a.lengths_out ? a.lengths_out[b0 + lane_]
-                          : (a.olen_default >= 0 ? a.olen_default : (a.lengths ? a.lengths[b0 + lane_] * a.len_mul : a.len_default));
-      const int nt = (l + BN - 1) / BN;
-      int incl = nt;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane_ >= o) incl += v;
-      }
-      const int total = __shfl(incl, 63, 64);
-      if (lin < base + total) {
-        const unsigned long long m = __ballot(base + incl > lin);
-        const int lb = __ffsll((long long)m) - 1;
-        b = __builtin_amdgcn_readfirstlane(b0 + lb);
-        bx = __builtin_amdgcn_readfirstlane(lin - base - __shfl(incl - nt, lb, 64));
-        break;
-      }
-      base += total;
-    }
-    if (b < 0) return;
-  }
+  int b, bx, by;
+  if (!conv_tile_of<BN>(a, b, bx, by)) return;
   const int len = (a.lengths ? a.lengths[b] * a.len_mul : a.len_default);  // valid INPUT positions
   const int olen = a.lengths_out ? a.lengths_out[b] : (a.olen_default >= 0 ? a.olen_default : len);
   const int t0 = bx * BN;
@@ -335,7 +280,6 @@ static const TileCfg32 kCfgs32[] = {
 //   fc1 1.217 -> 0.746, qkv 0.752 -> 0.569), time unchanged (27.66 vs 27.66 ms); the generator's few instances: no change
 //   in either (bit 2 stays off).
 // option "xcd_mg" (Options::xcd_mg, default 0 = automatic): M tiles per sweep of that order
-// option "mfast" (Options::mfast, default 0): measured neutral on HuBERT linears (weights are L2/MALL resident either way)
 
 void conv32_set_cfg(int bm_class, int cfg) {
   if (bm_class >= 0 && bm_class < 4 && cfg >= 0 && cfg < 8) g_defaults.cfg32_for_bm[bm_class] = cfg;
@@ -419,15 +363,11 @@ static int launch32_t(ConvArgs a, int B, int Lmax_out, hipStream_t stream) {
   a.mt_per_group = (a.M + BM - 1) / BM;
   // EPI_STORE_ACT writes zero tails up to the end of the output rows: the grid covers ldo, not just the longest utterance
   dim3 grid(((a.epi == EPI_STORE_ACT ? a.ldo : Lmax_out) + BN - 1) / BN, a.mt_per_group * a.groups, B);
-  // Many M tiles (HuBERT's 768..3072-row linears): let blockIdx.x walk them, so that the blocks an
-  // XCD receives (id % 8) share a few M tiles and their weight slices stay L2-resident.
-  a.mfast = (a.mt_per_group * a.groups >= 3 && opts().mfast) ? 1 : 0;
-  if (a.mfast) grid = dim3(grid.y, grid.x, grid.z);
   a.ragged_enum = (opts().ragged_enum && (a.lengths || a.lengths_out) && a.epi != EPI_STORE_ACT && B > 1) ? 1 : 0;
   // option "xcd_order" (Options::xcd_order): bit 0: 1x1 convs (linears), bit 1: stride-2 convs, bit 2: every other
   // instance -- launches with >= 2 M tiles only (with one there is nothing to share)
   const int xcd_bit = (STRIDE == 2) ? 2 : (SPAN == 0 ? 1 : 4);
-  a.xcd = ((opts().xcd_order & xcd_bit) && a.mt_per_group * a.groups >= 2 && !a.mfast) ? 1 : 0;
+  a.xcd = ((opts().xcd_order & xcd_bit) && a.mt_per_group * a.groups >= 2) ? 1 : 0;
   if (a.xcd) {
     // M tiles per sweep: as many 32*MI*WM-row weight slabs as stay L2-resident next to the streamed windows (~3.2 MB of
     // the 4 MB, and a divisor of the M tile count); "xcd_mg" overrides.  Slabs of which fewer than two fit (fc2, K = 3072: 3 MB

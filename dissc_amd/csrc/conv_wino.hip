@@ -126,40 +126,18 @@ __global__ void __launch_bounds__(768, DISSC_WINO_LB) conv_wino_kernel(const Win
   if (lin >= a.gx * a.B) return;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  // lin counts the tiles that EXIST: utterance 0's ceil(len_0 / OT), then utterance 1's, ...  (Enumerating gx tiles for
-  // every utterance and returning from those beyond its end costs 7-9 % on padded or ragged batches: the empty workgroups
-  // sit between the real ones in dispatch order and the real ones land unevenly on the XCDs.)  Every wave finds (b, tile)
-  // by a prefix sum of the tile counts over its lanes.
-  int b = -1, len = a.len_default, t0 = 0;
+  // lin counts the tiles that EXIST (ragged_tile; enumerating gx tiles for every utterance and returning from those beyond
+  // its end costs 7-9 % on padded or ragged batches: the empty workgroups sit between the real ones in dispatch order and
+  // the real ones land unevenly on the XCDs)
+  int b, len = a.len_default, t0;
   if (a.lengths == nullptr) {
     b = lin / a.gx;
     t0 = (lin - b * a.gx) * OT;
     if (t0 >= len) return;
   } else {
-    int base = 0;
-    for (int b0 = 0; b0 < a.B; b0 += 64) {
-      const int l = b0 + lane < a.B ? a.lengths[b0 + lane] * a.len_mul : 0;
-      const int nt = (l + OT - 1) / OT;
-      int incl = nt;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-      }
-      const int total = __shfl(incl, 63, 64);
-      if (lin < base + total) {
-        const unsigned long long m = __ballot(base + incl > lin);
-        const int lb = __ffsll((long long)m) - 1;
-        b = b0 + lb;
-        len = __builtin_amdgcn_readfirstlane(__shfl(l, lb, 64));
-        t0 = (lin - base - __builtin_amdgcn_readfirstlane(__shfl(incl - nt, lb, 64))) * OT;
-        break;
-      }
-      base += total;
-    }
-    if (b < 0) return;
-    b = __builtin_amdgcn_readfirstlane(b);
-    t0 = __builtin_amdgcn_readfirstlane(t0);
+    int tile;
+    if (!ragged_tile<OT>(lin, a.B, [&](int i) { return a.lengths[i] * a.len_mul; }, b, tile, len)) return;
+    t0 = tile * OT;
   }
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = wave % 6;   // this wave's evaluation point
@@ -561,43 +539,10 @@ __global__ void __launch_bounds__(768, DISSC_WINO_LB) conv_wino_kernel(const Win
       }
       const size_t ix = ob + (size_t)grow * a.ldo + n0;
       if (n0 + 4 <= len) {
-        if (epi == EPI_STORE) {
-          *reinterpret_cast<f32x4*>(a.out + ix) = v;
-        } else {
-          const f32x4 rs = pres[it];
-          v[0] += rs[0]; v[1] += rs[1]; v[2] += rs[2]; v[3] += rs[3];
-          if (epi == EPI_RES) {
-            *reinterpret_cast<f32x4*>(a.out + ix) = v;
-          } else if (epi == EPI_MRF_SET) {
-            *reinterpret_cast<f32x4*>(a.acc + ix) = v;
-          } else {
-            const f32x4 ac = *reinterpret_cast<const f32x4*>(a.acc + ix);
-            v[0] = ac[0] + v[0]; v[1] = ac[1] + v[1]; v[2] = ac[2] + v[2]; v[3] = ac[3] + v[3];
-            if (epi == EPI_MRF_DIV) {
-              v[0] = __fdiv_rn(v[0], a.mrf_div); v[1] = __fdiv_rn(v[1], a.mrf_div);
-              v[2] = __fdiv_rn(v[2], a.mrf_div); v[3] = __fdiv_rn(v[3], a.mrf_div);
-            }
-            *reinterpret_cast<f32x4*>(a.acc + ix) = v;
-          }
-        }
+        epi_store(epi, quad_at(a.out + ix), quad_at(a.acc + ix), v, [&] { return pres[it]; },
+                  [&] { return load_quad(a.acc + ix); }, a.mrf_div);
       } else {
-        for (int e = 0; e < len - n0; ++e) {
-          float x = v[e];
-          if (epi == EPI_STORE) {
-            a.out[ix + e] = x;
-          } else {
-            x += a.res[ix + e];
-            if (epi == EPI_RES) {
-              a.out[ix + e] = x;
-            } else if (epi == EPI_MRF_SET) {
-              a.acc[ix + e] = x;
-            } else {
-              x = a.acc[ix + e] + x;
-              if (epi == EPI_MRF_DIV) x = __fdiv_rn(x, a.mrf_div);
-              a.acc[ix + e] = x;
-            }
-          }
-        }
+        for (int e = 0; e < len - n0; ++e) epi_store1(epi, a.out, a.acc, a.res, ix + e, v[e], a.mrf_div);
       }
     }
   }
@@ -613,40 +558,14 @@ bool wino_supported(int Cout, int Cin, int KS, int dil) {
 }
 
 // w: [C][C][KS] -> transform-domain weights U[p][co][ci][j] = sum_i G[p][i] w[co][ci][j + NS i] as a grouped conv tensor
-// [6 C][C][NS] (group = point), packed in A-fragment order for the 32x32x2 kernel
+// [6 C][C][NS] (group = point), packed in A-fragment order for the 32x32x2 kernel (pack_wino_weights)
 int make_wino(const float* w, const float* bias, int C, int KS, int dil, DevConv& dc) {
-  const int NS = (KS + 2) / 3;
-  std::vector<float> wt((size_t)6 * C * C * NS);
-  for (int p = 0; p < 6; ++p)
-    for (int co = 0; co < C; ++co)
-      for (int ci = 0; ci < C; ++ci)
-        for (int j = 0; j < NS; ++j) {
-          double u = 0.0;
-          for (int i = 0; i < 3; ++i) {
-            const int tap = j + NS * i;
-            if (tap < KS) u += kWinoG[p][i] * (double)w[((size_t)co * C + ci) * KS + tap];
-          }
-          wt[(((size_t)p * C + co) * C + ci) * NS + j] = (float)u;
-        }
-  // A-fragment order of the 32x32x2 MFMA, blocks in the order the kernel walks them:
-  // [point][32-row subtile][chunk][half][tap][lane][k-step e]: W[32 ms + (lane & 31)][16 c + 8 half + 2 e + (lane >> 5)][tap]
   if (C % 32 != 0 || C % KC != 0) {
     set_error("make_wino: C = %d is not a multiple of the row tile", C);
     return DISSC_EINVAL;
   }
-  const int nchunk = C / KC, nsub = C / 32;
-  std::vector<float> packed((size_t)6 * nsub * nchunk * 2 * NS * 64 * 4);
-  size_t o = 0;
-  for (int p = 0; p < 6; ++p)
-    for (int ms = 0; ms < nsub; ++ms)
-      for (int c = 0; c < nchunk; ++c)
-        for (int hf = 0; hf < 2; ++hf)
-          for (int j = 0; j < NS; ++j)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int e = 0; e < 4; ++e) {
-                const int co = ms * 32 + (lane & 31), ci = c * KC + 8 * hf + 2 * e + (lane >> 5);
-                packed[o++] = wt[(((size_t)p * C + co) * C + ci) * NS + j];
-              }
+  const int nchunk = C / KC;
+  const std::vector<float> packed = pack_wino_weights(w, C, KS, 6, 3, [](int p, int i) { return kWinoG[p][i]; });
   std::vector<float> b(C, 0.f);
   if (bias) memcpy(b.data(), bias, C * sizeof(float));
   dc.CIN = C; dc.M = C; dc.KS = KS; dc.dil = dil; dc.nchunk = nchunk; dc.up = 1;
@@ -726,8 +645,7 @@ int run_wino(const DevConv& dc, const float* x, float* out, const float* res, fl
   a.x_bstride = (long long)dc.M * ldx; a.o_bstride = (long long)dc.M * ldo;
   a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = opts().kernel_dbg;
   // the window staging, the residual / accumulator reads and the stores are 16-byte accesses
-  auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
-  if (ldx < 4 || ldx % 4 || ldo % 4 || misaligned(x) || misaligned(out) || misaligned(res) || misaligned(acc)) {
+  if (ldx < 4 || ldx % 4 || ldo % 4 || misaligned16(x) || misaligned16(out) || misaligned16(res) || misaligned16(acc)) {
     set_error("run_wino: rows must be 16-byte aligned (ldx %d, ldo %d: multiples of 4 floats, ldx >= 4)", ldx, ldo);
     return DISSC_EINVAL;
   }

@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "conv_epilogue32.h"
+#include "wino_common.h"
 
 namespace dissc {
 
@@ -166,36 +167,15 @@ __global__ void __launch_bounds__(512, (NI == 1 ? 2 : WPS)) conv_wino8_kernel(co
   if (lin >= a.gx * a.B) return;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  int b = -1, len = a.len_default, t0 = 0;
+  int b, len = a.len_default, t0;
   if (a.lengths == nullptr) {
     b = lin / a.gx;
     t0 = (lin - b * a.gx) * OT;
     if (t0 >= len) return;
   } else {  // only the tiles that exist are enumerated (conv_wino.hip)
-    int base = 0;
-    for (int b0 = 0; b0 < a.B; b0 += 64) {
-      const int l = b0 + lane < a.B ? a.lengths[b0 + lane] * a.len_mul : 0;
-      const int nt = (l + OT - 1) / OT;
-      int incl = nt;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-      }
-      const int total = __shfl(incl, 63, 64);
-      if (lin < base + total) {
-        const unsigned long long m = __ballot(base + incl > lin);
-        const int lb = __ffsll((long long)m) - 1;
-        b = b0 + lb;
-        len = __builtin_amdgcn_readfirstlane(__shfl(l, lb, 64));
-        t0 = (lin - base - __builtin_amdgcn_readfirstlane(__shfl(incl - nt, lb, 64))) * OT;
-        break;
-      }
-      base += total;
-    }
-    if (b < 0) return;
-    b = __builtin_amdgcn_readfirstlane(b);
-    t0 = __builtin_amdgcn_readfirstlane(t0);
+    int tile;
+    if (!ragged_tile<OT>(lin, a.B, [&](int i) { return a.lengths[i] * a.len_mul; }, b, tile, len)) return;
+    t0 = tile * OT;
   }
   const int p = __builtin_amdgcn_readfirstlane(tid >> 6);  // this wave's evaluation point
   const int l31 = lane & 31, h = lane >> 5;
@@ -609,25 +589,7 @@ __global__ void __launch_bounds__(512, (NI == 1 ? 2 : WPS)) conv_wino8_kernel(co
       v[0] += bz; v[1] += bz; v[2] += bz; v[3] += bz;
       const size_t ix = ob + (size_t)grow * a.ldo + n0;
       if (hi - lo == 4) {
-        if (epi == EPI_STORE) {
-          *reinterpret_cast<f32x4*>(a.out + ix) = v;
-        } else {
-          const f32x4 rs = pres[it];
-          v[0] += rs[0]; v[1] += rs[1]; v[2] += rs[2]; v[3] += rs[3];
-          if (epi == EPI_RES) {
-            *reinterpret_cast<f32x4*>(a.out + ix) = v;
-          } else if (epi == EPI_MRF_SET) {
-            *reinterpret_cast<f32x4*>(a.acc + ix) = v;
-          } else {
-            const f32x4 ac = pacc[it];
-            v[0] = ac[0] + v[0]; v[1] = ac[1] + v[1]; v[2] = ac[2] + v[2]; v[3] = ac[3] + v[3];
-            if (epi == EPI_MRF_DIV) {
-              v[0] = __fdiv_rn(v[0], a.mrf_div); v[1] = __fdiv_rn(v[1], a.mrf_div);
-              v[2] = __fdiv_rn(v[2], a.mrf_div); v[3] = __fdiv_rn(v[3], a.mrf_div);
-            }
-            *reinterpret_cast<f32x4*>(a.acc + ix) = v;
-          }
-        }
+        epi_store(epi, quad_at(a.out + ix), quad_at(a.acc + ix), v, [&] { return pres[it]; }, [&] { return pacc[it]; }, a.mrf_div);
       } else {
         // a quad shared with the neighbouring tile, or cut by the utterance's end: element by element -- every load first (loaded
         // inside the store loop, an element's residual could not be hoisted over the previous element's store: up to three
@@ -642,21 +604,7 @@ __global__ void __launch_bounds__(512, (NI == 1 ? 2 : WPS)) conv_wino8_kernel(co
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           if (n0 + e < lo || n0 + e >= hi) continue;
-          float x = v[e];
-          if (epi == EPI_STORE) {
-            a.out[ix + e] = x;
-          } else {
-            x += rr[e];
-            if (epi == EPI_RES) {
-              a.out[ix + e] = x;
-            } else if (epi == EPI_MRF_SET) {
-              a.acc[ix + e] = x;
-            } else {
-              x = aa[e] + x;
-              if (epi == EPI_MRF_DIV) x = __fdiv_rn(x, a.mrf_div);
-              a.acc[ix + e] = x;
-            }
-          }
+          epi_store(epi, a.out + ix + e, a.acc + ix + e, v[e], [&] { return rr[e]; }, [&] { return aa[e]; }, a.mrf_div);
         }
       }
     }
@@ -674,36 +622,19 @@ bool wino8_supported(int Cout, int Cin, int KS, int dil) {
 
 bool wino8_r4_supported(int C, int KS, int dil) { return wino8_supported(C, C, KS, dil) && (KS == 7 || KS == 11); }
 
-// w: [C][C][KS] -> U[p][co][ci][j] = sum_i G[p][i] w[co][ci][j + NS i], packed in A-fragment order (make_wino's, 8 points);
+// w: [C][C][KS] -> U[p][co][ci][j] = sum_i G[p][i] w[co][ci][j + NS i], packed in A-fragment order (pack_wino_weights, 8 points);
 // R = taps per sub-filter (3: F(6,3), 4: F(5,4)), NS = ceil(KS / R)
 int make_wino8(const float* w, const float* bias, int C, int KS, int dil, DevConv& dc, int R) {
   if (R != 3 && !(R == 4 && wino8_r4_supported(C, KS, dil))) {
     set_error("make_wino8: no instance with %d-tap sub-filters for C = %d, k = %d, dilation %d", R, C, KS, dil);
     return DISSC_EINVAL;
   }
-  const int NS = (KS + R - 1) / R;
   if (C % 32 != 0 || C % KC != 0) {
     set_error("make_wino8: C = %d is not a multiple of the row tile", C);
     return DISSC_EINVAL;
   }
-  const int nchunk = C / KC, nsub = C / 32;
-  std::vector<float> packed((size_t)8 * nsub * nchunk * 2 * NS * 64 * 4);
-  size_t o = 0;
-  for (int p = 0; p < 8; ++p)
-    for (int ms = 0; ms < nsub; ++ms)
-      for (int c = 0; c < nchunk; ++c)
-        for (int hf = 0; hf < 2; ++hf)
-          for (int j = 0; j < NS; ++j)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int e = 0; e < 4; ++e) {
-                const int co = ms * 32 + (lane & 31), ci = c * KC + 8 * hf + 2 * e + (lane >> 5);
-                double u = 0.0;
-                for (int i = 0; i < R; ++i) {
-                  const int tap = j + NS * i;
-                  if (tap < KS) u += w8_g(p, i, R) * (double)w[((size_t)co * C + ci) * KS + tap];
-                }
-                packed[o++] = (float)u;
-              }
+  const int nchunk = C / KC;
+  const std::vector<float> packed = pack_wino_weights(w, C, KS, 8, R, [R](int p, int i) { return w8_g(p, i, R); });
   std::vector<float> b(C, 0.f);
   if (bias) memcpy(b.data(), bias, C * sizeof(float));
   dc.CIN = C; dc.M = C; dc.KS = KS; dc.dil = dil; dc.nchunk = nchunk; dc.up = 1;
@@ -754,8 +685,7 @@ int run_wino8(const DevConv& dc, const float* x, float* out, const float* res, f
   a.x_bstride = (long long)dc.M * ldx; a.o_bstride = (long long)dc.M * ldo;
   a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = opts().kernel_dbg;
   a.gx = a.gy = a.B = 0;
-  auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
-  if (ldx < 4 || ldx % 4 || ldo % 4 || misaligned(x) || misaligned(out) || misaligned(res) || misaligned(acc)) {
+  if (ldx < 4 || ldx % 4 || ldo % 4 || misaligned16(x) || misaligned16(out) || misaligned16(res) || misaligned16(acc)) {
     set_error("run_wino8: rows must be 16-byte aligned (ldx %d, ldo %d: multiples of 4 floats, ldx >= 4)", ldx, ldo);
     return DISSC_EINVAL;
   }

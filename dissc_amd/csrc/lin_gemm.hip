@@ -130,61 +130,6 @@ __device__ __forceinline__ void lin128_store(const ConvArgs& a, f32x16 (&acc)[MI
 #undef DISSC_LIN128_EPI
 }
 
-// Which tile is this workgroup's?  XCD order and ragged enumeration as in conv_mfma32_kernel (conv_mfma32.hip has the descriptions).
-// false: nothing to do.
-__device__ __forceinline__ bool tile128_of(const ConvArgs& a, int& b, int& bx, int& by) {
-  constexpr int BN = 128;
-  b = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
-  int ntile_g = gridDim.x, nb_g = gridDim.z;
-  if (a.xcd) {
-    const int mt = a.mt_per_group, mg = a.xcd_mg;
-    const int sweep = blockIdx.x / a.xcd_span, r = blockIdx.x - sweep * a.xcd_span;
-    const int s = r >> 3, sq = s / mg;
-    const int tt = (r & 7) + 8 * sq;
-    by = sweep * mg + (s - sq * mg);
-    ntile_g = a.xcd_ntile;
-    nb_g = a.xcd_nb;
-    if (tt >= ntile_g * nb_g || by >= mt) return false;
-    b = tt / ntile_g;
-    bx = tt - b * ntile_g;
-  }
-  if (a.ragged_enum) {
-    const int lin = b * ntile_g + bx;
-    const int lane_ = threadIdx.x & 63;
-    int base = 0;
-    b = -1;
-    for (int b0 = 0; b0 < nb_g; b0 += 64) {
-      int l = 0;
-      if (b0 + lane_ < nb_g)
-        l = a.lengths_out ? a.lengths_out[b0 + lane_]
-                          : (a.olen_default >= 0 ? a.olen_default : (a.lengths ? a.lengths[b0 + lane_] * a.len_mul : a.len_default));
-      const int nt = (l + BN - 1) / BN;
-      int incl = nt;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane_ >= o) incl += v;
-      }
-      const int total = __shfl(incl, 63, 64);
-      if (lin < base + total) {
-        const unsigned long long m = __ballot(base + incl > lin);
-        const int lb = __ffsll((long long)m) - 1;
-        b = __builtin_amdgcn_readfirstlane(b0 + lb);
-        bx = __builtin_amdgcn_readfirstlane(lin - base - __shfl(incl - nt, lb, 64));
-        break;
-      }
-      base += total;
-    }
-    if (b < 0) return false;
-  }
-  // wave-uniform by construction; say so (the ragged search's __shfl results look divergent to the compiler, and with them every
-  // address derived from the tile: 64-bit per-lane address math instead of scalar bases)
-  b = __builtin_amdgcn_readfirstlane(b);
-  bx = __builtin_amdgcn_readfirstlane(bx);
-  by = __builtin_amdgcn_readfirstlane(by);
-  return true;
-}
-
 // DBG (diagnostics, option "kernel_dbg"): bit 3: no epilogue, bit 5: timeline stamps into a.acc (the knock-outs of the first,
 // compiler-scheduled form -- A loads 5.7 %, epilogue 8 %, barrier 3 % of fc1 -- are on record in profiles/r06/lin128_gate_v3.txt)
 template <int MI, int KCB, int WGPC, int DBG = 0>
@@ -195,7 +140,7 @@ __global__ void __launch_bounds__(256, WGPC) lin128_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // 2 x [KCB][128]
 
   int b, bx, by;
-  if (!tile128_of(a, b, bx, by)) return;
+  if (!conv_tile_of<128>(a, b, bx, by)) return;
   unsigned long long* tl = nullptr;  // DBG bit 5: 100 MHz wall-clock stamps of wave 0 (start, loop start, loop end, stores issued) + placement
   if constexpr ((DBG & 32) != 0) {
     const unsigned id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
@@ -368,7 +313,6 @@ static int launch_lin128_t(ConvArgs a, int B, int Lmax_out, hipStream_t stream) 
   constexpr int BM = 128 * MI, BN = 128;
   a.mt_per_group = (a.M + BM - 1) / BM;
   dim3 grid((Lmax_out + BN - 1) / BN, a.mt_per_group, B);
-  a.mfast = 0;
   a.ragged_enum = (opts().ragged_enum && (a.lengths || a.lengths_out) && B > 1) ? 1 : 0;
   const int mt = a.mt_per_group;
   const long long tt_pad = ((long long)grid.x * B + 7) / 8 * 8;
@@ -459,7 +403,7 @@ __global__ void __launch_bounds__(256, WGPC) conv2s128_kernel(const ConvArgs a) 
   static_assert(G == 6 && KCB % 16 == 0, "k = 3 only");
 
   int b, bx, by;
-  if (!tile128_of(a, b, bx, by)) return;
+  if (!conv_tile_of<128>(a, b, bx, by)) return;
   unsigned long long* tl = nullptr;
   if constexpr ((DBG & 32) != 0) {
     const unsigned id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
@@ -683,7 +627,6 @@ static int launch_conv2s128_t(ConvArgs a, int B, int Lmax_out, hipStream_t strea
   constexpr int BM = 128 * MI, BN = 128;
   a.mt_per_group = a.M / BM;
   dim3 grid((Lmax_out + BN - 1) / BN, a.mt_per_group, B);
-  a.mfast = 0;
   a.ragged_enum = (opts().ragged_enum && a.lengths_out && B > 1) ? 1 : 0;
   const int mt = a.mt_per_group;
   const long long tt_pad = ((long long)grid.x * B + 7) / 8 * 8;

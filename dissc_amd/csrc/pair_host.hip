@@ -58,8 +58,7 @@ void free_pairw(DevPairW& pw) {
 
 int launch_respair_wino(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
                         int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream) {
-  auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
-  if (!pw.w1 || epi == EPI_STORE || x == out || ld < 4 || ld % 4 || misaligned(x) || misaligned(out) || misaligned(acc) ||
+  if (!pw.w1 || epi == EPI_STORE || x == out || ld < 4 || ld % 4 || misaligned16(x) || misaligned16(out) || misaligned16(acc) ||
       B <= 0 || Lmax <= 0) {
     set_error("launch_respair_wino: bad argument (C=%d k=%d d=%d ld=%d epi=%d)", pw.C, pw.KS, pw.dil, ld, epi);
     return DISSC_EINVAL;

@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "ragged_epi.h"
 
 namespace dissc {
 
@@ -44,8 +45,6 @@ struct ResblockBf3Args {
   int epi;               // EPI_MRF_SET / EPI_MRF_ADD / EPI_MRF_DIV, or EPI_STORE: acc = x_k (a partial block)
   int m0, m1;            // residual pairs [m0, m1) of the block's three run in this launch
 };
-
-__device__ __forceinline__ float lrelu_b(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // C = 16: K = 32 of one MFMA holds TWO taps x 16 channels (lane group g = l >> 4: tap 2s + (g >> 1),
 //         channels 8 (g & 1) .. +7; an odd tap count is padded with a zero-weight tap); all weight
@@ -149,7 +148,7 @@ __global__ void __launch_bounds__(64 * NW) resblock_bf3_kernel(const ResblockBf3
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         xk[mi][ni][r] = S[(16 * mi + 4 * g + r) * XW + PAD + u];
-        av[r] = lrelu_b(xk[mi][ni][r], slope);
+        av[r] = lrelu(xk[mi][ni][r], slope);
       }
       publish(Ap, mi, u, av);
     }
@@ -241,7 +240,7 @@ __global__ void __launch_bounds__(64 * NW) resblock_bf3_kernel(const ResblockBf3
           for (int mi = 0; mi < MI; ++mi) {
             float v[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = inside ? lrelu_b(acc[tb][mi][ni][r] + bz[mi][r], slope) : 0.f;
+            for (int r = 0; r < 4; ++r) v[r] = inside ? lrelu(acc[tb][mi][ni][r] + bz[mi][r], slope) : 0.f;
             publish(Tp, mi, u, v);
           }
         }
@@ -272,7 +271,7 @@ __global__ void __launch_bounds__(64 * NW) resblock_bf3_kernel(const ResblockBf3
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               xk[mi][nn][r] = inside ? xk[mi][nn][r] + (acc[tb][mi][ni][r] + bz[mi][r]) : 0.f;
-              v[r] = lrelu_b(xk[mi][nn][r], slope);
+              v[r] = lrelu(xk[mi][nn][r], slope);
             }
             if (m + 1 < a.m1) publish(Ap, mi, u, v);
           }
@@ -293,7 +292,7 @@ __global__ void __launch_bounds__(64 * NW) resblock_bf3_kernel(const ResblockBf3
   __syncthreads();
   {
     const int nv = a.BN >> 2;
-    const bool rmw = a.epi == EPI_MRF_ADD || a.epi == EPI_MRF_DIV;
+    const bool rmw = epi_rmw(a.epi);
     float* ab = a.acc + (size_t)b * a.bstride;
     for (int e = tid; e < C * nv; e += NT) {
       const int r = e / nv, v4 = e - r * nv;
@@ -303,24 +302,10 @@ __global__ void __launch_bounds__(64 * NW) resblock_bf3_kernel(const ResblockBf3
       float* dst = ab + (size_t)r * a.ld + t;
       const int nval = len - t;
       if (nval >= 4) {
-        if (rmw) {
-          const f32x4 o = *reinterpret_cast<const f32x4*>(dst);
-          v[0] = o[0] + v[0]; v[1] = o[1] + v[1]; v[2] = o[2] + v[2]; v[3] = o[3] + v[3];
-          if (a.epi == EPI_MRF_DIV) {
-            v[0] = __fdiv_rn(v[0], a.mrf_div); v[1] = __fdiv_rn(v[1], a.mrf_div);
-            v[2] = __fdiv_rn(v[2], a.mrf_div); v[3] = __fdiv_rn(v[3], a.mrf_div);
-          }
-        }
-        *reinterpret_cast<f32x4*>(dst) = v;
+        if (rmw) v = epi_mrf(a.epi, v, load_quad(dst), a.mrf_div);
+        *quad_at(dst) = v;
       } else {
-        for (int k = 0; k < nval; ++k) {
-          float x = v[k];
-          if (rmw) {
-            x = dst[k] + x;
-            if (a.epi == EPI_MRF_DIV) x = __fdiv_rn(x, a.mrf_div);
-          }
-          dst[k] = x;
-        }
+        for (int k = 0; k < nval; ++k) dst[k] = rmw ? epi_mrf(a.epi, v[k], dst[k], a.mrf_div) : v[k];
       }
     }
   }

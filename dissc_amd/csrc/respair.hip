@@ -23,6 +23,7 @@
 // 4-channel k-steps inner, bias / residual / MRF in the same order), so results are identical to the
 // two-launch path; tests/test_gpu_generator.py holds the two against each other bitwise.
 #include "common.h"
+#include "ragged_epi.h"
 
 namespace dissc {
 
@@ -42,82 +43,32 @@ struct PairArgs {
   int epi;
 };
 
-__device__ __forceinline__ float lrelu_p(float v, float slope) { return v > 0.f ? v : v * slope; }
-constexpr int round32_16(int n) { return (n - 16 + 31) / 32 * 32 + 16; }  // smallest v >= n with v % 32 == 16
-
-// rows of the 16 B-per-lane epilogue: v = conv + bias (+ residual) -> out / MRF accumulate
+// rows of the 16 B-per-lane epilogue: v = conv + bias, rv = the residual -> out / MRF accumulate
 __device__ __forceinline__ void pair_store4(const PairArgs& a, size_t idx, f32x4 v, const f32x4& rv, int nv) {
-  const int epi = a.epi;
   if (nv >= 4) {
-    v[0] += rv[0]; v[1] += rv[1]; v[2] += rv[2]; v[3] += rv[3];
-    if (epi == EPI_RES) {
-      *reinterpret_cast<f32x4*>(a.out + idx) = v;
-    } else if (epi == EPI_MRF_SET) {
-      *reinterpret_cast<f32x4*>(a.acc + idx) = v;
-    } else {
-      const f32x4 ac = *reinterpret_cast<const f32x4*>(a.acc + idx);
-      v[0] = ac[0] + v[0]; v[1] = ac[1] + v[1]; v[2] = ac[2] + v[2]; v[3] = ac[3] + v[3];
-      if (epi == EPI_MRF_DIV) {
-        v[0] = __fdiv_rn(v[0], a.mrf_div); v[1] = __fdiv_rn(v[1], a.mrf_div);
-        v[2] = __fdiv_rn(v[2], a.mrf_div); v[3] = __fdiv_rn(v[3], a.mrf_div);
-      }
-      *reinterpret_cast<f32x4*>(a.acc + idx) = v;
-    }
+    epi_store_res(a.epi, quad_at(a.out + idx), quad_at(a.acc + idx), epi_plus(v, rv), [&] { return load_quad(a.acc + idx); },
+                  a.mrf_div);
   } else {
-    for (int e = 0; e < nv; ++e) {
-      float x = v[e] + rv[e];
-      if (epi == EPI_RES) {
-        a.out[idx + e] = x;
-      } else if (epi == EPI_MRF_SET) {
-        a.acc[idx + e] = x;
-      } else {
-        x = a.acc[idx + e] + x;
-        if (epi == EPI_MRF_DIV) x = __fdiv_rn(x, a.mrf_div);
-        a.acc[idx + e] = x;
-      }
-    }
+    for (int e = 0; e < nv; ++e)
+      epi_store_res(a.epi, a.out + idx + e, a.acc + idx + e, v[e] + rv[e], [&] { return a.acc[idx + e]; }, a.mrf_div);
   }
 }
 
-
-// (b, first output column) of workgroup `lin` when only the tiles that EXIST are enumerated: utterance 0's
-// ceil(len_0 / WOUT) tiles, then utterance 1's, ...  The grid still holds gridDim.x tiles for each of the B utterances;
-// the workgroups beyond the last real tile all sit at the END of the dispatch order and return at once -- enumerating
-// (tile, utterance) pairs and returning from the tiles beyond an utterance's end leaves the empty workgroups between the
-// real ones (7-9 % on ragged batches for conv_wino_kernel, +0.65 ms per ragged forward for these stages).  Every wave
-// finds its pair by a prefix sum of the tile counts over its lanes (the scheme of conv_wino.hip).
+// (b, len, first output column) of workgroup (blockIdx.x: tile, blockIdx.y: utterance); with lengths only the tiles that
+// EXIST are enumerated (ragged_tile)
 template <int WOUT>
 __device__ __forceinline__ bool pair_tile(const PairArgs& a, int B, int& b, int& len, int& o0) {
-  const int lin = blockIdx.y * gridDim.x + blockIdx.x;
   if (a.lengths == nullptr) {
     b = blockIdx.y;
     len = a.len_default;
     o0 = blockIdx.x * WOUT;
     return o0 < len;
   }
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  for (int b0 = 0; b0 < B; b0 += 64) {
-    const int l = b0 + lane < B ? a.lengths[b0 + lane] * a.len_mul : 0;
-    const int nt = (l + WOUT - 1) / WOUT;
-    int incl = nt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += v;
-    }
-    const int total = __shfl(incl, 63, 64);
-    if (lin < base + total) {
-      const unsigned long long m = __ballot(base + incl > lin);
-      const int lb = __ffsll((long long)m) - 1;
-      b = __builtin_amdgcn_readfirstlane(b0 + lb);
-      len = __builtin_amdgcn_readfirstlane(__shfl(l, lb, 64));
-      o0 = __builtin_amdgcn_readfirstlane((lin - base - __shfl(incl - nt, lb, 64)) * WOUT);
-      return true;
-    }
-    base += total;
-  }
-  return false;
+  int tile;
+  if (!ragged_tile<WOUT>(blockIdx.y * gridDim.x + blockIdx.x, B, [&](int i) { return a.lengths[i] * a.len_mul; }, b, tile, len))
+    return false;
+  o0 = tile * WOUT;
+  return true;
 }
 
 // ---- C = 16: v_mfma_f32_16x16x4_f32, both convs' weights in registers -------------------------
@@ -176,7 +127,7 @@ __global__ void __launch_bounds__(256) respair16_kernel(const PairArgs a) {
         const int t = tb + 4 * vv;
         f32x4 val = sv[i];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? lrelu_p(val[e], slope) : 0.f;
+        for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? lrelu(val[e], slope) : 0.f;
         *reinterpret_cast<f32x4*>(Xs + rr * XW1 + 4 * vv) = val;
       }
       vv += dv; rr += dr;
@@ -215,7 +166,7 @@ __global__ void __launch_bounds__(256) respair16_kernel(const PairArgs a) {
     const bool inside = t >= 0 && t < len;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float v = lrelu_p(acc[ni][r] + bias1[r], slope);
+      const float v = lrelu(acc[ni][r] + bias1[r], slope);
       Ts[(4 * g + r) * XW2 + u] = inside ? v : 0.f;
     }
   }
@@ -337,7 +288,7 @@ __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
           const int t = tb + 4 * vv;
           f32x4 val = sv[i];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? lrelu_p(val[e], slope) : 0.f;
+          for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? lrelu(val[e], slope) : 0.f;
           *reinterpret_cast<f32x4*>(Xs + rr * XW1 + 4 * vv) = val;
         }
         vv += dv; rr += dr;
@@ -388,7 +339,7 @@ __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-      const float v = lrelu_p(acc[ni][r] + a.b1[row], slope);
+      const float v = lrelu(acc[ni][r] + a.b1[row], slope);
       Ts[row * XW2 + u] = inside ? v : 0.f;
     }
   }

@@ -35,8 +35,8 @@ struct F23Geo {
   static constexpr int NU2 = NCOLS / D2, NC2 = NU2 * D2, W2 = 2 * NC2;  // outputs conv_1 computes: [o0, o0 + W2)
   static constexpr int WOUT = ((W1 - 2 * P2) < W2 ? (W1 - 2 * P2) : W2) & ~3;  // outputs a workgroup owns
   static constexpr int REACH1 = (3 * NS - 1) * DIL, REACH2 = 3 * NS - 1;       // samples read beyond the last column's first
-  static constexpr int XW1 = f23_round32_16(3 + W1 + REACH1);
-  static constexpr int XW2 = f23_round32_16(W2 + REACH2 + 1);
+  static constexpr int XW1 = round32_16(3 + W1 + REACH1);
+  static constexpr int XW2 = round32_16(W2 + REACH2 + 1);
   static constexpr int XW = XW1 > XW2 ? XW1 : XW2;  // row stride of the one LDS buffer (x window, then T, then the patches)
   static constexpr int PW = 128 + 4;                // patch row: a wave's 128 outputs
   static_assert(NW * 8 * PW <= C * XW, "the epilogue patches fit the buffer");
@@ -241,32 +241,10 @@ __global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairFArgs a
         const f32x4 r4 = rv[p];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (v[e] + bz) + r4[e];
-        if (epi == EPI_RES) {
-          *reinterpret_cast<f32x4*>(a.out + idx) = v;
-        } else if (epi == EPI_MRF_SET) {
-          *reinterpret_cast<f32x4*>(a.acc + idx) = v;
-        } else {
-          const f32x4 ac = pa[p];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[e] = ac[e] + v[e];
-            if (epi == EPI_MRF_DIV) v[e] = __fdiv_rn(v[e], a.mrf_div);
-          }
-          *reinterpret_cast<f32x4*>(a.acc + idx) = v;
-        }
+        epi_store_res(epi, quad_at(a.out + idx), quad_at(a.acc + idx), v, [&] { return pa[p]; }, a.mrf_div);
       } else {
-        for (int e = 0; e < nv; ++e) {
-          float x = (v[e] + bz) + a.x[idx + e];
-          if (epi == EPI_RES) {
-            a.out[idx + e] = x;
-          } else if (epi == EPI_MRF_SET) {
-            a.acc[idx + e] = x;
-          } else {
-            x = a.acc[idx + e] + x;
-            if (epi == EPI_MRF_DIV) x = __fdiv_rn(x, a.mrf_div);
-            a.acc[idx + e] = x;
-          }
-        }
+        for (int e = 0; e < nv; ++e)
+          epi_store_res(epi, a.out + idx + e, a.acc + idx + e, (v[e] + bz) + a.x[idx + e], [&] { return a.acc[idx + e]; }, a.mrf_div);
       }
     }
   }
@@ -284,7 +262,6 @@ bool pair_f23_supported(int C, int KS, int dil) {
 // w: [32][32][11] -> U_p[co][ci][j] = sum_i G[p][i] w[co][ci][j + 4 i] in A-fragment order [chunk][sub-filter][point][half][lane][4]
 int pack_pair_f23(const float* w, float** dev, int C_, int KS) {
   if (C_ == 16) return pack_pair16_f23(w, dev, KS);
-  static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
   constexpr int C = 32;
   const int NS = (KS + 2) / 3;
   std::vector<float> packed((size_t)2 * NS * 4 * 2 * 64 * 4);
@@ -299,7 +276,7 @@ int pack_pair_f23(const float* w, float** dev, int C_, int KS) {
               double u = 0.0;
               for (int i = 0; i < 3; ++i) {
                 const int tap = j + NS * i;
-                if (tap < KS) u += G[p][i] * (double)w[((size_t)co * C + ci) * KS + tap];
+                if (tap < KS) u += kF23G[p][i] * (double)w[((size_t)co * C + ci) * KS + tap];
               }
               packed[o++] = (float)u;
             }

@@ -33,4 +33,31 @@ __device__ __forceinline__ float wino_bt(float r0, float r1, float r2, float r3,
   return 0.f;
 }
 
+// w: [C][C][KS] -> transform-domain weights U[p][co][ci][j] = sum_i g(p, i) w[co][ci][j + NS i] (double, rounded to float) for
+// NP points and R taps per sub-filter (NS = ceil(KS / R)), packed in the A-fragment order of the 32x32x2 MFMA, blocks in the
+// order the kernels walk them: [point][32-row subtile][chunk][half][j][lane][k-step e]:
+// U_p[32 ms + (lane & 31)][16 c + 8 half + 2 e + (lane >> 5)][j].  C: a multiple of 32.
+template <class GF>
+std::vector<float> pack_wino_weights(const float* w, int C, int KS, int NP, int R, GF g) {
+  const int NS = (KS + R - 1) / R, nchunk = C / KC, nsub = C / 32;
+  std::vector<float> packed((size_t)NP * nsub * nchunk * 2 * NS * 64 * 4);
+  size_t o = 0;
+  for (int p = 0; p < NP; ++p)
+    for (int ms = 0; ms < nsub; ++ms)
+      for (int c = 0; c < nchunk; ++c)
+        for (int hf = 0; hf < 2; ++hf)
+          for (int j = 0; j < NS; ++j)
+            for (int lane = 0; lane < 64; ++lane)
+              for (int e = 0; e < 4; ++e) {
+                const int co = ms * 32 + (lane & 31), ci = c * KC + 8 * hf + 2 * e + (lane >> 5);
+                double u = 0.0;
+                for (int i = 0; i < R; ++i) {
+                  const int tap = j + NS * i;
+                  if (tap < KS) u += g(p, i) * (double)w[((size_t)co * C + ci) * KS + tap];
+                }
+                packed[o++] = (float)u;
+              }
+  return packed;
+}
+
 }  // namespace dissc

@@ -431,8 +431,7 @@ static int launch_s2tc_t(const S2tcArgs& a, long long nwg, hipStream_t stream) {
 
 int run_s2tc(const DevS2tc& dc, const float* x, float* out, const int32_t* lengths_in, const int32_t* lengths_out,
              int len_default, int olen_default, int B, int ldx, int ldo, int Lmax_out, hipStream_t stream) {
-  auto misaligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
-  if (B <= 0 || Lmax_out <= 0 || !dc.wpack || ldx < 4 || ldx % 4 || ldo % 4 || misaligned(x) || misaligned(out)) {
+  if (B <= 0 || Lmax_out <= 0 || !dc.wpack || ldx < 4 || ldx % 4 || ldo % 4 || misaligned16(x) || misaligned16(out)) {
     set_error("run_s2tc: bad call (B %d, Lmax_out %d, ldx %d, ldo %d: rows must be 16-byte aligned)", B, Lmax_out, ldx, ldo);
     return DISSC_EINVAL;
   }

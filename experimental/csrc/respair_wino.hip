@@ -143,28 +143,10 @@ __global__ void __launch_bounds__(384 * CHV, 3) respair_wino_kernel(const PairWA
       to0 = (lin - tb_ * a.gx) * G::OT;
       return tb_ < a.B && to0 < tlen;
     }
-    int base = 0;
-    for (int b0 = 0; b0 < a.B; b0 += 64) {
-      const int l = b0 + lane < a.B ? a.lengths[b0 + lane] * a.len_mul : 0;
-      const int nt = (l + G::OT - 1) / G::OT;
-      int incl = nt;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-      }
-      const int total = __shfl(incl, 63, 64);
-      if (lin < base + total) {
-        const unsigned long long m = __ballot(base + incl > lin);
-        const int lb = __ffsll((long long)m) - 1;
-        tb_ = __builtin_amdgcn_readfirstlane(b0 + lb);
-        tlen = __builtin_amdgcn_readfirstlane(__shfl(l, lb, 64));
-        to0 = __builtin_amdgcn_readfirstlane((lin - base - __shfl(incl - nt, lb, 64)) * G::OT);
-        return true;
-      }
-      base += total;
-    }
-    return false;
+    int tile;
+    if (!ragged_tile<G::OT>(lin, a.B, [&](int i) { return a.lengths[i] * a.len_mul; }, tb_, tile, tlen)) return false;
+    to0 = tile * G::OT;
+    return true;
   };
   const int lin = blockIdx.x;
   int b, len, o0;
@@ -524,34 +506,11 @@ __global__ void __launch_bounds__(384 * CHV, 3) respair_wino_kernel(const PairWA
         v[0] += bz; v[1] += bz; v[2] += bz; v[3] += bz;
         const size_t ix = ob + (size_t)row * a.ld + n0;
         if (n0 + 4 <= len) {
-          const f32x4 rs = pres[it];
-          v[0] += rs[0]; v[1] += rs[1]; v[2] += rs[2]; v[3] += rs[3];
-          if (epi == EPI_RES) {
-            *reinterpret_cast<f32x4*>(a.out + ix) = v;
-          } else if (epi == EPI_MRF_SET) {
-            *reinterpret_cast<f32x4*>(a.acc + ix) = v;
-          } else {
-            const f32x4 ac = *reinterpret_cast<const f32x4*>(a.acc + ix);
-            v[0] = ac[0] + v[0]; v[1] = ac[1] + v[1]; v[2] = ac[2] + v[2]; v[3] = ac[3] + v[3];
-            if (epi == EPI_MRF_DIV) {
-              v[0] = __fdiv_rn(v[0], a.mrf_div); v[1] = __fdiv_rn(v[1], a.mrf_div);
-              v[2] = __fdiv_rn(v[2], a.mrf_div); v[3] = __fdiv_rn(v[3], a.mrf_div);
-            }
-            *reinterpret_cast<f32x4*>(a.acc + ix) = v;
-          }
+          epi_store_res(epi, quad_at(a.out + ix), quad_at(a.acc + ix), epi_plus(v, pres[it]), [&] { return load_quad(a.acc + ix); },
+                        a.mrf_div);
         } else {
-          for (int e = 0; e < len - n0; ++e) {
-            float x = v[e] + a.x[ix + e];
-            if (epi == EPI_RES) {
-              a.out[ix + e] = x;
-            } else if (epi == EPI_MRF_SET) {
-              a.acc[ix + e] = x;
-            } else {
-              x = a.acc[ix + e] + x;
-              if (epi == EPI_MRF_DIV) x = __fdiv_rn(x, a.mrf_div);
-              a.acc[ix + e] = x;
-            }
-          }
+          for (int e = 0; e < len - n0; ++e)
+            epi_store_res(epi, a.out + ix + e, a.acc + ix + e, v[e] + a.x[ix + e], [&] { return a.acc[ix + e]; }, a.mrf_div);
         }
       }
     }
