@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(256) attn_fused_kernel(const float* __restrict
   }
 }
 
-// option "xcd_order" bit 3 (Options::xcd_order): the 1-D grid in XCD order (see the kernel)
+// option "xcd_order" bit 3: the 1-D grid in XCD order (see the kernel)
 int launch_attn_fused(const float* qkv, const int32_t* lens, int D, int hd, int ld, float* out, int T, int H, int B, hipStream_t st) {
   if (hd != 64 || T <= 0 || B <= 0 || H <= 0) {
     set_error("launch_attn_fused: head dimension %d (64 only), T %d, H %d, B %d", hd, T, H, B);

@@ -72,26 +72,6 @@ struct Options {
   DISSC_OPTION_LIST_EXPERIMENTAL(DISSC_OPT_CONST)
 #undef DISSC_OPT_CONST
 #endif
-  // Settled choices that were run-time options through round 5 (every one measured, the records are under profiles/): constants now,
-  // so that code paths stay readable where they are used (`opts().x`) without being part of the tuning surface.
-  static constexpr int stream_prio = 1;  // generator streams of the k = 7 / 11 chains at higher priority
-  static constexpr int par_ups = 1;  // the phase groups of a ConvTranspose on parallel streams
-  static constexpr int pos48 = 1;  // HuBERT's positional conv (48 rows per group) as three 16-row tiles of the 16x16x4 kernel
-  static constexpr int lin_tile = 2;  // channels per barrier / 16 of the register-staged 1x1 convs
-  static constexpr int cpb2 = 0;  // two chunks per barrier for short kernels
-  static constexpr int lin_dma = 1;  // 1x1 convs of the 256 x 64 kernel stage their window with global_load_lds
-  static constexpr int conv_pad_lds = 0;  // extra LDS bytes per workgroup (occupancy experiments)
-  static constexpr int c64_wide = 1;  // 64 x 256 tile for the DMA-staged second convs of the C = 64 stage
-  static constexpr int conv2_dma = 1;  // stride-2 valid convs of the 256 x 64 kernel stage by global_load_lds
-  static constexpr int wino_min_c = 64;  // narrowest stage on the transform-domain kernels
-  static constexpr int wino_c64_kmin = 3;  // smallest kernel size of the C = 64 stage on them
-  static constexpr int wino_small = 96;  // workgroups below which conv_wino steps down to 32 x 32 wave tiles
-  static constexpr int wino_cpr = 32;  // channels per barrier round of conv_wino
-  static constexpr int attn_fused = 1;  // one fused attention kernel per layer
-  static constexpr int bf3_variant = 0;  // split-bf16 fused-block variant
-  static constexpr int bf3_pairs = -1;  // split-bf16 blocks as pair launches (-1: by shape)
-  static constexpr int pair_lds_mode = 1;  // LDS layout of the direct pair kernels
-  static constexpr int pair_pad_lds = 0;  // extra LDS bytes per pair workgroup (occupancy experiments)
   int cfg_for_bm[5] = {6, 5, 7, 1, 0};  // conv_mfma.hip: index log2(BM / 16) -> tile shape id ("conv_cfg_bm{16..256}")
   int cfg32_for_bm[4] = {3, 2, 1, 0};   // conv_mfma32.hip: BM class 32, 64, 128, 256 -> tile shape id ("conv32_cfg_bm{32..256}")
 };

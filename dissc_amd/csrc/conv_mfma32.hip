@@ -268,18 +268,12 @@ static const TileCfg32 kCfgs32[] = {
     {1, 1, 2, 2},  // 10:  64 x 64   (small grids only, see conv32_pick_cfg)
     {1, 1, 1, 4},  // 11:  32 x 128  (likewise)
 };
-// option "lin_tile" (Options::lin_tile, default 2): "lin_tile" option: channels per barrier / 16 of the 1x1 (linear) convs (2 or 4)
-// option "cpb2" (Options::cpb2, default 0): "cpb2" option: kernels with KS <= this stage 32 channels per barrier
-// option "lin_dma" (Options::lin_dma, default 1): "lin_dma" option: 1x1 convs stage their window with global_load_lds (1: 64, 2: 32 channels per barrier)
-// option "conv_pad_lds" (Options::conv_pad_lds, default 0): "conv_pad_lds" option (diagnostics): extra LDS bytes per workgroup
-// option "c64_wide" (Options::c64_wide, default 1): "c64_wide" option: 64 x 256 tile (64 x 64 wave tiles) for the DMA-staged second convs of the C = 64 stage
-// option "conv2_dma" (Options::conv2_dma, default 1): "conv2_dma" option: stride-2 valid convs stage their window with global_load_lds
-// option "xcd_order" (Options::xcd_order, default 11): XCD-aware workgroup order (bit 0: 1x1 convs, 1: stride-2 convs, 2: the rest,
+// option "xcd_order" (default 11): XCD-aware workgroup order (bit 0: 1x1 convs, 1: stride-2 convs, 2: the rest,
 //   3: the fused attention, hubert.hip).
 //   Encoder, 32 x 10 s (profiles/r05/xcd_order.md): fabric traffic (PMC) 39.60 -> 31.25 GB per forward (conv1 7.98 -> 5.41,
 //   fc1 1.217 -> 0.746, qkv 0.752 -> 0.569), time unchanged (27.66 vs 27.66 ms); the generator's few instances: no change
 //   in either (bit 2 stays off).
-// option "xcd_mg" (Options::xcd_mg, default 0 = automatic): M tiles per sweep of that order
+// option "xcd_mg" (default 0 = automatic): M tiles per sweep of that order
 
 void conv32_set_cfg(int bm_class, int cfg) {
   if (bm_class >= 0 && bm_class < 4 && cfg >= 0 && cfg < 8) g_defaults.cfg32_for_bm[bm_class] = cfg;
@@ -310,7 +304,7 @@ int conv32_cfg_bn(int cfg) { return 32 * kCfgs32[cfg].NI * kCfgs32[cfg].WN; }
 // launch steps down to smaller tiles.  Every output element still sees the same sequence of
 // 32x32x2 MFMAs over (chunk, tap, k), so the result is bit-identical for every tile shape and an
 // utterance's samples stay independent of the batch it runs in.
-// option "small_grid" (Options::small_grid, default 1): "small_grid" option: workgroups per CU below which a launch steps down (0 = never)
+// option "small_grid" (default 1): workgroups per CU below which a launch steps down (0 = never)
 int conv32_pick_cfg(int M, int B, int Lmax_out) {
   const int base = conv32_cfg(M);
   if (!opts().small_grid) return base;
@@ -364,7 +358,7 @@ static int launch32_t(ConvArgs a, int B, int Lmax_out, hipStream_t stream) {
   // EPI_STORE_ACT writes zero tails up to the end of the output rows: the grid covers ldo, not just the longest utterance
   dim3 grid(((a.epi == EPI_STORE_ACT ? a.ldo : Lmax_out) + BN - 1) / BN, a.mt_per_group * a.groups, B);
   a.ragged_enum = (opts().ragged_enum && (a.lengths || a.lengths_out) && a.epi != EPI_STORE_ACT && B > 1) ? 1 : 0;
-  // option "xcd_order" (Options::xcd_order): bit 0: 1x1 convs (linears), bit 1: stride-2 convs, bit 2: every other
+  // option "xcd_order": bit 0: 1x1 convs (linears), bit 1: stride-2 convs, bit 2: every other
   // instance -- launches with >= 2 M tiles only (with one there is nothing to share)
   const int xcd_bit = (STRIDE == 2) ? 2 : (SPAN == 0 ? 1 : 4);
   a.xcd = ((opts().xcd_order & xcd_bit) && a.mt_per_group * a.groups >= 2) ? 1 : 0;
@@ -392,7 +386,7 @@ static int launch32_t(ConvArgs a, int B, int Lmax_out, hipStream_t stream) {
   }
   size_t lds_f = (size_t)2 * KC * CPB * a.XW;
   if (lds_f < (size_t)NW * 8 * CW) lds_f = (size_t)NW * 8 * CW;
-  const size_t lds = lds_f * sizeof(float) + (size_t)opts().conv_pad_lds;  // (+ diagnostics: occupancy experiments)
+  const size_t lds = lds_f * sizeof(float);
   static DeviceOnce attr_once;  // per device (common.h)
   DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&conv_mfma32_kernel<MI, NI, WM, WN, STRIDE, SPAN, CPB, DMA>), 160 * 1024));
   hipLaunchKernelGGL((conv_mfma32_kernel<MI, NI, WM, WN, STRIDE, SPAN, CPB, DMA>), grid, dim3(64 * WM * WN), lds,
@@ -408,7 +402,7 @@ int launch_conv32(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_
   if (stride == 2 && span <= MAX_TAP_SPAN && a.up == 1) {
     // valid (unpadded) convs on an already-activated input: raw LDS-DMA window, nothing to mask -- every output column
     // below the utterance's output length reads inputs below its input length
-    if (cfg == 0 && opts().conv2_dma && a.slope == 1.0f && a.pad_left == 0 && a.groups == 1 && a.KS <= 9 && a.dil == 1 &&
+    if (cfg == 0 && a.slope == 1.0f && a.pad_left == 0 && a.groups == 1 && a.KS <= 9 && a.dil == 1 &&
         a.CIN % KC == 0 && a.ldx >= 4 && a.ldx % 4 == 0)
       return launch32_t<2, 2, 4, 1, 2, MAX_TAP_SPAN, 1, true>(a, B, Lmax_out, stream);
     if (cfg == 0) return launch32_t<2, 2, 4, 1, 2, MAX_TAP_SPAN>(a, B, Lmax_out, stream);
@@ -425,28 +419,22 @@ int launch_conv32(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_
     return DISSC_EINVAL;
   }
   if (span == 0 && stride == 1 && opts().lin128 && lin128_supported(a) && a.nchunk >= 8) return launch_lin128(a, B, Lmax_out, stream);
-  if (span == 0 && bm32_of(a.M) == 256 && a.nchunk >= 8) {  // 1x1 convs: 64 channels per barrier
+  if (span == 0 && bm32_of(a.M) == 256 && a.nchunk >= 8) {  // 1x1 convs: 32 or 64 channels per barrier
     // (the tile must stay the default 256 x 64: a.XW was sized for its BN)
-    const bool dma = opts().lin_dma && a.slope == 1.0f && a.pad_left == 0 && a.up == 1 && a.groups == 1 &&
-                     a.CIN % (2 * KC) == 0 && a.ldx >= 4 && a.ldx % 4 == 0;
+    const bool dma = a.slope == 1.0f && a.pad_left == 0 && a.up == 1 && a.groups == 1 && a.CIN % (2 * KC) == 0 &&
+                     a.ldx >= 4 && a.ldx % 4 == 0;
     // without staging registers 64 channels per barrier fit 3 waves per SIMD (measured: 28.84 -> 28.67 ms per encode)
-    if (dma && opts().lin_dma == 1 && a.CIN % (4 * KC) == 0) return launch32_t<2, 2, 4, 1, 1, 0, 4, true>(a, B, Lmax_out, stream);
+    if (dma && a.CIN % (4 * KC) == 0) return launch32_t<2, 2, 4, 1, 1, 0, 4, true>(a, B, Lmax_out, stream);
     if (dma) return launch32_t<2, 2, 4, 1, 1, 0, 2, true>(a, B, Lmax_out, stream);
-    if (opts().lin_tile == 4) return launch32_t<2, 2, 4, 1, 1, 0, 4>(a, B, Lmax_out, stream);  // 64 ch / barrier
-    return launch32_t<2, 2, 4, 1, 1, 0, 2>(a, B, Lmax_out, stream);                        // 32 ch / barrier
+    return launch32_t<2, 2, 4, 1, 1, 0, 2>(a, B, Lmax_out, stream);  // 32 ch / barrier
   }
   if (a.prec == 1) return launch_conv_bf3(a, B, Lmax_out, stream);  // split-bf16 kernels (conv_bf3.hip)
-  if (opts().cpb2 && a.KS <= opts().cpb2 && a.nchunk >= 4 && a.up == 1) {  // two chunks per barrier for short kernels
-    if (cfg == 0) return launch32_t<2, 2, 4, 1, 1, MAX_TAP_SPAN, 2>(a, B, Lmax_out, stream);
-    if (cfg == 1) return launch32_t<2, 2, 2, 2, 1, MAX_TAP_SPAN, 2>(a, B, Lmax_out, stream);
-    if (cfg == 2) return launch32_t<1, 2, 2, 2, 1, MAX_TAP_SPAN, 2>(a, B, Lmax_out, stream);
-  }
   if (a.dma_in && a.slope == 1.0f && a.up == 1 && a.groups == 1 && a.CIN % KC == 0 && a.KS > 1) {
     // input in the EPI_STORE_ACT layout (generator: the second conv of a residual pair): raw LDS-DMA windows
     if (cfg == 0) return launch32_t<2, 2, 4, 1, 1, MAX_TAP_SPAN, 1, true>(a, B, Lmax_out, stream);
     if (cfg == 1) return launch32_t<2, 2, 2, 2, 1, MAX_TAP_SPAN, 1, true>(a, B, Lmax_out, stream);
-    if (cfg == 2 && opts().c64_wide) return launch32_t<2, 2, 1, 4, 1, MAX_TAP_SPAN, 1, true>(a, B, Lmax_out, stream);  // 64 x 256
-    if (cfg == 2) return launch32_t<1, 2, 2, 2, 1, MAX_TAP_SPAN, 1, true>(a, B, Lmax_out, stream);
+    // 64-row tiles as 64 x 256 (64 x 64 wave tiles) in place of cfg 2's 64 x 128
+    if (cfg == 2) return launch32_t<2, 2, 1, 4, 1, MAX_TAP_SPAN, 1, true>(a, B, Lmax_out, stream);
   }
   switch (cfg) {
     case 0: return launch32_t<2, 2, 4, 1, 1, MAX_TAP_SPAN>(a, B, Lmax_out, stream);

@@ -38,7 +38,6 @@
 
 namespace dissc {
 
-// option "wino_small" (Options::wino_small, default 96): "wino_small" option: launches with fewer 64 x 64-tile workgroups than this use 32 x 32 wave tiles
 // option "kernel_dbg": diagnostics: knock-outs, bit 0 transform, 1 MFMAs, 2 epilogue, 3 staging
 
 struct WinoArgs {
@@ -605,8 +604,10 @@ static int launch_wino_c(const WinoArgs& a, int B, int Lmax, hipStream_t stream)
   return DISSC_OK;
 }
 
-// option "wino_cpr" (Options::wino_cpr, default 32): "wino_cpr" option: channels per barrier round (16 or 32)
-// option "wino_sv" (Options::wino_sv, default 1): "wino_sv" option: shared transform in the row-half form (C >= 128)
+// launches with fewer 64 x 64-tile workgroups than this use 32 x 32 wave tiles
+constexpr int WINO_SMALL_GRID = 96;
+
+// option "wino_sv" (default 1): shared transform in the row-half form (C >= 128)
 template <int NS, int DIL>
 static int launch_wino_t(const WinoArgs& a, int B, int Lmax, hipStream_t stream) {
   // Small grids (a short or single utterance: the reference's one-at-a-time mode) step down to 32 x 32 wave tiles: four
@@ -616,15 +617,16 @@ static int launch_wino_t(const WinoArgs& a, int B, int Lmax, hipStream_t stream)
   const bool c64 = a.C % 128 != 0;
   const int ot = 4 * D * (64 / D) * (c64 ? 2 : 1);
   const long long nwg = (long long)((Lmax + ot - 1) / ot) * (c64 ? a.C / 64 : a.C / 128) * B;
-  const bool small = opts().small_grid && nwg < (long long)opts().wino_small;
+  const bool small = opts().small_grid && nwg < WINO_SMALL_GRID;
   if (a.C == 32) return launch_wino_c<NS, DIL, 16, 1, 1>(a, B, Lmax, stream);  // diagnostics only (dissc_respair1d mode 2)
   if (c64) {
     if (small) return launch_wino_c<NS, DIL, 16, 1, 1>(a, B, Lmax, stream);  // 32 rows x 64 columns
     return launch_wino_c<NS, DIL, 16, 1, 2>(a, B, Lmax, stream);            // 64 rows x 128 columns
   }
   if (small) return launch_wino_c<NS, DIL, 16, 2, 1>(a, B, Lmax, stream);    // 64 rows x 32 columns
-  // (k = 11, d = 5 with 32 channels per round needs more registers than three waves per SIMD leave: 16 there)
-  const bool r32 = opts().wino_cpr == 32 && a.nchunk % 2 == 0 && !(NS == 4 && DIL == 5);
+  // 32 channels per barrier round where the chunks pair up (k = 11, d = 5 with 32 channels per round needs more registers
+  // than three waves per SIMD leave: 16 there)
+  const bool r32 = a.nchunk % 2 == 0 && !(NS == 4 && DIL == 5);
   if (opts().wino_sv) {
     // (with 32 channels per round the k = 7 / 11 instances spill a few registers; k = 3 has room)
     if (NS == 1 && r32) return launch_wino_c<NS, DIL, 32, 2, 2, 1>(a, B, Lmax, stream);

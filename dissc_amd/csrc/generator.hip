@@ -44,20 +44,18 @@ thread_local const Options* t_opts = nullptr;
 
 using namespace dissc;
 
-// option "stream_prio" (Options::stream_prio, default 1): "stream_prio" option: prioritise the longer ResBlock chains
-// option "graphs" (Options::graphs, default 0): "graphs" option: replay small forwards from a captured hipGraph.  OFF by default:
+// option "graphs" (default 0): replay small forwards from a captured hipGraph.  OFF by default:
                                   // measured on ROCm 7.2 / MI355X, hipGraphLaunch of the ~85-node three-branch graph costs
                                   // 1.3-1.8 ms MORE per forward than the plain three-stream launches (tools/graph_ab.py)
-// option "graph_frames" (Options::graph_frames, default 2048): "graph_frames" option: largest B * Tmax that is graphed
+// option "graph_frames" (default 2048): largest B * Tmax that is graphed
 [[maybe_unused]] static int g_graph_hits = 0, g_graph_captures = 0;  // diagnostics (dissc_get_option)
-// option "multistream" (Options::multistream, default 1): "multistream" option: concurrent ResBlock chains (read at create)
-// option "par_ups" (Options::par_ups, default 1): "par_ups" option: ConvTranspose phase groups on concurrent streams
+// option "multistream" (default 1): concurrent ResBlock chains (read at create)
 
 // ---- the ResBlock plan -------------------------------------------------------------------------------------------------------
 // Each ResBlock is a chain of three residual pairs x = x + conv_1(lrelu(conv_d(lrelu(x)))).  Which kernels run a chain and its
 // pairs is decided ONCE per handle, by plan_chain() under the handle's options when it is created: packing follows the plan, and
 // the plan is all that the forward and the executed-FLOP count read.  The policy below is the only code that reads the form
-// options (wino, wino8*, pair_*, bf3_pairs) and the handle's precision; the kernel files only say which instances exist
+// options (wino, wino8*, pair_*) and the handle's precision; the kernel files only say which instances exist
 // (*_supported).
 enum class ChainForm : uint8_t {
   pairs,      // three pair launches or launch pairs, each in its own PairForm
@@ -82,28 +80,30 @@ struct ChainPlan {
   PairPlan pair[3];
 };
 
-// option "wino" (Options::wino, default 1): 1 = the ResBlock convs of the stages with C >= wino_min_c (64; at C = 64 those with
-//   k >= wino_c64_kmin = 3: k = 3 / 7 gain 2 % per forward there, in isolation break-even against the DMA-staged direct pair) run
-//   in the Toom-Cook transform domain; 0 = all direct (and no fused transform-domain pairs either); 2 = dissc_conv1d too (tests)
+// option "wino" (default 1): 1 = the ResBlock convs of the stages with C >= WINO_MIN_C (at C = 64 those with
+//   k >= WINO_C64_KMIN) run in the Toom-Cook transform domain; 0 = all direct (and no fused transform-domain pairs either);
+//   2 = dissc_conv1d too (tests)
+constexpr int WINO_MIN_C = 64;    // narrowest stage on the transform-domain kernels
+constexpr int WINO_C64_KMIN = 3;  // C = 64: k = 3 / 7 gain 2 % per forward, in isolation break-even against the DMA-staged direct pair
 static bool wino_wanted(int C, int KS) {
-  if (!opts().wino || C < Options::wino_min_c) return false;
-  if (C < 128 && KS < Options::wino_c64_kmin) return false;
+  if (!opts().wino || C < WINO_MIN_C) return false;
+  if (C < 128 && KS < WINO_C64_KMIN) return false;
   return wino_supported(C, C, KS, 1);
 }
 
-// option "wino8" (Options::wino8, default 1): 1 = the transform-domain convs "wino8_mask" names run on conv_wino8.hip's eight
+// option "wino8" (default 1): 1 = the transform-domain convs "wino8_mask" names run on conv_wino8.hip's eight
 //   points instead of conv_wino's F(4,3) form; 0 = none; 2 = dissc_conv1d too (tests).  Per launch 3-17 % faster than F(4,3) on 26
 //   of the 36 (C, k, d, epilogue) shapes of the generator (tools/wino8_gate.py), 4-9 % slower on the d = 1 shapes of the
 //   128-channel stage (864 workgroups = 3.4 rounds of 256 CUs where the F(4,3) tiles make exactly 5.0): the default mask leaves
 //   that stage alone.  Whole forward 35.17 / 35.27 -> 34.84 / 34.91 ms, in-run parity rms 5.5e-7 -> 6.5e-7.
-// option "wino8_mask" (Options::wino8_mask, default 0450770550): one bit per SHAPE, from per-launch measurements and same-box
+// option "wino8_mask" (default 0450770550): one bit per SHAPE, from per-launch measurements and same-box
 //   forward A/Bs (tools/opt_ab.sh): bit 9 cls + 3 ki + di with cls = 0 / 1 / 2 for C = 64 / 128 / >= 256, ki = 0 / 1 / 2 for
 //   k = 3 / 7 / 11, di = 0 / 1 / 2 for dilation 1 / 3 / 5 -- in octal three digits per class (k = 11, k = 7, k = 3 from the left),
 //   each digit = the dilations d5 d3 d1.  Speed alone picked every k = 7 / 11 shape and k = 3, d = 1 at C = 64 (0770770771);
 //   on trained-like weights and inputs (tests/test_gpu_trained_like.py, profiles/trained_like_error.md) seven of those shapes
 //   rounded above 3x the direct kernel's rms error in their eight-point form and stay on F(4,3): C >= 256 k = 7 d = 3 and
 //   k = 11 d = 1 / 3 (F(5,4)), C = 64 k = 3 d = 1, k = 7 d = 3 and k = 11 d = 3 (F(6,3)).
-// option "wino8_r4" (Options::wino8_r4, default 1): 1 = the shapes "wino8_r4_mask" (same layout, k = 3 bits ignored; default every
+// option "wino8_r4" (default 1): 1 = the shapes "wino8_r4_mask" (same layout, k = 3 bits ignored; default every
 //   k = 7 / 11 shape of the C >= 128 stages and k = 7, d = 1 at C = 64) run as F(5,4) instead of F(6,3); 2 = dissc_conv1d too
 //   (tests); 0 = never
 static int w8_shape_bit(int C, int KS, int dil) {
@@ -117,7 +117,7 @@ static ConvForm td_conv_form(int C, int KS, int dil) {
   return r4 ? ConvForm::f54 : ConvForm::f63;
 }
 
-// option "pair_f23" (Options::pair_f23, default 3), a bit mask: 1 = the C = 32, k = 11 pairs run as register-only F(2,3)
+// option "pair_f23" (default 3), a bit mask: 1 = the C = 32, k = 11 pairs run as register-only F(2,3)
 //   (respair_f23.hip; per launch 857 / 894 / 924 us at d = 1 / 3 / 5 against 1 042 / 1 037 / 1 052 for the direct pair,
 //   B = 32 x 10 s), 2 = the C = 16, k = 11 pairs (respair16_f23.hip: 525 against 604 us at d = 1); 4 / 8 = the k = 3 pairs of the
 //   two stages (C = 32: 365 against 417 us, C = 16: 262 against 263; forward 33.11 -> 33.09 ms: off).  Also picks the form of
@@ -125,7 +125,7 @@ static ConvForm td_conv_form(int C, int KS, int dil) {
 static bool pair_f23_wanted(int C, int KS, int dil) {
   return pair_f23_supported(C, KS, dil) && (opts().pair_f23 & ((C == 32 ? 1 : 2) << (KS == 3 ? 2 : 0)));
 }
-// option "pair_wino" (Options::pair_wino, default 0; experimental builds): 1 = the pairs respair_wino.hip's F(4,3) kernel measured
+// option "pair_wino" (default 0; experimental builds): 1 = the pairs respair_wino.hip's F(4,3) kernel measured
 //   faster for (tools/pair_gate.py, B = 32 x 10 s: C = 32, k = 11, d = 1 / 3: 895 / 988 us against 1 042 / 1 047 for the direct
 //   fused pair; C = 64, k = 3, d = 1: 624 against 658 for two conv_wino launches) run on it; 2 = every shape with an instance
 //   (tests); 0 = none.  Off: its gate failed (whole forward 35.36 against 35.42 ms, executed-FLOP utilisation 0.619 -> 0.602).
@@ -137,17 +137,15 @@ static bool pairw_wanted(int C, int KS, int dil) {
   return C == 64 && KS == 3 && dil == 1;
 }
 
-// bf3_pairs (a constant now, Options::bf3_pairs = -1): split-bf16 blocks of >= 64 channels run as three pair launches.  With 64
-// channels the LDS holds 256-column windows only, and the 120-column halo of a whole 11-tap block would be recomputed ~2x; a
-// pair's halo is 10-30 columns, at the price of two more read+write passes of x_k per block.
-static bool bf3_pairs_wanted(int C) { return Options::bf3_pairs < 0 ? C >= 64 : Options::bf3_pairs != 0; }
-
-// option "pair_max_c" (Options::pair_max_c, default 32): widest stage whose pairs run as one launch each (0 = off)
-// option "pair_dma" (Options::pair_dma, default 1): the direct pairs of the wide stages hand t over in the EPI_STORE_ACT layout
+// option "pair_max_c" (default 32): widest stage whose pairs run as one launch each (0 = off)
+// option "pair_dma" (default 1): the direct pairs of the wide stages hand t over in the EPI_STORE_ACT layout
 static ChainPlan plan_chain(int C, int KS, const int* dil, int prec) {
   ChainPlan cp;
   if (prec == 1 && resblock_bf3_supported(C, KS, dil)) {
-    cp.form = bf3_pairs_wanted(C) ? ChainForm::bf3_pairs : ChainForm::bf3_block;
+    // split-bf16 blocks of >= 64 channels run as three pair launches.  With 64 channels the LDS holds 256-column windows only,
+    // and the 120-column halo of a whole 11-tap block would be recomputed ~2x; a pair's halo is 10-30 columns, at the price of
+    // two more read+write passes of x_k per block.
+    cp.form = C >= 64 ? ChainForm::bf3_pairs : ChainForm::bf3_block;
     return cp;
   }
   // the direct fused pair needs fp32 weights in its layout (16x16x4 at C = 16, 32x32x2 at C = 32: make_conv's choice)
@@ -541,8 +539,7 @@ int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, s
       // path, so it gets the highest stream priority and the short chains fill in around it
       int lo = 0, hi = 0;
       (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // lo = least urgent, hi = most urgent (numerically lower)
-      int prio = lo;
-      if (opts().stream_prio && nk > 1) prio = lo + (hi - lo) * j / (nk - 1);
+      const int prio = lo + (hi - lo) * j / (nk - 1);
       if (j > 0 && !(g->aux[j] = shared_aux_stream(j, prio))) return fail(DISSC_EHIP);
     }
   }
@@ -708,7 +705,7 @@ static int gen_forward_body(dissc_gen_t g, const int64_t* code, const float* f0,
     // (phase groups write disjoint output phases: with side streams they run concurrently, which
     // fills the CUs better than two or three small grids one after the other)
     const int ngrp = (int)g->ups[i].size();
-    const bool par_ups = multi && opts().par_ups && ngrp > 1 && ngrp <= nk;
+    const bool par_ups = multi && ngrp > 1 && ngrp <= nk;
     if (par_ups) DISSC_HIP_CHECK(hipEventRecord(g->ev_x, stream));  // ACC is complete
     for (int gi = 0; gi < ngrp; ++gi) {
       hipStream_t sg = (par_ups && gi > 0) ? g->aux[gi] : stream;

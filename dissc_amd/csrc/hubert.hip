@@ -43,12 +43,6 @@ __global__ void hubert_lengths_kernel(const int32_t* __restrict__ n_samples, int
 constexpr int C0_TILE = 1024;  // outputs per block: 256 threads x 4
 constexpr int C0_CH = 512;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // pass 1: GroupNorm statistics WITHOUT evaluating the 512 channels.  conv0 has one input channel, so
 // channel c's output is x_c[t] = sum_j w[c][j] * s[5t + j] and its moments are linear / quadratic forms of
 // the waveform's own lag moments:
@@ -253,109 +247,6 @@ __global__ void __launch_bounds__(64 * LN_WAVES) ln_cf_kernel(const float* __res
     }
 }
 
-// ---- batched fp32 MFMA GEMM for attention: C[z] = alpha * A[z] (MxK) * B[z] (KxN) ------------
-struct BGemmArgs {
-  const float* A; const float* B; float* C;
-  long long a_bs, a_hs, b_bs, b_hs, c_bs, c_hs;  // per-utterance / per-head offsets (floats)
-  long long sam, sak, sbk, sbn, scm;             // element strides; C is n-contiguous
-  const int32_t* lens;                           // T_b
-  int m_is_t, n_is_t, k_is_t, fixed;             // dims: T_b where the flag is set, else `fixed`
-  int H;
-  float alpha;
-};
-constexpr int BG_LD = 80;  // LDS row stride: 80 % 32 == 16 -> conflict-free fragment reads
-
-__global__ void __launch_bounds__(256) bgemm_kernel(const BGemmArgs a) {
-  __shared__ float As[16 * BG_LD];
-  __shared__ float Bs[16 * BG_LD];
-  const int z = blockIdx.z, b = z / a.H, h = z - b * a.H;
-  const int T = a.lens[b];
-  const int M = a.m_is_t ? T : a.fixed, N = a.n_is_t ? T : a.fixed, K = a.k_is_t ? T : a.fixed;
-  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-  if (m0 >= M || n0 >= N) return;
-  const float* A = a.A + b * a.a_bs + h * a.a_hs;
-  const float* B = a.B + b * a.b_bs + h * a.b_hs;
-  float* C = a.C + b * a.c_bs + h * a.c_hs;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l15 = lane & 15, g = lane >> 4;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bool a_mfast = a.sam == 1, b_nfast = a.sbn == 1;
-  for (int k0 = 0; k0 < K; k0 += 16) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + i * 256;
-      int kk, mm;
-      if (a_mfast) { kk = e >> 6; mm = e & 63; } else { mm = e >> 4; kk = e & 15; }
-      float v = 0.f;
-      if (m0 + mm < M && k0 + kk < K) v = A[(long long)(m0 + mm) * a.sam + (long long)(k0 + kk) * a.sak];
-      As[kk * BG_LD + mm] = v;
-      int nn;
-      if (b_nfast) { kk = e >> 6; nn = e & 63; } else { nn = e >> 4; kk = e & 15; }
-      v = 0.f;
-      if (n0 + nn < N && k0 + kk < K) v = B[(long long)(k0 + kk) * a.sbk + (long long)(n0 + nn) * a.sbn];
-      Bs[kk * BG_LD + nn] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int cq = 0; cq < 4; ++cq) {
-      float av[2], bv[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        av[i] = As[(g + 4 * cq) * BG_LD + wm * 32 + i * 16 + l15];
-        bv[i] = Bs[(g + 4 * cq) * BG_LD + wn * 32 + i * 16 + l15];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = m0 + wm * 32 + i * 16 + 4 * g + r;
-      if (m >= M) continue;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 32 + j * 16 + l15;
-        if (n < N) C[(long long)m * a.scm + n] = a.alpha * acc[i][j][r];
-      }
-    }
-}
-
-// in-place softmax over the first T_b entries of every row of S[b][h][i][:]
-__global__ void __launch_bounds__(256) softmax_rows_kernel(float* __restrict__ S,
-                                                           const int32_t* __restrict__ lens, int H,
-                                                           int Tmax, int ldS) {
-  const int b = blockIdx.z;
-  const int T = lens[b];
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per row
-  const int h = blockIdx.y;
-  if (row >= T) return;
-  float* p = S + (((size_t)b * H + h) * Tmax + row) * ldS;
-  const int lane = threadIdx.x & 63;
-  float mx = -INFINITY;
-  for (int j = lane; j < T; j += 64) mx = fmaxf(mx, p[j]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-  float sum = 0.f;
-  for (int j = lane; j < T; j += 64) {
-    const float e = expf(p[j] - mx);
-    p[j] = e;
-    sum += e;
-  }
-  sum = wave_sum(sum);
-  for (int j = lane; j < T; j += 64) p[j] = __fdiv_rn(p[j], sum);
-}
-
 // ---- fused exact attention: attn.hip (a translation unit of its own: it is compiled with -amdgpu-mfma-vgpr-form) ----------------
 int launch_attn_fused(const float* qkv, const int32_t* lens, int D, int hd, int ld, float* out, int T, int H, int B, hipStream_t st);
 
@@ -511,8 +402,7 @@ int launch_kmeans_assign(const float* x, long long x_bstride, long long st, long
 using namespace dissc;
 
 namespace dissc {
-// option "attn_fused" (Options::attn_fused, default 1): "attn_fused" option: 0 = S=QK^T -> softmax -> PV through HBM (3 kernels)
-// option "hubert_split" (Options::hubert_split, default 1): "hubert_split" option: batches of >= 16 utterances run as 2-4 parts on streams of their own (0 never, 1
+// option "hubert_split" (default 1): batches of >= 16 utterances run as 2-4 parts on streams of their own (0 never, 1
                          // unless the batch fills whole workgroup rounds by itself, N >= 2: always N parts)
 }
 
@@ -727,7 +617,6 @@ struct HubertWs {
   float *x, *y, *t1; // [B][768][ldT]
   float* qkv;        // [B][2304][ldT]
   float* ffn;        // [B][3072][ldT]
-  float* S;          // [B][H][T][ldS]
   size_t bytes;
 };
 
@@ -754,8 +643,6 @@ static HubertWs carve(const dissc_hubert* m, int B, int Nmax, void* base_) {
   w.t1 = (float*)take((size_t)B * m->D * ldT * 4);
   w.qkv = (float*)take((size_t)B * 3 * m->D * ldT * 4);
   w.ffn = (float*)take((size_t)B * m->F * ldT * 4);
-  const bool need_s = !(opts().attn_fused && m->D / m->H == 64);  // the fused attention keeps S on chip
-  w.S = (float*)take(need_s ? (size_t)B * m->H * (size_t)(T > 0 ? T : 1) * ldT * 4 : 256);
   w.bytes = (size_t)(p - p0) + 256;
   return w;
 }
@@ -918,29 +805,8 @@ static int hubert_forward_part(dissc_hubert_t m, const float* wav, const int32_t
   for (int i = 0; i < m->n_layers; ++i) {
     auto& L = m->layers[i];
     if ((rc = run_conv_ex(L.qkv, w.x, w.qkv, nullptr, ioT, B, D, ldT, ldT, T, 1.0f, EPI_STORE, st))) return rc;
-    if (opts().attn_fused && hd == 64) {
-      if ((rc = launch_attn_fused(w.qkv, lensT, D, hd, ldT, w.t1, T, H, B, st))) return rc;
-    } else {
-    BGemmArgs a;
-      // S[b,h][i][j] = sum_d Q[d][i] K[d][j]      (Q already scaled by 1/sqrt(hd))
-      a.A = w.qkv; a.B = w.qkv + (size_t)D * ldT; a.C = w.S;
-      a.a_bs = (long long)3 * D * ldT; a.a_hs = (long long)hd * ldT; a.b_bs = a.a_bs; a.b_hs = a.a_hs;
-      a.c_bs = (long long)H * T * ldT; a.c_hs = (long long)T * ldT;
-      a.sam = 1; a.sak = ldT; a.sbk = ldT; a.sbn = 1; a.scm = ldT;
-      a.lens = lensT; a.m_is_t = 1; a.n_is_t = 1; a.k_is_t = 0; a.fixed = hd; a.H = H; a.alpha = 1.f;
-      dim3 gs((T + 63) / 64, (T + 63) / 64, B * H);
-      hipLaunchKernelGGL(bgemm_kernel, gs, dim3(256), 0, st, a);
-      hipLaunchKernelGGL(softmax_rows_kernel, dim3((T + 3) / 4, H, B), dim3(256), 0, st, w.S, lensT, H, T, ldT);
-      // O[h*hd + d][i] = sum_j V[d][j] P[i][j]  -> t1 (channels-first)
-      a.A = w.qkv + (size_t)2 * D * ldT; a.B = w.S; a.C = w.t1;
-      a.a_bs = (long long)3 * D * ldT; a.a_hs = (long long)hd * ldT;
-      a.b_bs = (long long)H * T * ldT; a.b_hs = (long long)T * ldT;
-      a.c_bs = (long long)D * ldT; a.c_hs = (long long)hd * ldT;
-      a.sam = ldT; a.sak = 1; a.sbk = 1; a.sbn = ldT; a.scm = ldT;
-      a.m_is_t = 0; a.n_is_t = 1; a.k_is_t = 1; a.fixed = hd;
-      dim3 go((T + 63) / 64, (hd + 63) / 64, B * H);
-      hipLaunchKernelGGL(bgemm_kernel, go, dim3(256), 0, st, a);
-    }
+    // fused exact attention (attn.hip): the scores stay on chip
+    if ((rc = launch_attn_fused(w.qkv, lensT, D, hd, ldT, w.t1, T, H, B, st))) return rc;
     // x = LN(x + out_proj(O))
     if ((rc = run_conv_ex(L.out, w.t1, w.y, w.x, ioT, B, D, ldT, ldT, T, 1.0f, EPI_RES, st))) return rc;
     hipLaunchKernelGGL(ln_cf_kernel, gln, dim3(64 * LN_WAVES), 0, st, w.y, (const float*)nullptr, L.ln1_g, L.ln1_b, lensT, D,

@@ -15,8 +15,6 @@
 //     are the ones pack_conv_weights32 makes) and the same epilogue arithmetic, so results are bit-identical to the 256 x 64
 //     kernel's: the tile shape is a schedule, not an arithmetic.
 // Window staging: global_load_lds_dwordx4, KCB channels x 128 frames per barrier, two buffers (KCB = 64: 64 KB per workgroup).
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.h"
@@ -301,7 +299,7 @@ __global__ void __launch_bounds__(256, WGPC) lin128_kernel(const ConvArgs a) {
   }
 }
 
-// option "lin128" (Options::lin128, default 1): HuBERT's linears on lin128_kernel (0: conv_mfma32_kernel's 256 x 64 instances)
+// option "lin128" (default 1): HuBERT's linears on lin128_kernel (0: conv_mfma32_kernel's 256 x 64 instances)
 bool lin128_supported(const ConvArgs& a) {
   return a.KS == 1 && a.groups == 1 && a.up == 1 && a.slope == 1.0f && a.pad_left == 0 && a.prec == 0 && a.m32 == 1 &&
          (a.epi == EPI_STORE || a.epi == EPI_RES) && !a.scale && a.M >= 256 && a.M % 256 == 0 && a.CIN % 64 == 0 && a.ldx >= 4 && a.ldx % 4 == 0 &&
@@ -346,7 +344,7 @@ static int launch_lin128_t(ConvArgs a, int B, int Lmax_out, hipStream_t stream) 
     }
   }
   size_t lds = (size_t)2 * KCB * BN * sizeof(float);
-  if (opts().kernel_dbg == 64 || getenv("DISSC_LIN128_ONE")) lds = 100 * 1024;  // diagnostics: ONE workgroup per CU (one wave per SIMD)
+  if (opts().kernel_dbg == 64) lds = 100 * 1024;  // diagnostics: ONE workgroup per CU (one wave per SIMD)
   static DeviceOnce attr_once;
   DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&lin128_kernel<MI, KCB, WGPC, DBG>), 160 * 1024));
   hipLaunchKernelGGL((lin128_kernel<MI, KCB, WGPC, DBG>), grid, dim3(256), lds, stream, a);
@@ -615,7 +613,7 @@ bool conv2s128_shape(int Cout, int Cin, int KS, int stride, int groups) {
   return stride == 2 && KS == 3 && groups == 1 && Cout % 256 == 0 && Cin % 32 == 0;
 }
 
-// option "conv2s128" (Options::conv2s128, default 1): stride-2 k = 3 convs on conv2s128_kernel (0: conv_mfma32_kernel; 2: 32 channels per barrier)
+// option "conv2s128" (default 1): stride-2 k = 3 convs on conv2s128_kernel (0: conv_mfma32_kernel; 2: 32 channels per barrier)
 bool conv2s128_supported(const ConvArgs& a) {
   return a.wpack2 && a.KS == 3 && a.dil == 1 && a.groups == 1 && a.up == 1 && a.slope == 1.0f && a.pad_left == 0 && a.prec == 0 &&
          a.epi == EPI_STORE && !a.scale && a.M % 256 == 0 && a.CIN % 32 == 0 && a.ldx >= 4 && a.ldx % 4 == 0 && a.ldo % 4 == 0 &&

@@ -52,7 +52,7 @@ void free_pairw(DevPairW& pw) {
   }
 }
 
-// option "pairw_chv" (Options::pairw_chv, default 2): "pairw_chv" option: column halves per workgroup of respair_wino_kernel (2: one 12-wave workgroup per CU;
+// option "pairw_chv" (default 2): column halves per workgroup of respair_wino_kernel (2: one 12-wave workgroup per CU;
                       // 1: two 6-wave workgroups with half the tile each -- measured 5-30 % slower, kept for the tests)
 
 

@@ -327,8 +327,6 @@ static inline float bf16_to_f32_host(uint16_t h) {
   return f;
 }
 
-// option "fused_variant" (Options::bf3_variant, default 0): "fused_variant" in precision mode: 0 = 512-column window, 1 = 1024
-
 bool resblock_bf3_supported(int C, int KS, const int* dil) {
   if (C != 16 && C != 32 && C != 64) return false;
   // (C = 64 leaves room for 256-column windows only; with 11 taps the halo is 120 of them and the
@@ -409,12 +407,8 @@ int launch_resblock_bf3(int C, const float* x, float* acc, const float* wpack, c
     if (KS == 7) return launch_bf3<32, 7, 8, 4>(a, B, Lmax, stream);
     return launch_bf3<32, 11, 8, 4>(a, B, Lmax, stream);
   }
-  if (opts().bf3_variant == 1) {  // 1024-column windows: less halo recompute, but one workgroup per CU
-    if (KS == 3) return launch_bf3<16, 3, 8, 8>(a, B, Lmax, stream);
-    if (KS == 7) return launch_bf3<16, 7, 8, 8>(a, B, Lmax, stream);
-    return launch_bf3<16, 11, 8, 8>(a, B, Lmax, stream);
-  }
-  // default: 512-column windows, two workgroups per CU overlap each other's memory phases
+  // C = 16: 512-column windows, two workgroups per CU overlap each other's memory phases (1024-column windows recompute
+  // less halo, but fit one workgroup per CU)
   if (KS == 3) return launch_bf3<16, 3, 8, 4>(a, B, Lmax, stream);
   if (KS == 7) return launch_bf3<16, 7, 8, 4>(a, B, Lmax, stream);
   return launch_bf3<16, 11, 8, 4>(a, B, Lmax, stream);

@@ -225,10 +225,10 @@ __global__ void __launch_bounds__(256) respair16_kernel(const PairArgs a) {
 // next step's fragments are fetched while the current 8*NI MFMAs run (sched_barrier pins the prefetch).
 typedef float f32x16p __attribute__((ext_vector_type(16)));
 
-// LM (LDS mode): 0 = separate windows for lrelu(x) and T (70-78 KB: two workgroups per CU); 1 (default) = T overwrites
-// the x window after one more barrier, wave-private epilogue patches in their own 8.7 KB (44-52 KB: three per CU,
-// -0.43 ms per forward).  Letting the patches overwrite the window too (35-43 KB, four per CU) measured the same.
-template <int KS, int DIL, int NI, int LM>
+// LDS: T overwrites the x window after one more barrier, and the wave-private epilogue patches have their own 8.7 KB
+// (44-52 KB: three workgroups per CU; separate x and T windows take 70-78 KB, two per CU, and cost 0.43 ms per forward).
+// Letting the patches overwrite the window too (35-43 KB, four per CU) measured the same.
+template <int KS, int DIL, int NI>
 __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
   constexpr int C = 32, NW = 4, NT = 64 * NW;
   constexpr int SLOTS = 32 * NI * NW;
@@ -240,12 +240,10 @@ __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
   constexpr int SV = (C * NV + NT - 1) / NT;
   constexpr int CW = 32 * NI + 4;
   constexpr int LPR = 8 * NI, RPP = 64 / LPR, NPASS = 8 / RPP;
-  static_assert(NW * 8 * CW <= C * XW1, "epilogue patches alias the input window");
   static_assert(XW2 <= XW1, "T fits the x window");
-  __shared__ __attribute__((aligned(16))) float Xs[C * XW1];
-  __shared__ __attribute__((aligned(16))) float Tsep[LM == 0 ? C * XW2 : 4];
-  __shared__ __attribute__((aligned(16))) float Psep[LM == 1 ? NW * 8 * CW : 4];
-  float* const Ts = LM == 0 ? Tsep : Xs;
+  __shared__ __attribute__((aligned(16))) float Xs[C * XW1];  // lrelu(x) window, then T
+  __shared__ __attribute__((aligned(16))) float Ps[NW * 8 * CW];  // epilogue patches
+  float* const Ts = Xs;
 
   int b, len, o0;
   if (!pair_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
@@ -330,7 +328,7 @@ __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
   }
   // epilogue 1: T = lrelu(conv_d + b1), 0 outside the utterance.  D layout: col = lane & 31,
   // row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
-  if constexpr (LM != 0) __syncthreads();  // every wave is done reading the x window T is about to overwrite
+  __syncthreads();  // every wave is done reading the x window T is about to overwrite
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) {
     const int u = wave * (32 * NI) + ni * 32 + l31;
@@ -354,7 +352,7 @@ __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
   }
 #undef DISSC_PAIR32_TAPS
   // epilogue 2: 8 rows at a time through a wave-private patch [8][CW] -> 16 B per lane
-  float* ep = (LM == 1 ? Psep : Xs) + wave * (8 * CW);
+  float* ep = Ps + wave * (8 * CW);
   const int prow = lane / LPR, pc4 = lane % LPR;
   const int ncol = wave * (32 * NI) + 4 * pc4;
   const int tcol = o0 + ncol;
@@ -393,10 +391,7 @@ template <int KS, int DIL>
 static int launch_pair32(const PairArgs& a, int B, int Lmax, hipStream_t stream) {
   constexpr int NI = 2, SLOTS = 32 * NI * 4, WOUT = (SLOTS - (KS - 1)) & ~3;
   dim3 grid((Lmax + WOUT - 1) / WOUT, B);
-  if (opts().pair_lds_mode == 0)
-    hipLaunchKernelGGL((respair32_kernel<KS, DIL, NI, 0>), grid, dim3(256), (size_t)opts().pair_pad_lds, stream, a);
-  else
-    hipLaunchKernelGGL((respair32_kernel<KS, DIL, NI, 1>), grid, dim3(256), (size_t)opts().pair_pad_lds, stream, a);
+  hipLaunchKernelGGL((respair32_kernel<KS, DIL, NI>), grid, dim3(256), 0, stream, a);
   DISSC_HIP_CHECK(hipGetLastError());
   return DISSC_OK;
 }
@@ -405,13 +400,10 @@ template <int KS, int DIL>
 static int launch_pair16(const PairArgs& a, int B, int Lmax, hipStream_t stream) {
   constexpr int NI = 4, SLOTS = 16 * NI * 4, WOUT = (SLOTS - (KS - 1)) & ~3;
   dim3 grid((Lmax + WOUT - 1) / WOUT, B);
-  hipLaunchKernelGGL((respair16_kernel<KS, DIL, NI>), grid, dim3(256), (size_t)opts().pair_pad_lds, stream, a);
+  hipLaunchKernelGGL((respair16_kernel<KS, DIL, NI>), grid, dim3(256), 0, stream, a);
   DISSC_HIP_CHECK(hipGetLastError());
   return DISSC_OK;
 }
-
-// option "pair_lds" (Options::pair_lds_mode, default 1): "pair_lds" option: LDS layout of respair32 (see LM)
-// option "pair_pad_lds" (Options::pair_pad_lds, default 0): diagnostics: extra dynamic LDS bytes per workgroup (lowers occupancy)
 
 bool respair_supported(int C, int KS, int dil) {
   if (C != 16 && C != 32) return false;

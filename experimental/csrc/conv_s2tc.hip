@@ -45,11 +45,11 @@
 
 namespace dissc {
 
-// option "enc_tc" (Options::enc_tc, default 0): "enc_tc" option (read at dissc_hubert_create): 1 = conv1..conv4 of the feature extractor use this kernel.
+// option "enc_tc" (default 0, read at dissc_hubert_create): 1 = conv1..conv4 of the feature extractor use this kernel.
                         // OFF by default: the round-5 gate (conv1 <= 5.3 ms AND per-layer rms <= 2x the direct form's) failed on both
                         // counts -- 5.95-6.09 ms against the direct kernel's 6.30-6.45 on the same boxes (conv1..4: 11.7 vs 12.4-12.5 ms,
                         // encode 27.48 vs 27.99 ms) and 2.35x the rms error (profiles/r05/s2tc_gate.txt)
-// option "s2tc_xmode" (Options::s2tc_xmode, default 0): "s2tc_xmode" option: 0 = row tiles pinned to XCDs (weights L2-resident), 1 = row tiles of a time tile share an XCD
+// option "s2tc_xmode" (default 0): 0 = row tiles pinned to XCDs (weights L2-resident), 1 = row tiles of a time tile share an XCD
 // option "kernel_dbg": diagnostics: knock-outs, bit 0 transform, 1 MFMAs, 2 epilogue, 3 staging loads
 
 namespace {
@@ -467,7 +467,7 @@ int run_s2tc(const DevS2tc& dc, const float* x, float* out, const int32_t* lengt
     case 45: return launch_s2tc_t<45>(a, nwg, stream);
     case 61: return launch_s2tc_t<61>(a, nwg, stream);
     case 9: return launch_s2tc_t<9>(a, nwg, stream);
-    default: set_error("run_s2tc: no instance for s2tc_dbg = %d", opts().kernel_dbg); return DISSC_EINVAL;
+    default: set_error("run_s2tc: no instance for kernel_dbg = %d", opts().kernel_dbg); return DISSC_EINVAL;
   }
 }
 

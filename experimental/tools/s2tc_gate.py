@@ -29,12 +29,12 @@ for name, lin in shapes:
           f"({gf / t1:6.1f} algorithmic, {gf * 15 / 21 / t1:6.1f} executed TFLOP/s)   x{t0 / t1:.3f}", flush=True)
 print(f"conv1..4: direct {tot[0]:.3f} ms, toom-cook {tot[1]:.3f} ms")
 for mode in (0, 1):
-    L.dissc_set_option(b"s2tc_xmode", mode)
+    dissc_amd.check(L.dissc_set_option(b"s2tc_xmode", mode), "set_option s2tc_xmode")
     print(f"conv1 xmode {mode}: {bench(32, 512, 31999, 1) * 1e3:8.1f} us", flush=True)
-L.dissc_set_option(b"s2tc_xmode", 0)
+dissc_amd.check(L.dissc_set_option(b"s2tc_xmode", 0), "set_option s2tc_xmode")
 for dbg, what in ((1, "no transform"), (2, "no MFMAs"), (4, "no epilogue"), (8, "no window staging"), (9, "no staging, no transform"),
                   (13, "MFMA loop with A loads and B reads only"), (29, "... without the A loads"), (45, "... without the B reads"),
                   (61, "MFMAs + barriers only"), (7, "skeleton + staging"), (15, "skeleton")):
-    L.dissc_set_option(b"s2tc_dbg", dbg)
+    dissc_amd.check(L.dissc_set_option(b"kernel_dbg", dbg), "set_option kernel_dbg")
     print(f"conv1 knock-out {dbg:2d} ({what}): {bench(32, 512, 31999, 1) * 1e3:8.1f} us", flush=True)
-L.dissc_set_option(b"s2tc_dbg", 0)
+dissc_amd.check(L.dissc_set_option(b"kernel_dbg", 0), "set_option kernel_dbg")

@@ -187,8 +187,8 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *   pairw_chv (2)        [experimental] respair_wino.hip: 2 = one 12-wave workgroup per CU, 1 = two 6-wave workgroups with half the tile
  *   graphs (0)           [experimental] generator forwards of B * Tmax <= graph_frames (2048) are captured once into a hipGraph
  *                        and replayed (off: slower than the plain three-stream launches on ROCm 7.2)
- *   wino (1)             read at dissc_gen_create: 1 = ResBlock convs with C >= wino_min_c (64; at C = 64 those with k >=
- *                        wino_c64_kmin = 3) run in the Toom-Cook F(4,3) transform domain (conv_wino.hip), 0 = all direct,
+ *   wino (1)             read at dissc_gen_create: 1 = ResBlock convs with C >= 64 (at C = 64 those with k >= 3) run in the
+ *                        Toom-Cook F(4,3) transform domain (conv_wino.hip), 0 = all direct,
  *                        2 = dissc_conv1d uses it too (tests)
  *   wino_sv (1)          conv_wino.hip, C >= 128: the 12 waves of a workgroup share the input transform (one barrier per
  *                        8 channels) instead of every wave forming its own tile; bit-identical, faster (0 = private tiles)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Knock-out timings of conv_wino_kernel (option wino_dbg: 1 no transform, 2 no MFMAs, 4 no epilogue, 8 no staging)."""
+"""Knock-out timings of conv_wino_kernel (option kernel_dbg: 1 no transform, 2 no MFMAs, 4 no epilogue, 8 no staging)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, dissc_amd
@@ -9,9 +9,7 @@ shapes = [(256, 11, 1, 2500), (256, 7, 1, 2500), (256, 3, 1, 2500), (128, 11, 5,
 if os.environ.get('WINO_SHAPES'):
     shapes = [tuple(int(v) for v in t.split('x')) for t in os.environ['WINO_SHAPES'].split(',')]
 for C, k, d, Ln in shapes:
-  for cpr in (32,):
-    check(L.dissc_set_option(b"wino_cpr", cpr), "opt")
-    out = [f"cpr{cpr}"]
+    out = []
     for dbg in [int(x) for x in os.environ.get('WINO_DBGS', '0,1,2,4,8,13,6,15').split(',')]:
         check(L.dissc_set_option(b"kernel_dbg", dbg), "opt")
         ms = ctypes.c_float()
