@@ -150,41 +150,8 @@ __global__ void train_bn_bwd_apply_kernel(const float* __restrict__ da, const fl
 }
 
 // per-utterance partial weight gradient: part[b][co][ci][j] = sum_t dz[b][co][t] * a_in[b][ci][t + j - pad]
-constexpr int WG_T = 64;
-__global__ void __launch_bounds__(256) train_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ ain,
-                                                          int Cout, int Cin, int K, int L, int ld_o, int ld_i,
-                                                          float* __restrict__ part) {
-  __shared__ float ds[16][WG_T];
-  __shared__ float as[16][WG_T + 4];
-  const int b = blockIdx.z, co0 = blockIdx.x * 16, ci0 = blockIdx.y * 16;
-  const int col = threadIdx.x >> 4, cil = threadIdx.x & 15;
-  const int pad = (K - 1) / 2;
-  float acc[3] = {0.f, 0.f, 0.f};
-  for (int t0 = 0; t0 < L; t0 += WG_T) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < 16 * WG_T; e += 256) {
-      const int r = e / WG_T, u = e - r * WG_T;
-      const int t = t0 + u;
-      ds[r][u] = (t < L && co0 + r < Cout) ? dz[((size_t)b * Cout + co0 + r) * ld_o + t] : 0.f;
-    }
-    for (int e = threadIdx.x; e < 16 * (WG_T + 2); e += 256) {
-      const int r = e / (WG_T + 2), u = e - r * (WG_T + 2);
-      const int t = t0 + u - pad;
-      as[r][u] = (t >= 0 && t < L && ci0 + r < Cin) ? ain[((size_t)b * Cin + ci0 + r) * ld_i + t] : 0.f;
-    }
-    __syncthreads();
-    for (int u = 0; u < WG_T; ++u) {
-      const float d = ds[col][u];
-      for (int j = 0; j < K && j < 3; ++j) acc[j] = fmaf(d, as[cil][u + j], acc[j]);
-    }
-  }
-  if (co0 + col < Cout && ci0 + cil < Cin)
-    for (int j = 0; j < K && j < 3; ++j)
-      part[(((size_t)b * Cout + co0 + col) * Cin + ci0 + cil) * K + j] = acc[j];
-}
-
-// dw[i] = sum_b part[b][i] (fixed order)
-// The same product on the matrix cores (k = 3 layers with >= 32 output rows): per utterance a [Cout x L] x [L x 3 Cin]
+// On the matrix cores (every wide layer of the three models has k = 3; dissc_train_create refuses anything else): per
+// utterance a [Cout x L] x [L x 3 Cin]
 // GEMM whose reduction axis is time.  One workgroup = 32 output rows x (4 waves x 32 input channels); a k-step of
 // v_mfma_f32_32x32x2 is two time positions, the three taps are three accumulators fed from the same LDS window
 // shifted by one.  Rows are padded to an odd stride so that the fragment reads (32 rows x 1 column) are conflict-free.
@@ -278,6 +245,7 @@ __global__ void __launch_bounds__(256) train_wgrad_mfma_kernel(const float* __re
   }
 }
 
+// dw[i] = sum_b part[b][i] (fixed order)
 __global__ void train_reduce_b_kernel(const float* __restrict__ part, int B, size_t n, float* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -514,15 +482,17 @@ __global__ void __launch_bounds__(256) train_spk_grad_kernel(const float* __rest
   }
 }
 
-// torch.optim.Adam (amsgrad False, weight_decay 0) over the flat trainable region
+// torch.optim.Adam (amsgrad False, weight_decay 0) over the flat trainable region.  omb1 / omb2 = 1 - beta, rounded
+// ONCE from double as torch does: 1.f - 0.999f is 0.99998713e-3, which made exp_avg_sq 1.3e-5 too small in relative
+// terms (200 x fp32 rounding; tests/test_gpu_train_stages.py)
 __global__ void train_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                  float* __restrict__ v, size_t n, float b1, float b2, float eps, float step_size,
-                                  float bc2_sqrt) {
+                                  float* __restrict__ v, size_t n, float omb1, float b2, float omb2, float eps,
+                                  float step_size, float bc2_sqrt) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float gi = g[i];
-  const float mi = m[i] + (1.f - b1) * (gi - m[i]);  // exp_avg.lerp_(grad, 1 - beta1)
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  const float mi = m[i] + omb1 * (gi - m[i]);  // exp_avg.lerp_(grad, 1 - beta1)
+  const float vi = b2 * v[i] + omb2 * gi * gi;
   m[i] = mi;
   v[i] = vi;
   const float denom = sqrtf(vi) / bc2_sqrt + eps;
@@ -591,6 +561,9 @@ struct dissc_trainer {
   float *id2mean = nullptr, *id2std = nullptr;
   int n_stats = 0;
   long long step = 0;
+  // diagnostics (dissc_train_debug_read): views into the workspace of the last step and its shape
+  float *dbg_x0 = nullptr, *dbg_dx0 = nullptr;
+  int dbg_B = 0, dbg_ld = 0;
   ~dissc_trainer() {
     for (float* p : {P, G, M, V, id2mean, id2std})
       if (p) (void)hipFree(p);
@@ -721,6 +694,10 @@ int dissc_train_create(int kind, const DisscTensor* tensors, size_t n, dissc_tra
       return fail(DISSC_EINVAL);
     }
     if (l.cout >= 32) {  // wide: matrix-core convs, forward and backward-data
+      if (l.k != 3) {  // train_wgrad_mfma_kernel holds exactly three taps
+        set_error("dissc_train_create: wide layer '%s' must have k = 3", l.conv.c_str());
+        return fail(DISSC_EINVAL);
+      }
       if ((rc = make_conv(w->data, byname[l.conv + ".bias"]->data, l.cout, l.cin, l.k, 1, l.fwd))) return fail(rc);
       std::vector<float> wt((size_t)l.cin * l.cout * l.k);
       for (int co = 0; co < l.cout; ++co)
@@ -768,31 +745,49 @@ long long dissc_train_tensor_numel(dissc_trainer_t t, int i) {
 }
 long long dissc_train_steps(dissc_trainer_t t) { return t ? t->step : 0; }
 
-// which: 0 = value, 1 = gradient of the last step (trainable tensors only); synchronous copy to the host
+// which: 0 = value; trainable tensors only: 1 = gradient of the last step, 2 / 3 = Adam's exp_avg / exp_avg_sq;
+// synchronous copy to the host
 int dissc_train_read(dissc_trainer_t t, int i, int which, float* host_out, void* stream) {
-  if (!t || i < 0 || i >= (int)t->params.size() || !host_out || which < 0 || which > 1 ||
-      (which == 1 && !t->params[i].trainable)) {
+  if (!t || i < 0 || i >= (int)t->params.size() || !host_out || which < 0 || which > 3 ||
+      (which != 0 && !t->params[i].trainable)) {
     set_error("dissc_train_read: bad argument");
     return DISSC_EINVAL;
   }
   DISSC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  const float* src = (which == 0 ? t->P : t->G) + t->params[i].off;
-  DISSC_HIP_CHECK(hipMemcpy(host_out, src, t->params[i].numel * sizeof(float), hipMemcpyDeviceToHost));
+  const float* base = which == 0 ? t->P : which == 1 ? t->G : which == 2 ? t->M : t->V;
+  DISSC_HIP_CHECK(hipMemcpy(host_out, base + t->params[i].off, t->params[i].numel * sizeof(float), hipMemcpyDeviceToHost));
   return DISSC_OK;
 }
 
-// Diagnostics: copy an activation buffer of the LAST step out of the caller's workspace (valid until the next step).
-// which: 0 z (conv output), 1 a (after BatchNorm / LeakyReLU), 2 da, 3 dz; layer -1: x0 (which 0) / dx0 (which 2).
-static float *g_dbg_x0 = nullptr, *g_dbg_dx0 = nullptr;
+// Diagnostics: copy a buffer of the LAST step out of the caller's workspace (valid until the next step on this handle
+// or until the workspace is reused).  which: 0 z (conv output), 1 a (after BatchNorm / LeakyReLU), 2 da, 3 dz -- rows
+// of ld = L rounded up to 4 floats, [B][cout][ld]; 4 / 5 the batch mean / invstd of a BatchNorm layer (cout floats).
+// layer -1: x0 (which 0) / dx0 (which 2).  A scalar head has no a / da (its z is its output, its dz comes from the loss).
+// n: floats to copy, at most the buffer's size.
 int dissc_train_debug_read(dissc_trainer_t t, int layer, int which, float* host_out, size_t n, void* stream) {
-  if (!t || !host_out || layer < -1 || layer >= (int)t->layers.size() || which < 0 || which > 3) return DISSC_EINVAL;
-  const float* src = nullptr;
-  if (layer < 0) src = which == 0 ? g_dbg_x0 : g_dbg_dx0;
-  else {
-    TLayer& l = t->layers[layer];
-    src = which == 0 ? l.z : which == 1 ? l.a : which == 2 ? l.da : l.dz;
+  if (!t || !host_out || layer < -1 || layer >= (int)t->layers.size() || which < 0 || which > 5 || !t->dbg_x0) {
+    set_error("dissc_train_debug_read: bad argument, or no step has run");
+    return DISSC_EINVAL;
   }
-  if (!src) return DISSC_EINVAL;
+  const float* src = nullptr;
+  size_t have = 0;
+  if (layer < 0) {
+    src = which == 0 ? t->dbg_x0 : which == 2 ? t->dbg_dx0 : nullptr;
+    have = (size_t)t->dbg_B * 2 * t->E * t->dbg_ld;
+  } else {
+    TLayer& l = t->layers[layer];
+    if (which >= 4) {
+      if (l.has_bn) src = which == 4 ? l.mean : l.invstd;
+      have = (size_t)l.cout;
+    } else {
+      if (l.cout >= 32 || which == 0 || which == 3) src = which == 0 ? l.z : which == 1 ? l.a : which == 2 ? l.da : l.dz;
+      have = (size_t)t->dbg_B * l.cout * t->dbg_ld;
+    }
+  }
+  if (!src || n > have) {
+    set_error("dissc_train_debug_read: layer %d has no buffer %d of %zu floats", layer, which, n);
+    return DISSC_EINVAL;
+  }
   DISSC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   DISSC_HIP_CHECK(hipMemcpy(host_out, src, n * sizeof(float), hipMemcpyDeviceToHost));
   return DISSC_OK;
@@ -844,8 +839,10 @@ int dissc_train_step(dissc_trainer_t t, const int64_t* seq, const int64_t* spk, 
   };
   float* x0 = take(t_act_floats(B, 64, ld));
   float* dx0 = take(t_act_floats(B, 64, ld));
-  g_dbg_x0 = x0;
-  g_dbg_dx0 = dx0;
+  t->dbg_x0 = x0;
+  t->dbg_dx0 = dx0;
+  t->dbg_B = B;
+  t->dbg_ld = ld;
   size_t wmax = 0;
   for (auto& l : t->layers) {
     l.z = take(t_act_floats(B, l.cout, ld));
@@ -918,15 +915,11 @@ int dissc_train_step(dissc_trainer_t t, const int64_t* seq, const int64_t* spk, 
                          l.has_bn ? G(l.be) : (const float*)nullptr, B, l.cout, L, ld, l.has_bn ? 1 : 0, l.leaky ? 1 : 0,
                          l.dz);
       // weight / bias gradients
-      if (l.k == 3)
-        hipLaunchKernelGGL(train_wgrad_mfma_kernel, dim3((l.cout + 31) / 32, (l.cin + 127) / 128, B * WGM_SPLIT),
-                           dim3(256), 0, st, l.dz, in, l.cout, l.cin, L, ld, ld, part);
-      else
-        hipLaunchKernelGGL(train_wgrad_kernel, dim3((l.cout + 15) / 16, (l.cin + 15) / 16, B), dim3(256), 0, st, l.dz, in,
-                           l.cout, l.cin, l.k, L, ld, ld, part);
+      hipLaunchKernelGGL(train_wgrad_mfma_kernel, dim3((l.cout + 31) / 32, (l.cin + 127) / 128, B * WGM_SPLIT),
+                         dim3(256), 0, st, l.dz, in, l.cout, l.cin, L, ld, ld, part);
       const size_t nw = (size_t)l.cout * l.cin * l.k;
       hipLaunchKernelGGL(train_reduce_b_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, part,
-                         l.k == 3 ? B * WGM_SPLIT : B, nw, G(l.w));
+                         B * WGM_SPLIT, nw, G(l.w));
       hipLaunchKernelGGL(train_bias_grad_kernel, dim3(l.cout), dim3(256), 0, st, l.dz, B, l.cout, L, ld, G(l.b));
       // input gradient: the same conv with W^T, taps flipped (accumulating where the input feeds two layers)
       if ((rc = run_conv(l.bwd, l.dz, din, acc_in ? din : nullptr, nullptr, nullptr, L, 1, B, l.cout, ld, ld, L, 1.0f,
@@ -944,7 +937,8 @@ int dissc_train_step(dissc_trainer_t t, const int64_t* seq, const int64_t* spk, 
   const double b1 = 0.9, b2 = 0.999;
   const double bc1 = 1.0 - pow(b1, (double)t->step), bc2 = 1.0 - pow(b2, (double)t->step);
   hipLaunchKernelGGL(train_adam_kernel, dim3((unsigned)((t->n_train + 255) / 256)), dim3(256), 0, st, t->P, t->G, t->M,
-                     t->V, t->n_train, (float)b1, (float)b2, 1e-8f, (float)((double)lr / bc1), (float)sqrt(bc2));
+                     t->V, t->n_train, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), 1e-8f, (float)((double)lr / bc1),
+                     (float)sqrt(bc2));
   for (auto& l : t->layers) {
     if (l.cout < 32) continue;
     const size_t nf = (size_t)(l.fwd.Mpad / 32) * l.fwd.nchunk * l.k * 512;

@@ -24,6 +24,14 @@ from ._lib import check, lib
 KINDS = {"len": 0, "new": 1, "base": 2}
 MASKING_RATE = {"len": 0.2, "new": 0.4, "base": 0.4}  # reference constructors' masking_rate defaults
 PE_DROPOUT = 0.4                                       # PositionalEncoding(dropout=0.4), model/pitch_predictor.py:7
+TAPS = {"z": 0, "a": 1, "da": 2, "dz": 3, "mean": 4, "invstd": 5}  # ``which`` of dissc_train_debug_read
+
+
+def layer_names(kind):
+    """the conv layers in the engine's order (dissc_train_create): trunk, head branches, then the scalar heads"""
+    if kind == "len":
+        return ["cnn1"] + [f"cnn1{i}" for i in range(1, 7)] + ["cnn2"]
+    return ["cnn1"] + [f"cnn1{i}" for i in range(1, 8)] + ["cnn2", "cnn_class1", "cnn_reg1", "cnn_class2", "cnn_reg2"]
 
 
 def _bind():
@@ -45,6 +53,7 @@ def _bind():
     lib.dissc_train_steps.argtypes = [vp]
     lib.dissc_train_steps.restype = ctypes.c_longlong
     lib.dissc_train_read.argtypes = [vp, i32, i32, vp, vp]
+    lib.dissc_train_debug_read.argtypes = [vp, i32, i32, vp, ctypes.c_size_t, vp]
 
 
 _bind()
@@ -67,6 +76,7 @@ class Trainer:
         self._ws = None
         self._gen = torch.Generator().manual_seed(int(seed))
         self._nbt = {k: int(v) for k, v in self._sd0.items() if k.endswith("num_batches_tracked")}
+        self._last = None  # (B, L) of the last step: the shape of the taps
 
     def to(self, device):
         self.device = torch.device(f"cuda:{device}" if isinstance(device, int) else device)
@@ -142,6 +152,7 @@ class Trainer:
                                        self._ws.data_ptr(), need, _lib.current_stream_ptr(dev)), "dissc_train_step")
         for k in self._nbt:
             self._nbt[k] += 1
+        self._last = (B, L)
         return loss[0]
 
     def _read(self, i, which):
@@ -164,12 +175,49 @@ class Trainer:
                 out[k] = got[k].view(v.shape).to(v.dtype)
         return out
 
-    def grads(self):
-        """{name: gradient of the last step} for the trainable tensors"""
+    def _trainable(self, which):
         self._ensure()
         skip = ("running_mean", "running_var")
-        return {name: self._read(i, 1).view(self._sd0[name].shape) for i, name in enumerate(self._names)
+        return {name: self._read(i, which).view(self._sd0[name].shape) for i, name in enumerate(self._names)
                 if not name.endswith(skip) and name != "pe.pe"}
+
+    def grads(self):
+        """{name: gradient of the last step} for the trainable tensors"""
+        return self._trainable(1)
+
+    def adam_state(self):
+        """({name: exp_avg}, {name: exp_avg_sq}, steps taken) of torch.optim.Adam for the trainable tensors"""
+        return self._trainable(2), self._trainable(3), int(lib.dissc_train_steps(self._h))
+
+    # -- diagnostics: the buffers of the last step --------------------------------------------------------
+    def layers(self):
+        """conv layer names in the engine's order; the scalar heads (one output channel) come last"""
+        return layer_names(self.kind)
+
+    def tap(self, layer, which=None):
+        """A buffer of the LAST step as a CPU tensor with the row padding stripped.  layer: a name of ``layers()`` and
+        which: 'z' conv output, 'a' activation, 'da' / 'dz' their gradients ([B, C, L]; a head has 'z' and 'dz' only,
+        [B, L]), 'mean' / 'invstd' the batch statistics of a BatchNorm layer ([C]); or layer 'x0' / 'dx0': the
+        embedding and its gradient ([B, 64, L]).  Valid until the next step or any other use of the workspace."""
+        self._ensure()
+        if self._last is None:
+            raise _lib.DisscError("Trainer.tap: no step has run")
+        B, L = self._last
+        ld = (L + 3) // 4 * 4
+        if layer in ("x0", "dx0"):
+            li, w, C = -1, (0 if layer == "x0" else 2), 64
+        else:
+            li, w = self.layers().index(layer), TAPS[which]
+            C = 1 if layer in self.layers()[-(1 if self.kind == "len" else 2):] else 128
+        stats = li >= 0 and w >= 4
+        out = torch.empty(C if stats else B * C * ld, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            check(lib.dissc_train_debug_read(self._h, li, w, out.data_ptr(), out.numel(),
+                                             _lib.current_stream_ptr(self.device)), "dissc_train_debug_read")
+        if stats:
+            return out
+        out = out.view(B, C, ld)[:, :, :L]
+        return (out[:, 0] if C == 1 else out).contiguous()
 
 
 # ---------------------------------------------------------------------------------------------------------

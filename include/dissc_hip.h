@@ -499,14 +499,20 @@ size_t dissc_train_workspace_bytes(dissc_trainer_t t, int B, int L);
 int dissc_train_step(dissc_trainer_t t, const int64_t* seq, const int64_t* spk, const float* target, const float* keep,
                      const float* pe_mult, int B, int L, float pad_value, float lr, float* loss_out, void* workspace,
                      size_t workspace_bytes, void* stream);
-/* state access: tensors in a fixed order (trainable ones first); which = 0 value, 1 gradient of the last step */
+/* state access: tensors in a fixed order (trainable ones first); which = 0 value; trainable tensors only: 1 gradient
+ * of the last step, 2 / 3 torch.optim.Adam's exp_avg / exp_avg_sq (DISSC_EINVAL for running statistics and "pe.pe") */
 int dissc_train_num_tensors(dissc_trainer_t t);
 const char* dissc_train_tensor_name(dissc_trainer_t t, int i);
 long long dissc_train_tensor_numel(dissc_trainer_t t, int i);
 long long dissc_train_steps(dissc_trainer_t t);
 int dissc_train_read(dissc_trainer_t t, int i, int which, float* host_out, void* stream);
-/* diagnostics: an activation buffer of the last step ([B][C][ld], ld = L rounded up to 4): which 0 conv output,
- * 1 activation, 2 gradient w.r.t. the activation, 3 gradient w.r.t. the conv output; layer -1 = the embedding */
+/* diagnostics: a buffer of this handle's LAST step, copied out of the caller's workspace (valid until the next step or
+ * any other use of that workspace; DISSC_EINVAL before the first step).  layer: index in the engine's order (trunk, head
+ * branches, scalar heads), or -1 = the embedding.  which: 0 conv output z, 1 activation a, 2 gradient w.r.t. a,
+ * 3 gradient w.r.t. z -- [B][cout][ld] floats, ld = L rounded up to 4 (columns L .. ld-1 are padding and hold
+ * nothing); 4 / 5 batch mean / 1/sqrt(var + eps) of the layer's BatchNorm, cout floats (DISSC_EINVAL for a layer
+ * without BatchNorm).  layer -1: which 0 = x0, 2 = dx0, [B][64][ld].  A scalar head has which 0 (its output) and 3 (written
+ * by the loss) only.  n: floats to copy, at most the buffer's size. */
 int dissc_train_debug_read(dissc_trainer_t t, int layer, int which, float* host_out, size_t n, void* stream);
 
 #ifdef __cplusplus

@@ -92,7 +92,7 @@ def len_sum_loss(preds, lens, pad_idx=-1):
 def pitch_loss(cls, reg, gts, spk_ids, id2mean, id2std, pad_idx=-100):
     mask = gts != pad_idx
     voiced = gts != 0
-    loss1 = (mask * F.binary_cross_entropy_with_logits(cls, voiced.float(), reduction="none")).sum()
+    loss1 = (mask * F.binary_cross_entropy_with_logits(cls, voiced.to(cls.dtype), reduction="none")).sum()
     std, mean = id2std[spk_ids.long()], id2mean[spk_ids.long()]
     loss2 = (mask * ((mean + std * reg) - (mean + std * gts)).abs() * voiced).sum()
     return 100 * loss1 + loss2
