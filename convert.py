@@ -62,6 +62,9 @@ def build_parser():
     ap.add_argument("--id_to_spkr", required=True, help="pickled speaker list (index = id)")
     ap.add_argument("--target_speakers", nargs="+", required=True)
     ap.add_argument("--no_pred_len", action="store_true", help="keep the source rhythm (infer.py without --pred_len)")
+    ap.add_argument("--precision", default=None, choices=["fp32", "split_bf16"],
+                    help="arithmetic of the encoder AND the generator (default: the process options, exact fp32); split_bf16 = "
+                         "their matrix-pipe-bound layers on the bf16 matrix cores (opt-in).  The predictors stay fp32")
     ap.add_argument("--round_seconds", default=16384.0, type=float,
                     help="input audio x targets per rank and round: each round is gathered, written and freed.  TWO "
                          "collectives per round: a 16-byte all_reduce(MAX) of the exchange-buffer geometry (predicted "
@@ -90,7 +93,8 @@ def main(argv=None):
     spk_id = formats.spk_id_dict_from_list(id_to_spkr)
     targets = [spk_id[t] for t in a.target_speakers]
 
-    enc = SpeechEncoder.by_name(a.model_name, a.quantizer_name, a.vocab_size, checkpoint_dir=a.hubert_dir).to(device)
+    enc = SpeechEncoder.by_name(a.model_name, a.quantizer_name, a.vocab_size, checkpoint_dir=a.hubert_dir,
+                                 precision=a.precision).to(device)
     len_model = None
     if not a.no_pred_len:
         len_model = LenPredictor(n_tokens=a.n_tokens, n_speakers=len(spk_id)).to(device)
@@ -108,7 +112,7 @@ def main(argv=None):
         config_file, cp_g = os.path.join(os.path.split(a.checkpoint_file)[0], "config.json"), a.checkpoint_file
     with open(config_file) as f:
         h = AttrDict(json.loads(f.read()))
-    generator = CodeGenerator(h).to(device)
+    generator = CodeGenerator(h, precision=a.precision).to(device)
     generator.load_state_dict(torch.load(cp_g, map_location="cpu")["generator"])
     generator.eval()
     generator.remove_weight_norm()

@@ -103,16 +103,18 @@ def partial_fingerprint(args):
         for fn in sorted(os.listdir(ck)):
             st = os.stat(os.path.join(ck, fn))
             ck_files.append([fn, st.st_size, int(st.st_mtime)])
-    return {"base_dir": os.path.abspath(args.base_dir), "model_name": args.model_name, "quantizer_name": args.quantizer_name,
-            "vocab_size": int(args.vocab_size), "f0": args.f0, "checkpoint_dir": ck, "checkpoint_files": ck_files}
+    fp = {"base_dir": os.path.abspath(args.base_dir), "model_name": args.model_name, "quantizer_name": args.quantizer_name,
+          "vocab_size": int(args.vocab_size), "f0": args.f0, "checkpoint_dir": ck, "checkpoint_files": ck_files}
+    if getattr(args, "precision", None) is not None:  # (absent = the default: leftovers of runs without the flag stay valid)
+        fp["precision"] = args.precision
+    return fp
 
 
 def partial_header(args):
     return (json.dumps({"dissc_encode_partial": 2, "fingerprint": partial_fingerprint(args)}) + "\n").encode()
 
 
-def main(argv=None):
-    tm = _Timing()
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--model_name', default='hubert-base-ls960', help='Name for pretrained dense model name')
     parser.add_argument('--quantizer_name', default='kmeans', help='Name for quantising the hidden units')
@@ -125,7 +127,15 @@ def main(argv=None):
     parser.add_argument('--f0', default='yaapt', choices=['yaapt', 'zeros'],
                         help="'yaapt': track F0 like the reference's encoder does; 'zeros': write an all-unvoiced "
                              "track (only valid for the --pred_pitch flows, which never read it)")
-    args = parser.parse_args(argv)
+    parser.add_argument('--precision', default=None, choices=['fp32', 'split_bf16'],
+                        help="encoder arithmetic (default: the process option, exact fp32); 'split_bf16': feature convs and "
+                             "linears on the bf16 matrix cores (opt-in; may flip a unit per utterance)")
+    return parser
+
+
+def main(argv=None):
+    tm = _Timing()
+    args = build_parser().parse_args(argv)
 
     if args.f0 == 'zeros':
         print("WARNING: data/encode.py --f0 zeros writes an all-zero (fully unvoiced) 'f0' track. It is only valid "
@@ -136,7 +146,7 @@ def main(argv=None):
     from dissc_amd.hubert import SpeechEncoder
     encoder = SpeechEncoder.by_name(dense_model_name=args.model_name, quantizer_model_name=args.quantizer_name,
                                     vocab_size=args.vocab_size, deduplicate=False,
-                                    checkpoint_dir=args.checkpoint_dir).to(args.device)
+                                    checkpoint_dir=args.checkpoint_dir, precision=args.precision).to(args.device)
     os.makedirs(Path(args.out_file).parent.absolute(), exist_ok=True)
     tm.add('encoder_load')
     files = os.listdir(args.base_dir)

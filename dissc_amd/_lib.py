@@ -86,6 +86,9 @@ def _load():
     L.dissc_expand.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp]
     L.dissc_hubert_create.argtypes = [i32, ctypes.POINTER(DisscTensor), ctypes.c_size_t, vp, i32,
                                       ctypes.POINTER(vp)]
+    L.dissc_hubert_create_ex.argtypes = [i32, ctypes.POINTER(DisscTensor), ctypes.c_size_t, vp, i32, i32,
+                                         ctypes.POINTER(vp)]
+    L.dissc_hubert_precision.argtypes = [vp]
     L.dissc_hubert_destroy.argtypes = [vp]
     L.dissc_hubert_destroy.restype = None
     L.dissc_hubert_frames.argtypes = [i32]
@@ -101,6 +104,8 @@ def _load():
     L.dissc_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     L.dissc_conv_bench.argtypes = [i32] * 9 + [ctypes.POINTER(ctypes.c_float)]
     L.dissc_conv1d_s2.argtypes = [vp, vp, vp, vp, vp] + [i32] * 9 + [vp]
+    L.dissc_conv1d_s2_prec.argtypes = [vp, vp, vp, vp, vp] + [i32] * 9 + [vp]
+    L.dissc_linear_prec.argtypes = [vp, vp, vp, vp, vp, vp] + [i32] * 7 + [vp]
     L.dissc_conv_s2_bench.argtypes = [i32] * 5 + [ctypes.POINTER(ctypes.c_float)]
     L.dissc_pair_bench.argtypes = [i32] * 8 + [ctypes.POINTER(ctypes.c_float)]
     L.dissc_respair1d.argtypes = [vp] * 8 + [i32] * 6 + [ctypes.c_float, i32, ctypes.c_float, i32, vp]

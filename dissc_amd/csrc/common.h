@@ -32,6 +32,7 @@ void set_error(const char* fmt, ...);
   X(multistream, 1, "multistream") \
   X(pair_dma, 1, "pair_dma") \
   X(precision, 0, "precision") \
+  X(enc_precision, 0, "enc_precision") \
   X(use_mfma32, 1, "mfma32") \
   X(ragged_enum, 1, "ragged_enum") \
   X(lin128, 1, "lin128") \
@@ -212,7 +213,8 @@ struct ConvArgs {
                         //    i % 8 + 8 * ((i / 8) / MT): the M tiles that read one input window follow each other on ONE XCD (one L2)
   int xcd_ntile, xcd_nb;  // time tiles per utterance / utterances of that enumeration
   int xcd_mg, xcd_span;   // M tiles per sweep (the weight slabs one sweep keeps L2-resident); ids per sweep = padded time tiles * xcd_mg
-  int prec;             // 0 exact fp32 MFMA; 1 split-bf16 ("bf16x3") on the bf16 matrix cores (opt-in)
+  int prec;             // 0 exact fp32 MFMA; 1 split-bf16 ("bf16x3") on the bf16 matrix cores (opt-in); 2 the same arithmetic on the
+                        // encoder's kernel (enc_bf3.hip: 1x1 and stride-2 convs)
   int m32;              // 1: weights packed for / launched on the 32x32x2 kernel (conv_mfma32.hip)
   int cfg32;            // tile shape id chosen for this launch (conv32_pick_cfg), -1 = the class default
   int CIN, M, KS, dil, nchunk;
@@ -261,8 +263,13 @@ void pack_conv_weights_bf3(const float* w, int Cout, int Cin, int KS, std::vecto
                            int& Mpad, int& nchunk);
 int launch_conv_bf3(const ConvArgs& a, int B, int Lmax_out, hipStream_t stream);
 int conv_bf3_tile_bn(int M);
-extern thread_local int g_conv_prec;   // precision make_conv packs for: opts().precision inside dissc_gen_create, else 0
-                          // (predictors and HuBERT feed integer decisions and always stay fp32)
+extern thread_local int g_conv_prec;   // precision make_conv packs for: opts().precision inside dissc_gen_create, 2 inside a
+                          // split-bf16 dissc_hubert_create_ex (the layers enc_bf3_supported takes), else 0 (the "precision" option
+                          // never reaches predictors or HuBERT: they feed integer decisions; HuBERT has "enc_precision")
+// the encoder's split-bf16 kernel (enc_bf3.hip): 1x1 convs and stride-2 VALID convs with k = 2 / 3; weights packed by
+// pack_conv_weights_bf3
+bool enc_bf3_supported(int Cout, int Cin, int KS, int dil, int groups, int stride, int pad_left);
+int launch_enc_bf3(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_t stream);
 
 // Host-side weight packing.  w: [Cout][Cin][KS] (Conv1d layout).  Returns the packed
 // buffer (Mpad/16 * nchunk * KS * 64 float4) and Mpad (M rounded up to 16).
@@ -286,7 +293,7 @@ struct DevConv {
   int up_np = 1, up_p0 = 0;                                 // ConvTranspose phase group (see ConvArgs)
   int act = 0;
   int m32 = 0;              // packed for the 32x32x2 kernel
-  int prec = 0;             // 1: packed as split-bf16 hi/lo fragments
+  int prec = 0;             // 1: packed as split-bf16 hi/lo fragments (conv_bf3.hip); 2: the same packing, run by enc_bf3.hip
   double macs_per_t = 0;  // MACs per input time step (algorithmic, zero taps excluded)
   int wino = 0;           // 1: packed for conv_wino_kernel (Toom-Cook F(4,3) transform-domain weights), 2: for conv_wino8_kernel
   int wr = 3;             // conv_wino8_kernel: taps per sub-filter (3: F(6,3), 4: F(5,4))

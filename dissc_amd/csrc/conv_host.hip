@@ -28,6 +28,8 @@ int make_conv(const float* w, const float* bias, int Cout, int Cin, int KS, int 
   const bool lin_big = (KS == 1 && Mg >= 256 && (Cg + KC - 1) / KC >= 8);
   dc.prec = (g_conv_prec == 1 && dc.m32 && stride == 1 && groups == 1 && (KS - 1) * dil <= MAX_TAP_SPAN && !lin_big)
                 ? 1 : 0;
+  // the encoder's route (a split-bf16 HuBERT handle): its own kernel, also for the linears and stride-2 convs refused above
+  if (g_conv_prec == 2 && dc.m32 && enc_bf3_supported(Cout, Cin, KS, dil, groups, stride, pad_left)) dc.prec = 2;
   if (dc.prec) pack_conv_weights_bf3(w, Cout, Cg, KS, packed, Mpad, nchunk);
   else if (dc.m32) pack_conv_weights32(w, Cout, Cg, KS, packed, Mpad, nchunk, groups);
   else pack_conv_weights(w, Cout, Cg, KS, packed, Mpad, nchunk, groups);

@@ -363,6 +363,7 @@ int launch_conv(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_t 
     set_error("launch_conv: activations must be 16-byte aligned with row strides %% 4 == 0");
     return DISSC_EINVAL;
   }
+  if (a.prec == 2) return launch_enc_bf3(a, B, Lmax_out, stride, stream);  // split-bf16 encoder layers (enc_bf3.hip)
   if (a.m32) return launch_conv32(a, B, Lmax_out, stride, stream);
   const int cfg = conv_cfg(a.M);
   if (stride == 2 && span <= MAX_TAP_SPAN && a.up == 1) {

@@ -9,7 +9,9 @@
 // Everything stays channels-first [B][C][ld] fp32 with time contiguous, so every dense layer
 // (strided feature convs, 1x1 projections, QKV/out/FFN linears, the grouped k=128 positional
 // conv, the centroid dot products) is the same fp32-MFMA implicit GEMM as the vocoder
-// (conv_mfma_kernel) with GELU / residual fused in its epilogue.  Attention is exact:
+// (conv_mfma_kernel) with GELU / residual fused in its epilogue.  A handle created with
+// enc_precision = 1 (dissc_hubert_create_ex) runs the feature convs 1..6 and every linear in
+// split-bf16 arithmetic instead (enc_bf3.hip); everything else is the same in both modes.  Attention is exact:
 // S = Q^T K (batched MFMA GEMM) -> row softmax -> O = V P^T (batched MFMA GEMM).
 // Ragged batches are per-utterance exact: GroupNorm statistics over valid frames only, zero
 // padding of the positional conv at each utterance's end, keys masked to T_b.
@@ -407,7 +409,7 @@ namespace dissc {
 }
 
 struct dissc_hubert {
-  Options opt;  // this handle's snapshot of the tuning options (common.h)
+  Options opt;  // this handle's snapshot of the tuning options (common.h); opt.enc_precision is the handle's arithmetic
   int n_layers = 6, H = 12, D = 768, F = 3072, CF = 512, K = 0;
   float* w0 = nullptr;   // conv0 [512][10]
   float* gn_g = nullptr; // GroupNorm affine
@@ -465,6 +467,22 @@ int dissc_hubert_frames(int n_samples) { return frames_of(n_samples); }
 
 int dissc_hubert_create(int n_layers, const DisscTensor* weights, size_t n_weights,
                         const float* centers, int n_centers, dissc_hubert_t* out) {
+  return dissc_hubert_create_ex(n_layers, weights, n_weights, centers, n_centers, -1, out);
+}
+
+int dissc_hubert_precision(dissc_hubert_t m) { return m ? m->opt.enc_precision : 0; }
+
+int dissc_hubert_create_ex(int n_layers, const DisscTensor* weights, size_t n_weights, const float* centers, int n_centers,
+                           int precision, dissc_hubert_t* out) {
+  if (precision < -1 || precision > 1) {
+    set_error("dissc_hubert_create_ex: precision %d (use -1 = the enc_precision option, 0 = fp32, 1 = split-bf16)", precision);
+    return DISSC_EINVAL;
+  }
+  const int prec = precision < 0 ? g_defaults.enc_precision : precision;  // this handle's arithmetic, fixed from here on
+  if (prec != 0 && prec != 1) {
+    set_error("dissc_hubert_create: option enc_precision = %d (0 = fp32, 1 = split-bf16)", prec);
+    return DISSC_EINVAL;
+  }
   if (!weights || !out || n_layers < 1 || n_layers > 12) {
     set_error("dissc_hubert_create: bad argument");
     return DISSC_EINVAL;
@@ -473,7 +491,14 @@ int dissc_hubert_create(int n_layers, const DisscTensor* weights, size_t n_weigh
   for (size_t i = 0; i < n_weights; ++i) by[weights[i].name] = &weights[i];
   dissc_hubert* m = new dissc_hubert();
   m->opt = g_defaults;  // frozen here
+  m->opt.enc_precision = prec;
   OptScope opt_scope(&m->opt);
+  // a split-bf16 handle packs hi / lo planes INSTEAD of the fp32 fragments for the layers enc_bf3.hip takes (the feature convs
+  // 1..6 and every linear; same bytes); conv0, the positional conv and everything that is not a conv stay fp32 in both modes
+  struct PrecScope {
+    explicit PrecScope(int p) { g_conv_prec = p ? 2 : 0; }
+    ~PrecScope() { g_conv_prec = 0; }
+  } prec_scope(prec);
   m->n_layers = n_layers;
   int rc = DISSC_OK;
   auto fail = [&](int code) {
@@ -887,6 +912,56 @@ int dissc_conv1d_s2(const float* x, const float* w_host, const float* bias_host,
     }
   }
   if (lout) (void)hipFree(lout);
+  return rc;
+}
+
+// dissc_conv1d_s2 (form 0) with the arithmetic as an argument: prec 0 = exact fp32, 1 = split-bf16 (enc_bf3.hip).
+int dissc_conv1d_s2_prec(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths_in, int B,
+                         int Cin, int Cout, int k, int ldx, int ldo, int Lmax_in, int act, int prec, void* stream_) {
+  if (prec != 0 && prec != 1) {
+    set_error("dissc_conv1d_s2_prec: prec %d (0 = fp32, 1 = split-bf16)", prec);
+    return DISSC_EINVAL;
+  }
+  if (prec == 1 && !enc_bf3_supported(Cout, Cin, k, 1, 1, 2, 0)) {
+    set_error("dissc_conv1d_s2_prec: no split-bf16 kernel for %d -> %d channels, k = %d", Cin, Cout, k);
+    return DISSC_EINVAL;
+  }
+  g_conv_prec = prec ? 2 : 0;
+  const int rc = dissc_conv1d_s2(x, w_host, bias_host, y, lengths_in, B, Cin, Cout, k, ldx, ldo, Lmax_in, act, 0, stream_);
+  g_conv_prec = 0;
+  return rc;
+}
+
+// Stand-alone linear as the encoder runs it (tests): x f32 [B,Cin,ld] -> y f32 [B,Cout,ld], columns [0, len_b) of every utterance,
+// y = W x + bias, then exact-erf GELU (act 1), then + res (res != NULL; same layout as y).  w HOST [Cout,Cin], bias HOST [Cout] or
+// NULL.  prec as above.  Synchronous; weights packed per call.
+int dissc_linear_prec(const float* x, const float* w_host, const float* bias_host, const float* res, float* y, const int32_t* lengths,
+                      int B, int Cin, int Cout, int ld, int Tmax, int act, int prec, void* stream_) {
+  if (!x || !w_host || !y || B <= 0 || Tmax <= 0 || Tmax > ld || Cin <= 0 || Cout <= 0 || (prec != 0 && prec != 1)) {
+    set_error("dissc_linear_prec: bad argument");
+    return DISSC_EINVAL;
+  }
+  if (prec == 1 && !enc_bf3_supported(Cout, Cin, 1, 1, 1, 1, 0)) {
+    set_error("dissc_linear_prec: no split-bf16 kernel for %d -> %d channels", Cin, Cout);
+    return DISSC_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream_;
+  DevConv dc;
+  g_conv_prec = prec ? 2 : 0;
+  int rc = make_conv(w_host, bias_host, Cout, Cin, 1, 1, dc, 1, 1, 0);
+  g_conv_prec = 0;
+  if (!rc) {
+    dc.act = act;
+    ConvIO io;
+    io.lengths_in = lengths; io.len_default = Tmax;
+    rc = run_conv_ex(dc, x, y, res, io, B, Cin, ld, ld, Tmax, 1.0f, res ? EPI_RES : EPI_STORE, st);
+  }
+  hipError_t e = hipStreamSynchronize(st);
+  free_conv(dc);
+  if (!rc && e != hipSuccess) {
+    set_error("dissc_linear_prec: %s", hipGetErrorString(e));
+    rc = DISSC_EHIP;
+  }
   return rc;
 }
 

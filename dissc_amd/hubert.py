@@ -73,7 +73,14 @@ def load_kmeans_centers(path):
 class HubertEncoder:
     """Dense HuBERT features (layer ``n_layers`` output) + optional k-means units."""
 
-    def __init__(self, state_dict, centers=None, n_layers=6):
+    _PRECISIONS = {"fp32": 0, "split_bf16": 1}
+
+    def __init__(self, state_dict, centers=None, n_layers=6, precision=None):
+        """precision (not in the reference): None = the process-wide "enc_precision" option (default exact fp32), "fp32", or
+        "split_bf16" (opt-in: the feature convs 1..6 and the linears on the bf16 matrix cores, include/dissc_hip.h)."""
+        if precision is not None and precision not in self._PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(self._PRECISIONS)} or None")
+        self.precision = precision
         sd = state_dict.get("model", state_dict) if isinstance(state_dict, dict) else state_dict
         if not any(k.startswith("post_extract_proj") for k in sd):
             sd = hf_to_fairseq(sd)
@@ -118,9 +125,10 @@ class HubertEncoder:
             table, keep = _lib.make_tensor_table(self._tensors())
             h = ctypes.c_void_p()
             c = self.centers
-            check(lib.dissc_hubert_create(self.n_layers, table, len(keep), c.data_ptr() if c is not None else None,
-                                          int(c.shape[0]) if c is not None else 0, ctypes.byref(h)),
-                  "dissc_hubert_create")
+            prec = -1 if self.precision is None else self._PRECISIONS[self.precision]
+            check(lib.dissc_hubert_create_ex(self.n_layers, table, len(keep), c.data_ptr() if c is not None else None,
+                                             int(c.shape[0]) if c is not None else 0, prec, ctypes.byref(h)),
+                  "dissc_hubert_create_ex")
             self._handle = h
 
     def __del__(self):
@@ -225,13 +233,13 @@ class SpeechEncoder:
         self.deduplicate = deduplicate
 
     @classmethod
-    def from_files(cls, hubert_ckpt, kmeans_file, layer=6, deduplicate=False):
+    def from_files(cls, hubert_ckpt, kmeans_file, layer=6, deduplicate=False, precision=None):
         sd = torch.load(hubert_ckpt, map_location="cpu", weights_only=False)
-        return cls(HubertEncoder(sd, load_kmeans_centers(kmeans_file), n_layers=layer), deduplicate)
+        return cls(HubertEncoder(sd, load_kmeans_centers(kmeans_file), n_layers=layer, precision=precision), deduplicate)
 
     @classmethod
     def by_name(cls, dense_model_name="hubert-base-ls960", quantizer_model_name="kmeans", vocab_size=100,
-                deduplicate=False, checkpoint_dir=None):
+                deduplicate=False, checkpoint_dir=None, precision=None):
         """textless downloads its checkpoints; offline we look them up in ``checkpoint_dir`` /
         $DISSC_CHECKPOINT_DIR: <dir>/<dense_model_name>.pt and <dir>/<quantizer>_<vocab>.{npy,bin,pt}"""
         d = checkpoint_dir or os.environ.get("DISSC_CHECKPOINT_DIR", "checkpoints/hubert")
@@ -241,7 +249,7 @@ class SpeechEncoder:
         if not os.path.exists(dense) or km is None:
             raise FileNotFoundError(f"need {dense} and {quantizer_model_name}_{vocab_size}.[npy|bin|pt] in {d} "
                                     "(no network access to download them)")
-        return cls.from_files(dense, km, layer=6, deduplicate=deduplicate)
+        return cls.from_files(dense, km, layer=6, deduplicate=deduplicate, precision=precision)
 
     def to(self, device):
         self.model.to(device)

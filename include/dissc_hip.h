@@ -134,6 +134,14 @@ int dissc_conv_transpose1d(const float* x, const float* w_host, const float* bia
  * lengths_in: device int32 [B] or NULL (= Lmax_in everywhere).  Synchronous; test / gate entry, weights packed per call. */
 int dissc_conv1d_s2(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths_in, int B,
                     int Cin, int Cout, int k, int ldx, int ldo, int Lmax_in, int act, int form, void* stream);
+/* dissc_conv1d_s2's direct form with the arithmetic as an argument: prec 0 = exact fp32, 1 = split-bf16 (enc_bf3.hip; k = 2 / 3,
+ * Cout >= 64). */
+int dissc_conv1d_s2_prec(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths_in, int B,
+                         int Cin, int Cout, int k, int ldx, int ldo, int Lmax_in, int act, int prec, void* stream);
+/* Stand-alone linear as the encoder runs it (tests): x f32 [B,Cin,ld] -> y f32 [B,Cout,ld] on columns [0, lengths[b]) (NULL = Tmax),
+ * y = W x + bias, exact-erf GELU if act 1, + res if res != NULL (layout of y).  w HOST [Cout,Cin]; prec as above.  Synchronous. */
+int dissc_linear_prec(const float* x, const float* w_host, const float* bias_host, const float* res, float* y,
+                      const int32_t* lengths, int B, int Cin, int Cout, int ld, int Tmax, int act, int prec, void* stream);
 /* Diagnostics: average ms of `iters` launches of one C -> C, k = 3, stride 2 conv + GELU on B rows of L input samples. */
 int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out);
 
@@ -151,7 +159,13 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *   precision (0)        0 = exact fp32 MFMA everywhere (default, bench.py's headline); 1 = split-bf16 GENERATOR
  *                        ("bf16x3": hi*hi + hi*lo + lo*hi on the bf16 matrix cores, fp32 accumulate; conv_bf3.hip,
  *                        resblock_bf3.hip) -- ~2^-17 product error, waveform RMS ~4e-6 vs the reference (bar 1e-4),
- *                        ~2x the fp32 rate.  Predictors and HuBERT feed integer decisions and always stay fp32.
+ *                        ~2x the fp32 rate.  Predictors and HuBERT feed integer decisions: `precision` never touches them;
+ *                        HuBERT has `enc_precision`.
+ *   enc_precision (0)    read at dissc_hubert_create: 0 = exact fp32 MFMA (default); 1 = split-bf16 ENCODER: the feature convs
+ *                        conv1..conv6 and every linear (post_extract_proj, qkv, out_proj, fc1, fc2) in the same hi*hi + hi*lo +
+ *                        lo*hi arithmetic (enc_bf3.hip); conv0 + GroupNorm, the LayerNorms, attention, the positional conv and the
+ *                        k-means step stay fp32.  Opt-in, never a default: the units it flips against float64 are counted and held
+ *                        to the derived bound of the fp32 path (tests/test_gpu_hubert_split_bf16.py).
  *   mfma32 (1)           use the 32x32x2 MFMA kernel for layers with >= 32 output rows
  *   conv_cfg_bm{16,32,64,128,256} / conv32_cfg_bm{32,64,128,256}
  *                        tile-shape id per GEMM-M class (tables in conv_mfma.hip / conv_mfma32.hip)
@@ -296,6 +310,12 @@ int dissc_expand(const int64_t* vals, const int32_t* lens_int, const int32_t* n,
 typedef struct dissc_hubert* dissc_hubert_t;
 int dissc_hubert_create(int n_layers, const DisscTensor* weights, size_t n_weights,
                         const float* centers, int n_centers, dissc_hubert_t* out);
+/* the same with the handle's arithmetic given explicitly instead of read from the process-wide "enc_precision" option:
+ * -1 = that option, 0 = exact fp32, 1 = split-bf16 (opt-in, see dissc_set_option); anything else DISSC_EINVAL */
+int dissc_hubert_create_ex(int n_layers, const DisscTensor* weights, size_t n_weights, const float* centers, int n_centers,
+                           int precision, dissc_hubert_t* out);
+/* the handle's arithmetic: 0 = fp32, 1 = split-bf16 */
+int dissc_hubert_precision(dissc_hubert_t m);
 void dissc_hubert_destroy(dissc_hubert_t m);
 /* frames produced for n_samples input samples: floor((n-400)/320)+1 for n >= 400 */
 int dissc_hubert_frames(int n_samples);

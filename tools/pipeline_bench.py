@@ -22,16 +22,18 @@ def main():
     ap.add_argument("--utts", type=int, default=8)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--precision", default=None, choices=["fp32", "split_bf16"],
+                    help="arithmetic of the encoder and the generator (convert.py --precision); the predictors stay fp32")
     a = ap.parse_args()
     dev = "cuda:0"
     n = int(a.seconds * 16000)
-    enc = HubertEncoder(synth.synth_hubert_state_dict(6), synth.synth_kmeans_centers(), 6).to(dev)
+    enc = HubertEncoder(synth.synth_hubert_state_dict(6), synth.synth_kmeans_centers(), 6, precision=a.precision).to(dev)
     lm = P.LenPredictor(100, 108).to(dev)
     lm.load_state_dict(synth.synth_len_state_dict(100, 108))
     lm.norm_mean, lm.norm_std = synth.synth_len_norm_stats()
     pm = P.PitchPredictor(100, 108).to(dev)
     pm.load_state_dict(synth.synth_pitch_state_dict("new", 100, 108))
-    g = dissc_amd.CodeGenerator(synth.VCTK_CONFIG).to(dev)
+    g = dissc_amd.CodeGenerator(synth.VCTK_CONFIG, precision=a.precision).to(dev)
     g.load_state_dict(synth.synth_generator_state_dict(0))
     g.eval().remove_weight_norm()
     wav = torch.stack([torch.from_numpy(synth.synth_waveform(n, seed=i)) for i in range(a.utts)]).to(dev)
@@ -83,6 +85,14 @@ def main():
         conv(dwaves, [6])
         wall_d.append(time.perf_counter() - t0)
     cwd = float(np.median(wall_d))
+    ev = []  # the same call between two HIP events on the current stream
+    for _ in range(a.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        conv(dwaves, [6])
+        e1.record()
+        torch.cuda.synchronize()
+        ev.append(e0.elapsed_time(e1))
     print(json.dumps({"utts": a.utts, "seconds_each": a.seconds, "ms": {k: round(med[k] * 1e3, 2) for k in ("encode", "infer", "resynth")},
                       "total_ms": round(tot * 1e3, 2), "input_audio_sec_per_sec": round(in_sec / tot, 1),
                       "encode_x_realtime": round(in_sec / med["encode"], 1),
@@ -90,6 +100,7 @@ def main():
                       "converter_wall_ms": round(cw * 1e3, 2), "converter_host_overhead_frac": round(cw / tot - 1.0, 4),
                       "converter_wall_ms_inputs_in_hbm": round(cwd * 1e3, 2),
                       "converter_overhead_frac_inputs_in_hbm": round(cwd / tot - 1.0, 4),
+                      "converter_event_ms_inputs_in_hbm": round(float(np.median(ev)), 2), "precision": a.precision or "default",
                       "converter_outputs": len(out)}))
 
 
