@@ -333,15 +333,19 @@ class YaaptTracker:
         return self._tws, need
 
     # -- the tracker -------------------------------------------------------------------------------------
-    def __call__(self, waveforms, host_dp=False):
+    def __call__(self, waveforms, host_dp=False, on_device=False):
         """list of 1-D float waveforms @fs -> list of float32 F0 tracks (one value per frame_space, 0 = unvoiced),
         each of len(arange(frame/2, n + frame - frame/2, hop)) values like pYAAPT's samp_values on the padded signal.
         Everything runs on the device (one D2H copy of the tracks at the end); host_dp=True runs the sequential
-        stages with the numpy functions above instead (kept as the readable form and for the tests)."""
+        stages with the numpy functions above instead (kept as the readable form and for the tests).
+        on_device=True skips that copy: (f0 f32 [B, F] device tensor, list of frame counts), row b valid in
+        [:counts[b]] and 0 beyond (dissc_amd.metrics consumes the tracks where they are)."""
         pad = self.flen // 2  # reference sr/dataset.py:29,33: 10 ms of zeros at both ends
         B = len(waveforms)
+        if on_device and host_dp:
+            raise ValueError("on_device=True returns the device stages' tensor: not with host_dp=True")
         if B == 0:
-            return []
+            return (torch.empty(0, 0, device=self.device), []) if on_device else []
         lens = [len(w) + 2 * pad for w in waveforms]
         N = (max(lens) + 3) // 4 * 4
         # page-locked staging, allocated once and reused (page-locking 20 MB costs tens of ms; the H2D copy inside
@@ -362,7 +366,10 @@ class YaaptTracker:
         st = self.spec_track(s, nfr, ntd)
         c1 = self.nccf(s["filt"], s["n_samples"], st["lag_min"], st["lag_max"])
         c2 = self.nccf(s["nlfilt"], s["n_samples"], st["lag_min"], st["lag_max"])
-        f0 = self.final_track_device(st, c1, c2).cpu().numpy()
+        f0 = self.final_track_device(st, c1, c2)
+        if on_device:
+            return f0, nfr
+        f0 = f0.cpu().numpy()
         return [f0[b, :nfr[b]].copy() for b in range(B)]
 
     def _host_stages(self, s, nfr, ntd):

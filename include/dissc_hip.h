@@ -488,6 +488,40 @@ int dissc_yaapt_final_track(const DisscYaaptTrackConfig* cfg, const float* tp1, 
                             size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Prosody metrics on device-side F0 tracks (csrc/prosody_metrics.hip).
+ * Replaces: the per-file numpy / scipy part of reference eval.py -- scipy.stats.wasserstein_distance on the two
+ * zero-extended tracks (eval.py:96-102) and aligned_ffe with utils.interp's nearest-neighbour resampling
+ * (eval.py:50-57, utils.py:39-45) -- restated in tests/eval_ref.py.
+ * tracks f32 [n_rows, ld] on the device (dissc_yaapt_final_track's output, one row per waveform); the tables are
+ * device i32 arrays of six columns per entry.  All arithmetic is IEEE double on the track values widened to double;
+ * every pair / interval is reduced in a fixed order, so its result does not depend on the batch around it.
+ * Asynchronous on `stream`, nothing is allocated.  The workspace queries return 0 today (every supported pair is
+ * sorted in LDS); the arguments are the place of a global-memory form for longer pairs.
+ *
+ * dissc_track_emd: first Wasserstein distance of n_pairs pairs (row_a, n_a, len_a, row_b, n_b, len_b): sample a =
+ *   tracks[row_a, 0:n_a] followed by len_a - n_a zeros (0 <= n_a <= min(len_a, ld), len_a >= 1), b alike; the sizes
+ *   may differ.  emd_out f64 [n_pairs] = sum |cdf_a - cdf_b| * delta over the merged sorted values, cdf = count /
+ *   size (scipy's definition); NaN for an entry that breaks the rules above.  max_pair_frames: an upper bound of
+ *   len_a + len_b over the table, at most DISSC_EMD_MAX_PAIR_FRAMES (DISSC_EINVAL beyond: the pair would not fit
+ *   the LDS of a workgroup); an entry above the bound given yields NaN.
+ * dissc_track_ffe: F0-frame-error of n_intervals intervals (row_ref, lo_ref, hi_ref, row_syn, lo_syn, hi_syn),
+ *   0 <= lo <= hi <= ld: the generated slice is resampled to the reference slice's length like utils.interp
+ *   (nearest neighbour on two linspace(0, 1, .) grids, the lower index on a tie; a length-1 slice becomes
+ *   target_len * value), ffe_out f64 [n_intervals] = share of frames with |(ref + 1e-4) / (syn + 1e-4) - 1| > 0.2,
+ *   NaN for an empty reference slice.  status_out i32 [n_intervals]: 0, DISSC_FFE_EMPTY_SYN (empty generated slice,
+ *   non-empty reference: the reference raises ValueError there; ffe_out is NaN) or DISSC_FFE_BAD_ENTRY.
+ * ------------------------------------------------------------------------- */
+#define DISSC_EMD_MAX_PAIR_FRAMES 40000
+#define DISSC_FFE_EMPTY_SYN 1
+#define DISSC_FFE_BAD_ENTRY 2
+size_t dissc_track_emd_workspace_bytes(int n_pairs, int max_pair_frames);
+int dissc_track_emd(const float* tracks, int n_rows, int ld, const int32_t* pairs, int n_pairs, int max_pair_frames,
+                    double* emd_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t dissc_track_ffe_workspace_bytes(int n_intervals);
+int dissc_track_ffe(const float* tracks, int n_rows, int ld, const int32_t* intervals, int n_intervals,
+                    double* ffe_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Band-limited sinc resampling.
  * Replaces: resampy.resample(data, sr, 16000) at reference data/preprocess.py:22 (and sr/dataset.py:226) --
  * an un-vendored third party; algorithm (Kaiser-windowed sinc table, linear table interpolation) restated in
