@@ -50,7 +50,8 @@ void set_error(const char* fmt, ...);
   X(wino, 1, "wino") \
   X(hubert_split, 1, "hubert_split") \
   X(pair_max_c, 32, "pair_max_c") \
-  X(pair_f23, 3, "pair_f23")
+  X(pair_f23, 3, "pair_f23") \
+  X(pair_tc6, 3, "pair_tc6")
 // options of the kernels that only DISSC_EXPERIMENTAL=1 builds carry (experimental/csrc: gates failed, kept for the record)
 #define DISSC_OPTION_LIST_EXPERIMENTAL(X) \
   X(graphs, 0, "graphs") \
@@ -348,11 +349,15 @@ struct DevPairW {
   float* b1 = nullptr;
   float* b2 = nullptr;
   int C = 0, KS = 0, dil = 1;
-  int form = 0;  // 0: respair_wino_kernel (F(4,3), Y exchanged through LDS); 1: respair32_f23_kernel (F(2,3), register-only)
+  int form = 0;  // 0: respair_wino_kernel (F(4,3), Y exchanged through LDS); register-only: 1: respair32/16_f23_kernel (F(2,3)),
+                 // 2: respair32_tc6_kernel (six points as F(3,4))
 };
 // register-only F(2,3) pairs of the 16- and 32-channel stages, k = 11 (respair_f23.hip, respair16_f23.hip)
 bool pair_f23_supported(int C, int KS, int dil);
 int pack_pair_f23(const float* w, float** dev, int C, int KS);
+// ... and on six points as F(3,4): the 32-channel stage, k = 7 / 11 (respair_f23.hip); launched by launch_pair_f23 (form 2)
+bool pair_tc6_supported(int C, int KS, int dil);
+int pack_pair_tc6(const float* w, float** dev, int C, int KS);
 int launch_pair_f23(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
                     int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream);
 // the F(4,3) form: experimental/csrc/respair_wino.hip in DISSC_EXPERIMENTAL=1 builds, experimental_stubs.hip otherwise
@@ -361,8 +366,9 @@ int pack_pairw43(const float* w, int C, int KS, float** dev);
 int launch_pairw43(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default, int len_mul,
                    int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream);
 bool pairw_supported(int C, int KS, int dil);
-// f23: the F(2,3) form (pair_f23_supported), else the F(4,3) one (pairw_supported)
-int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, bool f23, DevPairW& pw);
+// form: DevPairW::form -- 1 the F(2,3) form (pair_f23_supported), 2 the six-point one (pair_tc6_supported), 0 the F(4,3) one
+// (pairw_supported)
+int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, int form, DevPairW& pw);
 void free_pairw(DevPairW& pw);
 int launch_respair_wino(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
                         int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream);

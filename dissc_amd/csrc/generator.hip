@@ -67,13 +67,15 @@ enum class PairForm : uint8_t {
   direct_dma,  // ... the first stores lrelu(t) with zero tails (EPI_STORE_ACT): the second stages its windows by LDS-DMA
   td,          // two transform-domain convs (PairPlan::conv)
   fused,       // one launch, direct, t in LDS (respair.hip)
-  fused_td,    // one launch, both convs in the transform domain (PairPlan::f23)
+  fused_td,    // one launch, both convs in the transform domain (PairPlan::reg_form)
 };
 enum class ConvForm : uint8_t { direct, f43, f63, f54 };  // f43: conv_wino.hip; f63 / f54: conv_wino8.hip with 3 / 4-tap sub-filters
 struct PairPlan {
   PairForm form = PairForm::direct;
   ConvForm conv[2] = {ConvForm::direct, ConvForm::direct};  // conv_d, conv_1
-  bool f23 = false;  // fused_td: the register-only F(2,3) kernels (respair_f23.hip); else F(4,3) (respair_wino.hip, experimental)
+  // fused_td: DevPairW::form -- 1 / 2 the register-only F(2,3) / six-point F(3,4) kernels (respair_f23.hip); 0 F(4,3)
+  // (respair_wino.hip, experimental)
+  uint8_t reg_form = 0;
 };
 struct ChainPlan {
   ChainForm form = ChainForm::pairs;
@@ -120,17 +122,31 @@ static ConvForm td_conv_form(int C, int KS, int dil) {
 // option "pair_f23" (default 3), a bit mask: 1 = the C = 32, k = 11 pairs run as register-only F(2,3)
 //   (respair_f23.hip; per launch 857 / 894 / 924 us at d = 1 / 3 / 5 against 1 042 / 1 037 / 1 052 for the direct pair,
 //   B = 32 x 10 s), 2 = the C = 16, k = 11 pairs (respair16_f23.hip: 525 against 604 us at d = 1); 4 / 8 = the k = 3 pairs of the
-//   two stages (C = 32: 365 against 417 us, C = 16: 262 against 263; forward 33.11 -> 33.09 ms: off).  Also picks the form of
-//   dissc_respair1d's mode 3.
-static bool pair_f23_wanted(int C, int KS, int dil) {
-  return pair_f23_supported(C, KS, dil) && (opts().pair_f23 & ((C == 32 ? 1 : 2) << (KS == 3 ? 2 : 0)));
+//   two stages (C = 32: 365 against 417 us, C = 16: 262 against 263; forward 33.11 -> 33.09 ms: off).  Bits 1 / 2 are the
+//   per-stage switch of the register-only transform-domain pairs: which form a (stage, k) takes is "pair_tc6"'s choice.
+// option "pair_tc6" (default 3), a bit mask honoured only for a stage whose "pair_f23" bit is set: 1 = the C = 32, k = 7
+//   pairs, 2 = the C = 32, k = 11 pairs run on six points as F(3,4) (respair32_tc6_kernel: 4 / 6 products per output where the
+//   direct pair executes 7 and F(2,3) 8).  Per launch at d = 1 / 3 / 5, B = 32 x 10 s, 1 000 alternated launches: k = 7
+//   478 / 482 / 538 us against 655 / 658 / 690 for the direct pair, k = 11 705 / 701 / 796 against 797 / 834 / 898 for F(2,3);
+//   forward 32.84-33.00 -> 32.10-32.23 ms (five alternated runs), bit 1 alone 32.30-32.79, bit 2 alone 32.64-32.77 against
+//   32.74-32.89 (profiles/r07).  Rounding on trained-like data <= 1.4 x the direct pair's rms (bar 3).  4 / 8 = the same for
+//   C = 16: no instance, ignored.  The two options together also pick the form of dissc_respair1d's mode 3.
+// the register-only form of a pair (DevPairW::form: 1 F(2,3), 2 six points), or 0
+static int pair_reg_form(int C, int KS, int dil) {
+  if (C != 16 && C != 32) return 0;
+  const int stage = C == 32 ? 1 : 2;
+  if (KS == 3) return pair_f23_supported(C, KS, dil) && (opts().pair_f23 & (stage << 2)) ? 1 : 0;
+  if (!(opts().pair_f23 & stage)) return 0;
+  const int tc6_bit = (C == 32 ? 1 : 4) << (KS == 11 ? 1 : 0);
+  if ((KS == 7 || KS == 11) && (opts().pair_tc6 & tc6_bit) && pair_tc6_supported(C, KS, dil)) return 2;
+  return pair_f23_supported(C, KS, dil) ? 1 : 0;
 }
 // option "pair_wino" (default 0; experimental builds): 1 = the pairs respair_wino.hip's F(4,3) kernel measured
 //   faster for (tools/pair_gate.py, B = 32 x 10 s: C = 32, k = 11, d = 1 / 3: 895 / 988 us against 1 042 / 1 047 for the direct
 //   fused pair; C = 64, k = 3, d = 1: 624 against 658 for two conv_wino launches) run on it; 2 = every shape with an instance
 //   (tests); 0 = none.  Off: its gate failed (whole forward 35.36 against 35.42 ms, executed-FLOP utilisation 0.619 -> 0.602).
 static bool pairw_wanted(int C, int KS, int dil) {
-  if (pair_f23_wanted(C, KS, dil)) return true;
+  if (pair_reg_form(C, KS, dil)) return true;
   if (!opts().pair_wino || !pairw_supported(C, KS, dil)) return false;
   if (opts().pair_wino >= 2) return true;
   if (C == 32) return KS == 11 && dil <= 3;
@@ -161,7 +177,7 @@ static ChainPlan plan_chain(int C, int KS, const int* dil, int prec) {
         prec == 0 && opts().wino && pairw_wanted(C, KS, d) && (C > 32 ? td : C <= opts().pair_max_c) && (fused || m == 0);
     if (fuse_td) {
       p.form = PairForm::fused_td;
-      p.f23 = pair_f23_wanted(C, KS, d);
+      p.reg_form = (uint8_t)pair_reg_form(C, KS, d);
     } else if (fused) {
       p.form = PairForm::fused;
     } else if (td) {
@@ -183,8 +199,10 @@ static double pair_macs(const PairPlan& p, int C, int KS, bool executed) {
          : f == ConvForm::f63 ? wino8_executed_macs_per_t(C, KS, 3)
          : f == ConvForm::f54 ? wino8_executed_macs_per_t(C, KS, 4) : direct;
   };
-  if (executed && p.form == PairForm::fused_td)  // F(2,3): 4 products per 2 outputs and sub-filter
-    return p.f23 ? 2.0 * C * C * 2.0 * ((KS + 2) / 3) : 2.0 * wino_executed_macs_per_t(C, KS);
+  if (executed && p.form == PairForm::fused_td) {  // F(2,3): 4 products per 2 outputs and sub-filter; six points: 6 per 3
+    if (p.reg_form == 2) return 2.0 * C * C * 2.0 * ((KS + 3) / 4);
+    return p.reg_form == 1 ? 2.0 * C * C * 2.0 * ((KS + 2) / 3) : 2.0 * wino_executed_macs_per_t(C, KS);
+  }
   return executed ? conv(p.conv[0]) + conv(p.conv[1]) : direct + direct;
 }
 
@@ -507,7 +525,7 @@ int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, s
         const int d = dl[m];
         const float *w1 = w6[2 * m], *b1 = b6[2 * m], *w2 = w6[2 * m + 1], *b2 = b6[2 * m + 1];
         if (p.form == PairForm::fused_td) {
-          tasks.push_back([=]() { return make_pairw(w1, b1, w2, b2, ch, rk, d, p.f23, g->pw[idx]); });
+          tasks.push_back([=]() { return make_pairw(w1, b1, w2, b2, ch, rk, d, p.reg_form, g->pw[idx]); });
         } else {
           tasks.push_back([=]() { return make_pair_conv(p.conv[0], w1, b1, ch, rk, d, g->rb1[idx]); });
           tasks.push_back([=]() { return make_pair_conv(p.conv[1], w2, b2, ch, rk, 1, g->rb2[idx]); });
@@ -863,7 +881,7 @@ static int pair_make(int mode, const float* w1, const float* b1, const float* w2
     if ((rc = make_wino(w1, b1, C, k, d, c1))) return rc;
     return make_wino(w2, b2, C, k, 1, c2);
   }
-  if (mode == 3) return make_pairw(w1, b1, w2, b2, C, k, d, pair_f23_wanted(C, k, d), pw);
+  if (mode == 3) return make_pairw(w1, b1, w2, b2, C, k, d, pair_reg_form(C, k, d), pw);
   if ((rc = make_conv(w1, b1, C, C, k, d, c1))) return rc;
   return make_conv(w2, b2, C, C, k, 1, c2);
 }

@@ -251,6 +251,247 @@ __global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairFArgs a
 }
 
 // ---------------------------------------------------------------------------------------------
+// respair32_tc6_kernel: the same pair on SIX points (0, +-1, +-2, inf) used as F(3,4) -- three outputs of a four-tap sub-filter,
+// still register-only.  k = 7 is NS = 2 sub-filters (taps j, j + 2, j + 4, j + 6; tap 7 is a zero), k = 11 is NS = 3: 6 products
+// per 3 outputs and sub-filter = 4 per output at k = 7 (direct: 7) and 6 at k = 11 (F(2,3): 8).
+//   * an MFMA column is a unit's phase: outputs t, t + D, t + 2 D (D = d NS; NS for conv_1) from the samples x_q at t + j d + q D
+//   * B^T (conv_wino.hip's F(4,3) matrix) on the way from LDS to the MFMA, 8 fused multiply-adds and 4 additions per 6 operands:
+//       b0 = 4 x0 - 5 x2 + x4      b1 = (x4 - 4 x2) + (x3 - 4 x1)      b3 = (x4 - x2) + 2 (x3 - x1)
+//       b5 = 4 x1 - 5 x3 + x5      b2 = (x4 - 4 x2) - (x3 - 4 x1)      b4 = (x4 - x2) - 2 (x3 - x1)
+//   * A^T in registers: y0 = Y0 + Y1 + Y2 + Y3 + Y4, y1 = (Y1 - Y2) + 2 (Y3 - Y4), y2 = (Y1 + Y2) + 4 (Y3 + Y4) + Y5
+//   * G (host, kTc6G): U_p = G w per quadruple of taps
+// Six points x 16 accumulators leave room for ONE 32-column tile per wave (two spill), and the weights of a (chunk,
+// sub-filter) come one 8-channel half at a time, double-buffered (6 x 16 bytes per lane and step).  conv_d's columns are dealt
+// over the workgroup's 128; conv_1's per wave (32 / D2 whole units, 96 outputs at k = 7 and 90 at k = 11), so that a wave's
+// outputs are one contiguous range and its epilogue patch stays private.  At k = 11 that range starts 2 mod 4 in the odd
+// waves: the patch is laid out from the 16-byte boundary below it and the two quads that straddle a neighbour's range are
+// stored element by element.
+// ---------------------------------------------------------------------------------------------
+template <int KS_, int DIL>
+struct Tc6Geo {
+  static constexpr int KS = KS_, NS = (KS_ + 3) / 4, C = 32, NW = 4;
+  static constexpr int P2 = (KS - 1) / 2, P1 = P2 * DIL;
+  static constexpr int D1 = DIL * NS, D2 = NS;
+  static constexpr int NCOLS = 32 * NW;                                 // columns of conv_d per workgroup
+  static constexpr int NU1 = NCOLS / D1, NC1 = NU1 * D1, W1 = 3 * NC1;  // positions of T conv_d produces: [o0 - P2, o0 - P2 + W1)
+  static constexpr int NCW2 = 32 / D2 * D2, OW = 3 * NCW2, W2 = NW * OW;  // conv_1: columns and outputs per wave, outputs [o0, o0 + W2)
+  static constexpr int WOUT = ((W1 - 2 * P2) < W2 ? (W1 - 2 * P2) : W2) & ~3;  // outputs a workgroup owns
+  static constexpr int REACH1 = (4 * NS - 1) * DIL, REACH2 = 4 * NS - 1;  // samples read beyond the conv's last position
+  // row stride of the one LDS buffer (x window, then T, then the patches): a multiple of 4 and no more -- the two halves of a
+  // wave read different rows, but a 4-byte LDS read serves them in separate passes, so the stride's residue modulo the 32 banks
+  // buys nothing here, and rounding it to 16 mod 32 as the F(2,3) kernel does would cost the d = 3 / 5 shapes a workgroup per CU
+  static constexpr int XW1 = (3 + W1 + REACH1 + 3) & ~3;
+  static constexpr int XW2 = (W2 + REACH2 + 3) & ~3;
+  static constexpr int XW = XW1 > XW2 ? XW1 : XW2;
+  static constexpr int PW = 96 + 4;                 // patch row: a wave's outputs from the 16-byte boundary below its first
+  static constexpr int OCC = 3 * 4 * C * XW <= 160 * 1024 ? 3 : 2;  // workgroups per CU the LDS admits: the register budget follows
+  static_assert(3 + OW <= PW - 1 && NW * 8 * PW <= C * XW, "the epilogue patches fit the buffer");
+  static_assert(W1 <= XW && WOUT + 2 * P2 <= W1 && WOUT <= W2, "T fits the buffer and covers what the owned outputs read");
+};
+
+template <int KS_, int DIL>
+__global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_kernel(const PairFArgs a) {
+  using G = Tc6Geo<KS_, DIL>;
+  constexpr int C = G::C, NW = G::NW, NT = 64 * NW, NS = G::NS, P2 = G::P2, P1 = G::P1, D1 = G::D1, D2 = G::D2, XW = G::XW,
+                W1 = G::W1, NC1 = G::NC1, NCW2 = G::NCW2, OW = G::OW, WOUT = G::WOUT, PW = G::PW;
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [C][XW]
+
+  int b, len, o0;
+  if (!f23_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, h = lane >> 5;
+  const int tin0 = o0 - P2 - P1;
+  const int tb = tin0 & ~3, sh = tin0 - tb;
+  const float slope = a.slope;
+  const float* xb = a.x + (size_t)b * a.bstride;
+
+  // ---- lrelu(x) on [tb, tb + XW) into LDS, as respair32_f23_kernel ----
+  {
+    constexpr int NV = XW / 4, NIT = (C * NV + NT - 1) / NT;
+    f32x4 sv[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = tid + it * NT;
+      const int r = i / NV < C ? i / NV : C - 1, v = i - (i / NV) * NV;
+      const int t = tb + 4 * v;
+      const int tc = t < 0 ? 0 : (t > a.ld - 4 ? a.ld - 4 : t);
+      sv[it] = *reinterpret_cast<const f32x4*>(xb + (size_t)r * a.ld + tc);
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = tid + it * NT;
+      if (i >= C * NV) continue;
+      const int r = i / NV, v = i - r * NV;
+      const int t = tb + 4 * v;
+      f32x4 val = sv[it];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? (val[e] > 0.f ? val[e] : val[e] * slope) : 0.f;
+      *reinterpret_cast<f32x4*>(xs + r * XW + 4 * v) = val;
+    }
+  }
+
+  // this lane's column of each conv: column -> (unit tau, phase rho) -> first sample 3 D tau + rho
+  int base1, base2;
+  {
+    const int c = wave * 32 + l31;
+    const int c1 = c < NC1 ? c : NC1 - 1, c2 = l31 < NCW2 ? l31 : NCW2 - 1;
+    base1 = 3 * D1 * (c1 / D1) + (c1 % D1);
+    base2 = wave * OW + 3 * D2 * (c2 / D2) + (c2 % D2);
+  }
+  typedef float f32x16f __attribute__((ext_vector_type(16)));
+  f32x16f acc[6];
+  auto clear = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int p = 0; p < 6; ++p)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[p][e] = 0.f;
+  };
+  // one conv: per (chunk of 16 channels, sub-filter, half of 8 channels) 4 k-steps x 6 points = 24 MFMAs fed by 24 fragment
+  // reads and 48 transform instructions
+  auto taps = [&](const float* wq, const float* src, int base, int dstep, int dunit) __attribute__((always_inline)) {
+    const __amdgpu_buffer_rsrc_t wr = wave_rsrc(wq, 0x7ffffff0u);  // scalar-base loads (common.h), constant offsets
+    const unsigned lane16 = lane * 16u;
+    constexpr int NST = 2 * NS * 2;  // step = (chunk * NS + sub-filter) * 2 + half
+    const unsigned wstep = (a.dbg & 8) ? 0u : 6 * 1024u;  // (knock-out: every step re-reads the first step's 6 KB)
+    f32x4 av[6], avn[6];
+#pragma unroll
+    for (int p = 0; p < 6; ++p) av[p] = rsrc_load16(wr, lane16, p * 1024u);
+#pragma unroll
+    for (int st = 0; st < NST; ++st) {
+      const int sn = st + 1 < NST ? st + 1 : st;
+#pragma unroll
+      for (int p = 0; p < 6; ++p) avn[p] = rsrc_load16(wr, lane16, sn * wstep + p * 1024u);
+      __builtin_amdgcn_sched_barrier(0);
+      const int chunk = (st >> 1) / NS, j = (st >> 1) % NS, hf = st & 1;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = 16 * chunk + 2 * (4 * hf + e) + h;
+        const float* q = src + row * XW + base + j * dstep;
+        const float x0 = q[0], x1 = q[dunit], x2 = q[2 * dunit], x3 = q[3 * dunit], x4 = q[4 * dunit], x5 = q[5 * dunit];
+        const float pe = __builtin_fmaf(-4.f, x2, x4), po = __builtin_fmaf(-4.f, x1, x3), re = x4 - x2, ro = x3 - x1;
+        float bq[6];
+        bq[0] = __builtin_fmaf(4.f, x0, __builtin_fmaf(-5.f, x2, x4));
+        bq[1] = pe + po;
+        bq[2] = pe - po;
+        bq[3] = __builtin_fmaf(2.f, ro, re);
+        bq[4] = __builtin_fmaf(-2.f, ro, re);
+        bq[5] = __builtin_fmaf(4.f, x1, __builtin_fmaf(-5.f, x3, x5));
+#pragma unroll
+        for (int p = 0; p < 6; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[p][e], bq[p], acc[p], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int p = 0; p < 6; ++p) av[p] = avn[p];
+    }
+  };
+  // A^T of accumulator element r: the unit's three outputs
+  auto outs = [&](int r, float& y0, float& y1, float& y2) __attribute__((always_inline)) {
+    const float s12 = acc[1][r] + acc[2][r], d12 = acc[1][r] - acc[2][r];
+    const float s34 = acc[3][r] + acc[4][r], d34 = acc[3][r] - acc[4][r];
+    y0 = (acc[0][r] + s12) + s34;
+    y1 = __builtin_fmaf(2.f, d34, d12);
+    y2 = __builtin_fmaf(4.f, s34, s12) + acc[5][r];
+  };
+
+  __syncthreads();
+  clear();
+  if (!(a.dbg & 1)) taps(a.w1, xs + sh, base1, DIL, D1);
+
+  // ---- T = lrelu(conv_d + b1) inside the utterance, 0 outside, into the same buffer: positions [0, W1) <-> times o0 - P2 + . ----
+  __syncthreads();  // every wave is done reading the x window
+  for (int i = tid; i < C * (XW - W1); i += NT) {
+    const int r = i / (XW - W1), v = i - r * (XW - W1);
+    xs[r * XW + W1 + v] = 0.f;  // what conv_1's last columns read beyond T
+  }
+  {
+    const int c = wave * 32 + l31;
+    if (c < NC1 && !(a.dbg & 2)) {
+      const int p0 = 3 * D1 * (c / D1) + (c % D1);
+      const int t0 = o0 - P2 + p0;
+      const bool in0 = t0 >= 0 && t0 < len, in1 = t0 + D1 >= 0 && t0 + D1 < len, in2 = t0 + 2 * D1 >= 0 && t0 + 2 * D1 < len;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const float bz = a.b1[row];
+        float v0, v1, v2;
+        outs(r, v0, v1, v2);
+        v0 += bz; v1 += bz; v2 += bz;
+        v0 = v0 > 0.f ? v0 : v0 * slope;
+        v1 = v1 > 0.f ? v1 : v1 * slope;
+        v2 = v2 > 0.f ? v2 : v2 * slope;
+        xs[row * XW + p0] = in0 ? v0 : 0.f;
+        xs[row * XW + p0 + D1] = in1 ? v1 : 0.f;
+        xs[row * XW + p0 + 2 * D1] = in2 ? v2 : 0.f;
+      }
+    }
+  }
+  __syncthreads();
+  clear();
+  if (!(a.dbg & 1)) taps(a.w2, xs, base2, 1, D2);
+
+  // ---- epilogue: y = x + conv_1 + b2 (or an MRF mode), 8 rows at a time through a wave-private patch [8][PW] ----
+  __syncthreads();  // every wave is done reading T, which the patches overwrite
+  float* ep = xs + wave * (8 * PW);
+  const int prow = lane >> 5, pc4 = lane & 31;
+  const int ws = wave * OW, woff = ws & 3;        // the wave's outputs [ws, ws + OW) of the tile
+  const int ncol = ws - woff + 4 * pc4;           // this lane's quad
+  const int tcol = o0 + ncol;
+  const size_t ob = (size_t)b * a.bstride;
+  const int wend = ws + OW < WOUT ? ws + OW : WOUT;
+  const int elo = ncol < ws ? ws - ncol : 0;      // elements [elo, ehi) of the quad are this wave's, owned and inside the utterance
+  const int ehi = (wend - ncol < len - tcol ? wend - ncol : len - tcol) < 4 ? (wend - ncol < len - tcol ? wend - ncol : len - tcol) : 4;
+  const bool live = ehi > elo, full = elo == 0 && ehi == 4;
+  const int epi = a.epi;
+  const bool rmw = epi != EPI_RES && epi != EPI_MRF_SET;
+  if (a.dbg & 4) {
+    if (acc[0][0] == 123.f) a.out[0] = 1.f;
+    return;
+  }
+  const int cl = l31 < NCW2 ? l31 : NCW2 - 1;  // (the lanes beyond the wave's columns rewrite its last one)
+  const int pcol = woff + 3 * D2 * (cl / D2) + (cl % D2);
+#pragma unroll
+  for (int qd = 0; qd < 4; ++qd) {  // rows 8 qd .. 8 qd + 7
+    __builtin_amdgcn_sched_barrier(0);  // (the loads of a later trip hoisted above this one spill: 96 accumulators are live)
+    f32x4 rv[4], pa[4];  // (both from the clamped quad, unconditionally: used by the lanes whose quad is `full`)
+    const int tc = tcol > a.ld - 4 ? a.ld - 4 : tcol;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) rv[p] = *reinterpret_cast<const f32x4*>(a.x + ob + (size_t)(8 * qd + 2 * p + prow) * a.ld + tc);
+    if (rmw) {
+#pragma unroll
+      for (int p = 0; p < 4; ++p) pa[p] = *reinterpret_cast<const f32x4*>(a.acc + ob + (size_t)(8 * qd + 2 * p + prow) * a.ld + tc);
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float y0, y1, y2;
+      outs(4 * qd + r, y0, y1, y2);
+      ep[(r + 4 * h) * PW + pcol] = y0;
+      ep[(r + 4 * h) * PW + pcol + D2] = y1;
+      ep[(r + 4 * h) * PW + pcol + 2 * D2] = y2;
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int prw = 2 * p + prow;
+      f32x4 v = *reinterpret_cast<const f32x4*>(ep + prw * PW + (4 * pc4 < PW - 4 ? 4 * pc4 : PW - 4));
+      if (!live) continue;
+      const int row = 8 * qd + prw;
+      const float bz = a.b2[row];
+      const size_t idx = ob + (size_t)row * a.ld + tcol;
+      if (full) {
+        const f32x4 r4 = rv[p];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (v[e] + bz) + r4[e];
+        epi_store_res(epi, quad_at(a.out + idx), quad_at(a.acc + idx), v, [&] { return pa[p]; }, a.mrf_div);
+      } else {
+        for (int e = elo; e < ehi; ++e)
+          epi_store_res(epi, a.out + idx + e, a.acc + idx + e, (v[e] + bz) + a.x[idx + e], [&] { return a.acc[idx + e]; }, a.mrf_div);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 // the 32-channel stage (this file) and the 16-channel one (respair16_f23.hip); k = 3 (one sub-filter, 2 products per output
@@ -283,6 +524,48 @@ int pack_pair_f23(const float* w, float** dev, int C_, int KS) {
   return upload(packed, dev);
 }
 
+// six points: the 32-channel stage, k = 7 and 11
+bool pair_tc6_supported(int C, int KS, int dil) { return C == 32 && (KS == 7 || KS == 11) && (dil == 1 || dil == 3 || dil == 5); }
+
+// w: [32][32][k] -> U_p[co][ci][j] = sum_i G[p][i] w[co][ci][j + NS i], NS = ceil(k / 4), in A-fragment order
+// [chunk][sub-filter][half][point][lane][4]
+int pack_pair_tc6(const float* w, float** dev, int C_, int KS) {
+  constexpr int C = 32;
+  if (C_ != C) {
+    set_error("pack_pair_tc6: no instance for C = %d", C_);
+    return DISSC_EINVAL;
+  }
+  const int NS = (KS + 3) / 4;
+  std::vector<float> packed((size_t)2 * NS * 2 * 6 * 64 * 4);
+  size_t o = 0;
+  for (int c = 0; c < 2; ++c)
+    for (int j = 0; j < NS; ++j)
+      for (int hf = 0; hf < 2; ++hf)
+        for (int p = 0; p < 6; ++p)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int e = 0; e < 4; ++e) {
+              const int co = lane & 31, ci = 16 * c + 2 * (4 * hf + e) + (lane >> 5);
+              double u = 0.0;
+              for (int i = 0; i < 4; ++i) {
+                const int tap = j + NS * i;
+                if (tap < KS) u += kTc6G[p][i] * (double)w[((size_t)co * C + ci) * KS + tap];
+              }
+              packed[o++] = (float)u;
+            }
+  return upload(packed, dev);
+}
+
+template <int KS_, int DIL>
+static int launch_tc6_t(const PairFArgs& a, int B, int Lmax, hipStream_t stream) {
+  using G = Tc6Geo<KS_, DIL>;
+  static DeviceOnce attr_once;  // per device (common.h)
+  DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&respair32_tc6_kernel<KS_, DIL>), 160 * 1024));
+  dim3 grid((Lmax + G::WOUT - 1) / G::WOUT, B);
+  hipLaunchKernelGGL((respair32_tc6_kernel<KS_, DIL>), grid, dim3(256), sizeof(float) * G::C * G::XW, stream, a);
+  DISSC_HIP_CHECK(hipGetLastError());
+  return DISSC_OK;
+}
+
 template <int KS_, int DIL>
 static int launch_f23_t(const PairFArgs& a, int B, int Lmax, hipStream_t stream) {
   using G = F23Geo<KS_, DIL>;
@@ -300,6 +583,14 @@ int launch_pair_f23(const DevPairW& pw, const float* x, float* out, float* acc, 
   a.x = x; a.out = out; a.acc = acc; a.w1 = pw.w1; a.w2 = pw.w2; a.b1 = pw.b1; a.b2 = pw.b2;
   a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul; a.ld = ld;
   a.bstride = (long long)pw.C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = opts().kernel_dbg;
+  if (pw.form == 2) {
+#define DISSC_TC6(K_, D_) \
+  if (pw.C == 32 && pw.KS == K_ && pw.dil == D_) return launch_tc6_t<K_, D_>(a, B, Lmax, stream);
+    DISSC_TC6(7, 1) DISSC_TC6(7, 3) DISSC_TC6(7, 5) DISSC_TC6(11, 1) DISSC_TC6(11, 3) DISSC_TC6(11, 5)
+#undef DISSC_TC6
+    set_error("launch_pair_f23: no six-point instance for C = %d, k = %d, dilation %d", pw.C, pw.KS, pw.dil);
+    return DISSC_EINVAL;
+  }
   if (pw.C == 16) return launch_pair16_f23(a, pw.KS, pw.dil, B, Lmax, stream);
 #define DISSC_F23(K_, D_) \
   if (pw.KS == K_ && pw.dil == D_) return launch_f23_t<K_, D_>(a, B, Lmax, stream);

@@ -180,7 +180,14 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *                        16-channel stage run as register-only Toom-Cook F(2,3) (respair_f23.hip / respair16_f23.hip: 8 products per
  *                        output instead of 11, no LDS exchange; forward 1.5 % faster; not bit-identical to the direct pairs, error no
  *                        larger); 4 / 8 = their k = 3 pairs too (2 products per output instead of 3: per launch -12 % at C = 32, 0 at
- *                        C = 16, nothing in the forward -- off); 0 = the direct pairs of respair.hip
+ *                        C = 16, nothing in the forward -- off); 0 = the direct pairs of respair.hip.  Bits 1 / 2 are the per-stage
+ *                        switch of the register-only transform-domain pairs; pair_tc6 picks the form per (stage, k)
+ *   pair_tc6 (3)         read at dissc_gen_create, a bit mask honoured only for a stage whose pair_f23 bit is set: 1 = the k = 7,
+ *                        2 = the k = 11 residual pairs of the 32-channel stage run on six Toom-Cook points as F(3,4)
+ *                        (respair32_tc6_kernel in respair_f23.hip: 4 / 6 products per output instead of the direct pair's 7 /
+ *                        F(2,3)'s 8, still no LDS exchange; per launch -22...-27 % at k = 7 and -11...-16 % at k = 11, forward
+ *                        2.3 % faster; rounding within 1.4 x the direct pair's on trained-like data); 4 / 8 = the same for
+ *                        the 16-channel stage (no instance: ignored); 0 = F(2,3) for k = 11, the direct pair for k = 7
  *   pair_dma (1)         read at dissc_gen_create: the two-launch direct residual pairs of the >= 32-channel stages hand their
  *                        intermediate over activated with zero tails, and the second conv stages its windows by LDS-DMA
  *   wino8 (1)            read at dissc_gen_create: 1 = the ResBlock convs selected by wino8_mask run on conv_wino8.hip's

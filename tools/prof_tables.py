@@ -151,6 +151,10 @@ def main():
             fx = fl * 6.0 * ((k + 2) // 3) / (4.0 * k)
         if "respair32_f23_kernel" in names[i][0] or "respair16_f23_kernel" in names[i][0]:  # register-only F(2,3) pairs (k = 11: four sub-filters): 8 products per output
             fx = fl * 8.0 / 11.0
+        if "respair32_tc6_kernel" in names[i][0]:  # register-only six-point pairs: 6 products per 3 outputs and 4-tap sub-filter
+            import re
+            k = int(re.search(r"respair32_tc6_kernel<(\d+)", names[i][0]).group(1))
+            fx = fl * 2.0 * ((k + 3) // 4) / k
         if "conv_wino8_kernel" in names[i][0]:
             # the eight-point forms: 8 ceil(k / R) / (9 - R) products per output -- R = the instance's sixth template
             # argument (3: F(6,3), 4: F(5,4))
