@@ -352,14 +352,10 @@ struct DevPairW {
   int form = 0;  // 0: respair_wino_kernel (F(4,3), Y exchanged through LDS); register-only: 1: respair32/16_f23_kernel (F(2,3)),
                  // 2: respair32_tc6_kernel (six points as F(3,4))
 };
-// register-only F(2,3) pairs of the 16- and 32-channel stages, k = 11 (respair_f23.hip, respair16_f23.hip)
+// register-only forms (pair_host.hip): F(2,3), k = 11 at C = 16 / 32 (respair16_f23.hip, respair_f23.hip); six points as F(3,4),
+// k = 7 / 11 at C = 32 (respair_f23.hip)
 bool pair_f23_supported(int C, int KS, int dil);
-int pack_pair_f23(const float* w, float** dev, int C, int KS);
-// ... and on six points as F(3,4): the 32-channel stage, k = 7 / 11 (respair_f23.hip); launched by launch_pair_f23 (form 2)
 bool pair_tc6_supported(int C, int KS, int dil);
-int pack_pair_tc6(const float* w, float** dev, int C, int KS);
-int launch_pair_f23(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
-                    int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream);
 // the F(4,3) form: experimental/csrc/respair_wino.hip in DISSC_EXPERIMENTAL=1 builds, experimental_stubs.hip otherwise
 bool pairw43_built();
 int pack_pairw43(const float* w, int C, int KS, float** dev);

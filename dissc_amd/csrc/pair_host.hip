@@ -13,10 +13,12 @@
 
 namespace dissc {
 
-// ---------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------
-// shapes that have an instance: a point's weights must fit 64 registers per lane (C^2 NS / 64 <= 64)
+// shapes with an instance.  Register-only F(2,3): k = 11 at C = 16 / 32 (k = 3 in DISSC_EXPERIMENTAL=1 builds); six points: k = 7 /
+// 11 at C = 32; the F(4,3) kernel: a point's weights must fit 64 registers per lane (C^2 NS / 64 <= 64)
+bool pair_f23_supported(int C, int KS, int dil) {
+  return (C == 16 || C == 32) && (KS == 11 || (KS == 3 && DISSC_EXPERIMENTAL)) && (dil == 1 || dil == 3 || dil == 5);
+}
+bool pair_tc6_supported(int C, int KS, int dil) { return C == 32 && (KS == 7 || KS == 11) && (dil == 1 || dil == 3 || dil == 5); }
 bool pairw_supported(int C, int KS, int dil) {
   if (!pairw43_built()) return false;  // (the kernel is in DISSC_EXPERIMENTAL=1 builds only)
   if (!(dil == 1 || dil == 3 || dil == 5)) return false;
@@ -25,8 +27,70 @@ bool pairw_supported(int C, int KS, int dil) {
   return false;
 }
 
-// w: [C][C][KS] -> U[p][co][ci][j] = sum_i G[p][i] w[co][ci][j + NS i] in the order the kernel's lanes hold them:
-// [point][mi][tap j][8-channel sub-chunk][lane][k-step e] = U_p[32 mi + (lane & 31)][8 ksub + 2 e + (lane >> 5)][j]
+// ---- weights of the register-only kernels ----
+// F(2,3) weight transform at the points 0, 1, -1, inf
+static const double kF23G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
+// F(3,4) weight transform at the points 0, 1, -1, 2, -2, inf
+static const double kTc6G[6][4] = {{1.0 / 4, 0.0, 0.0, 0.0},
+                                   {-1.0 / 6, -1.0 / 6, -1.0 / 6, -1.0 / 6},
+                                   {-1.0 / 6, 1.0 / 6, -1.0 / 6, 1.0 / 6},
+                                   {1.0 / 24, 2.0 / 24, 4.0 / 24, 8.0 / 24},
+                                   {1.0 / 24, -2.0 / 24, 4.0 / 24, -8.0 / 24},
+                                   {0.0, 0.0, 0.0, 1.0}};
+
+// w: [C][C][KS] -> U[p][co][ci][j] = sum_i G[p][i] w[co][ci][j + NS i] for the NS = ceil(KS / taps) sub-filters j (taps beyond
+// KS are zeros): each sum in double over ascending i, rounded once
+static std::vector<float> transform_taps(const float* w, int C, int KS, const double* G, int points, int taps) {
+  const int NS = (KS + taps - 1) / taps;
+  std::vector<float> U((size_t)points * C * C * NS);
+  size_t o = 0;
+  for (int p = 0; p < points; ++p)
+    for (int cc = 0; cc < C * C; ++cc)
+      for (int j = 0; j < NS; ++j) {
+        double u = 0.0;
+        for (int i = 0; i < taps; ++i)
+          if (j + NS * i < KS) u += G[p * taps + i] * (double)w[(size_t)cc * KS + j + NS * i];
+        U[o++] = (float)u;
+      }
+  return U;
+}
+
+static int pack_pair_reg(const float* w, float** dev, int C, int KS, int form) {
+  if ((form != 1 && form != 2) || (C != 16 && C != 32) || (form == 2 && C != 32)) {  // (a layout loop exists for these only)
+    set_error("pack_pair_reg: no layout for form %d, C = %d", form, C);
+    return DISSC_EINVAL;
+  }
+  const int points = form == 2 ? 6 : 4, taps = form == 2 ? 4 : 3, NS = (KS + taps - 1) / taps;
+  const std::vector<float> U = transform_taps(w, C, KS, form == 2 ? &kTc6G[0][0] : &kF23G[0][0], points, taps);
+  auto u = [&](int p, int co, int ci, int j) { return U[(((size_t)p * C + co) * C + ci) * NS + j]; };
+  std::vector<float> packed(U.size());
+  size_t o = 0;
+  if (C == 16) {
+    // respair16_f23_kernel: [sub-filter][point][lane][k-step]; lane l, k-step cq -> U_p[l & 15][4 cq + (l >> 4)][j]
+    for (int j = 0; j < NS; ++j)
+      for (int p = 0; p < 4; ++p)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int cq = 0; cq < 4; ++cq) packed[o++] = u(p, lane & 15, 4 * cq + (lane >> 4), j);
+  } else if (form == 1) {
+    // respair32_f23_kernel: [chunk 2][sub-filter][point 4][half 2][64 lanes][4 k-steps]; lane l, k-step 4 hf + e ->
+    // U_p[l & 31][16 chunk + 2 (4 hf + e) + (l >> 5)][j]
+    for (int c = 0; c < 2; ++c)
+      for (int j = 0; j < NS; ++j)
+        for (int p = 0; p < 4; ++p)
+          for (int hf = 0; hf < 2; ++hf)
+            for (int lane = 0; lane < 64; ++lane)
+              for (int e = 0; e < 4; ++e) packed[o++] = u(p, lane & 31, 16 * c + 2 * (4 * hf + e) + (lane >> 5), j);
+  } else {
+    // respair32_tc6_kernel: the same map with the half outside the point: [chunk 2][sub-filter][half 2][point 6][64 lanes][4 k-steps]
+    for (int c = 0; c < 2; ++c)
+      for (int j = 0; j < NS; ++j)
+        for (int hf = 0; hf < 2; ++hf)
+          for (int p = 0; p < 6; ++p)
+            for (int lane = 0; lane < 64; ++lane)
+              for (int e = 0; e < 4; ++e) packed[o++] = u(p, lane & 31, 16 * c + 2 * (4 * hf + e) + (lane >> 5), j);
+  }
+  return upload(packed, dev);
+}
 
 int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, int form, DevPairW& pw) {
   pw.form = form;
@@ -36,7 +100,7 @@ int make_pairw(const float* w1, const float* b1, const float* w2, const float* b
   }
   pw.C = C; pw.KS = KS; pw.dil = dil;
   auto pack = [&](const float* w, float** dev) {
-    return form == 2 ? pack_pair_tc6(w, dev, C, KS) : form == 1 ? pack_pair_f23(w, dev, C, KS) : pack_pairw43(w, C, KS, dev);
+    return form ? pack_pair_reg(w, dev, C, KS, form) : pack_pairw43(w, C, KS, dev);
   };
   int rc = pack(w1, &pw.w1);
   if (!rc) rc = pack(w2, &pw.w2);
@@ -56,9 +120,39 @@ void free_pairw(DevPairW& pw) {
   }
 }
 
-// option "pairw_chv" (default 2): column halves per workgroup of respair_wino_kernel (2: one 12-wave workgroup per CU;
-                      // 1: two 6-wave workgroups with half the tile each -- measured 5-30 % slower, kept for the tests)
+// ---- launches of the register-only kernels ----
+// grid from Geo::WOUT, the one LDS buffer [C][XW] as dynamic shared memory; want_max_lds: the buffer exceeds the 64 KB a kernel
+// gets without the attribute (once per device and instance: DeviceOnce, common.h)
+template <auto Kernel, class Geo>
+static int launch_pair_reg(const PairArgs& a, int B, int Lmax, hipStream_t stream, bool want_max_lds) {
+  static DeviceOnce attr_once;
+  if (want_max_lds) DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(Kernel), 160 * 1024));
+  dim3 grid((Lmax + Geo::WOUT - 1) / Geo::WOUT, B);
+  hipLaunchKernelGGL(Kernel, grid, dim3(256), sizeof(float) * Geo::C * Geo::XW, stream, a);
+  DISSC_HIP_CHECK(hipGetLastError());
+  return DISSC_OK;
+}
 
+static int launch_pair_f23(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
+                           int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream) {
+  PairArgs a;
+  a.x = x; a.out = out; a.acc = acc; a.w1 = pw.w1; a.w2 = pw.w2; a.b1 = pw.b1; a.b2 = pw.b2;
+  a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul; a.ld = ld;
+  a.bstride = (long long)pw.C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = opts().kernel_dbg;
+#define DISSC_CASE(FORM_, C_, KERNEL_, GEO_, MAX_LDS_, K_, D_)             \
+  if (pw.form == FORM_ && pw.C == C_ && pw.KS == K_ && pw.dil == D_) \
+    return launch_pair_reg<KERNEL_<K_, D_>, GEO_<K_, D_>>(a, B, Lmax, stream, MAX_LDS_);
+#define DISSC_TC6(K_, D_) DISSC_CASE(2, 32, respair32_tc6_kernel, Tc6Geo, true, K_, D_)
+#define DISSC_F23_32(K_, D_) DISSC_CASE(1, 32, respair32_f23_kernel, F23Geo32, true, K_, D_)
+#define DISSC_F23_16(K_, D_) DISSC_CASE(1, 16, respair16_f23_kernel, F23Geo16, false, K_, D_)
+  DISSC_PAIR_TC6_SHAPES(DISSC_TC6) DISSC_PAIR_F23_SHAPES(DISSC_F23_32) DISSC_PAIR_F23_SHAPES(DISSC_F23_16)
+#undef DISSC_F23_16
+#undef DISSC_F23_32
+#undef DISSC_TC6
+#undef DISSC_CASE
+  set_error("launch_pair_f23: no instance of form %d for C = %d, k = %d, dilation %d", pw.form, pw.C, pw.KS, pw.dil);
+  return DISSC_EINVAL;
+}
 
 int launch_respair_wino(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
                         int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream) {

@@ -23,53 +23,9 @@
 // 4-channel k-steps inner, bias / residual / MRF in the same order), so results are identical to the
 // two-launch path; tests/test_gpu_generator.py holds the two against each other bitwise.
 #include "common.h"
-#include "ragged_epi.h"
+#include "respair_f23.h"
 
 namespace dissc {
-
-struct PairArgs {
-  const float* x;     // [B][C][ld] pair input x_k
-  float* out;         // EPI_RES: x_k' (may not alias x: neighbouring workgroups still read x's halo)
-  float* acc;         // EPI_MRF_*: the stage accumulator
-  const float* w1;    // packed conv weights (DevConv::wpack of the dilated conv / of the dil-1 conv)
-  const float* w2;
-  const float* b1;    // [C]
-  const float* b2;
-  const int32_t* lengths;
-  int len_default, len_mul;
-  int ld;
-  long long bstride;
-  float slope, mrf_div;
-  int epi;
-};
-
-// rows of the 16 B-per-lane epilogue: v = conv + bias, rv = the residual -> out / MRF accumulate
-__device__ __forceinline__ void pair_store4(const PairArgs& a, size_t idx, f32x4 v, const f32x4& rv, int nv) {
-  if (nv >= 4) {
-    epi_store_res(a.epi, quad_at(a.out + idx), quad_at(a.acc + idx), epi_plus(v, rv), [&] { return load_quad(a.acc + idx); },
-                  a.mrf_div);
-  } else {
-    for (int e = 0; e < nv; ++e)
-      epi_store_res(a.epi, a.out + idx + e, a.acc + idx + e, v[e] + rv[e], [&] { return a.acc[idx + e]; }, a.mrf_div);
-  }
-}
-
-// (b, len, first output column) of workgroup (blockIdx.x: tile, blockIdx.y: utterance); with lengths only the tiles that
-// EXIST are enumerated (ragged_tile)
-template <int WOUT>
-__device__ __forceinline__ bool pair_tile(const PairArgs& a, int B, int& b, int& len, int& o0) {
-  if (a.lengths == nullptr) {
-    b = blockIdx.y;
-    len = a.len_default;
-    o0 = blockIdx.x * WOUT;
-    return o0 < len;
-  }
-  int tile;
-  if (!ragged_tile<WOUT>(blockIdx.y * gridDim.x + blockIdx.x, B, [&](int i) { return a.lengths[i] * a.len_mul; }, b, tile, len))
-    return false;
-  o0 = tile * WOUT;
-  return true;
-}
 
 // ---- C = 16: v_mfma_f32_16x16x4_f32, both convs' weights in registers -------------------------
 template <int KS, int DIL, int NI>
@@ -105,7 +61,8 @@ __global__ void __launch_bounds__(256) respair16_kernel(const PairArgs a) {
   }
   const f32x4 bias1 = *reinterpret_cast<const f32x4*>(a.b1 + 4 * g);
 
-  // ---- stage lrelu(x) on [tb, tb + XW1) into LDS (16 B per lane, clamped unconditional loads) ----
+  // ---- stage lrelu(x) on [tb, tb + XW1) into LDS: pair_stage_window (respair_f23.h) with the indices kept incrementally -- through
+  // the helper this kernel is 1.3-2.2 % slower per launch (profiles/r08) ----
   {
     f32x4 sv[SV];
     int r = tid / NV, v = tid - (tid / NV) * NV;
@@ -206,14 +163,14 @@ __global__ void __launch_bounds__(256) respair16_kernel(const PairArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) patch[(4 * g + r) * CW + ni * 16 + l15] = acc[ni][r];
   __builtin_amdgcn_wave_barrier();
+  const int ehi = len - tcol < 4 ? len - tcol : 4;
   if (ncol < WOUT && tcol < len) {
 #pragma unroll
     for (int p = 0; p < NI; ++p) {
       const int row = p * RPP + prow;
       f32x4 v = *reinterpret_cast<const f32x4*>(patch + row * CW + 4 * pc4);
-      const float bz = a.b2[row];
-      v[0] += bz; v[1] += bz; v[2] += bz; v[3] += bz;
-      pair_store4(a, ob + (size_t)row * a.ld + tcol, v, rv[p], len - tcol);
+      const size_t idx = ob + (size_t)row * a.ld + tcol;
+      pair_store_tail(a, a.epi, idx, v, a.b2[row], rv[p], [&] { return load_quad(a.acc + idx); }, 0, ehi);
     }
   }
 }
@@ -236,8 +193,6 @@ __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
   constexpr int WOUT = (SLOTS - 2 * P2) & ~3;
   constexpr int XW1 = round32_16(3 + SLOTS + 2 * P1);
   constexpr int XW2 = round32_16(SLOTS + 2 * P2);
-  constexpr int NV = XW1 / 4;
-  constexpr int SV = (C * NV + NT - 1) / NT;
   constexpr int CW = 32 * NI + 4;
   constexpr int LPR = 8 * NI, RPP = 64 / LPR, NPASS = 8 / RPP;
   static_assert(XW2 <= XW1, "T fits the x window");
@@ -262,38 +217,7 @@ __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
   av[0] = rsrc_load16(w1p, lane16, 0);
   av[1] = rsrc_load16(w1p, lane16, 1024u);
 
-  {
-    int rr = tid / NV, vv = tid - (tid / NV) * NV;
-    constexpr int dr = NT / NV, dv = NT - dr * NV;
-    // two half-batches keep the staging registers low (SV float4 would be ~40 VGPRs)
-    constexpr int SVH = (SV + 1) / 2;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      f32x4 sv[SVH];
-      int r1 = rr, v1 = vv;
-#pragma unroll
-      for (int i = 0; i < SVH; ++i) {
-        const int ci = r1 < C ? r1 : C - 1;
-        int t = tb + 4 * v1;
-        t = t < 0 ? 0 : (t > a.ld - 4 ? a.ld - 4 : t);
-        sv[i] = *reinterpret_cast<const f32x4*>(xb + (size_t)ci * a.ld + t);
-        v1 += dv; r1 += dr;
-        if (v1 >= NV) { v1 -= NV; ++r1; }
-      }
-#pragma unroll
-      for (int i = 0; i < SVH; ++i) {
-        if (rr < C) {
-          const int t = tb + 4 * vv;
-          f32x4 val = sv[i];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? lrelu(val[e], slope) : 0.f;
-          *reinterpret_cast<f32x4*>(Xs + rr * XW1 + 4 * vv) = val;
-        }
-        vv += dv; rr += dr;
-        if (vv >= NV) { vv -= NV; ++rr; }
-      }
-    }
-  }
+  pair_stage_window<C, XW1, NT, 2>(a, xb, Xs, tb, len, tid);  // two half-batches keep the staging registers low (one would be ~40 VGPRs)
   __syncthreads();
 
   f32x16p acc[NI];
@@ -358,6 +282,7 @@ __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
   const int tcol = o0 + ncol;
   const size_t ob = (size_t)b * a.bstride;
   const bool live = ncol < WOUT && tcol < len;
+  const int ehi = len - tcol < 4 ? len - tcol : 4;
 #pragma unroll
   for (int qd = 0; qd < 4; ++qd) {  // rows 8*qd .. 8*qd+7
     // residual rows of this pass (raw x, L2-hot), issued before the patch round trip
@@ -380,9 +305,8 @@ __global__ void __launch_bounds__(256) respair32_kernel(const PairArgs a) {
       f32x4 v = *reinterpret_cast<const f32x4*>(ep + prw * CW + 4 * pc4);
       if (!live) continue;
       const int row = 8 * qd + prw;
-      const float bz = a.b2[row];
-      v[0] += bz; v[1] += bz; v[2] += bz; v[3] += bz;
-      pair_store4(a, ob + (size_t)row * a.ld + tcol, v, rv[p], len - tcol);
+      const size_t idx = ob + (size_t)row * a.ld + tcol;
+      pair_store_tail(a, a.epi, idx, v, a.b2[row], rv[p], [&] { return load_quad(a.acc + idx); }, 0, ehi);
     }
   }
 }
@@ -423,7 +347,7 @@ int launch_respair(const DevConv& c1, const DevConv& c2, const float* x, float* 
   PairArgs a;
   a.x = x; a.out = out; a.acc = acc; a.w1 = c1.wpack; a.w2 = c2.wpack; a.b1 = c1.bias; a.b2 = c2.bias;
   a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul; a.ld = ld;
-  a.bstride = (long long)C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi;
+  a.bstride = (long long)C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = 0;
 #define DISSC_PAIR16(K, D)                                                        \
   if (c1.KS == K && c1.dil == D)                                                  \
     return C == 16 ? launch_pair16<K, D>(a, B, Lmax, stream) : launch_pair32<K, D>(a, B, Lmax, stream);

@@ -3,43 +3,22 @@
 // tiles, no exchange) on v_mfma_f32_16x16x4_f32: M = 16 rows, a k-step is 4 channels, the 16 channels of a conv are 4 k-steps.
 // Both convs' transform-domain weights live in registers like respair16_kernel's taps do: 4 sub-filters x 4 points = 16 float4
 // per conv (64 registers, loaded per conv) where the direct form holds 11; 8 products per output instead of 11.
-// A wave's 4 column tiles x 16 columns = 64 output PAIRS = 128 outputs; geometry as in respair_f23.hip.
-#include <string.h>
-
-#include <vector>
-
+// A wave's 4 column tiles x 16 columns = 64 output PAIRS = 128 outputs; geometry (F23Geo16) in respair_f23.h, weights and
+// launch in pair_host.hip.
 #include "common.h"
 #include "respair_f23.h"
 
 namespace dissc {
 
 template <int KS_, int DIL>
-struct F23Geo16 {
-  static constexpr int KS = KS_, NS = (KS_ + 2) / 3, C = 16, NW = 4;
-  static constexpr int P2 = (KS - 1) / 2, P1 = P2 * DIL;
-  static constexpr int D1 = DIL * NS, D2 = NS;
-  static constexpr int NCOLS = 64 * NW;
-  static constexpr int NU1 = NCOLS / D1, NC1 = NU1 * D1, W1 = 2 * NC1;
-  static constexpr int NU2 = NCOLS / D2, NC2 = NU2 * D2, W2 = 2 * NC2;
-  static constexpr int WOUT = ((W1 - 2 * P2) < W2 ? (W1 - 2 * P2) : W2) & ~3;
-  static constexpr int REACH1 = (3 * NS - 1) * DIL, REACH2 = 3 * NS - 1;
-  static constexpr int XW1 = round32_16(3 + W1 + REACH1);
-  static constexpr int XW2 = round32_16(W2 + REACH2 + 1);
-  static constexpr int XW = XW1 > XW2 ? XW1 : XW2;
-  static constexpr int PW = 128 + 4;  // patch row: a wave's 128 outputs
-  static_assert(NW * 16 * PW <= C * XW, "the epilogue patches fit the buffer");
-  static_assert(W1 <= XW && W2 + REACH2 < XW, "T fits the buffer");
-};
-
-template <int KS_, int DIL>
-__global__ void __launch_bounds__(256, 3) respair16_f23_kernel(const PairFArgs a) {
+__global__ void __launch_bounds__(256, 3) respair16_f23_kernel(const PairArgs a) {
   using G = F23Geo16<KS_, DIL>;
   constexpr int C = G::C, NW = G::NW, NT = 64 * NW, NS = G::NS, P2 = G::P2, P1 = G::P1, D1 = G::D1, D2 = G::D2, XW = G::XW,
                 W1 = G::W1, NC1 = G::NC1, NC2 = G::NC2, WOUT = G::WOUT, PW = G::PW, NI = 4;
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [C][XW]
 
   int b, len, o0;
-  if (!f23_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
+  if (!pair_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, g = lane >> 4;
   const int tin0 = o0 - P2 - P1;
@@ -47,29 +26,7 @@ __global__ void __launch_bounds__(256, 3) respair16_f23_kernel(const PairFArgs a
   const float slope = a.slope;
   const float* xb = a.x + (size_t)b * a.bstride;
 
-  {  // lrelu(x) on [tb, tb + XW) into LDS: every load first, then activation / zeros outside the utterance / stores
-    constexpr int NV = XW / 4, NIT = (C * NV + NT - 1) / NT;
-    f32x4 sv[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * NT;
-      const int r = i / NV < C ? i / NV : C - 1, v = i - (i / NV) * NV;
-      const int t = tb + 4 * v;
-      const int tc = t < 0 ? 0 : (t > a.ld - 4 ? a.ld - 4 : t);
-      sv[it] = *reinterpret_cast<const f32x4*>(xb + (size_t)r * a.ld + tc);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * NT;
-      if (i >= C * NV) continue;
-      const int r = i / NV, v = i - r * NV;
-      const int t = tb + 4 * v;
-      f32x4 val = sv[it];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? (val[e] > 0.f ? val[e] : val[e] * slope) : 0.f;
-      *reinterpret_cast<f32x4*>(xs + r * XW + 4 * v) = val;
-    }
-  }
+  pair_stage_window<C, XW, NT>(a, xb, xs, tb, len, tid);
 
   // this lane's four columns of each conv: column -> (unit tau, phase rho) -> first sample 2 D tau + rho
   int base1[NI], base2[NI];
@@ -129,10 +86,7 @@ __global__ void __launch_bounds__(256, 3) respair16_f23_kernel(const PairFArgs a
 
   // ---- T = lrelu(conv_d + b1) inside the utterance, 0 outside, into the same buffer.  D layout: col = lane & 15, row = 4 g + r ----
   __syncthreads();
-  for (int i = tid; i < C * (XW - W1); i += NT) {
-    const int r = i / (XW - W1), v = i - r * (XW - W1);
-    xs[r * XW + W1 + v] = 0.f;
-  }
+  pair_zero_beyond_t<C, XW, W1, NT>(xs, tid);
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) {
     const int c = wave * 64 + ni * 16 + l15;
@@ -198,60 +152,12 @@ __global__ void __launch_bounds__(256, 3) respair16_f23_kernel(const PairFArgs a
     if (!live) continue;
     const float bz = a.b2[row];
     const size_t idx = ob + (size_t)row * a.ld + tcol;
-    const int nv = len - tcol;
-    if (nv >= 4) {
-      const f32x4 r4 = rv[p];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (v[e] + bz) + r4[e];
-      epi_store_res(epi, quad_at(a.out + idx), quad_at(a.acc + idx), v, [&] { return pa[p]; }, a.mrf_div);
-    } else {
-      for (int e = 0; e < nv; ++e)
-        epi_store_res(epi, a.out + idx + e, a.acc + idx + e, (v[e] + bz) + a.x[idx + e], [&] { return a.acc[idx + e]; }, a.mrf_div);
-    }
+    pair_store_tail(a, epi, idx, v, bz, rv[p], [&] { return pa[p]; }, 0, len - tcol < 4 ? len - tcol : 4);
   }
 }
 
-// w: [16][16][11] -> U_p[co][ci][j] = sum_i G[p][i] w[co][ci][j + 4 i] in A-fragment order [sub-filter][point][lane][k-step]:
-// lane l, k-step cq -> U_p[co = l & 15][ci = 4 cq + (l >> 4)][j]
-int pack_pair16_f23(const float* w, float** dev, int KS) {
-  constexpr int C = 16;
-  const int NS = (KS + 2) / 3;
-  std::vector<float> packed((size_t)NS * 4 * 64 * 4);
-  size_t o = 0;
-  for (int j = 0; j < NS; ++j)
-    for (int p = 0; p < 4; ++p)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int cq = 0; cq < 4; ++cq) {
-          const int co = lane & 15, ci = 4 * cq + (lane >> 4);
-          double u = 0.0;
-          for (int i = 0; i < 3; ++i) {
-            const int tap = j + NS * i;
-            if (tap < KS) u += kF23G[p][i] * (double)w[((size_t)co * C + ci) * KS + tap];
-          }
-          packed[o++] = (float)u;
-        }
-  return upload(packed, dev);
-}
-
-template <int KS_, int DIL>
-static int launch_f23_16_t(const PairFArgs& a, int B, int Lmax, hipStream_t stream) {
-  using G = F23Geo16<KS_, DIL>;
-  dim3 grid((Lmax + G::WOUT - 1) / G::WOUT, B);
-  hipLaunchKernelGGL((respair16_f23_kernel<KS_, DIL>), grid, dim3(256), sizeof(float) * G::C * G::XW, stream, a);
-  DISSC_HIP_CHECK(hipGetLastError());
-  return DISSC_OK;
-}
-
-int launch_pair16_f23(const PairFArgs& a, int KS, int dil, int B, int Lmax, hipStream_t stream) {
-#define DISSC_F23(K_, D_) \
-  if (KS == K_ && dil == D_) return launch_f23_16_t<K_, D_>(a, B, Lmax, stream);
-  DISSC_F23(11, 1) DISSC_F23(11, 3) DISSC_F23(11, 5)
-#if DISSC_EXPERIMENTAL  // k = 3 through these kernels measured neutral in the forward (NOTES round 4): not in the default build
-  DISSC_F23(3, 1) DISSC_F23(3, 3) DISSC_F23(3, 5)
-#endif
-#undef DISSC_F23
-  set_error("launch_pair16_f23: no instance for k = %d, dilation %d", KS, dil);
-  return DISSC_EINVAL;
-}
+#define DISSC_INSTANCE(K_, D_) template __global__ void respair16_f23_kernel<K_, D_>(const PairArgs);
+DISSC_PAIR_F23_SHAPES(DISSC_INSTANCE)
+#undef DISSC_INSTANCE
 
 }  // namespace dissc

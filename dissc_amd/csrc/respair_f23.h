@@ -1,18 +1,20 @@
-// Shared by respair_f23.hip (C = 32) and respair16_f23.hip (C = 16): the register-only Toom-Cook residual pairs, F(2,3) on four
-// points and F(3,4) on six.
+// What the one-launch residual-pair kernels share -- the direct pairs (respair.hip) and the register-only Toom-Cook pairs, F(2,3)
+// on four points and F(3,4) on six (respair_f23.hip at C = 32, respair16_f23.hip at C = 16): the argument struct, the tile finder,
+// the staging of the lrelu(x) window into LDS, the zero fill beyond T and the store tail; and, for the register-only kernels, the
+// geometry, the declarations and the instance lists that pair_host.hip launches from.
 #pragma once
 #include "common.h"
 #include "ragged_epi.h"
 
 namespace dissc {
 
-struct PairFArgs {
-  const float* x;
-  float* out;
-  float* acc;
-  const float* w1;  // [chunk 2][sub-filter 4][point 4][half 2][64 lanes][4 k-steps]
+struct PairArgs {
+  const float* x;   // [B][C][ld] pair input x_k
+  float* out;       // EPI_RES: x_k' (may not alias x: neighbouring workgroups still read x's halo)
+  float* acc;       // EPI_MRF_*: the stage accumulator
+  const float* w1;  // conv_d / conv_1 weights in the kernel's fragment order (direct: DevConv::wpack; register-only: pair_host.hip)
   const float* w2;
-  const float* b1;
+  const float* b1;  // [C]
   const float* b2;
   const int32_t* lengths;
   int len_default, len_mul;
@@ -20,13 +22,14 @@ struct PairFArgs {
   long long bstride;
   float slope, mrf_div;
   int epi;
-  int dbg;  // diagnostics ("kernel_dbg" option): knock-outs -- bit 0 the tap loops, 1 the T epilogue, 2 the output epilogue,
-            // 3 (six-point kernel) the weight stream: every step loads the first step's 6 KB
+  int dbg;  // diagnostics ("kernel_dbg" option; the direct kernels ignore it): knock-outs -- bit 0 the tap loops, 1 the T epilogue,
+            // 2 the output epilogue, 3 (six-point kernel) the weight stream: every step loads the first step's 6 KB
 };
 
-// (b, len, first output column) of workgroup (blockIdx.x: tile, blockIdx.y: utterance), as respair.hip's pair_tile
+// (b, len, first output column) of workgroup (blockIdx.x: tile, blockIdx.y: utterance); with lengths only the tiles that
+// EXIST are enumerated (ragged_tile)
 template <int WOUT>
-__device__ __forceinline__ bool f23_tile(const PairFArgs& a, int B, int& b, int& len, int& o0) {
+__device__ __forceinline__ bool pair_tile(const PairArgs& a, int B, int& b, int& len, int& o0) {
   if (a.lengths == nullptr) {
     b = blockIdx.y;
     len = a.len_default;
@@ -40,19 +43,121 @@ __device__ __forceinline__ bool f23_tile(const PairFArgs& a, int B, int& b, int&
   return true;
 }
 
-// F(2,3) weight transform at the points 0, 1, -1, inf (host, double)
-static const double kF23G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
+// lrelu(x) on [tb, tb + XW) of the C rows at xb into xs[C][XW], 16 bytes per lane and trip: every load of a batch first (clamped,
+// unconditional: loads issued one per trip would be as many dependent round trips), then activation, zeros outside [0, len) and
+// the stores.  tb and ld are multiples of 4, so a clamped quad lies wholly outside the utterance and is zeroed.  NBATCH = 2 halves
+// the staging registers where a kernel is short of them.
+template <int C, int XW, int NT, int NBATCH = 1>
+__device__ __forceinline__ void pair_stage_window(const PairArgs& a, const float* xb, float* xs, int tb, int len, int tid) {
+  constexpr int NV = XW / 4, NIT = ((C * NV + NT - 1) / NT + NBATCH - 1) / NBATCH;
+  const float slope = a.slope;
+#pragma unroll
+  for (int nb = 0; nb < NBATCH; ++nb) {
+    f32x4 sv[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = tid + (nb * NIT + it) * NT;
+      const int r = i / NV < C ? i / NV : C - 1, v = i - (i / NV) * NV;
+      const int t = tb + 4 * v;
+      const int tc = t < 0 ? 0 : (t > a.ld - 4 ? a.ld - 4 : t);
+      sv[it] = *reinterpret_cast<const f32x4*>(xb + (size_t)r * a.ld + tc);
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = tid + (nb * NIT + it) * NT;
+      if (i >= C * NV) continue;
+      const int r = i / NV, v = i - r * NV;
+      const int t = tb + 4 * v;
+      f32x4 val = sv[it];
+#pragma unroll
+      // (lrelu() spelled out: through the call the register-only kernels compile to other code, 0.2-1.3 % slower per launch at C = 32)
+      for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? (val[e] > 0.f ? val[e] : val[e] * slope) : 0.f;
+      *reinterpret_cast<f32x4*>(xs + r * XW + 4 * v) = val;
+    }
+  }
+}
 
-// F(3,4) weight transform at the points 0, 1, -1, 2, -2, inf (host, double)
-static const double kTc6G[6][4] = {{1.0 / 4, 0.0, 0.0, 0.0},
-                                   {-1.0 / 6, -1.0 / 6, -1.0 / 6, -1.0 / 6},
-                                   {-1.0 / 6, 1.0 / 6, -1.0 / 6, 1.0 / 6},
-                                   {1.0 / 24, 2.0 / 24, 4.0 / 24, 8.0 / 24},
-                                   {1.0 / 24, -2.0 / 24, 4.0 / 24, -8.0 / 24},
-                                   {0.0, 0.0, 0.0, 1.0}};
+// zeros in xs[r][W1 .. XW): what conv_1's last columns read beyond T
+template <int C, int XW, int W1, int NT>
+__device__ __forceinline__ void pair_zero_beyond_t(float* xs, int tid) {
+  for (int i = tid; i < C * (XW - W1); i += NT) {
+    const int r = i / (XW - W1), v = i - r * (XW - W1);
+    xs[r * XW + W1 + v] = 0.f;
+  }
+}
 
-// respair16_f23.hip
-int pack_pair16_f23(const float* w, float** dev, int KS);
-int launch_pair16_f23(const PairFArgs& a, int KS, int dil, int B, int Lmax, hipStream_t stream);
+// Store tail of one row quad at idx: v from the epilogue patch, (v + bz) + residual, then the epilogue mode -- on the whole quad
+// when its elements [elo, ehi) are all four (rv: the residual quad fetched earlier; acc_old(): the accumulator's old quad),
+// element by element otherwise (a ragged tail, a quad shared with the neighbouring wave).
+template <class AccOld>
+__device__ __forceinline__ void pair_store_tail(const PairArgs& a, int epi, size_t idx, f32x4 v, float bz, const f32x4& rv,
+                                                AccOld acc_old, int elo, int ehi) {
+  if (elo == 0 && ehi == 4) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (v[e] + bz) + rv[e];
+    epi_store_res(epi, quad_at(a.out + idx), quad_at(a.acc + idx), v, acc_old, a.mrf_div);
+  } else {
+    for (int e = elo; e < ehi; ++e)
+      epi_store_res(epi, a.out + idx + e, a.acc + idx + e, (v[e] + bz) + a.x[idx + e], [&] { return a.acc[idx + e]; }, a.mrf_div);
+  }
+}
+
+// ---- the register-only kernels: geometry, declarations, instances ----
+// F(2,3): respair32_f23_kernel (C = 32, patches of 8 rows) and respair16_f23_kernel (C = 16, patches of 16 rows)
+template <int C_, int PROWS, int KS_, int DIL>
+struct F23Geo {
+  static constexpr int KS = KS_, NS = (KS_ + 2) / 3, C = C_, NW = 4;
+  static constexpr int P2 = (KS - 1) / 2, P1 = P2 * DIL;
+  static constexpr int D1 = DIL * NS, D2 = NS;
+  static constexpr int NCOLS = 64 * NW;                               // pair-columns per conv and workgroup
+  static constexpr int NU1 = NCOLS / D1, NC1 = NU1 * D1, W1 = 2 * NC1;  // positions of T conv_d produces: [o0 - P2, o0 - P2 + W1)
+  static constexpr int NU2 = NCOLS / D2, NC2 = NU2 * D2, W2 = 2 * NC2;  // outputs conv_1 computes: [o0, o0 + W2)
+  static constexpr int WOUT = ((W1 - 2 * P2) < W2 ? (W1 - 2 * P2) : W2) & ~3;  // outputs a workgroup owns
+  static constexpr int REACH1 = (3 * NS - 1) * DIL, REACH2 = 3 * NS - 1;       // samples read beyond the last column's first
+  static constexpr int XW1 = round32_16(3 + W1 + REACH1);
+  static constexpr int XW2 = round32_16(W2 + REACH2 + 1);
+  static constexpr int XW = XW1 > XW2 ? XW1 : XW2;  // row stride of the one LDS buffer (x window, then T, then the patches)
+  static constexpr int PW = 128 + 4;                // patch row: a wave's 128 outputs
+  static_assert(NW * PROWS * PW <= C * XW, "the epilogue patches fit the buffer");
+  static_assert(W1 <= XW && W2 + REACH2 < XW, "T fits the buffer");
+};
+template <int KS, int DIL> using F23Geo32 = F23Geo<32, 8, KS, DIL>;
+template <int KS, int DIL> using F23Geo16 = F23Geo<16, 16, KS, DIL>;
+
+// six points: respair32_tc6_kernel (the scheme is described in respair_f23.hip)
+template <int KS_, int DIL>
+struct Tc6Geo {
+  static constexpr int KS = KS_, NS = (KS_ + 3) / 4, C = 32, NW = 4;
+  static constexpr int P2 = (KS - 1) / 2, P1 = P2 * DIL;
+  static constexpr int D1 = DIL * NS, D2 = NS;
+  static constexpr int NCOLS = 32 * NW;                                 // columns of conv_d per workgroup
+  static constexpr int NU1 = NCOLS / D1, NC1 = NU1 * D1, W1 = 3 * NC1;  // positions of T conv_d produces: [o0 - P2, o0 - P2 + W1)
+  static constexpr int NCW2 = 32 / D2 * D2, OW = 3 * NCW2, W2 = NW * OW;  // conv_1: columns and outputs per wave, outputs [o0, o0 + W2)
+  static constexpr int WOUT = ((W1 - 2 * P2) < W2 ? (W1 - 2 * P2) : W2) & ~3;  // outputs a workgroup owns
+  static constexpr int REACH1 = (4 * NS - 1) * DIL, REACH2 = 4 * NS - 1;  // samples read beyond the conv's last position
+  // row stride of the one LDS buffer (x window, then T, then the patches): a multiple of 4 and no more -- the two halves of a
+  // wave read different rows, but a 4-byte LDS read serves them in separate passes, so the stride's residue modulo the 32 banks
+  // buys nothing here, and rounding it to 16 mod 32 as the F(2,3) kernel does would cost the d = 3 / 5 shapes a workgroup per CU
+  static constexpr int XW1 = (3 + W1 + REACH1 + 3) & ~3;
+  static constexpr int XW2 = (W2 + REACH2 + 3) & ~3;
+  static constexpr int XW = XW1 > XW2 ? XW1 : XW2;
+  static constexpr int PW = 96 + 4;                 // patch row: a wave's outputs from the 16-byte boundary below its first
+  static constexpr int OCC = 3 * 4 * C * XW <= 160 * 1024 ? 3 : 2;  // workgroups per CU the LDS admits: the register budget follows
+  static_assert(3 + OW <= PW - 1 && NW * 8 * PW <= C * XW, "the epilogue patches fit the buffer");
+  static_assert(W1 <= XW && WOUT + 2 * P2 <= W1 && WOUT <= W2, "T fits the buffer and covers what the owned outputs read");
+};
+
+// Each kernel is defined and instantiated in its own file for the (k, dilation) listed here; pair_host.hip launches from the
+// same lists.  k = 3 through the F(2,3) kernels (one sub-filter, 2 products per output instead of 3) measured neutral in the
+// forward (NOTES round 4): DISSC_EXPERIMENTAL=1 builds only.
+template <int KS, int DIL> __global__ void respair32_f23_kernel(const PairArgs a);
+template <int KS, int DIL> __global__ void respair32_tc6_kernel(const PairArgs a);
+template <int KS, int DIL> __global__ void respair16_f23_kernel(const PairArgs a);
+#if DISSC_EXPERIMENTAL
+#define DISSC_PAIR_F23_SHAPES(X) X(11, 1) X(11, 3) X(11, 5) X(3, 1) X(3, 3) X(3, 5)
+#else
+#define DISSC_PAIR_F23_SHAPES(X) X(11, 1) X(11, 3) X(11, 5)
+#endif
+#define DISSC_PAIR_TC6_SHAPES(X) X(7, 1) X(7, 3) X(7, 5) X(11, 1) X(11, 3) X(11, 5)
 
 }  // namespace dissc

@@ -8,7 +8,7 @@
 //   * B^T (entries 0 / +-1) is one subtraction or addition per B operand on the way from LDS to the MFMA:
 //       b0 = x0 - x2, b1 = x1 + x2, b2 = x2 - x1, b3 = x1 - x3           (x_q = window sample at + q D)
 //   * A^T is three additions per output, in registers: y_even = Y0 + Y1 + Y2, y_odd = Y1 - Y2 - Y3
-//   * G (host): U_p = G w per triple of taps, rows (1, 0, 0), (1/2, 1/2, 1/2), (1/2, -1/2, 1/2), (0, 0, 1)
+//   * G (host, pair_host.hip): U_p = G w per triple of taps, rows (1, 0, 0), (1/2, 1/2, 1/2), (1/2, -1/2, 1/2), (0, 0, 1)
 // and the kernel keeps the shape of respair32_kernel (respair.hip): window of lrelu(x) in LDS, conv_d, T = lrelu(. + b1) back
 // into the same LDS, conv_1, wave-private epilogue patches.  The k = 11 taps are four sub-filters of three taps with tap
 // stride NS = 4 (tap 11 is a zero: its samples still enter the transforms, so the window holds real data there); an MFMA
@@ -16,42 +16,21 @@
 // LDS fragment reads where the direct form makes 6.  A wave's 64 columns are 128 outputs, the workgroup's 256 columns 512
 // (480 / 504 for d = 5 / 3, whose units of 2 D outputs do not divide 512).
 // fp32 operands, fp32 products, fp32 accumulation on v_mfma_f32_32x32x2_f32; not bit-identical to the direct pair.
-#include <string.h>
-
-#include <vector>
-
+// Geometry (F23Geo32, Tc6Geo) and what every pair kernel shares: respair_f23.h; weights, launch and dispatch: pair_host.hip.
 #include "common.h"
 #include "respair_f23.h"
 
 namespace dissc {
 
 template <int KS_, int DIL>
-struct F23Geo {
-  static constexpr int KS = KS_, NS = (KS_ + 2) / 3, C = 32, NW = 4;
-  static constexpr int P2 = (KS - 1) / 2, P1 = P2 * DIL;
-  static constexpr int D1 = DIL * NS, D2 = NS;
-  static constexpr int NCOLS = 64 * NW;                               // pair-columns per conv and workgroup
-  static constexpr int NU1 = NCOLS / D1, NC1 = NU1 * D1, W1 = 2 * NC1;  // positions of T conv_d produces: [o0 - P2, o0 - P2 + W1)
-  static constexpr int NU2 = NCOLS / D2, NC2 = NU2 * D2, W2 = 2 * NC2;  // outputs conv_1 computes: [o0, o0 + W2)
-  static constexpr int WOUT = ((W1 - 2 * P2) < W2 ? (W1 - 2 * P2) : W2) & ~3;  // outputs a workgroup owns
-  static constexpr int REACH1 = (3 * NS - 1) * DIL, REACH2 = 3 * NS - 1;       // samples read beyond the last column's first
-  static constexpr int XW1 = round32_16(3 + W1 + REACH1);
-  static constexpr int XW2 = round32_16(W2 + REACH2 + 1);
-  static constexpr int XW = XW1 > XW2 ? XW1 : XW2;  // row stride of the one LDS buffer (x window, then T, then the patches)
-  static constexpr int PW = 128 + 4;                // patch row: a wave's 128 outputs
-  static_assert(NW * 8 * PW <= C * XW, "the epilogue patches fit the buffer");
-  static_assert(W1 <= XW && W2 + REACH2 < XW, "T fits the buffer");
-};
-
-template <int KS_, int DIL>
-__global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairFArgs a) {
-  using G = F23Geo<KS_, DIL>;
+__global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairArgs a) {
+  using G = F23Geo32<KS_, DIL>;
   constexpr int C = G::C, NW = G::NW, NT = 64 * NW, NS = G::NS, P2 = G::P2, P1 = G::P1, D1 = G::D1, D2 = G::D2, XW = G::XW,
                 W1 = G::W1, NC1 = G::NC1, NC2 = G::NC2, WOUT = G::WOUT, PW = G::PW;
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [C][XW]
 
   int b, len, o0;
-  if (!f23_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
+  if (!pair_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   const int tin0 = o0 - P2 - P1;
@@ -59,32 +38,7 @@ __global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairFArgs a
   const float slope = a.slope;
   const float* xb = a.x + (size_t)b * a.bstride;
 
-  // ---- lrelu(x) on [tb, tb + XW) into LDS: every 16-byte load of the thread first (clamped, unconditional), then activation,
-  // zeros outside the utterance and the stores (loads issued one per loop trip would be as many dependent round trips) ----
-  {
-    constexpr int NV = XW / 4, NIT = (C * NV + NT - 1) / NT;
-    f32x4 sv[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * NT;
-      const int r = i / NV < C ? i / NV : C - 1, v = i - (i / NV) * NV;
-      const int t = tb + 4 * v;
-      const int tc = t < 0 ? 0 : (t > a.ld - 4 ? a.ld - 4 : t);
-      sv[it] = *reinterpret_cast<const f32x4*>(xb + (size_t)r * a.ld + tc);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * NT;
-      if (i >= C * NV) continue;
-      const int r = i / NV, v = i - r * NV;
-      const int t = tb + 4 * v;
-      // (t is a multiple of 4 and so is ld: a clamped quad lies wholly outside [0, len) and is zeroed here)
-      f32x4 val = sv[it];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? (val[e] > 0.f ? val[e] : val[e] * slope) : 0.f;
-      *reinterpret_cast<f32x4*>(xs + r * XW + 4 * v) = val;
-    }
-  }
+  pair_stage_window<C, XW, NT>(a, xb, xs, tb, len, tid);
 
   // this lane's two columns of each conv: column -> (unit tau, phase rho) -> first sample 2 D tau + rho
   int base1[2], base2[2];
@@ -162,10 +116,7 @@ __global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairFArgs a
 
   // ---- T = lrelu(conv_d + b1) inside the utterance, 0 outside, into the same buffer: positions [0, W1) <-> times o0 - P2 + . ----
   __syncthreads();  // every wave is done reading the x window
-  for (int i = tid; i < C * (XW - W1); i += NT) {
-    const int r = i / (XW - W1), v = i - r * (XW - W1);
-    xs[r * XW + W1 + v] = 0.f;  // what conv_1's last columns read beyond T
-  }
+  pair_zero_beyond_t<C, XW, W1, NT>(xs, tid);
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni) {
     const int c = wave * 64 + ni * 32 + l31;
@@ -236,16 +187,7 @@ __global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairFArgs a
       const int row = 8 * qd + prw;
       const float bz = a.b2[row];
       const size_t idx = ob + (size_t)row * a.ld + tcol;
-      const int nv = len - tcol;
-      if (nv >= 4) {
-        const f32x4 r4 = rv[p];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (v[e] + bz) + r4[e];
-        epi_store_res(epi, quad_at(a.out + idx), quad_at(a.acc + idx), v, [&] { return pa[p]; }, a.mrf_div);
-      } else {
-        for (int e = 0; e < nv; ++e)
-          epi_store_res(epi, a.out + idx + e, a.acc + idx + e, (v[e] + bz) + a.x[idx + e], [&] { return a.acc[idx + e]; }, a.mrf_div);
-      }
+      pair_store_tail(a, epi, idx, v, bz, rv[p], [&] { return pa[p]; }, 0, len - tcol < 4 ? len - tcol : 4);
     }
   }
 }
@@ -259,7 +201,7 @@ __global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairFArgs a
 //       b0 = 4 x0 - 5 x2 + x4      b1 = (x4 - 4 x2) + (x3 - 4 x1)      b3 = (x4 - x2) + 2 (x3 - x1)
 //       b5 = 4 x1 - 5 x3 + x5      b2 = (x4 - 4 x2) - (x3 - 4 x1)      b4 = (x4 - x2) - 2 (x3 - x1)
 //   * A^T in registers: y0 = Y0 + Y1 + Y2 + Y3 + Y4, y1 = (Y1 - Y2) + 2 (Y3 - Y4), y2 = (Y1 + Y2) + 4 (Y3 + Y4) + Y5
-//   * G (host, kTc6G): U_p = G w per quadruple of taps
+//   * G (host, kTc6G in pair_host.hip): U_p = G w per quadruple of taps
 // Six points x 16 accumulators leave room for ONE 32-column tile per wave (two spill), and the weights of a (chunk,
 // sub-filter) come one 8-channel half at a time, double-buffered (6 x 16 bytes per lane and step).  conv_d's columns are dealt
 // over the workgroup's 128; conv_1's per wave (32 / D2 whole units, 96 outputs at k = 7 and 90 at k = 11), so that a wave's
@@ -268,36 +210,14 @@ __global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairFArgs a
 // stored element by element.
 // ---------------------------------------------------------------------------------------------
 template <int KS_, int DIL>
-struct Tc6Geo {
-  static constexpr int KS = KS_, NS = (KS_ + 3) / 4, C = 32, NW = 4;
-  static constexpr int P2 = (KS - 1) / 2, P1 = P2 * DIL;
-  static constexpr int D1 = DIL * NS, D2 = NS;
-  static constexpr int NCOLS = 32 * NW;                                 // columns of conv_d per workgroup
-  static constexpr int NU1 = NCOLS / D1, NC1 = NU1 * D1, W1 = 3 * NC1;  // positions of T conv_d produces: [o0 - P2, o0 - P2 + W1)
-  static constexpr int NCW2 = 32 / D2 * D2, OW = 3 * NCW2, W2 = NW * OW;  // conv_1: columns and outputs per wave, outputs [o0, o0 + W2)
-  static constexpr int WOUT = ((W1 - 2 * P2) < W2 ? (W1 - 2 * P2) : W2) & ~3;  // outputs a workgroup owns
-  static constexpr int REACH1 = (4 * NS - 1) * DIL, REACH2 = 4 * NS - 1;  // samples read beyond the conv's last position
-  // row stride of the one LDS buffer (x window, then T, then the patches): a multiple of 4 and no more -- the two halves of a
-  // wave read different rows, but a 4-byte LDS read serves them in separate passes, so the stride's residue modulo the 32 banks
-  // buys nothing here, and rounding it to 16 mod 32 as the F(2,3) kernel does would cost the d = 3 / 5 shapes a workgroup per CU
-  static constexpr int XW1 = (3 + W1 + REACH1 + 3) & ~3;
-  static constexpr int XW2 = (W2 + REACH2 + 3) & ~3;
-  static constexpr int XW = XW1 > XW2 ? XW1 : XW2;
-  static constexpr int PW = 96 + 4;                 // patch row: a wave's outputs from the 16-byte boundary below its first
-  static constexpr int OCC = 3 * 4 * C * XW <= 160 * 1024 ? 3 : 2;  // workgroups per CU the LDS admits: the register budget follows
-  static_assert(3 + OW <= PW - 1 && NW * 8 * PW <= C * XW, "the epilogue patches fit the buffer");
-  static_assert(W1 <= XW && WOUT + 2 * P2 <= W1 && WOUT <= W2, "T fits the buffer and covers what the owned outputs read");
-};
-
-template <int KS_, int DIL>
-__global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_kernel(const PairFArgs a) {
+__global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_kernel(const PairArgs a) {
   using G = Tc6Geo<KS_, DIL>;
   constexpr int C = G::C, NW = G::NW, NT = 64 * NW, NS = G::NS, P2 = G::P2, P1 = G::P1, D1 = G::D1, D2 = G::D2, XW = G::XW,
                 W1 = G::W1, NC1 = G::NC1, NCW2 = G::NCW2, OW = G::OW, WOUT = G::WOUT, PW = G::PW;
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [C][XW]
 
   int b, len, o0;
-  if (!f23_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
+  if (!pair_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   const int tin0 = o0 - P2 - P1;
@@ -305,30 +225,7 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
   const float slope = a.slope;
   const float* xb = a.x + (size_t)b * a.bstride;
 
-  // ---- lrelu(x) on [tb, tb + XW) into LDS, as respair32_f23_kernel ----
-  {
-    constexpr int NV = XW / 4, NIT = (C * NV + NT - 1) / NT;
-    f32x4 sv[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * NT;
-      const int r = i / NV < C ? i / NV : C - 1, v = i - (i / NV) * NV;
-      const int t = tb + 4 * v;
-      const int tc = t < 0 ? 0 : (t > a.ld - 4 ? a.ld - 4 : t);
-      sv[it] = *reinterpret_cast<const f32x4*>(xb + (size_t)r * a.ld + tc);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * NT;
-      if (i >= C * NV) continue;
-      const int r = i / NV, v = i - r * NV;
-      const int t = tb + 4 * v;
-      f32x4 val = sv[it];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) val[e] = ((t + e) >= 0 && (t + e) < len) ? (val[e] > 0.f ? val[e] : val[e] * slope) : 0.f;
-      *reinterpret_cast<f32x4*>(xs + r * XW + 4 * v) = val;
-    }
-  }
+  pair_stage_window<C, XW, NT>(a, xb, xs, tb, len, tid);
 
   // this lane's column of each conv: column -> (unit tau, phase rho) -> first sample 3 D tau + rho
   int base1, base2;
@@ -399,10 +296,7 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
 
   // ---- T = lrelu(conv_d + b1) inside the utterance, 0 outside, into the same buffer: positions [0, W1) <-> times o0 - P2 + . ----
   __syncthreads();  // every wave is done reading the x window
-  for (int i = tid; i < C * (XW - W1); i += NT) {
-    const int r = i / (XW - W1), v = i - r * (XW - W1);
-    xs[r * XW + W1 + v] = 0.f;  // what conv_1's last columns read beyond T
-  }
+  pair_zero_beyond_t<C, XW, W1, NT>(xs, tid);
   {
     const int c = wave * 32 + l31;
     if (c < NC1 && !(a.dbg & 2)) {
@@ -440,7 +334,7 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
   const int wend = ws + OW < WOUT ? ws + OW : WOUT;
   const int elo = ncol < ws ? ws - ncol : 0;      // elements [elo, ehi) of the quad are this wave's, owned and inside the utterance
   const int ehi = (wend - ncol < len - tcol ? wend - ncol : len - tcol) < 4 ? (wend - ncol < len - tcol ? wend - ncol : len - tcol) : 4;
-  const bool live = ehi > elo, full = elo == 0 && ehi == 4;
+  const bool live = ehi > elo;
   const int epi = a.epi;
   const bool rmw = epi != EPI_RES && epi != EPI_MRF_SET;
   if (a.dbg & 4) {
@@ -478,129 +372,16 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
       const int row = 8 * qd + prw;
       const float bz = a.b2[row];
       const size_t idx = ob + (size_t)row * a.ld + tcol;
-      if (full) {
-        const f32x4 r4 = rv[p];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (v[e] + bz) + r4[e];
-        epi_store_res(epi, quad_at(a.out + idx), quad_at(a.acc + idx), v, [&] { return pa[p]; }, a.mrf_div);
-      } else {
-        for (int e = elo; e < ehi; ++e)
-          epi_store_res(epi, a.out + idx + e, a.acc + idx + e, (v[e] + bz) + a.x[idx + e], [&] { return a.acc[idx + e]; }, a.mrf_div);
-      }
+      pair_store_tail(a, epi, idx, v, bz, rv[p], [&] { return pa[p]; }, elo, ehi);
     }
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------
-// the 32-channel stage (this file) and the 16-channel one (respair16_f23.hip); k = 3 (one sub-filter, 2 products per output
-// instead of 3) in DISSC_EXPERIMENTAL=1 builds only
-bool pair_f23_supported(int C, int KS, int dil) {
-  return (C == 16 || C == 32) && (KS == 11 || (KS == 3 && DISSC_EXPERIMENTAL)) && (dil == 1 || dil == 3 || dil == 5);
-}
-
-// w: [32][32][11] -> U_p[co][ci][j] = sum_i G[p][i] w[co][ci][j + 4 i] in A-fragment order [chunk][sub-filter][point][half][lane][4]
-int pack_pair_f23(const float* w, float** dev, int C_, int KS) {
-  if (C_ == 16) return pack_pair16_f23(w, dev, KS);
-  constexpr int C = 32;
-  const int NS = (KS + 2) / 3;
-  std::vector<float> packed((size_t)2 * NS * 4 * 2 * 64 * 4);
-  size_t o = 0;
-  for (int c = 0; c < 2; ++c)
-    for (int j = 0; j < NS; ++j)
-      for (int p = 0; p < 4; ++p)
-        for (int hf = 0; hf < 2; ++hf)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < 4; ++e) {
-              const int co = lane & 31, ci = 16 * c + 2 * (4 * hf + e) + (lane >> 5);
-              double u = 0.0;
-              for (int i = 0; i < 3; ++i) {
-                const int tap = j + NS * i;
-                if (tap < KS) u += kF23G[p][i] * (double)w[((size_t)co * C + ci) * KS + tap];
-              }
-              packed[o++] = (float)u;
-            }
-  return upload(packed, dev);
-}
-
-// six points: the 32-channel stage, k = 7 and 11
-bool pair_tc6_supported(int C, int KS, int dil) { return C == 32 && (KS == 7 || KS == 11) && (dil == 1 || dil == 3 || dil == 5); }
-
-// w: [32][32][k] -> U_p[co][ci][j] = sum_i G[p][i] w[co][ci][j + NS i], NS = ceil(k / 4), in A-fragment order
-// [chunk][sub-filter][half][point][lane][4]
-int pack_pair_tc6(const float* w, float** dev, int C_, int KS) {
-  constexpr int C = 32;
-  if (C_ != C) {
-    set_error("pack_pair_tc6: no instance for C = %d", C_);
-    return DISSC_EINVAL;
-  }
-  const int NS = (KS + 3) / 4;
-  std::vector<float> packed((size_t)2 * NS * 2 * 6 * 64 * 4);
-  size_t o = 0;
-  for (int c = 0; c < 2; ++c)
-    for (int j = 0; j < NS; ++j)
-      for (int hf = 0; hf < 2; ++hf)
-        for (int p = 0; p < 6; ++p)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < 4; ++e) {
-              const int co = lane & 31, ci = 16 * c + 2 * (4 * hf + e) + (lane >> 5);
-              double u = 0.0;
-              for (int i = 0; i < 4; ++i) {
-                const int tap = j + NS * i;
-                if (tap < KS) u += kTc6G[p][i] * (double)w[((size_t)co * C + ci) * KS + tap];
-              }
-              packed[o++] = (float)u;
-            }
-  return upload(packed, dev);
-}
-
-template <int KS_, int DIL>
-static int launch_tc6_t(const PairFArgs& a, int B, int Lmax, hipStream_t stream) {
-  using G = Tc6Geo<KS_, DIL>;
-  static DeviceOnce attr_once;  // per device (common.h)
-  DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&respair32_tc6_kernel<KS_, DIL>), 160 * 1024));
-  dim3 grid((Lmax + G::WOUT - 1) / G::WOUT, B);
-  hipLaunchKernelGGL((respair32_tc6_kernel<KS_, DIL>), grid, dim3(256), sizeof(float) * G::C * G::XW, stream, a);
-  DISSC_HIP_CHECK(hipGetLastError());
-  return DISSC_OK;
-}
-
-template <int KS_, int DIL>
-static int launch_f23_t(const PairFArgs& a, int B, int Lmax, hipStream_t stream) {
-  using G = F23Geo<KS_, DIL>;
-  static DeviceOnce attr_once;  // per device (common.h)
-  DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&respair32_f23_kernel<KS_, DIL>), 160 * 1024));
-  dim3 grid((Lmax + G::WOUT - 1) / G::WOUT, B);
-  hipLaunchKernelGGL((respair32_f23_kernel<KS_, DIL>), grid, dim3(256), sizeof(float) * G::C * G::XW, stream, a);
-  DISSC_HIP_CHECK(hipGetLastError());
-  return DISSC_OK;
-}
-
-int launch_pair_f23(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
-                    int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream) {
-  PairFArgs a;
-  a.x = x; a.out = out; a.acc = acc; a.w1 = pw.w1; a.w2 = pw.w2; a.b1 = pw.b1; a.b2 = pw.b2;
-  a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul; a.ld = ld;
-  a.bstride = (long long)pw.C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = opts().kernel_dbg;
-  if (pw.form == 2) {
-#define DISSC_TC6(K_, D_) \
-  if (pw.C == 32 && pw.KS == K_ && pw.dil == D_) return launch_tc6_t<K_, D_>(a, B, Lmax, stream);
-    DISSC_TC6(7, 1) DISSC_TC6(7, 3) DISSC_TC6(7, 5) DISSC_TC6(11, 1) DISSC_TC6(11, 3) DISSC_TC6(11, 5)
-#undef DISSC_TC6
-    set_error("launch_pair_f23: no six-point instance for C = %d, k = %d, dilation %d", pw.C, pw.KS, pw.dil);
-    return DISSC_EINVAL;
-  }
-  if (pw.C == 16) return launch_pair16_f23(a, pw.KS, pw.dil, B, Lmax, stream);
-#define DISSC_F23(K_, D_) \
-  if (pw.KS == K_ && pw.dil == D_) return launch_f23_t<K_, D_>(a, B, Lmax, stream);
-  DISSC_F23(11, 1) DISSC_F23(11, 3) DISSC_F23(11, 5)
-#if DISSC_EXPERIMENTAL  // k = 3 through these kernels measured neutral in the forward (NOTES round 4): not in the default build
-  DISSC_F23(3, 1) DISSC_F23(3, 3) DISSC_F23(3, 5)
-#endif
-#undef DISSC_F23
-  set_error("launch_pair_f23: no instance for k = %d, dilation %d", pw.KS, pw.dil);
-  return DISSC_EINVAL;
-}
+#define DISSC_INSTANCE(K_, D_) template __global__ void respair32_f23_kernel<K_, D_>(const PairArgs);
+DISSC_PAIR_F23_SHAPES(DISSC_INSTANCE)
+#undef DISSC_INSTANCE
+#define DISSC_INSTANCE(K_, D_) template __global__ void respair32_tc6_kernel<K_, D_>(const PairArgs);
+DISSC_PAIR_TC6_SHAPES(DISSC_INSTANCE)
+#undef DISSC_INSTANCE
 
 }  // namespace dissc

@@ -11,7 +11,6 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SHAPES = [(32, 7, 1), (32, 7, 3), (32, 7, 5), (32, 11, 1), (32, 11, 3), (32, 11, 5), (64, 3, 1), (64, 3, 3), (64, 3, 5)]
 
 
 @pytest.fixture(scope="module")

@@ -3,7 +3,7 @@ the matrices of F(3,4) at the points 0, +-1, +-2, inf in exact rational arithmet
 kernel's fp32 arithmetic (operands rounded to fp32, one rounding per fused multiply-add, the kernel's order of channels,
 sub-filters and transform steps) against float64, next to a direct-order fp32 model of the same pair.
 
-The host packing (pack_pair_tc6: U = G w in double, rounded once) uploads to the device and has no host-only entry, so it is
+The host packing (pack_pair_reg: U = G w in double, rounded once) uploads to the device and has no host-only entry, so it is
 covered by the GPU tests (tests/test_gpu_pairs_tc6.py); the model below forms U the same way."""
 from fractions import Fraction as Fr
 

@@ -3,7 +3,7 @@
 #   tools/capture_profiles.sh <out dir under gpurun_out> gen|enc
 # One --kernel-trace --stats pass and three --pmc passes (SQ counters, FETCH_SIZE, WRITE_SIZE: separate passes,
 # never combined with other trace domains), all with serial launches (multistream=0) so that per-kernel
-# durations do not overlap.  Tables: tools/prof_tables.py.
+# durations do not overlap.  Stops at the first pass that fails or exceeds its time limit.  Tables: tools/prof_tables.py.
 set -u
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/$1
 WHAT=$2
@@ -17,8 +17,10 @@ cd /tmp && export TMPDIR=/tmp
 export DISSC_OPTIONS=multistream=0${EXTRA_OPTS:+,$EXTRA_OPTS}
 run() {  # name, rocprof args...
   local name=$1; shift
-  timeout 300 rocprofv3 "$@" --output-format csv -d "$OUT/$name" -o "$name" -- $CMD > "$OUT/$name.log" 2>&1
-  echo "$name rc=$?"
+  timeout -k 10 300 rocprofv3 "$@" --output-format csv -d "$OUT/$name" -o "$name" -- $CMD > "$OUT/$name.log" 2>&1
+  local rc=$?
+  echo "$name rc=$rc"
+  [ $rc -eq 0 ] || exit $rc
 }
 run trace --kernel-trace --stats
 # the BENCHED schedule (multistream=1: parallel streams), kernel trace only: its wall span per forward closes the check "kernel time
