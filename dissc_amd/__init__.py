@@ -8,5 +8,6 @@ without the built library raises.
 """
 from ._lib import lib, DisscError, library_path  # noqa: F401
 from .generator import CodeGenerator, AttrDict  # noqa: F401
+from .mel import MelSpectrogram, mel_spectrogram  # noqa: F401
 
-__all__ = ["lib", "DisscError", "library_path", "CodeGenerator", "AttrDict"]
+__all__ = ["lib", "DisscError", "library_path", "CodeGenerator", "AttrDict", "MelSpectrogram", "mel_spectrogram"]

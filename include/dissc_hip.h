@@ -576,6 +576,39 @@ int dissc_train_read(dissc_trainer_t t, int i, int which, float* host_out, void*
  * by the loss) only.  n: floats to copy, at most the buffer's size. */
 int dissc_train_debug_read(dissc_trainer_t t, int layer, int which, float* host_out, size_t n, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Log-mel spectrogram and the L1 distance between two of them (the vocoder's validation figure).
+ * Replaces: mel_spectrogram, reference sr/dataset.py:46-69 (center=False), and the F.l1_loss on its outputs that
+ *   sr/train.py:231-269 logs as validation/mel_spec_error.  Restated in tests/mel_ref.py.
+ * dissc_mel_filterbank: librosa's default filterbank (Slaney scale, Slaney area normalisation), fp64
+ *   [num_mels][n_fft / 2 + 1] into a HOST array; fmax <= 0 means sr / 2.  Host only, no GPU needed.
+ * dissc_mel_create: host only as well (the packed bases go to the device with the handle's first launch, on the device
+ *   current then; a handle serves that one device).  Supported: n_fft a multiple of 64 up to 2048, win <= n_fft,
+ *   4 <= hop <= n_fft with n_fft - hop even (a multiple of 4 takes the faster 16-byte LDS reads), num_mels <= 128, 0 <= fmin < fmax <= sr / 2, and a tile of
+ *   DISSC_MEL_TILE_FRAMES frames that fits the LDS; anything else is DISSC_EINVAL with a message.
+ * dissc_mel_frames: n_samples / hop.
+ * wav f32 [B][ld], n_samples_dev i32 [B] on the device (cut to ld).  An utterance needs n_samples > (n_fft - hop) / 2,
+ *   or its mirror extension is undefined: the caller checks (the counts are on the device here); such an utterance has no
+ *   frames, and a NaN sum.
+ * dissc_mel_forward: mel_out f32 [B][num_mels][ldF], ldF >= ld / hop; columns at and beyond an utterance's frames are not
+ *   written.  flags: DISSC_MEL_LINEAR = mel before the log.
+ * dissc_mel_l1: a [B][lda], b [B][ldb], the same n_samples for both (cut to the shorter row) -> sum_out f64 [B] =
+ *   sum over the utterance's frames x num_mels cells of |logmel(a) - logmel(b)|; neither mel is stored.  One fp32
+ *   subtraction per cell, all additions in double in a fixed order: bit-reproducible, independent of the batch.
+ * ------------------------------------------------------------------------- */
+#define DISSC_MEL_TILE_FRAMES 64
+#define DISSC_MEL_LINEAR 1
+typedef struct dissc_mel* dissc_mel_t;
+int dissc_mel_filterbank(int sr, int n_fft, int num_mels, double fmin, double fmax, double* out);
+int dissc_mel_create(int sr, int n_fft, int num_mels, int hop, int win, double fmin, double fmax, dissc_mel_t* out);
+void dissc_mel_destroy(dissc_mel_t h);
+int dissc_mel_frames(dissc_mel_t h, int n_samples);
+size_t dissc_mel_workspace_bytes(dissc_mel_t h, int B, int Nmax);
+int dissc_mel_forward(dissc_mel_t h, const float* wav, int ld, const int32_t* n_samples_dev, int B, float* mel_out, int ldF,
+                      int flags, void* workspace, size_t workspace_bytes, void* stream);
+int dissc_mel_l1(dissc_mel_t h, const float* a, int lda, const float* b, int ldb, const int32_t* n_samples_dev, int B,
+                 double* sum_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
