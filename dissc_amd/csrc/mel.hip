@@ -20,47 +20,14 @@
 //
 // DFT bins whose mel column is all zero below the first / above the last used bin are not computed (DC and Nyquist for the
 // shipped 0 .. sr / 2 configs: 511 bins = 16 blocks with one zero row), k chunks where the window is zero are skipped.
+// The steps of a tile are in mel_tile.h, shared with the gradient (mel_grad.hip), which recomputes the forward with them.
 #include <math.h>
 
 #include <algorithm>
 
-#include "common.h"
-#include "ragged_epi.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "mel_tile.h"
 
 namespace dissc {
-
-constexpr int MEL_TF = DISSC_MEL_TILE_FRAMES;  // frames per workgroup: two 32-column MFMA tiles per wave
-constexpr int MEL_NT = 256;
-constexpr int MEL_MAX_LDS = 160 * 1024;
-static_assert(MEL_TF == 64, "a wave runs exactly two 32-frame MFMA tiles");
-
-struct MelArgs {
-  const float* sig[2];  // [B][ld[s]] each; sig[1] only for mel_l1
-  int ld[2];
-  int n_cap;                 // an utterance is cut to this many samples (the shorter row)
-  const int32_t* n_samples;  // [B]
-  int B;
-  const float* dft;   // [block][chunk][cos | sin][lane][4]: lane l, e -> row (l & 31) of the block, k = 8 chunk + 4 (l >> 5) + e
-  const float* melw;  // [block][mel tile][q][lane][4]: lane l, e -> mel row (l & 31) of the tile, bin 8 q + 4 (l >> 5) + e
-  unsigned dft_bytes, melw_bytes;
-  int n_fft, hop, pad, rs, rows, nblk, nchunk, j_lo, j_hi, num_mels;
-  float* out;  // [B][num_mels][ldF] (mel_forward)
-  int ldF, linear;
-  float log_floor;     // log(1e-5f), rounded once on the host
-  double* tile_sums;   // one per enumerated workgroup (mel_l1)
-};
-
-__device__ __forceinline__ int mel_len(const MelArgs& p, int i) {
-  const int n = p.n_samples[i];
-  return n < p.n_cap ? n : p.n_cap;
-}
-// frames of utterance i; none when it is too short to mirror
-__device__ __forceinline__ int mel_nframes(const MelArgs& p, int i) {
-  const int n = mel_len(p, i);
-  return n > p.pad ? n / p.hop : 0;
-}
 
 template <int NMT, int NSIG, bool VEC>
 __global__ void __launch_bounds__(MEL_NT) mel_kernel(const MelArgs p) {
@@ -69,7 +36,6 @@ __global__ void __launch_bounds__(MEL_NT) mel_kernel(const MelArgs p) {
   if (!ragged_tile<MEL_TF>(blockIdx.x, p.B, [&](int i) { return mel_nframes(p, i); }, b, tile, F)) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, h = lane >> 5;
   const int n = mel_len(p, b);
-  const int hop = p.hop, RS = p.rs;
   const __amdgpu_buffer_rsrc_t rs_dft = wave_rsrc(p.dft, p.dft_bytes), rs_mel = wave_rsrc(p.melw, p.melw_bytes);
 
   float keep[2][NMT][16];  // wave 0: log-mel of the first signal (mel_l1)
@@ -78,18 +44,7 @@ __global__ void __launch_bounds__(MEL_NT) mel_kernel(const MelArgs p) {
 #pragma unroll 1
   for (int sg = 0; sg < NSIG; ++sg) {
     if (sg) __syncthreads();  // wave 0 has read the last partial sums out of the LDS
-    // ---- the tile's samples, mirrored about the utterance's own ends; row r of the LDS holds samples [hop r, hop (r + 1))
-    {
-      const float* x = p.sig[sg] + (size_t)b * p.ld[sg];
-      const int s0 = tile * MEL_TF * hop - p.pad, total = p.rows * hop;
-      for (int i = tid; i < total; i += MEL_NT) {
-        int s = s0 + i;
-        s = s < 0 ? -s : s;
-        s = s >= n ? 2 * (n - 1) - s : s;
-        const int r = i / hop;
-        smem[r * RS + (i - r * hop)] = (s >= 0 && s < n) ? x[s] : 0.f;  // beyond the mirror: frames that are not stored
-      }
-    }
+    mel_stage(p, smem, p.sig[sg] + (size_t)b * p.ld[sg], n, tile, tid);
     __syncthreads();
 
     f32x16 macc[2][NMT];
@@ -103,98 +58,17 @@ __global__ void __launch_bounds__(MEL_NT) mel_kernel(const MelArgs p) {
 #pragma unroll 1
     for (int blk = wave; blk < p.nblk; blk += 4) {
       f32x16 ac[2], as[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ac[t][r] = as[t][r] = 0.f;
-      // the lane's four consecutive k of chunk j start at k0 = 8 j + 4 h: LDS row k0 / hop further down, column k0 % hop
-      int k0 = 8 * p.j_lo + 4 * h;
-      int col = k0 % hop;
-      int base = (l31 + k0 / hop) * RS;
-      unsigned aoff = (unsigned)(blk * p.nchunk + p.j_lo) * 2048u;
-      for (int j = p.j_lo; j < p.j_hi; ++j) {
-        const f32x4 wc = rsrc_load16(rs_dft, lane * 16, aoff);
-        const f32x4 ws = rsrc_load16(rs_dft, lane * 16, aoff + 1024u);
-        f32x4 x0, x1;
-        if (VEC) {  // hop % 4 == 0: the four k sit in one row, 16-byte aligned
-          x0 = *reinterpret_cast<const f32x4*>(smem + base + col);
-          x1 = *reinterpret_cast<const f32x4*>(smem + base + 32 * RS + col);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int c = col + e, at = base + (c >= hop ? c - hop + RS : c);  // hop >= 4: at most one row further
-            x0[e] = smem[at];
-            x1[e] = smem[at + 32 * RS];
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          ac[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wc[e], x0[e], ac[0], 0, 0, 0);
-          as[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ws[e], x0[e], as[0], 0, 0, 0);
-          ac[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wc[e], x1[e], ac[1], 0, 0, 0);
-          as[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ws[e], x1[e], as[1], 0, 0, 0);
-        }
-        aoff += 2048u;
-        col += 8;
-        while (col >= hop) {
-          col -= hop;
-          base += RS;
-        }
-      }
+      mel_stft_block<VEC>(p, smem, rs_dft, blk, lane, ac, as);
       // magnitudes in place, then straight into the mel GEMM as its B operand
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) ac[t][r] = sqrtf(ac[t][r] * ac[t][r] + as[t][r] * as[t][r] + 1e-9f);
-      const unsigned moff = (unsigned)blk * (unsigned)(NMT * 4096);
-#pragma unroll
-      for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 w = rsrc_load16(rs_mel, lane * 16, moff + (unsigned)((mt * 4 + q) * 1024));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            macc[0][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[e], ac[0][4 * q + e], macc[0][mt], 0, 0, 0);
-            macc[1][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[e], ac[1][4 * q + e], macc[1][mt], 0, 0, 0);
-          }
-        }
+        for (int r = 0; r < 16; ++r) ac[t][r] = mel_mag(ac[t][r], as[t][r]);
+      mel_gemm_block<NMT>(rs_mel, blk, lane, ac, macc);
     }
 
-    // ---- the four waves' partial mels: (w0 + w2) + (w1 + w3), through the LDS the samples no longer need
-    constexpr int PER_WAVE = 2 * NMT * 16 * 64;
-    __syncthreads();
-    if (wave >= 2) {
-      float* dst = smem + (wave - 2) * PER_WAVE + lane;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) dst[((t * NMT + mt) * 16 + r) * 64] = macc[t][mt][r];
-    }
-    __syncthreads();
-    if (wave < 2) {
-      const float* src = smem + wave * PER_WAVE + lane;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) macc[t][mt][r] += src[((t * NMT + mt) * 16 + r) * 64];
-    }
-    __syncthreads();
-    if (wave == 1) {
-      float* dst = smem + lane;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) dst[((t * NMT + mt) * 16 + r) * 64] = macc[t][mt][r];
-    }
-    __syncthreads();
+    mel_sum_waves<NMT>(smem, wave, lane, macc);  // through the LDS the samples no longer need
     if (wave == 0) {
-      const float* src = smem + lane;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int frame = tile * MEL_TF + t * 32 + l31;
@@ -202,7 +76,7 @@ __global__ void __launch_bounds__(MEL_NT) mel_kernel(const MelArgs p) {
         for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            float v = macc[t][mt][r] + src[((t * NMT + mt) * 16 + r) * 64];
+            float v = mel_total<NMT>(smem, lane, macc, t, mt, r);
             const int row = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
             const bool live = row < p.num_mels && frame < F;
             if (NSIG == 1) {
@@ -270,17 +144,6 @@ static bool mel_filterbank(int sr, int n_fft, int num_mels, double fmin, double 
 }
 
 }  // namespace dissc
-
-struct dissc_mel {
-  int sr, n_fft, num_mels, hop, win, pad;
-  int b_lo, nblk, nmt, nchunk, j_lo, j_hi, rs, rows;
-  size_t lds_bytes;
-  std::vector<float> dft_host, melw_host;  // packed, uploaded by the first launch
-  std::mutex mu;
-  int device = -1;
-  float* dft = nullptr;
-  float* melw = nullptr;
-};
 
 using namespace dissc;
 
@@ -376,6 +239,36 @@ int dissc_mel_create(int sr, int n_fft, int num_mels, int hop, int win, double f
             if (m < num_mels && bin <= b_hi)
               h->melw_host[((((size_t)blk * h->nmt + mt) * 4 + q) * 64 + l) * 4 + e] = (float)fb[(size_t)m * nb + bin];
           }
+  // the gradient's operands (mel_grad.hip): the same rows packed transposed.  Synthesis: slab of 32 frame samples x bin block,
+  // [block][slab][cos | sin][q][lane][4]: lane l, e -> sample 32 slab + (l & 31), bin 8 q + 4 (l >> 5) + e of the block -- the
+  // order in which an accumulator of the analysis holds its bins.  Mel: [block][q][lane][4]: bin l & 31, mel 8 q + 4 (l >> 5) + e.
+  h->s_lo = w_lo / 32;
+  h->s_hi = (w_lo + win + 31) / 32;
+  h->srs = hop | 1;  // odd: the 32 frames of an accumulator register fall into 32 banks
+  h->grad_lds_bytes = ((size_t)h->rows * h->rs + std::max((size_t)h->rows * h->srs, (size_t)2 * 2 * h->nmt * 16 * 64)) * sizeof(float);
+  const int nslab = n_fft / 32;
+  h->dftT_host.assign((size_t)h->nblk * nslab * 2 * 4 * 256, 0.f);
+  for (int blk = 0; blk < h->nblk; ++blk)
+    for (int sl = 0; sl < nslab; ++sl)
+      for (int q = 0; q < 4; ++q)
+        for (int l = 0; l < 64; ++l)
+          for (int e = 0; e < 4; ++e) {
+            const int bin = b_lo + blk * 32 + 8 * q + 4 * (l >> 5) + e, k = 32 * sl + (l & 31);
+            if (bin > b_hi) continue;
+            const double ph = tw * (double)(((long long)bin * k) % n_fft);
+            const size_t at = (((((size_t)blk * nslab + sl) * 2) * 4 + q) * 64 + l) * 4 + e;
+            h->dftT_host[at] = (float)(wnd[k] * cos(ph));
+            h->dftT_host[at + 1024] = (float)(wnd[k] * sin(ph));
+          }
+  h->melT_host.assign((size_t)h->nblk * h->nmt * 4 * 256, 0.f);
+  for (int blk = 0; blk < h->nblk; ++blk)
+    for (int q = 0; q < h->nmt * 4; ++q)
+      for (int l = 0; l < 64; ++l)
+        for (int e = 0; e < 4; ++e) {
+          const int m = 8 * q + 4 * (l >> 5) + e, bin = b_lo + blk * 32 + (l & 31);
+          if (m < num_mels && bin <= b_hi)
+            h->melT_host[(((size_t)blk * h->nmt * 4 + q) * 64 + l) * 4 + e] = (float)fb[(size_t)m * nb + bin];
+        }
   *out = h;
   return DISSC_OK;
 }
@@ -384,12 +277,12 @@ void dissc_mel_destroy(dissc_mel_t h) {
   if (!h) return;
   if (h->dft) (void)hipFree(h->dft);
   if (h->melw) (void)hipFree(h->melw);
+  if (h->dftT) (void)hipFree(h->dftT);
+  if (h->melT) (void)hipFree(h->melT);
   delete h;
 }
 
 int dissc_mel_frames(dissc_mel_t h, int n_samples) { return h && n_samples > 0 ? n_samples / h->hop : 0; }
-
-static int mel_max_tiles(const dissc_mel* h, int B, int Nmax) { return B * ((Nmax / h->hop + MEL_TF - 1) / MEL_TF); }
 
 size_t dissc_mel_workspace_bytes(dissc_mel_t h, int B, int Nmax) {
   if (!h || B < 1 || Nmax < 1) return 0;
@@ -399,7 +292,7 @@ size_t dissc_mel_workspace_bytes(dissc_mel_t h, int B, int Nmax) {
 }  // extern "C"
 
 // the packed bases go to the device with the handle's first launch (creating a handle needs no GPU); a handle serves one device
-static int mel_upload(dissc_mel* h) {
+int dissc::mel_upload(dissc_mel* h) {
   std::lock_guard<std::mutex> g(h->mu);
   int dev = 0;
   DISSC_HIP_CHECK(hipGetDevice(&dev));
@@ -417,7 +310,7 @@ static int mel_upload(dissc_mel* h) {
   return DISSC_OK;
 }
 
-static void mel_fill(const dissc_mel* h, MelArgs& p) {
+void dissc::mel_fill(const dissc_mel* h, MelArgs& p) {
   p.dft = h->dft; p.melw = h->melw;
   p.dft_bytes = (unsigned)((size_t)h->nblk * h->nchunk * 2048);
   p.melw_bytes = (unsigned)((size_t)h->nblk * h->nmt * 4096);

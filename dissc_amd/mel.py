@@ -4,20 +4,26 @@
     ms = MelSpectrogram.from_config(h).to('cuda:0')
     ms.forward(wav, n_samples)["mel"]          # f32 [B, num_mels, F], log(max(mel, 1e-5))
     ms.l1(gt, y_hat, n_samples)["mean"]        # f64 [B]: mean |logmel(gt) - logmel(y_hat)| per utterance
+    ms.l1_loss(gt, y_hat).backward()           # the generator's mel loss (reference sr/train.py:154-176, before the * 45)
 
 Kernels: csrc/mel.hip (C ABI ``dissc_mel_*``): the STFT as a GEMM on the fp32 matrix cores with the frames read straight
 from the staged samples, magnitudes and the mel GEMM in registers, and for ``l1`` a fused reduction that stores neither
-mel.  Restated for the tests in tests/mel_ref.py.  No torch compute op, no CPU fallback.
+mel.  csrc/mel_grad.hip: the gradient with respect to the samples (``dissc_mel_backward``, and ``dissc_mel_l1_grad``, which
+gives the L1 sums and their gradient in one pass); a waveform that requires grad goes through it, so ``mel_spectrogram``
+and ``forward`` return a mel with a ``grad_fn``.  Restated for the tests in tests/mel_ref.py.  No torch compute op on the
+hot path, no CPU fallback.
 """
 import ctypes
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import check, lib
 
 TILE_FRAMES = 64  # DISSC_MEL_TILE_FRAMES: frames per workgroup of the kernel (the tests straddle it)
+GRAD_TILE_FRAMES = 64  # DISSC_MEL_GRAD_TILE_FRAMES: the same for the gradient's kernel
 _LINEAR = 1       # DISSC_MEL_LINEAR
 
 
@@ -32,9 +38,46 @@ def _bind():
     lib.dissc_mel_workspace_bytes.restype = sz
     lib.dissc_mel_forward.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, vp, sz, vp]
     lib.dissc_mel_l1.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, sz, vp]
+    lib.dissc_mel_grad_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.dissc_mel_grad_workspace_bytes.restype = sz
+    lib.dissc_mel_backward.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, vp, i32, vp, sz, vp]
+    lib.dissc_mel_l1_grad.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, sz, vp]
 
 
 _bind()
+
+
+class _MelFn(torch.autograd.Function):
+    """mel of a waveform that requires grad: forward is the plain kernel, backward is dissc_mel_backward (first order
+    only: a backward through the backward raises)"""
+
+    @staticmethod
+    def forward(ctx, wav, ms, ns_dev, linear):
+        ctx.ms, ctx.ns_dev, ctx.linear = ms, ns_dev, linear
+        ctx.save_for_backward(wav)
+        return ms._forward(wav, ns_dev, linear)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_mel):
+        (wav,) = ctx.saved_tensors
+        return ctx.ms._backward(wav, ctx.ns_dev, g_mel, ctx.linear), None, None, None
+
+
+class _L1LossFn(torch.autograd.Function):
+    """sum_b scale_b * sum |logmel(a_b) - logmel(y_b)|: value and gradient from one dissc_mel_l1_grad call"""
+
+    @staticmethod
+    def forward(ctx, y_hat, ms, target, ns_dev, scale):
+        total, grad = ms._l1_grad(target, y_hat, ns_dev, scale)
+        ctx.save_for_backward(grad)
+        return (total * scale).sum().to(torch.float32)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g.to(torch.float32), None, None, None, None
 
 
 def mel_filterbank(sampling_rate, n_fft, num_mels, fmin=0.0, fmax=None):
@@ -58,6 +101,7 @@ class MelSpectrogram:
         self.device = None
         self._h = None
         self._ws = None
+        self._gws = None
 
     @classmethod
     def from_config(cls, h, for_loss=True):
@@ -78,7 +122,7 @@ class MelSpectrogram:
     def close(self):
         if self._h is not None:
             lib.dissc_mel_destroy(self._h)
-        self._h, self._ws = None, None
+        self._h, self._ws, self._gws = None, None, None
 
     def __del__(self):
         try:
@@ -126,21 +170,79 @@ class MelSpectrogram:
                                   f"(n_fft - hop) / 2 = {self.pad}; need more than that")
         return ns, torch.from_numpy(ns.astype(np.int32)).to(self.device)
 
+    def _grad_workspace(self, B, N):
+        need = lib.dissc_mel_grad_workspace_bytes(self._h, B, N)
+        if self._gws is None or self._gws.numel() < need:
+            self._gws = None
+            self._gws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        return self._gws, need
+
+    def _forward(self, wav, ns_dev, linear):
+        B, N = wav.shape
+        ldF = max(N // self.hop_size, 1)
+        mel = torch.zeros(B, self.num_mels, ldF, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib.dissc_mel_forward(self.handle(), wav.data_ptr(), N, ns_dev.data_ptr(), B, mel.data_ptr(), ldF,
+                                        _LINEAR if linear else 0, None, 0, _lib.current_stream_ptr(self.device)),
+                  "dissc_mel_forward")
+        return mel
+
+    def _backward(self, wav, ns_dev, g_mel, linear):
+        h = self.handle()
+        B, N = wav.shape
+        ldF = max(N // self.hop_size, 1)
+        if tuple(g_mel.shape) != (B, self.num_mels, ldF):
+            raise ValueError(f"g_mel: expected {(B, self.num_mels, ldF)}, got {tuple(g_mel.shape)}")
+        g_mel = g_mel.to(self.device, torch.float32).contiguous()
+        grad = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            ws, need = self._grad_workspace(B, N)
+            check(lib.dissc_mel_backward(h, wav.data_ptr(), N, ns_dev.data_ptr(), B, g_mel.data_ptr(), ldF,
+                                         _LINEAR if linear else 0, grad.data_ptr(), N, ws.data_ptr(), need,
+                                         _lib.current_stream_ptr(self.device)), "dissc_mel_backward")
+        return grad
+
+    def _l1_grad(self, a, b, ns_dev, scale):
+        h = self.handle()
+        B = a.shape[0]
+        total = torch.empty(B, dtype=torch.float64, device=self.device)
+        grad = torch.empty_like(b)
+        with torch.cuda.device(self.device):
+            ws, need = self._grad_workspace(B, min(a.shape[1], b.shape[1]))
+            check(lib.dissc_mel_l1_grad(h, a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1], ns_dev.data_ptr(), B,
+                                        scale.data_ptr(), total.data_ptr(), grad.data_ptr(), b.shape[1], ws.data_ptr(), need,
+                                        _lib.current_stream_ptr(self.device)), "dissc_mel_l1_grad")
+        return total, grad
+
     def forward(self, wav, n_samples=None, linear=False):
         """wav f32 [B, N] (device or host), n_samples [B] (default: N) -> {"mel": f32 [B, num_mels, max frames] on the
-        device, zero beyond an utterance's frames; "frames": int64 [B] (host)}; linear=True: the mel before the log"""
-        h = self.handle()
+        device, zero beyond an utterance's frames; "frames": int64 [B] (host)}; linear=True: the mel before the log.
+        A wav that requires grad gives a mel with a grad_fn (backward: dissc_mel_backward; cotangent columns beyond an
+        utterance's frames are ignored); any other input takes the plain path."""
+        self.handle()
+        tracked = torch.is_grad_enabled() and isinstance(wav, torch.Tensor) and wav.requires_grad
         wav = self._signal(wav, "wav")
         B, N = wav.shape
         ns, ns_dev = self._lengths(n_samples, B, N)
         frames = ns // self.hop_size
-        ldF = max(N // self.hop_size, 1)
-        mel = torch.zeros(B, self.num_mels, ldF, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(lib.dissc_mel_forward(h, wav.data_ptr(), N, ns_dev.data_ptr(), B, mel.data_ptr(), ldF,
-                                        _LINEAR if linear else 0, None, 0, _lib.current_stream_ptr(self.device)),
-                  "dissc_mel_forward")
+        mel = _MelFn.apply(wav, self, ns_dev, bool(linear)) if tracked else self._forward(wav, ns_dev, linear)
         return {"mel": mel[:, :, :max(int(frames.max()), 1)], "frames": torch.from_numpy(frames)}
+
+    def backward(self, wav, g_mel, n_samples=None, linear=False):
+        """the vector-Jacobian product of forward: g_mel f32 [B, num_mels, >= max frames] -> f32 [B, N] on the device,
+        zero at and beyond an utterance's n_samples.  Bit-reproducible, independent of the rest of the batch."""
+        self.handle()
+        wav = self._signal(wav, "wav").detach()
+        B, N = wav.shape
+        _, ns_dev = self._lengths(n_samples, B, N)
+        g_mel = torch.as_tensor(g_mel).to(self.device, torch.float32)
+        ldF = max(N // self.hop_size, 1)
+        if g_mel.dim() == 3 and g_mel.shape[2] != ldF:  # any width that holds the frames
+            full = torch.zeros(B, self.num_mels, ldF, dtype=torch.float32, device=self.device)
+            k = min(ldF, g_mel.shape[2])
+            full[:, :, :k] = g_mel[:, :, :k]
+            g_mel = full
+        return self._backward(wav, ns_dev, g_mel, linear)
 
     __call__ = forward
 
@@ -163,12 +265,53 @@ class MelSpectrogram:
                   "dissc_mel_l1")
         return {"sum": total, "cells": cells, "mean": total / cells}
 
+    def l1_grad(self, a, b, n_samples=None, scale=None):
+        """l1 and its gradient in one pass: {"sum", "cells", "mean"} as l1 gives them (the same bits), and "grad" f32
+        [B, Nb] = scale_b * d sum_b / d b (scale f64 [B], default 1), zero beyond an utterance's samples"""
+        self.handle()
+        a, b = self._signal(a, "a").detach(), self._signal(b, "b").detach()
+        if a.shape[0] != b.shape[0]:
+            raise ValueError(f"l1_grad: {a.shape[0]} and {b.shape[0]} utterances")
+        B, N = a.shape[0], min(a.shape[1], b.shape[1])
+        ns, ns_dev = self._lengths(n_samples, B, N)
+        scale = torch.ones(B, dtype=torch.float64) if scale is None else torch.as_tensor(scale, dtype=torch.float64).reshape(-1)
+        if scale.shape[0] != B:
+            raise ValueError(f"scale: need {B} factors")
+        cells = torch.from_numpy((ns // self.hop_size) * self.num_mels).to(self.device)
+        total, grad = self._l1_grad(a, b, ns_dev, scale.to(self.device).contiguous())
+        return {"sum": total, "cells": cells, "mean": total / cells, "grad": grad}
+
+    def l1_loss(self, target, y_hat, n_samples=None, reduction="mean"):
+        """the mel loss of the reference's generator step as a scalar with a grad_fn: |logmel(target) - logmel(y_hat)|
+        reduced by "mean" (all sums / all cells: F.l1_loss of the two mels for equal lengths), "utterance_mean" (the mean
+        of the utterances' means, validate.py's figure) or "sum".  One dissc_mel_l1_grad call; neither mel is stored.
+        The gradient goes to y_hat alone: a target that requires grad raises."""
+        self.handle()
+        if isinstance(target, torch.Tensor) and target.requires_grad:
+            raise ValueError("l1_loss: the target gets no gradient; detach it")
+        a, b = self._signal(target, "target"), self._signal(y_hat, "y_hat")
+        if a.shape[0] != b.shape[0]:
+            raise ValueError(f"l1_loss: {a.shape[0]} and {b.shape[0]} utterances")
+        B, N = a.shape[0], min(a.shape[1], b.shape[1])
+        ns, ns_dev = self._lengths(n_samples, B, N)
+        cells = ((ns // self.hop_size) * self.num_mels).astype(np.float64)
+        if reduction == "mean":
+            scale = np.full(B, 1.0 / cells.sum())
+        elif reduction == "utterance_mean":
+            scale = 1.0 / (B * cells)
+        elif reduction == "sum":
+            scale = np.ones(B)
+        else:
+            raise ValueError(f"l1_loss: reduction {reduction!r} (mean, utterance_mean or sum)")
+        return _L1LossFn.apply(b, self, a, ns_dev, torch.from_numpy(scale).to(self.device))
+
 
 _cache = {}
 
 
 def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False):
-    """the reference's signature (sr/dataset.py:46): y f32 [B, N] on an MI355X -> log-mel f32 [B, num_mels, N // hop_size].
+    """the reference's signature (sr/dataset.py:46): y f32 [B, N] on an MI355X -> log-mel f32 [B, num_mels, N // hop_size],
+    with a grad_fn when y requires grad (F.l1_loss on top of it trains as in the reference).
     One handle per parameter set and device (the reference keys its cache by fmax alone; that quirk is not reproduced)."""
     if center:
         raise NotImplementedError("mel_spectrogram: center=True is not implemented (the reference never uses it)")

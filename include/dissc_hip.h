@@ -595,8 +595,22 @@ int dissc_train_debug_read(dissc_trainer_t t, int layer, int which, float* host_
  * dissc_mel_l1: a [B][lda], b [B][ldb], the same n_samples for both (cut to the shorter row) -> sum_out f64 [B] =
  *   sum over the utterance's frames x num_mels cells of |logmel(a) - logmel(b)|; neither mel is stored.  One fp32
  *   subtraction per cell, all additions in double in a fixed order: bit-reproducible, independent of the batch.
+ * The gradient with respect to the samples (csrc/mel_grad.hip; the generator's mel loss, sr/train.py:154-176).  Nothing of a
+ *   forward call is kept: re / im are recomputed per tile.  No atomics, a fixed summation order: bit-reproducible, an
+ *   utterance's gradient does not depend on the batch.  Needs hop >= 8 and a tile's samples plus its overlap-add strip in
+ *   the LDS (DISSC_EINVAL otherwise), and a 16-byte aligned workspace of dissc_mel_grad_workspace_bytes(h, B, Nmax)
+ *   (Nmax: ld, or the shorter row).  The tile of the gradient is DISSC_MEL_GRAD_TILE_FRAMES frames.
+ * dissc_mel_backward: the vector-Jacobian product of dissc_mel_forward (same wav, n_samples, flags): g_mel f32
+ *   [B][num_mels][ldF], read only inside an utterance's frames -> grad_wav f32 [B][ldg], ldg >= ld; samples at and beyond
+ *   n_samples, up to ld, are written as zero.  Log mode: a cell's cotangent is divided by the mel where mel > 1e-5f (the
+ *   forward's own fp32 value and comparison) and dropped where it clamps.
+ * dissc_mel_l1_grad: the fused training form.  a (target), b (generated), scale_dev f64 [B] = d loss / d sum_b ->
+ *   sum_out f64 [B], the bits of dissc_mel_l1, and grad_b f32 [B][ldg] (ldg >= ldb) = scale_b d sum_b / d b, the bits of
+ *   dissc_mel_backward(b) for the cotangent (float)scale_b * sign(logmel(b) - logmel(a)) with sign(0) = 0; neither mel
+ *   is stored.
  * ------------------------------------------------------------------------- */
 #define DISSC_MEL_TILE_FRAMES 64
+#define DISSC_MEL_GRAD_TILE_FRAMES 64
 #define DISSC_MEL_LINEAR 1
 typedef struct dissc_mel* dissc_mel_t;
 int dissc_mel_filterbank(int sr, int n_fft, int num_mels, double fmin, double fmax, double* out);
@@ -608,6 +622,12 @@ int dissc_mel_forward(dissc_mel_t h, const float* wav, int ld, const int32_t* n_
                       int flags, void* workspace, size_t workspace_bytes, void* stream);
 int dissc_mel_l1(dissc_mel_t h, const float* a, int lda, const float* b, int ldb, const int32_t* n_samples_dev, int B,
                  double* sum_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t dissc_mel_grad_workspace_bytes(dissc_mel_t h, int B, int Nmax);
+int dissc_mel_backward(dissc_mel_t h, const float* wav, int ld, const int32_t* n_samples_dev, int B, const float* g_mel, int ldF,
+                       int flags, float* grad_wav, int ldg, void* workspace, size_t workspace_bytes, void* stream);
+int dissc_mel_l1_grad(dissc_mel_t h, const float* a, int lda, const float* b, int ldb, const int32_t* n_samples_dev, int B,
+                      const double* scale_dev, double* sum_out, float* grad_b, int ldg, void* workspace, size_t workspace_bytes,
+                      void* stream);
 
 #ifdef __cplusplus
 }
