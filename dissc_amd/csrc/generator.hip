@@ -131,8 +131,13 @@ static ConvForm td_conv_form(int C, int KS, int dil) {
 //   forward 32.84-33.00 -> 32.10-32.23 ms (five alternated runs), bit 1 alone 32.30-32.79, bit 2 alone 32.64-32.77 against
 //   32.74-32.89 (profiles/r07).  Rounding on trained-like data <= 1.4 x the direct pair's rms (bar 3).  4 / 8 = the same for
 //   C = 16: no instance, ignored.  The two options together also pick the form of dissc_respair1d's mode 3.
+// option "pair_f23_c64" (default 1), honoured only while "pair_f23" != 0: the k = 3 pairs of the 64-channel stage run as ONE
+//   register-only F(2,3) launch each (respair64_f23_kernel in respair_f23.hip: 2 C^2 products per output and conv where the two
+//   conv_wino launches it replaces execute 1.5 C^2, for two tensor passes instead of five); 0 = two transform-domain launches.
+//   Measurements: profiles/r09.
 // the register-only form of a pair (DevPairW::form: 1 F(2,3), 2 six points), or 0
 static int pair_reg_form(int C, int KS, int dil) {
+  if (C == 64) return KS == 3 && opts().pair_f23 != 0 && opts().pair_f23_c64 && pair_f23_supported(C, KS, dil) ? 1 : 0;
   if (C != 16 && C != 32) return 0;
   const int stage = C == 32 ? 1 : 2;
   if (KS == 3) return pair_f23_supported(C, KS, dil) && (opts().pair_f23 & (stage << 2)) ? 1 : 0;
@@ -167,14 +172,17 @@ static ChainPlan plan_chain(int C, int KS, const int* dil, int prec) {
   // the direct fused pair needs fp32 weights in its layout (16x16x4 at C = 16, 32x32x2 at C = 32: make_conv's choice)
   bool fused = prec == 0 && (C < 32 || opts().use_mfma32) && C <= opts().pair_max_c;
   for (int m = 0; m < 3; ++m) fused = fused && respair_supported(C, KS, dil[m]);
+  // ... or when every pair of the chain takes a one-launch transform-domain form: x_k then ping-pongs X -> XK -> TMP -> ACC
+  bool all_td = prec == 0 && opts().wino && C > 32 && wino_wanted(C, KS);
+  for (int m = 0; m < 3; ++m) all_td = all_td && wino_supported(C, C, KS, dil[m]) && pairw_wanted(C, KS, dil[m]);
   for (int m = 0; m < 3; ++m) {
     PairPlan& p = cp.pair[m];
     const int d = dil[m];
     const bool td = prec == 0 && wino_wanted(C, KS) && wino_supported(C, C, KS, d);
     // a fused transform-domain pair writes a new x_k: at C = 64 (where the other pairs update x_k in place) and in a chain whose
     // pairs do not all fuse, only the first pair of the chain takes it
-    const bool fuse_td =
-        prec == 0 && opts().wino && pairw_wanted(C, KS, d) && (C > 32 ? td : C <= opts().pair_max_c) && (fused || m == 0);
+    const bool fuse_td = prec == 0 && opts().wino && pairw_wanted(C, KS, d) && (C > 32 ? td : C <= opts().pair_max_c) &&
+                         (fused || all_td || m == 0);
     if (fuse_td) {
       p.form = PairForm::fused_td;
       p.reg_form = (uint8_t)pair_reg_form(C, KS, d);

@@ -103,13 +103,14 @@ __device__ __forceinline__ void pair_store_tail(const PairArgs& a, int epi, size
 }
 
 // ---- the register-only kernels: geometry, declarations, instances ----
-// F(2,3): respair32_f23_kernel (C = 32, patches of 8 rows) and respair16_f23_kernel (C = 16, patches of 16 rows)
-template <int C_, int PROWS, int KS_, int DIL>
+// F(2,3): respair32_f23_kernel (C = 32, patches of 8 rows), respair16_f23_kernel (C = 16, patches of 16 rows) and
+// respair64_f23_kernel (C = 64, patches of 8 rows; WCOLS = 32: one 32-column tile per wave under two 32-row blocks)
+template <int C_, int PROWS, int KS_, int DIL, int WCOLS = 64>
 struct F23Geo {
   static constexpr int KS = KS_, NS = (KS_ + 2) / 3, C = C_, NW = 4;
   static constexpr int P2 = (KS - 1) / 2, P1 = P2 * DIL;
   static constexpr int D1 = DIL * NS, D2 = NS;
-  static constexpr int NCOLS = 64 * NW;                               // pair-columns per conv and workgroup
+  static constexpr int NCOLS = WCOLS * NW;                            // pair-columns per conv and workgroup
   static constexpr int NU1 = NCOLS / D1, NC1 = NU1 * D1, W1 = 2 * NC1;  // positions of T conv_d produces: [o0 - P2, o0 - P2 + W1)
   static constexpr int NU2 = NCOLS / D2, NC2 = NU2 * D2, W2 = 2 * NC2;  // outputs conv_1 computes: [o0, o0 + W2)
   static constexpr int WOUT = ((W1 - 2 * P2) < W2 ? (W1 - 2 * P2) : W2) & ~3;  // outputs a workgroup owns
@@ -117,12 +118,13 @@ struct F23Geo {
   static constexpr int XW1 = round32_16(3 + W1 + REACH1);
   static constexpr int XW2 = round32_16(W2 + REACH2 + 1);
   static constexpr int XW = XW1 > XW2 ? XW1 : XW2;  // row stride of the one LDS buffer (x window, then T, then the patches)
-  static constexpr int PW = 128 + 4;                // patch row: a wave's 128 outputs
+  static constexpr int PW = 2 * WCOLS + 4;          // patch row: a wave's 2 WCOLS outputs
   static_assert(NW * PROWS * PW <= C * XW, "the epilogue patches fit the buffer");
   static_assert(W1 <= XW && W2 + REACH2 < XW, "T fits the buffer");
 };
 template <int KS, int DIL> using F23Geo32 = F23Geo<32, 8, KS, DIL>;
 template <int KS, int DIL> using F23Geo16 = F23Geo<16, 16, KS, DIL>;
+template <int KS, int DIL> using F23Geo64 = F23Geo<64, 8, KS, DIL, 32>;
 
 // six points: respair32_tc6_kernel (the scheme is described in respair_f23.hip)
 template <int KS_, int DIL>
@@ -148,16 +150,18 @@ struct Tc6Geo {
 };
 
 // Each kernel is defined and instantiated in its own file for the (k, dilation) listed here; pair_host.hip launches from the
-// same lists.  k = 3 through the F(2,3) kernels (one sub-filter, 2 products per output instead of 3) measured neutral in the
-// forward (NOTES round 4): DISSC_EXPERIMENTAL=1 builds only.
+// same lists.  k = 3 through the C = 16 / 32 F(2,3) kernels (one sub-filter, 2 products per output instead of 3) measured neutral
+// in the forward (NOTES round 4): DISSC_EXPERIMENTAL=1 builds only.  At C = 64 k = 3 is the only shape (respair64_f23_kernel).
 template <int KS, int DIL> __global__ void respair32_f23_kernel(const PairArgs a);
 template <int KS, int DIL> __global__ void respair32_tc6_kernel(const PairArgs a);
 template <int KS, int DIL> __global__ void respair16_f23_kernel(const PairArgs a);
+template <int KS, int DIL> __global__ void respair64_f23_kernel(const PairArgs a);
 #if DISSC_EXPERIMENTAL
 #define DISSC_PAIR_F23_SHAPES(X) X(11, 1) X(11, 3) X(11, 5) X(3, 1) X(3, 3) X(3, 5)
 #else
 #define DISSC_PAIR_F23_SHAPES(X) X(11, 1) X(11, 3) X(11, 5)
 #endif
+#define DISSC_PAIR_F23_C64_SHAPES(X) X(3, 1) X(3, 3) X(3, 5)
 #define DISSC_PAIR_TC6_SHAPES(X) X(7, 1) X(7, 3) X(7, 5) X(11, 1) X(11, 3) X(11, 5)
 
 }  // namespace dissc

@@ -16,7 +16,7 @@
 // LDS fragment reads where the direct form makes 6.  A wave's 64 columns are 128 outputs, the workgroup's 256 columns 512
 // (480 / 504 for d = 5 / 3, whose units of 2 D outputs do not divide 512).
 // fp32 operands, fp32 products, fp32 accumulation on v_mfma_f32_32x32x2_f32; not bit-identical to the direct pair.
-// Geometry (F23Geo32, Tc6Geo) and what every pair kernel shares: respair_f23.h; weights, launch and dispatch: pair_host.hip.
+// Geometry (F23Geo32, F23Geo64, Tc6Geo) and what every pair kernel shares: respair_f23.h; weights, launch and dispatch: pair_host.hip.
 #include "common.h"
 #include "respair_f23.h"
 
@@ -377,11 +377,185 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// respair64_f23_kernel: the k = 3 residual pairs of the 64-channel stage in the same F(2,3) scheme with the roles of rows and
+// columns swapped: a wave holds the four points of ONE 32-column tile under BOTH 32-row blocks (4 x 2 x 16 accumulators), so a B
+// operand -- one LDS read and one addition -- feeds two MFMAs, and the weights come one 8-channel step at a time,
+// double-buffered (4 points x 2 row blocks x 16 bytes per lane and step).  k = 3 is one sub-filter (NS = 1): a column is the
+// output pair (t, t + d) of conv_d and (t, t + 1) of conv_1, whose four samples are two aligned 8-byte LDS reads.  A wave's 32
+// columns are 64 outputs, the workgroup's 128 columns 256 (252 / 250 for d = 3 / 5); 252 / 248 / 248 of them are owned
+// (F23Geo64).  The summation order over the input channels is ascending in steps of two, whatever the grid.
+// ---------------------------------------------------------------------------------------------
+template <int KS_, int DIL>
+__global__ void __launch_bounds__(256, 2) respair64_f23_kernel(const PairArgs a) {
+  using G = F23Geo64<KS_, DIL>;
+  constexpr int C = G::C, NW = G::NW, NT = 64 * NW, P2 = G::P2, P1 = G::P1, D1 = G::D1, D2 = G::D2, XW = G::XW, W1 = G::W1,
+                NC1 = G::NC1, NC2 = G::NC2, WOUT = G::WOUT, PW = G::PW;
+  static_assert(G::NS == 1 && D2 == 1 && XW % 2 == 0, "one sub-filter; conv_1's samples pair up into 8-byte reads");
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [C][XW]
+
+  int b, len, o0;
+  if (!pair_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, h = lane >> 5;
+  const int tin0 = o0 - P2 - P1;
+  const int tb = tin0 & ~3, sh = tin0 - tb;
+  const float slope = a.slope;
+  const float* xb = a.x + (size_t)b * a.bstride;
+
+  pair_stage_window<C, XW, NT, 2>(a, xb, xs, tb, len, tid);
+
+  // this lane's column of each conv: column -> (unit tau, phase rho) -> first sample 2 D tau + rho
+  const int col = wave * 32 + l31;
+  const int c1 = col < NC1 ? col : NC1 - 1, c2 = col < NC2 ? col : NC2 - 1;
+  const int base1 = 2 * D1 * (c1 / D1) + (c1 % D1), base2 = 2 * D2 * (c2 / D2) + (c2 % D2);
+  typedef float f32x16f __attribute__((ext_vector_type(16)));
+  typedef float f32x2f __attribute__((ext_vector_type(2)));
+  f32x16f acc[4][2];
+  auto clear = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[p][mi][e] = 0.f;
+  };
+  // one conv: 8 steps of 8 channels; per step 4 k-steps x 4 points x 2 row blocks = 32 MFMAs fed by 16 fragment reads (8 of 8
+  // bytes where the samples are neighbours) and 16 additions
+  auto taps = [&](const float* wq, const float* src, int dunit) __attribute__((always_inline)) {
+    const __amdgpu_buffer_rsrc_t wr = wave_rsrc(wq, 0x7ffffff0u);  // scalar-base loads (common.h), constant offsets
+    const unsigned lane16 = lane * 16u;
+    constexpr int NST = C / 8;
+    f32x4 av[4][2], avn[4][2];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) av[p][mi] = rsrc_load16(wr, lane16, (p * 2 + mi) * 1024u);
+#pragma unroll
+    for (int st = 0; st < NST; ++st) {
+      const int sn = st + 1 < NST ? st + 1 : st;
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) avn[p][mi] = rsrc_load16(wr, lane16, ((sn * 4 + p) * 2 + mi) * 1024u);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float* q = src + (8 * st + 2 * e + h) * XW;
+        float x0, x1, x2, x3;
+        if (dunit == 1) {  // (src + base is even in floats: 8-byte aligned)
+          const f32x2f lo = *reinterpret_cast<const f32x2f*>(q), hi = *reinterpret_cast<const f32x2f*>(q + 2);
+          x0 = lo[0]; x1 = lo[1]; x2 = hi[0]; x3 = hi[1];
+        } else {
+          x0 = q[0]; x1 = q[dunit]; x2 = q[2 * dunit]; x3 = q[3 * dunit];
+        }
+        float bq[4];
+        bq[0] = x0 - x2;
+        bq[1] = x1 + x2;
+        bq[2] = x2 - x1;
+        bq[3] = x1 - x3;
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+          for (int mi = 0; mi < 2; ++mi)
+            acc[p][mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[p][mi][e], bq[p], acc[p][mi], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) av[p][mi] = avn[p][mi];
+    }
+  };
+
+  __syncthreads();
+  clear();
+  if (!(a.dbg & 1)) taps(a.w1, xs + sh + base1, D1);
+
+  // ---- T = lrelu(conv_d + b1) inside the utterance, 0 outside, into the same buffer: positions [0, W1) <-> times o0 - P2 + . ----
+  __syncthreads();  // every wave is done reading the x window
+  pair_zero_beyond_t<C, XW, W1, NT>(xs, tid);
+  if (col < NC1 && !(a.dbg & 2)) {
+    const int pe = base1, po = pe + D1;
+    const int te = o0 - P2 + pe, to = te + D1;
+    const bool ine = te >= 0 && te < len, ino = to >= 0 && to < len;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const float bz = a.b1[row];
+        const float y0 = acc[0][mi][r], y1 = acc[1][mi][r], y2 = acc[2][mi][r], y3 = acc[3][mi][r];
+        float ve = (y0 + y1) + y2 + bz, vo = (y1 - y2) - y3 + bz;
+        ve = ve > 0.f ? ve : ve * slope;
+        vo = vo > 0.f ? vo : vo * slope;
+        xs[row * XW + pe] = ine ? ve : 0.f;
+        xs[row * XW + po] = ino ? vo : 0.f;
+      }
+  }
+  __syncthreads();
+  clear();
+  if (!(a.dbg & 1)) taps(a.w2, xs + base2, D2);
+
+  // ---- epilogue: y = x + conv_1 + b2 (or an MRF mode), 8 rows at a time through a wave-private patch [8][PW] ----
+  __syncthreads();  // every wave is done reading T, which the patches overwrite
+  float* ep = xs + wave * (8 * PW);
+  const int prow = lane >> 4, pc4 = lane & 15;
+  const int ncol = wave * 64 + 4 * pc4;
+  const int tcol = o0 + ncol;
+  const size_t ob = (size_t)b * a.bstride;
+  const bool live = ncol < WOUT && tcol < len;
+  const int epi = a.epi;
+  const bool rmw = epi != EPI_RES && epi != EPI_MRF_SET;
+  if (a.dbg & 4) {
+    if (acc[0][0][0] == 123.f) a.out[0] = 1.f;
+    return;
+  }
+  const int pcol = 2 * l31;  // (D2 = 1: the column's outputs are neighbours)
+#pragma unroll
+  for (int mq = 0; mq < 8; ++mq) {  // rows 8 mq .. 8 mq + 7
+    const int mi = mq >> 2, qd = mq & 3;
+    __builtin_amdgcn_sched_barrier(0);  // (the loads of a later trip hoisted above this one spill: 128 accumulators are live)
+    f32x4 rv[2], pa[2];
+    const int tc = tcol > a.ld - 4 ? a.ld - 4 : tcol;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int row = 8 * mq + 4 * p + prow;
+      rv[p] = *reinterpret_cast<const f32x4*>(a.x + ob + (size_t)row * a.ld + tc);
+      if (rmw && live && tcol + 4 <= len) pa[p] = *reinterpret_cast<const f32x4*>(a.acc + ob + (size_t)row * a.ld + tcol);
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rr = 4 * qd + r;
+      const float y0 = acc[0][mi][rr], y1 = acc[1][mi][rr], y2 = acc[2][mi][rr], y3 = acc[3][mi][rr];
+      f32x2f v;
+      v[0] = (y0 + y1) + y2;
+      v[1] = (y1 - y2) - y3;
+      *reinterpret_cast<f32x2f*>(ep + (r + 4 * h) * PW + pcol) = v;
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int prw = 4 * p + prow;
+      f32x4 v = *reinterpret_cast<const f32x4*>(ep + prw * PW + 4 * pc4);
+      if (!live) continue;
+      const int row = 8 * mq + prw;
+      const float bz = a.b2[row];
+      const size_t idx = ob + (size_t)row * a.ld + tcol;
+      pair_store_tail(a, epi, idx, v, bz, rv[p], [&] { return pa[p]; }, 0, len - tcol < 4 ? len - tcol : 4);
+    }
+  }
+}
+
 #define DISSC_INSTANCE(K_, D_) template __global__ void respair32_f23_kernel<K_, D_>(const PairArgs);
 DISSC_PAIR_F23_SHAPES(DISSC_INSTANCE)
 #undef DISSC_INSTANCE
 #define DISSC_INSTANCE(K_, D_) template __global__ void respair32_tc6_kernel<K_, D_>(const PairArgs);
 DISSC_PAIR_TC6_SHAPES(DISSC_INSTANCE)
+#undef DISSC_INSTANCE
+#define DISSC_INSTANCE(K_, D_) template __global__ void respair64_f23_kernel<K_, D_>(const PairArgs);
+DISSC_PAIR_F23_C64_SHAPES(DISSC_INSTANCE)
 #undef DISSC_INSTANCE
 
 }  // namespace dissc

@@ -188,6 +188,9 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *                        F(2,3)'s 8, still no LDS exchange; per launch -22...-27 % at k = 7 and -11...-16 % at k = 11, forward
  *                        2.3 % faster; rounding within 1.4 x the direct pair's on trained-like data); 4 / 8 = the same for
  *                        the 16-channel stage (no instance: ignored); 0 = F(2,3) for k = 11, the direct pair for k = 7
+ *   pair_f23_c64 (1)     read at dissc_gen_create, honoured only while pair_f23 != 0: the k = 3 residual pairs of the 64-channel
+ *                        stage run as ONE register-only F(2,3) launch each (respair64_f23_kernel in respair_f23.hip) instead of two
+ *                        conv_wino launches; 0 = the two launches.  Not bit-identical to them; rounding no larger
  *   pair_dma (1)         read at dissc_gen_create: the two-launch direct residual pairs of the >= 32-channel stages hand their
  *                        intermediate over activated with zero tails, and the second conv stages its windows by LDS-DMA
  *   wino8 (1)            read at dissc_gen_create: 1 = the ResBlock convs selected by wino8_mask run on conv_wino8.hip's

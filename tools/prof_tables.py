@@ -24,6 +24,7 @@ UPS = [(5, 11), (4, 8), (4, 8), (2, 4), (2, 4)]
 RK = [3, 7, 11]
 DIL = [1, 3, 5]
 PAIR_MAX_C = 32
+PAIR_F23_C64 = 1  # option "pair_f23_c64": the k = 3 pairs of the 64-channel stage are one launch each (respair64_f23_kernel)
 
 
 def gen_layers():
@@ -44,7 +45,7 @@ def gen_layers():
             for m, d in enumerate(DIL):
                 fl = 2.0 * ch * ch * rk * L * B
                 last = m == 2
-                if ch <= PAIR_MAX_C:  # one launch per residual pair: read x, write y (+ MRF accumulator r/w)
+                if ch <= PAIR_MAX_C or (PAIR_F23_C64 and ch == 64 and rk == 3):  # one launch per residual pair: read x, write y (+ MRF accumulator r/w)
                     out.append((f"s{i} C{ch} k{rk} d{d} pair", 2 * fl, act * (2 + (2 if last and rk != RK[0] else (1 if last else 0)))))
                 else:
                     out.append((f"s{i} C{ch} k{rk} d{d} conv1", fl, 2 * act))
@@ -151,6 +152,8 @@ def main():
             fx = fl * 6.0 * ((k + 2) // 3) / (4.0 * k)
         if "respair32_f23_kernel" in names[i][0] or "respair16_f23_kernel" in names[i][0]:  # register-only F(2,3) pairs (k = 11: four sub-filters): 8 products per output
             fx = fl * 8.0 / 11.0
+        if "respair64_f23_kernel" in names[i][0]:  # k = 3, one sub-filter: 2 products per output
+            fx = fl * 2.0 / 3.0
         if "respair32_tc6_kernel" in names[i][0]:  # register-only six-point pairs: 6 products per 3 outputs and 4-tap sub-filter
             import re
             k = int(re.search(r"respair32_tc6_kernel<(\d+)", names[i][0]).group(1))
