@@ -363,6 +363,8 @@ int pack_pairw43(const float* w, int C, int KS, float** dev);
 int launch_pairw43(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default, int len_mul,
                    int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream);
 bool pairw_supported(int C, int KS, int dil);
+bool pair_form_supported(int form, int C, int KS, int dil);  // whether make_pairw has an instance of that form
+int pair_reg_tile(int form, int C, int KS, int dil);         // outputs a workgroup of a register-only instance owns, or 0
 // form: DevPairW::form -- 1 the F(2,3) form (pair_f23_supported), 2 the six-point one (pair_tc6_supported), 0 the F(4,3) one
 // (pairw_supported)
 int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, int form, DevPairW& pw);

@@ -306,7 +306,7 @@ static inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; 
 extern "C" {
 
 const char* dissc_last_error(void) { return g_err; }
-int dissc_abi_version(void) { return 3; }
+int dissc_abi_version(void) { return 4; }
 
 int dissc_device_count(void) {
   int n = 0;
@@ -918,6 +918,19 @@ int dissc_respair1d(const float* x, const float* w1_host, const float* b1_host, 
   free_pairw(pw);
   if (rc) return rc;
   DISSC_HIP_CHECK(e);
+  return DISSC_OK;
+}
+
+// Diagnostics: the form and tile of what mode 3 of dissc_respair1d / dissc_pair_bench builds under the current option
+// defaults.  Host only: no HIP call.
+int dissc_pair_info(int C, int k, int dilation, int* form_out, int* tile_out) {
+  const int form = pair_reg_form(C, k, dilation);
+  if (!pair_form_supported(form, C, k, dilation)) {
+    set_error("dissc_pair_info: no instance for C = %d, k = %d, dilation %d", C, k, dilation);
+    return DISSC_EINVAL;
+  }
+  if (form_out) *form_out = form;
+  if (tile_out) *tile_out = pair_reg_tile(form, C, k, dilation);
   return DISSC_OK;
 }
 

@@ -29,6 +29,9 @@ bool pairw_supported(int C, int KS, int dil) {
   if (C == 64) return KS == 3;
   return false;
 }
+bool pair_form_supported(int form, int C, int KS, int dil) {
+  return form == 2 ? pair_tc6_supported(C, KS, dil) : form == 1 ? pair_f23_supported(C, KS, dil) : pairw_supported(C, KS, dil);
+}
 
 // ---- weights of the register-only kernels ----
 // F(2,3) weight transform at the points 0, 1, -1, inf
@@ -106,7 +109,7 @@ static int pack_pair_reg(const float* w, float** dev, int C, int KS, int form) {
 
 int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, int form, DevPairW& pw) {
   pw.form = form;
-  if (!(form == 2 ? pair_tc6_supported(C, KS, dil) : form == 1 ? pair_f23_supported(C, KS, dil) : pairw_supported(C, KS, dil))) {
+  if (!pair_form_supported(form, C, KS, dil)) {
     set_error("make_pairw: no instance for C = %d, k = %d, dilation %d", C, KS, dil);
     return DISSC_EINVAL;
   }
@@ -145,25 +148,34 @@ static int launch_pair_reg(const PairArgs& a, int B, int Lmax, hipStream_t strea
   return DISSC_OK;
 }
 
+// every register-only instance, as DISSC_CASE(form, C, kernel, Geo, want_max_lds, k, dilation)
+#define DISSC_TC6(K_, D_) DISSC_CASE(2, 32, respair32_tc6_kernel, Tc6Geo, true, K_, D_)
+#define DISSC_F23_32(K_, D_) DISSC_CASE(1, 32, respair32_f23_kernel, F23Geo32, true, K_, D_)
+#define DISSC_F23_16(K_, D_) DISSC_CASE(1, 16, respair16_f23_kernel, F23Geo16, false, K_, D_)
+#define DISSC_F23_64(K_, D_) DISSC_CASE(1, 64, respair64_f23_kernel, F23Geo64, true, K_, D_)
+#define DISSC_PAIR_REG_INSTANCES                                                                          \
+  DISSC_PAIR_TC6_SHAPES(DISSC_TC6) DISSC_PAIR_F23_SHAPES(DISSC_F23_32) DISSC_PAIR_F23_SHAPES(DISSC_F23_16) \
+  DISSC_PAIR_F23_C64_SHAPES(DISSC_F23_64)
+
+// outputs a workgroup of the instance owns (the Geo::WOUT its launch sizes the grid by); 0: no register-only instance
+int pair_reg_tile(int form, int C, int KS, int dil) {
+#define DISSC_CASE(FORM_, C_, KERNEL_, GEO_, MAX_LDS_, K_, D_) \
+  if (form == FORM_ && C == C_ && KS == K_ && dil == D_) return GEO_<K_, D_>::WOUT;
+  DISSC_PAIR_REG_INSTANCES
+#undef DISSC_CASE
+  return 0;
+}
+
 static int launch_pair_f23(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
                            int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream) {
   PairArgs a;
   a.x = x; a.out = out; a.acc = acc; a.w1 = pw.w1; a.w2 = pw.w2; a.b1 = pw.b1; a.b2 = pw.b2;
   a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul; a.ld = ld;
   a.bstride = (long long)pw.C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = opts().kernel_dbg;
-#define DISSC_CASE(FORM_, C_, KERNEL_, GEO_, MAX_LDS_, K_, D_)             \
+#define DISSC_CASE(FORM_, C_, KERNEL_, GEO_, MAX_LDS_, K_, D_)       \
   if (pw.form == FORM_ && pw.C == C_ && pw.KS == K_ && pw.dil == D_) \
     return launch_pair_reg<KERNEL_<K_, D_>, GEO_<K_, D_>>(a, B, Lmax, stream, MAX_LDS_);
-#define DISSC_TC6(K_, D_) DISSC_CASE(2, 32, respair32_tc6_kernel, Tc6Geo, true, K_, D_)
-#define DISSC_F23_32(K_, D_) DISSC_CASE(1, 32, respair32_f23_kernel, F23Geo32, true, K_, D_)
-#define DISSC_F23_16(K_, D_) DISSC_CASE(1, 16, respair16_f23_kernel, F23Geo16, false, K_, D_)
-#define DISSC_F23_64(K_, D_) DISSC_CASE(1, 64, respair64_f23_kernel, F23Geo64, true, K_, D_)
-  DISSC_PAIR_TC6_SHAPES(DISSC_TC6) DISSC_PAIR_F23_SHAPES(DISSC_F23_32) DISSC_PAIR_F23_SHAPES(DISSC_F23_16)
-  DISSC_PAIR_F23_C64_SHAPES(DISSC_F23_64)
-#undef DISSC_F23_64
-#undef DISSC_F23_16
-#undef DISSC_F23_32
-#undef DISSC_TC6
+  DISSC_PAIR_REG_INSTANCES
 #undef DISSC_CASE
   set_error("launch_pair_f23: no instance of form %d for C = %d, k = %d, dilation %d", pw.form, pw.C, pw.KS, pw.dil);
   return DISSC_EINVAL;

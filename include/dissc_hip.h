@@ -253,6 +253,11 @@ int dissc_respair1d(const float* x, const float* w1_host, const float* b1_host, 
                     float* y, float* acc, const int32_t* lengths, int B, int C, int k, int dilation, int ld, int Lmax,
                     float slope, int epi, float mrf_div, int mode, void* stream);
 int dissc_pair_bench(int B, int C, int k, int dilation, int L, int epi, int iters, int mode, float* ms_out);
+/* What mode 3 of the two would build for (C, k, dilation) under the current option defaults: `form_out` 1 = the register-only
+ * F(2,3) pair, 2 = the register-only six-point pair, 0 = the F(4,3) pair kernel (DISSC_EXPERIMENTAL=1 builds); `tile_out` the
+ * outputs one workgroup of that instance owns (0 for form 0).  DISSC_EINVAL where mode 3 has no instance.  Host only: no GPU
+ * is touched. */
+int dissc_pair_info(int C, int k, int dilation, int* form_out, int* tile_out);
 
 /* ------------------------------------------------------------------------- *
  * Length / pitch predictors and infer.py's integer sample logic.

@@ -9,7 +9,8 @@ from fractions import Fraction as Fr
 import numpy as np
 import pytest
 
-from test_tc6_model import _conv_direct, _fma32, _pair
+from test_tc6_model import _conv_direct, _fma32, _rms_errors
+from test_tc6_model import trained_like  # noqa: F401  (its fixture: the trained-like checkpoint and the oracle's conv inputs)
 
 BT = [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]]
 AT = [[1, 1, 1, 0], [0, 1, -1, -1]]
@@ -58,15 +59,6 @@ def test_model_is_exact_on_small_integers():
         assert np.array_equal(_conv_f23(x, w, d), _conv_direct(x, w, d, np.float32)), d
 
 
-def _rms_errors(x, w1, b1, w2, b2, d):
-    ref = _pair(x.astype(np.float64), w1.astype(np.float64), b1.astype(np.float64), w2.astype(np.float64), b2.astype(np.float64), d,
-                lambda v, w, dd: _conv_direct(v, w, dd, np.float64))
-    yf = _pair(x, w1, b1, w2, b2, d, _conv_f23)
-    yd = _pair(x, w1, b1, w2, b2, d, lambda v, w, dd: _conv_direct(v, w, dd, np.float32))
-    assert yf.dtype == np.float32 and yd.dtype == np.float32
-    return float(np.sqrt(np.mean((yf - ref) ** 2))), float(np.sqrt(np.mean((yd - ref) ** 2))), float(np.sqrt(np.mean(ref ** 2)))
-
-
 @pytest.mark.parametrize("d", [1, 3, 5])
 def test_f23_c64_pair_model_on_uniform_data(d):
     """data and weights as tests/test_gpu_pairs_f23.py::_data (uniform, weights scaled 0.9 / sqrt(C k)), L = 2000: the pair's rms
@@ -77,24 +69,9 @@ def test_f23_c64_pair_model_on_uniform_data(d):
     x = (rs.rand(C, L) * 2 - 1).astype(np.float32)
     w1, w2 = [((rs.rand(C, C, k) * 2 - 1) * sc).astype(np.float32) for _ in range(2)]
     b1, b2 = [((rs.rand(C) * 2 - 1) * 0.1).astype(np.float32) for _ in range(2)]
-    ef, ed, _ = _rms_errors(x, w1, b1, w2, b2, d)
+    ef, ed, _ = _rms_errors(x, w1, b1, w2, b2, d, _conv_f23)
     print(f"C={C} k={k} d={d} uniform: F(2,3) rms {ef:.2e}, direct order {ed:.2e}, ratio {ef / ed:.2f}")
     assert ef <= 3.0 * ed
-
-
-@pytest.fixture(scope="module")
-def trained_like():
-    """the trained-like checkpoint and the float64 oracle's inputs of every ResBlock conv on a trained-like utterance"""
-    import torch
-    from oracle import generator_ref as gr
-    import synthdata as synth
-    folded = gr.fold_state_dict(synth.synth_generator_state_dict(seed=0, kind="trained_like"))
-    w64 = gr.to_double(folded)
-    code, f0, spkr, _ = synth.synth_generator_inputs(1, 16, seed=199, kind="trained_like")
-    x = gr.embed_concat(w64, torch.from_numpy(code), torch.from_numpy(f0), torch.from_numpy(spkr))
-    conv_taps = {}
-    gr.generator_forward(w64, synth.VCTK_CONFIG, x, taps={}, conv_taps=conv_taps)
-    return folded, {key[:-2]: v[0].float().numpy() for key, v in conv_taps.items() if key.endswith(".x")}
 
 
 def test_f23_c64_pair_model_on_trained_like_draws(trained_like):
@@ -108,6 +85,6 @@ def test_f23_c64_pair_model_on_trained_like_draws(trained_like):
         w2, b2 = folded[f"{p}.convs2.{m}.weight"].numpy(), folded[f"{p}.convs2.{m}.bias"].numpy()
         x = np.ascontiguousarray(inp[f"{p}.convs1.{m}"])
         assert x.shape[0] == C and x.shape[1] >= 1000 and w1.shape == (C, C, k)
-        ef, ed, sig = _rms_errors(x, w1, b1, w2, b2, d)
+        ef, ed, sig = _rms_errors(x, w1, b1, w2, b2, d, _conv_f23)
         print(f"C={C} k={k} d={d} trained-like: F(2,3) rms {ef:.2e}, direct order {ed:.2e}, ratio {ef / ed:.2f} (signal {sig:.3g})")
         assert ef <= 3.0 * ed, (d, ef, ed)

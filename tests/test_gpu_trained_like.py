@@ -19,7 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import is_experimental_build
+import pair_harness as ph
 from test_gpu_generator import FP32_GUARD_RMS, NORTH_STAR_RMS, _generator_with, _rms, _run_conv
 
 pytestmark = pytest.mark.gpu
@@ -44,22 +44,7 @@ GUARD_FACTOR = 3.0     # fp32 guard: error vs float64 <= max(FP32_GUARD_RMS, thi
 def tl():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    from dissc_amd import _lib
-    from oracle import generator_ref as gr
-    import synthdata as synth
-    sd = synth.synth_generator_state_dict(seed=0, kind="trained_like")
-    folded = gr.fold_state_dict(sd)
-    w64 = gr.to_double(folded)
-    code, f0, spkr, _ = synth.synth_generator_inputs(1, 99, seed=199, kind="trained_like")
-    x = gr.embed_concat(w64, torch.from_numpy(code), torch.from_numpy(f0), torch.from_numpy(spkr))
-    taps, conv_taps = {}, {}
-    gr.generator_forward(w64, synth.VCTK_CONFIG, x, taps=taps, conv_taps=conv_taps)
-    # the pre-activation inputs (the kernels apply the leaky ReLU on load), as the fp32 data a kernel is fed
-    inp = {k[:-2]: v[0].float() for k, v in conv_taps.items() if k.endswith(".x")}
-    inp["conv_pre"] = x[0].float()
-    for i in range(5):
-        inp[f"ups.{i}"] = (taps["conv_pre"] if i == 0 else taps[f"mrf{i - 1}"])[0].float()
-    return dict(lib=_lib.lib, _lib=_lib, gr=gr, synth=synth, sd=sd, folded=folded, inp=inp, experimental=is_experimental_build())
+    return ph.tl_context()  # (one per process, shared with the files that import this fixture)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -280,22 +265,6 @@ def _plan_conv_form(lib, C, k, d):
 # ------------------------------------------------------------------------------------------------------------------------
 # per-layer: the residual pairs of the 32 / 16-channel stages through dissc_respair1d
 # ------------------------------------------------------------------------------------------------------------------------
-def _pair(tl, mode, x, w1, b1, w2, b2, lengths, k, d, epi=1, acc=None):
-    lib = tl["lib"]
-    B, C, ld = x.shape
-    xd = x.to(DEV)
-    for i, n in enumerate(lengths):
-        xd[i, :, n:] = float("nan")  # never read
-    y = torch.full_like(xd, -7.0)
-    ln = torch.as_tensor(lengths, dtype=torch.int32, device=DEV)
-    a = None if acc is None else acc.to(DEV).clone()
-    tl["_lib"].check(lib.dissc_respair1d(xd.data_ptr(), w1.contiguous().data_ptr(), b1.contiguous().data_ptr(),
-                                         w2.contiguous().data_ptr(), b2.contiguous().data_ptr(), y.data_ptr(),
-                                         None if a is None else a.data_ptr(), ln.data_ptr(), B, C, k, d, ld, int(max(lengths)),
-                                         ctypes.c_float(SLOPE), epi, ctypes.c_float(3.0), mode, None), f"dissc_respair1d {mode}")
-    return (y if epi == 1 else a).cpu()
-
-
 def _ref_pair(x, w1, b1, w2, b2, k, d, dtype):
     x = x.to(dtype)[None]
     t = F.conv1d(F.leaky_relu(x, SLOPE), w1.to(dtype), b1.to(dtype), padding=(k - 1) * d // 2, dilation=d)
@@ -304,60 +273,15 @@ def _ref_pair(x, w1, b1, w2, b2, k, d, dtype):
 
 @pytest.mark.parametrize("stage,j", [(i, j) for i in (3, 4) for j in range(3)])
 def test_trained_like_residual_pairs(tl, stage, j):
-    """every residual pair of the 32 / 16-channel stages: two direct launches (mode 0), the fused direct pair (mode 1) and,
-    for k = 11, the register-only F(2,3) pair (mode 3); the MRF epilogues (2: store, 3: accumulate, 4: accumulate / 3) on the
-    last pair of the chain"""
-    folded = tl["folded"]
+    """every residual pair of the 32 / 16-channel stages: two direct launches (mode 0), the fused direct pair (mode 1) and every
+    register-only form mode 3 can build for the shape (dissc_pair_info: the shipped plan's, and F(2,3) under "pair_tc6" = 0 where
+    the plan's is the six-point one); the plan's form is the first of those, the fused direct pair where there is none"""
     C, k = STAGES[stage], KS[j]
     bad = []
-    for m in range(3):
-        d = DILS[m]
-        p = f"resblocks.{3 * stage + j}"
-        w1, b1 = folded[f"{p}.convs1.{m}.weight"], folded[f"{p}.convs1.{m}.bias"]
-        w2, b2 = folded[f"{p}.convs2.{m}.weight"], folded[f"{p}.convs2.{m}.bias"]
-        forms = [("direct", 0, 4), ("fused", 1, 4)] + ([("F(2,3)", 3, 2)] if k == 11 else [])
-        tap = tl["inp"][f"{p}.convs1.{m}"]
-        adv = _adversarial_rows(tap, [2 * d, 4 * d, 6 * d], seed=1000 * stage + 100 * j + m)
-        rows = [(tap, None)] + adv
-        x, lens = _batch(rows)
-        pad = (k - 1) * d // 2 + (k - 1) // 2
-        unit = F.leaky_relu(x, SLOPE).abs().amax((1, 2))
-        s1 = float(w1.double().abs().sum((1, 2)).max())
-        wsum = w2.double().abs().sum((1, 2)) * s1  # the gain of the pair's path from a loud input, per output channel
-        refs = [_ref_pair(x[i, :, :n], w1, b1, w2, b2, k, d, torch.float64) for i, n in enumerate(lens)]
-        cpu = [_ref_pair(x[i, :, :n], w1, b1, w2, b2, k, d, torch.float32) for i, n in enumerate(lens)]
-        res, outs = {}, {}
-        for form, mode, _tile in [("cpu", -1, 0)] + forms:
-            acc_a, acc_b = _Acc(C), _Acc(C)
-            if form == "cpu":
-                y = cpu
-            else:
-                yb = _pair(tl, mode, x, w1, b1, w2, b2, lens, k, d)
-                outs[form] = yb
-                for i, n in enumerate(lens):
-                    assert (yb[i, :, n:] == -7.0).all(), (p, m, form, i, "wrote beyond the utterance")
-                    assert torch.isfinite(yb[i, :, :n]).all(), (p, m, form, i)
-                y = [yb[i, :, :n] for i, n in enumerate(lens)]
-                if m == 2:  # the MRF epilogues of the chain's last pair: exactly the pair's output stored / accumulated
-                    acc0 = torch.rand(x.shape, generator=torch.Generator().manual_seed(m))
-                    for epi in (2, 3, 4):
-                        a = _pair(tl, mode, x, w1, b1, w2, b2, lens, k, d, epi=epi, acc=acc0)
-                        for i, n in enumerate(lens):
-                            want = yb[i, :, :n] if epi == 2 else acc0[i, :, :n] + yb[i, :, :n]
-                            if epi == 4:
-                                want = want / 3.0
-                            assert torch.equal(a[i, :, :n], want), (p, form, epi, i)
-                            assert torch.equal(a[i, :, n:], acc0[i, :, n:]), (p, form, epi, i)
-            for i, (r, loud) in enumerate(rows):
-                if i == 0:
-                    acc_a.add(y[i], refs[i])
-                else:
-                    acc_b.add(y[i], refs[i], loud, pad, float(unit[i]) * wsum * U)
-            res[form] = (acc_a.metrics(), acc_b.metrics())
-        # the default plan: F(2,3) for the k = 11 pairs ("pair_f23" = 3), the fused direct pair otherwise
-        bad += _check(f"{p}.pair{m}", [f[0] for f in forms], res, "F(2,3)" if k == 11 else "fused")
-        if k == 11:
-            assert not torch.equal(outs["F(2,3)"], outs["direct"])
+    for m, d in enumerate(DILS):
+        reg = ph.register_only_forms(tl["_lib"], C, k, d)
+        bad += ph.trained_like_pair_layer(tl, C, k, d, f"resblocks.{3 * stage + j}", m, [ph.TL_DIRECT, ph.TL_FUSED] + reg,
+                                          reg[0].name if reg else "fused", [2 * d, 4 * d, 6 * d], 1000 * stage + 100 * j + m)
     assert not bad, bad
 
 

@@ -5,6 +5,7 @@ sub-filters and transform steps) against float64, next to a direct-order fp32 mo
 
 The host packing (pack_pair_reg: U = G w in double, rounded once) uploads to the device and has no host-only entry, so it is
 covered by the GPU tests (tests/test_gpu_pairs_tc6.py); the model below forms U the same way."""
+import functools
 from fractions import Fraction as Fr
 
 import numpy as np
@@ -108,10 +109,11 @@ def _pair(x, w1, b1, w2, b2, d, conv):
     return x + (conv(t, w2, 1) + b2[:, None])
 
 
-def _rms_errors(x, w1, b1, w2, b2, d):
+def _rms_errors(x, w1, b1, w2, b2, d, conv):
+    """rms error against float64 of the pair with `conv` as its conv model and with the direct-order fp32 one; the signal's rms"""
     ref = _pair(x.astype(np.float64), w1.astype(np.float64), b1.astype(np.float64), w2.astype(np.float64), b2.astype(np.float64), d,
                 lambda v, w, dd: _conv_direct(v, w, dd, np.float64))
-    y6 = _pair(x, w1, b1, w2, b2, d, _conv_tc6)
+    y6 = _pair(x, w1, b1, w2, b2, d, conv)
     yd = _pair(x, w1, b1, w2, b2, d, lambda v, w, dd: _conv_direct(v, w, dd, np.float32))
     assert y6.dtype == np.float32 and yd.dtype == np.float32
     return float(np.sqrt(np.mean((y6 - ref) ** 2))), float(np.sqrt(np.mean((yd - ref) ** 2))), float(np.sqrt(np.mean(ref ** 2)))
@@ -128,15 +130,13 @@ def test_six_point_pair_model_on_uniform_data(C, k, d):
     x = (rs.rand(C, L) * 2 - 1).astype(np.float32)
     w1, w2 = [((rs.rand(C, C, k) * 2 - 1) * sc).astype(np.float32) for _ in range(2)]
     b1, b2 = [((rs.rand(C) * 2 - 1) * 0.1).astype(np.float32) for _ in range(2)]
-    e6, ed, _ = _rms_errors(x, w1, b1, w2, b2, d)
+    e6, ed, _ = _rms_errors(x, w1, b1, w2, b2, d, _conv_tc6)
     print(f"C={C} k={k} d={d} uniform: six-point rms {e6:.2e}, direct order {ed:.2e}, ratio {e6 / ed:.2f}")
     assert e6 <= 3.0 * ed
 
 
-@pytest.fixture(scope="module")
-def trained_like():
-    """the trained-like checkpoint (per-channel gains over decades, outlier channels, heavy tails) and the float64 oracle's
-    inputs of every ResBlock conv on a trained-like utterance"""
+@functools.lru_cache(maxsize=None)
+def _trained_like():
     import torch
     from oracle import generator_ref as gr
     import synthdata as synth
@@ -147,6 +147,13 @@ def trained_like():
     conv_taps = {}
     gr.generator_forward(w64, synth.VCTK_CONFIG, x, taps={}, conv_taps=conv_taps)
     return folded, {key[:-2]: v[0].float().numpy() for key, v in conv_taps.items() if key.endswith(".x")}
+
+
+@pytest.fixture(scope="module")
+def trained_like():
+    """the trained-like checkpoint (per-channel gains over decades, outlier channels, heavy tails) and the float64 oracle's
+    inputs of every ResBlock conv on a trained-like utterance: built once per process, read-only"""
+    return _trained_like()
 
 
 @pytest.mark.parametrize("stage,C", [(3, 32), (4, 16)])
@@ -162,6 +169,6 @@ def test_six_point_pair_model_on_trained_like_draws(trained_like, stage, C, k):
         w2, b2 = folded[f"{p}.convs2.{m}.weight"].numpy(), folded[f"{p}.convs2.{m}.bias"].numpy()
         x = np.ascontiguousarray(inp[f"{p}.convs1.{m}"][:, 300:2300])
         assert x.shape == (C, 2000) and w1.shape == (C, C, k)
-        e6, ed, sig = _rms_errors(x, w1, b1, w2, b2, d)
+        e6, ed, sig = _rms_errors(x, w1, b1, w2, b2, d, _conv_tc6)
         print(f"C={C} k={k} d={d} trained-like: six-point rms {e6:.2e}, direct order {ed:.2e}, ratio {e6 / ed:.2f} (signal {sig:.3g})")
         assert e6 <= 3.0 * ed, (d, e6, ed)
