@@ -47,7 +47,7 @@ typedef struct {
 } DisscTensor;
 
 const char* dissc_last_error(void);
-/* ABI version of this header: bumped when a signature changes. */
+/* ABI version of this header: bumped when a signature changes or a section is added (5: dissc_convgrad_*). */
 int dissc_abi_version(void);
 /* Number of HIP devices visible / name of device `dev` (for diagnostics). */
 int dissc_device_count(void);
@@ -636,6 +636,47 @@ int dissc_mel_backward(dissc_mel_t h, const float* wav, int ld, const int32_t* n
 int dissc_mel_l1_grad(dissc_mel_t h, const float* a, int lda, const float* b, int ldb, const int32_t* n_samples_dev, int B,
                       const double* scale_dev, double* sum_out, float* grad_b, int ldg, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * A differentiable, ragged, stride-1 "same" Conv1d layer (csrc/conv_grad.hip): the op 92 of the generator's 97 conv layers
+ * are (conv_pre, the ResBlock convs, conv_post; reference sr/models.py:34-41, :98-114), for training the vocoder.
+ *   y[b,:,t] = bias + sum_j w[:,:,j] . lrelu(x, in_slope)[b,:,t + j d - pad]  (+ add[b,:,t]),  pad = (k - 1) d / 2,
+ *   with dissc_conv1d's conventions: x f32 [B][Cin][ldx], y / add / gy f32 [B][Cout][ldo], 16-byte aligned, ldx and ldo
+ *   multiples of 4 and >= Lmax; lengths i32 [B] on the device or NULL (= Lmax); positions >= lengths[b] are read as zero
+ *   and never written by the forward.
+ * dissc_convgrad_create: HOST ONLY (no HIP call; the device buffers come with the first dissc_convgrad_set_weights).  k odd,
+ *   k <= 11, (k - 1) dilation <= 60, 1 <= Cin, Cout <= 65535; anything else is DISSC_EINVAL with a message.  The handle
+ *   snapshots the tuning options, as every handle does.
+ * dissc_convgrad_set_weights: w_dev f32 [Cout][Cin][k] and bias_dev f32 [Cout] (NULL = no bias) are DEVICE pointers; packs the
+ *   weights for the forward and, transposed and tap-flipped, for the data gradient, on the device.  The handle keeps only
+ *   these packed copies: call it again whenever the weights changed, and before a backward if another layer that shares
+ *   the handle ran in between.
+ * dissc_convgrad_forward: the forward on the direct conv kernels, the bits of dissc_conv1d for the same weights; add may be
+ *   NULL.
+ * dissc_convgrad_partials: HOST ONLY.  The weight gradient's reduction over (utterance, time) is cut into chunks of
+ *   DISSC_CONVGRAD_CHUNK positions; the (utterance, chunk) pairs, utterance-major with ceil(Lmax / chunk) chunks per
+ *   utterance, are dealt in consecutive runs of *pairs_per_partial to *P partials, summed afterwards in a fixed order.
+ *   Both are functions of (B, Lmax, Cin, Cout, k) only, never of lengths.
+ * dissc_convgrad_workspace_bytes: bytes of the backward's workspace (the partials; at most 64 MB for every generator layer
+ *   at B = 32 x 8 960 samples).
+ * dissc_convgrad_backward: x and in_slope as in the forward, gy the gradient of y (read as zero beyond lengths).
+ *   gx f32 [B][Cin][ldx] = (x > 0 ? 1 : in_slope) * conv^T(gy) (torch's rule at x = 0), zero from lengths[b] to ldx;
+ *   gw f32 [Cout][Cin][k]; gb f32 [Cout].  Each may be NULL ("not needed"): its kernels are skipped.  The gradient of add is
+ *   gy itself.  No atomics, fixed summation orders: bit-reproducible from call to call, and an utterance's gx does not
+ *   depend on the batch it is in.  workspace: 16-byte aligned device memory, needed for gw / gb only.
+ * ------------------------------------------------------------------------- */
+#define DISSC_CONVGRAD_CHUNK 64
+typedef struct dissc_convgrad* dissc_convgrad_t;
+int dissc_convgrad_create(int Cin, int Cout, int k, int dilation, dissc_convgrad_t* out);
+void dissc_convgrad_destroy(dissc_convgrad_t h);
+int dissc_convgrad_set_weights(dissc_convgrad_t h, const float* w_dev, const float* bias_dev, void* stream);
+int dissc_convgrad_forward(dissc_convgrad_t h, const float* x, const float* add, float* y, const int32_t* lengths, int B,
+                           int ldx, int ldo, int Lmax, float in_slope, void* stream);
+int dissc_convgrad_partials(dissc_convgrad_t h, int B, int Lmax, int* P, int* pairs_per_partial);
+size_t dissc_convgrad_workspace_bytes(dissc_convgrad_t h, int B, int Lmax);
+int dissc_convgrad_backward(dissc_convgrad_t h, const float* x, const float* gy, const int32_t* lengths, int B, int ldx,
+                            int ldo, int Lmax, float in_slope, float* gx, float* gw, float* gb, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

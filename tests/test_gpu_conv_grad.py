@@ -1,0 +1,231 @@
+"""dissc_amd.nn on the GPU: the device-side packings bit for bit against dissc_conv1d on host weights, every gradient of
+the layer against torch in float64 under the bars of tests/train_stage_cases.py (ragged lengths around the padding, the
+chunk and a partial boundary; the training shapes at B = 32), and resblock1 against the float64 block evaluated with
+the engine's own branch decisions.  Measured ratios: profiles/conv_grad.md."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import conv_grad_ref as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def nn():
+    import __graft_entry__ as ge
+    ge.build()
+    from dissc_amd import nn
+    return nn
+
+
+def _case(cin, cout, k, B, ld, seed, bias=True):
+    rs = np.random.RandomState(seed)
+    x = torch.from_numpy(rs.randn(B, cin, ld).astype(np.float32))
+    x[torch.from_numpy(rs.rand(B, cin, ld) < 0.02)] = 0.0  # exact zeros: the x = 0 branch is the slope
+    w = torch.from_numpy((rs.uniform(-1, 1, (cout, cin, k)) / np.sqrt(cin * k)).astype(np.float32))
+    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)) if bias else None
+    gy = torch.from_numpy(rs.randn(B, cout, ld).astype(np.float32))
+    return x, w, b, gy
+
+
+def _run(nn, x, w, b, gy, lengths, d, slope, add=None, need=(True, True, True)):
+    """one forward + backward of nn.conv1d on the device; returns y, gx, gw, gb (and the gradient of add)"""
+    xd = x.to(DEV).requires_grad_(need[0])
+    wd = w.to(DEV).requires_grad_(need[1])
+    bd = None if b is None else b.to(DEV).requires_grad_(need[2])
+    ad = None if add is None else add.to(DEV).requires_grad_(True)
+    ln = None if lengths is None else torch.tensor(lengths, dtype=torch.int32, device=DEV)
+    y = nn.conv1d(xd, wd, bd, lengths=ln, dilation=d, in_slope=slope, add=ad)
+    y.backward(gy.to(DEV))
+    torch.cuda.synchronize()
+    out = [y.detach().cpu()] + [None if t is None or t.grad is None else t.grad.cpu() for t in (xd, wd, bd)]
+    return out + [None if ad is None else ad.grad.cpu()]
+
+
+def _conv1d_host(x, w, b, lengths, d, slope):
+    """dissc_conv1d: host weights packed on the host"""
+    from dissc_amd import _lib
+    B, cin, ld = x.shape
+    cout, _, k = w.shape
+    xd, y = x.to(DEV), torch.zeros(B, cout, ld, device=DEV)
+    wc = w.contiguous()
+    ln = torch.tensor(lengths, dtype=torch.int32, device=DEV)
+    _lib.check(_lib.lib.dissc_conv1d(xd.data_ptr(), wc.data_ptr(), None if b is None else b.data_ptr(), y.data_ptr(), ln.data_ptr(),
+                                     B, cin, cout, k, d, ld, ld, ld, ctypes.c_float(slope), None), "dissc_conv1d")
+    torch.cuda.synchronize()
+    return y.cpu()
+
+
+@pytest.mark.parametrize("cin,cout,k,d,slope", [(16, 16, 11, 5, 0.1), (32, 32, 7, 3, 0.1), (64, 64, 3, 1, 0.1), (257, 512, 7, 1, 1.0),
+                                                (16, 1, 7, 1, 0.01)])
+def test_device_packing_bit_for_bit(nn, cin, cout, k, d, slope):
+    B, ld, lengths = 3, 100, [100, 37, 3]
+    x, w, b, gy = _case(cin, cout, k, B, ld, seed=cin + k)
+    y, gx, _, _, _ = _run(nn, x, w, b, gy, lengths, d, slope)
+    assert torch.equal(y, _conv1d_host(x, w, b, lengths, d, slope))
+    wt = w.transpose(0, 1).flip(2).contiguous()  # [Cin][Cout][k], taps flipped
+    plain = _conv1d_host(gy, wt, None, lengths, d, 1.0)  # the data gradient before the mask
+    assert torch.equal(gx, plain * torch.where(x > 0, torch.tensor(1.0), torch.tensor(np.float32(slope))))
+    assert plain.abs().sum() > 0
+
+
+def _lengths_for(nn, cin, cout, k, d):
+    """1, 2, pad, pad + 1, chunk - 1, chunk, chunk + 1, 2 chunk + 1, and, where the plan has one inside an utterance, a length
+    on either side of a partial boundary (placed in the utterance the boundary falls in)"""
+    T, pad = nn.WGRAD_CHUNK, (k - 1) * d // 2
+    lengths = [1, 2, pad, pad + 1, T - 1, T, T + 1, 2 * T + 1, T, 2 * T + 1]
+    B, ld = len(lengths), (2 * T + 1 + 3) // 4 * 4
+    P, pairs = nn.wgrad_partials(B, ld, cin, cout, k)
+    nch = -(-ld // T)
+    inside = [divmod(p * pairs, nch) for p in range(1, P) if (p * pairs) % nch]
+    if inside:
+        b, c = inside[len(inside) // 2]
+        lengths[8], lengths[9] = c * T, c * T + 1
+        lengths[b], lengths[9] = lengths[9], lengths[b]  # this utterance's chunk c belongs to the next partial
+    return lengths, ld, (P, pairs)
+
+
+LAYERS = [(16, 16, 3, 1), (16, 16, 11, 5), (32, 32, 7, 3), (64, 64, 11, 5), (128, 128, 3, 3), (256, 256, 7, 1), (257, 512, 7, 1),
+          (16, 1, 7, 1)]
+
+
+@pytest.mark.parametrize("cin,cout,k,d", LAYERS)
+def test_layer_gradients_against_float64(nn, cin, cout, k, d):
+    slope = 0.1
+    lengths, ld, plan = _lengths_for(nn, cin, cout, k, d)
+    B = len(lengths)
+    x, w, b, gy = _case(cin, cout, k, B, ld, seed=7 * cin + k + d)
+    add = torch.from_numpy(np.random.RandomState(1).randn(B, cout, ld).astype(np.float32))
+    print(f"\nlayer {cin} -> {cout} k {k} d {d}: lengths {lengths}, ld {ld}, (P, pairs) {plan}")
+    y, gx, gw, gb, gadd = _run(nn, x, w, b, gy, lengths, d, slope, add=add)
+    r64 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float64)
+    r32 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float32)
+    valid = torch.zeros(B, 1, ld)
+    for i, n in enumerate(lengths):
+        valid[i, :, :n] = 1
+    bad = R.check("batch y", "act", y, r64[0] + add.double() * valid.double(), r32[0] + add * valid, *k_direct(cin * k))
+    bad += R.check("batch gx", "act", gx, r64[1], r32[1], *k_direct(cout * k))
+    bad += R.check("batch gw", "weight", gw, r64[2], r32[2])
+    bad += R.check("batch gb", "vec", gb, r64[3], r32[3])
+    # the gradient of add is gy itself; nothing is written or propagated beyond lengths
+    assert torch.equal(gadd, gy)
+    assert not gx[(valid == 0).expand_as(gx)].any() and not y[(valid == 0).expand_as(y)].any()
+    # bit-reproducible
+    again = _run(nn, x, w, b, gy, lengths, d, slope, add=add)
+    assert torch.equal(again[2], gw) and torch.equal(again[3], gb) and torch.equal(again[1], gx)
+    # poison beyond lengths changes nothing
+    xp, gyp = x.clone(), gy.clone()
+    xp[(valid == 0).expand_as(x)] = 1e30
+    gyp[(valid == 0).expand_as(gy)] = 1e30
+    yq, gxq, gwq, gbq, _ = _run(nn, xp, w, b, gyp, lengths, d, slope, add=add)
+    assert torch.equal(yq, y) and torch.equal(gxq, gx) and torch.equal(gwq, gw) and torch.equal(gbq, gb)
+    # needs_input_grad false for x or for weight: the others keep their bits
+    _, gx0, gw0, gb0, _ = _run(nn, x, w, b, gy, lengths, d, slope, add=add, need=(False, True, True))
+    assert gx0 is None and torch.equal(gw0, gw) and torch.equal(gb0, gb)
+    _, gx1, gw1, gb1, _ = _run(nn, x, w, b, gy, lengths, d, slope, add=add, need=(True, False, True))
+    assert gw1 is None and torch.equal(gx1, gx) and torch.equal(gb1, gb)
+    _, gx2, gw2, gb2, _ = _run(nn, x, w, b, gy, lengths, d, slope, add=add, need=(True, True, False))
+    assert gb2 is None and torch.equal(gx2, gx) and torch.equal(gw2, gw)
+    # every utterance alone: the same gx bits as in the batch, its own gradients inside the bars
+    worst = {}
+    for i, n in enumerate(lengths):
+        if n <= 0:
+            continue
+        sl = slice(i, i + 1)
+        yi, gxi, gwi, gbi, _ = _run(nn, x[sl], w, b, gy[sl], [n], d, slope)
+        assert torch.equal(gxi, gx[sl]), (i, n)
+        a64 = R.layer_ref(x[sl], w, b, gy[sl], [n], d, slope, torch.float64)
+        a32 = R.layer_ref(x[sl], w, b, gy[sl], [n], d, slope, torch.float32)
+        for name, kind, t, j in (("gw", "weight", gwi, 2), ("gb", "vec", gbi, 3)):
+            m = R.compare(kind, t, a64[j], a32[j])
+            bad += R.check(f"alone len {n} {name}", kind, t, a64[j], a32[j], verbose=False)
+            for what in ("ratio", "ch_ratio"):
+                worst[(name, what)] = max(worst.get((name, what), 0.0), m[what])
+    print("CG alone, worst over the lengths:", {f"{a}/{b}": round(v, 3) for (a, b), v in worst.items()})
+    assert not bad, bad
+
+
+# The one exception to K = 4 (tests/train_stage_cases.py's rule): the forward and the data gradient are the direct conv
+# kernels (conv_mfma32_kernel / conv_mfma_kernel), where every output is ONE fp32 chain of n = Cin k (forward) or Cout k
+# (data gradient) products in a matrix-core accumulator and torch sums in SIMD-wide blocks -- the exception that file
+# records for conv_fwd.  K = 2 x the measured worst ratio, rounded up, never above min(32, max(4, sqrt(n))); measured on
+# an MI355X over every case of this file (profiles/conv_grad.md).  Chains below 1 024 products, the weight and bias
+# gradients and the whole of resblock1 stay at 4.
+# Measured worst ratios (whole / worst channel) and the K they give:
+#   n = 3 584 (data gradient of 257 -> 512, k = 7): 4.55 / 4.77 (ragged batch), 4.14 / 4.31 (B = 32)  -> 10 / 10 (cap 32)
+#   n = 2 816 (256 -> 256, k = 11, B = 32):          forward 3.11 / 4.70, data gradient 3.78 / 3.81  ->  4 / 10 (cap 32)
+#   n = 1 799 (forward of 257 -> 512, k = 7):        2.40 / 3.54 (ragged batch), 2.03 / 4.06 (B = 32) ->  4 / 9  (cap 32)
+K_DIRECT = {3584: (10.0, 10.0), 2816: (4.0, 10.0), 1799: (4.0, 9.0)}  # n -> (whole, worst channel)
+
+
+def k_direct(n):
+    kw, kc = K_DIRECT.get(n, (R.K_WHOLE, R.K_CH))
+    assert max(kw, kc) <= R.k_cap(n)
+    return kw, kc
+
+
+TRAIN = [(16, 16, 11, 5, 8960), (256, 256, 11, 5, 140), (257, 512, 7, 1, 28)]
+
+
+@pytest.mark.parametrize("cin,cout,k,d,L", TRAIN)
+def test_training_shapes(nn, cin, cout, k, d, L):
+    """B = 32 at the generator's own lengths (28 frames): the 286 720-long reduction of the narrowest stage, the widest
+    ResBlock layer, conv_pre"""
+    B, slope = 32, 0.1
+    lengths = [L] * B
+    for i, n in zip((1, 5, 17, 31), (L // 2 + 1, 1, L - 1, max(1, L // 3))):
+        lengths[i] = n
+    x, w, b, gy = _case(cin, cout, k, B, L, seed=L + k)
+    print(f"\ntraining shape {cin} -> {cout} k {k} d {d} L {L}: plan {nn.wgrad_partials(B, L, cin, cout, k)}")
+    y, gx, gw, gb, _ = _run(nn, x, w, b, gy, lengths, d, slope)
+    r64 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float64)
+    r32 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float32)
+    bad = R.check("train y", "act", y, r64[0], r32[0], *k_direct(cin * k))
+    bad += R.check("train gx", "act", gx, r64[1], r32[1], *k_direct(cout * k))
+    bad += R.check("train gw", "weight", gw, r64[2], r32[2])
+    bad += R.check("train gb", "vec", gb, r64[3], r32[3])
+    assert not bad, bad
+    again = _run(nn, x, w, b, gy, lengths, d, slope)
+    assert torch.equal(again[2], gw) and torch.equal(again[3], gb)
+
+
+@pytest.mark.parametrize("C,k", [(32, 7), (16, 11)])
+def test_resblock1_against_float64_with_the_engines_masks(nn, C, k):
+    lengths, ld, dil = [1, 5, 63, 64, 65, 131], 132, (1, 3, 5)
+    B = len(lengths)
+    rs = np.random.RandomState(C + k)
+    w = {}
+    for m in range(3):
+        for c in ("convs1", "convs2"):
+            w[f"{c}.{m}.weight"] = torch.from_numpy((rs.uniform(-1, 1, (C, C, k)) / np.sqrt(C * k)).astype(np.float32))
+            w[f"{c}.{m}.bias"] = torch.from_numpy((rs.uniform(-1, 1, C) / np.sqrt(C * k)).astype(np.float32))
+    x = torch.from_numpy(rs.randn(B, C, ld).astype(np.float32))
+    valid = torch.zeros(B, 1, ld, dtype=torch.bool)
+    for i, n in enumerate(lengths):
+        valid[i, :, :n] = True
+    # the cotangent of an output that is never written: zero (the residual hands it through unmasked, as the gradient of add)
+    gy = torch.from_numpy(rs.randn(B, C, ld).astype(np.float32)) * valid
+    wd = {n: t.to(DEV).requires_grad_(True) for n, t in w.items()}
+    xd = x.to(DEV).requires_grad_(True)
+    taps = []
+    y = nn.resblock1(xd, wd, k, dil, lengths=torch.tensor(lengths, dtype=torch.int32, device=DEV), taps=taps)
+    y.backward(gy.to(DEV))
+    torch.cuda.synchronize()
+    assert len(taps) == 6
+    masks = [t.detach().cpu() > 0 for t in taps]
+    own = []
+    y64, gx64, g64 = R.resblock1_ref(w, x, k, dil, torch.float64, masks=masks, lengths=lengths, gy=gy)
+    y32, gx32, g32 = R.resblock1_ref(w, x, k, dil, torch.float32, masks=masks, lengths=lengths, gy=gy)
+    R.resblock1_ref(w, x, k, dil, torch.float64, lengths=lengths, taps=own)
+    differ = sum(int((((t > 0) != m) & valid).sum()) for t, m in zip(own, masks))
+    print(f"\nresblock1 C {C} k {k}: mask positions where float64's own sign differs: {differ} of {6 * int(valid.sum()) * C}")
+    bad = R.check("block y", "act", y.detach(), y64, y32, *k_direct(C * k))
+    bad += R.check("block gx", "act", xd.grad, gx64, gx32, *k_direct(C * k))
+    for n in sorted(w):
+        bad += R.check("block grad " + n, "weight" if n.endswith("weight") else "vec", wd[n].grad, g64[n], g32[n])
+    assert not bad, bad
+    assert not xd.grad.cpu()[(~valid).expand(B, C, ld)].any()

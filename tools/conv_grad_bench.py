@@ -1,0 +1,150 @@
+"""Time of the differentiable Conv1d layer (dissc_amd.nn, csrc/conv_grad.hip) on every distinct stride-1 layer shape of the
+generator at the trainer's batch, 32 segments of 28 frames (8 960 samples), against torch-ROCm's own conv1d autograd on
+the same tensors in the same process:
+
+    python tools/conv_grad_bench.py [--batch 32] [--frames 28] [--blocks 5] [--iters 10] [--only CIN,COUT,K] [--markdown]
+
+Per shape: ms of the forward, the data gradient (conv^T + the leaky-ReLU mask) and the weight + bias gradient (partials +
+their reduction), each through the C ABI alone, and torch's forward (leaky_relu + conv1d), and its data / weight + bias
+gradients alone (aten.convolution_backward with one output mask each -- what conv1d's autograd node runs; torch's data
+gradient leaves the mask to the leaky ReLU's own node, so its figure is a little short of ours).  Medians of alternating
+blocks (ours, torch, ours, ...), each block `iters` calls between two device events.  TFLOP/s are of the EXECUTED matrix
+work: padded rows / channel chunks for the direct convs, padded 32 x 32 tiles x tap groups for the weight gradient.  One
+JSON line per shape; --markdown adds the table of profiles/conv_grad.md.
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def rup(x, m):
+    return (x + m - 1) // m * m
+
+
+def executed_flops(cin, cout, k, positions):
+    """(forward, data gradient, weight gradient) as the kernels execute them"""
+    def direct(m, c):
+        return 2.0 * rup(m, 32 if m >= 32 else 16) * rup(c, 16) * k * positions
+    cib = 32
+    while cib > 1 and cib // 2 >= cin:
+        cib //= 2
+    ng = -(-k // (32 // cib))
+    return direct(cout, cin), direct(cin, cout), 2.0 * rup(cout, 32) * 32 * -(-cin // 32) * ng * positions
+
+
+def bench_shape(a, cin, cout, k, d, L):
+    from dissc_amd import nn
+    from dissc_amd._lib import check, current_stream_ptr, lib
+    F = torch.nn.functional
+    dev = torch.device("cuda:0")
+    B, slope = a.batch, 0.1
+    rs = np.random.RandomState(0)
+    ld = rup(L, 4)
+    x = torch.from_numpy(rs.standard_normal((B, cin, ld)).astype(np.float32)).to(dev)
+    gy = torch.from_numpy(rs.standard_normal((B, cout, ld)).astype(np.float32)).to(dev)
+    w = torch.from_numpy((rs.uniform(-1, 1, (cout, cin, k)) / np.sqrt(cin * k)).astype(np.float32)).to(dev)
+    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)).to(dev)
+    lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
+    y, gx, gw, gb = torch.zeros_like(gy), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
+    h = nn._handle(cin, cout, k, d, dev)
+    st = current_stream_ptr(dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    nws = int(lib.dissc_convgrad_workspace_bytes(h, B, ld))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    check(lib.dissc_convgrad_set_weights(h, p(w), p(b), st), "set_weights")
+    pad = (k - 1) * d // 2
+
+    def ours_bwd(gx_, gw_, gb_):
+        check(lib.dissc_convgrad_backward(h, p(x), p(gy), p(lengths), B, ld, ld, ld, slope, gx_, gw_, gb_, p(ws), nws, st), "backward")
+
+    xa = F.leaky_relu(x, slope)
+    conv_bwd = torch.ops.aten.convolution_backward
+
+    def torch_bwd(mask):
+        return conv_bwd(gy, xa, w, [cout], [1], [pad], [d], False, [0], 1, mask)
+
+    cases = {
+        "fwd": lambda: check(lib.dissc_convgrad_forward(h, p(x), None, p(y), p(lengths), B, ld, ld, ld, slope, st), "forward"),
+        "torch_fwd": lambda: F.conv1d(F.leaky_relu(x, slope), w, b, padding=pad, dilation=d),
+        "dgrad": lambda: ours_bwd(p(gx), None, None),
+        "torch_dgrad": lambda: torch_bwd([True, False, False]),
+        "wgrad": lambda: ours_bwd(None, p(gw), p(gb)),
+        "torch_wgrad": lambda: torch_bwd([False, True, True]),
+        "repack": lambda: check(lib.dissc_convgrad_set_weights(h, p(w), p(b), st), "set_weights"),
+    }
+    # agreement first (fp32 both sides)
+    cases["fwd"](), cases["dgrad"](), cases["wgrad"]()
+    tg = torch_bwd([True, True, True])
+    rel = lambda u, v: float((u - v).norm() / v.norm())
+    agree = {"y": rel(y, cases["torch_fwd"]()), "gx": rel(gx, tg[0] * torch.where(x > 0, 1.0, slope)), "gw": rel(gw, tg[1]),
+             "gb": rel(gb, tg[2])}
+    for fn in cases.values():
+        timed(fn, 2)
+    times = {n: [] for n in cases}
+    for _ in range(a.blocks):
+        for n, fn in cases.items():  # alternating
+            times[n].append(timed(fn, a.iters))
+    P, pairs = nn.wgrad_partials(B, ld, cin, cout, k)
+    out = {"cin": cin, "cout": cout, "k": k, "dilation": d, "L": L, "batch": B, "partials": P, "pairs_per_partial": pairs,
+           "workspace_mb": round(nws / 2**20, 2), "rel_diff_to_torch": {n: float(f"{v:.2e}") for n, v in agree.items()}}
+    for n, v in times.items():
+        out[n + "_ms"] = round(float(np.median(v)), 4)
+        out[n + "_ms_spread"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
+    for n, fl in zip(("fwd", "dgrad", "wgrad"), executed_flops(cin, cout, k, B * L)):
+        out[n + "_tflops"] = round(fl / (out[n + "_ms"] * 1e-3) / 1e12, 2)
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--frames", type=int, default=28)
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--only", default=None, help="CIN,COUT,K: that shape only")
+    ap.add_argument("--markdown", action="store_true")
+    a = ap.parse_args(argv)
+    import conv_grad_ref as R
+    seen, rows = set(), []
+    for cin, cout, k, d, L in R.generator_layer_shapes(a.frames):
+        if (cin, cout, k) in seen or d not in (1, 3) or (cin == cout and d != 3):
+            continue  # one dilation per shape (3 for the ResBlock convs): it moves no work
+        if a.only and [cin, cout, k] != [int(v) for v in a.only.split(",")]:
+            continue
+        seen.add((cin, cout, k))
+        rows.append(bench_shape(a, cin, cout, k, d, L))
+    if a.markdown:
+        print("| layer | L | fwd ms (torch) | dgrad ms (torch) | wgrad ms (torch) | TFLOP/s fwd / dgrad / wgrad | P | repack ms |")
+        print("|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['cin']} -> {r['cout']}, k = {r['k']} | {r['L']} | {r['fwd_ms']:.3f} ({r['torch_fwd_ms']:.3f}) | "
+                  f"{r['dgrad_ms']:.3f} ({r['torch_dgrad_ms']:.3f}) | {r['wgrad_ms']:.3f} ({r['torch_wgrad_ms']:.3f}) | "
+                  f"{r['fwd_tflops']} / {r['dgrad_tflops']} / {r['wgrad_tflops']} | {r['partials']} | {r['repack_ms']:.3f} |")
+        tot = lambda n: sum(r[n] * (6 if r["cin"] == r["cout"] else 1) for r in rows)  # a ResBlock has six convs of its shape
+        print(f"\nsum over the generator's 92 stride-1 layers, ours (torch): "
+              f"fwd {tot('fwd_ms'):.2f} ({tot('torch_fwd_ms'):.2f}), dgrad {tot('dgrad_ms'):.2f} ({tot('torch_dgrad_ms'):.2f}), "
+              f"wgrad {tot('wgrad_ms'):.2f} ({tot('torch_wgrad_ms'):.2f}) ms")
+    return rows
+
+
+if __name__ == "__main__":
+    main()
