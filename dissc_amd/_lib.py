@@ -41,6 +41,10 @@ class DisscGenConfig(ctypes.Structure):
                 ("num_speakers", ctypes.c_int32), ("has_f0", ctypes.c_int32), ("has_spkr", ctypes.c_int32)]
 
 
+class DisscConvLaunch(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("family", "cfg", "bm", "bn", "rows", "p0", "np", "ntap", "pad_left")]
+
+
 def _load():
     path = library_path()
     if not os.path.exists(path):
@@ -109,6 +113,7 @@ def _load():
     L.dissc_conv_s2_bench.argtypes = [i32] * 5 + [ctypes.POINTER(ctypes.c_float)]
     L.dissc_pair_bench.argtypes = [i32] * 8 + [ctypes.POINTER(ctypes.c_float)]
     L.dissc_pair_info.argtypes = [i32] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2
+    L.dissc_conv_info.argtypes = [i32] * 7 + [ctypes.POINTER(DisscConvLaunch), i32, ctypes.POINTER(ctypes.c_int)]
     L.dissc_respair1d.argtypes = [vp] * 8 + [i32] * 6 + [ctypes.c_float, i32, ctypes.c_float, i32, vp]
     L.dissc_wav_postprocess.argtypes = [vp, vp, i32, i32, vp]
     L.dissc_pitch_stats.argtypes = [vp, vp, i32, vp, vp, vp, vp]
@@ -155,3 +160,23 @@ def make_tensor_table(named):
         for d in range(t.dim()):
             arr[i].shape[d] = t.shape[d]
     return arr, keep
+
+
+def conv_info(Cin, Cout, k, dilation=1, up=1, B=1, Lmax_out=1):
+    """dissc_conv_info: the launches of dissc_conv1d (up = 1) / dissc_conv_transpose1d (up > 1) for the shape under the current
+    option defaults, as a list of dicts (family, cfg, bm, bn, rows, p0, np, ntap, pad_left).  Host only."""
+    out = (DisscConvLaunch * 16)()
+    n = ctypes.c_int(0)
+    check(lib.dissc_conv_info(Cin, Cout, k, dilation, up, B, Lmax_out, out, 16, ctypes.byref(n)), "dissc_conv_info")
+    assert n.value <= 16
+    return [{f: getattr(out[i], f) for f, _ in DisscConvLaunch._fields_} for i in range(n.value)]
+
+
+def get_option(key):
+    v = ctypes.c_int(0)
+    check(lib.dissc_get_option(key.encode(), ctypes.byref(v)), f"dissc_get_option({key})")
+    return v.value
+
+
+def set_option(key, value):
+    check(lib.dissc_set_option(key.encode(), int(value)), f"dissc_set_option({key})")

@@ -241,6 +241,8 @@ int launch_conv(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_t 
 // LDS row stride for a (KS, dil) conv with time tile BN.
 int conv_tile_bn(int M);
 int conv_cfg(int M);
+int conv_cfg_bm(int cfg);  // rows / columns of tile shape `cfg`
+int conv_cfg_bn(int cfg);
 void conv_set_cfg(int bm_class, int cfg);  // tuning hook (dissc_conv_bench / dissc_set_option)
 int conv_xw(int M, int KS, int dil, int stride = 1, int m32 = 0, int bn = 0);  // bn > 0: explicit time tile
 // 32x32x2 form (conv_mfma32.hip)
@@ -256,6 +258,8 @@ int launch_conv2s128(const ConvArgs& a, int B, int Lmax_out, hipStream_t stream)
 int conv32_tile_bn(int M);
 int conv32_cfg(int M);
 int conv32_pick_cfg(int M, int B, int Lmax_out);  // per-launch choice (steps down on small grids)
+int conv32_launch_cfg(int cfg32, int M);  // the id launch_conv32 runs: ConvArgs::cfg32, or the class default where that is -1
+int conv32_cfg_bm(int cfg);
 int conv32_cfg_bn(int cfg);
 void conv32_set_cfg(int bm_class, int cfg);
 void pack_conv_weights32(const float* w, int Cout, int Cin, int KS, std::vector<float>& packed,
@@ -307,6 +311,13 @@ struct ConvIO {
   int len_default = 0, olen_default = -1, len_mul = 1;
 };
 int upload(const std::vector<float>& h, float** d);
+// host-only planning shared by the packers, the launch path and dissc_conv_info (conv_host.hip)
+int conv_m32_rule(int Mg, int groups);  // 1: the layer is packed for / launched on the 32x32x2 kernel
+void conv_geometry(DevConv& dc, int Cout, int Cin, int KS, int dil, int groups, int stride, int pad_left);
+struct ConvTGroup { int p0, np, dlo, ntap; };  // output phases [p0, p0 + np) over the input taps dlo .. dlo + ntap - 1
+void convT_groups(int Cout, int k, int s, std::vector<ConvTGroup>& out);
+int conv_launch_cfg32(const DevConv& dc, int B, int Lmax_out);
+int conv_launch_info(const DevConv& dc, int B, int Lmax_out, int* family, int* cfg, int* bm, int* bn);
 int make_conv(const float* w, const float* bias, int Cout, int Cin, int KS, int dil, DevConv& dc,
               int groups = 1, int stride = 1, int pad_left = -1);
 // ConvTranspose1d = one conv per group of output phases sharing the same input taps.

@@ -15,30 +15,41 @@ int upload(const std::vector<float>& h, float** d) {
   return DISSC_OK;
 }
 
-// w: [Cout][Cin/groups][KS] (PyTorch layout); Cout, Cin are the TOTAL channel counts.
-int make_conv(const float* w, const float* bias, int Cout, int Cin, int KS, int dil, DevConv& dc,
-              int groups, int stride, int pad_left) {
-  std::vector<float> packed;
-  int Mpad, nchunk;
+// Which kernel family a layer of Mg rows per group is packed for and launched on.
+// 64-cycle MFMAs wherever a 32-row tile is not mostly padding; 48 rows per group (HuBERT's positional conv) are three
+// 16-row tiles of the 16x16x4 kernel instead of two 32-row tiles of which a quarter is padding
+int conv_m32_rule(int Mg, int groups) { return (opts().use_mfma32 && Mg >= 32 && !(Mg == 48 && groups > 1)) ? 1 : 0; }
+
+// The launch geometry of a layer (everything of a DevConv that is not a device pointer or a packing's Mpad): what make_conv
+// packs for and what dissc_conv_info answers from, without an upload.
+void conv_geometry(DevConv& dc, int Cout, int Cin, int KS, int dil, int groups, int stride, int pad_left) {
   const int Mg = Cout / groups, Cg = Cin / groups;
-  // 64-cycle MFMAs wherever a 32-row tile is not mostly padding; 48 rows per group (HuBERT's positional conv) are three
-  // 16-row tiles of the 16x16x4 kernel instead of two 32-row tiles of which a quarter is padding
-  dc.m32 = (opts().use_mfma32 && Mg >= 32 && !(Mg == 48 && groups > 1)) ? 1 : 0;
+  dc.m32 = conv_m32_rule(Mg, groups);
   // split-bf16 only where conv_mfma32.hip has an instance for it
   const bool lin_big = (KS == 1 && Mg >= 256 && (Cg + KC - 1) / KC >= 8);
   dc.prec = (g_conv_prec == 1 && dc.m32 && stride == 1 && groups == 1 && (KS - 1) * dil <= MAX_TAP_SPAN && !lin_big)
                 ? 1 : 0;
   // the encoder's route (a split-bf16 HuBERT handle): its own kernel, also for the linears and stride-2 convs refused above
   if (g_conv_prec == 2 && dc.m32 && enc_bf3_supported(Cout, Cin, KS, dil, groups, stride, pad_left)) dc.prec = 2;
+  dc.CIN = Cg; dc.M = Mg; dc.KS = KS; dc.dil = dil; dc.nchunk = (Cg + KC - 1) / KC; dc.up = 1;
+  dc.groups = groups; dc.stride = stride; dc.pad_left = pad_left;
+  dc.macs_per_t = (double)Cout * Cg * KS;
+}
+
+// w: [Cout][Cin/groups][KS] (PyTorch layout); Cout, Cin are the TOTAL channel counts.
+int make_conv(const float* w, const float* bias, int Cout, int Cin, int KS, int dil, DevConv& dc,
+              int groups, int stride, int pad_left) {
+  std::vector<float> packed;
+  int Mpad, nchunk;
+  const int Mg = Cout / groups, Cg = Cin / groups;
+  conv_geometry(dc, Cout, Cin, KS, dil, groups, stride, pad_left);
   if (dc.prec) pack_conv_weights_bf3(w, Cout, Cg, KS, packed, Mpad, nchunk);
   else if (dc.m32) pack_conv_weights32(w, Cout, Cg, KS, packed, Mpad, nchunk, groups);
   else pack_conv_weights(w, Cout, Cg, KS, packed, Mpad, nchunk, groups);
   std::vector<float> b((size_t)Mpad * groups, 0.f);
   if (bias)
     for (int g = 0; g < groups; ++g) memcpy(b.data() + (size_t)g * Mpad, bias + (size_t)g * Mg, Mg * sizeof(float));
-  dc.CIN = Cg; dc.M = Mg; dc.KS = KS; dc.dil = dil; dc.nchunk = nchunk; dc.up = 1;
-  dc.groups = groups; dc.Mpad = Mpad; dc.stride = stride; dc.pad_left = pad_left;
-  dc.macs_per_t = (double)Cout * Cg * KS;
+  dc.nchunk = nchunk; dc.Mpad = Mpad;
   int rc = upload(packed, &dc.wpack);
   if (rc) return rc;
   if (dc.m32 && !dc.prec && dil == 1 && conv2s128_shape(Cout, Cin, KS, stride, groups) && opts().conv2s128) {
@@ -49,10 +60,10 @@ int make_conv(const float* w, const float* bias, int Cout, int Cin, int KS, int 
   return upload(b, &dc.bias);
 }
 
-int make_convT(const float* w, const float* bias, int Cin, int Cout, int k, int s,
-               std::vector<DevConv>& groups) {
+// The phase groups of ConvTranspose1d(k, s, padding (k - s) / 2): one conv launch per group of output phases.
+void convT_groups(int Cout, int k, int s, std::vector<ConvTGroup>& out) {
   const int pad = (k - s) / 2;
-  groups.clear();
+  out.clear();
   // input taps of phase p: delta in [dlo, dhi] with 0 <= p + pad - s*delta < k
   auto taps = [&](int p, int& dlo, int& dhi) {
     dlo = 1 << 30;
@@ -82,7 +93,18 @@ int make_convT(const float* w, const float* bias, int Cin, int Cout, int k, int 
       }
       ++np;
     }
-    const int ntap = dhi - dlo + 1;
+    out.push_back(ConvTGroup{p0, np, dlo, dhi - dlo + 1});
+    p0 += np;
+  }
+}
+
+int make_convT(const float* w, const float* bias, int Cin, int Cout, int k, int s,
+               std::vector<DevConv>& groups) {
+  groups.clear();
+  std::vector<ConvTGroup> plan;
+  convT_groups(Cout, k, s, plan);
+  for (const ConvTGroup& g : plan) {
+    const int p0 = g.p0, np = g.np, dlo = g.dlo, ntap = g.ntap;
     std::vector<float> wc;
     convT_phase_weights(w, Cin, Cout, k, s, p0, np, dlo, ntap, wc);
     std::vector<float> bc((size_t)Cout * np);
@@ -96,7 +118,6 @@ int make_convT(const float* w, const float* bias, int Cin, int Cout, int k, int 
     dc.up_np = np;
     dc.up_p0 = p0;
     dc.macs_per_t = groups.size() == 1 ? (double)Cin * Cout * k : 0.0;  // algorithmic MACs counted once
-    p0 += np;
   }
   return DISSC_OK;
 }
@@ -124,6 +145,41 @@ void free_conv(DevConv& dc) {
 }
 
 
+// Tile shape id of the 32-row kernel for one launch of the layer, -1 = the class default.  General path only: the special
+// instances (split-bf16, strided, grouped, wide-tap and the big 1x1 layers) keep their tile.
+int conv_launch_cfg32(const DevConv& dc, int B, int Lmax_out) {
+  const int span = (dc.KS - 1) * dc.dil;
+  const bool lin_big = (dc.KS == 1 && dc.M >= 256 && dc.nchunk >= 8);
+  if (dc.m32 && !dc.prec && dc.stride == 1 && dc.groups == 1 && span <= MAX_TAP_SPAN && !lin_big)
+    return conv32_pick_cfg(dc.M, B, Lmax_out);
+  return -1;
+}
+
+// What one launch of the layer runs on: kernel family, tile shape id in force, BM x BN.  Host only.
+int conv_launch_info(const DevConv& dc, int B, int Lmax_out, int* family, int* cfg, int* bm, int* bn) {
+  const int span = (dc.KS - 1) * dc.dil;
+  if (dc.prec || dc.stride != 1 || dc.groups != 1 || span > MAX_TAP_SPAN) {
+    set_error("conv_launch_info: only the general stride-1 fp32 instances (span <= %d) are described", MAX_TAP_SPAN);
+    return DISSC_EINVAL;
+  }
+  if (dc.m32) {
+    const int c32 = conv_launch_cfg32(dc, B, Lmax_out);
+    if (c32 < 0) {
+      set_error("conv_launch_info: %d x %d 1x1 layer runs on a special instance with a fixed tile", dc.M, dc.CIN);
+      return DISSC_EINVAL;
+    }
+    *family = 32; *cfg = conv32_launch_cfg(c32, dc.M); *bm = conv32_cfg_bm(*cfg); *bn = conv32_cfg_bn(*cfg);
+  } else {
+    *family = 16; *cfg = conv_cfg(dc.M);
+    if (span == 0 && *cfg == 0 && dc.nchunk >= 8) {
+      set_error("conv_launch_info: %d x %d 1x1 layer runs on a special instance with a fixed tile", dc.M, dc.CIN);
+      return DISSC_EINVAL;
+    }
+    *bm = conv_cfg_bm(*cfg); *bn = conv_cfg_bn(*cfg);
+  }
+  return DISSC_OK;
+}
+
 int run_conv_ex(const DevConv& dc, const float* x, float* out, const float* res, float* acc,
                 const ConvIO& io, int B, int C_x_total, int ldx, int ldo, int Lmax_out, float slope,
                 int epi, float mrf_div, hipStream_t stream, float out_slope, int dma_in) {
@@ -138,11 +194,7 @@ int run_conv_ex(const DevConv& dc, const float* x, float* out, const float* res,
   a.xcd = 0; a.xcd_ntile = 0; a.xcd_nb = 0; a.xcd_mg = 0; a.xcd_span = 0;
   a.ragged_enum = 0;
   a.groups = dc.groups; a.nsub_group = dc.Mpad / (dc.m32 ? 32 : 16); a.act = dc.act; a.m32 = dc.m32; a.prec = dc.prec;
-  a.cfg32 = -1;
-  const int span = (dc.KS - 1) * dc.dil;
-  const bool lin_big = (dc.KS == 1 && dc.M >= 256 && dc.nchunk >= 8);
-  if (dc.m32 && !dc.prec && dc.stride == 1 && dc.groups == 1 && span <= MAX_TAP_SPAN && !lin_big)
-    a.cfg32 = conv32_pick_cfg(dc.M, B, Lmax_out);  // general path only: the special instances keep their tile
+  a.cfg32 = conv_launch_cfg32(dc, B, Lmax_out);
   a.XW = conv_xw(dc.M, dc.KS, dc.dil, dc.stride, dc.m32, a.cfg32 >= 0 ? conv32_cfg_bn(a.cfg32) : 0);
   a.ldx = ldx; a.ldo = ldo;
   a.x_bstride = (long long)C_x_total * ldx;

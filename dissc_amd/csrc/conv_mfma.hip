@@ -269,8 +269,10 @@ static const TileCfg kCfgs[] = {
 };
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 
+// (id 10, 48 x 256, is pick_bm(48)'s alone and no override: 48 rows divide no class's padded M, and the last M tile of a
+// 64 / 128 / 256-row class would read weight slabs beyond the packed array)
 void conv_set_cfg(int bm_class, int cfg) {
-  if (bm_class >= 0 && bm_class < 5 && cfg >= 0 && cfg < kNumCfgs) g_defaults.cfg_for_bm[bm_class] = cfg;
+  if (bm_class >= 0 && bm_class < 5 && cfg >= 0 && cfg < kNumCfgs && cfg != 10) g_defaults.cfg_for_bm[bm_class] = cfg;
 }
 
 int conv_cfg(int M) {
@@ -282,6 +284,9 @@ int conv_cfg(int M) {
   if (16 * kCfgs[cfg].MI * kCfgs[cfg].WM > bm) cfg = 4 - cls;  // override must divide the padded M
   return cfg;
 }
+
+int conv_cfg_bm(int cfg) { return 16 * kCfgs[cfg].MI * kCfgs[cfg].WM; }
+int conv_cfg_bn(int cfg) { return 16 * kCfgs[cfg].NI * kCfgs[cfg].WN; }
 
 int conv_tile_bn(int M) {
   const TileCfg& c = kCfgs[conv_cfg(M)];

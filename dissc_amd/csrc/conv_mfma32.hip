@@ -297,6 +297,8 @@ int conv32_tile_bn(int M) {
 }
 
 int conv32_cfg_bn(int cfg) { return 32 * kCfgs32[cfg].NI * kCfgs32[cfg].WN; }
+int conv32_cfg_bm(int cfg) { return 32 * kCfgs32[cfg].MI * kCfgs32[cfg].WM; }
+int conv32_launch_cfg(int cfg32, int M) { return cfg32 >= 0 ? cfg32 : conv32_cfg(M); }
 
 // Tile shape for one launch.  The defaults are tuned for grids that fill the chip several times;
 // a short or single utterance (the reference's one-at-a-time mode) gives a 256 x 64 tile only a
@@ -397,7 +399,7 @@ static int launch32_t(ConvArgs a, int B, int Lmax_out, hipStream_t stream) {
 
 int launch_conv32(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_t stream) {
   const int span = (a.KS - 1) * a.dil;
-  const int cfg = a.cfg32 >= 0 ? a.cfg32 : conv32_cfg(a.M);
+  const int cfg = conv32_launch_cfg(a.cfg32, a.M);
   if (stride == 2 && opts().conv2s128 && conv2s128_supported(a)) return launch_conv2s128(a, B, Lmax_out, stream);
   if (stride == 2 && span <= MAX_TAP_SPAN && a.up == 1) {
     // valid (unpadded) convs on an already-activated input: raw LDS-DMA window, nothing to mask -- every output column

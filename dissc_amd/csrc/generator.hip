@@ -306,7 +306,7 @@ static inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; 
 extern "C" {
 
 const char* dissc_last_error(void) { return g_err; }
-int dissc_abi_version(void) { return 5; }
+int dissc_abi_version(void) { return 6; }
 
 int dissc_device_count(void) {
   int n = 0;
@@ -934,6 +934,38 @@ int dissc_pair_info(int C, int k, int dilation, int* form_out, int* tile_out) {
   return DISSC_OK;
 }
 
+// Diagnostics: the launches dissc_conv1d (up == 1) / dissc_conv_transpose1d (up > 1: k taps, stride up) make for a layer on a
+// batch of B utterances of at most Lmax_out columns per launch, under the current option defaults: the planning functions of
+// make_conv / make_convT / run_conv_ex / launch_conv themselves, without packing or uploading anything.  Host only: no HIP call.
+int dissc_conv_info(int Cin, int Cout, int k, int dilation, int up, int B, int Lmax_out, DisscConvLaunch* out, int max_out,
+                    int* n_out) {
+  if (Cin < 1 || Cout < 1 || k < 1 || dilation < 1 || up < 1 || B < 1 || Lmax_out < 1 || max_out < 0 || (max_out && !out) ||
+      (up == 1 && k % 2 != 1) || (up > 1 && ((k - up) % 2 != 0 || k < up || dilation != 1))) {
+    set_error("dissc_conv_info: bad argument");
+    return DISSC_EINVAL;
+  }
+  std::vector<ConvTGroup> plan;
+  if (up > 1) convT_groups(Cout, k, up, plan);
+  else plan.push_back(ConvTGroup{0, 1, 0, k});
+  int n = 0;
+  for (const ConvTGroup& g : plan) {
+    DevConv dc;  // geometry only: nothing is uploaded, nothing to free
+    conv_geometry(dc, Cout * g.np, Cin, g.ntap, up > 1 ? 1 : dilation, 1, 1, up > 1 ? -g.dlo : -1);
+    int family, cfg, bm, bn;
+    const int rc = conv_launch_info(dc, B, Lmax_out, &family, &cfg, &bm, &bn);
+    if (rc) return rc;
+    if (n < max_out) {
+      DisscConvLaunch& o = out[n];
+      o.family = family; o.cfg = cfg; o.bm = bm; o.bn = bn; o.rows = dc.M;
+      o.p0 = g.p0; o.np = g.np; o.ntap = g.ntap;
+      o.pad_left = dc.pad_left >= 0 ? dc.pad_left : ((dc.KS - 1) * dc.dil) / 2;
+    }
+    ++n;
+  }
+  if (n_out) *n_out = n;
+  return DISSC_OK;
+}
+
 // Diagnostics: average ms of `iters` launches of one residual pair (modes as dissc_respair1d) on synthetic data.
 int dissc_pair_bench(int B, int C, int k, int dilation, int L, int epi, int iters, int mode, float* ms_out) {
   if (!ms_out || B <= 0 || L <= 0 || iters <= 0 || epi < EPI_RES || epi > EPI_MRF_DIV) {
@@ -1013,6 +1045,14 @@ int dissc_get_option(const char* key, int* value) {
   if (strcmp(key, "graph_hits") == 0) { *value = g_graph_hits; return DISSC_OK; }
   if (strcmp(key, "graph_captures") == 0) { *value = g_graph_captures; return DISSC_OK; }
   if (strcmp(key, "experimental") == 0) { *value = DISSC_EXPERIMENTAL; return DISSC_OK; }
+  // the tile-shape tables, under the keys dissc_set_option takes: "conv_cfg_bm16|32|64|128|256", "conv32_cfg_bm32|64|128|256"
+  for (int cls = 0; cls < 5; ++cls) {
+    char name[32];
+    snprintf(name, sizeof name, "conv_cfg_bm%d", 16 << cls);
+    if (strcmp(key, name) == 0) { *value = g_defaults.cfg_for_bm[cls]; return DISSC_OK; }
+    snprintf(name, sizeof name, "conv32_cfg_bm%d", 32 << cls);
+    if (cls < 4 && strcmp(key, name) == 0) { *value = g_defaults.cfg32_for_bm[cls]; return DISSC_OK; }
+  }
 #define DISSC_OPT_GET(f, d, k) if (strcmp(key, k) == 0) { *value = g_defaults.f; return DISSC_OK; }
   DISSC_OPTION_LIST(DISSC_OPT_GET)
 #undef DISSC_OPT_GET

@@ -47,7 +47,8 @@ typedef struct {
 } DisscTensor;
 
 const char* dissc_last_error(void);
-/* ABI version of this header: bumped when a signature changes or a section is added (5: dissc_convgrad_*). */
+/* ABI version of this header: bumped when a signature changes or a section is added (5: dissc_convgrad_*;
+ * 6: dissc_conv_info, and dissc_get_option reads the tile-shape keys). */
 int dissc_abi_version(void);
 /* Number of HIP devices visible / name of device `dev` (for diagnostics). */
 int dissc_device_count(void);
@@ -232,7 +233,8 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *                        XCD: its K / V rows cross the fabric once)
  * Unknown keys return DISSC_EINVAL. */
 int dissc_set_option(const char* key, int value);
-/* Read back any option's DEFAULT (so that a wrapper can set an option around the creation of one handle and restore it), plus
+/* Read back any option's DEFAULT (so that a wrapper can set an option around the creation of one handle and restore it), the
+ * conv_cfg_bm* / conv32_cfg_bm* tile-shape ids as set (before the clamps of the launch path: dissc_conv_info has those), plus
  * "experimental" (1: the library was built with DISSC_EXPERIMENTAL=1), "graph_hits", "graph_captures". */
 int dissc_get_option(const char* key, int* value);
 
@@ -258,6 +260,21 @@ int dissc_pair_bench(int B, int C, int k, int dilation, int L, int epi, int iter
  * outputs one workgroup of that instance owns (0 for form 0).  DISSC_EINVAL where mode 3 has no instance.  Host only: no GPU
  * is touched. */
 int dissc_pair_info(int C, int k, int dilation, int* form_out, int* tile_out);
+/* The launches dissc_conv1d (up = 1: Cin -> Cout, k taps, `dilation`) or dissc_conv_transpose1d (up > 1: k taps, stride `up`,
+ * dilation 1) makes on a batch of B utterances of at most Lmax_out columns per launch (for a ConvTranspose: INPUT columns), under
+ * the current option defaults: one for a conv, one per group of output phases for a ConvTranspose.  Per launch: the kernel
+ * family (16 = conv_mfma_kernel, 32 = conv_mfma32_kernel), the tile shape id in force after the overrides' clamps and the
+ * small-grid step-down, its BM x BN, the GEMM rows (Cout, or Cout * np), and for a ConvTranspose the phases [p0, p0 + np) of
+ * the group, its input taps `ntap` and the left padding of its conv (np = 1, p0 = 0, ntap = k and (k - 1) dilation / 2 for a conv).
+ * The answer comes from the launch path's own planning functions.  Up to max_out entries are written, *n_out is the number of
+ * launches.  DISSC_EINVAL for the layers that run on a special instance with a fixed tile (taps spanning more than 60 columns,
+ * the big 1x1 layers).  Host only: no GPU is touched. */
+typedef struct {
+  int32_t family, cfg, bm, bn, rows;
+  int32_t p0, np, ntap, pad_left;
+} DisscConvLaunch;
+int dissc_conv_info(int Cin, int Cout, int k, int dilation, int up, int B, int Lmax_out, DisscConvLaunch* out, int max_out,
+                    int* n_out);
 
 /* ------------------------------------------------------------------------- *
  * Length / pitch predictors and infer.py's integer sample logic.

@@ -47,21 +47,35 @@ def test_dma_handover_of_wide_residual_pairs_on_a_poisoned_workspace(env):
     code, f0, spkr, _ = synth.synth_generator_inputs(B, T, seed=11)
     kw = dict(code=torch.from_numpy(code).cuda(), f0=torch.from_numpy(f0).cuda(), spkr=torch.from_numpy(spkr).cuda())
     lens = torch.tensor([70, 64, 33, 1, 17], dtype=torch.int32).cuda()
+    from dissc_amd import _lib
+    hop_of = np.cumprod(synth.VCTK_CONFIG["upsample_rates"])
+    wide = [(synth.VCTK_CONFIG["upsample_initial_channel"] >> (i + 1), T * int(hop_of[i])) for i in range(3)]  # C = 256, 128, 64
     outs = {}
-    for v in (0, 1):  # a handle snapshots the options when it is created: one generator per setting
-        try:
-            assert lib.dissc_set_option(b"wino", 0) == 0 and lib.dissc_set_option(b"pair_dma", v) == 0
-            g = dissc_amd.CodeGenerator(synth.VCTK_CONFIG).to("cuda:0")
-            g.load_state_dict(synth.synth_generator_state_dict(seed=0))
-            g.eval().remove_weight_norm()
-            g(**kw, lengths=lens)  # builds the native handle (every conv direct) and sizes the workspace
-        finally:
-            lib.dissc_set_option(b"wino", 1)
-            lib.dissc_set_option(b"pair_dma", 1)
-        g._ws.view(torch.float32)[: g._ws.numel() // 4].fill_(float("nan"))
-        outs[v] = g(**kw, lengths=lens).clone()
-        assert torch.isfinite(outs[v]).all(), v
-    assert torch.equal(outs[0], outs[1])
+    # small_grid 1 (shipped): whatever tier the step-down picks at this size.  small_grid 0: the wide stages stay on tile ids
+    # 0 / 1 / 2, the only ones with an LDS-DMA instance (launch_conv32 falls through to the masked kernel for the others) --
+    # asserted through dissc_conv_info, so that the two settings of pair_dma cannot silently run the same code
+    for sg in (1, 0):
+        for v in (0, 1):  # a handle snapshots the options when it is created: one generator per setting
+            before = {k: _lib.get_option(k) for k in ("wino", "pair_dma", "small_grid")}
+            try:
+                assert lib.dissc_set_option(b"wino", 0) == 0 and lib.dissc_set_option(b"pair_dma", v) == 0
+                assert lib.dissc_set_option(b"small_grid", sg) == 0
+                if sg == 0:
+                    ids = [_lib.conv_info(C, C, 3, 1, 1, B, L)[0] for C, L in wide]
+                    assert [(i["family"], i["cfg"]) for i in ids] == [(32, 0), (32, 1), (32, 2)], ids
+                g = dissc_amd.CodeGenerator(synth.VCTK_CONFIG).to("cuda:0")
+                g.load_state_dict(synth.synth_generator_state_dict(seed=0))
+                g.eval().remove_weight_norm()
+                g(**kw, lengths=lens)  # builds the native handle (every conv direct) and sizes the workspace
+            finally:
+                for k, val in before.items():
+                    _lib.set_option(k, val)
+            g._ws.view(torch.float32)[: g._ws.numel() // 4].fill_(float("nan"))
+            outs[sg, v] = g(**kw, lengths=lens).clone()
+            assert torch.isfinite(outs[sg, v]).all(), (sg, v)
+        assert torch.equal(outs[sg, 0], outs[sg, 1]), sg
+    assert torch.equal(outs[0, 1], outs[1, 1])  # (every tile shape gives the same bits)
+    outs = {v: outs[1, v] for v in (0, 1)}
     hop = outs[0].shape[-1] // T
     for b, n in enumerate([70, 64, 33, 1, 17]):
         assert not outs[1][b, 0, n * hop:].any()
