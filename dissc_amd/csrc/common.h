@@ -52,7 +52,8 @@ void set_error(const char* fmt, ...);
   X(pair_max_c, 32, "pair_max_c") \
   X(pair_f23, 3, "pair_f23") \
   X(pair_tc6, 3, "pair_tc6") \
-  X(pair_f23_c64, 1, "pair_f23_c64")
+  X(pair_f23_c64, 1, "pair_f23_c64") \
+  X(pair_tc6_c64, 1, "pair_tc6_c64")
 // options of the kernels that only DISSC_EXPERIMENTAL=1 builds carry (experimental/csrc: gates failed, kept for the record)
 #define DISSC_OPTION_LIST_EXPERIMENTAL(X) \
   X(graphs, 0, "graphs") \
@@ -362,10 +363,10 @@ struct DevPairW {
   float* b2 = nullptr;
   int C = 0, KS = 0, dil = 1;
   int form = 0;  // 0: respair_wino_kernel (F(4,3), Y exchanged through LDS); register-only: 1: respair32/16_f23_kernel (F(2,3)),
-                 // 2: respair32_tc6_kernel (six points as F(3,4))
+                 // 2: respair32_tc6_kernel / respair64_tc6_kernel (six points as F(3,4))
 };
 // register-only forms (pair_host.hip): F(2,3), k = 11 at C = 16 / 32 (respair16_f23.hip, respair_f23.hip) and k = 3 at C = 64
-// (respair_f23.hip); six points as F(3,4), k = 7 / 11 at C = 32 (respair_f23.hip)
+// (respair_f23.hip); six points as F(3,4), k = 7 / 11 at C = 32 / 64 (respair_f23.hip)
 bool pair_f23_supported(int C, int KS, int dil);
 bool pair_tc6_supported(int C, int KS, int dil);
 // the F(4,3) form: experimental/csrc/respair_wino.hip in DISSC_EXPERIMENTAL=1 builds, experimental_stubs.hip otherwise

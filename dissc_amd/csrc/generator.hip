@@ -135,9 +135,21 @@ static ConvForm td_conv_form(int C, int KS, int dil) {
 //   register-only F(2,3) launch each (respair64_f23_kernel in respair_f23.hip: 2 C^2 products per output and conv where the two
 //   conv_wino launches it replaces execute 1.5 C^2, for two tensor passes instead of five); 0 = two transform-domain launches.
 //   Measurements: profiles/r09.
+// option "pair_tc6_c64" (default 1), a bit mask honoured only while "pair_f23" != 0, independent of "pair_tc6" and
+//   "pair_f23_c64": 1 = the k = 7 pairs, 2 = the k = 11 pairs of the 64-channel stage run as ONE register-only six-point launch
+//   each (respair64_tc6_kernel in respair_f23.hip: 4 / 6 C^2 products per output and conv, two tensor passes instead of five);
+//   0 = two transform-domain launches in the forms td_conv_form() gives.  Per launch at d = 1 / 3 / 5, B = 32 x 40 000: k = 7
+//   810 / 869 / 950 us against 979 / 1 117 / 1 095 for the two launches, forward 31.89-32.06 -> 31.43-31.65 ms (five alternated
+//   runs); k = 11 1 210 / 1 307 / 1 465 against 1 251 / 1 318 / 1 317, forward slower with bit 2 than without: off
+//   (profiles/r10).
 // the register-only form of a pair (DevPairW::form: 1 F(2,3), 2 six points), or 0
 static int pair_reg_form(int C, int KS, int dil) {
-  if (C == 64) return KS == 3 && opts().pair_f23 != 0 && opts().pair_f23_c64 && pair_f23_supported(C, KS, dil) ? 1 : 0;
+  if (C == 64) {
+    if (opts().pair_f23 == 0) return 0;
+    if (KS == 3) return opts().pair_f23_c64 && pair_f23_supported(C, KS, dil) ? 1 : 0;
+    const int bit = KS == 7 ? 1 : KS == 11 ? 2 : 0;
+    return (opts().pair_tc6_c64 & bit) && pair_tc6_supported(C, KS, dil) ? 2 : 0;
+  }
   if (C != 16 && C != 32) return 0;
   const int stage = C == 32 ? 1 : 2;
   if (KS == 3) return pair_f23_supported(C, KS, dil) && (opts().pair_f23 & (stage << 2)) ? 1 : 0;
@@ -858,7 +870,8 @@ int dissc_conv1d(const float* x, const float* w_host, const float* bias_host, fl
 
 // Diagnostics / tests: ONE residual pair y = x + conv_1(lrelu(conv_d(lrelu(x)))) (or its MRF modes) on device data with
 // host weights, through a chosen implementation: mode 0 = two direct conv launches, 1 = the fused direct pair
-// (respair.hip), 2 = two conv_wino launches, 3 = the fused transform-domain pair (respair_wino.hip).  Synchronous.
+// (respair.hip), 2 = two conv_wino launches, 3 = the fused transform-domain pair (pair_host.hip), 4 = two transform-domain
+// launches in the forms the plan gives a PairForm::td pair of the shape (td_conv_form).  Synchronous.
 static int pair_run(int mode, const DevConv& c1, const DevConv& c2, const DevPairW& pw, const float* x, float* tmp, float* y,
                     float* acc, const int32_t* lengths, int B, int C, int ld, int Lmax, float slope, int epi, float mrf_div,
                     hipStream_t st) {
@@ -866,6 +879,7 @@ static int pair_run(int mode, const DevConv& c1, const DevConv& c2, const DevPai
   switch (mode) {
     case 0:
     case 2:
+    case 4:
       if ((rc = run_conv(c1, x, tmp, nullptr, nullptr, lengths, Lmax, 1, B, C, ld, ld, Lmax, slope, EPI_STORE, 1.f, st))) return rc;
       return run_conv(c2, tmp, y, x, acc, lengths, Lmax, 1, B, C, ld, ld, Lmax, slope, epi, mrf_div, st);
     case 1:
@@ -890,6 +904,14 @@ static int pair_make(int mode, const float* w1, const float* b1, const float* w2
     return make_wino(w2, b2, C, k, 1, c2);
   }
   if (mode == 3) return make_pairw(w1, b1, w2, b2, C, k, d, pair_reg_form(C, k, d), pw);
+  if (mode == 4) {
+    if (!wino_supported(C, C, k, d) || !wino_supported(C, C, k, 1)) {
+      set_error("pair mode 4: no transform-domain conv instance for C = %d, k = %d, d = %d", C, k, d);
+      return DISSC_EINVAL;
+    }
+    if ((rc = make_pair_conv(td_conv_form(C, k, d), w1, b1, C, k, d, c1))) return rc;
+    return make_pair_conv(td_conv_form(C, k, 1), w2, b2, C, k, 1, c2);
+  }
   if ((rc = make_conv(w1, b1, C, C, k, d, c1))) return rc;
   return make_conv(w2, b2, C, C, k, 1, c2);
 }
@@ -906,7 +928,7 @@ int dissc_respair1d(const float* x, const float* w1_host, const float* b1_host, 
   DevPairW pw;
   float* tmp = nullptr;
   int rc = pair_make(mode, w1_host, b1_host, w2_host, b2_host, C, k, dilation, c1, c2, pw);
-  if (!rc && (mode == 0 || mode == 2) && hipMalloc((void**)&tmp, (size_t)B * C * ld * sizeof(float)) != hipSuccess) {
+  if (!rc && (mode == 0 || mode == 2 || mode == 4) && hipMalloc((void**)&tmp, (size_t)B * C * ld * sizeof(float)) != hipSuccess) {
     set_error("dissc_respair1d: hipMalloc");
     rc = DISSC_ENOMEM;
   }

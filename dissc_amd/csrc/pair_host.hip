@@ -1,7 +1,8 @@
 // Host side of the one-launch residual pairs in the Toom-Cook transform domain: which shapes have an instance, packing, dispatch.
 //   form 1: the register-only F(2,3) pairs (respair_f23.hip, respair16_f23.hip) -- the default for k = 11 at C = 16, and the
 //           k = 3 pairs at C = 64 (respair64_f23_kernel, option "pair_f23_c64");
-//   form 2: the register-only six-point F(3,4) pairs (respair_f23.hip) -- the default for k = 7 / 11 at C = 32;
+//   form 2: the register-only six-point F(3,4) pairs (respair_f23.hip) -- the default for k = 7 / 11 at C = 32, and the
+//           k = 7 / 11 pairs at C = 64 (respair64_tc6_kernel, option "pair_tc6_c64");
 //   form 0: the F(4,3) pair kernel with the Y exchange through LDS (experimental/csrc/respair_wino.hip: its gate FAILED in round 4,
 //           it is in DISSC_EXPERIMENTAL=1 builds only; experimental_stubs.hip answers for it otherwise).
 #include <string.h>
@@ -15,13 +16,13 @@
 namespace dissc {
 
 // shapes with an instance.  Register-only F(2,3): k = 11 at C = 16 / 32 (k = 3 in DISSC_EXPERIMENTAL=1 builds), k = 3 at C = 64;
-// six points: k = 7 / 11 at C = 32; the F(4,3) kernel: a point's weights must fit 64 registers per lane (C^2 NS / 64 <= 64)
+// six points: k = 7 / 11 at C = 32 / 64; the F(4,3) kernel: a point's weights must fit 64 registers per lane (C^2 NS / 64 <= 64)
 bool pair_f23_supported(int C, int KS, int dil) {
   if (!(dil == 1 || dil == 3 || dil == 5)) return false;
   if (C == 64) return KS == 3;
   return (C == 16 || C == 32) && (KS == 11 || (KS == 3 && DISSC_EXPERIMENTAL));
 }
-bool pair_tc6_supported(int C, int KS, int dil) { return C == 32 && (KS == 7 || KS == 11) && (dil == 1 || dil == 3 || dil == 5); }
+bool pair_tc6_supported(int C, int KS, int dil) { return (C == 32 || C == 64) && (KS == 7 || KS == 11) && (dil == 1 || dil == 3 || dil == 5); }
 bool pairw_supported(int C, int KS, int dil) {
   if (!pairw43_built()) return false;  // (the kernel is in DISSC_EXPERIMENTAL=1 builds only)
   if (!(dil == 1 || dil == 3 || dil == 5)) return false;
@@ -62,7 +63,7 @@ static std::vector<float> transform_taps(const float* w, int C, int KS, const do
 }
 
 static int pack_pair_reg(const float* w, float** dev, int C, int KS, int form) {
-  if ((form != 1 && form != 2) || (C != 16 && C != 32 && C != 64) || (form == 2 && C != 32) || (C == 64 && KS != 3)) {
+  if ((form != 1 && form != 2) || (C != 16 && C != 32 && C != 64) || (form == 2 && C == 16) || (form == 1 && C == 64 && KS != 3)) {
     // (a layout loop exists for these only)
     set_error("pack_pair_reg: no layout for form %d, C = %d", form, C);
     return DISSC_EINVAL;
@@ -78,6 +79,16 @@ static int pack_pair_reg(const float* w, float** dev, int C, int KS, int form) {
       for (int p = 0; p < 4; ++p)
         for (int lane = 0; lane < 64; ++lane)
           for (int cq = 0; cq < 4; ++cq) packed[o++] = u(p, lane & 15, 4 * cq + (lane >> 4), j);
+  } else if (C == 64 && form == 2) {
+    // respair64_tc6_kernel: respair32_tc6_kernel's map below with four chunks, one slab per 32-row block (a wave streams its own
+    // slab, 6 KB per step): [row block 2][chunk 4][sub-filter][half 2][point 6][64 lanes][4 k-steps]
+    for (int mi = 0; mi < 2; ++mi)
+      for (int c = 0; c < 4; ++c)
+        for (int j = 0; j < NS; ++j)
+          for (int hf = 0; hf < 2; ++hf)
+            for (int p = 0; p < 6; ++p)
+              for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 4; ++e) packed[o++] = u(p, 32 * mi + (lane & 31), 16 * c + 2 * (4 * hf + e) + (lane >> 5), j);
   } else if (C == 64) {
     // respair64_f23_kernel (one sub-filter): [8-channel step 8][point 4][row block 2][64 lanes][4 k-steps]; lane l, k-step e ->
     // U_p[32 mi + (l & 31)][8 s + 2 e + (l >> 5)]
@@ -150,12 +161,13 @@ static int launch_pair_reg(const PairArgs& a, int B, int Lmax, hipStream_t strea
 
 // every register-only instance, as DISSC_CASE(form, C, kernel, Geo, want_max_lds, k, dilation)
 #define DISSC_TC6(K_, D_) DISSC_CASE(2, 32, respair32_tc6_kernel, Tc6Geo, true, K_, D_)
+#define DISSC_TC6_64(K_, D_) DISSC_CASE(2, 64, respair64_tc6_kernel, Tc6Geo64, false, K_, D_)
 #define DISSC_F23_32(K_, D_) DISSC_CASE(1, 32, respair32_f23_kernel, F23Geo32, true, K_, D_)
 #define DISSC_F23_16(K_, D_) DISSC_CASE(1, 16, respair16_f23_kernel, F23Geo16, false, K_, D_)
 #define DISSC_F23_64(K_, D_) DISSC_CASE(1, 64, respair64_f23_kernel, F23Geo64, true, K_, D_)
 #define DISSC_PAIR_REG_INSTANCES                                                                          \
   DISSC_PAIR_TC6_SHAPES(DISSC_TC6) DISSC_PAIR_F23_SHAPES(DISSC_F23_32) DISSC_PAIR_F23_SHAPES(DISSC_F23_16) \
-  DISSC_PAIR_F23_C64_SHAPES(DISSC_F23_64)
+  DISSC_PAIR_F23_C64_SHAPES(DISSC_F23_64) DISSC_PAIR_TC6_SHAPES(DISSC_TC6_64)
 
 // outputs a workgroup of the instance owns (the Geo::WOUT its launch sizes the grid by); 0: no register-only instance
 int pair_reg_tile(int form, int C, int KS, int dil) {

@@ -126,15 +126,17 @@ template <int KS, int DIL> using F23Geo32 = F23Geo<32, 8, KS, DIL>;
 template <int KS, int DIL> using F23Geo16 = F23Geo<16, 16, KS, DIL>;
 template <int KS, int DIL> using F23Geo64 = F23Geo<64, 8, KS, DIL, 32>;
 
-// six points: respair32_tc6_kernel (the scheme is described in respair_f23.hip)
-template <int KS_, int DIL>
-struct Tc6Geo {
-  static constexpr int KS = KS_, NS = (KS_ + 3) / 4, C = 32, NW = 4;
+// six points: respair32_tc6_kernel and respair64_tc6_kernel (the scheme is described in respair_f23.hip).  At C = 64 the two 32-row
+// blocks of a column tile go to a wave pair (RB = 2): wave w has column tile w / RB and row block w % RB, so a workgroup holds
+// NCT = 2 column tiles where C = 32 holds 4.
+template <int C_, int KS_, int DIL_>
+struct Tc6GeoC {
+  static constexpr int KS = KS_, DIL = DIL_, NS = (KS_ + 3) / 4, C = C_, NW = 4, RB = C_ / 32, NCT = NW / RB;
   static constexpr int P2 = (KS - 1) / 2, P1 = P2 * DIL;
   static constexpr int D1 = DIL * NS, D2 = NS;
-  static constexpr int NCOLS = 32 * NW;                                 // columns of conv_d per workgroup
+  static constexpr int NCOLS = 32 * NCT;                                // columns of conv_d per workgroup
   static constexpr int NU1 = NCOLS / D1, NC1 = NU1 * D1, W1 = 3 * NC1;  // positions of T conv_d produces: [o0 - P2, o0 - P2 + W1)
-  static constexpr int NCW2 = 32 / D2 * D2, OW = 3 * NCW2, W2 = NW * OW;  // conv_1: columns and outputs per wave, outputs [o0, o0 + W2)
+  static constexpr int NCW2 = 32 / D2 * D2, OW = 3 * NCW2, W2 = NCT * OW;  // conv_1: columns and outputs per column tile, outputs [o0, o0 + W2)
   static constexpr int WOUT = ((W1 - 2 * P2) < W2 ? (W1 - 2 * P2) : W2) & ~3;  // outputs a workgroup owns
   static constexpr int REACH1 = (4 * NS - 1) * DIL, REACH2 = 4 * NS - 1;  // samples read beyond the conv's last position
   // row stride of the one LDS buffer (x window, then T, then the patches): a multiple of 4 and no more -- the two halves of a
@@ -145,9 +147,12 @@ struct Tc6Geo {
   static constexpr int XW = XW1 > XW2 ? XW1 : XW2;
   static constexpr int PW = 96 + 4;                 // patch row: a wave's outputs from the 16-byte boundary below its first
   static constexpr int OCC = 3 * 4 * C * XW <= 160 * 1024 ? 3 : 2;  // workgroups per CU the LDS admits: the register budget follows
+  static_assert(C == 32 || C == 64, "one or two 32-row blocks");
   static_assert(3 + OW <= PW - 1 && NW * 8 * PW <= C * XW, "the epilogue patches fit the buffer");
   static_assert(W1 <= XW && WOUT + 2 * P2 <= W1 && WOUT <= W2, "T fits the buffer and covers what the owned outputs read");
 };
+template <int KS, int DIL> using Tc6Geo = Tc6GeoC<32, KS, DIL>;
+template <int KS, int DIL> using Tc6Geo64 = Tc6GeoC<64, KS, DIL>;
 
 // Each kernel is defined and instantiated in its own file for the (k, dilation) listed here; pair_host.hip launches from the
 // same lists.  k = 3 through the C = 16 / 32 F(2,3) kernels (one sub-filter, 2 products per output instead of 3) measured neutral
@@ -156,6 +161,7 @@ template <int KS, int DIL> __global__ void respair32_f23_kernel(const PairArgs a
 template <int KS, int DIL> __global__ void respair32_tc6_kernel(const PairArgs a);
 template <int KS, int DIL> __global__ void respair16_f23_kernel(const PairArgs a);
 template <int KS, int DIL> __global__ void respair64_f23_kernel(const PairArgs a);
+template <int KS, int DIL> __global__ void respair64_tc6_kernel(const PairArgs a);
 #if DISSC_EXPERIMENTAL
 #define DISSC_PAIR_F23_SHAPES(X) X(11, 1) X(11, 3) X(11, 5) X(3, 1) X(3, 3) X(3, 5)
 #else

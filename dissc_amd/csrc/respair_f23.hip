@@ -209,31 +209,31 @@ __global__ void __launch_bounds__(256, 2) respair32_f23_kernel(const PairArgs a)
 // waves: the patch is laid out from the 16-byte boundary below it and the two quads that straddle a neighbour's range are
 // stored element by element.
 // ---------------------------------------------------------------------------------------------
-template <int KS_, int DIL>
-__global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_kernel(const PairArgs a) {
-  using G = Tc6Geo<KS_, DIL>;
+template <class G>
+__device__ __forceinline__ void pair_tc6_body(const PairArgs a) {
   constexpr int C = G::C, NW = G::NW, NT = 64 * NW, NS = G::NS, P2 = G::P2, P1 = G::P1, D1 = G::D1, D2 = G::D2, XW = G::XW,
-                W1 = G::W1, NC1 = G::NC1, NCW2 = G::NCW2, OW = G::OW, WOUT = G::WOUT, PW = G::PW;
+                W1 = G::W1, NC1 = G::NC1, NCW2 = G::NCW2, OW = G::OW, WOUT = G::WOUT, PW = G::PW, RB = G::RB, DIL = G::DIL;
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [C][XW]
 
   int b, len, o0;
   if (!pair_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
+  const int ct = wave / RB, mrow = 32 * (wave % RB);  // the wave's column tile and the first row of its 32-row block
   const int tin0 = o0 - P2 - P1;
   const int tb = tin0 & ~3, sh = tin0 - tb;
   const float slope = a.slope;
   const float* xb = a.x + (size_t)b * a.bstride;
 
-  pair_stage_window<C, XW, NT>(a, xb, xs, tb, len, tid);
+  pair_stage_window<C, XW, NT, RB>(a, xb, xs, tb, len, tid);
 
   // this lane's column of each conv: column -> (unit tau, phase rho) -> first sample 3 D tau + rho
   int base1, base2;
   {
-    const int c = wave * 32 + l31;
+    const int c = ct * 32 + l31;
     const int c1 = c < NC1 ? c : NC1 - 1, c2 = l31 < NCW2 ? l31 : NCW2 - 1;
     base1 = 3 * D1 * (c1 / D1) + (c1 % D1);
-    base2 = wave * OW + 3 * D2 * (c2 / D2) + (c2 % D2);
+    base2 = ct * OW + 3 * D2 * (c2 / D2) + (c2 % D2);
   }
   typedef float f32x16f __attribute__((ext_vector_type(16)));
   f32x16f acc[6];
@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
   auto taps = [&](const float* wq, const float* src, int base, int dstep, int dunit) __attribute__((always_inline)) {
     const __amdgpu_buffer_rsrc_t wr = wave_rsrc(wq, 0x7ffffff0u);  // scalar-base loads (common.h), constant offsets
     const unsigned lane16 = lane * 16u;
-    constexpr int NST = 2 * NS * 2;  // step = (chunk * NS + sub-filter) * 2 + half
+    constexpr int NST = C / 16 * NS * 2;  // step = (chunk * NS + sub-filter) * 2 + half
     const unsigned wstep = (a.dbg & 8) ? 0u : 6 * 1024u;  // (knock-out: every step re-reads the first step's 6 KB)
     f32x4 av[6], avn[6];
 #pragma unroll
@@ -290,22 +290,23 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
     y2 = __builtin_fmaf(4.f, s34, s12) + acc[5][r];
   };
 
+  const int wslab = (wave % RB) * (C / 16 * NS * 2 * 6 * 256);  // the row block's slab of either conv's weights
   __syncthreads();
   clear();
-  if (!(a.dbg & 1)) taps(a.w1, xs + sh, base1, DIL, D1);
+  if (!(a.dbg & 1)) taps(a.w1 + wslab, xs + sh, base1, DIL, D1);
 
   // ---- T = lrelu(conv_d + b1) inside the utterance, 0 outside, into the same buffer: positions [0, W1) <-> times o0 - P2 + . ----
   __syncthreads();  // every wave is done reading the x window
   pair_zero_beyond_t<C, XW, W1, NT>(xs, tid);
   {
-    const int c = wave * 32 + l31;
+    const int c = ct * 32 + l31;
     if (c < NC1 && !(a.dbg & 2)) {
       const int p0 = 3 * D1 * (c / D1) + (c % D1);
       const int t0 = o0 - P2 + p0;
       const bool in0 = t0 >= 0 && t0 < len, in1 = t0 + D1 >= 0 && t0 + D1 < len, in2 = t0 + 2 * D1 >= 0 && t0 + 2 * D1 < len;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int row = mrow + (r & 3) + 8 * (r >> 2) + 4 * h;
         const float bz = a.b1[row];
         float v0, v1, v2;
         outs(r, v0, v1, v2);
@@ -321,13 +322,13 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
   }
   __syncthreads();
   clear();
-  if (!(a.dbg & 1)) taps(a.w2, xs, base2, 1, D2);
+  if (!(a.dbg & 1)) taps(a.w2 + wslab, xs, base2, 1, D2);
 
   // ---- epilogue: y = x + conv_1 + b2 (or an MRF mode), 8 rows at a time through a wave-private patch [8][PW] ----
   __syncthreads();  // every wave is done reading T, which the patches overwrite
   float* ep = xs + wave * (8 * PW);
   const int prow = lane >> 5, pc4 = lane & 31;
-  const int ws = wave * OW, woff = ws & 3;        // the wave's outputs [ws, ws + OW) of the tile
+  const int ws = ct * OW, woff = ws & 3;          // the wave's outputs [ws, ws + OW) of the tile
   const int ncol = ws - woff + 4 * pc4;           // this lane's quad
   const int tcol = o0 + ncol;
   const size_t ob = (size_t)b * a.bstride;
@@ -349,10 +350,10 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
     f32x4 rv[4], pa[4];  // (both from the clamped quad, unconditionally: used by the lanes whose quad is `full`)
     const int tc = tcol > a.ld - 4 ? a.ld - 4 : tcol;
 #pragma unroll
-    for (int p = 0; p < 4; ++p) rv[p] = *reinterpret_cast<const f32x4*>(a.x + ob + (size_t)(8 * qd + 2 * p + prow) * a.ld + tc);
+    for (int p = 0; p < 4; ++p) rv[p] = *reinterpret_cast<const f32x4*>(a.x + ob + (size_t)(mrow + 8 * qd + 2 * p + prow) * a.ld + tc);
     if (rmw) {
 #pragma unroll
-      for (int p = 0; p < 4; ++p) pa[p] = *reinterpret_cast<const f32x4*>(a.acc + ob + (size_t)(8 * qd + 2 * p + prow) * a.ld + tc);
+      for (int p = 0; p < 4; ++p) pa[p] = *reinterpret_cast<const f32x4*>(a.acc + ob + (size_t)(mrow + 8 * qd + 2 * p + prow) * a.ld + tc);
     }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -369,12 +370,21 @@ __global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_ke
       const int prw = 2 * p + prow;
       f32x4 v = *reinterpret_cast<const f32x4*>(ep + prw * PW + (4 * pc4 < PW - 4 ? 4 * pc4 : PW - 4));
       if (!live) continue;
-      const int row = 8 * qd + prw;
+      const int row = mrow + 8 * qd + prw;
       const float bz = a.b2[row];
       const size_t idx = ob + (size_t)row * a.ld + tcol;
       pair_store_tail(a, epi, idx, v, bz, rv[p], [&] { return pa[p]; }, elo, ehi);
     }
   }
+}
+
+template <int KS_, int DIL>
+__global__ void __launch_bounds__(256, (Tc6Geo<KS_, DIL>::OCC)) respair32_tc6_kernel(const PairArgs a) {
+  pair_tc6_body<Tc6Geo<KS_, DIL>>(a);
+}
+template <int KS_, int DIL>
+__global__ void __launch_bounds__(256, (Tc6Geo64<KS_, DIL>::OCC)) respair64_tc6_kernel(const PairArgs a) {
+  pair_tc6_body<Tc6Geo64<KS_, DIL>>(a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -556,6 +566,9 @@ DISSC_PAIR_TC6_SHAPES(DISSC_INSTANCE)
 #undef DISSC_INSTANCE
 #define DISSC_INSTANCE(K_, D_) template __global__ void respair64_f23_kernel<K_, D_>(const PairArgs);
 DISSC_PAIR_F23_C64_SHAPES(DISSC_INSTANCE)
+#undef DISSC_INSTANCE
+#define DISSC_INSTANCE(K_, D_) template __global__ void respair64_tc6_kernel<K_, D_>(const PairArgs);
+DISSC_PAIR_TC6_SHAPES(DISSC_INSTANCE)
 #undef DISSC_INSTANCE
 
 }  // namespace dissc

@@ -192,6 +192,12 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *   pair_f23_c64 (1)     read at dissc_gen_create, honoured only while pair_f23 != 0: the k = 3 residual pairs of the 64-channel
  *                        stage run as ONE register-only F(2,3) launch each (respair64_f23_kernel in respair_f23.hip) instead of two
  *                        conv_wino launches; 0 = the two launches.  Not bit-identical to them; rounding no larger
+ *   pair_tc6_c64 (1)     read at dissc_gen_create, a bit mask honoured only while pair_f23 != 0 (independent of pair_tc6 and
+ *                        pair_f23_c64): 1 = the k = 7, 2 = the k = 11 residual pairs of the 64-channel stage run as ONE
+ *                        register-only six-point F(3,4) launch each (respair64_tc6_kernel in respair_f23.hip) instead of two
+ *                        transform-domain launches (k = 7: per launch -13...-22 %, forward 1.4 % faster; k = 11: slower at
+ *                        d = 5 and in the forward, off); 0 = the two launches.  Not bit-identical to them; rounding within
+ *                        1.6 x the direct launches' on trained-like data
  *   pair_dma (1)         read at dissc_gen_create: the two-launch direct residual pairs of the >= 32-channel stages hand their
  *                        intermediate over activated with zero tails, and the second conv stages its windows by LDS-DMA
  *   wino8 (1)            read at dissc_gen_create: 1 = the ResBlock convs selected by wino8_mask run on conv_wino8.hip's
@@ -249,7 +255,10 @@ int dissc_conv_bench(int B, int Cin, int Cout, int k, int dilation, int L, int e
  *   y = x + conv_1(lrelu(conv_d(lrelu(x))))          (reference sr/models.py:34-41; `epi` 1 = that, 2..4 = the MRF modes on `acc`)
  * on device data x / y / acc f32 [B,C,ld] with host weights [C,C,k] + biases [C], through a chosen implementation:
  * mode 0 = two direct conv launches, 1 = the fused direct pair (C = 16 / 32), 2 = two transform-domain launches
- * (conv_wino), 3 = the fused transform-domain pair (respair_wino: C = 32 with k = 7 / 11, C = 64 with k = 3).
+ * (conv_wino), 3 = the fused transform-domain pair (C = 16 with k = 11, C = 32 with k = 7 / 11, C = 64 with k = 3 / 7 / 11, in
+ * the form dissc_pair_info reports under the current options), 4 = two transform-domain launches in the forms the generator's
+ * plan gives the shape under the current options when it does not fuse the pair (F(4,3) on conv_wino, F(6,3) or F(5,4) on
+ * conv_wino8, per conv).
  * y must not alias x.  dissc_respair1d synchronises the stream; dissc_pair_bench times `iters` launches on synthetic data. */
 int dissc_respair1d(const float* x, const float* w1_host, const float* b1_host, const float* w2_host, const float* b2_host,
                     float* y, float* acc, const int32_t* lengths, int B, int C, int k, int dilation, int ld, int Lmax,

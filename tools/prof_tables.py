@@ -25,9 +25,10 @@ RK = [3, 7, 11]
 DIL = [1, 3, 5]
 PAIR_MAX_C = 32
 PAIR_F23_C64 = 1  # option "pair_f23_c64": the k = 3 pairs of the 64-channel stage are one launch each (respair64_f23_kernel)
+PAIR_TC6_C64 = 1  # option "pair_tc6_c64" (--pair-tc6-c64): bit 1 its k = 7, bit 2 its k = 11 pairs are one launch each (respair64_tc6_kernel)
 
 
-def gen_layers():
+def gen_layers(pair_tc6_c64=PAIR_TC6_C64):
     """(name, flops, algorithmic bytes) of every dissc:: launch of one generator forward, in launch order."""
     f4 = 4.0
     out = [("embed_concat", 0.0, B * 257 * T * f4)]
@@ -45,7 +46,8 @@ def gen_layers():
             for m, d in enumerate(DIL):
                 fl = 2.0 * ch * ch * rk * L * B
                 last = m == 2
-                if ch <= PAIR_MAX_C or (PAIR_F23_C64 and ch == 64 and rk == 3):  # one launch per residual pair: read x, write y (+ MRF accumulator r/w)
+                c64_pair = ch == 64 and ((PAIR_F23_C64 and rk == 3) or (pair_tc6_c64 & {7: 1, 11: 2}.get(rk, 0)))
+                if ch <= PAIR_MAX_C or c64_pair:  # one launch per residual pair: read x, write y (+ MRF accumulator r/w)
                     out.append((f"s{i} C{ch} k{rk} d{d} pair", 2 * fl, act * (2 + (2 if last and rk != RK[0] else (1 if last else 0)))))
                 else:
                     out.append((f"s{i} C{ch} k{rk} d{d} conv1", fl, 2 * act))
@@ -124,8 +126,9 @@ def main():
     ap.add_argument("--md")
     ap.add_argument("--json")
     ap.add_argument("--skip", type=int, default=0)
+    ap.add_argument("--pair-tc6-c64", type=int, default=PAIR_TC6_C64, help="the capture's \"pair_tc6_c64\" (0: a build before the option)")
     a = ap.parse_args()
-    layers = gen_layers() if a.what == "gen" else enc_layers()
+    layers = gen_layers(a.pair_tc6_c64) if a.what == "gen" else enc_layers()
     n = len(layers)
     rows = dissc_rows(a.trace)
     dur = fold([(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows], n, a.skip)
@@ -154,9 +157,10 @@ def main():
             fx = fl * 8.0 / 11.0
         if "respair64_f23_kernel" in names[i][0]:  # k = 3, one sub-filter: 2 products per output
             fx = fl * 2.0 / 3.0
-        if "respair32_tc6_kernel" in names[i][0]:  # register-only six-point pairs: 6 products per 3 outputs and 4-tap sub-filter
+        if "respair32_tc6_kernel" in names[i][0] or "respair64_tc6_kernel" in names[i][0]:
+            # register-only six-point pairs: 6 products per 3 outputs and 4-tap sub-filter
             import re
-            k = int(re.search(r"respair32_tc6_kernel<(\d+)", names[i][0]).group(1))
+            k = int(re.search(r"respair(?:32|64)_tc6_kernel<(\d+)", names[i][0]).group(1))
             fx = fl * 2.0 * ((k + 3) // 4) / k
         if "conv_wino8_kernel" in names[i][0]:
             # the eight-point forms: 8 ceil(k / R) / (9 - R) products per output -- R = the instance's sixth template
