@@ -45,6 +45,10 @@ class DisscConvLaunch(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("family", "cfg", "bm", "bn", "rows", "p0", "np", "ntap", "pad_left")]
 
 
+class DisscWino8Plan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("mi", "ni", "wps", "r", "ns", "unit", "ot", "cpr", "gx", "gy")]
+
+
 def _load():
     path = library_path()
     if not os.path.exists(path):
@@ -114,6 +118,7 @@ def _load():
     L.dissc_pair_bench.argtypes = [i32] * 8 + [ctypes.POINTER(ctypes.c_float)]
     L.dissc_pair_info.argtypes = [i32] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2
     L.dissc_conv_info.argtypes = [i32] * 7 + [ctypes.POINTER(DisscConvLaunch), i32, ctypes.POINTER(ctypes.c_int)]
+    L.dissc_wino8_info.argtypes = [i32] * 6 + [ctypes.POINTER(DisscWino8Plan)]
     L.dissc_respair1d.argtypes = [vp] * 8 + [i32] * 6 + [ctypes.c_float, i32, ctypes.c_float, i32, vp]
     L.dissc_wav_postprocess.argtypes = [vp, vp, i32, i32, vp]
     L.dissc_pitch_stats.argtypes = [vp, vp, i32, vp, vp, vp, vp]
@@ -170,6 +175,14 @@ def conv_info(Cin, Cout, k, dilation=1, up=1, B=1, Lmax_out=1):
     check(lib.dissc_conv_info(Cin, Cout, k, dilation, up, B, Lmax_out, out, 16, ctypes.byref(n)), "dissc_conv_info")
     assert n.value <= 16
     return [{f: getattr(out[i], f) for f, _ in DisscConvLaunch._fields_} for i in range(n.value)]
+
+
+def wino8_info(C, k, dilation, R, B, Lmax):
+    """dissc_wino8_info: the conv_wino8_kernel instance and grid of the shape as F(6,3) (R = 3) or F(5,4) (R = 4) under the current
+    option defaults, as a dict (mi, ni, wps, r, ns, unit, ot, cpr, gx, gy).  Host only."""
+    out = DisscWino8Plan()
+    check(lib.dissc_wino8_info(C, k, dilation, R, B, Lmax, ctypes.byref(out)), "dissc_wino8_info")
+    return {f: getattr(out, f) for f, _ in DisscWino8Plan._fields_}
 
 
 def get_option(key):

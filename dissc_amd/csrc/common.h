@@ -354,6 +354,12 @@ double wino8_executed_macs_per_t(int C, int KS, int R);
 int run_wino8(const DevConv& dc, const float* x, float* out, const float* res, float* acc, const int32_t* lengths,
               int len_default, int len_mul, int B, int ldx, int ldo, int Lmax, float slope, int epi, float mrf_div,
               hipStream_t stream);
+// the instance and grid run_wino8 launches for (C, k, d, R-tap sub-filters) on B utterances of at most Lmax columns under the current
+// options (host only; dissc_wino8_info reports it): tile = (32 MI) rows x (32 NI) columns built for WPS waves per SIMD, `unit` =
+// Wino8Geo's MO D outputs per transform unit and phase group, OT outputs per tile, CPR channels per staging round, gx time tiles of
+// the longest utterance, gy row tiles; `inst` indexes conv_wino8.hip's instance table
+struct Wino8Plan { int inst, R, NS, MI, NI, WPS, unit, OT, CPR, gx, gy; };
+int wino8_plan(int C, int KS, int dil, int R, int B, int Lmax, Wino8Plan& p);
 
 // one residual pair per launch with BOTH convs in the Toom-Cook transform domain, t kept in LDS (respair_wino.hip)
 struct DevPairW {

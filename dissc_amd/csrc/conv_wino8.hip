@@ -39,7 +39,7 @@ namespace dissc {
 // option "kernel_dbg": diagnostics: knock-outs, bit 0 transform, 1 MFMAs, 2 epilogue
 // option "wino8_c64_wide" (default 3): C = 64 instances: 1 = 64 x 128 tiles (768 outputs), 0 = 64 x 64, 2 = 64 x 64 built for TWO
                            // workgroups per CU (<= 128 registers, <= 80 KB LDS: their phases overlap; +3-9 % on k = 11, mixed on
-                           // k = 7 as F(6,3), +2-8 % on k = 7 as F(5,4)), 3 (default) = 1 for k = 7 as F(6,3), 2 otherwise (run_wino8)
+                           // k = 7 as F(6,3), +2-8 % on k = 7 as F(5,4)), 3 (default) = 1 for k = 7 as F(6,3), 2 otherwise (wino8_plan)
 
 struct Wino8Args {
   const float* x;
@@ -615,7 +615,7 @@ __global__ void __launch_bounds__(512, (NI == 1 ? 2 : WPS)) conv_wino8_kernel(co
 // host side
 // ---------------------------------------------------------------------------------------------
 bool wino8_supported(int Cout, int Cin, int KS, int dil) {
-  if (KS == 3 && !DISSC_EXPERIMENTAL && !(Cout == 64 && dil == 1)) return false;  // (see run_wino8)
+  if (KS == 3 && !DISSC_EXPERIMENTAL && !(Cout == 64 && dil == 1)) return false;  // (see wino8_plan)
   return Cout == Cin && (Cout == 64 || Cout == 128 || Cout == 256 || Cout == 512) && (KS == 3 || KS == 7 || KS == 11) &&
          (dil == 1 || dil == 3 || dil == 5);
 }
@@ -651,26 +651,123 @@ int make_wino8(const float* w, const float* bias, int C, int KS, int dil, DevCon
 double wino8_executed_macs_per_t(int C, int KS, int R) { return (double)C * C * 8.0 * ((KS + R - 1) / R) / (9.0 - R); }
 
 template <int NS, int DIL, int MI, int NI, int WPS = 2, int R = 3>
-static int launch_wino8_t(const Wino8Args& a, int B, int Lmax, hipStream_t stream) {
+static int launch_wino8_t(const Wino8Args& a, hipStream_t stream) {  // a.gx, a.gy, a.B: wino8_plan's
   using G = Wino8Geo<NS, DIL, MI, NI, WPS, R>;
   static DeviceOnce attr_once;  // per device (common.h)
   DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&conv_wino8_kernel<NS, DIL, MI, NI, WPS, R>), 160 * 1024));
-  Wino8Args aa = a;
-  aa.gx = (Lmax + G::OT - 1) / G::OT;
-  aa.gy = a.C / (32 * MI);
-  aa.B = B;
-  if (aa.gy < 1 || 8 % aa.gy != 0) {
-    set_error("launch_wino8: %d row tiles do not divide the 8 XCDs", aa.gy);
-    return DISSC_EINVAL;
-  }
-  const int per = 8 / aa.gy;
-  dim3 grid(8 * ((aa.gx * B + per - 1) / per));
-  if (a.C % G::CPR != 0) {
-    set_error("launch_wino8: %d channels are not a multiple of the %d a round stages", a.C, G::CPR);
-    return DISSC_EINVAL;
-  }
-  hipLaunchKernelGGL((conv_wino8_kernel<NS, DIL, MI, NI, WPS, R>), grid, dim3(512), (size_t)G::LDS_FLOATS * sizeof(float), stream, aa);
+  const int per = 8 / a.gy;
+  dim3 grid(8 * ((a.gx * a.B + per - 1) / per));
+  hipLaunchKernelGGL((conv_wino8_kernel<NS, DIL, MI, NI, WPS, R>), grid, dim3(512), (size_t)G::LDS_FLOATS * sizeof(float), stream, a);
   DISSC_HIP_CHECK(hipGetLastError());
+  return DISSC_OK;
+}
+
+// The instances the library carries: the geometry of each comes from its own Wino8Geo, the launch is its own launch_wino8_t.
+// wino8_plan (and through it run_wino8 and dissc_wino8_info) reads widths and channel rounds from this table alone.
+struct Wino8Inst {
+  int R, NS, dil, MI, NI, WPS;
+  int unit, OT, CPR;  // Wino8Geo's MO * D, OT, CPR
+  int (*launch)(const Wino8Args&, hipStream_t);
+};
+#define DISSC_W8_INST(R_, NS_, D_, MI_, NI_, WPS_)                                                                   \
+  {R_, NS_, D_, MI_, NI_, WPS_, Wino8Geo<NS_, D_, MI_, NI_, WPS_, R_>::MO * Wino8Geo<NS_, D_, MI_, NI_, WPS_, R_>::D, \
+   Wino8Geo<NS_, D_, MI_, NI_, WPS_, R_>::OT, Wino8Geo<NS_, D_, MI_, NI_, WPS_, R_>::CPR,                             \
+   &launch_wino8_t<NS_, D_, MI_, NI_, WPS_, R_>}
+// the six tiles (MI, NI, WPS) of a transform shape: the four tiers of C >= 128, and (2, 1, 4) with the three "wino8_c64_wide" tiles of C = 64
+#define DISSC_W8_SHAPE(R_, NS_, D_)                                                                                    \
+  DISSC_W8_INST(R_, NS_, D_, 1, 1, 4), DISSC_W8_INST(R_, NS_, D_, 2, 1, 4), DISSC_W8_INST(R_, NS_, D_, 2, 2, 4),       \
+  DISSC_W8_INST(R_, NS_, D_, 4, 2, 2), DISSC_W8_INST(R_, NS_, D_, 2, 4, 2), DISSC_W8_INST(R_, NS_, D_, 2, 2, 2)
+static const Wino8Inst kW8Inst[] = {
+#if DISSC_EXPERIMENTAL  // k = 3 through this kernel: only the C = 64, d = 1 shape on two-per-CU tiles is a default (wino8_mask); the rest
+    DISSC_W8_SHAPE(3, 1, 1), DISSC_W8_SHAPE(3, 1, 3), DISSC_W8_SHAPE(3, 1, 5),  // measured neutral and is only in DISSC_EXPERIMENTAL=1 builds
+#else
+    DISSC_W8_INST(3, 1, 1, 2, 2, 4),  // the default build carries ONE k = 3 instance (wino8_plan)
+#endif
+    DISSC_W8_SHAPE(3, 3, 1), DISSC_W8_SHAPE(3, 3, 3), DISSC_W8_SHAPE(3, 3, 5),
+    DISSC_W8_SHAPE(3, 4, 1), DISSC_W8_SHAPE(3, 4, 3), DISSC_W8_SHAPE(3, 4, 5),
+    DISSC_W8_SHAPE(4, 2, 1), DISSC_W8_SHAPE(4, 2, 3), DISSC_W8_SHAPE(4, 2, 5),
+    DISSC_W8_SHAPE(4, 3, 1), DISSC_W8_SHAPE(4, 3, 3), DISSC_W8_SHAPE(4, 3, 5)};
+#undef DISSC_W8_SHAPE
+#undef DISSC_W8_INST
+
+static int w8_find(int R, int ns, int dil, int MI, int NI, int WPS) {
+  for (int i = 0; i < (int)(sizeof(kW8Inst) / sizeof(kW8Inst[0])); ++i) {
+    const Wino8Inst& t = kW8Inst[i];
+    if (t.R == R && t.NS == ns && t.dil == dil && t.MI == MI && t.NI == NI && t.WPS == WPS) return i;
+  }
+  return -1;
+}
+
+// The tile a launch runs on, from (C, k, d, form, B, Lmax) and the options "small_grid" / "wino8_c64_wide": host only, the one
+// place that chooses (run_wino8 launches what this returns; dissc_wino8_info reports it).
+//
+// wave tile = workgroup tile: 128 rows x 64 columns for C >= 128, 64 x 128 ("wino8_c64_wide", default) or 64 x 64 for C = 64.
+// C = 64 (measured per shape, tools/wino8_c64.py): k = 7 as F(6,3) on 64 x 128 tiles, everything else -- k = 11, and k = 7 as
+// F(5,4) -- on 64 x 64 tiles built for two workgroups per CU (4 = the round's earlier policy: k = 7 wide in both forms).
+// Small grids (a short or single utterance: the reference's one-at-a-time mode): the 128-row tiles of C >= 128 give a 10 s utterance
+// 16-32 workgroups on 256 CUs, each walking the whole K loop (B = 1: 240 us per k = 11 launch of the first stage); below one
+// workgroup per two CUs (128 of the 128-row tiles) the launch steps down to 64-row tiles on two workgroups per CU.  Same column
+// tiles (NI), so the same unit grid and the same MFMA and transform sequence per output: bit-identical, an utterance's samples stay
+// independent of its batch.
+// ... below one workgroup per four CUs (64) to 64 rows x 32 columns (NI = 1), below one per eight (32) to 32 x 32: every tile still
+// starts on a multiple of the unit width MO D, so the global unit grid -- and with it every output's arithmetic -- is unchanged
+// (tests/test_gpu_wino8_tiles.py holds every tile of a shape to the same bits).
+// B = 1 x 10 s (tools/batch_scaling.py): 3.78 ms (128-row tiles only) -> 3.35 -> 2.60 (NI = 1) -> see NOTES round 6.
+// The ladder never steps below the tile whose row tiles number 8 (gy = C / (32 MI) must divide the 8 XCDs the row tiles are pinned
+// to): C = 512 stops at MI = 2 -- (2, 1, 4) where C = 128 / 256 take (1, 1, 4); the same NI, so the same bits.
+// C = 64: below 192 of the 64 x 64 tiles, 64 rows x 32 columns.
+// k = 3: the default build carries ONE instance -- C = 64, d = 1 on the two-per-CU tiles: "wino8_c64_wide" does not apply to it,
+// a handle created under another tile mode runs this instance instead of failing every forward; no small-grid tier
+// (36 us at B = 1).  DISSC_EXPERIMENTAL=1 builds carry the k = 3 shapes in every tile and plan them like the others.
+int wino8_plan(int C, int KS, int dil, int R, int B, int Lmax, Wino8Plan& p) {
+  if (B <= 0 || Lmax <= 0 || (R != 3 && R != 4) || !wino8_supported(C, C, KS, dil) || (R == 4 && !wino8_r4_supported(C, KS, dil))) {
+    set_error("wino8_plan: no instance (B %d, Lmax %d, C %d, k %d, d %d, %d-tap sub-filters)", B, Lmax, C, KS, dil, R);
+    return DISSC_EINVAL;
+  }
+  const int ns = (KS + R - 1) / R;
+  const int wide = opts().wino8_c64_wide;
+  const int c64_mode = wide == 3 ? ((KS == 7 && R == 3) ? 1 : 2) : wide == 4 ? (KS == 7 ? 1 : 2) : wide;
+  const bool sg = opts().small_grid != 0;
+  auto tiles_of = [&](int MI, int NI, int WPS, int rows) -> long long {  // workgroups the launch would have on that tile
+    const int i = w8_find(R, ns, dil, MI, NI, WPS);
+    if (i < 0) return -1;
+    return (long long)((Lmax + kW8Inst[i].OT - 1) / kW8Inst[i].OT) * (C / rows) * B;
+  };
+  int MI, NI, WPS;
+  if (ns == 1 && !DISSC_EXPERIMENTAL) {
+    MI = 2; NI = 2; WPS = 4;
+  } else if (C >= 128) {
+    const long long nwg = tiles_of(4, 2, 2, 128);
+    if (sg && nwg >= 0 && nwg < 32) { MI = C / 32 > 8 ? 2 : 1; NI = 1; WPS = 4; }
+    else if (sg && nwg >= 0 && nwg < 64) { MI = 2; NI = 1; WPS = 4; }
+    else if (sg && nwg >= 0 && nwg < 128) { MI = 2; NI = 2; WPS = 4; }
+    else { MI = 4; NI = 2; WPS = 2; }
+  } else {
+    const long long nwg = tiles_of(2, 2, 4, 64);
+    if (sg && nwg >= 0 && nwg < 192) { MI = 2; NI = 1; WPS = 4; }
+    else if (c64_mode == 1) { MI = 2; NI = 4; WPS = 2; }
+    else if (c64_mode == 2) { MI = 2; NI = 2; WPS = 4; }
+    else { MI = 2; NI = 2; WPS = 2; }
+  }
+  const int i = w8_find(R, ns, dil, MI, NI, WPS);
+  if (i < 0) {
+    set_error("wino8_plan: no %d x %d tile (%d waves per SIMD) for k = %d, dilation %d, %d-tap sub-filters", 32 * MI, 32 * NI, WPS, KS, dil, R);
+    return DISSC_EINVAL;
+  }
+  const Wino8Inst& t = kW8Inst[i];
+  p.inst = i;
+  p.R = R; p.NS = ns; p.MI = MI; p.NI = NI; p.WPS = WPS;
+  p.unit = t.unit; p.OT = t.OT; p.CPR = t.CPR;
+  p.gx = (Lmax + t.OT - 1) / t.OT;
+  p.gy = C / (32 * MI);
+  if (p.gy < 1 || 8 % p.gy != 0) {
+    set_error("wino8_plan: %d row tiles do not divide the 8 XCDs", p.gy);
+    return DISSC_EINVAL;
+  }
+  if (C % t.CPR != 0) {
+    set_error("wino8_plan: %d channels are not a multiple of the %d a round stages", C, t.CPR);
+    return DISSC_EINVAL;
+  }
   return DISSC_OK;
 }
 
@@ -689,60 +786,11 @@ int run_wino8(const DevConv& dc, const float* x, float* out, const float* res, f
     set_error("run_wino8: rows must be 16-byte aligned (ldx %d, ldo %d: multiples of 4 floats, ldx >= 4)", ldx, ldo);
     return DISSC_EINVAL;
   }
-  if (B <= 0 || Lmax <= 0 || !wino8_supported(dc.M, dc.M, dc.KS, dc.dil)) {
-    set_error("run_wino8: unsupported call (B %d, Lmax %d, C %d, k %d, d %d)", B, Lmax, dc.M, dc.KS, dc.dil);
-    return DISSC_EINVAL;
-  }
-  const int R = dc.wr == 4 ? 4 : 3;
-  const int ns = (dc.KS + R - 1) / R;
-  // C = 64 (measured per shape, tools/wino8_c64.py): k = 7 as F(6,3) on 64 x 128 tiles, everything else -- k = 11, and k = 7 as
-  // F(5,4) -- on 64 x 64 tiles built for two workgroups per CU (4 = the round's earlier policy: k = 7 wide in both forms)
-  const int c64_mode = opts().wino8_c64_wide == 3 ? ((dc.KS == 7 && R == 3) ? 1 : 2) : opts().wino8_c64_wide == 4 ? (dc.KS == 7 ? 1 : 2) : opts().wino8_c64_wide;
-  // wave tile = workgroup tile: 128 rows x 64 columns for C >= 128, 64 x 128 ("wino8_c64_wide", default) or 64 x 64 for C = 64
-  // Small grids (a short or single utterance: the reference's one-at-a-time mode): the 128-row tiles of C >= 128 give a 10 s utterance
-  // 16-32 workgroups on 256 CUs, each walking the whole K loop (B = 1: 240 us per k = 11 launch of the first stage); below one
-  // workgroup per two CUs the launch steps down to 64-row tiles on two workgroups per CU.  Same column tiles (NI), so the same unit
-  // grid and the same MFMA and transform sequence per output: bit-identical, an utterance's samples stay independent of its batch.
-#define DISSC_W8_NWG(R_, NS_, D_) \
-  ((long long)((Lmax + Wino8Geo<NS_, D_, 4, 2, 2, R_>::OT - 1) / Wino8Geo<NS_, D_, 4, 2, 2, R_>::OT) * (dc.M / 128) * B)
-  // ... below one workgroup per four CUs to 64 rows x 32 columns (NI = 1), below one per eight to 32 x 32: every tile still starts
-  // on a multiple of the unit width MO D, so the global unit grid -- and with it every output's arithmetic -- is unchanged.
-  // B = 1 x 10 s (tools/batch_scaling.py): 3.78 ms (128-row tiles only) -> 3.35 -> 2.60 (NI = 1) -> see NOTES round 6.
-#define DISSC_W8_NWG64(R_, NS_, D_) \
-  ((long long)((Lmax + Wino8Geo<NS_, D_, 2, 2, 4, R_>::OT - 1) / Wino8Geo<NS_, D_, 2, 2, 4, R_>::OT) * (dc.M / 64) * B)
-#define DISSC_W8(R_, NS_, D_)                                                                        \
-  if (R == R_ && ns == NS_ && dc.dil == D_)                                                          \
-    return dc.M >= 128 ? ((opts().small_grid && DISSC_W8_NWG(R_, NS_, D_) < 32)                      \
-                              ? launch_wino8_t<NS_, D_, 1, 1, 4, R_>(a, B, Lmax, stream)             \
-                          : (opts().small_grid && DISSC_W8_NWG(R_, NS_, D_) < 64)                    \
-                              ? launch_wino8_t<NS_, D_, 2, 1, 4, R_>(a, B, Lmax, stream)             \
-                          : (opts().small_grid && DISSC_W8_NWG(R_, NS_, D_) < 128)                   \
-                              ? launch_wino8_t<NS_, D_, 2, 2, 4, R_>(a, B, Lmax, stream)             \
-                              : launch_wino8_t<NS_, D_, 4, 2, 2, R_>(a, B, Lmax, stream))            \
-                       : (opts().small_grid && DISSC_W8_NWG64(R_, NS_, D_) < 192)                     \
-                          ? launch_wino8_t<NS_, D_, 2, 1, 4, R_>(a, B, Lmax, stream)                 \
-                       : (c64_mode == 1 ? launch_wino8_t<NS_, D_, 2, 4, 2, R_>(a, B, Lmax, stream)  \
-                          : c64_mode == 2 ? launch_wino8_t<NS_, D_, 2, 2, 4, R_>(a, B, Lmax, stream) \
-                                          : launch_wino8_t<NS_, D_, 2, 2, 2, R_>(a, B, Lmax, stream));
-#if DISSC_EXPERIMENTAL  // k = 3 through this kernel: only the C = 64, d = 1 shape on two-per-CU tiles is a default (wino8_mask); the rest
-  DISSC_W8(3, 1, 1) DISSC_W8(3, 1, 3) DISSC_W8(3, 1, 5)  // measured neutral and is only in DISSC_EXPERIMENTAL=1 builds
-#else
-  // (the default build carries ONE k = 3 instance -- C = 64, d = 1 on the two-per-CU tiles: "wino8_c64_wide" does not apply to it,
-  //  a handle created under another tile mode runs this instance instead of failing every forward: ADVICE r05)
-  if (R == 3 && ns == 1 && dc.dil == 1 && dc.M == 64) return launch_wino8_t<1, 1, 2, 2, 4, 3>(a, B, Lmax, stream);  // (no small-grid tier: 36 us at B = 1)
-  if (R == 3 && ns == 1) {
-    set_error("run_wino8: k = 3 with C = %d, dilation %d, tile mode %d is only in DISSC_EXPERIMENTAL=1 builds", dc.M, dc.dil, c64_mode);
-    return DISSC_EINVAL;
-  }
-#endif
-  DISSC_W8(3, 3, 1) DISSC_W8(3, 3, 3) DISSC_W8(3, 3, 5)
-  DISSC_W8(3, 4, 1) DISSC_W8(3, 4, 3) DISSC_W8(3, 4, 5)
-  DISSC_W8(4, 2, 1) DISSC_W8(4, 2, 3) DISSC_W8(4, 2, 5) DISSC_W8(4, 3, 1) DISSC_W8(4, 3, 3) DISSC_W8(4, 3, 5)
-#undef DISSC_W8
-#undef DISSC_W8_NWG
-#undef DISSC_W8_NWG64
-  set_error("run_wino8: k = %d, dilation %d unsupported", dc.KS, dc.dil);
-  return DISSC_EINVAL;
+  Wino8Plan p;
+  const int rc = wino8_plan(dc.M, dc.KS, dc.dil, dc.wr == 4 ? 4 : 3, B, Lmax, p);
+  if (rc) return rc;
+  a.gx = p.gx; a.gy = p.gy; a.B = B;
+  return kW8Inst[p.inst].launch(a, stream);
 }
 
 }  // namespace dissc

@@ -318,7 +318,7 @@ static inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; 
 extern "C" {
 
 const char* dissc_last_error(void) { return g_err; }
-int dissc_abi_version(void) { return 6; }
+int dissc_abi_version(void) { return 7; }
 
 int dissc_device_count(void) {
   int n = 0;
@@ -985,6 +985,20 @@ int dissc_conv_info(int Cin, int Cout, int k, int dilation, int up, int B, int L
     ++n;
   }
   if (n_out) *n_out = n;
+  return DISSC_OK;
+}
+
+// Diagnostics: the conv_wino8_kernel instance and grid a k = 7 / 11 (or the k = 3) conv of C channels launches as F(6,3) (R = 3) or
+// F(5,4) (R = 4) on a batch of B utterances of at most Lmax columns, under the current option defaults: wino8_plan, which
+// run_wino8 launches from.  Host only: no HIP call.
+int dissc_wino8_info(int C, int k, int dilation, int R, int B, int Lmax, DisscWino8Plan* out) {
+  Wino8Plan p;
+  const int rc = wino8_plan(C, k, dilation, R, B, Lmax, p);
+  if (rc) return rc;
+  if (out) {
+    out->mi = p.MI; out->ni = p.NI; out->wps = p.WPS; out->r = p.R; out->ns = p.NS;
+    out->unit = p.unit; out->ot = p.OT; out->cpr = p.CPR; out->gx = p.gx; out->gy = p.gy;
+  }
   return DISSC_OK;
 }
 

@@ -48,7 +48,7 @@ typedef struct {
 
 const char* dissc_last_error(void);
 /* ABI version of this header: bumped when a signature changes or a section is added (5: dissc_convgrad_*;
- * 6: dissc_conv_info, and dissc_get_option reads the tile-shape keys). */
+ * 6: dissc_conv_info, and dissc_get_option reads the tile-shape keys; 7: dissc_wino8_info). */
 int dissc_abi_version(void);
 /* Number of HIP devices visible / name of device `dev` (for diagnostics). */
 int dissc_device_count(void);
@@ -284,6 +284,19 @@ typedef struct {
 } DisscConvLaunch;
 int dissc_conv_info(int Cin, int Cout, int k, int dilation, int up, int B, int Lmax_out, DisscConvLaunch* out, int max_out,
                     int* n_out);
+
+/* The conv_wino8_kernel instance and grid that a C -> C conv of k taps and `dilation` launches in its eight-point Toom-Cook form
+ * -- R = 3: F(6,3), R = 4: F(5,4) -- on a batch of B utterances of at most Lmax columns, under the current option defaults
+ * ("small_grid", "wino8_c64_wide"): the tile of (32 mi) rows x (32 ni) columns built for `wps` waves per SIMD, ns = ceil(k / r)
+ * sub-filters, `unit` = (9 - r) dilation ns outputs per transform unit, `ot` outputs per tile (a multiple of unit), `cpr` input
+ * channels staged per round, gx = ceil(Lmax / ot) time tiles of the longest utterance and gy = C / (32 mi) row tiles (a divisor of
+ * 8).  The answer is the launch path's own plan, the widths those of the instance itself.  DISSC_EINVAL for a shape without an
+ * instance.  Host only: no GPU is touched. */
+typedef struct {
+  int32_t mi, ni, wps, r, ns;
+  int32_t unit, ot, cpr, gx, gy;
+} DisscWino8Plan;
+int dissc_wino8_info(int C, int k, int dilation, int R, int B, int Lmax, DisscWino8Plan* out);
 
 /* ------------------------------------------------------------------------- *
  * Length / pitch predictors and infer.py's integer sample logic.
