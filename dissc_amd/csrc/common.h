@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -82,12 +83,24 @@ struct Options {
 extern Options g_defaults;
 extern thread_local const Options* t_opts;  // the snapshot of the handle this thread is working for, or nullptr
 inline const Options& opts() { return t_opts ? *t_opts : g_defaults; }
+extern int g_graph_hits, g_graph_captures;  // hipGraph replay of experimental builds (generator.hip): diagnostics of dissc_get_option
 struct OptScope {
   const Options* prev;
   explicit OptScope(const Options* o) : prev(t_opts) { t_opts = o; }
   ~OptScope() { t_opts = prev; }
   OptScope(const OptScope&) = delete;
   OptScope& operator=(const OptScope&) = delete;
+};
+
+extern thread_local int g_conv_prec;   // precision make_conv packs for: opts().precision inside dissc_gen_create, 2 inside a
+                          // split-bf16 dissc_hubert_create_ex (the layers enc_bf3_supported takes), else 0 (the "precision" option
+                          // never reaches predictors or HuBERT: they feed integer decisions; HuBERT has "enc_precision")
+struct PrecScope {  // what this thread packs for, for the life of the scope (the workers of a packing pool take their creator's)
+  const int prev;
+  explicit PrecScope(int p) : prev(g_conv_prec) { g_conv_prec = p; }
+  ~PrecScope() { g_conv_prec = prev; }
+  PrecScope(const PrecScope&) = delete;
+  PrecScope& operator=(const PrecScope&) = delete;
 };
 
 #define DISSC_HIP_CHECK(expr)                                                       \
@@ -270,9 +283,6 @@ void pack_conv_weights_bf3(const float* w, int Cout, int Cin, int KS, std::vecto
                            int& Mpad, int& nchunk);
 int launch_conv_bf3(const ConvArgs& a, int B, int Lmax_out, hipStream_t stream);
 int conv_bf3_tile_bn(int M);
-extern thread_local int g_conv_prec;   // precision make_conv packs for: opts().precision inside dissc_gen_create, 2 inside a
-                          // split-bf16 dissc_hubert_create_ex (the layers enc_bf3_supported takes), else 0 (the "precision" option
-                          // never reaches predictors or HuBERT: they feed integer decisions; HuBERT has "enc_precision")
 // the encoder's split-bf16 kernel (enc_bf3.hip): 1x1 convs and stride-2 VALID convs with k = 2 / 3; weights packed by
 // pack_conv_weights_bf3
 bool enc_bf3_supported(int Cout, int Cin, int KS, int dil, int groups, int stride, int pad_left);
@@ -305,13 +315,38 @@ struct DevConv {
   int wino = 0;           // 1: packed for conv_wino_kernel (Toom-Cook F(4,3) transform-domain weights), 2: for conv_wino8_kernel
   int wr = 3;             // conv_wino8_kernel: taps per sub-filter (3: F(6,3), 4: F(5,4))
 };
-// Per-call extras of run_conv_ex (strided / valid convolutions with their own output lengths).
-struct ConvIO {
-  const int32_t* lengths_in = nullptr;
-  const int32_t* lengths_out = nullptr;
-  int len_default = 0, olen_default = -1, len_mul = 1;
+// Who is how long, for one launch (or a stage's worth of them): utterance b has lengths[b] * len_mul input columns (len_default
+// where lengths is null); Lmax, in OUTPUT columns, sizes the grid.  Strided / valid convolutions give their output lengths too.
+struct Batch {
+  const int32_t* lengths = nullptr;
+  int len_default = 0, len_mul = 1, B = 0, Lmax = 0;
+  const int32_t* lengths_out = nullptr;  // [B] valid OUTPUT positions; nullptr = same as input
+  int olen_default = -1;                 // used when lengths_out == nullptr and >= 0
 };
+// the common case: "same" layers on rows of at most Lmax columns
+inline Batch batch_of(const int32_t* lengths, int len_mul, int B, int Lmax) {
+  Batch bt;
+  bt.lengths = lengths; bt.len_default = bt.Lmax = Lmax; bt.len_mul = len_mul; bt.B = B;
+  return bt;
+}
+// What happens to the result of a launch (Epi): the residual and MRF accumulator it reads, the divisor of EPI_MRF_DIV, the slope
+// of EPI_STORE_ACT.  The fused pairs take their residual from x and ignore `res`.
+struct EpiSpec {
+  int epi = EPI_STORE;
+  const float* res = nullptr;
+  float* acc = nullptr;
+  float mrf_div = 1.f, out_slope = 0.f;
+};
+inline EpiSpec epi_of(int epi, const float* res = nullptr, float* acc = nullptr, float mrf_div = 1.f) {
+  EpiSpec ep;
+  ep.epi = epi; ep.res = res; ep.acc = acc; ep.mrf_div = mrf_div;
+  return ep;
+}
 int upload(const std::vector<float>& h, float** d);
+// Host-side packing in parallel (pack_pool.hip): runs the tasks on at most nthr host threads (the caller's included) on the caller's
+// device, each under an OptScope of `opt` and a PrecScope of `prec`; the first error's code, its message in set_error.
+int pack_thread_count();  // min(8, CPUs this process may use / LOCAL_WORLD_SIZE), or a valid DISSC_PACK_THREADS
+int run_pack_tasks(const std::vector<std::function<int()>>& tasks, int nthr, const Options& opt, int prec);
 // host-only planning shared by the packers, the launch path and dissc_conv_info (conv_host.hip)
 int conv_m32_rule(int Mg, int groups);  // 1: the layer is packed for / launched on the 32x32x2 kernel
 void conv_geometry(DevConv& dc, int Cout, int Cin, int KS, int dil, int groups, int stride, int pad_left);
@@ -326,24 +361,15 @@ int make_convT(const float* w, const float* bias, int Cin, int Cout, int k, int 
                std::vector<DevConv>& groups);
 int set_affine(DevConv& dc, const float* scale, const float* shift, int n);  // host pointers
 void free_conv(DevConv& dc);
-// dispatches on dc.wino: the transform-domain layers run through run_wino / run_wino8
-int run_conv(const DevConv& dc, const float* x, float* out, const float* res, float* acc,
-             const int32_t* lengths, int len_default, int len_mul, int B, int C_x, int ldx, int ldo,
-             int Lmax, float slope, int epi, float mrf_div, hipStream_t stream, float out_slope = 0.f, int dma_in = 0);
-
-int run_conv_ex(const DevConv& dc, const float* x, float* out, const float* res, const ConvIO& io,
-                int B, int C_x_total, int ldx, int ldo, int Lmax_out, float slope, int epi,
-                hipStream_t stream);
-int run_conv_ex(const DevConv& dc, const float* x, float* out, const float* res, float* acc,
-                const ConvIO& io, int B, int C_x_total, int ldx, int ldo, int Lmax_out, float slope,
-                int epi, float mrf_div, hipStream_t stream, float out_slope = 0.f, int dma_in = 0);
+// dispatches on dc.wino: the transform-domain layers run through run_wino / run_wino8.  C_x: channels of a row of x (all groups)
+int run_conv(const DevConv& dc, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int C_x, int ldx, int ldo,
+             float slope, hipStream_t stream, int dma_in = 0);
 
 // Toom-Cook F(4,3) form of the wide ResBlock convs (conv_wino.hip)
 bool wino_supported(int Cout, int Cin, int KS, int dil);
 int make_wino(const float* w, const float* bias, int C, int KS, int dil, DevConv& dc);
 double wino_executed_macs_per_t(int C, int KS);
-int run_wino(const DevConv& dc, const float* x, float* out, const float* res, float* acc, const int32_t* lengths,
-             int len_default, int len_mul, int B, int ldx, int ldo, int Lmax, float slope, int epi, float mrf_div,
+int run_wino(const DevConv& dc, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ldx, int ldo, float slope,
              hipStream_t stream);
 
 // Toom-Cook F(6,3) form on 8-wave workgroups (conv_wino8.hip): the k = 7 / 11 ResBlock convs of the C >= 64 stages
@@ -351,8 +377,7 @@ bool wino8_supported(int Cout, int Cin, int KS, int dil);
 bool wino8_r4_supported(int C, int KS, int dil);
 int make_wino8(const float* w, const float* bias, int C, int KS, int dil, DevConv& dc, int R = 3);  // sets dc.wino = 2, dc.wr = R
 double wino8_executed_macs_per_t(int C, int KS, int R);
-int run_wino8(const DevConv& dc, const float* x, float* out, const float* res, float* acc, const int32_t* lengths,
-              int len_default, int len_mul, int B, int ldx, int ldo, int Lmax, float slope, int epi, float mrf_div,
+int run_wino8(const DevConv& dc, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ldx, int ldo, float slope,
               hipStream_t stream);
 // the instance and grid run_wino8 launches for (C, k, d, R-tap sub-filters) on B utterances of at most Lmax columns under the current
 // options (host only; dissc_wino8_info reports it): tile = (32 MI) rows x (32 NI) columns built for WPS waves per SIMD, `unit` =
@@ -378,8 +403,8 @@ bool pair_tc6_supported(int C, int KS, int dil);
 // the F(4,3) form: experimental/csrc/respair_wino.hip in DISSC_EXPERIMENTAL=1 builds, experimental_stubs.hip otherwise
 bool pairw43_built();
 int pack_pairw43(const float* w, int C, int KS, float** dev);
-int launch_pairw43(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default, int len_mul,
-                   int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream);
+int launch_pairw43(const DevPairW& pw, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld, float slope,
+                   hipStream_t stream);
 bool pairw_supported(int C, int KS, int dil);
 bool pair_form_supported(int form, int C, int KS, int dil);  // whether make_pairw has an instance of that form
 int pair_reg_tile(int form, int C, int KS, int dil);         // outputs a workgroup of a register-only instance owns, or 0
@@ -387,22 +412,20 @@ int pair_reg_tile(int form, int C, int KS, int dil);         // outputs a workgr
 // (pairw_supported)
 int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, int form, DevPairW& pw);
 void free_pairw(DevPairW& pw);
-int launch_respair_wino(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
-                        int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream);
+int launch_respair_wino(const DevPairW& pw, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld, float slope,
+                        hipStream_t stream);
 
 // one residual pair y = x + conv_1(lrelu(conv_d(lrelu(x)))) per launch, exact fp32 (respair.hip)
 bool respair_supported(int C, int KS, int dil);
-int launch_respair(const DevConv& c1, const DevConv& c2, const float* x, float* out, float* acc,
-                   const int32_t* lengths, int len_default, int len_mul, int B, int Lmax, int ld, float slope,
-                   int epi, float mrf_div, hipStream_t stream);
+int launch_respair(const DevConv& c1, const DevConv& c2, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld,
+                   float slope, hipStream_t stream);
 
 // the same block in split-bf16 arithmetic ("precision" = 1 only; resblock_bf3.hip)
 bool resblock_bf3_supported(int C, int KS, const int* dil);
 void pack_resblock_bf3(int C, int KS, const float* const* w6, std::vector<float>& packed);
-// residual pairs [m0, m1) of the block; epi = EPI_STORE writes x_k to `acc` (a partial block)
-int launch_resblock_bf3(int C, const float* x, float* acc, const float* wpack, const float* bias,
-                        const int32_t* lengths, int len_default, int len_mul, int KS, const int* dil,
-                        int B, int Lmax, int ld, float slope, int epi, float mrf_div, int m0, int m1,
+struct Bf3Block { int C, KS; const int* dil; const float *wpack, *bias; };  // one block: pack_resblock_bf3's weights, the six biases
+// residual pairs [m0, m1) of the block, into ep.acc; ep.epi = EPI_STORE writes x_k there (a partial block)
+int launch_resblock_bf3(const Bf3Block& blk, const float* x, const Batch& bt, const EpiSpec& ep, int ld, float slope, int m0, int m1,
                         hipStream_t stream);
 
 // HuBERT's stride-2, k = 3 feature convs in polyphase Toom-Cook form (conv_s2tc.hip)
@@ -415,8 +438,7 @@ bool s2tc_supported(int Cout, int Cin, int KS, int stride);
 int make_s2tc(const float* w, const float* bias, int Cout, int Cin, DevS2tc& dc);
 void free_s2tc(DevS2tc& dc);
 double s2tc_executed_macs_per_out(int Cout, int Cin);
-int run_s2tc(const DevS2tc& dc, const float* x, float* out, const int32_t* lengths_in, const int32_t* lengths_out,
-             int len_default, int olen_default, int B, int ldx, int ldo, int Lmax_out, hipStream_t stream);
+int run_s2tc(const DevS2tc& dc, const float* x, float* out, const Batch& bt, int ldx, int ldo, hipStream_t stream);
 
 // misc kernels (gen_misc.hip)
 struct ZeroSpans {  // ZERO_TAIL floats at each pointer, zeroed by the forward's first kernel

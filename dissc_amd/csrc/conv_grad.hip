@@ -401,8 +401,8 @@ int dissc_convgrad_forward(dissc_convgrad_t h, const float* x, const float* add,
     return DISSC_EINVAL;
   }
   OptScope opt_scope(&h->opt);
-  return run_conv(h->fwd, x, y, add, nullptr, lengths, Lmax, 1, B, h->Cin, ldx, ldo, Lmax, in_slope,
-                  add ? EPI_RES : EPI_STORE, 1.f, (hipStream_t)stream);
+  return run_conv(h->fwd, x, y, batch_of(lengths, 1, B, Lmax), epi_of(add ? EPI_RES : EPI_STORE, add), h->Cin, ldx, ldo, in_slope,
+                  (hipStream_t)stream);
 }
 
 int dissc_convgrad_partials(dissc_convgrad_t h, int B, int Lmax, int* P, int* chunk) {
@@ -462,8 +462,7 @@ int dissc_convgrad_backward(dissc_convgrad_t h, const float* x, const float* gy,
   }
   if (gx) {
     // the same conv with W^T, taps flipped: channels swapped, gy read as zero beyond lengths
-    if ((rc = run_conv(h->bwd, gy, gx, nullptr, nullptr, lengths, Lmax, 1, B, h->Cout, ldo, ldx, Lmax, 1.0f, EPI_STORE, 1.f, st)))
-      return rc;
+    if ((rc = run_conv(h->bwd, gy, gx, batch_of(lengths, 1, B, Lmax), EpiSpec(), h->Cout, ldo, ldx, 1.0f, st))) return rc;
     hipLaunchKernelGGL(convgrad_mask_kernel, dim3((ldx / 4 + 127) / 128, h->Cin, B), dim3(128), 0, st, x, lengths, h->Cin, Lmax,
                        ldx, in_slope, gx);
   }

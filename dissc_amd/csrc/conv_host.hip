@@ -144,7 +144,6 @@ void free_conv(DevConv& dc) {
   dc.wpack = dc.wpack2 = dc.bias = dc.scale = dc.shift = nullptr;
 }
 
-
 // Tile shape id of the 32-row kernel for one launch of the layer, -1 = the class default.  General path only: the special
 // instances (split-bf16, strided, grouped, wide-tap and the big 1x1 layers) keep their tile.
 int conv_launch_cfg32(const DevConv& dc, int B, int Lmax_out) {
@@ -180,50 +179,33 @@ int conv_launch_info(const DevConv& dc, int B, int Lmax_out, int* family, int* c
   return DISSC_OK;
 }
 
-int run_conv_ex(const DevConv& dc, const float* x, float* out, const float* res, float* acc,
-                const ConvIO& io, int B, int C_x_total, int ldx, int ldo, int Lmax_out, float slope,
-                int epi, float mrf_div, hipStream_t stream, float out_slope, int dma_in) {
+int run_conv(const DevConv& dc, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int C_x, int ldx, int ldo,
+             float slope, hipStream_t stream, int dma_in) {
+  if (dc.wino) {  // transform-domain layers: no activated store (EPI_STORE_ACT, out_slope), no LDS-DMA input
+    if (ep.epi == EPI_STORE_ACT || dma_in || C_x != dc.CIN) {
+      set_error("run_conv: transform-domain layer (C = %d, k = %d): no EPI_STORE_ACT, no dma_in, C_x must be C (%d)", dc.M, dc.KS, C_x);
+      return DISSC_EINVAL;
+    }
+    return (dc.wino == 2 ? run_wino8 : run_wino)(dc, x, out, bt, ep, ldx, ldo, slope, stream);
+  }
   ConvArgs a;
-  a.out_slope = out_slope; a.dma_in = dma_in;
-  a.x = x; a.wpack = dc.wpack; a.wpack2 = dc.wpack2; a.bias = dc.bias; a.scale = dc.scale; a.shift = dc.shift; a.res = res;
-  a.out = out; a.acc = acc;
-  a.lengths = io.lengths_in; a.len_default = io.len_default; a.len_mul = io.len_mul;
-  a.lengths_out = io.lengths_out; a.olen_default = io.olen_default;
+  a.out_slope = ep.out_slope; a.dma_in = dma_in;
+  a.x = x; a.wpack = dc.wpack; a.wpack2 = dc.wpack2; a.bias = dc.bias; a.scale = dc.scale; a.shift = dc.shift; a.res = ep.res;
+  a.out = out; a.acc = ep.acc;
+  a.lengths = bt.lengths; a.len_default = bt.len_default; a.len_mul = bt.len_mul;
+  a.lengths_out = bt.lengths_out; a.olen_default = bt.olen_default;
   a.CIN = dc.CIN; a.M = dc.M; a.KS = dc.KS; a.dil = dc.dil; a.nchunk = dc.nchunk;
   a.pad_left = dc.pad_left >= 0 ? dc.pad_left : ((dc.KS - 1) * dc.dil) / 2;
   a.xcd = 0; a.xcd_ntile = 0; a.xcd_nb = 0; a.xcd_mg = 0; a.xcd_span = 0;
   a.ragged_enum = 0;
   a.groups = dc.groups; a.nsub_group = dc.Mpad / (dc.m32 ? 32 : 16); a.act = dc.act; a.m32 = dc.m32; a.prec = dc.prec;
-  a.cfg32 = conv_launch_cfg32(dc, B, Lmax_out);
+  a.cfg32 = conv_launch_cfg32(dc, bt.B, bt.Lmax);
   a.XW = conv_xw(dc.M, dc.KS, dc.dil, dc.stride, dc.m32, a.cfg32 >= 0 ? conv32_cfg_bn(a.cfg32) : 0);
   a.ldx = ldx; a.ldo = ldo;
-  a.x_bstride = (long long)C_x_total * ldx;
+  a.x_bstride = (long long)C_x * ldx;
   a.o_bstride = (long long)(dc.M * dc.groups / dc.up_np) * ldo;
-  a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.up = dc.up; a.up_np = dc.up_np; a.up_p0 = dc.up_p0;
-  return launch_conv(a, B, Lmax_out, dc.stride, stream);
-}
-
-int run_conv_ex(const DevConv& dc, const float* x, float* out, const float* res, const ConvIO& io,
-                int B, int C_x_total, int ldx, int ldo, int Lmax_out, float slope, int epi,
-                hipStream_t stream) {
-  return run_conv_ex(dc, x, out, res, nullptr, io, B, C_x_total, ldx, ldo, Lmax_out, slope, epi, 1.f,
-                     stream);
-}
-
-int run_conv(const DevConv& dc, const float* x, float* out, const float* res, float* acc,
-             const int32_t* lengths, int len_default, int len_mul, int B, int C_x, int ldx, int ldo,
-             int Lmax, float slope, int epi, float mrf_div, hipStream_t stream, float out_slope, int dma_in) {
-  if (dc.wino) {  // transform-domain layers: no activated store (EPI_STORE_ACT, out_slope), no LDS-DMA input
-    if (epi == EPI_STORE_ACT || dma_in || C_x != dc.CIN) {
-      set_error("run_conv: transform-domain layer (C = %d, k = %d): no EPI_STORE_ACT, no dma_in, C_x must be C (%d)", dc.M, dc.KS, C_x);
-      return DISSC_EINVAL;
-    }
-    return (dc.wino == 2 ? run_wino8 : run_wino)(dc, x, out, res, acc, lengths, len_default, len_mul, B, ldx, ldo, Lmax, slope, epi,
-                                                 mrf_div, stream);
-  }
-  ConvIO io;
-  io.lengths_in = lengths; io.len_default = len_default; io.len_mul = len_mul;
-  return run_conv_ex(dc, x, out, res, acc, io, B, C_x, ldx, ldo, Lmax, slope, epi, mrf_div, stream, out_slope, dma_in);
+  a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi; a.up = dc.up; a.up_np = dc.up_np; a.up_p0 = dc.up_p0;
+  return launch_conv(a, bt.B, bt.Lmax, dc.stride, stream);
 }
 
 }  // namespace dissc

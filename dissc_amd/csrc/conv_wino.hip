@@ -636,18 +636,18 @@ static int launch_wino_t(const WinoArgs& a, int B, int Lmax, hipStream_t stream)
   return launch_wino_c<NS, DIL, 16, 2, 2>(a, B, Lmax, stream);
 }
 
-int run_wino(const DevConv& dc, const float* x, float* out, const float* res, float* acc, const int32_t* lengths,
-             int len_default, int len_mul, int B, int ldx, int ldo, int Lmax, float slope, int epi, float mrf_div,
+int run_wino(const DevConv& dc, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ldx, int ldo, float slope,
              hipStream_t stream) {
+  const int B = bt.B, Lmax = bt.Lmax;
   WinoArgs a;
-  a.x = x; a.wpack = dc.wpack; a.bias = dc.bias; a.res = res; a.out = out; a.acc = acc;
-  a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul;
+  a.x = x; a.wpack = dc.wpack; a.bias = dc.bias; a.res = ep.res; a.out = out; a.acc = ep.acc;
+  a.lengths = bt.lengths; a.len_default = bt.len_default; a.len_mul = bt.len_mul;
   a.C = dc.M; a.nchunk = dc.nchunk; a.pad = (dc.KS - 1) * dc.dil / 2;
   a.ldx = ldx; a.ldo = ldo;
   a.x_bstride = (long long)dc.M * ldx; a.o_bstride = (long long)dc.M * ldo;
-  a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = opts().kernel_dbg;
+  a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi; a.dbg = opts().kernel_dbg;
   // the window staging, the residual / accumulator reads and the stores are 16-byte accesses
-  if (ldx < 4 || ldx % 4 || ldo % 4 || misaligned16(x) || misaligned16(out) || misaligned16(res) || misaligned16(acc)) {
+  if (ldx < 4 || ldx % 4 || ldo % 4 || misaligned16(x) || misaligned16(out) || misaligned16(ep.res) || misaligned16(ep.acc)) {
     set_error("run_wino: rows must be 16-byte aligned (ldx %d, ldo %d: multiples of 4 floats, ldx >= 4)", ldx, ldo);
     return DISSC_EINVAL;
   }

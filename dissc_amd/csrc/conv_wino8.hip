@@ -771,25 +771,24 @@ int wino8_plan(int C, int KS, int dil, int R, int B, int Lmax, Wino8Plan& p) {
   return DISSC_OK;
 }
 
-int run_wino8(const DevConv& dc, const float* x, float* out, const float* res, float* acc, const int32_t* lengths,
-              int len_default, int len_mul, int B, int ldx, int ldo, int Lmax, float slope, int epi, float mrf_div,
+int run_wino8(const DevConv& dc, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ldx, int ldo, float slope,
               hipStream_t stream) {
   Wino8Args a;
-  a.x = x; a.wpack = dc.wpack; a.bias = dc.bias; a.res = res; a.out = out; a.acc = acc;
-  a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul;
+  a.x = x; a.wpack = dc.wpack; a.bias = dc.bias; a.res = ep.res; a.out = out; a.acc = ep.acc;
+  a.lengths = bt.lengths; a.len_default = bt.len_default; a.len_mul = bt.len_mul;
   a.C = dc.M; a.nchunk = dc.nchunk; a.pad = (dc.KS - 1) * dc.dil / 2;
   a.ldx = ldx; a.ldo = ldo;
   a.x_bstride = (long long)dc.M * ldx; a.o_bstride = (long long)dc.M * ldo;
-  a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = opts().kernel_dbg;
+  a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi; a.dbg = opts().kernel_dbg;
   a.gx = a.gy = a.B = 0;
-  if (ldx < 4 || ldx % 4 || ldo % 4 || misaligned16(x) || misaligned16(out) || misaligned16(res) || misaligned16(acc)) {
+  if (ldx < 4 || ldx % 4 || ldo % 4 || misaligned16(x) || misaligned16(out) || misaligned16(ep.res) || misaligned16(ep.acc)) {
     set_error("run_wino8: rows must be 16-byte aligned (ldx %d, ldo %d: multiples of 4 floats, ldx >= 4)", ldx, ldo);
     return DISSC_EINVAL;
   }
   Wino8Plan p;
-  const int rc = wino8_plan(dc.M, dc.KS, dc.dil, dc.wr == 4 ? 4 : 3, B, Lmax, p);
+  const int rc = wino8_plan(dc.M, dc.KS, dc.dil, dc.wr == 4 ? 4 : 3, bt.B, bt.Lmax, p);
   if (rc) return rc;
-  a.gx = p.gx; a.gy = p.gy; a.B = B;
+  a.gx = p.gx; a.gy = p.gy; a.B = bt.B;
   return kW8Inst[p.inst].launch(a, stream);
 }
 

@@ -1,0 +1,379 @@
+// Stand-alone entry points for tests and diagnostics: one conv, one transposed conv, one residual pair per call (weights packed per
+// call), what a shape would launch, and the per-launch benchmarks.  Host only: no kernel here.
+#include <stdlib.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "gen_plan.h"
+
+using namespace dissc;
+
+namespace {
+
+// What one entry packs and allocates on the device, released on every way out: up to two convs and a one-launch pair, scratch
+// buffers, the two events of a benchmark.
+struct DiagScope {
+  DevConv c1, c2;
+  DevPairW pw;
+  DevS2tc tc;
+  std::vector<float*> bufs;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipError_t alloc(float** p, size_t n) {
+    const hipError_t e = hipMalloc((void**)p, n * sizeof(float));
+    if (e == hipSuccess) bufs.push_back(*p);
+    return e;
+  }
+  hipError_t events() {
+    const hipError_t e = hipEventCreate(&e0);
+    return e != hipSuccess ? e : hipEventCreate(&e1);
+  }
+  ~DiagScope() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    for (float* q : bufs) (void)hipFree(q);
+    free_conv(c1);
+    free_conv(c2);
+    free_pairw(pw);
+    free_s2tc(tc);
+  }
+};
+
+// the synthetic data of the benchmarks: one LCG stream per call, weights then input
+struct Lcg {
+  uint32_t s = 12345u;
+  void fill(std::vector<float>& v, float scale, float centre = 0.5f) {
+    for (auto& x : v) {
+      s = s * 1664525u + 1013904223u;
+      x = ((s >> 8) / 16777216.0f - centre) * scale;
+    }
+  }
+};
+
+// warm twice, then the average ms of `iters` launches between the scope's two events
+template <class Once>
+int time_launches(const DiagScope& d, int iters, Once once, float* ms_out) {
+  int rc = DISSC_OK;
+  for (int it = 0; it < 2 && !rc; ++it) rc = once();
+  if (rc) return rc;
+  DISSC_HIP_CHECK(hipEventRecord(d.e0, nullptr));
+  for (int it = 0; it < iters && !rc; ++it) rc = once();
+  DISSC_HIP_CHECK(hipEventRecord(d.e1, nullptr));
+  const hipError_t e = hipEventSynchronize(d.e1);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, d.e0, d.e1);
+  *ms_out = ms / iters;
+  if (rc) return rc;
+  DISSC_HIP_CHECK(e);
+  return DISSC_OK;
+}
+
+// DISSC_TIMELINE: `bytes` of a device buffer into that file
+void dump_timeline(const char* path, const float* dev, size_t bytes) {
+  std::vector<char> hb(bytes);
+  if (hipMemcpy(hb.data(), dev, hb.size(), hipMemcpyDeviceToHost) == hipSuccess)
+    if (FILE* f = fopen(path, "wb")) {
+      fwrite(hb.data(), 1, hb.size(), f);
+      fclose(f);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- stand-alone conv entry points (weights packed per call: tests only) ----------------
+// what a synchronous entry returns: its launches' code, or the error the drained stream reports
+static int drained(int rc, hipStream_t stream) {
+  const hipError_t e = hipStreamSynchronize(stream);
+  if (rc) return rc;
+  DISSC_HIP_CHECK(e);
+  return DISSC_OK;
+}
+
+static int conv_once(DevConv& dc, const float* x, float* y, const Batch& bt, int ldx, int ldo, float in_slope, hipStream_t stream) {
+  const int rc = drained(run_conv(dc, x, y, bt, EpiSpec(), dc.CIN, ldx, ldo, in_slope, stream), stream);
+  free_conv(dc);
+  return rc;
+}
+
+int dissc_conv1d(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths, int B, int Cin,
+                 int Cout, int k, int dilation, int ldx, int ldo, int Lmax, float in_slope, void* stream) {
+  if (!x || !w_host || !y || k % 2 != 1 || dilation < 1) {
+    set_error("dissc_conv1d: bad argument");
+    return DISSC_EINVAL;
+  }
+  // "wino" / "wino8" / "wino8_r4" = 2: this entry takes the transform-domain forms too (tests)
+  DevConv dc;
+  int rc;
+  if (opts().wino8 >= 2 && wino8_supported(Cout, Cin, k, dilation))
+    rc = make_wino8(w_host, bias_host, Cout, k, dilation, dc, opts().wino8_r4 >= 2 && wino8_r4_supported(Cout, k, dilation) ? 4 : 3);
+  else if (opts().wino >= 2 && wino_supported(Cout, Cin, k, dilation))
+    rc = make_wino(w_host, bias_host, Cout, k, dilation, dc);
+  else
+    rc = make_conv(w_host, bias_host, Cout, Cin, k, dilation, dc);
+  if (rc) return rc;
+  return conv_once(dc, x, y, batch_of(lengths, 1, B, Lmax), ldx, ldo, in_slope, (hipStream_t)stream);
+}
+
+// Diagnostics / tests: ONE residual pair y = x + conv_1(lrelu(conv_d(lrelu(x)))) (or its MRF modes) on device data with
+// host weights, through a chosen implementation: mode 0 = two direct conv launches, 1 = the fused direct pair
+// (respair.hip), 2 = two conv_wino launches, 3 = the fused transform-domain pair (pair_host.hip), 4 = two transform-domain
+// launches in the forms the plan gives a PairForm::td pair of the shape (td_conv_form).  Synchronous.
+static int pair_run(int mode, const DiagScope& d, const float* x, float* tmp, float* y, const Batch& bt, const EpiSpec& ep, int C,
+                    int ld, float slope, hipStream_t st) {
+  int rc;
+  switch (mode) {
+    case 0: case 2: case 4:  // two launches, t through tmp
+      if ((rc = run_conv(d.c1, x, tmp, bt, EpiSpec(), C, ld, ld, slope, st))) return rc;
+      return run_conv(d.c2, tmp, y, bt, epi_of(ep.epi, x, ep.acc, ep.mrf_div), C, ld, ld, slope, st);
+    case 1:
+      return launch_respair(d.c1, d.c2, x, y, bt, ep, ld, slope, st);
+    case 3:
+      return launch_respair_wino(d.pw, x, y, bt, ep, ld, slope, st);
+    default:
+      set_error("pair mode %d", mode);
+      return DISSC_EINVAL;
+  }
+}
+
+static int pair_make(int mode, const float* w1, const float* b1, const float* w2, const float* b2, int C, int k, int d, DiagScope& ds) {
+  DevConv &c1 = ds.c1, &c2 = ds.c2;
+  int rc;
+  if (mode == 2) {
+    if (!wino_supported(C, C, k, d) && !(C == 32 && (k == 3 || k == 7 || k == 11) && (d == 1 || d == 3 || d == 5))) {
+      set_error("pair mode 2: no conv_wino instance for C = %d, k = %d, d = %d", C, k, d);
+      return DISSC_EINVAL;
+    }
+    if ((rc = make_wino(w1, b1, C, k, d, c1))) return rc;
+    return make_wino(w2, b2, C, k, 1, c2);
+  }
+  if (mode == 3) return make_pairw(w1, b1, w2, b2, C, k, d, pair_reg_form(C, k, d), ds.pw);
+  if (mode == 4) {
+    if (!wino_supported(C, C, k, d) || !wino_supported(C, C, k, 1)) {
+      set_error("pair mode 4: no transform-domain conv instance for C = %d, k = %d, d = %d", C, k, d);
+      return DISSC_EINVAL;
+    }
+    if ((rc = make_pair_conv(td_conv_form(C, k, d), w1, b1, C, k, d, c1))) return rc;
+    return make_pair_conv(td_conv_form(C, k, 1), w2, b2, C, k, 1, c2);
+  }
+  if ((rc = make_conv(w1, b1, C, C, k, d, c1))) return rc;
+  return make_conv(w2, b2, C, C, k, 1, c2);
+}
+
+int dissc_respair1d(const float* x, const float* w1_host, const float* b1_host, const float* w2_host, const float* b2_host,
+                    float* y, float* acc, const int32_t* lengths, int B, int C, int k, int dilation, int ld, int Lmax,
+                    float slope, int epi, float mrf_div, int mode, void* stream) {
+  if (!x || !w1_host || !w2_host || !y || k % 2 != 1 || dilation < 1 || B <= 0 || epi < EPI_RES || epi > EPI_MRF_DIV ||
+      (epi != EPI_RES && !acc)) {
+    set_error("dissc_respair1d: bad argument");
+    return DISSC_EINVAL;
+  }
+  DiagScope ds;
+  float* tmp = nullptr;
+  int rc = pair_make(mode, w1_host, b1_host, w2_host, b2_host, C, k, dilation, ds);
+  if (!rc && (mode == 0 || mode == 2 || mode == 4) && ds.alloc(&tmp, (size_t)B * C * ld) != hipSuccess) {
+    set_error("dissc_respair1d: hipMalloc");
+    rc = DISSC_ENOMEM;
+  }
+  if (!rc)
+    rc = pair_run(mode, ds, x, tmp, y, batch_of(lengths, 1, B, Lmax), epi_of(epi, nullptr, acc, mrf_div), C, ld, slope, (hipStream_t)stream);
+  return drained(rc, (hipStream_t)stream);
+}
+
+// Diagnostics: the form and tile of what mode 3 of dissc_respair1d / dissc_pair_bench builds under the current option
+// defaults.  Host only: no HIP call.
+int dissc_pair_info(int C, int k, int dilation, int* form_out, int* tile_out) {
+  const int form = pair_reg_form(C, k, dilation);
+  if (!pair_form_supported(form, C, k, dilation)) {
+    set_error("dissc_pair_info: no instance for C = %d, k = %d, dilation %d", C, k, dilation);
+    return DISSC_EINVAL;
+  }
+  if (form_out) *form_out = form;
+  if (tile_out) *tile_out = pair_reg_tile(form, C, k, dilation);
+  return DISSC_OK;
+}
+
+// Diagnostics: the launches dissc_conv1d (up == 1) / dissc_conv_transpose1d (up > 1: k taps, stride up) make for a layer on a
+// batch of B utterances of at most Lmax_out columns per launch, under the current option defaults: the planning functions of
+// make_conv / make_convT / run_conv / launch_conv themselves, without packing or uploading anything.  Host only: no HIP call.
+int dissc_conv_info(int Cin, int Cout, int k, int dilation, int up, int B, int Lmax_out, DisscConvLaunch* out, int max_out,
+                    int* n_out) {
+  if (Cin < 1 || Cout < 1 || k < 1 || dilation < 1 || up < 1 || B < 1 || Lmax_out < 1 || max_out < 0 || (max_out && !out) ||
+      (up == 1 && k % 2 != 1) || (up > 1 && ((k - up) % 2 != 0 || k < up || dilation != 1))) {
+    set_error("dissc_conv_info: bad argument");
+    return DISSC_EINVAL;
+  }
+  std::vector<ConvTGroup> plan;
+  if (up > 1) convT_groups(Cout, k, up, plan);
+  else plan.push_back(ConvTGroup{0, 1, 0, k});
+  int n = 0;
+  for (const ConvTGroup& g : plan) {
+    DevConv dc;  // geometry only: nothing is uploaded, nothing to free
+    conv_geometry(dc, Cout * g.np, Cin, g.ntap, up > 1 ? 1 : dilation, 1, 1, up > 1 ? -g.dlo : -1);
+    int family, cfg, bm, bn;
+    const int rc = conv_launch_info(dc, B, Lmax_out, &family, &cfg, &bm, &bn);
+    if (rc) return rc;
+    if (n < max_out) {
+      DisscConvLaunch& o = out[n];
+      o.family = family; o.cfg = cfg; o.bm = bm; o.bn = bn; o.rows = dc.M;
+      o.p0 = g.p0; o.np = g.np; o.ntap = g.ntap;
+      o.pad_left = dc.pad_left >= 0 ? dc.pad_left : ((dc.KS - 1) * dc.dil) / 2;
+    }
+    ++n;
+  }
+  if (n_out) *n_out = n;
+  return DISSC_OK;
+}
+
+// Diagnostics: the conv_wino8_kernel instance and grid a k = 7 / 11 (or the k = 3) conv of C channels launches as F(6,3) (R = 3) or
+// F(5,4) (R = 4) on a batch of B utterances of at most Lmax columns, under the current option defaults: wino8_plan, which
+// run_wino8 launches from.  Host only: no HIP call.
+int dissc_wino8_info(int C, int k, int dilation, int R, int B, int Lmax, DisscWino8Plan* out) {
+  Wino8Plan p;
+  const int rc = wino8_plan(C, k, dilation, R, B, Lmax, p);
+  if (rc) return rc;
+  if (out) {
+    out->mi = p.MI; out->ni = p.NI; out->wps = p.WPS; out->r = p.R; out->ns = p.NS;
+    out->unit = p.unit; out->ot = p.OT; out->cpr = p.CPR; out->gx = p.gx; out->gy = p.gy;
+  }
+  return DISSC_OK;
+}
+
+// Diagnostics: average ms of `iters` launches of one residual pair (modes as dissc_respair1d) on synthetic data.
+int dissc_pair_bench(int B, int C, int k, int dilation, int L, int epi, int iters, int mode, float* ms_out) {
+  if (!ms_out || B <= 0 || L <= 0 || iters <= 0 || epi < EPI_RES || epi > EPI_MRF_DIV) {
+    set_error("dissc_pair_bench: bad argument");
+    return DISSC_EINVAL;
+  }
+  std::vector<float> w1((size_t)C * C * k), w2((size_t)C * C * k), bias(C, 0.1f);
+  Lcg rnd;
+  rnd.fill(w1, 0.05f);
+  rnd.fill(w2, 0.05f);
+  DiagScope ds;
+  int rc = pair_make(mode, w1.data(), bias.data(), w2.data(), bias.data(), C, k, dilation, ds);
+  if (rc) return rc;
+  const int ld = (L + 3) / 4 * 4;
+  const size_t n = (size_t)B * C * ld;
+  float *x = nullptr, *y = nullptr, *t = nullptr, *a = nullptr;
+  std::vector<float> hx(n);
+  rnd.fill(hx, 2.f);
+  if (ds.alloc(&x, n) != hipSuccess || ds.alloc(&y, n) != hipSuccess || ds.alloc(&t, n) != hipSuccess ||
+      ds.alloc(&a, n) != hipSuccess || hipMemcpy(x, hx.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(a, 0, n * 4) != hipSuccess || ds.events() != hipSuccess) {
+    set_error("dissc_pair_bench: allocation failed");
+    return DISSC_ENOMEM;
+  }
+  const Batch bt = batch_of(nullptr, 1, B, L);
+  const EpiSpec ep = epi_of(epi, nullptr, a, 3.f);
+  return time_launches(ds, iters, [&]() { return pair_run(mode, ds, x, t, y, bt, ep, C, ld, 0.1f, nullptr); }, ms_out);
+}
+
+int dissc_conv_transpose1d(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths, int B,
+                           int Cin, int Cout, int k, int stride, int ldx, int ldo, int Lmax, float in_slope, void* stream) {
+  if (!x || !w_host || !y || stride < 1 || (k - stride) % 2 != 0) {
+    set_error("dissc_conv_transpose1d: bad argument");
+    return DISSC_EINVAL;
+  }
+  std::vector<DevConv> grp;
+  int rc = make_convT(w_host, bias_host, Cin, Cout, k, stride, grp);
+  for (auto& dc : grp) {
+    int r2 = rc ? rc : conv_once(dc, x, y, batch_of(lengths, 1, B, Lmax), ldx, ldo, in_slope, (hipStream_t)stream);
+    if (rc) free_conv(dc);
+    rc = rc ? rc : r2;
+  }
+  return rc;
+}
+
+// Diagnostics: average ms of `iters` launches of one conv layer on synthetic data.
+int dissc_conv_bench(int B, int Cin, int Cout, int k, int dilation, int L, int epi, int iters, int flags, float* ms_out) {
+  if (!ms_out || B <= 0 || L <= 0 || iters <= 0) {
+    set_error("dissc_conv_bench: bad argument");
+    return DISSC_EINVAL;
+  }
+  std::vector<float> w((size_t)Cout * Cin * k), bias(Cout, 0.1f);
+  Lcg rnd;
+  rnd.fill(w, 0.05f);
+  // flags bit 5 (0x20): zero-filled operands (the chip clocks to its power budget: how much of a launch's time is the data's
+  // switching activity, not the schedule?  never a number to quote)
+  if (flags & 0x20) std::fill(w.begin(), w.end(), 0.f);
+  DiagScope ds;
+  DevConv& dc = ds.c1;
+  const bool w8 = (flags & 4) && wino8_supported(Cout, Cin, k, dilation);
+  const bool wino = w8 || ((flags & 2) && wino_supported(Cout, Cin, k, dilation));
+  int rc;
+  {
+    PrecScope prec_scope(opts().precision);  // diagnostics follow the "precision" option like the generator does
+    rc = w8 ? make_wino8(w.data(), bias.data(), Cout, k, dilation, dc, (flags & 8) && wino8_r4_supported(Cout, k, dilation) ? 4 : 3)
+            : wino ? make_wino(w.data(), bias.data(), Cout, k, dilation, dc)
+                   : make_conv(w.data(), bias.data(), Cout, Cin, k, dilation, dc);
+  }
+  if (rc) return rc;
+  const int ld = (L + 3) / 4 * 4;
+  const size_t nx = (size_t)B * Cin * ld, no = (size_t)B * Cout * ld;
+  float *x = nullptr, *y = nullptr, *r = nullptr, *a = nullptr;
+  std::vector<float> hx(nx);
+  rnd.fill(hx, 2.f);
+  if (flags & 0x20) std::fill(hx.begin(), hx.end(), 0.f);
+  DISSC_HIP_CHECK(ds.alloc(&x, nx));
+  DISSC_HIP_CHECK(ds.alloc(&y, no));
+  DISSC_HIP_CHECK(ds.alloc(&r, no));
+  DISSC_HIP_CHECK(ds.alloc(&a, no));
+  DISSC_HIP_CHECK(hipMemcpy(x, hx.data(), nx * 4, hipMemcpyHostToDevice));
+  DISSC_HIP_CHECK(hipMemset(r, 0, no * 4));
+  DISSC_HIP_CHECK(hipMemset(a, 0, no * 4));
+  DISSC_HIP_CHECK(ds.events());
+  const int saved_cls = (flags >> 16) & 0xf;
+  if (flags & 0x8000) conv_set_cfg(saved_cls, (flags >> 8) & 0x3f);
+  const Batch bt = batch_of(nullptr, 1, B, L);
+  const EpiSpec ep = epi_of(epi, r, a, 3.f);
+  rc = time_launches(ds, iters, [&]() { return run_conv(dc, x, y, bt, ep, Cin, ld, ld, (flags & 1) ? 1.0f : 0.1f, nullptr); }, ms_out);
+  // diagnostics: the head of the accumulator buffer (a kernel's timeline stamps)
+  if (const char* tlp = getenv("DISSC_TIMELINE")) dump_timeline(tlp, a, std::min<size_t>(no * 4, (size_t)4096 * 64));
+  return rc;
+}
+
+// Diagnostics: average ms of `iters` launches of one stride-2, k = 3 conv (C -> C channels, L input samples per utterance,
+// GELU fused) on synthetic data; form as dissc_conv1d_s2 (hubert.hip).
+int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out) {
+  if (!ms_out || B <= 0 || L < 3 || iters <= 0 || (form != 0 && form != 1)) {
+    set_error("dissc_conv_s2_bench: bad argument");
+    return DISSC_EINVAL;
+  }
+  std::vector<float> w((size_t)C * C * 3);
+  Lcg rnd;
+  rnd.fill(w, 0.1f);
+  const int Lo = (L - 3) / 2 + 1;
+  const int ldx = (L + 3) / 4 * 4, ldo = (Lo + 3) / 4 * 4;
+  const size_t nx = (size_t)B * C * ldx, no = (size_t)B * C * ldo;
+  std::vector<float> hx(nx);
+  rnd.fill(hx, 2.f, 0.3f);
+  DiagScope ds;
+  float *x = nullptr, *y = nullptr;
+  DISSC_HIP_CHECK(ds.alloc(&x, nx));
+  DISSC_HIP_CHECK(ds.alloc(&y, no));
+  DISSC_HIP_CHECK(hipMemcpy(x, hx.data(), nx * 4, hipMemcpyHostToDevice));
+  DevS2tc& tc = ds.tc;
+  DevConv& dc = ds.c1;
+  int rc = form == 1 ? make_s2tc(w.data(), nullptr, C, C, tc) : make_conv(w.data(), nullptr, C, C, 3, 1, dc, 1, 2, 0);
+  if (rc) return rc;
+  tc.act = 1;
+  dc.act = 1;
+  Batch bt;
+  bt.len_default = L; bt.olen_default = Lo; bt.B = B; bt.Lmax = Lo;
+  float* tlbuf = nullptr;  // diagnostics (DISSC_TIMELINE): a kernel's timeline stamps, handed over as the accumulator pointer
+  const char* tlp = getenv("DISSC_TIMELINE");
+  if (tlp) {
+    DISSC_HIP_CHECK(ds.alloc(&tlbuf, (size_t)1024 * 64));
+    DISSC_HIP_CHECK(hipMemset(tlbuf, 0, (size_t)4096 * 64));
+  }
+  DISSC_HIP_CHECK(ds.events());
+  rc = time_launches(ds, iters, [&]() {
+    return form == 1 ? run_s2tc(tc, x, y, bt, ldx, ldo, nullptr)
+                     : run_conv(dc, x, y, bt, epi_of(EPI_STORE, nullptr, tlbuf), C, ldx, ldo, 1.0f, nullptr);
+  }, ms_out);
+  if (tlbuf) dump_timeline(tlp, tlbuf, (size_t)4096 * 64);
+  return rc;
+}
+
+}  // extern "C"

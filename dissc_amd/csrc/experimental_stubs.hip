@@ -13,7 +13,7 @@ int make_s2tc(const float*, const float*, int, int, DevS2tc&) {
 }
 void free_s2tc(DevS2tc&) {}
 double s2tc_executed_macs_per_out(int Cout, int Cin) { return (double)Cout * Cin * 3.0; }
-int run_s2tc(const DevS2tc&, const float*, float*, const int32_t*, const int32_t*, int, int, int, int, int, int, hipStream_t) {
+int run_s2tc(const DevS2tc&, const float*, float*, const Batch&, int, int, hipStream_t) {
   set_error("run_s2tc: only in DISSC_EXPERIMENTAL=1 builds");
   return DISSC_EINVAL;
 }
@@ -24,7 +24,7 @@ int pack_pairw43(const float*, int, int, float**) {
   set_error("make_pairw: the F(4,3) pair kernel is only in DISSC_EXPERIMENTAL=1 builds");
   return DISSC_EINVAL;
 }
-int launch_pairw43(const DevPairW&, const float*, float*, float*, const int32_t*, int, int, int, int, int, float, int, float, hipStream_t) {
+int launch_pairw43(const DevPairW&, const float*, float*, const Batch&, const EpiSpec&, int, float, hipStream_t) {
   set_error("launch_respair_wino: the F(4,3) pair kernel is only in DISSC_EXPERIMENTAL=1 builds");
   return DISSC_EINVAL;
 }

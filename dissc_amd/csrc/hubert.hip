@@ -495,10 +495,7 @@ int dissc_hubert_create_ex(int n_layers, const DisscTensor* weights, size_t n_we
   OptScope opt_scope(&m->opt);
   // a split-bf16 handle packs hi / lo planes INSTEAD of the fp32 fragments for the layers enc_bf3.hip takes (the feature convs
   // 1..6 and every linear; same bytes); conv0, the positional conv and everything that is not a conv stay fp32 in both modes
-  struct PrecScope {
-    explicit PrecScope(int p) { g_conv_prec = p ? 2 : 0; }
-    ~PrecScope() { g_conv_prec = 0; }
-  } prec_scope(prec);
+  PrecScope prec_scope(prec ? 2 : 0);
   m->n_layers = n_layers;
   int rc = DISSC_OK;
   auto fail = [&](int code) {
@@ -799,15 +796,14 @@ static int hubert_forward_part(dissc_hubert_t m, const float* wav, const int32_t
   for (int l = 1; l < NCONV; ++l) {
     const int n_out = frames_after(Nmax, l);
     const int ld_out = (int)rup(n_out > 0 ? n_out : 1, 4);
-    ConvIO io;
-    io.lengths_in = w.lens + (size_t)(l - 1) * B;
-    io.lengths_out = w.lens + (size_t)l * B;
+    Batch bt;
+    bt.lengths = w.lens + (size_t)(l - 1) * B;
+    bt.lengths_out = w.lens + (size_t)l * B;
+    bt.B = B; bt.Lmax = n_out;
     if (m->ftc[l - 1].wpack) {
-      if ((rc = run_s2tc(m->ftc[l - 1], w.f[cur], w.f[cur ^ 1], io.lengths_in, io.lengths_out, n_in, n_out, B, ld_in, ld_out,
-                         n_out, st)))
-        return rc;
-    } else if ((rc = run_conv_ex(m->fconv[l - 1], w.f[cur], w.f[cur ^ 1], nullptr, io, B, 512, ld_in, ld_out, n_out,
-                                 1.0f, EPI_STORE, st)))
+      bt.len_default = n_in; bt.olen_default = n_out;
+      if ((rc = run_s2tc(m->ftc[l - 1], w.f[cur], w.f[cur ^ 1], bt, ld_in, ld_out, st))) return rc;
+    } else if ((rc = run_conv(m->fconv[l - 1], w.f[cur], w.f[cur ^ 1], bt, EpiSpec(), 512, ld_in, ld_out, 1.0f, st)))
       return rc;
     cur ^= 1;
     ld_in = ld_out;
@@ -815,30 +811,31 @@ static int hubert_forward_part(dissc_hubert_t m, const float* wav, const int32_t
   }
   (void)n_in;
   const int32_t* lensT = w.lens + (size_t)(NCONV - 1) * B;
-  ConvIO ioT;
-  ioT.lengths_in = lensT;
+  Batch btT;
+  btT.lengths = lensT; btT.B = B; btT.Lmax = T;
+  const EpiSpec store, add_x = epi_of(EPI_RES, w.x);
   dim3 gln((T + 63) / 64, B);
   // LayerNorm(512) -> Linear(512,768)
   float* fn = w.f[cur ^ 1];  // free buffer, [B][512][ldT] fits (ldT <= ld of that buffer)
   hipLaunchKernelGGL(ln_cf_kernel, gln, dim3(64 * LN_WAVES), 0, st, w.f[cur], (const float*)nullptr, m->ln0_g, m->ln0_b,
                      lensT, 512, ldT, 1e-5f, fn);
-  if ((rc = run_conv_ex(m->proj, fn, w.x, nullptr, ioT, B, 512, ldT, ldT, T, 1.0f, EPI_STORE, st))) return rc;
+  if ((rc = run_conv(m->proj, fn, w.x, btT, store, 512, ldT, ldT, 1.0f, st))) return rc;
   // x = LN(x + GELU(pos_conv(x)))
-  if ((rc = run_conv_ex(m->pos, w.x, w.y, w.x, ioT, B, D, ldT, ldT, T, 1.0f, EPI_RES, st))) return rc;
+  if ((rc = run_conv(m->pos, w.x, w.y, btT, add_x, D, ldT, ldT, 1.0f, st))) return rc;
   hipLaunchKernelGGL(ln_cf_kernel, gln, dim3(64 * LN_WAVES), 0, st, w.y, (const float*)nullptr, m->eln_g, m->eln_b, lensT,
                      D, ldT, 1e-5f, w.x);
   for (int i = 0; i < m->n_layers; ++i) {
     auto& L = m->layers[i];
-    if ((rc = run_conv_ex(L.qkv, w.x, w.qkv, nullptr, ioT, B, D, ldT, ldT, T, 1.0f, EPI_STORE, st))) return rc;
+    if ((rc = run_conv(L.qkv, w.x, w.qkv, btT, store, D, ldT, ldT, 1.0f, st))) return rc;
     // fused exact attention (attn.hip): the scores stay on chip
     if ((rc = launch_attn_fused(w.qkv, lensT, D, hd, ldT, w.t1, T, H, B, st))) return rc;
     // x = LN(x + out_proj(O))
-    if ((rc = run_conv_ex(L.out, w.t1, w.y, w.x, ioT, B, D, ldT, ldT, T, 1.0f, EPI_RES, st))) return rc;
+    if ((rc = run_conv(L.out, w.t1, w.y, btT, add_x, D, ldT, ldT, 1.0f, st))) return rc;
     hipLaunchKernelGGL(ln_cf_kernel, gln, dim3(64 * LN_WAVES), 0, st, w.y, (const float*)nullptr, L.ln1_g, L.ln1_b, lensT, D,
                        ldT, 1e-5f, w.x);
     // x = LN(x + fc2(GELU(fc1(x))))
-    if ((rc = run_conv_ex(L.fc1, w.x, w.ffn, nullptr, ioT, B, D, ldT, ldT, T, 1.0f, EPI_STORE, st))) return rc;
-    if ((rc = run_conv_ex(L.fc2, w.ffn, w.y, w.x, ioT, B, m->F, ldT, ldT, T, 1.0f, EPI_RES, st))) return rc;
+    if ((rc = run_conv(L.fc1, w.x, w.ffn, btT, store, D, ldT, ldT, 1.0f, st))) return rc;
+    if ((rc = run_conv(L.fc2, w.ffn, w.y, btT, add_x, m->F, ldT, ldT, 1.0f, st))) return rc;
     hipLaunchKernelGGL(ln_cf_kernel, gln, dim3(64 * LN_WAVES), 0, st, w.y, (const float*)nullptr, L.ln2_g, L.ln2_b, lensT, D,
                        ldT, 1e-5f, w.x);
   }
@@ -881,6 +878,9 @@ int dissc_conv1d_s2(const float* x, const float* w_host, const float* bias_host,
     hipLaunchKernelGGL(s2_out_lengths_kernel, dim3((B + 63) / 64), dim3(64), 0, st, lengths_in, B, k, lout);
   }
   int rc;
+  Batch bt;
+  bt.lengths = lengths_in; bt.lengths_out = lout; bt.len_default = Lmax_in; bt.olen_default = Lmax_out;
+  bt.B = B; bt.Lmax = Lmax_out;
   if (form == 1) {
     DevS2tc dc;
     if (k != 3) {
@@ -888,7 +888,7 @@ int dissc_conv1d_s2(const float* x, const float* w_host, const float* bias_host,
       rc = DISSC_EINVAL;
     } else if (!(rc = make_s2tc(w_host, bias_host, Cout, Cin, dc))) {
       dc.act = act;
-      rc = run_s2tc(dc, x, y, lengths_in, lout, Lmax_in, Lmax_out, B, ldx, ldo, Lmax_out, st);
+      rc = run_s2tc(dc, x, y, bt, ldx, ldo, st);
     }
     hipError_t e = hipStreamSynchronize(st);
     free_s2tc(dc);
@@ -900,9 +900,7 @@ int dissc_conv1d_s2(const float* x, const float* w_host, const float* bias_host,
     DevConv dc;
     if (!(rc = make_conv(w_host, bias_host, Cout, Cin, k, 1, dc, 1, 2, 0))) {
       dc.act = act;
-      ConvIO io;
-      io.lengths_in = lengths_in; io.lengths_out = lout; io.len_default = Lmax_in; io.olen_default = Lmax_out;
-      rc = run_conv_ex(dc, x, y, nullptr, io, B, Cin, ldx, ldo, Lmax_out, 1.0f, EPI_STORE, st);
+      rc = run_conv(dc, x, y, bt, EpiSpec(), Cin, ldx, ldo, 1.0f, st);
     }
     hipError_t e = hipStreamSynchronize(st);
     free_conv(dc);
@@ -926,10 +924,8 @@ int dissc_conv1d_s2_prec(const float* x, const float* w_host, const float* bias_
     set_error("dissc_conv1d_s2_prec: no split-bf16 kernel for %d -> %d channels, k = %d", Cin, Cout, k);
     return DISSC_EINVAL;
   }
-  g_conv_prec = prec ? 2 : 0;
-  const int rc = dissc_conv1d_s2(x, w_host, bias_host, y, lengths_in, B, Cin, Cout, k, ldx, ldo, Lmax_in, act, 0, stream_);
-  g_conv_prec = 0;
-  return rc;
+  PrecScope prec_scope(prec ? 2 : 0);
+  return dissc_conv1d_s2(x, w_host, bias_host, y, lengths_in, B, Cin, Cout, k, ldx, ldo, Lmax_in, act, 0, stream_);
 }
 
 // Stand-alone linear as the encoder runs it (tests): x f32 [B,Cin,ld] -> y f32 [B,Cout,ld], columns [0, len_b) of every utterance,
@@ -947,14 +943,14 @@ int dissc_linear_prec(const float* x, const float* w_host, const float* bias_hos
   }
   hipStream_t st = (hipStream_t)stream_;
   DevConv dc;
-  g_conv_prec = prec ? 2 : 0;
-  int rc = make_conv(w_host, bias_host, Cout, Cin, 1, 1, dc, 1, 1, 0);
-  g_conv_prec = 0;
+  int rc;
+  {
+    PrecScope prec_scope(prec ? 2 : 0);
+    rc = make_conv(w_host, bias_host, Cout, Cin, 1, 1, dc, 1, 1, 0);
+  }
   if (!rc) {
     dc.act = act;
-    ConvIO io;
-    io.lengths_in = lengths; io.len_default = Tmax;
-    rc = run_conv_ex(dc, x, y, res, io, B, Cin, ld, ld, Tmax, 1.0f, res ? EPI_RES : EPI_STORE, st);
+    rc = run_conv(dc, x, y, batch_of(lengths, 1, B, Tmax), epi_of(res ? EPI_RES : EPI_STORE, res), Cin, ld, ld, 1.0f, st);
   }
   hipError_t e = hipStreamSynchronize(st);
   free_conv(dc);
@@ -963,78 +959,6 @@ int dissc_linear_prec(const float* x, const float* w_host, const float* bias_hos
     rc = DISSC_EHIP;
   }
   return rc;
-}
-
-// Diagnostics: average ms of `iters` launches of one stride-2, k = 3 conv (C -> C channels, L input samples per utterance,
-// GELU fused) on synthetic data; form as above.
-int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out) {
-  if (!ms_out || B <= 0 || L < 3 || iters <= 0 || (form != 0 && form != 1)) {
-    set_error("dissc_conv_s2_bench: bad argument");
-    return DISSC_EINVAL;
-  }
-  std::vector<float> w((size_t)C * C * 3);
-  uint32_t s = 12345u;
-  for (auto& v : w) {
-    s = s * 1664525u + 1013904223u;
-    v = ((s >> 8) / 16777216.0f - 0.5f) * 0.1f;
-  }
-  const int Lo = (L - 3) / 2 + 1;
-  const int ldx = (L + 3) / 4 * 4, ldo = (Lo + 3) / 4 * 4;
-  const size_t nx = (size_t)B * C * ldx, no = (size_t)B * C * ldo;
-  std::vector<float> hx(nx);
-  for (auto& v : hx) {
-    s = s * 1664525u + 1013904223u;
-    v = ((s >> 8) / 16777216.0f - 0.3f) * 2.f;
-  }
-  float *x = nullptr, *y = nullptr;
-  DISSC_HIP_CHECK(hipMalloc((void**)&x, nx * 4));
-  DISSC_HIP_CHECK(hipMalloc((void**)&y, no * 4));
-  DISSC_HIP_CHECK(hipMemcpy(x, hx.data(), nx * 4, hipMemcpyHostToDevice));
-  DevS2tc tc;
-  DevConv dc;
-  int rc = form == 1 ? make_s2tc(w.data(), nullptr, C, C, tc) : make_conv(w.data(), nullptr, C, C, 3, 1, dc, 1, 2, 0);
-  tc.act = 1;
-  dc.act = 1;
-  ConvIO io;
-  io.len_default = L; io.olen_default = Lo;
-  float* tlbuf = nullptr;  // diagnostics (DISSC_TIMELINE): a kernel's timeline stamps, handed over as the accumulator pointer
-  const char* tlp = getenv("DISSC_TIMELINE");
-  if (tlp) {
-    DISSC_HIP_CHECK(hipMalloc((void**)&tlbuf, (size_t)4096 * 64));
-    DISSC_HIP_CHECK(hipMemset(tlbuf, 0, (size_t)4096 * 64));
-  }
-  auto once = [&]() {
-    return form == 1 ? run_s2tc(tc, x, y, nullptr, nullptr, L, Lo, B, ldx, ldo, Lo, nullptr)
-                     : run_conv_ex(dc, x, y, nullptr, tlbuf, io, B, C, ldx, ldo, Lo, 1.0f, EPI_STORE, 1.f, nullptr);
-  };
-  hipEvent_t e0, e1;
-  DISSC_HIP_CHECK(hipEventCreate(&e0));
-  DISSC_HIP_CHECK(hipEventCreate(&e1));
-  for (int it = 0; it < 2 && !rc; ++it) rc = once();
-  DISSC_HIP_CHECK(hipEventRecord(e0, nullptr));
-  for (int it = 0; it < iters && !rc; ++it) rc = once();
-  DISSC_HIP_CHECK(hipEventRecord(e1, nullptr));
-  hipError_t e = hipEventSynchronize(e1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  *ms_out = ms / iters;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (tlbuf) {
-    std::vector<char> hb((size_t)4096 * 64);
-    if (hipMemcpy(hb.data(), tlbuf, hb.size(), hipMemcpyDeviceToHost) == hipSuccess)
-      if (FILE* f = fopen(tlp, "wb")) {
-        fwrite(hb.data(), 1, hb.size(), f);
-        fclose(f);
-      }
-    (void)hipFree(tlbuf);
-  }
-  (void)hipFree(x); (void)hipFree(y);
-  free_s2tc(tc);
-  free_conv(dc);
-  if (rc) return rc;
-  DISSC_HIP_CHECK(e);
-  return DISSC_OK;
 }
 
 // Diagnostics: the encoder's fused attention (attn.hip) and its LayerNorm on their own, on caller-made inputs (device pointers,

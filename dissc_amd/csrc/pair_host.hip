@@ -178,32 +178,29 @@ int pair_reg_tile(int form, int C, int KS, int dil) {
   return 0;
 }
 
-static int launch_pair_f23(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
-                           int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream) {
+int launch_respair_wino(const DevPairW& pw, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld, float slope,
+                        hipStream_t stream) {
+  const int B = bt.B, Lmax = bt.Lmax;
+  if (!pw.w1 || ep.epi == EPI_STORE || x == out || ld < 4 || ld % 4 || misaligned16(x) || misaligned16(out) || misaligned16(ep.acc) ||
+      B <= 0 || Lmax <= 0) {
+    set_error("launch_respair_wino: bad argument (C=%d k=%d d=%d ld=%d epi=%d)", pw.C, pw.KS, pw.dil, ld, ep.epi);
+    return DISSC_EINVAL;
+  }
+  if (!pw.form) {
+    if (pairw43_built()) return launch_pairw43(pw, x, out, bt, ep, ld, slope, stream);
+    set_error("launch_respair_wino: no instance (the F(4,3) pair kernel is only in DISSC_EXPERIMENTAL=1 builds)");
+    return DISSC_EINVAL;
+  }
   PairArgs a;
-  a.x = x; a.out = out; a.acc = acc; a.w1 = pw.w1; a.w2 = pw.w2; a.b1 = pw.b1; a.b2 = pw.b2;
-  a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul; a.ld = ld;
-  a.bstride = (long long)pw.C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = opts().kernel_dbg;
+  a.x = x; a.out = out; a.acc = ep.acc; a.w1 = pw.w1; a.w2 = pw.w2; a.b1 = pw.b1; a.b2 = pw.b2;
+  a.lengths = bt.lengths; a.len_default = bt.len_default; a.len_mul = bt.len_mul; a.ld = ld;
+  a.bstride = (long long)pw.C * ld; a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi; a.dbg = opts().kernel_dbg;
 #define DISSC_CASE(FORM_, C_, KERNEL_, GEO_, MAX_LDS_, K_, D_)       \
   if (pw.form == FORM_ && pw.C == C_ && pw.KS == K_ && pw.dil == D_) \
     return launch_pair_reg<KERNEL_<K_, D_>, GEO_<K_, D_>>(a, B, Lmax, stream, MAX_LDS_);
   DISSC_PAIR_REG_INSTANCES
 #undef DISSC_CASE
   set_error("launch_pair_f23: no instance of form %d for C = %d, k = %d, dilation %d", pw.form, pw.C, pw.KS, pw.dil);
-  return DISSC_EINVAL;
-}
-
-int launch_respair_wino(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
-                        int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream) {
-  if (!pw.w1 || epi == EPI_STORE || x == out || ld < 4 || ld % 4 || misaligned16(x) || misaligned16(out) || misaligned16(acc) ||
-      B <= 0 || Lmax <= 0) {
-    set_error("launch_respair_wino: bad argument (C=%d k=%d d=%d ld=%d epi=%d)", pw.C, pw.KS, pw.dil, ld, epi);
-    return DISSC_EINVAL;
-  }
-  if (pw.form) return launch_pair_f23(pw, x, out, acc, lengths, len_default, len_mul, B, Lmax, ld, slope, epi, mrf_div, stream);
-  if (pairw43_built())
-    return launch_pairw43(pw, x, out, acc, lengths, len_default, len_mul, B, Lmax, ld, slope, epi, mrf_div, stream);
-  set_error("launch_respair_wino: no instance (the F(4,3) pair kernel is only in DISSC_EXPERIMENTAL=1 builds)");
   return DISSC_EINVAL;
 }
 

@@ -366,8 +366,7 @@ static int pred_body(dissc_pred* p, const int64_t* seq, const int64_t* spk, cons
   float slope = 1.0f;  // raw embeddings into cnn1, LeakyReLU(0.01) afterwards
   for (size_t i = 0; i < p->body.size(); ++i) {
     float* o = (i & 1) ? b : a;
-    int rc = run_conv(p->body[i], in, o, nullptr, nullptr, lengths, L, 1, B, cin, ld, ld, L, slope,
-                      EPI_STORE, 1.f, stream);
+    int rc = run_conv(p->body[i], in, o, batch_of(lengths, 1, B, L), EpiSpec(), cin, ld, ld, slope, stream);
     if (rc) return rc;
     in = o;
     cin = p->C;
@@ -393,8 +392,7 @@ int dissc_len_forward(dissc_pred_t p, const int64_t* seq, const int64_t* spk, co
   int rc = pred_body(p, seq, spk, lengths, B, Lmax, ws, ws_bytes, stream, &h, &spare, &ld);
   if (rc) return rc;
   // cnn2 (128 -> 1) with the label de-normalisation (*std + mean) as its affine epilogue
-  rc = run_conv(p->head, h, out, nullptr, nullptr, lengths, Lmax, 1, B, p->C, ld, ldo, Lmax, 0.01f,
-                EPI_STORE, 1.f, stream);
+  rc = run_conv(p->head, h, out, batch_of(lengths, 1, B, Lmax), EpiSpec(), p->C, ld, ldo, 0.01f, stream);
   if (rc) return rc;
   DISSC_HIP_CHECK(hipGetLastError());
   return DISSC_OK;
@@ -429,8 +427,7 @@ int dissc_pitch_forward(dissc_pred_t p, const int64_t* seq, const int64_t* spk,
   int rc = pred_body(p, seq, spk, lengths, B, Tmax, ws, ws_bytes, stream, &h, &spare, &ld);
   if (rc) return rc;
   float* heads = (float*)rup((size_t)ws, 256) + (size_t)B * ld * (2 * p->E + 2 * p->C);
-  rc = run_conv(p->head, h, heads, nullptr, nullptr, lengths, Tmax, 1, B, p->C, ld, ld, Tmax, 0.01f,
-                EPI_STORE, 1.f, stream);
+  rc = run_conv(p->head, h, heads, batch_of(lengths, 1, B, Tmax), EpiSpec(), p->C, ld, ld, 0.01f, stream);
   if (rc) return rc;
   dim3 grid((Tmax + 127) / 128, B);
   hipLaunchKernelGGL(pitch_head_kernel, grid, dim3(128), 0, stream, heads, p->wc, p->wr, p->bc, p->br,

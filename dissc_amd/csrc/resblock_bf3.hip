@@ -383,19 +383,18 @@ static int launch_bf3(ResblockBf3Args a, int B, int Lmax, hipStream_t stream) {
   return DISSC_OK;
 }
 
-int launch_resblock_bf3(int C, const float* x, float* acc, const float* wpack, const float* bias,
-                        const int32_t* lengths, int len_default, int len_mul, int KS, const int* dil,
-                        int B, int Lmax, int ld, float slope, int epi, float mrf_div, int m0, int m1,
+int launch_resblock_bf3(const Bf3Block& blk, const float* x, const Batch& bt, const EpiSpec& ep, int ld, float slope, int m0, int m1,
                         hipStream_t stream) {
-  if (!resblock_bf3_supported(C, KS, dil) || m0 < 0 || m1 > 3 || m0 >= m1) {
+  const int C = blk.C, KS = blk.KS, B = bt.B, Lmax = bt.Lmax;
+  if (!resblock_bf3_supported(C, KS, blk.dil) || m0 < 0 || m1 > 3 || m0 >= m1) {
     set_error("launch_resblock_bf3: C=%d k=%d unsupported", C, KS);
     return DISSC_EINVAL;
   }
   ResblockBf3Args a;
-  a.x = x; a.acc = acc; a.wpack = reinterpret_cast<const bf16x8*>(wpack); a.bias = bias; a.lengths = lengths;
-  a.len_default = len_default; a.len_mul = len_mul;
-  a.dil[0] = dil[0]; a.dil[1] = dil[1]; a.dil[2] = dil[2];
-  a.ld = ld; a.bstride = (long long)C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi;
+  a.x = x; a.acc = ep.acc; a.wpack = reinterpret_cast<const bf16x8*>(blk.wpack); a.bias = blk.bias; a.lengths = bt.lengths;
+  a.len_default = bt.len_default; a.len_mul = bt.len_mul;
+  a.dil[0] = blk.dil[0]; a.dil[1] = blk.dil[1]; a.dil[2] = blk.dil[2];
+  a.ld = ld; a.bstride = (long long)C * ld; a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi;
   a.BN = 0; a.H4 = 0; a.m0 = m0; a.m1 = m1;
   if (C == 64) {  // 256-column windows fill the CU's 160 KB of LDS
     if (KS == 3) return launch_bf3<64, 3, 8, 2>(a, B, Lmax, stream);

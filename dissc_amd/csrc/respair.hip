@@ -335,19 +335,18 @@ bool respair_supported(int C, int KS, int dil) {
 }
 
 // c1 / c2: the DevConvs of the dilated conv and of the dil-1 conv (fp32, 16x16x4 packing)
-int launch_respair(const DevConv& c1, const DevConv& c2, const float* x, float* out, float* acc,
-                   const int32_t* lengths, int len_default, int len_mul, int B, int Lmax, int ld, float slope,
-                   int epi, float mrf_div, hipStream_t stream) {
-  const int C = c1.M;
+int launch_respair(const DevConv& c1, const DevConv& c2, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld,
+                   float slope, hipStream_t stream) {
+  const int C = c1.M, B = bt.B, Lmax = bt.Lmax;
   if (!respair_supported(C, c1.KS, c1.dil) || c2.KS != c1.KS || c2.dil != 1 || c1.m32 != (C == 32) ||
-      c2.m32 != (C == 32) || c1.prec || c2.prec || c1.CIN != C || c2.CIN != C || c2.M != C || epi == EPI_STORE || x == out) {
+      c2.m32 != (C == 32) || c1.prec || c2.prec || c1.CIN != C || c2.CIN != C || c2.M != C || ep.epi == EPI_STORE || x == out) {
     set_error("launch_respair: unsupported pair (C=%d k=%d d=%d)", C, c1.KS, c1.dil);
     return DISSC_EINVAL;
   }
   PairArgs a;
-  a.x = x; a.out = out; a.acc = acc; a.w1 = c1.wpack; a.w2 = c2.wpack; a.b1 = c1.bias; a.b2 = c2.bias;
-  a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul; a.ld = ld;
-  a.bstride = (long long)C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.dbg = 0;
+  a.x = x; a.out = out; a.acc = ep.acc; a.w1 = c1.wpack; a.w2 = c2.wpack; a.b1 = c1.bias; a.b2 = c2.bias;
+  a.lengths = bt.lengths; a.len_default = bt.len_default; a.len_mul = bt.len_mul; a.ld = ld;
+  a.bstride = (long long)C * ld; a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi; a.dbg = 0;
 #define DISSC_PAIR16(K, D)                                                        \
   if (c1.KS == K && c1.dil == D)                                                  \
     return C == 16 ? launch_pair16<K, D>(a, B, Lmax, stream) : launch_pair32<K, D>(a, B, Lmax, stream);

@@ -868,8 +868,7 @@ int dissc_train_step(dissc_trainer_t t, const int64_t* seq, const int64_t* spk, 
     TLayer& l = t->layers[li];
     const float* in = l.in < 0 ? x0 : t->layers[l.in].a;
     if (l.cout >= 32) {
-      if ((rc = run_conv(l.fwd, in, l.z, nullptr, nullptr, nullptr, L, 1, B, l.cin, ld, ld, L, 1.0f, EPI_STORE, 1.f, st)))
-        return rc;
+      if ((rc = run_conv(l.fwd, in, l.z, batch_of(nullptr, 1, B, L), EpiSpec(), l.cin, ld, ld, 1.0f, st))) return rc;
       if (l.has_bn)
         hipLaunchKernelGGL(train_bn_stats_kernel, dim3(l.cout), dim3(256), 0, st, l.z, B, l.cout, L, ld, l.mean,
                            l.invstd, P(l.rm), P(l.rv));
@@ -922,9 +921,8 @@ int dissc_train_step(dissc_trainer_t t, const int64_t* seq, const int64_t* spk, 
                          B * WGM_SPLIT, nw, G(l.w));
       hipLaunchKernelGGL(train_bias_grad_kernel, dim3(l.cout), dim3(256), 0, st, l.dz, B, l.cout, L, ld, G(l.b));
       // input gradient: the same conv with W^T, taps flipped (accumulating where the input feeds two layers)
-      if ((rc = run_conv(l.bwd, l.dz, din, acc_in ? din : nullptr, nullptr, nullptr, L, 1, B, l.cout, ld, ld, L, 1.0f,
-                         acc_in ? EPI_RES : EPI_STORE, 1.f, st)))
-        return rc;
+      const EpiSpec ep = acc_in ? epi_of(EPI_RES, din) : EpiSpec();
+      if ((rc = run_conv(l.bwd, l.dz, din, batch_of(nullptr, 1, B, L), ep, l.cout, ld, ld, 1.0f, st))) return rc;
     }
     if (l.in < 0) dx0_set = true; else has_da[l.in] = 1;
   }

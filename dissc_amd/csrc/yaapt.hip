@@ -528,14 +528,12 @@ int dissc_yaapt_spectral(dissc_yaapt_t y, const float* wav, const int32_t* n_sam
     hipLaunchKernelGGL(yaapt_fir_kernel, grid, dim3(256), lds, st, wav, n_samples, y->fir, y->ntaps, Nmax, filt, nlfilt);
   }
   int rc;
-  ConvIO io;
-  io.lengths_in = nfr;   // "time" axis of the GEMM = frames
-  io.len_default = F;
+  const Batch bt = batch_of(nfr, 1, B, F);  // "time" axis of the GEMM = frames
   // 2. NLFER: frames of the filtered signal -> band DFT (hann folded into the rows) -> sum of magnitudes
   {
     dim3 grid((ldf + 255) / 256, y->flen, B);
     hipLaunchKernelGGL(yaapt_im2col_kernel, grid, dim3(256), 0, st, filt, n_samples, nfr, Nmax, y->flen, y->hop, F, ldf, col);
-    if ((rc = run_conv_ex(y->dft_nlfer, col, spec, nullptr, io, B, y->flen, ldf, ldf, F, 1.0f, EPI_STORE, st))) return rc;
+    if ((rc = run_conv(y->dft_nlfer, col, spec, bt, EpiSpec(), y->flen, ldf, ldf, 1.0f, st))) return rc;
     dim3 g2((F + 255) / 256, B);
     hipLaunchKernelGGL(yaapt_band_energy_kernel, g2, dim3(256), 0, st, spec, nfr, y->nl_nb, 2 * y->nl_nb, F, ldf, energy);
   }
@@ -544,7 +542,7 @@ int dissc_yaapt_spectral(dissc_yaapt_t y, const float* wav, const int32_t* n_sam
     const int fl2 = 2 * y->flen;
     dim3 grid((ldf + 255) / 256, fl2, B);
     hipLaunchKernelGGL(yaapt_im2col_kernel, grid, dim3(256), 0, st, nlfilt, n_samples, nfr, Nmax, fl2, y->hop, F, ldf, col);
-    if ((rc = run_conv_ex(y->dft_shc, col, spec, nullptr, io, B, fl2, ldf, ldf, F, 1.0f, EPI_STORE, st))) return rc;
+    if ((rc = run_conv(y->dft_shc, col, spec, bt, EpiSpec(), fl2, ldf, ldf, 1.0f, st))) return rc;
     ShcArgs a;
     a.spec = spec; a.dre = y->dre; a.dim = y->dim; a.nfr = nfr; a.nb = y->shc_nb; a.rows_ld = 2 * y->shc_nb;
     a.F = F; a.ldf = ldf; a.flen2 = fl2; a.nharm = y->nharm; a.wl = y->wl; a.half = y->half; a.min_shc = y->min_shc;

@@ -429,15 +429,15 @@ static int launch_s2tc_t(const S2tcArgs& a, long long nwg, hipStream_t stream) {
   return DISSC_OK;
 }
 
-int run_s2tc(const DevS2tc& dc, const float* x, float* out, const int32_t* lengths_in, const int32_t* lengths_out,
-             int len_default, int olen_default, int B, int ldx, int ldo, int Lmax_out, hipStream_t stream) {
+int run_s2tc(const DevS2tc& dc, const float* x, float* out, const Batch& bt, int ldx, int ldo, hipStream_t stream) {
+  const int B = bt.B, Lmax_out = bt.Lmax;
   if (B <= 0 || Lmax_out <= 0 || !dc.wpack || ldx < 4 || ldx % 4 || ldo % 4 || misaligned16(x) || misaligned16(out)) {
     set_error("run_s2tc: bad call (B %d, Lmax_out %d, ldx %d, ldo %d: rows must be 16-byte aligned)", B, Lmax_out, ldx, ldo);
     return DISSC_EINVAL;
   }
   S2tcArgs a;
   a.x = x; a.wpack = dc.wpack; a.bias = dc.bias; a.out = out;
-  a.lengths_in = lengths_in; a.lengths_out = lengths_out; a.len_default = len_default; a.olen_default = olen_default;
+  a.lengths_in = bt.lengths; a.lengths_out = bt.lengths_out; a.len_default = bt.len_default; a.olen_default = bt.olen_default;
   a.CIN = dc.CIN; a.M = dc.M; a.act = dc.act; a.ldx = ldx; a.ldo = ldo;
   a.x_bstride = (long long)dc.CIN * ldx; a.o_bstride = (long long)dc.M * ldo;
   a.gx = (Lmax_out + S2_OT - 1) / S2_OT;

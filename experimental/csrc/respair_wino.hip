@@ -562,12 +562,13 @@ static int launch_pairw_t(PairWArgs a, int B, int Lmax, hipStream_t stream) {
   return DISSC_OK;
 }
 
-int launch_pairw43(const DevPairW& pw, const float* x, float* out, float* acc, const int32_t* lengths, int len_default,
-                   int len_mul, int B, int Lmax, int ld, float slope, int epi, float mrf_div, hipStream_t stream) {
+int launch_pairw43(const DevPairW& pw, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld, float slope,
+                   hipStream_t stream) {
+  const int B = bt.B, Lmax = bt.Lmax;
   PairWArgs a;
-  a.x = x; a.out = out; a.acc = acc; a.w1 = pw.w1; a.w2 = pw.w2; a.b1 = pw.b1; a.b2 = pw.b2;
-  a.lengths = lengths; a.len_default = len_default; a.len_mul = len_mul; a.ld = ld;
-  a.bstride = (long long)pw.C * ld; a.slope = slope; a.mrf_div = mrf_div; a.epi = epi; a.gx = 0; a.B = B; a.dbg = opts().kernel_dbg;
+  a.x = x; a.out = out; a.acc = ep.acc; a.w1 = pw.w1; a.w2 = pw.w2; a.b1 = pw.b1; a.b2 = pw.b2;
+  a.lengths = bt.lengths; a.len_default = bt.len_default; a.len_mul = bt.len_mul; a.ld = ld;
+  a.bstride = (long long)pw.C * ld; a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi; a.gx = 0; a.B = B; a.dbg = opts().kernel_dbg;
 #define DISSC_PAIRW(C_, K_, D_)                                                                       \
   if (pw.C == C_ && pw.KS == K_ && pw.dil == D_)                                                      \
     return opts().pairw_chv == 2 ? launch_pairw_t<C_, K_, D_, 2>(a, B, Lmax, stream) : launch_pairw_t<C_, K_, D_, 1>(a, B, Lmax, stream);

@@ -221,7 +221,7 @@ def test_trained_like_resblock_convs(tl, stage, j):
 def _check(name, forms, res, plan_form):
     """the bars of one layer; returns the broken ones (every layer and form is measured before a test fails).  plan_form: the
     form the default plan runs this layer in -- a transform-domain form above TD_RMS x the direct kernel's e_rms must not be it
-    (generator.hip falls back to a safer form there); the e_ch and leak bars hold for every form"""
+    (gen_plan.hip falls back to a safer form there); the e_ch and leak bars hold for every form"""
     bad = []
     (ca, cb), (da, db) = res["cpu"], res["direct"]
     _report(name, "cpu-fp32", ca, cb)
@@ -248,7 +248,7 @@ def _check(name, forms, res, plan_form):
 
 
 def _plan_conv_form(lib, C, k, d):
-    """generator.hip td_conv_form under the current option defaults (the ResBlock convs of the C >= 64 stages)"""
+    """gen_plan.hip td_conv_form under the current option defaults (the ResBlock convs of the C >= 64 stages)"""
     opt = {}
     for key in ("wino", "wino8", "wino8_mask", "wino8_r4", "wino8_r4_mask"):
         v = ctypes.c_int(0)
