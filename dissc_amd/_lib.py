@@ -45,6 +45,10 @@ class DisscConvLaunch(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("family", "cfg", "bm", "bn", "rows", "p0", "np", "ntap", "pad_left")]
 
 
+class DisscBf3Info(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("bm", "bn", "small_grid", "tile", "cols", "h4", "pad")]
+
+
 class DisscWino8Plan(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("mi", "ni", "wps", "r", "ns", "unit", "ot", "cpr", "gx", "gy")]
 
@@ -80,6 +84,8 @@ def _load():
                                ctypes.c_float, vp]
     L.dissc_conv_transpose1d.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32,
                                          ctypes.c_float, vp]
+    L.dissc_conv1d_prec.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.c_float, i32, vp]
+    L.dissc_conv_transpose1d_prec.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.c_float, i32, vp]
     L.dissc_pred_create.argtypes = [i32, ctypes.POINTER(DisscTensor), ctypes.c_size_t, ctypes.POINTER(vp)]
     L.dissc_pred_destroy.argtypes = [vp]
     L.dissc_pred_destroy.restype = None
@@ -119,6 +125,8 @@ def _load():
     L.dissc_pair_info.argtypes = [i32] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2
     L.dissc_conv_info.argtypes = [i32] * 7 + [ctypes.POINTER(DisscConvLaunch), i32, ctypes.POINTER(ctypes.c_int)]
     L.dissc_wino8_info.argtypes = [i32] * 6 + [ctypes.POINTER(DisscWino8Plan)]
+    L.dissc_resblock1d_bf3.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, ctypes.c_float, i32, ctypes.c_float, i32, i32, vp]
+    L.dissc_bf3_info.argtypes = [i32] * 6 + [vp, i32, i32, ctypes.POINTER(DisscBf3Info)]
     L.dissc_respair1d.argtypes = [vp] * 8 + [i32] * 6 + [ctypes.c_float, i32, ctypes.c_float, i32, vp]
     L.dissc_wav_postprocess.argtypes = [vp, vp, i32, i32, vp]
     L.dissc_pitch_stats.argtypes = [vp, vp, i32, vp, vp, vp, vp]
@@ -183,6 +191,23 @@ def wino8_info(C, k, dilation, R, B, Lmax):
     out = DisscWino8Plan()
     check(lib.dissc_wino8_info(C, k, dilation, R, B, Lmax, ctypes.byref(out)), "dissc_wino8_info")
     return {f: getattr(out, f) for f, _ in DisscWino8Plan._fields_}
+
+
+def bf3_conv_info(Cin, Cout, k, dilation=1, B=1, Lmax=1):
+    """dissc_bf3_info for a conv: the conv_bf3_kernel tile of the layer (for a ConvTranspose phase group: Cout = its GEMM rows, k = its
+    taps) under the current option defaults, as a dict (bm, bn, small_grid, tile).  Raises where the layer gets no split-bf16
+    instance.  Host only."""
+    out = DisscBf3Info()
+    check(lib.dissc_bf3_info(Cout, Cin, k, dilation, B, Lmax, None, 0, 0, ctypes.byref(out)), "dissc_bf3_info")
+    return {f: getattr(out, f) for f in ("bm", "bn", "small_grid", "tile")}
+
+
+def bf3_block_info(C, k, dil, m0=0, m1=3):
+    """dissc_bf3_info for pairs [m0, m1) of a ResBlock on resblock_bf3_kernel, as a dict (cols, pad, h4, bn).  Host only."""
+    out = DisscBf3Info()
+    d3 = (ctypes.c_int32 * 3)(*dil)
+    check(lib.dissc_bf3_info(C, C, k, 1, 1, 1, d3, m0, m1, ctypes.byref(out)), "dissc_bf3_info")
+    return {f: getattr(out, f) for f in ("cols", "pad", "h4", "bn")}
 
 
 def get_option(key):

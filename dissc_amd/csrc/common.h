@@ -283,6 +283,11 @@ void pack_conv_weights_bf3(const float* w, int Cout, int Cin, int KS, std::vecto
                            int& Mpad, int& nchunk);
 int launch_conv_bf3(const ConvArgs& a, int B, int Lmax_out, hipStream_t stream);
 int conv_bf3_tile_bn(int M);
+// the tile launch_conv_bf3 runs a layer of M rows on for B utterances of at most Lmax_out columns under the current options (host
+// only; dissc_bf3_info reports it): `tile` indexes conv_bf3.hip's table, BM x BN its shape, small = 1 the 64 x 128 tile a small
+// grid of a >= 128-row layer steps down to
+struct ConvBf3Plan { int tile, BM, BN, small; };
+int conv_bf3_plan(int M, int KS, int dil, int groups, int B, int Lmax_out, ConvBf3Plan& p);
 // the encoder's split-bf16 kernel (enc_bf3.hip): 1x1 convs and stride-2 VALID convs with k = 2 / 3; weights packed by
 // pack_conv_weights_bf3
 bool enc_bf3_supported(int Cout, int Cin, int KS, int dil, int groups, int stride, int pad_left);
@@ -427,6 +432,11 @@ struct Bf3Block { int C, KS; const int* dil; const float *wpack, *bias; };  // o
 // residual pairs [m0, m1) of the block, into ep.acc; ep.epi = EPI_STORE writes x_k there (a partial block)
 int launch_resblock_bf3(const Bf3Block& blk, const float* x, const Batch& bt, const EpiSpec& ep, int ld, float slope, int m0, int m1,
                         hipStream_t stream);
+// the instance and window launch_resblock_bf3 runs pairs [m0, m1) of a block on (host only; dissc_bf3_info reports it): a workgroup
+// of NW waves owns COLS = 16 NW NI window columns, PAD LDS padding columns on each side, the halo H of the pairs rounded up to H4,
+// BN = COLS - 2 H4 centre columns written back
+struct ResblockBf3Plan { int NW, NI, COLS, PAD, H4, BN; };
+int resblock_bf3_plan(int C, int KS, const int* dil, int m0, int m1, ResblockBf3Plan& p);
 
 // HuBERT's stride-2, k = 3 feature convs in polyphase Toom-Cook form (conv_s2tc.hip)
 struct DevS2tc {

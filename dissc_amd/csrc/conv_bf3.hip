@@ -13,6 +13,8 @@
 // of one time step -- is then a single conflict-free ds_read_b128 at any tap offset, and the tap
 // loop holds nothing but weight loads, LDS reads and MFMAs.
 // (A producer/consumer wave split of this kernel was measured slower on every layer shape.)
+// On its own: dissc_conv1d_prec / dissc_conv_transpose1d_prec (prec = 1) and mode 5 of dissc_respair1d (diag.hip); dissc_bf3_info
+// reports conv_bf3_plan, the tile a launch takes.  Every tile at tile-edge lengths: tests/test_gpu_gen_split_bf16.py.
 #include <string.h>
 
 #include "common.h"
@@ -221,10 +223,41 @@ void pack_conv_weights_bf3(const float* w, int Cout, int Cin, int KS, std::vecto
           }
 }
 
+// The tile of one launch: the class tile of the layer's rows, or the 64 x 128 one for the small grid of a >= 128-row layer.
+int conv_bf3_plan(int M, int KS, int dil, int groups, int B, int Lmax_out, ConvBf3Plan& p) {
+  if (groups != 1 || (KS - 1) * dil > MAX_TAP_SPAN || M < 32 || B < 1 || Lmax_out < 1) {
+    set_error("launch_conv_bf3: unsupported layer (groups %d, k %d, dilation %d, rows %d) or batch (%d x %d)", groups, KS, dil, M, B,
+              Lmax_out);
+    return DISSC_EINVAL;
+  }
+  const int cls = bf3_class(M);
+  p.tile = cls;
+  p.small = 0;
+  if (cls >= 2 && opts().small_grid) {
+    // small grids (short or single utterances): 64 x 128 tiles instead of the 128-accumulator ones,
+    // same MFMA sequence per output element, bit-identical result (cf. conv32_pick_cfg)
+    const TileBf3& t = kBf3[cls];
+    const int bm = 32 * t.MI * t.WM, bn = 32 * t.NI * t.WN;
+    const long long nwg = (long long)((Lmax_out + bn - 1) / bn) * ((M + bm - 1) / bm) * B;
+    if (nwg < 256LL * opts().small_grid) {
+      p.tile = 1;
+      p.small = 1;
+    }
+  }
+  const TileBf3& t = kBf3[p.tile];
+  p.BM = 32 * t.MI * t.WM;
+  p.BN = 32 * t.NI * t.WN;
+  return DISSC_OK;
+}
+
 template <int MI, int NI, int WM, int WN>
-static int launch_bf3_t(ConvArgs a, int B, int Lmax_out, hipStream_t stream) {
+static int launch_bf3_t(ConvArgs a, const ConvBf3Plan& p, int B, int Lmax_out, hipStream_t stream) {
   constexpr int BM = 32 * MI * WM, BN = 32 * NI * WN;
   constexpr int CW = 32 * NI + 4;
+  if (p.BM != BM || p.BN != BN) {
+    set_error("launch_conv_bf3: plan %d x %d on the %d x %d instance", p.BM, p.BN, BM, BN);
+    return DISSC_EINVAL;
+  }
   a.XW = bf3_xw(BN, (a.KS - 1) * a.dil);
   a.mt_per_group = (a.M + BM - 1) / BM;
   dim3 grid((Lmax_out + BN - 1) / BN, a.mt_per_group, B);
@@ -238,25 +271,15 @@ static int launch_bf3_t(ConvArgs a, int B, int Lmax_out, hipStream_t stream) {
 }
 
 int launch_conv_bf3(const ConvArgs& a, int B, int Lmax_out, hipStream_t stream) {
-  if (a.groups != 1 || (a.KS - 1) * a.dil > MAX_TAP_SPAN || a.M < 32) {
-    set_error("launch_conv_bf3: unsupported layer (groups %d, k %d, dilation %d, rows %d)", a.groups, a.KS,
-              a.dil, a.M);
-    return DISSC_EINVAL;
-  }
-  const int cls = bf3_class(a.M);
-  if (cls >= 2 && opts().small_grid) {
-    // small grids (short or single utterances): 64 x 128 tiles instead of the 128-accumulator ones,
-    // same MFMA sequence per output element, bit-identical result (cf. conv32_pick_cfg)
-    const TileBf3& t = kBf3[cls];
-    const int bm = 32 * t.MI * t.WM, bn = 32 * t.NI * t.WN;
-    const long long nwg = (long long)((Lmax_out + bn - 1) / bn) * ((a.M + bm - 1) / bm) * B;
-    if (nwg < 256LL * opts().small_grid) return launch_bf3_t<1, 2, 2, 2>(a, B, Lmax_out, stream);
-  }
-  switch (cls) {
-    case 0: return launch_bf3_t<1, 2, 1, 4>(a, B, Lmax_out, stream);
-    case 1: return launch_bf3_t<1, 2, 2, 2>(a, B, Lmax_out, stream);
-    case 2: return launch_bf3_t<2, 4, 2, 2>(a, B, Lmax_out, stream);
-    default: return launch_bf3_t<2, 4, 4, 1>(a, B, Lmax_out, stream);
+  ConvBf3Plan p;
+  const int rc = conv_bf3_plan(a.M, a.KS, a.dil, a.groups, B, Lmax_out, p);
+  if (rc) return rc;
+  // (launch_conv has checked what the staging relies on: x 16-byte aligned, ldx a multiple of 4 -- whole quads clamp to [0, ldx - 4])
+  switch (p.tile) {
+    case 0: return launch_bf3_t<1, 2, 1, 4>(a, p, B, Lmax_out, stream);
+    case 1: return launch_bf3_t<1, 2, 2, 2>(a, p, B, Lmax_out, stream);
+    case 2: return launch_bf3_t<2, 4, 2, 2>(a, p, B, Lmax_out, stream);
+    default: return launch_bf3_t<2, 4, 4, 1>(a, p, B, Lmax_out, stream);
   }
 }
 

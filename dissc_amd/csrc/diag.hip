@@ -1,5 +1,5 @@
-// Stand-alone entry points for tests and diagnostics: one conv, one transposed conv, one residual pair per call (weights packed per
-// call), what a shape would launch, and the per-launch benchmarks.  Host only: no kernel here.
+// Stand-alone entry points for tests and diagnostics: one conv, one transposed conv, one residual pair, one split-bf16 ResBlock per
+// call (weights packed per call), what a shape would launch, and the per-launch benchmarks.  Host only: no kernel here.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -97,34 +97,59 @@ static int conv_once(DevConv& dc, const float* x, float* y, const Batch& bt, int
   return rc;
 }
 
-int dissc_conv1d(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths, int B, int Cin,
-                 int Cout, int k, int dilation, int ldx, int ldo, int Lmax, float in_slope, void* stream) {
-  if (!x || !w_host || !y || k % 2 != 1 || dilation < 1) {
-    set_error("dissc_conv1d: bad argument");
+// prec = 1: the layer must come out of conv_geometry under PrecScope(1) as a split-bf16 one -- the very function make_conv packs
+// by -- or the entry refuses, before anything is packed or uploaded: a test of conv_bf3_kernel never runs fp32 unnoticed
+static int prec_available(const char* who, int prec, int Cout, int Cin, int k, int dilation) {
+  if (prec != 1) return DISSC_OK;
+  DevConv dc;  // geometry only
+  PrecScope prec_scope(1);
+  conv_geometry(dc, Cout, Cin, k, dilation, 1, 1, -1);
+  if (dc.prec != 1) {
+    set_error("%s: no split-bf16 instance for %d rows, k = %d, dilation %d (>= 32 rows, taps spanning <= %d columns, not the big "
+              "1x1 layers)", who, dc.M, dc.KS, dc.dil, MAX_TAP_SPAN);
     return DISSC_EINVAL;
   }
+  return DISSC_OK;
+}
+
+int dissc_conv1d_prec(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths, int B, int Cin,
+                      int Cout, int k, int dilation, int ldx, int ldo, int Lmax, float in_slope, int prec, void* stream) {
+  if (!x || !w_host || !y || k % 2 != 1 || dilation < 1 || (prec != 0 && prec != 1)) {
+    set_error("dissc_conv1d: bad argument (prec %d: 0 = fp32, 1 = split-bf16)", prec);
+    return DISSC_EINVAL;
+  }
+  int rc = prec_available("dissc_conv1d_prec", prec, Cout, Cin, k, dilation);
+  if (rc) return rc;
   // "wino" / "wino8" / "wino8_r4" = 2: this entry takes the transform-domain forms too (tests)
   DevConv dc;
-  int rc;
-  if (opts().wino8 >= 2 && wino8_supported(Cout, Cin, k, dilation))
-    rc = make_wino8(w_host, bias_host, Cout, k, dilation, dc, opts().wino8_r4 >= 2 && wino8_r4_supported(Cout, k, dilation) ? 4 : 3);
-  else if (opts().wino >= 2 && wino_supported(Cout, Cin, k, dilation))
-    rc = make_wino(w_host, bias_host, Cout, k, dilation, dc);
-  else
-    rc = make_conv(w_host, bias_host, Cout, Cin, k, dilation, dc);
+  {
+    PrecScope prec_scope(prec);
+    if (!prec && opts().wino8 >= 2 && wino8_supported(Cout, Cin, k, dilation))
+      rc = make_wino8(w_host, bias_host, Cout, k, dilation, dc, opts().wino8_r4 >= 2 && wino8_r4_supported(Cout, k, dilation) ? 4 : 3);
+    else if (!prec && opts().wino >= 2 && wino_supported(Cout, Cin, k, dilation))
+      rc = make_wino(w_host, bias_host, Cout, k, dilation, dc);
+    else
+      rc = make_conv(w_host, bias_host, Cout, Cin, k, dilation, dc);
+  }
   if (rc) return rc;
   return conv_once(dc, x, y, batch_of(lengths, 1, B, Lmax), ldx, ldo, in_slope, (hipStream_t)stream);
+}
+
+int dissc_conv1d(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths, int B, int Cin,
+                 int Cout, int k, int dilation, int ldx, int ldo, int Lmax, float in_slope, void* stream) {
+  return dissc_conv1d_prec(x, w_host, bias_host, y, lengths, B, Cin, Cout, k, dilation, ldx, ldo, Lmax, in_slope, 0, stream);
 }
 
 // Diagnostics / tests: ONE residual pair y = x + conv_1(lrelu(conv_d(lrelu(x)))) (or its MRF modes) on device data with
 // host weights, through a chosen implementation: mode 0 = two direct conv launches, 1 = the fused direct pair
 // (respair.hip), 2 = two conv_wino launches, 3 = the fused transform-domain pair (pair_host.hip), 4 = two transform-domain
-// launches in the forms the plan gives a PairForm::td pair of the shape (td_conv_form).  Synchronous.
+// launches in the forms the plan gives a PairForm::td pair of the shape (td_conv_form), 5 = two direct launches packed for
+// split-bf16 (conv_bf3_kernel: how the 128- and 256-channel pairs run under "precision" = 1).  Synchronous.
 static int pair_run(int mode, const DiagScope& d, const float* x, float* tmp, float* y, const Batch& bt, const EpiSpec& ep, int C,
                     int ld, float slope, hipStream_t st) {
   int rc;
   switch (mode) {
-    case 0: case 2: case 4:  // two launches, t through tmp
+    case 0: case 2: case 4: case 5:  // two launches, t through tmp
       if ((rc = run_conv(d.c1, x, tmp, bt, EpiSpec(), C, ld, ld, slope, st))) return rc;
       return run_conv(d.c2, tmp, y, bt, epi_of(ep.epi, x, ep.acc, ep.mrf_div), C, ld, ld, slope, st);
     case 1:
@@ -157,6 +182,8 @@ static int pair_make(int mode, const float* w1, const float* b1, const float* w2
     if ((rc = make_pair_conv(td_conv_form(C, k, d), w1, b1, C, k, d, c1))) return rc;
     return make_pair_conv(td_conv_form(C, k, 1), w2, b2, C, k, 1, c2);
   }
+  if (mode == 5 && ((rc = prec_available("pair mode 5", 1, C, C, k, d)) || (rc = prec_available("pair mode 5", 1, C, C, k, 1)))) return rc;
+  PrecScope prec_scope(mode == 5 ? 1 : 0);
   if ((rc = make_conv(w1, b1, C, C, k, d, c1))) return rc;
   return make_conv(w2, b2, C, C, k, 1, c2);
 }
@@ -172,13 +199,78 @@ int dissc_respair1d(const float* x, const float* w1_host, const float* b1_host, 
   DiagScope ds;
   float* tmp = nullptr;
   int rc = pair_make(mode, w1_host, b1_host, w2_host, b2_host, C, k, dilation, ds);
-  if (!rc && (mode == 0 || mode == 2 || mode == 4) && ds.alloc(&tmp, (size_t)B * C * ld) != hipSuccess) {
+  if (!rc && (mode == 0 || mode == 2 || mode == 4 || mode == 5) && ds.alloc(&tmp, (size_t)B * C * ld) != hipSuccess) {
     set_error("dissc_respair1d: hipMalloc");
     rc = DISSC_ENOMEM;
   }
   if (!rc)
     rc = pair_run(mode, ds, x, tmp, y, batch_of(lengths, 1, B, Lmax), epi_of(epi, nullptr, acc, mrf_div), C, ld, slope, (hipStream_t)stream);
   return drained(rc, (hipStream_t)stream);
+}
+
+// Diagnostics / tests: residual pairs [m0, m1) of ONE ResBlock1 in split-bf16 arithmetic on resblock_bf3_kernel, as the generator
+// launches it under "precision" = 1: the whole block (m0 = 0, m1 = 3) or a pair at a time, chained through EPI_STORE.  x / acc on
+// the device, the six weights [C,C,k] and biases [C] on the host in execution order (c1_0, c2_0, c1_1, c2_1, c1_2, c2_2).  Synchronous.
+int dissc_resblock1d_bf3(const float* x, const float* const* w6_host, const float* const* b6_host, float* acc, const int32_t* lengths,
+                         int B, int C, int k, const int32_t* dil3, int ld, int Lmax, float slope, int epi, float mrf_div, int m0, int m1,
+                         void* stream) {
+  if (!x || !w6_host || !b6_host || !acc || !dil3 || x == acc) {
+    set_error("dissc_resblock1d_bf3: bad argument (null pointer, or acc aliasing x)");
+    return DISSC_EINVAL;
+  }
+  for (int l = 0; l < 6; ++l)
+    if (!w6_host[l] || !b6_host[l]) {
+      set_error("dissc_resblock1d_bf3: weight or bias %d is null", l);
+      return DISSC_EINVAL;
+    }
+  const int dil[3] = {dil3[0], dil3[1], dil3[2]};
+  ResblockBf3Plan plan;  // refuses an unsupported (C, k, dil) or [m0, m1) before anything is packed or uploaded
+  int rc = resblock_bf3_plan(C, k, dil, m0, m1, plan);
+  if (rc) return rc;
+  std::vector<float> fw, fb;
+  pack_resblock_bf3(C, k, w6_host, fw);
+  for (int l = 0; l < 6; ++l) fb.insert(fb.end(), b6_host[l], b6_host[l] + C);
+  DiagScope ds;
+  float *dw = nullptr, *db = nullptr;
+  if (ds.alloc(&dw, fw.size()) != hipSuccess || ds.alloc(&db, fb.size()) != hipSuccess) {
+    set_error("dissc_resblock1d_bf3: hipMalloc");
+    return DISSC_ENOMEM;
+  }
+  DISSC_HIP_CHECK(hipMemcpy(dw, fw.data(), fw.size() * sizeof(float), hipMemcpyHostToDevice));
+  DISSC_HIP_CHECK(hipMemcpy(db, fb.data(), fb.size() * sizeof(float), hipMemcpyHostToDevice));
+  Bf3Block blk;
+  blk.C = C; blk.KS = k; blk.dil = dil; blk.wpack = dw; blk.bias = db;
+  rc = launch_resblock_bf3(blk, x, batch_of(lengths, 1, B, Lmax), epi_of(epi, nullptr, acc, mrf_div), ld, slope, m0, m1,
+                           (hipStream_t)stream);
+  return drained(rc, (hipStream_t)stream);
+}
+
+// Diagnostics: what the split-bf16 kernels of the generator would launch, from the planning functions the launches themselves call.
+// dil3 == NULL: the conv_bf3_kernel tile of a Cin -> Cout conv of k taps and `dilation` (for a ConvTranspose phase group: its GEMM
+// rows and taps, dissc_conv_info) on B utterances of at most Lmax columns under the current option defaults; DISSC_EINVAL where
+// the layer gets no split-bf16 instance.  dil3 != NULL: the resblock_bf3_kernel window of pairs [m0, m1) of a block of C = Cout
+// channels.  Host only: no HIP call.
+int dissc_bf3_info(int Cout, int Cin, int k, int dilation, int B, int Lmax, const int32_t* dil3, int m0, int m1, DisscBf3Info* out) {
+  DisscBf3Info o = {};
+  if (!dil3) {
+    if (Cin < 1 || Cout < 1 || k < 1 || dilation < 1) {
+      set_error("dissc_bf3_info: bad argument");
+      return DISSC_EINVAL;
+    }
+    int rc = prec_available("dissc_bf3_info", 1, Cout, Cin, k, dilation);
+    ConvBf3Plan p;
+    if (!rc) rc = conv_bf3_plan(Cout, k, dilation, 1, B, Lmax, p);
+    if (rc) return rc;
+    o.bm = p.BM; o.bn = p.BN; o.small_grid = p.small; o.tile = p.tile;
+  } else {
+    const int dil[3] = {dil3[0], dil3[1], dil3[2]};
+    ResblockBf3Plan p;
+    const int rc = resblock_bf3_plan(Cout, k, dil, m0, m1, p);
+    if (rc) return rc;
+    o.bn = p.BN; o.cols = p.COLS; o.h4 = p.H4; o.pad = p.PAD;
+  }
+  if (out) *out = o;
+  return DISSC_OK;
 }
 
 // Diagnostics: the form and tile of what mode 3 of dissc_respair1d / dissc_pair_bench builds under the current option
@@ -269,20 +361,35 @@ int dissc_pair_bench(int B, int C, int k, int dilation, int L, int epi, int iter
   return time_launches(ds, iters, [&]() { return pair_run(mode, ds, x, t, y, bt, ep, C, ld, 0.1f, nullptr); }, ms_out);
 }
 
-int dissc_conv_transpose1d(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths, int B,
-                           int Cin, int Cout, int k, int stride, int ldx, int ldo, int Lmax, float in_slope, void* stream) {
-  if (!x || !w_host || !y || stride < 1 || (k - stride) % 2 != 0) {
-    set_error("dissc_conv_transpose1d: bad argument");
+int dissc_conv_transpose1d_prec(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths, int B,
+                                int Cin, int Cout, int k, int stride, int ldx, int ldo, int Lmax, float in_slope, int prec,
+                                void* stream) {
+  if (!x || !w_host || !y || stride < 1 || (k - stride) % 2 != 0 || (prec != 0 && prec != 1)) {
+    set_error("dissc_conv_transpose1d: bad argument (prec %d: 0 = fp32, 1 = split-bf16)", prec);
     return DISSC_EINVAL;
   }
+  std::vector<ConvTGroup> plan;
+  convT_groups(Cout, k, stride, plan);
+  int rc = DISSC_OK;
+  for (const ConvTGroup& g : plan)  // every phase group, before anything is packed
+    if (!rc) rc = prec_available("dissc_conv_transpose1d_prec", prec, Cout * g.np, Cin, g.ntap, 1);
+  if (rc) return rc;
   std::vector<DevConv> grp;
-  int rc = make_convT(w_host, bias_host, Cin, Cout, k, stride, grp);
+  {
+    PrecScope prec_scope(prec);
+    rc = make_convT(w_host, bias_host, Cin, Cout, k, stride, grp);
+  }
   for (auto& dc : grp) {
     int r2 = rc ? rc : conv_once(dc, x, y, batch_of(lengths, 1, B, Lmax), ldx, ldo, in_slope, (hipStream_t)stream);
     if (rc) free_conv(dc);
     rc = rc ? rc : r2;
   }
   return rc;
+}
+
+int dissc_conv_transpose1d(const float* x, const float* w_host, const float* bias_host, float* y, const int32_t* lengths, int B,
+                           int Cin, int Cout, int k, int stride, int ldx, int ldo, int Lmax, float in_slope, void* stream) {
+  return dissc_conv_transpose1d_prec(x, w_host, bias_host, y, lengths, B, Cin, Cout, k, stride, ldx, ldo, Lmax, in_slope, 0, stream);
 }
 
 // Diagnostics: average ms of `iters` launches of one conv layer on synthetic data.

@@ -19,6 +19,9 @@
 //     [t0, t0 + BN) is written back.  HBM traffic: one read of x, one read-modify-write of acc.
 // The reference's per-layer zero padding is reproduced by forcing every published value to 0
 // outside the utterance's [0, len).
+// On its own: dissc_resblock1d_bf3 (diag.hip) runs pairs [m0, m1) of one block; dissc_bf3_info reports resblock_bf3_plan, the
+// window a launch takes.  All nine instances as one launch and as three, which must agree bit for bit (a column's k-step
+// sequence does not depend on where its window starts): tests/test_gpu_gen_split_bf16.py.
 #include <string.h>
 
 #include <algorithm>
@@ -366,14 +369,41 @@ void pack_resblock_bf3(int C, int KS, const float* const* w6, std::vector<float>
         }
 }
 
-template <int C, int KS, int NW, int NI>
-static int launch_bf3(ResblockBf3Args a, int B, int Lmax, hipStream_t stream) {
-  constexpr int COLS = 16 * NW * NI, XW = COLS + 2 * bf3_pad(C, KS);
+// The instance of (C, KS) and the window of pairs [m0, m1): what launch_resblock_bf3 launches.  Host only.
+//   C = 64: 256-column windows fill the CU's 160 KB of LDS
+//   C = 32: 512-column windows (135-145 KB of LDS): one workgroup of 8 waves per CU
+//   C = 16: 512-column windows, two workgroups per CU overlap each other's memory phases (1024-column windows recompute less halo,
+//           but fit one workgroup per CU)
+int resblock_bf3_plan(int C, int KS, const int* dil, int m0, int m1, ResblockBf3Plan& p) {
+  if (!dil || !resblock_bf3_supported(C, KS, dil)) {
+    set_error("launch_resblock_bf3: no instance for C = %d, k = %d (C = 16 / 32 / 64, k = 3 / 7 / 11, dilations 1 .. 5)", C, KS);
+    return DISSC_EINVAL;
+  }
+  if (m0 < 0 || m1 > 3 || m0 >= m1) {
+    set_error("launch_resblock_bf3: pairs [%d, %d) of a block's three", m0, m1);
+    return DISSC_EINVAL;
+  }
+  p.NW = 8;
+  p.NI = C == 64 ? 2 : 4;
+  p.COLS = 16 * p.NW * p.NI;
+  p.PAD = bf3_pad(C, KS);
   const int P2 = (KS - 1) / 2;
   int H = 0;
-  for (int m = a.m0; m < a.m1; ++m) H += P2 * (a.dil[m] + 1);
-  a.H4 = (H + 3) & ~3;
-  a.BN = COLS - 2 * a.H4;
+  for (int m = m0; m < m1; ++m) H += P2 * (dil[m] + 1);
+  p.H4 = (H + 3) & ~3;
+  p.BN = p.COLS - 2 * p.H4;
+  return DISSC_OK;
+}
+
+template <int C, int KS, int NW, int NI>
+static int launch_bf3(ResblockBf3Args a, const ResblockBf3Plan& p, int B, int Lmax, hipStream_t stream) {
+  constexpr int COLS = 16 * NW * NI, XW = COLS + 2 * bf3_pad(C, KS);
+  if (p.COLS != COLS || p.PAD != bf3_pad(C, KS) || p.BN < 4) {
+    set_error("launch_resblock_bf3: plan of %d columns (centre %d) on the %d-column instance", p.COLS, p.BN, COLS);
+    return DISSC_EINVAL;
+  }
+  a.H4 = p.H4;
+  a.BN = p.BN;
   const size_t lds = (size_t)4 * (C / 8) * XW * 16;
   static DeviceOnce attr_once;  // per device (common.h)
   DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&resblock_bf3_kernel<C, KS, NW, NI>), 160 * 1024));
@@ -386,8 +416,20 @@ static int launch_bf3(ResblockBf3Args a, int B, int Lmax, hipStream_t stream) {
 int launch_resblock_bf3(const Bf3Block& blk, const float* x, const Batch& bt, const EpiSpec& ep, int ld, float slope, int m0, int m1,
                         hipStream_t stream) {
   const int C = blk.C, KS = blk.KS, B = bt.B, Lmax = bt.Lmax;
-  if (!resblock_bf3_supported(C, KS, blk.dil) || m0 < 0 || m1 > 3 || m0 >= m1) {
-    set_error("launch_resblock_bf3: C=%d k=%d unsupported", C, KS);
+  ResblockBf3Plan p;
+  const int rc = resblock_bf3_plan(C, KS, blk.dil, m0, m1, p);
+  if (rc) return rc;
+  if (B <= 0 || Lmax <= 0) {
+    set_error("launch_resblock_bf3: batch of %d utterances of at most %d columns", B, Lmax);
+    return DISSC_EINVAL;
+  }
+  // the window load, the MRF update and the clamp of whole quads to [0, ld - 4] move 16 bytes at a time
+  if (ld < 4 || ld % 4 != 0 || !x || !ep.acc || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(ep.acc) & 15)) {
+    set_error("launch_resblock_bf3: x and acc must be 16-byte aligned with a row stride that is a multiple of 4 (ld %d)", ld);
+    return DISSC_EINVAL;
+  }
+  if (ep.epi != EPI_STORE && ep.epi != EPI_MRF_SET && ep.epi != EPI_MRF_ADD && ep.epi != EPI_MRF_DIV) {
+    set_error("launch_resblock_bf3: epilogue %d (EPI_STORE or an MRF mode)", ep.epi);
     return DISSC_EINVAL;
   }
   ResblockBf3Args a;
@@ -396,21 +438,19 @@ int launch_resblock_bf3(const Bf3Block& blk, const float* x, const Batch& bt, co
   a.dil[0] = blk.dil[0]; a.dil[1] = blk.dil[1]; a.dil[2] = blk.dil[2];
   a.ld = ld; a.bstride = (long long)C * ld; a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi;
   a.BN = 0; a.H4 = 0; a.m0 = m0; a.m1 = m1;
-  if (C == 64) {  // 256-column windows fill the CU's 160 KB of LDS
-    if (KS == 3) return launch_bf3<64, 3, 8, 2>(a, B, Lmax, stream);
-    if (KS == 7) return launch_bf3<64, 7, 8, 2>(a, B, Lmax, stream);
-    return launch_bf3<64, 11, 8, 2>(a, B, Lmax, stream);
+  if (C == 64) {
+    if (KS == 3) return launch_bf3<64, 3, 8, 2>(a, p, B, Lmax, stream);
+    if (KS == 7) return launch_bf3<64, 7, 8, 2>(a, p, B, Lmax, stream);
+    return launch_bf3<64, 11, 8, 2>(a, p, B, Lmax, stream);
   }
-  if (C == 32) {  // 512-column windows (135-145 KB of LDS): one workgroup of 8 waves per CU
-    if (KS == 3) return launch_bf3<32, 3, 8, 4>(a, B, Lmax, stream);
-    if (KS == 7) return launch_bf3<32, 7, 8, 4>(a, B, Lmax, stream);
-    return launch_bf3<32, 11, 8, 4>(a, B, Lmax, stream);
+  if (C == 32) {
+    if (KS == 3) return launch_bf3<32, 3, 8, 4>(a, p, B, Lmax, stream);
+    if (KS == 7) return launch_bf3<32, 7, 8, 4>(a, p, B, Lmax, stream);
+    return launch_bf3<32, 11, 8, 4>(a, p, B, Lmax, stream);
   }
-  // C = 16: 512-column windows, two workgroups per CU overlap each other's memory phases (1024-column windows recompute
-  // less halo, but fit one workgroup per CU)
-  if (KS == 3) return launch_bf3<16, 3, 8, 4>(a, B, Lmax, stream);
-  if (KS == 7) return launch_bf3<16, 7, 8, 4>(a, B, Lmax, stream);
-  return launch_bf3<16, 11, 8, 4>(a, B, Lmax, stream);
+  if (KS == 3) return launch_bf3<16, 3, 8, 4>(a, p, B, Lmax, stream);
+  if (KS == 7) return launch_bf3<16, 7, 8, 4>(a, p, B, Lmax, stream);
+  return launch_bf3<16, 11, 8, 4>(a, p, B, Lmax, stream);
 }
 
 }  // namespace dissc

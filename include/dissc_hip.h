@@ -48,7 +48,8 @@ typedef struct {
 
 const char* dissc_last_error(void);
 /* ABI version of this header: bumped when a signature changes or a section is added (5: dissc_convgrad_*;
- * 6: dissc_conv_info, and dissc_get_option reads the tile-shape keys; 7: dissc_wino8_info). */
+ * 6: dissc_conv_info, and dissc_get_option reads the tile-shape keys; 7: dissc_wino8_info; 8: the split-bf16 diagnostics
+ * dissc_conv1d_prec, dissc_conv_transpose1d_prec, dissc_resblock1d_bf3, dissc_bf3_info and mode 5 of dissc_respair1d). */
 int dissc_abi_version(void);
 /* Number of HIP devices visible / name of device `dev` (for diagnostics). */
 int dissc_device_count(void);
@@ -127,6 +128,16 @@ int dissc_conv1d(const float* x, const float* w_host, const float* bias_host, fl
 int dissc_conv_transpose1d(const float* x, const float* w_host, const float* bias_host, float* y,
                            const int32_t* lengths, int B, int Cin, int Cout, int k, int stride,
                            int ldx, int ldo, int Lmax, float in_slope, void* stream);
+/* The same two with the arithmetic given: prec 0 = exactly the entries above, 1 = the generator's split-bf16 mode ("precision" = 1:
+ * conv_bf3_kernel, csrc/conv_bf3.hip).  prec = 1 is DISSC_EINVAL with a message, before anything is packed, where the layer (or a
+ * phase group of the ConvTranspose) gets no split-bf16 instance -- fewer than 32 GEMM rows, taps spanning more than 60 columns,
+ * the big 1x1 layers -- and where x is not 16-byte aligned or ldx no multiple of 4: it never runs fp32 instead. */
+int dissc_conv1d_prec(const float* x, const float* w_host, const float* bias_host, float* y,
+                      const int32_t* lengths, int B, int Cin, int Cout, int k, int dilation, int ldx,
+                      int ldo, int Lmax, float in_slope, int prec, void* stream);
+int dissc_conv_transpose1d_prec(const float* x, const float* w_host, const float* bias_host, float* y,
+                                const int32_t* lengths, int B, int Cin, int Cout, int k, int stride,
+                                int ldx, int ldo, int Lmax, float in_slope, int prec, void* stream);
 
 /* Stride-2 VALID conv (HuBERT's feature convs; reference data/encode.py:21-22,32 via fairseq ConvFeatureExtractionModel):
  * x f32 [B,Cin,ldx] -> y f32 [B,Cout,ldo] with (len - k) / 2 + 1 outputs per utterance, no padding; w HOST [Cout,Cin,k];
@@ -258,7 +269,8 @@ int dissc_conv_bench(int B, int Cin, int Cout, int k, int dilation, int L, int e
  * (conv_wino), 3 = the fused transform-domain pair (C = 16 with k = 11, C = 32 with k = 7 / 11, C = 64 with k = 3 / 7 / 11, in
  * the form dissc_pair_info reports under the current options), 4 = two transform-domain launches in the forms the generator's
  * plan gives the shape under the current options when it does not fuse the pair (F(4,3) on conv_wino, F(6,3) or F(5,4) on
- * conv_wino8, per conv).
+ * conv_wino8, per conv), 5 = two direct launches packed for split-bf16 (conv_bf3_kernel, the epilogue on the second: how the
+ * generator runs its 128- and 256-channel pairs under "precision" = 1; DISSC_EINVAL where the shape gets no such instance).
  * y must not alias x.  dissc_respair1d synchronises the stream; dissc_pair_bench times `iters` launches on synthetic data. */
 int dissc_respair1d(const float* x, const float* w1_host, const float* b1_host, const float* w2_host, const float* b2_host,
                     float* y, float* acc, const int32_t* lengths, int B, int C, int k, int dilation, int ld, int Lmax,
@@ -297,6 +309,32 @@ typedef struct {
   int32_t unit, ot, cpr, gx, gy;
 } DisscWino8Plan;
 int dissc_wino8_info(int C, int k, int dilation, int R, int B, int Lmax, DisscWino8Plan* out);
+
+/* Diagnostics / tests: residual pairs [m0, m1) of ONE ResBlock1 (three pairs x_k += conv_1(lrelu(conv_d(lrelu(x_k)))), d =
+ * dil3[0..2]) in split-bf16 arithmetic on resblock_bf3_kernel (csrc/resblock_bf3.hip), as the generator launches it under
+ * "precision" = 1: the whole block (m0 = 0, m1 = 3; C = 16 / 32) or one pair per launch chained through epi 0 (C = 64).
+ * x f32 [B,C,ld] on the device; w6_host / b6_host: six HOST pointers [C,C,k] / [C] in execution order (c1_0, c2_0, c1_1, c2_1,
+ * c1_2, c2_2); acc f32 [B,C,ld] on the device, updated on [0, len) only: epi 0 acc = x_k (a partial block), 2 acc = x_k, 3 acc += x_k,
+ * 4 acc = (acc + x_k) / mrf_div.  DISSC_EINVAL with a message, nothing launched: C not 16 / 32 / 64, k not 3 / 7 / 11, a dilation
+ * outside 1 .. 5, m0 >= m1 or outside [0, 3], another epi, B or Lmax <= 0, ld < 4 or no multiple of 4, x or acc not 16-byte
+ * aligned, acc aliasing x.  Synchronises the stream. */
+int dissc_resblock1d_bf3(const float* x, const float* const* w6_host, const float* const* b6_host, float* acc,
+                         const int32_t* lengths, int B, int C, int k, const int32_t* dil3, int ld, int Lmax, float slope,
+                         int epi, float mrf_div, int m0, int m1, void* stream);
+/* What the generator's split-bf16 kernels would launch, answered by the planning functions the launches themselves call.
+ * dil3 == NULL: the conv_bf3_kernel tile of a Cin -> Cout conv of k taps and `dilation` (for a phase group of a ConvTranspose:
+ * its GEMM rows and taps as dissc_conv_info reports them, dilation 1) on B utterances of at most Lmax columns under the current
+ * option defaults ("small_grid"): bm x bn, `tile` its index in the kernel's table (0 .. 3 by row class 32 / 64 / 128 / 256),
+ * small_grid = 1 where a layer of >= 128 rows steps down to the 64 x 128 tile; DISSC_EINVAL where the layer gets no split-bf16
+ * instance.  dil3 != NULL: the resblock_bf3_kernel window of pairs [m0, m1) of a block of C = Cout channels and k taps (Cin,
+ * dilation, B, Lmax unused): `cols` window columns per workgroup, `pad` LDS padding columns on each side, `h4` halo columns on
+ * each side, bn = cols - 2 h4 centre columns written.  Host only: no GPU is touched. */
+typedef struct {
+  int32_t bm, bn, small_grid, tile;
+  int32_t cols, h4, pad;
+} DisscBf3Info;
+int dissc_bf3_info(int Cout, int Cin, int k, int dilation, int B, int Lmax, const int32_t* dil3, int m0, int m1,
+                   DisscBf3Info* out);
 
 /* ------------------------------------------------------------------------- *
  * Length / pitch predictors and infer.py's integer sample logic.

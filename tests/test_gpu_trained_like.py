@@ -288,8 +288,9 @@ def test_trained_like_residual_pairs(tl, stage, j):
 @pytest.mark.parametrize("name", ["conv_pre"] + [f"ups.{i}" for i in range(5)])
 def test_trained_like_outer_layers_on_the_direct_kernels(tl, name):
     """conv_pre (no activation on its input) and the five ConvTranspose1d layers on their float64-oracle inputs, direct
-    kernels: e_rms within 4x of CPU fp32.  (conv_post runs on its own fused kernel with the tanh, gen_misc.hip, which has no
-    stand-alone entry: the whole-generator tests below cover it.)"""
+    kernels: e_rms within 4x of CPU fp32.  (Their split-bf16 forms on conv_bf3_kernel have stand-alone entries of their own,
+    dissc_conv1d_prec / dissc_conv_transpose1d_prec: tests/test_gpu_gen_split_bf16.py.  Only conv_post, on its own fused kernel
+    with the tanh in gen_misc.hip and fp32 in both modes, is reached through the whole-generator tests below alone.)"""
     h = tl["synth"].VCTK_CONFIG
     w, b = tl["folded"][name + ".weight"], tl["folded"][name + ".bias"]
     tap = tl["inp"][name]
