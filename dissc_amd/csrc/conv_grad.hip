@@ -18,36 +18,24 @@
 //   * Narrow layers.  With Cin <= 16 the 32 B columns hold TS = 32 / CIB taps of CIB = 16 (8, 4, ..) channels each, so a
 //     C = 16, k = 11 layer issues 6 MFMAs per step instead of 11; with Cin <= 64 the four waves that would sit on absent
 //     channel blocks split the chunk's positions instead (WT = 2 or 4 time slices, each its own partial).
-//   * Tap offsets are off_j = off0 + j dstep with |off_j| <= 32: nothing ties them to (k - 1) d / 2, which is what a
-//     ConvTranspose1d's weight gradient (a stride-1 correlation of x with the phase planes of gy) will need.
+//   * Tap offsets are off_j = off0 + j dstep with |off_j| <= 32: nothing ties them to (k - 1) d / 2.  A ConvTranspose1d's
+//     weight gradient (a stride-1 correlation of x with the phase planes of gy) is conv_grad_t.hip's kernel: this one with a
+//     (plane, shift) per tap; it shares the plan, the reduction and the bias kernels below through conv_grad.h.
 #include <string.h>
 
 #include <algorithm>
 
-#include "common.h"
+#include "conv_grad.h"
 
 namespace dissc {
 
-constexpr int CG_T = DISSC_CONVGRAD_CHUNK;  // positions per chunk
 constexpr int CG_HALO = 32;                 // largest |tap offset|, rounded up to 4 (MAX_TAP_SPAN / 2 = 30)
 constexpr int CG_LDD = CG_T + 1;            // odd row strides: a fragment read (32 rows x 1 column) is conflict-free
 constexpr int CG_LDA = CG_T + 2 * CG_HALO + 1;
-constexpr int CG_MAX_K = 11;
 constexpr size_t CG_PART_BUDGET = (size_t)56 << 20;  // bytes of partials (the workspace stays under 64 MB)
 constexpr int CG_TARGET_WG = 512;           // two workgroups per CU
-typedef float cg_f32x16 __attribute__((ext_vector_type(16)));
 
-struct CgPlan {
-  int WCI, WT;    // waves of a workgroup: WCI blocks of 32 input channels x WT time slices of a chunk
-  int CIB, TS;    // B columns: TS taps x CIB channels (CIB = 32: one tap)
-  int NG;         // tap groups = accumulators per wave
-  int coT, ciS;   // output tiles, input super-blocks (grid x, y)
-  int nch;        // chunks per utterance
-  int P, cpp;     // partials per output tile (grid z), (utterance, chunk) pairs per partial
-  size_t gw;      // floats of one gradient
-};
-
-static CgPlan cg_plan(int Cin, int Cout, int K, int B, int Lmax) {
+CgPlan cg_plan(int Cin, int Cout, int K, int B, int Lmax) {
   CgPlan p;
   p.WCI = Cin > 64 ? 4 : (Cin > 32 ? 2 : 1);
   p.WT = 4 / p.WCI;
@@ -207,12 +195,13 @@ __device__ __forceinline__ double cg_block_sum_d(double v, double* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// bpart[b][co] = sum_{t < len_b} gy[b][co][t]
+// bpart[b][co] = sum_{t < len_b} gy[b][co][t], len_b = lengths[b] * len_mul (a ConvTranspose1d's rows are stride times its lengths)
 __global__ void __launch_bounds__(256) convgrad_bias_part_kernel(const float* __restrict__ gy, const int32_t* __restrict__ lengths,
-                                                                 int Cout, int Lmax, int ldo, double* __restrict__ bpart) {
+                                                                 int len_mul, int Cout, int Lmax, int ldo,
+                                                                 double* __restrict__ bpart) {
   __shared__ double red[4];
   const int co = blockIdx.x, b = blockIdx.y;
-  int len = lengths ? lengths[b] : Lmax;
+  int len = lengths ? lengths[b] * len_mul : Lmax;
   len = len < 0 ? 0 : (len > Lmax ? Lmax : len);
   const float* row = gy + ((size_t)b * Cout + co) * ldo;
   double s = 0.0;
@@ -292,6 +281,16 @@ static int cg_launch_wgrad(const WgradArgs& a, const CgPlan& p, hipStream_t st) 
   return DISSC_OK;
 }
 
+void cg_launch_reduce(const float* part, int NP, size_t n, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(convgrad_reduce_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, part, NP, n, out);
+}
+
+void cg_launch_bias(const float* gy, const int32_t* lengths, int len_mul, int B, int Cout, int Lmax, int ldo, double* bpart,
+                    float* gb, hipStream_t st) {
+  hipLaunchKernelGGL(convgrad_bias_part_kernel, dim3(Cout, B), dim3(256), 0, st, gy, lengths, len_mul, Cout, Lmax, ldo, bpart);
+  hipLaunchKernelGGL(convgrad_bias_reduce_kernel, dim3((Cout + 63) / 64), dim3(64), 0, st, bpart, B, Cout, gb);
+}
+
 }  // namespace dissc
 
 using namespace dissc;
@@ -306,8 +305,6 @@ struct dissc_convgrad {
     free_conv(bwd);
   }
 };
-
-static inline size_t cg_rup(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
 static bool cg_bad_call(dissc_convgrad_t h, int B, int Lmax, const char* who) {
   if (!h || B <= 0 || Lmax <= 0 || B > 65535) {
@@ -454,12 +451,9 @@ int dissc_convgrad_backward(dissc_convgrad_t h, const float* x, const float* gy,
         rc = DISSC_EINVAL;
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(convgrad_reduce_kernel, dim3((unsigned)((p.gw + 15) / 16)), dim3(256), 0, st, part, p.P * p.WT, p.gw, gw);
+    cg_launch_reduce(part, p.P * p.WT, p.gw, gw, st);
   }
-  if (gb) {
-    hipLaunchKernelGGL(convgrad_bias_part_kernel, dim3(h->Cout, B), dim3(256), 0, st, gy, lengths, h->Cout, Lmax, ldo, bpart);
-    hipLaunchKernelGGL(convgrad_bias_reduce_kernel, dim3((h->Cout + 63) / 64), dim3(64), 0, st, bpart, B, h->Cout, gb);
-  }
+  if (gb) cg_launch_bias(gy, lengths, 1, B, h->Cout, Lmax, ldo, bpart, gb, st);
   if (gx) {
     // the same conv with W^T, taps flipped: channels swapped, gy read as zero beyond lengths
     if ((rc = run_conv(h->bwd, gy, gx, batch_of(lengths, 1, B, Lmax), EpiSpec(), h->Cout, ldo, ldx, 1.0f, st))) return rc;

@@ -755,6 +755,37 @@ int dissc_convgrad_backward(dissc_convgrad_t h, const float* x, const float* gy,
                             int ldo, int Lmax, float in_slope, float* gx, float* gw, float* gb, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * A differentiable, ragged ConvTranspose1d layer (csrc/conv_grad_t.hip): the generator's five upsamplers ups[i]
+ * (reference sr/models.py), the layers dissc_convgrad_* leaves out.  Added without an ABI bump, as the mel entries were.
+ *   y[b,co,u] = bias[co] + sum_{ci,t,kk : stride t + kk - pad = u} w[ci,co,kk] lrelu(x, in_slope)[b,ci,t],  pad = (k - stride) / 2
+ *   x f32 [B][Cin][ldx], y / gy f32 [B][Cout][ldo], 16-byte aligned, ldx and ldo multiples of 4, ldx >= Lmax and
+ *   ldo >= stride Lmax.  lengths i32 [B] on the device or NULL (= Lmax) and Lmax are INPUT positions: utterance b has
+ *   stride lengths[b] valid output positions; what lies beyond is read as zero and never written by the forward.
+ * dissc_convtgrad_create: HOST ONLY.  1 <= stride <= 8, stride <= k <= 11, k - stride even, 1 <= Cin, Cout <= 65535; anything
+ *   else is DISSC_EINVAL with a message that names the rule.
+ * dissc_convtgrad_set_weights: w_dev f32 [Cin][Cout][k] (torch's ConvTranspose1d layout) and bias_dev f32 [Cout] (NULL = no
+ *   bias) are DEVICE pointers; one kernel packs every phase group of the forward (the groups and packings of
+ *   dissc_conv_transpose1d) and the data gradient's fragments.  Call it again whenever the weights changed.
+ * dissc_convtgrad_forward: the bits of dissc_conv_transpose1d for the same weights.
+ * dissc_convtgrad_partials / _workspace_bytes: HOST ONLY, as dissc_convgrad_*: chunks of DISSC_CONVGRAD_CHUNK INPUT positions.
+ * dissc_convtgrad_backward: gx f32 [B][Cin][ldx] (times the leaky ReLU's derivative, torch's rule at x = 0; zero from
+ *   lengths[b] to ldx), gw f32 [Cin][Cout][k], gb f32 [Cout]; each may be NULL and its kernels are skipped.  No atomics, fixed
+ *   summation orders: bit-reproducible, and an utterance's gx does not depend on the batch it is in (it does on ldx: rows of
+ *   fewer than 8 tiles of 32 x 128 split each reduction in two).
+ * ------------------------------------------------------------------------- */
+typedef struct dissc_convtgrad* dissc_convtgrad_t;
+int dissc_convtgrad_create(int Cin, int Cout, int k, int stride, dissc_convtgrad_t* out);
+void dissc_convtgrad_destroy(dissc_convtgrad_t h);
+int dissc_convtgrad_set_weights(dissc_convtgrad_t h, const float* w_dev, const float* bias_dev, void* stream);
+int dissc_convtgrad_forward(dissc_convtgrad_t h, const float* x, float* y, const int32_t* lengths, int B, int ldx, int ldo,
+                            int Lmax_in, float in_slope, void* stream);
+int dissc_convtgrad_partials(dissc_convtgrad_t h, int B, int Lmax_in, int* P, int* pairs_per_partial);
+size_t dissc_convtgrad_workspace_bytes(dissc_convtgrad_t h, int B, int Lmax_in);
+int dissc_convtgrad_backward(dissc_convtgrad_t h, const float* x, const float* gy, const int32_t* lengths, int B, int ldx,
+                             int ldo, int Lmax_in, float in_slope, float* gx, float* gw, float* gb, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,13 @@ gradient leaves the mask to the leaky ReLU's own node, so its figure is a little
 blocks (ours, torch, ours, ...), each block `iters` calls between two device events.  TFLOP/s are of the EXECUTED matrix
 work: padded rows / channel chunks for the direct convs, padded 32 x 32 tiles x tap groups for the weight gradient.  One
 JSON line per shape; --markdown adds the table of profiles/conv_grad.md.
+
+    python tools/conv_grad_bench.py --transpose [--batch 32] [--frames 28] [--markdown]
+
+The same for the differentiable ConvTranspose1d (nn.conv_transpose1d, csrc/conv_grad_t.hip) on the generator's five
+upsamplers against torch's conv_transpose1d autograd (leaky_relu + conv_transpose1d; aten.convolution_backward, transposed,
+one output mask each): the table of profiles/conv_transpose_grad.md.  Its TFLOP/s are of the direct form's MACs,
+Cin Cout k per input position (the forward's phase groups execute some zero taps on top).
 """
 import argparse
 import ctypes
@@ -114,6 +121,92 @@ def bench_shape(a, cin, cout, k, d, L):
     return out
 
 
+def bench_transpose(a, cin, cout, k, s, L):
+    from dissc_amd import nn
+    from dissc_amd._lib import check, current_stream_ptr, lib
+    F = torch.nn.functional
+    dev = torch.device("cuda:0")
+    B, slope = a.batch, 0.1
+    rs = np.random.RandomState(0)
+    ld = rup(L, 4)
+    x = torch.from_numpy(rs.standard_normal((B, cin, ld)).astype(np.float32)).to(dev)
+    gy = torch.from_numpy(rs.standard_normal((B, cout, s * ld)).astype(np.float32)).to(dev)
+    w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k)) / np.sqrt(cin * k / s)).astype(np.float32)).to(dev)
+    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)).to(dev)
+    lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
+    y, gx, gw, gb = torch.zeros_like(gy), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
+    h = nn._handle_t(cin, cout, k, s, dev)
+    st = current_stream_ptr(dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    nws = int(lib.dissc_convtgrad_workspace_bytes(h, B, ld))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    check(lib.dissc_convtgrad_set_weights(h, p(w), p(b), st), "set_weights")
+    pad = (k - s) // 2
+
+    def ours_bwd(gx_, gw_, gb_):
+        check(lib.dissc_convtgrad_backward(h, p(x), p(gy), p(lengths), B, ld, s * ld, ld, slope, gx_, gw_, gb_, p(ws), nws, st),
+              "backward")
+
+    xa = F.leaky_relu(x, slope)
+    conv_bwd = torch.ops.aten.convolution_backward
+
+    def torch_bwd(mask):
+        return conv_bwd(gy, xa, w, [cout], [s], [pad], [1], True, [0], 1, mask)
+
+    cases = {
+        "fwd": lambda: check(lib.dissc_convtgrad_forward(h, p(x), p(y), p(lengths), B, ld, s * ld, ld, slope, st), "forward"),
+        "torch_fwd": lambda: F.conv_transpose1d(F.leaky_relu(x, slope), w, b, stride=s, padding=pad),
+        "dgrad": lambda: ours_bwd(p(gx), None, None),
+        "torch_dgrad": lambda: torch_bwd([True, False, False]),
+        "wgrad": lambda: ours_bwd(None, p(gw), p(gb)),
+        "torch_wgrad": lambda: torch_bwd([False, True, True]),
+        "repack": lambda: check(lib.dissc_convtgrad_set_weights(h, p(w), p(b), st), "set_weights"),
+    }
+    cases["fwd"](), cases["dgrad"](), cases["wgrad"]()
+    tg = torch_bwd([True, True, True])
+    rel = lambda u, v: float((u - v).norm() / v.norm())
+    valid = (torch.arange(ld, device=dev) < L).float()
+    agree = {"y": rel(y[:, :, :s * L], cases["torch_fwd"]()[:, :, :s * L]) if ld == L else None,
+             "gx": rel(gx, tg[0] * torch.where(x > 0, 1.0, slope) * valid), "gw": rel(gw, tg[1]), "gb": rel(gb, tg[2])}
+    for fn in cases.values():
+        timed(fn, 2)
+    times = {n: [] for n in cases}
+    for _ in range(a.blocks):
+        for n, fn in cases.items():  # alternating
+            times[n].append(timed(fn, a.iters))
+    P, pairs = nn.wgrad_partials_transpose(B, ld, cin, cout, k, s)
+    out = {"transpose": True, "cin": cin, "cout": cout, "k": k, "stride": s, "L": L, "batch": B, "partials": P,
+           "pairs_per_partial": pairs, "workspace_mb": round(nws / 2**20, 2),
+           "rel_diff_to_torch": {n: None if v is None else float(f"{v:.2e}") for n, v in agree.items()}}
+    for n, v in times.items():
+        out[n + "_ms"] = round(float(np.median(v)), 4)
+        out[n + "_ms_spread"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
+    for n in ("fwd", "dgrad", "wgrad"):
+        out[n + "_tflops"] = round(2.0 * cin * cout * k * B * L / (out[n + "_ms"] * 1e-3) / 1e12, 2)
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def main_transpose(a):
+    import conv_transpose_grad_ref as RT
+    rows, L = [], a.frames
+    for cin, cout, k, s in RT.ups_from_config():
+        if not a.only or [cin, cout, k] == [int(v) for v in a.only.split(",")]:
+            rows.append(bench_transpose(a, cin, cout, k, s, L))
+        L *= s
+    if a.markdown:
+        print("| layer | L in | fwd ms (torch) | dgrad ms (torch) | wgrad ms (torch) | TFLOP/s fwd / dgrad / wgrad | P | repack ms |")
+        print("|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['cin']} -> {r['cout']}, k = {r['k']}, s = {r['stride']} | {r['L']} | {r['fwd_ms']:.3f} ({r['torch_fwd_ms']:.3f}) | "
+                  f"{r['dgrad_ms']:.3f} ({r['torch_dgrad_ms']:.3f}) | {r['wgrad_ms']:.3f} ({r['torch_wgrad_ms']:.3f}) | "
+                  f"{r['fwd_tflops']} / {r['dgrad_tflops']} / {r['wgrad_tflops']} | {r['partials']} | {r['repack_ms']:.3f} |")
+        tot = lambda n: sum(r[n] for r in rows)
+        print(f"\nsum over the five upsamplers, ours (torch): fwd {tot('fwd_ms'):.2f} ({tot('torch_fwd_ms'):.2f}), "
+              f"dgrad {tot('dgrad_ms'):.2f} ({tot('torch_dgrad_ms'):.2f}), wgrad {tot('wgrad_ms'):.2f} ({tot('torch_wgrad_ms'):.2f}) ms")
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -122,7 +215,10 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--only", default=None, help="CIN,COUT,K: that shape only")
     ap.add_argument("--markdown", action="store_true")
+    ap.add_argument("--transpose", action="store_true", help="the five ConvTranspose1d upsamplers instead")
     a = ap.parse_args(argv)
+    if a.transpose:
+        return main_transpose(a)
     import conv_grad_ref as R
     seen, rows = set(), []
     for cin, cout, k, d, L in R.generator_layer_shapes(a.frames):
