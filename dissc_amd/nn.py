@@ -14,6 +14,7 @@ No torch compute op on the hot path, no CPU fallback.  First order only.
 """
 import ctypes
 
+import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -281,3 +282,491 @@ def resblock1(x, weights, k, dilations=(1, 3, 5), lengths=None, taps=None):
         x = conv1d(xt, weights[f"convs2.{m}.weight"], weights.get(f"convs2.{m}.bias"), lengths=lengths, dilation=1,
                    in_slope=LRELU_SLOPE, add=x)
     return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The rest of the generator's training step (C ABI dissc_wnorm_* / dissc_embed_concat_* / dissc_mrf_mean_* / dissc_tanh_*,
+# csrc/gen_train.hip) and the module that composes it: nn.CodeGenerator.
+# ---------------------------------------------------------------------------------------------------------------------
+def _bind_gen_train():
+    vp, i32, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    lib.dissc_wnorm_create.argtypes = [i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp)]
+    lib.dissc_wnorm_destroy.argtypes = [vp]
+    lib.dissc_wnorm_destroy.restype = None
+    lib.dissc_wnorm_offsets.argtypes = [vp, ctypes.POINTER(ll), ctypes.POINTER(ll), ctypes.POINTER(ll), ctypes.POINTER(ll)]
+    lib.dissc_wnorm_wave_cols.argtypes = []
+    lib.dissc_wnorm_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.dissc_wnorm_backward.argtypes = [vp, vp, vp, ctypes.POINTER(vp), vp, vp, ctypes.POINTER(vp), ctypes.POINTER(i32), vp, vp]
+    lib.dissc_embed_concat_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]
+    lib.dissc_embed_concat_bwd.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.dissc_mrf_mean_fwd.argtypes = [ctypes.POINTER(vp), i32, vp, vp, i32, i32, i32, i32, vp]
+    lib.dissc_mrf_mean_bwd.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp]
+    lib.dissc_tanh_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.dissc_tanh_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+
+
+_bind_gen_train()
+
+WNORM_WAVE_COLS = int(lib.dissc_wnorm_wave_cols())  # rows of up to this many columns: one wave; longer: one workgroup
+POST_SLOPE = 0.01  # F.leaky_relu's default, in front of conv_post (reference sr/models.py:110)
+
+
+def _f32(t, name, who):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise DisscError(f"{who}: {name} must be a contiguous fp32 device tensor")
+    return t
+
+
+class WeightNorm:
+    """w = g v / ||v|| over every dim but 0 for a whole list of tensors at once (dissc_wnorm_*): ``shapes`` are the tensors'
+    (rows, cols), cols the product of every dim but 0.  ``off[i]`` / ``row_off[i]`` place tensor i in the flat layouts of
+    ``total`` floats (v, w, gv; every tensor 16-byte aligned) and ``total_rows`` rows (g, gg, 1 / ||v||).  ``bias_sizes``
+    (optional): the layers' bias lengths; ``bias_off[i]`` places them, each 16-byte aligned, in ``bias_total`` floats."""
+
+    def __init__(self, shapes, bias_sizes=None):
+        n = len(shapes)
+        rows = (ctypes.c_int * max(n, 1))(*[int(r) for r, _ in shapes])
+        cols = (ctypes.c_int * max(n, 1))(*[int(c) for _, c in shapes])
+        self._h = ctypes.c_void_p()
+        check(lib.dissc_wnorm_create(n, rows, cols, ctypes.byref(self._h)), "dissc_wnorm_create")
+        self.n, self.shapes = n, [(int(r), int(c)) for r, c in shapes]
+        off, roff = (ctypes.c_longlong * n)(), (ctypes.c_longlong * n)()
+        tot, rtot = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        check(lib.dissc_wnorm_offsets(self._h, off, roff, ctypes.byref(tot), ctypes.byref(rtot)), "dissc_wnorm_offsets")
+        self.off, self.row_off, self.total, self.total_rows = list(off), list(roff), tot.value, rtot.value
+        self.has_gaps = self.total != sum(r * c for r, c in self.shapes)
+        self.bias_sizes = None if bias_sizes is None else [int(b) for b in bias_sizes]
+        self.bias_off, self.bias_total = [], 0
+        if self.bias_sizes is not None:
+            if len(self.bias_sizes) != n:
+                raise DisscError("WeightNorm: one bias size per tensor")
+            at = 0
+            for b in self.bias_sizes:
+                at = (at + 3) & ~3
+                self.bias_off.append(at)
+                at += b
+            self.bias_total = (at + 3) & ~3
+            self._bias_n = (ctypes.c_int * n)(*self.bias_sizes)
+
+    def __del__(self):
+        try:
+            lib.dissc_wnorm_destroy(self._h)
+        except Exception:
+            pass
+
+    def forward(self, v_flat, g_flat, bias_flat=None, out=None):
+        """-> (buf, inv_norm): buf = [w_flat (total) | the biases (bias_total)] in one buffer (``out``, or a new one whose
+        alignment gaps are zero), inv_norm [total_rows]"""
+        who = "WeightNorm.forward"
+        _f32(v_flat, "v_flat", who), _f32(g_flat, "g_flat", who)
+        nb = 0 if bias_flat is None else self.bias_total
+        if v_flat.numel() != self.total or g_flat.numel() != self.total_rows or (nb and _f32(bias_flat, "bias_flat", who).numel() != nb):
+            raise DisscError(f"{who}: v_flat / g_flat / bias_flat must have {self.total} / {self.total_rows} / {self.bias_total} floats")
+        dev = v_flat.device
+        if out is None:
+            out = (torch.zeros if self.has_gaps else torch.empty)(self.total + nb, dtype=torch.float32, device=dev)
+        inv = torch.empty(self.total_rows, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.dissc_wnorm_forward(self._h, _ptr(v_flat), _ptr(g_flat), _ptr(out), _ptr(inv), _ptr(bias_flat),
+                                          ctypes.c_void_p(out.data_ptr() + 4 * self.total) if nb else None, nb,
+                                          current_stream_ptr(dev)), "dissc_wnorm_forward")
+        return out, inv
+
+    def backward(self, v_flat, g_flat, gws, gbs=None, gv_out=None):
+        """gws: the layers' own weight gradients (None = zero); gbs: their bias gradients (None = zero), or None for no
+        biases at all -> (gv_flat, gg_flat, gb_flat or None)"""
+        who = "WeightNorm.backward"
+        dev = v_flat.device
+        if len(gws) != self.n or (gbs is not None and (self.bias_sizes is None or len(gbs) != self.n)):
+            raise DisscError(f"{who}: {self.n} weight gradients (and bias gradients, with bias_sizes) expected")
+        for i, t in enumerate(gws):
+            if t is not None and _f32(t, f"gws[{i}]", who).numel() != self.shapes[i][0] * self.shapes[i][1]:
+                raise DisscError(f"{who}: gws[{i}] has {t.numel()} elements, expected {self.shapes[i]}")
+        for i, t in enumerate(gbs or ()):
+            if t is not None and _f32(t, f"gbs[{i}]", who).numel() != self.bias_sizes[i]:
+                raise DisscError(f"{who}: gbs[{i}] has {t.numel()} elements, expected {self.bias_sizes[i]}")
+        pw = (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in gws])
+        pb = None if gbs is None else (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in gbs])
+        gv = gv_out if gv_out is not None else \
+            (torch.zeros if self.has_gaps else torch.empty)(self.total, dtype=torch.float32, device=dev)
+        gg = torch.empty(self.total_rows, dtype=torch.float32, device=dev)
+        gb = None if gbs is None else torch.zeros(self.bias_total, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.dissc_wnorm_backward(self._h, _ptr(v_flat), _ptr(g_flat), pw, _ptr(gv), _ptr(gg), pb,
+                                           None if gbs is None else self._bias_n, _ptr(gb), current_stream_ptr(dev)),
+                  "dissc_wnorm_backward")
+        return gv, gg, gb
+
+
+class _WeightsFn(torch.autograd.Function):
+    """(v_flat, g_flat, bias_flat) -> every layer's weight and bias, views of ONE buffer made here (children of a flat leaf by
+    narrow / view would make autograd zero-fill and add a whole flat tensor per layer); the backward is one launch"""
+
+    @staticmethod
+    def forward(ctx, v_flat, g_flat, bias_flat, wn, dims):
+        buf, _ = wn.forward(v_flat, g_flat, bias_flat)
+        ctx.save_for_backward(v_flat, g_flat)
+        ctx.wn = wn
+        ws = [buf[o:o + r * c].view(d) for o, (r, c), d in zip(wn.off, wn.shapes, dims)]
+        bs = [buf[wn.total + o:wn.total + o + n] for o, n in zip(wn.bias_off, wn.bias_sizes)]
+        return tuple(ws + bs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        v_flat, g_flat = ctx.saved_tensors
+        n = ctx.wn.n
+        gws = [None if t is None else t.contiguous() for t in grads[:n]]
+        gbs = [None if t is None else t.contiguous() for t in grads[n:]]
+        gv, gg, gb = ctx.wn.backward(v_flat, g_flat, gws, gbs)
+        return gv, gg, gb, None, None
+
+
+class _EmbedConcatFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dict_w, spkr_w, code, f0, spkr, lengths, ld):
+        B, T = code.shape
+        n_codes, E = dict_w.shape
+        C = E + (0 if f0 is None else 1) + (0 if spkr is None else E)
+        dev = dict_w.device
+        x = torch.zeros((B, C, ld), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.dissc_embed_concat_fwd(_ptr(code), _ptr(f0), _ptr(spkr), _ptr(dict_w), _ptr(spkr_w) if spkr is not None else None,
+                                             _ptr(lengths), B, T, E, n_codes, 0 if spkr is None else spkr_w.shape[0], _ptr(x), ld,
+                                             current_stream_ptr(dev)), "dissc_embed_concat_fwd")
+        ctx.code, ctx.spkr, ctx.lengths, ctx.has_f0 = code, spkr, lengths, f0 is not None
+        ctx.dims = (B, T, E, n_codes, 0 if spkr is None else spkr_w.shape[0], ld)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gx):
+        B, T, E, n_codes, n_spk, ld = ctx.dims
+        gx = gx.contiguous()
+        dev = gx.device
+        g_dict = torch.empty((n_codes, E), dtype=torch.float32, device=dev)
+        g_spkr = None if ctx.spkr is None else torch.empty((n_spk, E), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.dissc_embed_concat_bwd(_ptr(gx), _ptr(ctx.code), int(ctx.has_f0), _ptr(ctx.spkr), _ptr(ctx.lengths), B, T, E,
+                                             n_codes, n_spk, ld, _ptr(g_dict), _ptr(g_spkr), current_stream_ptr(dev)),
+                  "dissc_embed_concat_bwd")
+        return g_dict, g_spkr, None, None, None, None, None
+
+
+def embed_concat(dict_w, spkr_w, code, f0=None, spkr=None, lengths=None, ld=None):
+    """x [B, C, ld] = [dict_w[code] (E) | f0 (1) | spkr_w[spkr] (E)] per position, zero at and beyond lengths[b] (the
+    generator's input; reference sr/models.py:189,207-215).  dict_w [n_codes, E] and spkr_w [n_spk, E]: device tensors that
+    get dense gradients (rows of unused ids: exact zeros); code i64 [B, T], f0 f32 [B, T] or None, spkr i64 [B] or None,
+    lengths i32 [B] (at most T) or None, all on the device; ids outside a table are clamped to it.  ld: the row stride,
+    default T rounded up to 4."""
+    who = "nn.embed_concat"
+    _f32(dict_w, "dict_w", who)
+    B, T = code.shape
+    ld = (T + 3) // 4 * 4 if ld is None else int(ld)
+    ok = code.is_cuda and code.dtype == torch.int64 and code.is_contiguous() and code.dim() == 2
+    ok = ok and (f0 is None or (f0.is_cuda and f0.dtype == torch.float32 and f0.is_contiguous() and tuple(f0.shape) == (B, T)))
+    ok = ok and (spkr is None or (spkr.is_cuda and spkr.dtype == torch.int64 and spkr.is_contiguous() and tuple(spkr.shape) == (B,)))
+    ok = ok and (lengths is None or (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous()
+                                     and tuple(lengths.shape) == (B,)))
+    if not ok or dict_w.dim() != 2 or (spkr is not None and (_f32(spkr_w, "spkr_w", who).dim() != 2 or spkr_w.shape[1] != dict_w.shape[1])):
+        raise DisscError(f"{who}: code i64 [B, T], f0 f32 [B, T], spkr i64 [B], lengths i32 [B], contiguous on the device; "
+                         "tables [rows, E]")
+    return _EmbedConcatFn.apply(dict_w, spkr_w if spkr is not None else None, code, f0, spkr, lengths, ld)
+
+
+class _MrfMeanFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lengths, *rs):
+        B, C, ld = rs[0].shape
+        dev = rs[0].device
+        y = torch.zeros_like(rs[0]) if lengths is not None else torch.empty_like(rs[0])
+        ptrs = (ctypes.c_void_p * len(rs))(*[r.data_ptr() for r in rs])
+        with torch.cuda.device(dev):
+            check(lib.dissc_mrf_mean_fwd(ptrs, len(rs), _ptr(y), _ptr(lengths), B, C, ld, ld, current_stream_ptr(dev)),
+                  "dissc_mrf_mean_fwd")
+        ctx.lengths, ctx.nk = lengths, len(rs)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = g.contiguous()
+        B, C, ld = g.shape
+        gx = torch.empty_like(g)
+        with torch.cuda.device(g.device):
+            check(lib.dissc_mrf_mean_bwd(_ptr(g), ctx.nk, _ptr(gx), _ptr(ctx.lengths), B, C, ld, ld, current_stream_ptr(g.device)),
+                  "dissc_mrf_mean_bwd")
+        return (None,) + (gx,) * ctx.nk  # written once: every branch takes the same tensor
+
+
+def mrf_mean(rs, lengths=None):
+    """((r0 + r1) + r2 ...) / len(rs) with a true division: the mean over the ResBlocks of a stage (reference
+    sr/models.py:104-109).  rs: 1 .. 4 tensors [B, C, ld] as nn.conv1d's; zero at and beyond lengths[b]."""
+    rs = list(rs)
+    if not 1 <= len(rs) <= 4:
+        raise DisscError("nn.mrf_mean: 1 to 4 branches")
+    for r in rs:
+        _check_act(r, "a branch", rs[0].shape[0], rs[0].shape[2], who="nn.mrf_mean")
+        if r.shape[1] != rs[0].shape[1]:
+            raise DisscError("nn.mrf_mean: the branches differ in channels")
+    return _MrfMeanFn.apply(lengths, *rs)
+
+
+class _TanhFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, lengths, cols):
+        B, C, ld = x.shape
+        y = torch.zeros((B, C, cols), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib.dissc_tanh_fwd(_ptr(x), _ptr(y), _ptr(lengths), B, C, ld, cols, cols, current_stream_ptr(x.device)),
+                  "dissc_tanh_fwd")
+        ctx.save_for_backward(y)
+        ctx.lengths, ctx.ld = lengths, ld
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        (y,) = ctx.saved_tensors
+        B, C, cols = y.shape
+        gy = gy.contiguous()
+        gx = torch.empty((B, C, ctx.ld), dtype=torch.float32, device=y.device)
+        with torch.cuda.device(y.device):
+            check(lib.dissc_tanh_bwd(_ptr(y), _ptr(gy), _ptr(gx), _ptr(ctx.lengths), B, C, ctx.ld, cols, cols,
+                                     current_stream_ptr(y.device)), "dissc_tanh_bwd")
+        return gx, None, None
+
+
+def tanh(x, lengths=None, cols=None):
+    """y [B, C, cols] = tanh(x [B, C, ld]) inside lengths[b] (default cols), zero beyond; cols <= ld (default ld) is the
+    output's row length: the waveform has hop * T samples, the activations rows of hop * ceil4(T).  The output is saved,
+    the gradient gy (1 - y^2) is zero from lengths[b] on."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise DisscError("nn.tanh: x must be a contiguous fp32 device tensor [B, C, ld]")
+    cols = x.shape[2] if cols is None else int(cols)
+    if not 1 <= cols <= x.shape[2]:
+        raise DisscError(f"nn.tanh: cols {cols} outside 1 .. {x.shape[2]}")
+    return _TanhFn.apply(x, lengths, cols)
+
+
+class CodeGenerator:
+    """The trainable twin of dissc_amd.generator.CodeGenerator (reference sr/models.py:125-225): the same config keys and
+    checkpoint format (the reference's UNFOLDED keys *.weight_g / *.weight_v / *.bias, dict.weight, spkr.weight), a forward
+    with a grad_fn composed from this module's layers.
+
+        G = nn.CodeGenerator(h).to("cuda:0"); G.load_state_dict(sd)
+        loss = 45 * mel.l1_loss(y, G(code=, f0=, spkr=, lengths=)); loss.backward()
+        torch.optim.AdamW(G.parameters()).step(); G.state_dict()          # loads into the inference CodeGenerator
+
+    parameters(): five flat leaves -- every weight_v, every weight_g, every bias, dict.weight, spkr.weight; weight norm of all
+    layers is one launch in each direction.  No torch compute op on the path (allocation, views, autograd's own sums where a
+    tensor feeds several layers)."""
+
+    _UNSUPPORTED = ("lambda_commit", "lambda_commit_code", "f0_quantizer_path")
+    N_SPEAKERS = 200  # nn.Embedding(200, ...), reference sr/models.py:133
+
+    def __init__(self, h):
+        from .generator import AttrDict
+        self.h = AttrDict(h)
+        for k in self._UNSUPPORTED:
+            if self.h.get(k, None):
+                raise NotImplementedError(f"config option '{k}' (VQ-VAE branch) is not supported")
+        if str(self.h.get("resblock", "1")) != "1":
+            raise NotImplementedError("only resblock type '1' is supported")
+        h = self.h
+        self.num_kernels, self.num_upsamples = len(h.resblock_kernel_sizes), len(h.upsample_rates)
+        if not 1 <= self.num_kernels <= 4:
+            raise NotImplementedError("1 to 4 ResBlocks per stage")
+        self.f0, self.multispkr = h.get("f0", None), h.get("multispkr", None)
+        self.hop = 1
+        for u in h.upsample_rates:
+            self.hop *= int(u)
+        c0, E = int(h.upsample_initial_channel), int(h.embedding_dim)
+        self.in_dim = int(h.get("model_in_dim", 128))
+        if self.in_dim != E + (1 if self.f0 else 0) + (E if self.multispkr else 0):
+            raise NotImplementedError(f"model_in_dim {self.in_dim} is not embedding_dim (+ 1 for f0) (+ embedding_dim for speakers)")
+        # (name, weight shape, bias length) in the reference's order
+        L = [("conv_pre", (c0, self.in_dim, 7), c0)]
+        for i, k in enumerate(h.upsample_kernel_sizes):
+            L.append((f"ups.{i}", (c0 >> i, c0 >> (i + 1), int(k)), c0 >> (i + 1)))
+        for i in range(self.num_upsamples):
+            ch = c0 >> (i + 1)
+            for j, (k, ds) in enumerate(zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes)):
+                if len(ds) != 3:
+                    raise NotImplementedError("ResBlock1 needs 3 dilations per kernel size")
+                for grp in ("convs1", "convs2"):
+                    L += [(f"resblocks.{i * self.num_kernels + j}.{grp}.{m}", (ch, ch, int(k)), ch) for m in range(3)]
+        L.append(("conv_post", (1, c0 >> self.num_upsamples, 7), 1))
+        self.layers = L
+        self._index = {name: i for i, (name, _, _) in enumerate(L)}
+        self.wn = WeightNorm([(s[0], s[1] * s[2]) for _, s, _ in L], [nb for _, _, nb in L])
+        self.device = torch.device("cuda:0")
+        self.v_flat = self.g_flat = self.bias_flat = self.dict_weight = self.spkr_weight = None
+
+    # -- nn.Module-like surface --------------------------------------------------------------------------------------
+    def to(self, device):
+        if isinstance(device, int):
+            device = f"cuda:{device}"
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise DisscError("dissc_amd.nn.CodeGenerator runs on an MI355X only (device='cuda:N')")
+        if self.v_flat is not None and device != self.device:
+            raise DisscError("nn.CodeGenerator: choose the device before load_state_dict()")
+        self.device = device
+        return self
+
+    def cuda(self, device=0):
+        return self.to(device)
+
+    def _keys(self):
+        keys = []
+        for name, _, _ in self.layers:
+            keys += [name + ".bias", name + ".weight_g", name + ".weight_v"]
+        return keys + ["dict.weight"] + (["spkr.weight"] if self.multispkr else [])
+
+    def load_state_dict(self, sd, strict=True):
+        """the reference's checkpoint layout: weight_g / weight_v / bias per conv, dict.weight, spkr.weight"""
+        keys = self._keys()
+        missing = [k for k in keys if k not in sd]
+        unexpected = sorted(set(sd.keys()) - set(keys))
+        if missing or (strict and unexpected):
+            raise RuntimeError(f"Error(s) in loading state_dict for CodeGenerator: missing {missing[:5]}, unexpected {unexpected[:5]}")
+        wn = self.wn
+        v, g, b = torch.zeros(wn.total), torch.zeros(wn.total_rows), torch.zeros(wn.bias_total)
+        for i, (name, shape, nb) in enumerate(self.layers):
+            tv, tg, tb = (sd[name + s].detach().to("cpu", torch.float32) for s in (".weight_v", ".weight_g", ".bias"))
+            if tuple(tv.shape) != shape or tg.numel() != shape[0] or tb.numel() != nb:
+                raise RuntimeError(f"size mismatch for {name}: weight_v {tuple(tv.shape)}, expected {shape}")
+            v[wn.off[i]:wn.off[i] + tv.numel()] = tv.reshape(-1)
+            g[wn.row_off[i]:wn.row_off[i] + shape[0]] = tg.reshape(-1)
+            b[wn.bias_off[i]:wn.bias_off[i] + nb] = tb.reshape(-1)
+        E = int(self.h.embedding_dim)
+        tables = [sd["dict.weight"]] + ([sd["spkr.weight"]] if self.multispkr else [])
+        if tuple(tables[0].shape) != (int(self.h.num_embeddings), E) or (self.multispkr and tuple(tables[1].shape) != (self.N_SPEAKERS, E)):
+            raise RuntimeError("size mismatch for dict.weight / spkr.weight")
+        leaf = lambda t: t.detach().to(self.device, torch.float32).contiguous().clone().requires_grad_(True)
+        self.v_flat, self.g_flat, self.bias_flat = leaf(v), leaf(g), leaf(b)
+        self.dict_weight = leaf(tables[0])
+        self.spkr_weight = leaf(tables[1]) if self.multispkr else None
+        return self
+
+    def _loaded(self):
+        if self.v_flat is None:
+            raise RuntimeError("load_state_dict() first")
+
+    def parameters(self):
+        """the five flat leaves (four without speakers): v_flat, g_flat, bias_flat, dict.weight, spkr.weight"""
+        self._loaded()
+        return [p for p in (self.v_flat, self.g_flat, self.bias_flat, self.dict_weight, self.spkr_weight) if p is not None]
+
+    def zero_grad(self):
+        for p in self.parameters():
+            p.grad = None
+
+    def _named(self, v, g, b, d, s):
+        out = {}
+        wn = self.wn
+        for i, (name, shape, nb) in enumerate(self.layers):
+            n = shape[0] * shape[1] * shape[2]
+            out[name + ".bias"] = b[wn.bias_off[i]:wn.bias_off[i] + nb]
+            out[name + ".weight_g"] = g[wn.row_off[i]:wn.row_off[i] + shape[0]].view(shape[0], 1, 1)
+            out[name + ".weight_v"] = v[wn.off[i]:wn.off[i] + n].view(shape)
+        out["dict.weight"] = d
+        if s is not None:
+            out["spkr.weight"] = s
+        return out
+
+    def named_grads(self):
+        """{reference key: a view of its leaf's .grad} after a backward"""
+        ps = self.parameters()
+        if any(p.grad is None for p in ps):
+            raise RuntimeError("named_grads(): run a backward first")
+        return self._named(self.v_flat.grad, self.g_flat.grad, self.bias_flat.grad, self.dict_weight.grad,
+                           None if self.spkr_weight is None else self.spkr_weight.grad)
+
+    def state_dict(self):
+        """host copies under the reference's unfolded keys"""
+        self._loaded()
+        host = [None if p is None else p.detach().cpu() for p in (self.v_flat, self.g_flat, self.bias_flat, self.dict_weight,
+                                                                   self.spkr_weight)]
+        return {k: t.clone() for k, t in self._named(*host).items()}
+
+    # -- forward -------------------------------------------------------------------------------------------------------
+    def forward(self, code=None, f0=None, spkr=None, lengths=None, taps=None, **extra):
+        """code [B, T] ids, f0 [B, 1, T'] or [B, T'] (with "f0" in the config), spkr [B, 1] (with "multispkr"), lengths [B]
+        valid frames (default T) -> wav [B, 1, hop T] with a grad_fn, zero beyond hop lengths[b].  The shorter of the code and
+        f0 streams is repeated up to the longer one, as in the reference.  taps: a list that receives every conv's input in
+        call order (conv_pre's, then per stage the upsampler's and its ResBlocks' as nn.resblock1 gives them, conv_post's)."""
+        from .generator import CodeGenerator as _Inference
+        self._loaded()
+        if extra:
+            raise NotImplementedError(f"extra conditioning features {sorted(extra)} are not supported")
+        dev = self.device
+        if torch.as_tensor(code).device.type == "cpu":  # nn.Embedding raises on a bad id; device ids are clamped
+            for name, t, rows in (("code", code, int(self.h.num_embeddings)), ("spkr", spkr if self.multispkr else None, self.N_SPEAKERS)):
+                t = None if t is None else torch.as_tensor(t)
+                if t is not None and t.device.type == "cpu" and t.numel() and (int(t.min()) < 0 or int(t.max()) >= rows):
+                    raise IndexError(f"{name} id out of range: [{int(t.min())}, {int(t.max())}] not within [0, {rows})")
+        code = torch.as_tensor(code).to(dev, torch.int64)
+        if code.dim() != 2:
+            raise ValueError("code must be [B,T]")
+        f0d = None
+        if self.f0:
+            f0d = torch.as_tensor(f0).to(dev, torch.float32)
+            if f0d.dim() == 2:
+                f0d = f0d.unsqueeze(1)
+            if code.shape[-1] < f0d.shape[-1]:
+                code = _Inference._upsample(code.unsqueeze(1), f0d.shape[-1]).squeeze(1)
+            elif f0d.shape[-1] != code.shape[-1]:
+                f0d = _Inference._upsample(f0d, code.shape[-1])
+            if f0d.shape[-1] != code.shape[-1] or f0d.shape[0] != code.shape[0] or f0d.shape[1] != 1:
+                raise RuntimeError(f"Sizes of tensors must match: code {tuple(code.shape)} vs f0 {tuple(f0d.shape)} "
+                                   "after conditioning upsample")
+            f0d = f0d.reshape(code.shape[0], -1).contiguous()
+        code = code.contiguous()
+        B, T = code.shape
+        sp = None
+        if self.multispkr:
+            sp = torch.as_tensor(spkr).to(dev, torch.int64).reshape(-1).contiguous()
+            if sp.numel() != B:
+                raise ValueError("spkr must be [B,1]")
+        ln = np.full(B, T, dtype=np.int64) if lengths is None else \
+            np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+        if ln.shape[0] != B or (ln < 0).any() or (ln > T).any():
+            raise ValueError(f"lengths must be [B] counts within 0 .. {T}")
+        muls, m = [1], 1
+        for u in self.h.upsample_rates:
+            m *= int(u)
+            muls.append(m)
+        # every stage's lengths in one upload
+        stage = torch.from_numpy(np.stack([ln * m for m in muls]).astype(np.int32)).to(dev)
+        lens = [stage[i] for i in range(len(muls))]
+        ld = (T + 3) // 4 * 4
+        n = len(self.layers)
+        dims = [s for _, s, _ in self.layers]
+        wb = _WeightsFn.apply(self.v_flat, self.g_flat, self.bias_flat, self.wn, dims)
+        W = lambda name: (wb[self._index[name]], wb[n + self._index[name]])
+
+        def tap(t):
+            if taps is not None:
+                taps.append(t)
+            return t
+
+        x = embed_concat(self.dict_weight, self.spkr_weight, code, f0d, sp, lens[0], ld)
+        x = conv1d(tap(x), *W("conv_pre"), lengths=lens[0])
+        nk = self.num_kernels
+        for i, u in enumerate(self.h.upsample_rates):
+            x = conv_transpose1d(tap(x), *W(f"ups.{i}"), stride=int(u), lengths=lens[i], in_slope=LRELU_SLOPE)
+            rs = []
+            for j, (k, ds) in enumerate(zip(self.h.resblock_kernel_sizes, self.h.resblock_dilation_sizes)):
+                pre = f"resblocks.{i * nk + j}."
+                wts = {}
+                for grp in ("convs1", "convs2"):
+                    for mm in range(3):
+                        wts[f"{grp}.{mm}.weight"], wts[f"{grp}.{mm}.bias"] = W(f"{pre}{grp}.{mm}")
+                rs.append(resblock1(x, wts, int(k), tuple(int(d) for d in ds), lengths=lens[i + 1], taps=taps))
+            x = mrf_mean(rs, lens[i + 1])
+        x = conv1d(tap(x), *W("conv_post"), lengths=lens[-1], in_slope=POST_SLOPE)
+        return tanh(x, lens[-1], self.hop * T)
+
+    __call__ = forward

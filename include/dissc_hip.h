@@ -786,6 +786,68 @@ int dissc_convtgrad_backward(dissc_convtgrad_t h, const float* x, const float* g
                              int ldo, int Lmax_in, float in_slope, float* gx, float* gw, float* gb, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * The rest of the generator's training step (csrc/gen_train.hip; composed in dissc_amd/nn.py's CodeGenerator): weight norm
+ * of every layer at once, the embeddings, the MRF mean, the tanh tail.  Added without an ABI bump, as the sections above.
+ * All device pointers f32 unless said otherwise; no atomics, fixed summation orders: bit-reproducible.
+ *
+ * Weight norm, w = g v / ||v|| per index of dim 0 (weight_norm(dim=0): for a ConvTranspose1d that is the INPUT channel;
+ * reference sr/models.py wraps all 97 convs).  One launch per direction for up to 128 tensors.
+ * dissc_wnorm_create: HOST ONLY.  n tensors of rows[i] x cols[i] (cols = the product of every dim but 0), each at least 1, at
+ *   most 2^22 rows and 2^40 floats in all; anything else is DISSC_EINVAL with a message.  It fixes a flat layout: tensor i at
+ *   the 16-byte aligned float offset off[i] (v, w and gv share it), its rows at row_off[i] in a flat per-row layout (g, gg
+ *   and 1 / ||v|| share that); the row table goes to the device current at the first launch (a handle serves that device).
+ * dissc_wnorm_offsets: HOST ONLY.  off / row_off: n entries each; the totals are the sizes of the two layouts (floats; the
+ *   first a multiple of 4).  Each may be NULL.
+ * dissc_wnorm_wave_cols: rows of up to this many columns are reduced by one wave, longer ones by a 256-thread workgroup.
+ * dissc_wnorm_forward: writes w_flat (the alignment gaps are left alone) and 1 / ||v|| per row; v_flat and w_flat 16-byte
+ *   aligned.  nbias > 0: the same launch copies bias_flat[0 .. nbias) to bias_out (the layers' biases next to their weights).
+ * dissc_wnorm_backward: gw_ptrs is a HOST array of n DEVICE pointers, each layer's own weight gradient [rows][cols], 16-byte
+ *   aligned; NULL = a zero gradient (its gv and gg are written as exact zeros).  The pointers travel in the kernel's
+ *   arguments, 128 tensors per launch: nothing is uploaded per step.
+ *   gg = (v . gw) / ||v||,  gv = (g / ||v||) (gw - v (v . gw) / ||v||^2).
+ *   gb_ptrs (HOST array of n device pointers, or NULL = no biases): the same launch gathers bias_n[i] floats of each (NULL:
+ *   zeros) into gb_flat, one after the other, each at the next multiple of 4 floats (the gaps are left alone).
+ *   A row's sums (in double: a float product is then exact, and the kernels stay bandwidth bound): per-thread chains over
+ *   (head to the next 16-byte boundary, float4s, tail), then a fixed butterfly; the order depends on cols and on the row's
+ *   start modulo 4 floats, i.e. on (row index, cols) alone.  The backward sums ||v||^2 again in the pass that reads v for
+ *   v . gw anyway, instead of taking the forward's fp32 1 / ||v|| (kept for the caller): gw - v (v . gw) / ||v||^2 cancels,
+ *   entirely for a row of one column, and a norm rounded to fp32 in between would leave its rounding error there.
+ *
+ * Embeddings.  dissc_embed_concat_fwd: the generator's first kernel on DEVICE tables: x [B][C][ldx], C = E + (f0 ? 1 : 0) +
+ *   (spkr ? E : 0), rows [dict_w[code] | f0 | spkr_w[spkr]]; code i64 [B][T], f0 f32 [B][T] or NULL, spkr i64 [B] or NULL; ids
+ *   are clamped to the tables; nothing is written at or beyond lengths[b] (i32 [B] on the device, at most T, or NULL = T).
+ * dissc_embed_concat_bwd: gx [B][C][ldx] ->  g_dict [n_codes][E] = sum over (b, t < lengths[b], code[b][t] = id) of
+ *   gx[b][c][t], g_spkr [n_spk][E] = sum over (b: spkr[b] = id, t < lengths[b]) of gx[b][E + has_f0 + c][t]; both dense (rows
+ *   of unused ids are exact zeros), ids clamped as the forward does; f0 gets no gradient.  One workgroup per table row, the
+ *   summation order a function of (B, T) alone.  E <= 256; bad arguments are DISSC_EINVAL with a message, on the host.
+ *
+ * MRF mean over [B][C][ld] rows (ld a multiple of 4, 16-byte aligned; lengths i32 [B] on the device or NULL = Lmax):
+ * dissc_mrf_mean_fwd: r = HOST array of nk (1 .. 4) device pointers; y = ((r0 + r1) + r2 ...) / nk with a true division;
+ *   nothing written at or beyond lengths[b].
+ * dissc_mrf_mean_bwd: gx = g / nk inside lengths[b], zero from there to ld; every branch takes the same tensor.
+ * dissc_tanh_fwd: y [B][C][ldy] = tanh(x [B][C][ldx]) inside lengths; dissc_tanh_bwd: gx = gy (1 - y^2) from the saved
+ *   output (y, gy with row stride ldy), zero from lengths[b] to ldx.
+ * ------------------------------------------------------------------------- */
+typedef struct dissc_wnorm* dissc_wnorm_t;
+int dissc_wnorm_create(int n, const int* rows, const int* cols, dissc_wnorm_t* out);
+void dissc_wnorm_destroy(dissc_wnorm_t h);
+int dissc_wnorm_offsets(dissc_wnorm_t h, long long* off, long long* row_off, long long* total_floats, long long* total_rows);
+int dissc_wnorm_wave_cols(void);
+int dissc_wnorm_forward(dissc_wnorm_t h, const float* v_flat, const float* g_flat, float* w_flat, float* inv_norm,
+                        const float* bias_flat, float* bias_out, int nbias, void* stream);
+int dissc_wnorm_backward(dissc_wnorm_t h, const float* v_flat, const float* g_flat, const float* const* gw_ptrs, float* gv_flat, float* gg_flat, const float* const* gb_ptrs,
+                         const int* bias_n, float* gb_flat, void* stream);
+int dissc_embed_concat_fwd(const int64_t* code, const float* f0, const int64_t* spkr, const float* dict_w, const float* spkr_w,
+                           const int32_t* lengths, int B, int T, int E, int n_codes, int n_spk, float* x, int ldx, void* stream);
+int dissc_embed_concat_bwd(const float* gx, const int64_t* code, int has_f0, const int64_t* spkr, const int32_t* lengths, int B,
+                           int T, int E, int n_codes, int n_spk, int ldx, float* g_dict, float* g_spkr, void* stream);
+int dissc_mrf_mean_fwd(const float* const* r, int nk, float* y, const int32_t* lengths, int B, int C, int ld, int Lmax, void* stream);
+int dissc_mrf_mean_bwd(const float* g, int nk, float* gx, const int32_t* lengths, int B, int C, int ld, int Lmax, void* stream);
+int dissc_tanh_fwd(const float* x, float* y, const int32_t* lengths, int B, int C, int ldx, int ldy, int Lmax, void* stream);
+int dissc_tanh_bwd(const float* y, const float* gy, float* gx, const int32_t* lengths, int B, int C, int ldx, int ldy, int Lmax,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

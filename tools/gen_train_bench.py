@@ -1,0 +1,221 @@
+"""Times of what csrc/gen_train.hip adds, and of one whole training step of nn.CodeGenerator, at the trainer's shape: the shipped
+VCTK config, 32 segments of 28 frames (8 960 samples).
+
+    python tools/gen_train_bench.py [--batch 32] [--frames 28] [--launches 1000] [--steps 50] [--markdown]
+
+Kernels (each through the C ABI or its thin Python wrapper, `--launches` calls between two device events after a warm-up), next
+to the bytes they must move (every operand read once, every result written once) and the GB/s that implies:
+  the multi-tensor weight norm, forward and backward over the generator's 97 tensors, against a loop of torch._weight_norm
+  and its autograd backward over the same 97 tensors on the same GPU (this one has a bar: ours must not be slower);
+  the embeddings' forward and gradient; the MRF mean (the five stages' rows, summed) and the tanh tail, both directions.
+Step: forward + 45 x mel L1 + backward of nn.CodeGenerator against the same model in eager torch (torch._weight_norm -- what
+weight_norm's hook evaluates --, F.embedding, F.conv1d / conv_transpose1d, F.l1_loss of torch log-mels) with the same weights,
+`--steps` steps each after a warm-up; and the number of GPU kernels one step of each launches (torch.profiler's device
+activities; null where the profiler gives none).  One JSON line per figure; --markdown adds the tables of profiles/gen_train.md."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+DEV = "cuda:0"
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def kernel_count(fn):
+    """GPU kernels of one call of fn, or None where the profiler records no device activity"""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA"))
+        return n or None
+    except Exception as e:  # a figure, not a requirement
+        print(f"# kernel count unavailable: {e}", file=sys.stderr)
+        return None
+
+
+def row(name, ms, mbytes, extra=None):
+    out = {"what": name, "us": round(1e3 * ms, 2), "MB": round(mbytes, 2), "GBps": round(mbytes / 1e3 / (ms * 1e-3), 1)}
+    out.update(extra or {})
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def torch_mel(y, basis, window, n_fft=1024, hop=256):
+    p = (n_fft - hop) // 2
+    y = torch.nn.functional.pad(y[:, None], (p, p), mode="reflect")[:, 0]
+    spec = torch.view_as_real(torch.stft(y, n_fft, hop_length=hop, win_length=n_fft, window=window, center=False, normalized=False,
+                                         onesided=True, return_complex=True))
+    return torch.log(torch.clamp(torch.matmul(basis, torch.sqrt(spec.pow(2).sum(-1) + 1e-9)), min=1e-5))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--frames", type=int, default=28)
+    ap.add_argument("--launches", type=int, default=1000)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--markdown", action="store_true")
+    a = ap.parse_args(argv)
+    import __graft_entry__ as ge
+    ge.build()
+    import dissc_amd
+    import gen_train_ref as GT
+    import synthdata as synth
+    from dissc_amd import nn
+    from dissc_amd._lib import check, lib
+    from oracle import generator_ref as G
+    F = torch.nn.functional
+    h = synth.VCTK_CONFIG
+    B, T = a.batch, a.frames
+    sd = synth.synth_generator_state_dict(h, seed=0)
+    gen = nn.CodeGenerator(h).to(DEV)
+    gen.load_state_dict(sd)
+    wn = gen.wn
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    rows = []
+
+    # ---- weight norm over the 97 tensors ----
+    v_flat, g_flat, b_flat = gen.v_flat.detach(), gen.g_flat.detach(), gen.bias_flat.detach()
+    gws = [torch.randn(r, c, device=DEV) for r, c in wn.shapes]
+    gbs = [torch.randn(n, device=DEV) for n in wn.bias_sizes]
+    buf = torch.empty(wn.total + wn.bias_total, device=DEV)
+    gv = torch.empty(wn.total, device=DEV)
+    # straight through the C ABI with the pointer arrays built once: the Python wrappers check ~200 tensors per call, which at
+    # these times would be what is measured
+    inv, gg, gbf = torch.empty(wn.total_rows, device=DEV), torch.empty(wn.total_rows, device=DEV), torch.zeros(wn.bias_total, device=DEV)
+    pw = (ctypes.c_void_p * wn.n)(*[t.data_ptr() for t in gws])
+    pb = (ctypes.c_void_p * wn.n)(*[t.data_ptr() for t in gbs])
+    bias_out = ctypes.c_void_p(buf.data_ptr() + 4 * wn.total)
+    fwd = lambda: check(lib.dissc_wnorm_forward(wn._h, p(v_flat), p(g_flat), p(buf), p(inv), p(b_flat), bias_out, wn.bias_total, None))
+    bwd = lambda: check(lib.dissc_wnorm_backward(wn._h, p(v_flat), p(g_flat), pw, p(gv), p(gg), pb, wn._bias_n, p(gbf), None))
+    tv = [t.to(DEV).requires_grad_(True) for k, t in sd.items() if k.endswith(".weight_v")]
+    tg = [t.to(DEV).requires_grad_(True) for k, t in sd.items() if k.endswith(".weight_g")]
+    tgw = [w.view(v.shape) for w, v in zip(gws, tv)]
+    assert [tuple(t.shape) for t in tv] == [s for _, s, _ in gen.layers]
+
+    def torch_fwd():
+        return [torch._weight_norm(v, g, 0) for v, g in zip(tv, tg)]
+
+    def torch_both():
+        torch.autograd.grad(torch_fwd(), tv + tg, tgw)
+
+    for fn in (fwd, bwd, torch_fwd, torch_both):
+        timed(fn, 3)
+    mb = 4e-6 * wn.total
+    n_t = max(20, a.launches // 10)
+    t_f, t_b = timed(fwd, a.launches), timed(bwd, a.launches)
+    t_tf, t_tb = timed(torch_fwd, n_t), timed(torch_both, n_t)
+    rows.append(row("wnorm forward, 97 tensors, one launch", t_f, 2 * mb))
+    rows.append(row("wnorm backward, 97 tensors, one launch", t_b, 3 * mb))
+    rows.append(row("torch._weight_norm loop, forward", t_tf, 2 * mb))
+    rows.append(row("torch._weight_norm loop, forward + autograd backward", t_tb, 5 * mb))
+    verdict = {"what": "wnorm bar: forward + backward not slower than the torch loop", "ours_us": round(1e3 * (t_f + t_b), 1),
+               "torch_us": round(1e3 * t_tb, 1), "holds": bool(t_f + t_b <= t_tb)}
+    print(json.dumps(verdict), flush=True)
+
+    # ---- embeddings ----
+    code, f0, spkr, _ = synth.synth_generator_inputs(B, T, seed=1, n_spk=200)
+    code_d, f0_d, spkr_d = torch.from_numpy(code).to(DEV), torch.from_numpy(f0).to(DEV).reshape(B, T).contiguous(), \
+        torch.from_numpy(spkr).to(DEV).reshape(-1).contiguous()
+    E, C, ld = 128, 257, (T + 3) // 4 * 4
+    lens = torch.full((B,), T, dtype=torch.int32, device=DEV)
+    x, gx = torch.zeros(B, C, ld, device=DEV), torch.randn(B, C, ld, device=DEV)
+    gd, gs = torch.empty(100, E, device=DEV), torch.empty(200, E, device=DEV)
+    dw, sw = gen.dict_weight.detach(), gen.spkr_weight.detach()
+    e_f = lambda: check(lib.dissc_embed_concat_fwd(p(code_d), p(f0_d), p(spkr_d), p(dw), p(sw), p(lens), B, T, E, 100, 200, p(x), ld, None))
+    e_b = lambda: check(lib.dissc_embed_concat_bwd(p(gx), p(code_d), 1, p(spkr_d), p(lens), B, T, E, 100, 200, ld, p(gd), p(gs), None))
+    timed(e_f, 3), timed(e_b, 3)
+    act = 4e-6 * B * C * T
+    rows.append(row("embed_concat forward", timed(e_f, a.launches), act + 4e-6 * (B * T * 2 + 300 * E)))
+    rows.append(row("embed_concat gradient (dense, 300 table rows)", timed(e_b, a.launches), act + 4e-6 * 300 * E))
+
+    # ---- MRF mean (five stages) and tanh ----
+    t_mf = t_mb = mrf_mb = 0.0
+    L, ch = T, 512
+    for u in h["upsample_rates"]:
+        L, ch = L * u, ch // 2
+        rs3 = [torch.randn(B, ch, L, device=DEV) for _ in range(3)]
+        y, ln = torch.empty(B, ch, L, device=DEV), torch.full((B,), L, dtype=torch.int32, device=DEV)
+        ptrs = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in rs3])
+        m_f = lambda: check(lib.dissc_mrf_mean_fwd(ptrs, 3, p(y), p(ln), B, ch, L, L, None))
+        m_b = lambda: check(lib.dissc_mrf_mean_bwd(p(rs3[0]), 3, p(y), p(ln), B, ch, L, L, None))
+        timed(m_f, 3), timed(m_b, 3)
+        t_mf += timed(m_f, a.launches)
+        t_mb += timed(m_b, a.launches)
+        mrf_mb += 4e-6 * B * ch * L
+    rows.append(row("MRF mean forward, five stages (nk = 3)", t_mf, 4 * mrf_mb))
+    rows.append(row("MRF mean backward, five stages", t_mb, 2 * mrf_mb))
+    xw, yw, lw = torch.randn(B, 1, L, device=DEV), torch.empty(B, 1, L, device=DEV), torch.full((B,), L, dtype=torch.int32, device=DEV)
+    t_f_ = lambda: check(lib.dissc_tanh_fwd(p(xw), p(yw), p(lw), B, 1, L, L, L, None))
+    gxw = torch.empty_like(xw)
+    t_b_ = lambda: check(lib.dissc_tanh_bwd(p(yw), p(xw), p(gxw), p(lw), B, 1, L, L, L, None))
+    timed(t_f_, 3), timed(t_b_, 3)
+    rows.append(row("tanh forward, [32, 1, 8960]", timed(t_f_, a.launches), 2 * 4e-6 * B * L))
+    rows.append(row("tanh backward", timed(t_b_, a.launches), 3 * 4e-6 * B * L))
+
+    # ---- one step: forward + 45 x mel L1 + backward, ours and eager torch ----
+    ms = dissc_amd.MelSpectrogram().to(DEV)
+    target = (0.3 * torch.randn(B, 320 * T)).to(DEV)
+    code_t, f0_t, spkr_t = torch.from_numpy(code), torch.from_numpy(f0), torch.from_numpy(spkr)
+
+    def ours_step():
+        gen.zero_grad()
+        (45 * ms.l1_loss(target, gen(code=code_t, f0=f0_t, spkr=spkr_t))).backward()
+
+    P = {k: t.to(DEV).requires_grad_(True) for k, t in sd.items()}
+    basis = torch.from_numpy(dissc_amd.mel.mel_filterbank(16000, 1024, 80)).float().to(DEV)
+    window = torch.hann_window(1024, device=DEV)
+    target_mel = torch_mel(target, basis, window)
+    cd, fd, sdv = code_t.to(DEV), f0_t.to(DEV), spkr_t.to(DEV)
+
+    def torch_step():
+        for t in P.values():
+            t.grad = None
+        w = {}
+        for k, t in P.items():
+            if k.endswith(".weight_g"):
+                w[k[:-2]] = torch._weight_norm(P[k[:-2] + "_v"], t, 0)
+            elif not k.endswith(".weight_v"):
+                w[k] = t
+        wav = GT._forward(w, h, G.embed_concat(w, cd, fd, sdv), None, None)
+        (45 * F.l1_loss(target_mel, torch_mel(wav[:, 0], basis, window))).backward()
+        return wav
+
+    ours_step(), torch_step()
+    rel = float((gen(code=code_t, f0=f0_t, spkr=spkr_t).detach() - torch_step().detach()).norm() / torch_step().detach().norm())
+    timed(ours_step, 3), timed(torch_step, 3)
+    t_o, t_t = timed(ours_step, a.steps), timed(torch_step, a.steps)
+    step = {"what": "step: forward + 45 x mel L1 + backward", "batch": B, "frames": T, "ours_ms": round(t_o, 3), "torch_ms": round(t_t, 3),
+            "wav_rel_diff": float(f"{rel:.2e}"), "ours_kernels": kernel_count(ours_step), "torch_kernels": kernel_count(torch_step)}
+    print(json.dumps(step), flush=True)
+    if a.markdown:
+        print("\n| kernel | us | MB moved | GB/s |\n|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['what']} | {r['us']} | {r['MB']} | {r['GBps']} |")
+        print(f"\nweight norm, forward + backward: ours {verdict['ours_us']} us, torch loop {verdict['torch_us']} us "
+              f"({'holds' if verdict['holds'] else 'MISSED'})")
+        print(f"step at B = {B}, T = {T}: ours {step['ours_ms']} ms ({step['ours_kernels']} kernels), eager torch {step['torch_ms']} ms "
+              f"({step['torch_kernels']} kernels); wav relative difference {step['wav_rel_diff']}")
+    return rows, verdict, step
+
+
+if __name__ == "__main__":
+    main()
