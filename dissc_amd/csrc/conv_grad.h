@@ -1,6 +1,9 @@
 // What the two differentiable conv layers share (conv_grad.hip: the stride-1 Conv1d; conv_grad_t.hip: ConvTranspose1d): the
-// partial plan of the weight gradient, the fixed-order sum over its partials and the bias gradient.  Defined in conv_grad.hip.
+// partial plan of the weight gradient, the fixed-order sum over its partials, the bias gradient, and the host side of a layer
+// handle (base, argument checks, the backward's workspace layout, the tap-group dispatch).  Defined in conv_grad.hip.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace dissc {
@@ -28,5 +31,45 @@ void cg_launch_reduce(const float* part, int NP, size_t n, float* out, hipStream
 // gb[co] = sum_b sum_{t < min(lengths[b] * len_mul, Lmax)} gy[b][co][t], in double; bpart: B * Cout doubles of workspace
 void cg_launch_bias(const float* gy, const int32_t* lengths, int len_mul, int B, int Cout, int Lmax, int ldo, double* bpart,
                     float* gb, hipStream_t st);
+
+// ---- the host side of a layer handle; `who` is the C entry that was called: every message starts with it ----
+struct CgLayer {  // the base of dissc_convgrad and dissc_convtgrad
+  Options opt;  // this handle's snapshot of the tuning options (common.h)
+  int Cin = 0, Cout = 0, k = 0;
+  bool ready = false;  // device buffers allocated (the first set_weights)
+};
+
+// create: the out pointer and the channel range; kernel size, dilation and stride rules are each layer's own
+int cg_check_create(const char* who, const void* out, int Cin, int Cout);
+// a call on a handle: the arguments; then, with len_mul > 0 (1, or the stride: a row of y / gy holds len_mul * Lmax), the row
+// strides and "set_weights first"
+int cg_check_call(const CgLayer* h, const char* who, int B, int Lmax, int len_mul = 0, int ldx = 0, int ldo = 0);
+
+// the backward's workspace behind its 256-byte aligned base: partials at 0, the bias gradient's doubles at `bpart`; `bytes` is
+// what *_workspace_bytes promises
+struct CgWorkspace {
+  size_t bpart, bytes;
+};
+CgWorkspace cg_workspace(const CgPlan& p, int B, int Cout);
+// the backward's preamble: x, gy and gx 16-byte aligned, the workspace as large as promised where gw or gb is wanted; carves it
+int cg_backward_begin(const char* who, const CgPlan& p, int B, int Cout, const float* x, const float* gy, const float* gx,
+                      bool wants_wb, void* workspace, size_t workspace_bytes, float** part, double** bpart);
+
+// launch(std::integral_constant<int, NG>) for NG in 1 .. CG_MAX_K; `unit` names what NG counts in the refusal of any other
+template <class F>
+int cg_dispatch_ng(int NG, const char* who, const char* unit, F&& launch) {
+  static_assert(CG_MAX_K == 11, "one case per tap-group count up to CG_MAX_K");
+  switch (NG) {
+#define CG_CASE(n) case n: return launch(std::integral_constant<int, n>());
+    CG_CASE(1) CG_CASE(2) CG_CASE(3) CG_CASE(4) CG_CASE(5) CG_CASE(6) CG_CASE(7) CG_CASE(8) CG_CASE(9) CG_CASE(10) CG_CASE(11)
+#undef CG_CASE
+  }
+  set_error("%s: %d %s", who, NG, unit);
+  return DISSC_EINVAL;
+}
+
+// set_weights' allocation of one direct conv: the zeros uploaded are the packing's padding (weights never leave the device); a
+// packing the device-side repack does not write is refused
+int cg_alloc_conv(const char* who, int rows, int cols, int taps, int dil, int pad_left, DevConv& dc);
 
 }  // namespace dissc

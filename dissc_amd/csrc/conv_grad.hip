@@ -21,6 +21,8 @@
 //   * Tap offsets are off_j = off0 + j dstep with |off_j| <= 32: nothing ties them to (k - 1) d / 2.  A ConvTranspose1d's
 //     weight gradient (a stride-1 correlation of x with the phase planes of gy) is conv_grad_t.hip's kernel: this one with a
 //     (plane, shift) per tap; it shares the plan, the reduction and the bias kernels below through conv_grad.h.
+// The host side the two layers have in common is defined here too (conv_grad.h: CgLayer, the argument checks, the workspace
+// layout with the preamble that carves it, cg_alloc_conv).
 #include <string.h>
 
 #include <algorithm>
@@ -291,14 +293,75 @@ void cg_launch_bias(const float* gy, const int32_t* lengths, int len_mul, int B,
   hipLaunchKernelGGL(convgrad_bias_reduce_kernel, dim3((Cout + 63) / 64), dim3(64), 0, st, bpart, B, Cout, gb);
 }
 
+int cg_check_create(const char* who, const void* out, int Cin, int Cout) {
+  if (!out) {
+    set_error("%s: bad argument", who);
+    return DISSC_EINVAL;
+  }
+  if (Cin < 1 || Cout < 1 || Cin > 65535 || Cout > 65535) {
+    set_error("%s: %d -> %d channels (both must be in 1 .. 65535)", who, Cin, Cout);
+    return DISSC_EINVAL;
+  }
+  return DISSC_OK;
+}
+
+int cg_check_call(const CgLayer* h, const char* who, int B, int Lmax, int len_mul, int ldx, int ldo) {
+  if (!h || B <= 0 || Lmax <= 0 || B > 65535) {
+    set_error("%s: bad argument (handle %p, B = %d, Lmax = %d)", who, (void*)h, B, Lmax);
+    return DISSC_EINVAL;
+  }
+  if (len_mul <= 0) return DISSC_OK;  // a host-only query: no rows
+  if (ldx < Lmax || (long long)ldo < (long long)len_mul * Lmax || (ldx & 3) || (ldo & 3)) {
+    set_error("%s: row strides %d / %d must be multiples of 4 and >= Lmax = %d / %d x Lmax = %d", who, ldx, ldo, Lmax, len_mul,
+              len_mul * Lmax);
+    return DISSC_EINVAL;
+  }
+  if (!h->ready) {  // "dissc_conv[t]grad_" of the entry's own name
+    set_error("%s: %.*sset_weights first", who, (int)(strrchr(who, '_') + 1 - who), who);
+    return DISSC_EINVAL;
+  }
+  return DISSC_OK;
+}
+
+CgWorkspace cg_workspace(const CgPlan& p, int B, int Cout) {
+  CgWorkspace w;
+  w.bpart = cg_rup((size_t)p.P * p.WT * p.gw * sizeof(float), 256);
+  w.bytes = w.bpart + cg_rup((size_t)B * Cout * sizeof(double), 256) + 256;
+  return w;
+}
+
+int cg_backward_begin(const char* who, const CgPlan& p, int B, int Cout, const float* x, const float* gy, const float* gx,
+                      bool wants_wb, void* workspace, size_t workspace_bytes, float** part, double** bpart) {
+  if (!x || !gy || ((uintptr_t)x & 15) || ((uintptr_t)gy & 15) || ((uintptr_t)gx & 15)) {
+    set_error("%s: x, gy and gx must be 16-byte aligned device pointers", who);
+    return DISSC_EINVAL;
+  }
+  const CgWorkspace w = cg_workspace(p, B, Cout);
+  if (wants_wb && (!workspace || workspace_bytes < w.bytes)) {
+    set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, w.bytes);
+    return DISSC_ENOMEM;
+  }
+  *part = (float*)cg_rup((size_t)workspace, 256);
+  *bpart = (double*)((char*)*part + w.bpart);
+  return DISSC_OK;
+}
+
+int cg_alloc_conv(const char* who, int rows, int cols, int taps, int dil, int pad_left, DevConv& dc) {
+  std::vector<float> zeros((size_t)rows * cols * taps, 0.f);
+  if (int rc = make_conv(zeros.data(), nullptr, rows, cols, taps, dil, dc, 1, 1, pad_left)) return rc;
+  if (dc.prec || dc.wino || dc.wpack2) {
+    set_error("%s: unexpected conv packing", who);
+    return DISSC_EINVAL;
+  }
+  return DISSC_OK;
+}
+
 }  // namespace dissc
 
 using namespace dissc;
 
-struct dissc_convgrad {
-  Options opt;  // this handle's snapshot of the tuning options (common.h)
-  int Cin = 0, Cout = 0, k = 0, dil = 1;
-  bool ready = false;  // device buffers allocated (first dissc_convgrad_set_weights)
+struct dissc_convgrad : CgLayer {
+  int dil = 1;
   DevConv fwd, bwd;
   ~dissc_convgrad() {
     free_conv(fwd);
@@ -306,26 +369,11 @@ struct dissc_convgrad {
   }
 };
 
-static bool cg_bad_call(dissc_convgrad_t h, int B, int Lmax, const char* who) {
-  if (!h || B <= 0 || Lmax <= 0 || B > 65535) {
-    set_error("%s: bad argument (handle %p, B = %d, Lmax = %d)", who, (void*)h, B, Lmax);
-    return true;
-  }
-  return false;
-}
-
 extern "C" {
 
 int dissc_convgrad_create(int Cin, int Cout, int k, int dilation, dissc_convgrad_t* out) {
-  if (!out) {
-    set_error("dissc_convgrad_create: bad argument");
-    return DISSC_EINVAL;
-  }
-  *out = nullptr;
-  if (Cin < 1 || Cout < 1 || Cin > 65535 || Cout > 65535) {
-    set_error("dissc_convgrad_create: %d -> %d channels (both must be in 1 .. 65535)", Cin, Cout);
-    return DISSC_EINVAL;
-  }
+  if (out) *out = nullptr;
+  if (int rc = cg_check_create("dissc_convgrad_create", out, Cin, Cout)) return rc;
   if (k < 1 || k % 2 != 1 || k > CG_MAX_K) {
     set_error("dissc_convgrad_create: kernel size %d (odd, at most %d)", k, CG_MAX_K);
     return DISSC_EINVAL;
@@ -351,14 +399,9 @@ int dissc_convgrad_set_weights(dissc_convgrad_t h, const float* w_dev, const flo
   OptScope opt_scope(&h->opt);
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  if (!h->ready) {  // allocation only: the zeros uploaded here are the packings' padding; weights never leave the device
-    std::vector<float> zeros((size_t)h->Cout * h->Cin * h->k, 0.f);
-    if ((rc = make_conv(zeros.data(), nullptr, h->Cout, h->Cin, h->k, h->dil, h->fwd))) return rc;
-    if ((rc = make_conv(zeros.data(), nullptr, h->Cin, h->Cout, h->k, h->dil, h->bwd))) return rc;
-    if (h->fwd.prec || h->bwd.prec || h->fwd.wino || h->bwd.wino || h->fwd.wpack2 || h->bwd.wpack2) {
-      set_error("dissc_convgrad_set_weights: unexpected conv packing");
-      return DISSC_EINVAL;
-    }
+  if (!h->ready) {
+    if ((rc = cg_alloc_conv("dissc_convgrad_set_weights", h->Cout, h->Cin, h->k, h->dil, -1, h->fwd))) return rc;
+    if ((rc = cg_alloc_conv("dissc_convgrad_set_weights", h->Cin, h->Cout, h->k, h->dil, -1, h->bwd))) return rc;
     h->ready = true;
   }
   for (int tr = 0; tr < 2; ++tr) {
@@ -376,23 +419,9 @@ int dissc_convgrad_set_weights(dissc_convgrad_t h, const float* w_dev, const flo
   return DISSC_OK;
 }
 
-static int cg_check_io(dissc_convgrad_t h, int B, int ldx, int ldo, int Lmax, const char* who) {
-  if (cg_bad_call(h, B, Lmax, who)) return DISSC_EINVAL;
-  if (ldx < Lmax || ldo < Lmax || (ldx & 3) || (ldo & 3)) {
-    set_error("%s: row strides %d / %d must be multiples of 4 and >= Lmax = %d", who, ldx, ldo, Lmax);
-    return DISSC_EINVAL;
-  }
-  if (!h->ready) {
-    set_error("%s: dissc_convgrad_set_weights first", who);
-    return DISSC_EINVAL;
-  }
-  return DISSC_OK;
-}
-
 int dissc_convgrad_forward(dissc_convgrad_t h, const float* x, const float* add, float* y, const int32_t* lengths, int B,
                            int ldx, int ldo, int Lmax, float in_slope, void* stream) {
-  int rc = cg_check_io(h, B, ldx, ldo, Lmax, "dissc_convgrad_forward");
-  if (rc) return rc;
+  if (int rc = cg_check_call(h, "dissc_convgrad_forward", B, Lmax, 1, ldx, ldo)) return rc;
   if (!x || !y) {
     set_error("dissc_convgrad_forward: bad argument");
     return DISSC_EINVAL;
@@ -403,7 +432,7 @@ int dissc_convgrad_forward(dissc_convgrad_t h, const float* x, const float* add,
 }
 
 int dissc_convgrad_partials(dissc_convgrad_t h, int B, int Lmax, int* P, int* chunk) {
-  if (cg_bad_call(h, B, Lmax, "dissc_convgrad_partials")) return DISSC_EINVAL;
+  if (int rc = cg_check_call(h, "dissc_convgrad_partials", B, Lmax)) return rc;
   const CgPlan p = cg_plan(h->Cin, h->Cout, h->k, B, Lmax);
   if (P) *P = p.P;
   if (chunk) *chunk = p.cpp;
@@ -412,28 +441,21 @@ int dissc_convgrad_partials(dissc_convgrad_t h, int B, int Lmax, int* P, int* ch
 
 size_t dissc_convgrad_workspace_bytes(dissc_convgrad_t h, int B, int Lmax) {
   if (!h || B <= 0 || Lmax <= 0) return 0;
-  const CgPlan p = cg_plan(h->Cin, h->Cout, h->k, B, Lmax);
-  return cg_rup((size_t)p.P * p.WT * p.gw * sizeof(float), 256) + cg_rup((size_t)B * h->Cout * sizeof(double), 256) + 256;
+  return cg_workspace(cg_plan(h->Cin, h->Cout, h->k, B, Lmax), B, h->Cout).bytes;
 }
 
 int dissc_convgrad_backward(dissc_convgrad_t h, const float* x, const float* gy, const int32_t* lengths, int B, int ldx,
                             int ldo, int Lmax, float in_slope, float* gx, float* gw, float* gb, void* workspace,
                             size_t workspace_bytes, void* stream) {
-  int rc = cg_check_io(h, B, ldx, ldo, Lmax, "dissc_convgrad_backward");
+  const char* who = "dissc_convgrad_backward";
+  int rc = cg_check_call(h, who, B, Lmax, 1, ldx, ldo);
   if (rc) return rc;
-  if (!x || !gy || ((uintptr_t)x & 15) || ((uintptr_t)gy & 15) || ((uintptr_t)gx & 15)) {
-    set_error("dissc_convgrad_backward: x, gy and gx must be 16-byte aligned device pointers");
-    return DISSC_EINVAL;
-  }
-  if ((gw || gb) && (!workspace || workspace_bytes < dissc_convgrad_workspace_bytes(h, B, Lmax))) {
-    set_error("dissc_convgrad_backward: workspace %zu < %zu bytes", workspace_bytes, dissc_convgrad_workspace_bytes(h, B, Lmax));
-    return DISSC_ENOMEM;
-  }
+  const CgPlan p = cg_plan(h->Cin, h->Cout, h->k, B, Lmax);
+  float* part;
+  double* bpart;
+  if ((rc = cg_backward_begin(who, p, B, h->Cout, x, gy, gx, gw || gb, workspace, workspace_bytes, &part, &bpart))) return rc;
   OptScope opt_scope(&h->opt);
   hipStream_t st = (hipStream_t)stream;
-  const CgPlan p = cg_plan(h->Cin, h->Cout, h->k, B, Lmax);
-  float* part = (float*)cg_rup((size_t)workspace, 256);
-  double* bpart = (double*)((char*)part + cg_rup((size_t)p.P * p.WT * p.gw * sizeof(float), 256));
   if (gw) {
     WgradArgs a;
     a.gy = gy; a.x = x; a.lengths = lengths; a.part = part;
@@ -442,15 +464,8 @@ int dissc_convgrad_backward(dissc_convgrad_t h, const float* x, const float* gy,
     a.halo = (((h->k - 1) * h->dil) / 2 + 3) & ~3;
     a.slope = in_slope;
     a.WCI = p.WCI; a.WT = p.WT; a.CIB = p.CIB; a.TS = p.TS; a.nch = p.nch; a.cpp = p.cpp;
-    switch (p.NG) {
-#define CG_CASE(n) case n: rc = cg_launch_wgrad<n>(a, p, st); break;
-      CG_CASE(1) CG_CASE(2) CG_CASE(3) CG_CASE(4) CG_CASE(5) CG_CASE(6) CG_CASE(7) CG_CASE(8) CG_CASE(9) CG_CASE(10) CG_CASE(11)
-#undef CG_CASE
-      default:
-        set_error("dissc_convgrad_backward: %d tap groups", p.NG);
-        rc = DISSC_EINVAL;
-    }
-    if (rc) return rc;
+    if ((rc = cg_dispatch_ng(p.NG, who, "tap groups", [&](auto ng) { return cg_launch_wgrad<decltype(ng)::value>(a, p, st); })))
+      return rc;
     cg_launch_reduce(part, p.P * p.WT, p.gw, gw, st);
   }
   if (gb) cg_launch_bias(gy, lengths, 1, B, h->Cout, Lmax, ldo, bpart, gb, st);

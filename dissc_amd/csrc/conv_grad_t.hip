@@ -15,7 +15,8 @@
 //     with a (plane, shift) per tap where that one has an offset per tap.  A chunk is 64 input positions = 64 s contiguous
 //     columns of gy, read once with float4 loads and de-interleaved into the s planes in LDS; all k taps accumulate in one pass
 //     on v_mfma_f32_32x32x2_f32 (as many MFMAs as the direct form: there are no zero taps).  The plan, the fixed-order sum over
-//     the partials and the bias gradient are conv_grad.hip's (conv_grad.h).
+//     the partials and the bias gradient are conv_grad.hip's (conv_grad.h), and so is the host side a layer handle shares with
+//     the stride-1 one: the base CgLayer, the argument checks, the workspace layout and its carve, the dispatch over the taps.
 //   * Data gradient: gx[ci][t] = lrelu'(x[ci][t]) sum_{co,kk} w[ci][co][kk] plane_p(kk)[co][t + dl(kk)], an implicit GEMM with
 //     rows ci, columns t and the reduction over (co, kk) on the same MFMA.  The gy window of a column tile is staged
 //     de-interleaved, so a B fragment is 32 consecutive floats of one plane; the derivative of the leaky ReLU (torch's rule at
@@ -347,10 +348,8 @@ static int ct_launch_wgrad(const WgradTArgs& a, const CgPlan& p, hipStream_t st)
 
 using namespace dissc;
 
-struct dissc_convtgrad {
-  Options opt;  // this handle's snapshot of the tuning options (common.h)
-  int Cin = 0, Cout = 0, k = 0, s = 1;
-  bool ready = false;  // device buffers allocated (first dissc_convtgrad_set_weights)
+struct dissc_convtgrad : CgLayer {
+  int s = 1;
   std::vector<ConvTGroup> plan;
   std::vector<DevConv> fwd;  // one per phase group
   float* apack = nullptr;    // the data gradient's A fragments
@@ -360,26 +359,11 @@ struct dissc_convtgrad {
   }
 };
 
-static bool ct_bad_call(dissc_convtgrad_t h, int B, int Lmax, const char* who) {
-  if (!h || B <= 0 || Lmax <= 0 || B > 65535) {
-    set_error("%s: bad argument (handle %p, B = %d, Lmax = %d)", who, (void*)h, B, Lmax);
-    return true;
-  }
-  return false;
-}
-
 extern "C" {
 
 int dissc_convtgrad_create(int Cin, int Cout, int k, int stride, dissc_convtgrad_t* out) {
-  if (!out) {
-    set_error("dissc_convtgrad_create: bad argument");
-    return DISSC_EINVAL;
-  }
-  *out = nullptr;
-  if (Cin < 1 || Cout < 1 || Cin > 65535 || Cout > 65535) {
-    set_error("dissc_convtgrad_create: %d -> %d channels (both must be in 1 .. 65535)", Cin, Cout);
-    return DISSC_EINVAL;
-  }
+  if (out) *out = nullptr;
+  if (int rc = cg_check_create("dissc_convtgrad_create", out, Cin, Cout)) return rc;
   if (stride < 1 || stride > CT_MAX_S) {
     set_error("dissc_convtgrad_create: stride %d (1 .. %d)", stride, CT_MAX_S);
     return DISSC_EINVAL;
@@ -407,21 +391,15 @@ int dissc_convtgrad_set_weights(dissc_convtgrad_t h, const float* w_dev, const f
   hipStream_t st = (hipStream_t)stream;
   const int nblk = (h->Cin + 31) / 32, cop8 = (h->Cout + 31) / 32 * 4;
   const size_t napack = (size_t)nblk * h->k * cop8 * 256;
-  if (!h->ready) {  // allocation only: the zeros uploaded here are the packings' padding; weights never leave the device
+  if (!h->ready) {
     std::vector<DevConv> fwd;  // handed to the handle only when every group and the fragments are allocated
     float* apack = nullptr;
     int rc = DISSC_OK;
     for (const ConvTGroup& g : h->plan) {
-      std::vector<float> zeros((size_t)h->Cout * g.np * h->Cin * g.ntap, 0.f);
       fwd.emplace_back();
       DevConv& dc = fwd.back();
-      if ((rc = make_conv(zeros.data(), nullptr, h->Cout * g.np, h->Cin, g.ntap, 1, dc, 1, 1, -g.dlo))) break;
+      if ((rc = cg_alloc_conv("dissc_convtgrad_set_weights", h->Cout * g.np, h->Cin, g.ntap, 1, -g.dlo, dc))) break;
       dc.up = h->s; dc.up_np = g.np; dc.up_p0 = g.p0;
-      if (dc.prec || dc.wino || dc.wpack2) {
-        set_error("dissc_convtgrad_set_weights: unexpected conv packing");
-        rc = DISSC_EINVAL;
-        break;
-      }
     }
     if (!rc && hipMalloc((void**)&apack, napack * sizeof(float)) != hipSuccess) {
       set_error("dissc_convtgrad_set_weights: cannot allocate %zu bytes", napack * sizeof(float));
@@ -453,23 +431,9 @@ int dissc_convtgrad_set_weights(dissc_convtgrad_t h, const float* w_dev, const f
 }
 
 // Lmax: input positions; a row of y / gy holds stride * Lmax
-static int ct_check_io(dissc_convtgrad_t h, int B, int ldx, int ldo, int Lmax, const char* who) {
-  if (ct_bad_call(h, B, Lmax, who)) return DISSC_EINVAL;
-  if (ldx < Lmax || (long long)ldo < (long long)h->s * Lmax || (ldx & 3) || (ldo & 3)) {
-    set_error("%s: row strides %d / %d must be multiples of 4 and >= Lmax = %d / stride x Lmax = %d", who, ldx, ldo, Lmax,
-              h->s * Lmax);
-    return DISSC_EINVAL;
-  }
-  if (!h->ready) {
-    set_error("%s: dissc_convtgrad_set_weights first", who);
-    return DISSC_EINVAL;
-  }
-  return DISSC_OK;
-}
-
 int dissc_convtgrad_forward(dissc_convtgrad_t h, const float* x, float* y, const int32_t* lengths, int B, int ldx, int ldo,
                             int Lmax, float in_slope, void* stream) {
-  int rc = ct_check_io(h, B, ldx, ldo, Lmax, "dissc_convtgrad_forward");
+  int rc = cg_check_call(h, "dissc_convtgrad_forward", B, Lmax, h ? h->s : 1, ldx, ldo);
   if (rc) return rc;
   if (!x || !y) {
     set_error("dissc_convtgrad_forward: bad argument");
@@ -483,7 +447,7 @@ int dissc_convtgrad_forward(dissc_convtgrad_t h, const float* x, float* y, const
 }
 
 int dissc_convtgrad_partials(dissc_convtgrad_t h, int B, int Lmax, int* P, int* chunk) {
-  if (ct_bad_call(h, B, Lmax, "dissc_convtgrad_partials")) return DISSC_EINVAL;
+  if (int rc = cg_check_call(h, "dissc_convtgrad_partials", B, Lmax)) return rc;
   const CgPlan p = ct_plan(h->Cin, h->Cout, h->k, B, Lmax);
   if (P) *P = p.P;
   if (chunk) *chunk = p.cpp;
@@ -492,29 +456,22 @@ int dissc_convtgrad_partials(dissc_convtgrad_t h, int B, int Lmax, int* P, int* 
 
 size_t dissc_convtgrad_workspace_bytes(dissc_convtgrad_t h, int B, int Lmax) {
   if (!h || B <= 0 || Lmax <= 0) return 0;
-  const CgPlan p = ct_plan(h->Cin, h->Cout, h->k, B, Lmax);
-  return cg_rup((size_t)p.P * p.WT * p.gw * sizeof(float), 256) + cg_rup((size_t)B * h->Cout * sizeof(double), 256) + 256;
+  return cg_workspace(ct_plan(h->Cin, h->Cout, h->k, B, Lmax), B, h->Cout).bytes;
 }
 
 int dissc_convtgrad_backward(dissc_convtgrad_t h, const float* x, const float* gy, const int32_t* lengths, int B, int ldx,
                              int ldo, int Lmax, float in_slope, float* gx, float* gw, float* gb, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  int rc = ct_check_io(h, B, ldx, ldo, Lmax, "dissc_convtgrad_backward");
+  const char* who = "dissc_convtgrad_backward";
+  int rc = cg_check_call(h, who, B, Lmax, h ? h->s : 1, ldx, ldo);
   if (rc) return rc;
-  if (!x || !gy || ((uintptr_t)x & 15) || ((uintptr_t)gy & 15) || ((uintptr_t)gx & 15)) {
-    set_error("dissc_convtgrad_backward: x, gy and gx must be 16-byte aligned device pointers");
-    return DISSC_EINVAL;
-  }
-  if ((gw || gb) && (!workspace || workspace_bytes < dissc_convtgrad_workspace_bytes(h, B, Lmax))) {
-    set_error("dissc_convtgrad_backward: workspace %zu < %zu bytes", workspace_bytes, dissc_convtgrad_workspace_bytes(h, B, Lmax));
-    return DISSC_ENOMEM;
-  }
+  const CgPlan p = ct_plan(h->Cin, h->Cout, h->k, B, Lmax);
+  float* part;
+  double* bpart;
+  if ((rc = cg_backward_begin(who, p, B, h->Cout, x, gy, gx, gw || gb, workspace, workspace_bytes, &part, &bpart))) return rc;
   OptScope opt_scope(&h->opt);
   hipStream_t st = (hipStream_t)stream;
-  const CgPlan p = ct_plan(h->Cin, h->Cout, h->k, B, Lmax);
   const CtTaps tp = ct_taps(h->k, h->s);
-  float* part = (float*)cg_rup((size_t)workspace, 256);
-  double* bpart = (double*)((char*)part + cg_rup((size_t)p.P * p.WT * p.gw * sizeof(float), 256));
   if (gw) {
     WgradTArgs a;
     a.gy = gy; a.x = x; a.lengths = lengths; a.part = part;
@@ -527,15 +484,7 @@ int dissc_convtgrad_backward(dissc_convtgrad_t h, const float* x, const float* g
       set_error("dissc_convtgrad_backward: the weight gradient's window does not fit (stride %d)", h->s);
       return DISSC_EINVAL;
     }
-    switch (p.NG) {
-#define CT_CASE(n) case n: rc = ct_launch_wgrad<n>(a, p, st); break;
-      CT_CASE(1) CT_CASE(2) CT_CASE(3) CT_CASE(4) CT_CASE(5) CT_CASE(6) CT_CASE(7) CT_CASE(8) CT_CASE(9) CT_CASE(10) CT_CASE(11)
-#undef CT_CASE
-      default:
-        set_error("dissc_convtgrad_backward: %d taps", p.NG);
-        rc = DISSC_EINVAL;
-    }
-    if (rc) return rc;
+    if ((rc = cg_dispatch_ng(p.NG, who, "taps", [&](auto ng) { return ct_launch_wgrad<decltype(ng)::value>(a, p, st); }))) return rc;
     cg_launch_reduce(part, p.P * p.WT, p.gw, gw, st);
   }
   if (gb) cg_launch_bias(gy, lengths, h->s, B, h->Cout, h->s * Lmax, ldo, bpart, gb, st);

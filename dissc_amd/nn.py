@@ -11,6 +11,10 @@ positions at and beyond ``lengths[b]`` are read as zero and never written.  Forw
 MFMA conv kernels, the weight gradient on its own MFMA kernel with fixed-order partial sums (no atomics: bit-reproducible).
 The weights are a DEVICE tensor and are packed on the device on every call, because they change every step in training.
 No torch compute op on the hot path, no CPU fallback.  First order only.
+
+The two conv layers are one core: a ``_Kind`` describes each (its C entries, the weight layout, the rows of y per row of x),
+and one handle cache, one set of checks, ``_forward`` and ``_backward`` work on that description; the two autograd Functions
+differ in their argument lists only.
 """
 import ctypes
 
@@ -24,81 +28,75 @@ WGRAD_CHUNK = 64  # DISSC_CONVGRAD_CHUNK: time positions per chunk of the weight
 LRELU_SLOPE = 0.1  # reference sr/models.py:13
 
 
-def _bind():
-    vp, i32, sz, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
-    lib.dissc_convgrad_create.argtypes = [i32, i32, i32, i32, ctypes.POINTER(vp)]
-    lib.dissc_convgrad_destroy.argtypes = [vp]
-    lib.dissc_convgrad_destroy.restype = None
-    lib.dissc_convgrad_set_weights.argtypes = [vp, vp, vp, vp]
-    lib.dissc_convgrad_forward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]
-    lib.dissc_convgrad_partials.argtypes = [vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    lib.dissc_convgrad_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.dissc_convgrad_workspace_bytes.restype = sz
-    lib.dissc_convgrad_backward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]
-    lib.dissc_convtgrad_create.argtypes = [i32, i32, i32, i32, ctypes.POINTER(vp)]
-    lib.dissc_convtgrad_destroy.argtypes = [vp]
-    lib.dissc_convtgrad_destroy.restype = None
-    lib.dissc_convtgrad_set_weights.argtypes = [vp, vp, vp, vp]
-    lib.dissc_convtgrad_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]
-    lib.dissc_convtgrad_partials.argtypes = [vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    lib.dissc_convtgrad_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.dissc_convtgrad_workspace_bytes.restype = sz
-    lib.dissc_convtgrad_backward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]
+_ENTRIES = ("create", "destroy", "set_weights", "forward", "partials", "workspace_bytes", "backward")
 
 
-_bind()
+class _Kind:
+    """one differentiable conv layer kind: its C entries, how (Cin, Cout, k) are read from the weight's shape, the rows of y per
+    row of x as a function of the layer's own parameter p (dilation or stride), and the names its messages use"""
 
-_handles = {}     # (Cin, Cout, k, dilation, device) -> handle; device None: host-only queries
+    def __init__(self, who, prefix, layout, dims, mul, fwd_args):
+        vp, i32, sz, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
+        self.who, self.prefix, self.layout, self.dims, self.mul = who, prefix, layout, dims, mul
+        self.names = {e: f"{prefix}_{e}" for e in _ENTRIES}
+        for e, name in self.names.items():
+            setattr(self, e, getattr(lib, name))
+        self.create.argtypes = [i32, i32, i32, i32, ctypes.POINTER(vp)]
+        self.destroy.argtypes, self.destroy.restype = [vp], None
+        self.set_weights.argtypes = [vp, vp, vp, vp]
+        self.forward.argtypes = fwd_args + [vp, vp, i32, i32, i32, i32, f32, vp]  # ..., y, lengths, B, ldx, ldo, Lmax, slope, stream
+        self.partials.argtypes = [vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        self.workspace_bytes.argtypes, self.workspace_bytes.restype = [vp, i32, i32], sz
+        self.backward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]
+
+
+# weight [Cout, Cin, k], p = dilation, forward(h, x, add, ...)  /  weight [Cin, Cout, k], p = stride, forward(h, x, ...)
+CONV1D = _Kind("nn.conv1d", "dissc_convgrad", "[Cout, {}, k]", lambda s: (s[1], s[0], s[2]), lambda p: 1, [ctypes.c_void_p] * 3)
+CONV_TRANSPOSE1D = _Kind("nn.conv_transpose1d", "dissc_convtgrad", "[{}, Cout, k]", lambda s: (s[0], s[1], s[2]), lambda p: p,
+                         [ctypes.c_void_p] * 2)
+
+_handles = {}     # (prefix, Cin, Cout, k, p, device) -> handle; device None: host-only queries
 _workspaces = {}  # device -> uint8 tensor, grown on demand (calls on one device are stream-ordered)
 
 
-def _handle(Cin, Cout, k, dilation, device=None):
-    key = (int(Cin), int(Cout), int(k), int(dilation), None if device is None else torch.device(device))
+def _handle(kind, Cin, Cout, k, p, device=None):
+    key = (kind.prefix, int(Cin), int(Cout), int(k), int(p), None if device is None else torch.device(device))
     h = _handles.get(key)
     if h is None:
         h = ctypes.c_void_p()
-        check(lib.dissc_convgrad_create(key[0], key[1], key[2], key[3], ctypes.byref(h)), "dissc_convgrad_create")
+        check(kind.create(key[1], key[2], key[3], key[4], ctypes.byref(h)), kind.names["create"])
         _handles[key] = h
     return h
+
+
+def _partials(kind, B, Lmax, Cin, Cout, k, p=1):
+    P, pairs = ctypes.c_int(0), ctypes.c_int(0)
+    check(kind.partials(_handle(kind, Cin, Cout, k, p), int(B), int(Lmax), ctypes.byref(P), ctypes.byref(pairs)),
+          kind.names["partials"])
+    return P.value, pairs.value
 
 
 def wgrad_partials(B, Lmax, Cin, Cout, k):
     """(P, pairs): the weight gradient of a [Cout, Cin, k] layer over B utterances of up to Lmax positions is summed in P
     partials; partial p takes the (utterance, chunk) pairs [p * pairs, (p + 1) * pairs) of the utterance-major list with
     ceil(Lmax / WGRAD_CHUNK) chunks per utterance.  A function of the shape only (host only, no GPU needed)."""
-    P, pairs = ctypes.c_int(0), ctypes.c_int(0)
-    check(lib.dissc_convgrad_partials(_handle(Cin, Cout, k, 1), int(B), int(Lmax), ctypes.byref(P), ctypes.byref(pairs)),
-          "dissc_convgrad_partials")
-    return P.value, pairs.value
+    return _partials(CONV1D, B, Lmax, Cin, Cout, k)
 
 
 def workspace_bytes(B, Lmax, Cin, Cout, k):
     """bytes of the backward's workspace (host only)"""
-    return int(lib.dissc_convgrad_workspace_bytes(_handle(Cin, Cout, k, 1), int(B), int(Lmax)))
-
-
-def _handle_t(Cin, Cout, k, stride, device=None):
-    key = ("T", int(Cin), int(Cout), int(k), int(stride), None if device is None else torch.device(device))
-    h = _handles.get(key)
-    if h is None:
-        h = ctypes.c_void_p()
-        check(lib.dissc_convtgrad_create(key[1], key[2], key[3], key[4], ctypes.byref(h)), "dissc_convtgrad_create")
-        _handles[key] = h
-    return h
+    return int(CONV1D.workspace_bytes(_handle(CONV1D, Cin, Cout, k, 1), int(B), int(Lmax)))
 
 
 def wgrad_partials_transpose(B, Lmax, Cin, Cout, k, stride):
     """wgrad_partials for conv_transpose1d's weight gradient [Cin, Cout, k]: Lmax and the chunks are INPUT positions (a chunk
     is stride * WGRAD_CHUNK columns of the output's gradient).  A function of the shape only (host only)."""
-    P, pairs = ctypes.c_int(0), ctypes.c_int(0)
-    check(lib.dissc_convtgrad_partials(_handle_t(Cin, Cout, k, stride), int(B), int(Lmax), ctypes.byref(P), ctypes.byref(pairs)),
-          "dissc_convtgrad_partials")
-    return P.value, pairs.value
+    return _partials(CONV_TRANSPOSE1D, B, Lmax, Cin, Cout, k, stride)
 
 
 def workspace_bytes_transpose(B, Lmax, Cin, Cout, k, stride):
     """bytes of conv_transpose1d's backward workspace (host only)"""
-    return int(lib.dissc_convtgrad_workspace_bytes(_handle_t(Cin, Cout, k, stride), int(B), int(Lmax)))
+    return int(CONV_TRANSPOSE1D.workspace_bytes(_handle(CONV_TRANSPOSE1D, Cin, Cout, k, stride), int(B), int(Lmax)))
 
 
 def _workspace(device, nbytes):
@@ -115,57 +113,88 @@ def _check_act(t, name, B=None, ld=None, who="nn.conv1d"):
         raise DisscError(f"{who}: {name} is {tuple(t.shape)}, expected batch {B} and row stride {ld}")
 
 
+def _lengths_ok(lengths, B):
+    return lengths is None or (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous()
+                               and tuple(lengths.shape) == (B,))
+
+
+def _check_layer(kind, x, weight, bias, lengths):
+    """the refusals both conv layers share; -> Cout"""
+    _check_act(x, "x", who=kind.who)
+    B, Cin, _ = x.shape
+    if not (weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 3 and weight.is_contiguous()
+            and kind.dims(weight.shape)[0] == Cin):
+        raise DisscError(f"{kind.who}: weight must be a contiguous fp32 device tensor {kind.layout.format(Cin)}")
+    Cout = kind.dims(weight.shape)[1]
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous()
+                                 and tuple(bias.shape) == (Cout,)):
+        raise DisscError(f"{kind.who}: bias must be a contiguous fp32 device tensor [Cout]")
+    if not _lengths_ok(lengths, B):
+        raise DisscError(f"{kind.who}: lengths must be a contiguous int32 device tensor [B]")
+    return Cout
+
+
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _forward(kind, ctx, x, weight, bias, lengths, p, in_slope, *add):
+    """set_weights, the output (zeros where lengths leave part of it unwritten), forward; saves x and weight, never y"""
+    B, _, ld = x.shape
+    Cin, Cout, k = kind.dims(weight.shape)
+    h = _handle(kind, Cin, Cout, k, p, x.device)
+    st = current_stream_ptr(x.device)
+    ldo = kind.mul(p) * ld
+    with torch.cuda.device(x.device):
+        check(kind.set_weights(h, _ptr(weight), _ptr(bias), st), kind.names["set_weights"])
+        y = torch.zeros((B, Cout, ldo), dtype=torch.float32, device=x.device) if lengths is not None else \
+            torch.empty((B, Cout, ldo), dtype=torch.float32, device=x.device)
+        check(kind.forward(h, _ptr(x), *map(_ptr, add), _ptr(y), _ptr(lengths), B, ld, ldo, ld, in_slope, st), kind.names["forward"])
+    ctx.save_for_backward(x, weight)
+    ctx.lengths, ctx.p, ctx.in_slope, ctx.has_bias = lengths, p, in_slope, bias is not None
+    return y
+
+
+def _backward(kind, ctx, gy):
+    """-> (gx, gw, gb, gy made contiguous) for the inputs 0 .. 2 that need a gradient, None for the others"""
+    x, weight = ctx.saved_tensors
+    B, _, ld = x.shape
+    Cin, Cout, k = kind.dims(weight.shape)
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    need_b = ctx.has_bias and ctx.needs_input_grad[2]
+    gy = gy.contiguous()
+    gx = gw = gb = ws = None
+    if need_x or need_w or need_b:
+        h = _handle(kind, Cin, Cout, k, ctx.p, x.device)
+        st = current_stream_ptr(x.device)
+        with torch.cuda.device(x.device):
+            if need_x:  # another layer sharing the handle may have run since the forward: pack again (device only)
+                check(kind.set_weights(h, _ptr(weight), None, st), kind.names["set_weights"])
+                gx = torch.empty_like(x)
+            if need_w:
+                gw = torch.empty_like(weight)
+            if need_b:
+                gb = torch.empty(Cout, dtype=torch.float32, device=x.device)
+            nws = 0
+            if need_w or need_b:
+                nws = int(kind.workspace_bytes(h, B, ld))
+                ws = _workspace(x.device, nws)
+            check(kind.backward(h, _ptr(x), _ptr(gy), _ptr(ctx.lengths), B, ld, kind.mul(ctx.p) * ld, ld, ctx.in_slope,
+                                _ptr(gx), _ptr(gw), _ptr(gb), _ptr(ws), nws, st), kind.names["backward"])
+    return gx, gw, gb, gy
 
 
 class _Conv1dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, add, lengths, dilation, in_slope):
-        B, Cin, ld = x.shape
-        Cout, _, k = weight.shape
-        h = _handle(Cin, Cout, k, dilation, x.device)
-        st = current_stream_ptr(x.device)
-        with torch.cuda.device(x.device):
-            check(lib.dissc_convgrad_set_weights(h, _ptr(weight), _ptr(bias), st), "dissc_convgrad_set_weights")
-            y = torch.zeros((B, Cout, ld), dtype=torch.float32, device=x.device) if lengths is not None else \
-                torch.empty((B, Cout, ld), dtype=torch.float32, device=x.device)
-            check(lib.dissc_convgrad_forward(h, _ptr(x), _ptr(add), _ptr(y), _ptr(lengths), B, ld, ld, ld, float(in_slope), st),
-                  "dissc_convgrad_forward")
-        ctx.save_for_backward(x, weight)  # never y
-        ctx.lengths, ctx.dilation, ctx.in_slope = lengths, int(dilation), float(in_slope)
-        ctx.has_bias, ctx.has_add = bias is not None, add is not None
-        return y
+        ctx.has_add = add is not None
+        return _forward(CONV1D, ctx, x, weight, bias, lengths, dilation, in_slope, add)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
-        B, Cin, ld = x.shape
-        Cout, _, k = weight.shape
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        need_add = ctx.has_add and ctx.needs_input_grad[3]
-        gy = gy.contiguous()
-        gx = gw = gb = ws = None
-        if need_x or need_w or need_b:
-            h = _handle(Cin, Cout, k, ctx.dilation, x.device)
-            st = current_stream_ptr(x.device)
-            with torch.cuda.device(x.device):
-                if need_x:  # another layer sharing the handle may have run since the forward: pack again (device only)
-                    check(lib.dissc_convgrad_set_weights(h, _ptr(weight), None, st), "dissc_convgrad_set_weights")
-                    gx = torch.empty_like(x)
-                if need_w:
-                    gw = torch.empty_like(weight)
-                if need_b:
-                    gb = torch.empty(Cout, dtype=torch.float32, device=x.device)
-                nws = 0
-                if need_w or need_b:
-                    nws = int(lib.dissc_convgrad_workspace_bytes(h, B, ld))
-                    ws = _workspace(x.device, nws)
-                check(lib.dissc_convgrad_backward(h, _ptr(x), _ptr(gy), _ptr(ctx.lengths), B, ld, ld, ld, ctx.in_slope,
-                                                  _ptr(gx), _ptr(gw), _ptr(gb), _ptr(ws), nws, st), "dissc_convgrad_backward")
-        return gx, gw, gb, (gy if need_add else None), None, None, None
+        gx, gw, gb, gy = _backward(CONV1D, ctx, gy)
+        return gx, gw, gb, (gy if ctx.has_add and ctx.needs_input_grad[3] else None), None, None, None
 
 
 def conv1d(x, weight, bias=None, lengths=None, dilation=1, in_slope=1.0, add=None):
@@ -176,71 +205,23 @@ def conv1d(x, weight, bias=None, lengths=None, dilation=1, in_slope=1.0, add=Non
     None = ld): positions at and beyond lengths[b] are read as zero and left zero in y.  Gradients flow to x, weight,
     bias and add (the gradient of add is the incoming gradient itself, handed through unmasked: the cotangent of a position
     beyond lengths[b], which the forward never writes, is the caller's to keep zero); x and weight are saved, y is not."""
-    _check_act(x, "x")
-    B, Cin, ld = x.shape
-    if not (weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 3 and weight.is_contiguous()
-            and weight.shape[1] == Cin):
-        raise DisscError(f"nn.conv1d: weight must be a contiguous fp32 device tensor [Cout, {Cin}, k]")
-    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous()
-                                 and tuple(bias.shape) == (weight.shape[0],)):
-        raise DisscError("nn.conv1d: bias must be a contiguous fp32 device tensor [Cout]")
+    Cout = _check_layer(CONV1D, x, weight, bias, lengths)
     if add is not None:
-        _check_act(add, "add", B, ld)
-        if add.shape[1] != weight.shape[0]:
+        _check_act(add, "add", x.shape[0], x.shape[2])
+        if add.shape[1] != Cout:
             raise DisscError("nn.conv1d: add must have Cout channels")
-    if lengths is not None and not (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous()
-                                    and tuple(lengths.shape) == (B,)):
-        raise DisscError("nn.conv1d: lengths must be a contiguous int32 device tensor [B]")
     return _Conv1dFn.apply(x, weight, bias, add, lengths, int(dilation), float(in_slope))
 
 
 class _ConvTranspose1dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, lengths, stride, in_slope):
-        B, Cin, ld = x.shape
-        _, Cout, k = weight.shape
-        h = _handle_t(Cin, Cout, k, stride, x.device)
-        st = current_stream_ptr(x.device)
-        ldo = stride * ld
-        with torch.cuda.device(x.device):
-            check(lib.dissc_convtgrad_set_weights(h, _ptr(weight), _ptr(bias), st), "dissc_convtgrad_set_weights")
-            y = torch.zeros((B, Cout, ldo), dtype=torch.float32, device=x.device) if lengths is not None else \
-                torch.empty((B, Cout, ldo), dtype=torch.float32, device=x.device)
-            check(lib.dissc_convtgrad_forward(h, _ptr(x), _ptr(y), _ptr(lengths), B, ld, ldo, ld, float(in_slope), st),
-                  "dissc_convtgrad_forward")
-        ctx.save_for_backward(x, weight)  # never y
-        ctx.lengths, ctx.stride, ctx.in_slope, ctx.has_bias = lengths, int(stride), float(in_slope), bias is not None
-        return y
+        return _forward(CONV_TRANSPOSE1D, ctx, x, weight, bias, lengths, stride, in_slope)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
-        B, Cin, ld = x.shape
-        _, Cout, k = weight.shape
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        gy = gy.contiguous()
-        gx = gw = gb = ws = None
-        if need_x or need_w or need_b:
-            h = _handle_t(Cin, Cout, k, ctx.stride, x.device)
-            st = current_stream_ptr(x.device)
-            with torch.cuda.device(x.device):
-                if need_x:  # another layer sharing the handle may have run since the forward: pack again (device only)
-                    check(lib.dissc_convtgrad_set_weights(h, _ptr(weight), None, st), "dissc_convtgrad_set_weights")
-                    gx = torch.empty_like(x)
-                if need_w:
-                    gw = torch.empty_like(weight)
-                if need_b:
-                    gb = torch.empty(Cout, dtype=torch.float32, device=x.device)
-                nws = 0
-                if need_w or need_b:
-                    nws = int(lib.dissc_convtgrad_workspace_bytes(h, B, ld))
-                    ws = _workspace(x.device, nws)
-                check(lib.dissc_convtgrad_backward(h, _ptr(x), _ptr(gy), _ptr(ctx.lengths), B, ld, ctx.stride * ld, ld,
-                                                   ctx.in_slope, _ptr(gx), _ptr(gw), _ptr(gb), _ptr(ws), nws, st),
-                      "dissc_convtgrad_backward")
-        return gx, gw, gb, None, None, None
+        return _backward(CONV_TRANSPOSE1D, ctx, gy)[:3] + (None, None, None)
 
 
 def conv_transpose1d(x, weight, bias=None, stride=1, lengths=None, in_slope=1.0):
@@ -252,18 +233,7 @@ def conv_transpose1d(x, weight, bias=None, stride=1, lengths=None, in_slope=1.0)
     lengths: int32 [B] on the device (or None = ld), INPUT lengths: utterance b has stride * lengths[b] valid output positions,
     y is left zero beyond them and the incoming gradient is read as zero there; the gradient of x is zero from lengths[b] on.
     Gradients flow to x, weight and bias; x and weight are saved, y is not."""
-    who = "nn.conv_transpose1d"
-    _check_act(x, "x", who=who)
-    B, Cin, ld = x.shape
-    if not (weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 3 and weight.is_contiguous()
-            and weight.shape[0] == Cin):
-        raise DisscError(f"{who}: weight must be a contiguous fp32 device tensor [{Cin}, Cout, k]")
-    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous()
-                                 and tuple(bias.shape) == (weight.shape[1],)):
-        raise DisscError(f"{who}: bias must be a contiguous fp32 device tensor [Cout]")
-    if lengths is not None and not (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous()
-                                    and tuple(lengths.shape) == (B,)):
-        raise DisscError(f"{who}: lengths must be a contiguous int32 device tensor [B]")
+    _check_layer(CONV_TRANSPOSE1D, x, weight, bias, lengths)
     return _ConvTranspose1dFn.apply(x, weight, bias, lengths, int(stride), float(in_slope))
 
 
@@ -466,8 +436,7 @@ def embed_concat(dict_w, spkr_w, code, f0=None, spkr=None, lengths=None, ld=None
     ok = code.is_cuda and code.dtype == torch.int64 and code.is_contiguous() and code.dim() == 2
     ok = ok and (f0 is None or (f0.is_cuda and f0.dtype == torch.float32 and f0.is_contiguous() and tuple(f0.shape) == (B, T)))
     ok = ok and (spkr is None or (spkr.is_cuda and spkr.dtype == torch.int64 and spkr.is_contiguous() and tuple(spkr.shape) == (B,)))
-    ok = ok and (lengths is None or (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous()
-                                     and tuple(lengths.shape) == (B,)))
+    ok = ok and _lengths_ok(lengths, B)
     if not ok or dict_w.dim() != 2 or (spkr is not None and (_f32(spkr_w, "spkr_w", who).dim() != 2 or spkr_w.shape[1] != dict_w.shape[1])):
         raise DisscError(f"{who}: code i64 [B, T], f0 f32 [B, T], spkr i64 [B], lengths i32 [B], contiguous on the device; "
                          "tables [rows, E]")

@@ -1,10 +1,12 @@
-"""Shared by tests/test_conv_transpose_grad_cpu.py and tests/test_gpu_conv_transpose_grad.py (not a test module): the
-float64 / float32 torch restatement of dissc_amd.nn.conv_transpose1d, the generator's five upsamplers, and the phase form
-of the weight gradient the kernel uses (for seeding defects).  The bars are conv_grad_ref's."""
+"""Shared by tests/test_conv_transpose_grad_cpu.py and tests/test_gpu_conv_transpose_grad.py (not a test module): what is
+nn.conv_transpose1d's own -- the generator's five upsamplers and the other shapes, the valid masks, the phase form of the weight
+gradient the kernel uses (for seeding defects) and one generator stage.  The float64 / float32 restatement of the layer
+(layer_ref with conv_transpose_op(stride)), the ResBlock chain and the bars are conv_grad_ref's."""
 import torch
 import torch.nn.functional as F
 
-from conv_grad_ref import SLOPE, check, compare, k_cap, K_WHOLE, K_CH  # noqa: F401
+from conv_grad_ref import (SLOPE, check, compare, k_cap, K_WHOLE, K_CH, layer_ref, conv_transpose_op,  # noqa: F401
+                           resblock_chain, mask_of, _ragged, _grad)
 
 # ups[i] of the reference generator (synthdata.VCTK_CONFIG): (Cin, Cout, k, stride), and the input length of each at 28 frames
 UPS = [(512, 256, 11, 5), (256, 128, 8, 4), (128, 64, 8, 4), (64, 32, 4, 2), (32, 16, 4, 2)]
@@ -24,41 +26,6 @@ def ups_from_config():
         out.append((ch, ch // 2, k, u))
         ch //= 2
     return out
-
-
-def layer_ref(x, w, b, gy, lengths, stride, in_slope, dtype):
-    """(y, gx, gw, gb) of y = b + conv_transpose1d(lrelu(x, in_slope), w, stride, padding (k - stride) // 2) by torch autograd,
-    per utterance on its valid INPUT length n (stride * n outputs); y and gx are zero beyond.  w [Cin, Cout, k]; b may be
-    None (gb is then None)."""
-    x = x.detach().to("cpu", dtype)
-    gy = gy.detach().to("cpu", dtype)
-    w = w.detach().to("cpu", dtype).requires_grad_(True)
-    bb = None if b is None else b.detach().to("cpu", dtype).requires_grad_(True)
-    k = w.shape[2]
-    pad = (k - stride) // 2
-    y = torch.zeros(x.shape[0], w.shape[1], stride * x.shape[2], dtype=dtype)
-    gx = torch.zeros_like(x)
-    loss = 0
-    xs = []
-    for i in range(x.shape[0]):
-        n = int(lengths[i])
-        if n <= 0:
-            xs.append(None)
-            continue
-        xi = x[i:i + 1, :, :n].clone().requires_grad_(True)
-        xs.append(xi)
-        yi = F.conv_transpose1d(F.leaky_relu(xi, in_slope), w, bb, stride=stride, padding=pad)
-        assert yi.shape[2] == stride * n
-        y[i, :, :stride * n] = yi[0].detach()
-        loss = loss + (yi * gy[i:i + 1, :, :stride * n]).sum()
-    if torch.is_tensor(loss):
-        loss.backward()
-    for i, xi in enumerate(xs):
-        if xi is not None:
-            gx[i, :, :xi.shape[2]] = xi.grad[0]
-    gw = w.grad if w.grad is not None else torch.zeros_like(w)
-    gb = None if bb is None else (bb.grad if bb.grad is not None else torch.zeros_like(bb))
-    return y, gx, gw.detach(), None if gb is None else gb.detach()
 
 
 def valid_masks(lengths, ld, stride):
@@ -101,35 +68,12 @@ def stage_ref(wt, bt, stride, w, x, k, dilations, dtype, masks, lengths, gy):
     (w: conv_grad_ref.resblock1_ref's dict) on the stride * lengths outputs.  masks: six boolean tensors [B, Cout, stride ld]
     (x > 0 of every ResBlock conv's input, in call order) that replace those leaky ReLUs' branch decisions; the upsampler's
     own leaky ReLU reads x, which is an input.  Returns (y, gx, {name: gradient}) with "ups.weight" / "ups.bias" added."""
-    from conv_grad_ref import _lrelu
-    B, _, ld = x.shape
-    wd = {n: t.detach().to("cpu", dtype).requires_grad_(True) for n, t in w.items()}
-    wd["ups.weight"] = wt.detach().to("cpu", dtype).requires_grad_(True)
-    wd["ups.bias"] = bt.detach().to("cpu", dtype).requires_grad_(True)
-    x = x.detach().to("cpu", dtype)
-    pad_t = (wt.shape[2] - stride) // 2
-    y = torch.zeros(B, wt.shape[1], stride * ld, dtype=dtype)
-    gx = torch.zeros_like(x)
-    loss, xs = 0, []
-    for i in range(B):
-        n = int(lengths[i])
-        if n <= 0:
-            xs.append(None)
-            continue
-        xi = x[i:i + 1, :, :n].clone().requires_grad_(True)
-        xs.append(xi)
-        h = F.conv_transpose1d(F.leaky_relu(xi, SLOPE), wd["ups.weight"], wd["ups.bias"], stride=stride, padding=pad_t)
-        m_ = stride * n
-        for m, d in enumerate(dilations):
-            mk = lambda j: masks[2 * m + j][i:i + 1, :, :m_].cpu()  # noqa: E731
-            t = F.conv1d(_lrelu(h, SLOPE, mk(0)), wd[f"convs1.{m}.weight"], wd[f"convs1.{m}.bias"], padding=(k - 1) * d // 2,
-                         dilation=d)
-            t = F.conv1d(_lrelu(t, SLOPE, mk(1)), wd[f"convs2.{m}.weight"], wd[f"convs2.{m}.bias"], padding=(k - 1) // 2)
-            h = t + h
-        y[i, :, :m_] = h[0].detach()
-        loss = loss + (h * gy[i:i + 1, :, :m_].detach().to("cpu", dtype)).sum()
-    loss.backward()
-    for i, xi in enumerate(xs):
-        if xi is not None:
-            gx[i, :, :xi.shape[2]] = xi.grad[0]
-    return y, gx, {n: (t.grad if t.grad is not None else torch.zeros_like(t)).detach() for n, t in wd.items()}
+    wd = {n: t.detach().to("cpu", dtype).requires_grad_(True) for n, t in dict(w, **{"ups.weight": wt, "ups.bias": bt}).items()}
+    up = conv_transpose_op(stride)
+
+    def stage(i, n, xi):
+        h = up.apply(F.leaky_relu(xi, SLOPE), wd["ups.weight"], wd["ups.bias"])
+        return resblock_chain(h, wd, k, dilations, mask_of(masks, i, stride * n))
+
+    y, gx = _ragged(x.detach().to("cpu", dtype), lengths, gy.detach().to("cpu", dtype), wt.shape[1], stride, stage)
+    return y, gx, {n: _grad(t) for n, t in wd.items()}

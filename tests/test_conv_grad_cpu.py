@@ -1,6 +1,7 @@
 """dissc_amd.nn without a GPU: what dissc_convgrad_create refuses and accepts, the partial plan of the weight gradient
 (a function of the shape only, inside 64 MB for the generator), and the reference of tests/test_gpu_conv_grad.py:
-conv_grad_ref.layer_ref agrees with finite differences in float64, and the bars it is used with catch seeded defects."""
+conv_grad_ref.layer_ref agrees with finite differences in float64, the bars it is used with catch seeded defects, and the
+harness both GPU files call (conv_grad_harness.assert_layer_gradients) passes the reference and catches seeded defects."""
 import ctypes
 
 import numpy as np
@@ -8,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_grad_harness as H
 import conv_grad_ref as R
 
 
@@ -86,14 +88,14 @@ def test_layer_ref_agrees_with_finite_differences():
     x = torch.from_numpy(rs.randn(B, cin, L))
     x = torch.where(x.abs() < 0.05, torch.full_like(x, 0.3), x)  # no kink inside a finite-difference step
     w, b, gy = (torch.from_numpy(rs.randn(*s)) for s in ((cout, cin, k), (cout,), (B, cout, L)))
-    y, gx, gw, gb = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float64)
+    y, gx, gw, gb = R.layer_ref(x, w, b, gy, lengths, R.conv_op(d), slope, torch.float64)
     valid = torch.zeros(B, 1, L, dtype=torch.bool)
     for i, n in enumerate(lengths):
         valid[i, :, :n] = True
     assert not y[~valid.expand_as(y)].any() and not gx[~valid.expand_as(gx)].any()
 
     def loss(x_, w_, b_):
-        return float((R.layer_ref(x_, w_, b_, gy, lengths, d, slope, torch.float64)[0] * gy).sum())
+        return float((R.layer_ref(x_, w_, b_, gy, lengths, R.conv_op(d), slope, torch.float64)[0] * gy).sum())
 
     eps = 1e-6
     for t, g, arg in ((x, gx, 0), (w, gw, 1), (b, gb, 2)):
@@ -126,8 +128,8 @@ def test_bars_catch_seeded_defects():
     """an fp32 "kernel result" (torch on the CPU) with one seeded defect fails its bar; the clean one passes"""
     B, cin, cout, k, d, L, slope, lengths, x, w, b, gy = _setup()
     pad = (k - 1) * d // 2
-    r64 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float32)
+    r64 = R.layer_ref(x, w, b, gy, lengths, R.conv_op(d), slope, torch.float64)
+    r32 = R.layer_ref(x, w, b, gy, lengths, R.conv_op(d), slope, torch.float32)
     Y = [t.clone() for t in r32]
     kinds = ("act", "act", "weight", "vec")
     for name, kind, y, a, c in zip(("y", "gx", "gw", "gb"), kinds, Y, r64, r32):
@@ -200,3 +202,36 @@ def test_resblock_ref_masks():
     assert torch.equal(y2, y) and torch.equal(gx2, gx) and all(torch.equal(g2[n], g[n]) for n in g)
     flipped = [~m for m in masks]
     assert not torch.equal(R.resblock1_ref(w, x, k, (1, 3, 5), torch.float64, masks=flipped, lengths=lengths), y)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the harness of the two GPU files (tests/conv_grad_harness.py)
+# ---------------------------------------------------------------------------------------------------------
+def _stand_in(spec, defect=None):
+    """conv_grad_harness.run's contract on the CPU: the float32 reference, with one seeded defect"""
+    def run(x, w, b, gy, lengths, slope, add=None, need=(True, True, True)):
+        y, gx, gw, gb = (t.clone() for t in R.layer_ref(x, w, b, gy, lengths, spec.op, slope, torch.float32))
+        vi, vo = H.valid_masks(lengths, x.shape[2], spec.mul)
+        if add is not None:
+            y += add * vo
+        if defect == "gx beyond a length" and len(lengths) > 1:
+            gx[1, 0, lengths[1]] = 1e-3
+        if defect == "gw reads beyond the lengths":  # too small to move a bit of gw until the poison arrives
+            gw.view(-1)[0] += 1e-12 * float((x * (1 - vi)).sum())
+        if defect == "one tap of gw zeroed":
+            gw[:, :, 1] = 0
+        grads = [g if on else None for g, on in zip((gx, gw, gb), need)]
+        return [y] + grads + [None if add is None else gy.clone()]
+    return run
+
+
+@pytest.mark.parametrize("spec", [H.Spec(False, 3, 2, 3, 1), H.Spec(True, 3, 2, 4, 2)], ids=["conv1d", "conv_transpose1d"])
+def test_harness_passes_the_reference_and_catches_seeded_defects(spec):
+    """assert_layer_gradients, as both GPU files call it, passes the float32 reference and fails on each of three defects:
+    the merged harness kept the strictness of the two copies it replaces"""
+    lengths, ld = [9, 4, 1], 12
+    H.assert_layer_gradients(_stand_in(spec), spec, lengths, ld, seed=5)
+    for defect, said in (("gx beyond a length", "beyond the lengths"), ("gw reads beyond the lengths", "poison beyond the lengths changes gw"),
+                         ("one tap of gw zeroed", "batch gw")):
+        with pytest.raises(AssertionError, match=said):
+            H.assert_layer_gradients(_stand_in(spec, defect), spec, lengths, ld, seed=5)

@@ -1,6 +1,6 @@
 """dissc_amd.nn.conv_transpose1d without a GPU: what dissc_convtgrad_create refuses and accepts, the partial plan of the
 weight gradient (a function of the shape only, inside 64 MB for the five upsamplers), and the reference of
-tests/test_gpu_conv_transpose_grad.py: conv_transpose_grad_ref.layer_ref agrees with finite differences in float64, and
+tests/test_gpu_conv_transpose_grad.py: conv_grad_ref.layer_ref with conv_transpose_op agrees with finite differences in float64, and
 the bars it is used with catch seeded defects."""
 import ctypes
 
@@ -92,13 +92,13 @@ def test_layer_ref_agrees_with_finite_differences():
     x = torch.from_numpy(rs.randn(B, cin, L))
     x = torch.where(x.abs() < 0.05, torch.full_like(x, 0.3), x)  # no kink inside a finite-difference step
     w, b, gy = (torch.from_numpy(rs.randn(*sh)) for sh in ((cin, cout, k), (cout,), (B, cout, s * L)))
-    y, gx, gw, gb = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float64)
+    y, gx, gw, gb = R.layer_ref(x, w, b, gy, lengths, R.conv_transpose_op(s), slope, torch.float64)
     vi, vo = R.valid_masks(lengths, L, s)
     assert not y[(vo == 0).expand_as(y)].any() and not gx[(vi == 0).expand_as(gx)].any()
     assert y[1, :, :s * 4].abs().min() > 0
 
     def loss(x_, w_, b_):
-        return float((R.layer_ref(x_, w_, b_, gy, lengths, s, slope, torch.float64)[0] * gy).sum())
+        return float((R.layer_ref(x_, w_, b_, gy, lengths, R.conv_transpose_op(s), slope, torch.float64)[0] * gy).sum())
 
     eps = 1e-6
     for t, g, arg in ((x, gx, 0), (w, gw, 1), (b, gb, 2)):
@@ -127,8 +127,8 @@ def test_bars_catch_seeded_defects():
     w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k)) / np.sqrt(cin * k)).astype(np.float32))
     b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32))
     gy = torch.from_numpy(rs.randn(B, cout, s * L).astype(np.float32))
-    r64 = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float32)
+    r64 = R.layer_ref(x, w, b, gy, lengths, R.conv_transpose_op(s), slope, torch.float64)
+    r32 = R.layer_ref(x, w, b, gy, lengths, R.conv_transpose_op(s), slope, torch.float32)
     kinds = ("act", "act", "weight", "vec")
     for name, kind, y, a, c in zip(("y", "gx", "gw", "gb"), kinds, r32, r64, r32):
         assert not R.check("clean " + name, kind, y.clone(), a, c)

@@ -8,10 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+import conv_grad_harness as H
 import conv_grad_ref as R
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+DEV = H.DEV
 
 
 @pytest.fixture(scope="module")
@@ -20,30 +21,6 @@ def nn():
     ge.build()
     from dissc_amd import nn
     return nn
-
-
-def _case(cin, cout, k, B, ld, seed, bias=True):
-    rs = np.random.RandomState(seed)
-    x = torch.from_numpy(rs.randn(B, cin, ld).astype(np.float32))
-    x[torch.from_numpy(rs.rand(B, cin, ld) < 0.02)] = 0.0  # exact zeros: the x = 0 branch is the slope
-    w = torch.from_numpy((rs.uniform(-1, 1, (cout, cin, k)) / np.sqrt(cin * k)).astype(np.float32))
-    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)) if bias else None
-    gy = torch.from_numpy(rs.randn(B, cout, ld).astype(np.float32))
-    return x, w, b, gy
-
-
-def _run(nn, x, w, b, gy, lengths, d, slope, add=None, need=(True, True, True)):
-    """one forward + backward of nn.conv1d on the device; returns y, gx, gw, gb (and the gradient of add)"""
-    xd = x.to(DEV).requires_grad_(need[0])
-    wd = w.to(DEV).requires_grad_(need[1])
-    bd = None if b is None else b.to(DEV).requires_grad_(need[2])
-    ad = None if add is None else add.to(DEV).requires_grad_(True)
-    ln = None if lengths is None else torch.tensor(lengths, dtype=torch.int32, device=DEV)
-    y = nn.conv1d(xd, wd, bd, lengths=ln, dilation=d, in_slope=slope, add=ad)
-    y.backward(gy.to(DEV))
-    torch.cuda.synchronize()
-    out = [y.detach().cpu()] + [None if t is None or t.grad is None else t.grad.cpu() for t in (xd, wd, bd)]
-    return out + [None if ad is None else ad.grad.cpu()]
 
 
 def _conv1d_host(x, w, b, lengths, d, slope):
@@ -64,29 +41,14 @@ def _conv1d_host(x, w, b, lengths, d, slope):
                                                 (16, 1, 7, 1, 0.01)])
 def test_device_packing_bit_for_bit(nn, cin, cout, k, d, slope):
     B, ld, lengths = 3, 100, [100, 37, 3]
-    x, w, b, gy = _case(cin, cout, k, B, ld, seed=cin + k)
-    y, gx, _, _, _ = _run(nn, x, w, b, gy, lengths, d, slope)
+    spec = H.Spec(False, cin, cout, k, d)
+    x, w, b, gy = H.case(spec, B, ld, seed=cin + k)
+    y, gx, _, _, _ = H.gpu_run(nn, spec)(x, w, b, gy, lengths, slope)
     assert torch.equal(y, _conv1d_host(x, w, b, lengths, d, slope))
     wt = w.transpose(0, 1).flip(2).contiguous()  # [Cin][Cout][k], taps flipped
     plain = _conv1d_host(gy, wt, None, lengths, d, 1.0)  # the data gradient before the mask
     assert torch.equal(gx, plain * torch.where(x > 0, torch.tensor(1.0), torch.tensor(np.float32(slope))))
     assert plain.abs().sum() > 0
-
-
-def _lengths_for(nn, cin, cout, k, d):
-    """1, 2, pad, pad + 1, chunk - 1, chunk, chunk + 1, 2 chunk + 1, and, where the plan has one inside an utterance, a length
-    on either side of a partial boundary (placed in the utterance the boundary falls in)"""
-    T, pad = nn.WGRAD_CHUNK, (k - 1) * d // 2
-    lengths = [1, 2, pad, pad + 1, T - 1, T, T + 1, 2 * T + 1, T, 2 * T + 1]
-    B, ld = len(lengths), (2 * T + 1 + 3) // 4 * 4
-    P, pairs = nn.wgrad_partials(B, ld, cin, cout, k)
-    nch = -(-ld // T)
-    inside = [divmod(p * pairs, nch) for p in range(1, P) if (p * pairs) % nch]
-    if inside:
-        b, c = inside[len(inside) // 2]
-        lengths[8], lengths[9] = c * T, c * T + 1
-        lengths[b], lengths[9] = lengths[9], lengths[b]  # this utterance's chunk c belongs to the next partial
-    return lengths, ld, (P, pairs)
 
 
 LAYERS = [(16, 16, 3, 1), (16, 16, 11, 5), (32, 32, 7, 3), (64, 64, 11, 5), (128, 128, 3, 3), (256, 256, 7, 1), (257, 512, 7, 1),
@@ -95,58 +57,10 @@ LAYERS = [(16, 16, 3, 1), (16, 16, 11, 5), (32, 32, 7, 3), (64, 64, 11, 5), (128
 
 @pytest.mark.parametrize("cin,cout,k,d", LAYERS)
 def test_layer_gradients_against_float64(nn, cin, cout, k, d):
-    slope = 0.1
-    lengths, ld, plan = _lengths_for(nn, cin, cout, k, d)
-    B = len(lengths)
-    x, w, b, gy = _case(cin, cout, k, B, ld, seed=7 * cin + k + d)
-    add = torch.from_numpy(np.random.RandomState(1).randn(B, cout, ld).astype(np.float32))
-    print(f"\nlayer {cin} -> {cout} k {k} d {d}: lengths {lengths}, ld {ld}, (P, pairs) {plan}")
-    y, gx, gw, gb, gadd = _run(nn, x, w, b, gy, lengths, d, slope, add=add)
-    r64 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float32)
-    valid = torch.zeros(B, 1, ld)
-    for i, n in enumerate(lengths):
-        valid[i, :, :n] = 1
-    bad = R.check("batch y", "act", y, r64[0] + add.double() * valid.double(), r32[0] + add * valid, *k_direct(cin * k))
-    bad += R.check("batch gx", "act", gx, r64[1], r32[1], *k_direct(cout * k))
-    bad += R.check("batch gw", "weight", gw, r64[2], r32[2])
-    bad += R.check("batch gb", "vec", gb, r64[3], r32[3])
-    # the gradient of add is gy itself; nothing is written or propagated beyond lengths
-    assert torch.equal(gadd, gy)
-    assert not gx[(valid == 0).expand_as(gx)].any() and not y[(valid == 0).expand_as(y)].any()
-    # bit-reproducible
-    again = _run(nn, x, w, b, gy, lengths, d, slope, add=add)
-    assert torch.equal(again[2], gw) and torch.equal(again[3], gb) and torch.equal(again[1], gx)
-    # poison beyond lengths changes nothing
-    xp, gyp = x.clone(), gy.clone()
-    xp[(valid == 0).expand_as(x)] = 1e30
-    gyp[(valid == 0).expand_as(gy)] = 1e30
-    yq, gxq, gwq, gbq, _ = _run(nn, xp, w, b, gyp, lengths, d, slope, add=add)
-    assert torch.equal(yq, y) and torch.equal(gxq, gx) and torch.equal(gwq, gw) and torch.equal(gbq, gb)
-    # needs_input_grad false for x or for weight: the others keep their bits
-    _, gx0, gw0, gb0, _ = _run(nn, x, w, b, gy, lengths, d, slope, add=add, need=(False, True, True))
-    assert gx0 is None and torch.equal(gw0, gw) and torch.equal(gb0, gb)
-    _, gx1, gw1, gb1, _ = _run(nn, x, w, b, gy, lengths, d, slope, add=add, need=(True, False, True))
-    assert gw1 is None and torch.equal(gx1, gx) and torch.equal(gb1, gb)
-    _, gx2, gw2, gb2, _ = _run(nn, x, w, b, gy, lengths, d, slope, add=add, need=(True, True, False))
-    assert gb2 is None and torch.equal(gx2, gx) and torch.equal(gw2, gw)
-    # every utterance alone: the same gx bits as in the batch, its own gradients inside the bars
-    worst = {}
-    for i, n in enumerate(lengths):
-        if n <= 0:
-            continue
-        sl = slice(i, i + 1)
-        yi, gxi, gwi, gbi, _ = _run(nn, x[sl], w, b, gy[sl], [n], d, slope)
-        assert torch.equal(gxi, gx[sl]), (i, n)
-        a64 = R.layer_ref(x[sl], w, b, gy[sl], [n], d, slope, torch.float64)
-        a32 = R.layer_ref(x[sl], w, b, gy[sl], [n], d, slope, torch.float32)
-        for name, kind, t, j in (("gw", "weight", gwi, 2), ("gb", "vec", gbi, 3)):
-            m = R.compare(kind, t, a64[j], a32[j])
-            bad += R.check(f"alone len {n} {name}", kind, t, a64[j], a32[j], verbose=False)
-            for what in ("ratio", "ch_ratio"):
-                worst[(name, what)] = max(worst.get((name, what), 0.0), m[what])
-    print("CG alone, worst over the lengths:", {f"{a}/{b}": round(v, 3) for (a, b), v in worst.items()})
-    assert not bad, bad
+    spec = H.Spec(False, cin, cout, k, d)
+    lengths, ld, plan = H.lengths_for(nn, spec)
+    print(f"\nlayer {spec}: lengths {lengths}, ld {ld}, (P, pairs) {plan}")
+    H.assert_layer_gradients(H.gpu_run(nn, spec), spec, lengths, ld, 7 * cin + k + d, k_direct(cin * k), k_direct(cout * k))
 
 
 # The one exception to K = 4 (tests/train_stage_cases.py's rule): the forward and the data gradient are the direct conv
@@ -175,22 +89,9 @@ TRAIN = [(16, 16, 11, 5, 8960), (256, 256, 11, 5, 140), (257, 512, 7, 1, 28)]
 def test_training_shapes(nn, cin, cout, k, d, L):
     """B = 32 at the generator's own lengths (28 frames): the 286 720-long reduction of the narrowest stage, the widest
     ResBlock layer, conv_pre"""
-    B, slope = 32, 0.1
-    lengths = [L] * B
-    for i, n in zip((1, 5, 17, 31), (L // 2 + 1, 1, L - 1, max(1, L // 3))):
-        lengths[i] = n
-    x, w, b, gy = _case(cin, cout, k, B, L, seed=L + k)
-    print(f"\ntraining shape {cin} -> {cout} k {k} d {d} L {L}: plan {nn.wgrad_partials(B, L, cin, cout, k)}")
-    y, gx, gw, gb, _ = _run(nn, x, w, b, gy, lengths, d, slope)
-    r64 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, d, slope, torch.float32)
-    bad = R.check("train y", "act", y, r64[0], r32[0], *k_direct(cin * k))
-    bad += R.check("train gx", "act", gx, r64[1], r32[1], *k_direct(cout * k))
-    bad += R.check("train gw", "weight", gw, r64[2], r32[2])
-    bad += R.check("train gb", "vec", gb, r64[3], r32[3])
-    assert not bad, bad
-    again = _run(nn, x, w, b, gy, lengths, d, slope)
-    assert torch.equal(again[2], gw) and torch.equal(again[3], gb)
+    spec = H.Spec(False, cin, cout, k, d)
+    print(f"\ntraining shape {spec} L {L}: plan {H.partials(nn, spec, 32, L)}")
+    H.assert_training_shape(H.gpu_run(nn, spec), spec, L, k_direct(cin * k), k_direct(cout * k))
 
 
 @pytest.mark.parametrize("C,k", [(32, 7), (16, 11)])

@@ -10,10 +10,11 @@ import numpy as np
 import pytest
 import torch
 
+import conv_grad_harness as H
 import conv_transpose_grad_ref as R
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+DEV = H.DEV
 
 
 @pytest.fixture(scope="module")
@@ -22,28 +23,6 @@ def nn():
     ge.build()
     from dissc_amd import nn
     return nn
-
-
-def _case(cin, cout, k, s, B, ld, seed, bias=True):
-    rs = np.random.RandomState(seed)
-    x = torch.from_numpy(rs.randn(B, cin, ld).astype(np.float32))
-    x[torch.from_numpy(rs.rand(B, cin, ld) < 0.02)] = 0.0  # exact zeros: the x = 0 branch is the slope
-    w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k)) / np.sqrt(cin * k / s)).astype(np.float32))
-    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)) if bias else None
-    gy = torch.from_numpy(rs.randn(B, cout, s * ld).astype(np.float32))
-    return x, w, b, gy
-
-
-def _run(nn, x, w, b, gy, lengths, s, slope, need=(True, True, True)):
-    """one forward + backward of nn.conv_transpose1d on the device; returns y, gx, gw, gb"""
-    xd = x.to(DEV).requires_grad_(need[0])
-    wd = w.to(DEV).requires_grad_(need[1])
-    bd = None if b is None else b.to(DEV).requires_grad_(need[2])
-    ln = None if lengths is None else torch.tensor(lengths, dtype=torch.int32, device=DEV)
-    y = nn.conv_transpose1d(xd, wd, bd, stride=s, lengths=ln, in_slope=slope)
-    y.backward(gy.to(DEV))
-    torch.cuda.synchronize()
-    return [y.detach().cpu()] + [None if t is None or t.grad is None else t.grad.cpu() for t in (xd, wd, bd)]
 
 
 def _conv_transpose1d_host(x, w, b, lengths, s, slope):
@@ -64,30 +43,15 @@ def _conv_transpose1d_host(x, w, b, lengths, s, slope):
 @pytest.mark.parametrize("cin,cout,k,s", R.UPS + R.OFF_GRID + R.OTHER_STRIDES)
 def test_device_packing_bit_for_bit(nn, cin, cout, k, s):
     B, ld, lengths, slope = 3, 100, [100, 37, 3], 0.1
-    x, w, b, gy = _case(cin, cout, k, s, B, ld, seed=cin + k)
-    y = _run(nn, x, w, b, gy, lengths, s, slope)[0]
+    spec = H.Spec(True, cin, cout, k, s)
+    x, w, b, gy = H.case(spec, B, ld, seed=cin + k)
+    y = H.gpu_run(nn, spec)(x, w, b, gy, lengths, slope)[0]
     host = _conv_transpose1d_host(x, w, b, lengths, s, slope)
     assert torch.equal(y, host)
     assert host[0].abs().min() > 0 and not host[2, :, s * 3:].any()
     # without a bias: the replicated bias rows are rewritten as zeros, not left over from the call above
-    y0 = _run(nn, x, w, None, gy, lengths, s, slope)[0]
+    y0 = H.gpu_run(nn, spec)(x, w, None, gy, lengths, slope)[0]
     assert torch.equal(y0, _conv_transpose1d_host(x, w, None, lengths, s, slope))
-
-
-def _lengths_for(nn, cin, cout, k, s):
-    """1, 2, 3, chunk - 1, chunk, chunk + 1, 2 chunk + 1, and, where the plan has one inside an utterance, a length on either
-    side of a partial boundary (placed in the utterance the boundary falls in)"""
-    T = nn.WGRAD_CHUNK
-    lengths = [1, 2, 3, T - 1, T, T + 1, 2 * T + 1, T, 2 * T + 1]
-    B, ld = len(lengths), (2 * T + 1 + 3) // 4 * 4
-    P, pairs = nn.wgrad_partials_transpose(B, ld, cin, cout, k, s)
-    nch = -(-ld // T)
-    inside = [divmod(p * pairs, nch) for p in range(1, P) if (p * pairs) % nch]
-    if inside:
-        b, c = inside[len(inside) // 2]
-        lengths[7], lengths[8] = c * T, c * T + 1
-        lengths[b], lengths[8] = lengths[8], lengths[b]  # this utterance's chunk c belongs to the next partial
-    return lengths, ld, (P, pairs)
 
 
 # Exceptions to K = 4 (tests/train_stage_cases.py's rule: only where one output is ONE sequential fp32 chain of n >= 1 024
@@ -110,59 +74,10 @@ def _k(tensor, cin, cout, k, s):
 
 @pytest.mark.parametrize("cin,cout,k,s", R.UPS + R.OFF_GRID + R.OTHER_STRIDES)
 def test_layer_gradients_against_float64(nn, cin, cout, k, s):
-    slope = 0.1
-    lengths, ld, plan = _lengths_for(nn, cin, cout, k, s)
-    B = len(lengths)
-    x, w, b, gy = _case(cin, cout, k, s, B, ld, seed=7 * cin + k + s)
-    print(f"\nlayer {cin} -> {cout} k {k} s {s}: lengths {lengths}, ld {ld}, (P, pairs) {plan}")
-    y, gx, gw, gb = _run(nn, x, w, b, gy, lengths, s, slope)
-    r64 = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float32)
-    vi, vo = R.valid_masks(lengths, ld, s)
-    bad = R.check("batch y", "act", y, r64[0], r32[0], *_k("y", cin, cout, k, s))
-    bad += R.check("batch gx", "act", gx, r64[1], r32[1], *_k("gx", cin, cout, k, s))
-    bad += R.check("batch gw", "weight", gw, r64[2], r32[2])
-    bad += R.check("batch gb", "vec", gb, r64[3], r32[3])
-    # nothing is written or propagated beyond the lengths
-    assert not gx[(vi == 0).expand_as(gx)].any() and not y[(vo == 0).expand_as(y)].any()
-    # bit-reproducible
-    again = _run(nn, x, w, b, gy, lengths, s, slope)
-    assert torch.equal(again[2], gw) and torch.equal(again[3], gb) and torch.equal(again[1], gx)
-    # poison beyond the lengths changes nothing
-    xp, gyp = x.clone(), gy.clone()
-    xp[(vi == 0).expand_as(x)] = 1e30
-    gyp[(vo == 0).expand_as(gy)] = 1e30
-    yq, gxq, gwq, gbq = _run(nn, xp, w, b, gyp, lengths, s, slope)
-    assert torch.equal(yq, y) and torch.equal(gxq, gx) and torch.equal(gwq, gw) and torch.equal(gbq, gb)
-    # needs_input_grad false for x, weight or bias: the others keep their bits
-    _, gx0, gw0, gb0 = _run(nn, x, w, b, gy, lengths, s, slope, need=(False, True, True))
-    assert gx0 is None and torch.equal(gw0, gw) and torch.equal(gb0, gb)
-    _, gx1, gw1, gb1 = _run(nn, x, w, b, gy, lengths, s, slope, need=(True, False, True))
-    assert gw1 is None and torch.equal(gx1, gx) and torch.equal(gb1, gb)
-    _, gx2, gw2, gb2 = _run(nn, x, w, b, gy, lengths, s, slope, need=(True, True, False))
-    assert gb2 is None and torch.equal(gx2, gx) and torch.equal(gw2, gw)
-    _, gx3, gw3, gb3 = _run(nn, x, w, b, gy, lengths, s, slope, need=(True, False, False))
-    assert gw3 is None and gb3 is None and torch.equal(gx3, gx)
-    _, gx4, gw4, gb4 = _run(nn, x, w, b, gy, lengths, s, slope, need=(False, False, True))
-    assert gx4 is None and gw4 is None and torch.equal(gb4, gb)
-    # every utterance alone: the same gx bits as in the batch, its own gradients inside the bars
-    worst = {}
-    for i, n in enumerate(lengths):
-        if n <= 0:
-            continue
-        sl = slice(i, i + 1)
-        yi, gxi, gwi, gbi = _run(nn, x[sl], w, b, gy[sl], [n], s, slope)
-        assert torch.equal(gxi, gx[sl]), (i, n)
-        assert torch.equal(yi, y[sl]), (i, n)
-        a64 = R.layer_ref(x[sl], w, b, gy[sl], [n], s, slope, torch.float64)
-        a32 = R.layer_ref(x[sl], w, b, gy[sl], [n], s, slope, torch.float32)
-        for name, kind, t, j in (("gw", "weight", gwi, 2), ("gb", "vec", gbi, 3)):
-            m = R.compare(kind, t, a64[j], a32[j])
-            bad += R.check(f"alone len {n} {name}", kind, t, a64[j], a32[j], verbose=False)
-            for what in ("ratio", "ch_ratio"):
-                worst[(name, what)] = max(worst.get((name, what), 0.0), m[what])
-    print("CG alone, worst over the lengths:", {f"{a}/{b}": round(v, 3) for (a, b), v in worst.items()})
-    assert not bad, bad
+    spec = H.Spec(True, cin, cout, k, s)
+    lengths, ld, plan = H.lengths_for(nn, spec)
+    print(f"\nlayer {spec}: lengths {lengths}, ld {ld}, (P, pairs) {plan}")
+    H.assert_layer_gradients(H.gpu_run(nn, spec), spec, lengths, ld, 7 * cin + k + s, _k("y", cin, cout, k, s), _k("gx", cin, cout, k, s))
 
 
 TRAIN = [(512, 256, 11, 5, 28), (32, 16, 4, 2, 4480)]
@@ -172,22 +87,9 @@ TRAIN = [(512, 256, 11, 5, 28), (32, 16, 4, 2, 4480)]
 def test_training_shapes(nn, cin, cout, k, s, L):
     """B = 32 at the generator's own lengths (28 frames): the widest upsampler at 28 input positions, and the longest
     reduction, 32 x 4 480, of the narrowest"""
-    B, slope = 32, 0.1
-    lengths = [L] * B
-    for i, n in zip((1, 5, 17, 31), (L // 2 + 1, 1, L - 1, max(1, L // 3))):
-        lengths[i] = n
-    x, w, b, gy = _case(cin, cout, k, s, B, L, seed=L + k)
-    print(f"\ntraining shape {cin} -> {cout} k {k} s {s} L {L}: plan {nn.wgrad_partials_transpose(B, L, cin, cout, k, s)}")
-    y, gx, gw, gb = _run(nn, x, w, b, gy, lengths, s, slope)
-    r64 = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float32)
-    bad = R.check("train y", "act", y, r64[0], r32[0], *_k("y", cin, cout, k, s))
-    bad += R.check("train gx", "act", gx, r64[1], r32[1], *_k("gx", cin, cout, k, s))
-    bad += R.check("train gw", "weight", gw, r64[2], r32[2])
-    bad += R.check("train gb", "vec", gb, r64[3], r32[3])
-    assert not bad, bad
-    again = _run(nn, x, w, b, gy, lengths, s, slope)
-    assert torch.equal(again[1], gx) and torch.equal(again[2], gw) and torch.equal(again[3], gb)
+    spec = H.Spec(True, cin, cout, k, s)
+    print(f"\ntraining shape {spec} L {L}: plan {H.partials(nn, spec, 32, L)}")
+    H.assert_training_shape(H.gpu_run(nn, spec), spec, L, _k("y", cin, cout, k, s), _k("gx", cin, cout, k, s))
 
 
 def test_stage_against_float64_with_the_engines_masks(nn):

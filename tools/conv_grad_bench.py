@@ -57,116 +57,60 @@ def executed_flops(cin, cout, k, positions):
     return direct(cout, cin), direct(cin, cout), 2.0 * rup(cout, 32) * 32 * -(-cin // 32) * ng * positions
 
 
-def bench_shape(a, cin, cout, k, d, L):
+def bench_layer(a, kind, cin, cout, k, p_, L):
+    """one layer through its nn layer kind (nn.CONV1D: p_ = dilation; nn.CONV_TRANSPOSE1D: p_ = stride) and through torch"""
     from dissc_amd import nn
-    from dissc_amd._lib import check, current_stream_ptr, lib
+    from dissc_amd._lib import check, current_stream_ptr
     F = torch.nn.functional
     dev = torch.device("cuda:0")
-    B, slope = a.batch, 0.1
-    rs = np.random.RandomState(0)
-    ld = rup(L, 4)
-    x = torch.from_numpy(rs.standard_normal((B, cin, ld)).astype(np.float32)).to(dev)
-    gy = torch.from_numpy(rs.standard_normal((B, cout, ld)).astype(np.float32)).to(dev)
-    w = torch.from_numpy((rs.uniform(-1, 1, (cout, cin, k)) / np.sqrt(cin * k)).astype(np.float32)).to(dev)
-    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)).to(dev)
-    lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
-    y, gx, gw, gb = torch.zeros_like(gy), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
-    h = nn._handle(cin, cout, k, d, dev)
-    st = current_stream_ptr(dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    nws = int(lib.dissc_convgrad_workspace_bytes(h, B, ld))
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    check(lib.dissc_convgrad_set_weights(h, p(w), p(b), st), "set_weights")
-    pad = (k - 1) * d // 2
-
-    def ours_bwd(gx_, gw_, gb_):
-        check(lib.dissc_convgrad_backward(h, p(x), p(gy), p(lengths), B, ld, ld, ld, slope, gx_, gw_, gb_, p(ws), nws, st), "backward")
-
-    xa = F.leaky_relu(x, slope)
-    conv_bwd = torch.ops.aten.convolution_backward
-
-    def torch_bwd(mask):
-        return conv_bwd(gy, xa, w, [cout], [1], [pad], [d], False, [0], 1, mask)
-
-    cases = {
-        "fwd": lambda: check(lib.dissc_convgrad_forward(h, p(x), None, p(y), p(lengths), B, ld, ld, ld, slope, st), "forward"),
-        "torch_fwd": lambda: F.conv1d(F.leaky_relu(x, slope), w, b, padding=pad, dilation=d),
-        "dgrad": lambda: ours_bwd(p(gx), None, None),
-        "torch_dgrad": lambda: torch_bwd([True, False, False]),
-        "wgrad": lambda: ours_bwd(None, p(gw), p(gb)),
-        "torch_wgrad": lambda: torch_bwd([False, True, True]),
-        "repack": lambda: check(lib.dissc_convgrad_set_weights(h, p(w), p(b), st), "set_weights"),
-    }
-    # agreement first (fp32 both sides)
-    cases["fwd"](), cases["dgrad"](), cases["wgrad"]()
-    tg = torch_bwd([True, True, True])
-    rel = lambda u, v: float((u - v).norm() / v.norm())
-    agree = {"y": rel(y, cases["torch_fwd"]()), "gx": rel(gx, tg[0] * torch.where(x > 0, 1.0, slope)), "gw": rel(gw, tg[1]),
-             "gb": rel(gb, tg[2])}
-    for fn in cases.values():
-        timed(fn, 2)
-    times = {n: [] for n in cases}
-    for _ in range(a.blocks):
-        for n, fn in cases.items():  # alternating
-            times[n].append(timed(fn, a.iters))
-    P, pairs = nn.wgrad_partials(B, ld, cin, cout, k)
-    out = {"cin": cin, "cout": cout, "k": k, "dilation": d, "L": L, "batch": B, "partials": P, "pairs_per_partial": pairs,
-           "workspace_mb": round(nws / 2**20, 2), "rel_diff_to_torch": {n: float(f"{v:.2e}") for n, v in agree.items()}}
-    for n, v in times.items():
-        out[n + "_ms"] = round(float(np.median(v)), 4)
-        out[n + "_ms_spread"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
-    for n, fl in zip(("fwd", "dgrad", "wgrad"), executed_flops(cin, cout, k, B * L)):
-        out[n + "_tflops"] = round(fl / (out[n + "_ms"] * 1e-3) / 1e12, 2)
-    print(json.dumps(out), flush=True)
-    return out
-
-
-def bench_transpose(a, cin, cout, k, s, L):
-    from dissc_amd import nn
-    from dissc_amd._lib import check, current_stream_ptr, lib
-    F = torch.nn.functional
-    dev = torch.device("cuda:0")
+    tr = kind is nn.CONV_TRANSPOSE1D
+    s, d = (p_, 1) if tr else (1, p_)
     B, slope = a.batch, 0.1
     rs = np.random.RandomState(0)
     ld = rup(L, 4)
     x = torch.from_numpy(rs.standard_normal((B, cin, ld)).astype(np.float32)).to(dev)
     gy = torch.from_numpy(rs.standard_normal((B, cout, s * ld)).astype(np.float32)).to(dev)
-    w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k)) / np.sqrt(cin * k / s)).astype(np.float32)).to(dev)
+    w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k) if tr else (cout, cin, k)) / np.sqrt(cin * k / s)).astype(np.float32)).to(dev)
     b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)).to(dev)
     lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
     y, gx, gw, gb = torch.zeros_like(gy), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
-    h = nn._handle_t(cin, cout, k, s, dev)
+    h = nn._handle(kind, cin, cout, k, p_, dev)
     st = current_stream_ptr(dev)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
-    nws = int(lib.dissc_convtgrad_workspace_bytes(h, B, ld))
+    nws = int(kind.workspace_bytes(h, B, ld))
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    check(lib.dissc_convtgrad_set_weights(h, p(w), p(b), st), "set_weights")
-    pad = (k - s) // 2
+    check(kind.set_weights(h, p(w), p(b), st), "set_weights")
+    pad = (k - s) // 2 if tr else (k - 1) * d // 2
+    add = () if tr else (None,)
 
     def ours_bwd(gx_, gw_, gb_):
-        check(lib.dissc_convtgrad_backward(h, p(x), p(gy), p(lengths), B, ld, s * ld, ld, slope, gx_, gw_, gb_, p(ws), nws, st),
-              "backward")
+        check(kind.backward(h, p(x), p(gy), p(lengths), B, ld, s * ld, ld, slope, gx_, gw_, gb_, p(ws), nws, st), "backward")
 
     xa = F.leaky_relu(x, slope)
     conv_bwd = torch.ops.aten.convolution_backward
 
     def torch_bwd(mask):
-        return conv_bwd(gy, xa, w, [cout], [s], [pad], [1], True, [0], 1, mask)
+        return conv_bwd(gy, xa, w, [cout], [s], [pad], [d], tr, [0], 1, mask)
+
+    def torch_fwd():
+        xl = F.leaky_relu(x, slope)
+        return F.conv_transpose1d(xl, w, b, stride=s, padding=pad) if tr else F.conv1d(xl, w, b, padding=pad, dilation=d)
 
     cases = {
-        "fwd": lambda: check(lib.dissc_convtgrad_forward(h, p(x), p(y), p(lengths), B, ld, s * ld, ld, slope, st), "forward"),
-        "torch_fwd": lambda: F.conv_transpose1d(F.leaky_relu(x, slope), w, b, stride=s, padding=pad),
+        "fwd": lambda: check(kind.forward(h, p(x), *add, p(y), p(lengths), B, ld, s * ld, ld, slope, st), "forward"),
+        "torch_fwd": torch_fwd,
         "dgrad": lambda: ours_bwd(p(gx), None, None),
         "torch_dgrad": lambda: torch_bwd([True, False, False]),
         "wgrad": lambda: ours_bwd(None, p(gw), p(gb)),
         "torch_wgrad": lambda: torch_bwd([False, True, True]),
-        "repack": lambda: check(lib.dissc_convtgrad_set_weights(h, p(w), p(b), st), "set_weights"),
+        "repack": lambda: check(kind.set_weights(h, p(w), p(b), st), "set_weights"),
     }
+    # agreement first (fp32 both sides)
     cases["fwd"](), cases["dgrad"](), cases["wgrad"]()
     tg = torch_bwd([True, True, True])
     rel = lambda u, v: float((u - v).norm() / v.norm())
     valid = (torch.arange(ld, device=dev) < L).float()
-    agree = {"y": rel(y[:, :, :s * L], cases["torch_fwd"]()[:, :, :s * L]) if ld == L else None,
+    agree = {"y": rel(y[:, :, :s * L], torch_fwd()[:, :, :s * L]) if ld == L else None,
              "gx": rel(gx, tg[0] * torch.where(x > 0, 1.0, slope) * valid), "gw": rel(gw, tg[1]), "gb": rel(gb, tg[2])}
     for fn in cases.values():
         timed(fn, 2)
@@ -174,25 +118,29 @@ def bench_transpose(a, cin, cout, k, s, L):
     for _ in range(a.blocks):
         for n, fn in cases.items():  # alternating
             times[n].append(timed(fn, a.iters))
-    P, pairs = nn.wgrad_partials_transpose(B, ld, cin, cout, k, s)
-    out = {"transpose": True, "cin": cin, "cout": cout, "k": k, "stride": s, "L": L, "batch": B, "partials": P,
-           "pairs_per_partial": pairs, "workspace_mb": round(nws / 2**20, 2),
-           "rel_diff_to_torch": {n: None if v is None else float(f"{v:.2e}") for n, v in agree.items()}}
+    P, pairs = nn._partials(kind, B, ld, cin, cout, k, p_)
+    out = {"transpose": True} if tr else {}
+    out.update({"cin": cin, "cout": cout, "k": k, "stride" if tr else "dilation": p_, "L": L, "batch": B, "partials": P,
+                "pairs_per_partial": pairs, "workspace_mb": round(nws / 2**20, 2),
+                "rel_diff_to_torch": {n: None if v is None else float(f"{v:.2e}") for n, v in agree.items()}})
     for n, v in times.items():
         out[n + "_ms"] = round(float(np.median(v)), 4)
         out[n + "_ms_spread"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
-    for n in ("fwd", "dgrad", "wgrad"):
-        out[n + "_tflops"] = round(2.0 * cin * cout * k * B * L / (out[n + "_ms"] * 1e-3) / 1e12, 2)
+    # the transposed layer: the direct form's MACs, Cin Cout k per input position
+    flops = [2.0 * cin * cout * k * B * L] * 3 if tr else executed_flops(cin, cout, k, B * L)
+    for n, fl in zip(("fwd", "dgrad", "wgrad"), flops):
+        out[n + "_tflops"] = round(fl / (out[n + "_ms"] * 1e-3) / 1e12, 2)
     print(json.dumps(out), flush=True)
     return out
 
 
 def main_transpose(a):
     import conv_transpose_grad_ref as RT
+    from dissc_amd import nn
     rows, L = [], a.frames
     for cin, cout, k, s in RT.ups_from_config():
         if not a.only or [cin, cout, k] == [int(v) for v in a.only.split(",")]:
-            rows.append(bench_transpose(a, cin, cout, k, s, L))
+            rows.append(bench_layer(a, nn.CONV_TRANSPOSE1D, cin, cout, k, s, L))
         L *= s
     if a.markdown:
         print("| layer | L in | fwd ms (torch) | dgrad ms (torch) | wgrad ms (torch) | TFLOP/s fwd / dgrad / wgrad | P | repack ms |")
@@ -220,6 +168,7 @@ def main(argv=None):
     if a.transpose:
         return main_transpose(a)
     import conv_grad_ref as R
+    from dissc_amd import nn
     seen, rows = set(), []
     for cin, cout, k, d, L in R.generator_layer_shapes(a.frames):
         if (cin, cout, k) in seen or d not in (1, 3) or (cin == cout and d != 3):
@@ -227,7 +176,7 @@ def main(argv=None):
         if a.only and [cin, cout, k] != [int(v) for v in a.only.split(",")]:
             continue
         seen.add((cin, cout, k))
-        rows.append(bench_shape(a, cin, cout, k, d, L))
+        rows.append(bench_layer(a, nn.CONV1D, cin, cout, k, d, L))
     if a.markdown:
         print("| layer | L | fwd ms (torch) | dgrad ms (torch) | wgrad ms (torch) | TFLOP/s fwd / dgrad / wgrad | P | repack ms |")
         print("|---|---|---|---|---|---|---|---|")
