@@ -53,6 +53,10 @@ class DisscWino8Plan(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("mi", "ni", "wps", "r", "ns", "unit", "ot", "cpr", "gx", "gy")]
 
 
+class DisscWinoPlan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("ns", "dilation", "cpr", "rh", "tw", "shv", "unit", "ot", "gx", "gy", "wgs", "lds_bytes")]
+
+
 def _load():
     path = library_path()
     if not os.path.exists(path):
@@ -125,6 +129,7 @@ def _load():
     L.dissc_pair_info.argtypes = [i32] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2
     L.dissc_conv_info.argtypes = [i32] * 7 + [ctypes.POINTER(DisscConvLaunch), i32, ctypes.POINTER(ctypes.c_int)]
     L.dissc_wino8_info.argtypes = [i32] * 6 + [ctypes.POINTER(DisscWino8Plan)]
+    L.dissc_wino_info.argtypes = [i32] * 5 + [ctypes.POINTER(DisscWinoPlan)]
     L.dissc_resblock1d_bf3.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, ctypes.c_float, i32, ctypes.c_float, i32, i32, vp]
     L.dissc_bf3_info.argtypes = [i32] * 6 + [vp, i32, i32, ctypes.POINTER(DisscBf3Info)]
     L.dissc_respair1d.argtypes = [vp] * 8 + [i32] * 6 + [ctypes.c_float, i32, ctypes.c_float, i32, vp]
@@ -191,6 +196,14 @@ def wino8_info(C, k, dilation, R, B, Lmax):
     out = DisscWino8Plan()
     check(lib.dissc_wino8_info(C, k, dilation, R, B, Lmax, ctypes.byref(out)), "dissc_wino8_info")
     return {f: getattr(out, f) for f, _ in DisscWino8Plan._fields_}
+
+
+def wino_info(C, k, dilation, B, Lmax):
+    """dissc_wino_info: the conv_wino_kernel (F(4,3)) instance and grid of the shape under the current option defaults, as a dict
+    (ns, dilation, cpr, rh, tw, shv, unit, ot, gx, gy, wgs, lds_bytes).  Host only."""
+    out = DisscWinoPlan()
+    check(lib.dissc_wino_info(C, k, dilation, B, Lmax, ctypes.byref(out)), "dissc_wino_info")
+    return {f: getattr(out, f) for f, _ in DisscWinoPlan._fields_}
 
 
 def bf3_conv_info(Cin, Cout, k, dilation=1, B=1, Lmax=1):

@@ -376,6 +376,13 @@ int make_wino(const float* w, const float* bias, int C, int KS, int dil, DevConv
 double wino_executed_macs_per_t(int C, int KS);
 int run_wino(const DevConv& dc, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ldx, int ldo, float slope,
              hipStream_t stream);
+// the instance and grid run_wino launches for (C, k, d) on B utterances of at most Lmax columns under the current options (host
+// only; dissc_wino_info reports it): conv_wino_kernel<NS, dil, CPR, RH, TW, SHV> -- CPR channels per barrier round, RH row halves
+// ((3 - RH) column halves) of (32 TW) x (32 TW) wave tiles, SHV the shared transform -- `unit` = 4 d NS outputs per tile unit, OT
+// outputs per workgroup tile, gx time tiles of the longest utterance, gy row tiles, wgs workgroups in the grid, lds_bytes of dynamic
+// LDS; `inst` indexes conv_wino.hip's instance table.  C = 32 (no layer takes it: mode 2 of dissc_respair1d) is planned too.
+struct WinoPlan { int inst, NS, dil, CPR, RH, TW, SHV, unit, OT, gx, gy, wgs, lds_bytes; };
+int wino_plan(int C, int KS, int dil, int B, int Lmax, WinoPlan& p);
 
 // Toom-Cook F(6,3) form on 8-wave workgroups (conv_wino8.hip): the k = 7 / 11 ResBlock convs of the C >= 64 stages
 bool wino8_supported(int Cout, int Cin, int KS, int dil);

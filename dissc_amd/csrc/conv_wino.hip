@@ -61,6 +61,7 @@ struct WinoArgs {
 #ifndef DISSC_WINO_LB
 #define DISSC_WINO_LB 3
 #endif
+constexpr int WINO_LDS_LIMIT = 160 * 1024;  // dynamic LDS every instance is allowed (hipFuncSetAttribute) and wino_plan holds it to
 #ifndef DISSC_WINO_EPI2
 #define DISSC_WINO_EPI2 1  // epilogue: A^T per column through an output tile in LDS (0: per output quad straight from the Y tiles)
 #endif
@@ -89,28 +90,47 @@ constexpr int wino_row_len(int D, int NTU, int XRW) {
   return need;
 }
 
+// The tile geometry of an instance (NS sub-filters, dilation DIL, CPR channels per barrier round, RH row halves, (32 TW)^2 wave
+// tiles): what the kernel indexes by, what the launch asks LDS for and what wino_plan / dissc_wino_info report.
+template <int NS, int DIL, int CPR, int RH, int TW>
+struct WinoGeo {
+  static constexpr int NTH = 768;                    // 12 waves: 6 points x 2 row halves (3 waves on every SIMD)
+  static constexpr int D = DIL * NS;                 // sample step of the F(4,3) sequences
+  static constexpr int W = DIL * (2 * NS - 1);       // V entries per tile unit
+  static constexpr int CHV = 3 - RH;                 // column halves per workgroup (RH = 2 row halves -> 1, RH = 1 -> 2)
+  static constexpr int TC = 32 * TW;                 // columns per wave
+  static constexpr int NTU = TC / D;                 // tile units per wave
+  static constexpr int NCOL = NTU * D;               // transform-domain columns of a wave in use (<= TC)
+  static constexpr int UNIT = 4 * D;                 // outputs per tile unit
+  static constexpr int OT = UNIT * NTU * CHV;        // outputs per workgroup tile
+  static constexpr int RAW = OT + DIL * (3 * NS - 1);  // input window
+  static constexpr int XRW = (RAW + 3 + 3) / 4 * 4;  // staged positions per channel (alignment shift <= 3)
+  static constexpr int NV = XRW / 4;
+  static constexpr int RL = wino_row_len(D, NTU * CHV, XRW);
+  static constexpr int CHF = D * RL;                 // floats per channel of the polyphase window
+  static constexpr int VROW = NTU * W;               // V entries per channel (<= 112)
+  static constexpr int XV = 112;                     // V row stride (112 % 32 == 16: the two k halves of a fragment read hit different banks)
+  static constexpr int YS = TC + 4;                  // row stride of the epilogue exchange
+  // epilogue form: A^T per column through an output tile in LDS for the steps D that are neither 1 nor a multiple of 4
+  // (k = 7 and the dilated k = 3 instances, whose per-quad form needs per-element divisions by D); per output quad
+  // straight from the Y tiles otherwise (measured: the D % 4 == 0 instances are 1-4 % SLOWER through the output tile)
+  static constexpr bool EPI2 = DISSC_WINO_EPI2 && D != 1 && D % 4 != 0;
+  static constexpr int OSW = UNIT * NTU + 4;         // row stride of the output tile of a pass (one column half)
+  // dynamic LDS: the two windows and the V tiles ([12 waves][8][XV], or [2][6 points][8][XV] shared) of the main loop; the
+  // epilogue's exchange [6][32][YS] and output tile [32][OSW] reuse them
+  static constexpr int LOOP_FLOATS = 2 * CPR * CHF + 12 * 8 * XV;
+  static constexpr int EPI_FLOATS = 6 * 32 * YS + (EPI2 ? 32 * OSW : 0);
+  static constexpr int LDS_FLOATS = LOOP_FLOATS > EPI_FLOATS ? LOOP_FLOATS : EPI_FLOATS;
+  static_assert(VROW <= XV && NCOL <= TC && NTU >= 1, "tile geometry");
+};
+
 template <int NS, int DIL, int CPR, int RH, int TW, int SHV = 0>
 __global__ void __launch_bounds__(768, DISSC_WINO_LB) conv_wino_kernel(const WinoArgs a) {
   static_assert(SHV == 0 || RH == 2, "the shared transform is for the row-half form");
-  constexpr int NTH = 768;                    // 12 waves: 6 points x 2 row halves (3 waves on every SIMD)
-  constexpr int D = DIL * NS;                 // sample step of the F(4,3) sequences
-  constexpr int W = DIL * (2 * NS - 1);       // V entries per tile unit
-  constexpr int CHV = 3 - RH;                 // column halves per workgroup (RH = 2 row halves -> 1, RH = 1 -> 2)
-  constexpr int MI = TW, NI = TW;             // wave tile = (32 MI) rows x (32 NI) columns: 64 x 64, or 32 x 32 on small grids
-  constexpr int TC = 32 * NI;                 // columns per wave
-  constexpr int NTU = TC / D;                 // tile units per wave
-  constexpr int NCOL = NTU * D;               // transform-domain columns of a wave in use (<= TC)
-  constexpr int OT = 4 * D * NTU * CHV;       // outputs per workgroup tile
-  constexpr int RAW = OT + DIL * (3 * NS - 1);  // input window
-  constexpr int XRW = (RAW + 3 + 3) / 4 * 4;  // staged positions per channel (alignment shift <= 3)
-  constexpr int NV = XRW / 4;
-  constexpr int RL = wino_row_len(D, NTU * CHV, XRW);
-  constexpr int CHF = D * RL;                 // floats per channel of the polyphase window
-  constexpr int VROW = NTU * W;               // V entries per channel (<= 112)
-  constexpr int XV = 112;                     // V row stride (112 % 32 == 16: the two k halves of a fragment read hit different banks)
+  using G = WinoGeo<NS, DIL, CPR, RH, TW>;
+  constexpr int NTH = G::NTH, D = G::D, W = G::W, MI = TW, NI = TW;  // wave tile = (32 MI) rows x (32 NI) columns: 64 x 64, or 32 x 32 on small grids
+  constexpr int TC = G::TC, NTU = G::NTU, NCOL = G::NCOL, OT = G::OT, NV = G::NV, RL = G::RL, CHF = G::CHF, XV = G::XV, YS = G::YS;
   constexpr int SV = (CPR * NV + NTH - 1) / NTH;
-  constexpr int YS = TC + 4;                  // row stride of the epilogue exchange
-  static_assert(VROW <= XV && NCOL <= TC && NTU >= 1, "tile geometry");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // 2 x [CPR][D][RL]: window sample x (position o + x) of a channel at [(x + 4 D) % D][(x + 4 D) / D]
   float* vbuf = lds + 2 * CPR * CHF;  // V tiles: [12 waves][8][XV], or [2][6 points][8][XV] in the shared form
@@ -408,11 +428,8 @@ __global__ void __launch_bounds__(768, DISSC_WINO_LB) conv_wino_kernel(const Win
   // (16-byte residual / accumulator / output accesses) of one row: output u = 4 g + e of unit tau comes from column
   // (tau, u % D) with A^T row a = u / D
   float* yb = lds;  // [6][32][YS]
-  // epilogue form: A^T per column through an output tile in LDS for the steps D that are neither 1 nor a multiple of 4
-  // (k = 7 and the dilated k = 3 instances, whose per-quad form needs per-element divisions by D); per output quad
-  // straight from the Y tiles otherwise (measured: the D % 4 == 0 instances are 1-4 % SLOWER through the output tile)
-  constexpr bool EPI2 = DISSC_WINO_EPI2 && D != 1 && D % 4 != 0;
-  constexpr int OSW = 4 * D * NTU + 4;     // row stride of the output tile of a pass (one column half)
+  constexpr bool EPI2 = G::EPI2;           // (WinoGeo: through an output tile in LDS, or per output quad from the Y tiles)
+  constexpr int OSW = G::OSW;
   float* const ot = lds + 6 * 32 * YS;     // [32][OSW]
   if (a.dbg & 4) {
     if (acc[0][0][0] == 123.f) a.out[0] = 1.f;
@@ -580,65 +597,106 @@ int make_wino(const float* w, const float* bias, int C, int KS, int dil, DevConv
 double wino_executed_macs_per_t(int C, int KS) { return (double)C * C * 6.0 * ((KS + 2) / 3) / 4.0; }
 
 template <int NS, int DIL, int CPR, int RH, int TW, int SHV = 0>
-static int launch_wino_c(const WinoArgs& a, int B, int Lmax, hipStream_t stream) {
-  constexpr int CHV = 3 - RH;
-  constexpr int D = DIL * NS, NTU = 32 * TW / D, OT = 4 * D * NTU * CHV, RAW = OT + DIL * (3 * NS - 1), XRW = (RAW + 6) / 4 * 4;
-  constexpr int RL = wino_row_len(D, NTU * CHV, XRW);
-  size_t lds_f = (size_t)2 * CPR * D * RL + 12 * 8 * 112;
-  const size_t epi_f = (size_t)6 * 32 * (32 * TW + 4) + ((DISSC_WINO_EPI2 && D != 1 && D % 4 != 0) ? (size_t)32 * (4 * D * NTU + 4) : 0);
-  if (lds_f < epi_f) lds_f = epi_f;
+static int launch_wino_c(const WinoArgs& a, hipStream_t stream) {  // a.gx, a.gy, a.B: wino_plan's
+  using G = WinoGeo<NS, DIL, CPR, RH, TW>;
   static DeviceOnce attr_once;  // per device (common.h)
-  DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&conv_wino_kernel<NS, DIL, CPR, RH, TW, SHV>), 160 * 1024));
-  WinoArgs aa = a;
-  aa.gx = (Lmax + OT - 1) / OT;
-  aa.gy = a.C / (32 * TW * RH);
-  aa.B = B;
-  if (8 % aa.gy != 0) {
-    set_error("launch_wino: %d row tiles do not divide the 8 XCDs", aa.gy);
-    return DISSC_EINVAL;
-  }
-  const int per = 8 / aa.gy;
-  dim3 grid(8 * ((aa.gx * B + per - 1) / per));
-  hipLaunchKernelGGL((conv_wino_kernel<NS, DIL, CPR, RH, TW, SHV>), grid, dim3(768), lds_f * sizeof(float), stream, aa);
+  DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&conv_wino_kernel<NS, DIL, CPR, RH, TW, SHV>), WINO_LDS_LIMIT));
+  const int per = 8 / a.gy;
+  dim3 grid(8 * ((a.gx * a.B + per - 1) / per));
+  hipLaunchKernelGGL((conv_wino_kernel<NS, DIL, CPR, RH, TW, SHV>), grid, dim3(G::NTH), (size_t)G::LDS_FLOATS * sizeof(float), stream, a);
   DISSC_HIP_CHECK(hipGetLastError());
   return DISSC_OK;
+}
+
+// The instances the library carries: five per (NS, d) shape.  Geometry from the instance's own WinoGeo, the launch its own
+// launch_wino_c; wino_plan (and through it run_wino and dissc_wino_info) reads this table alone.
+//   (16, 1, 1, 0)  C = 64 on small grids (and the C = 32 diagnostic instance): 32 rows x 64 columns
+//   (16, 1, 2, 0)  C = 64: 64 rows x 128 columns
+//   (16, 2, 1, 0)  C >= 128 on small grids: 64 rows x 32 columns
+//   (.., 2, 2, 1)  C >= 128, "wino_sv" = 1 (default): 128 rows x 64 columns, shared transform; 32 channels per barrier round for
+//                  k = 3 (with 32 the k = 7 / 11 instances spill a few registers: 16 there)
+//   (.., 2, 2, 0)  C >= 128, "wino_sv" = 0: each wave its own V tile; 32 channels per round (k = 11, d = 5 with 32 needs more
+//                  registers than three waves per SIMD leave: 16 there)
+// Every supported C has an even number of 16-channel chunks, so the 16-channel fallbacks of the 32-channel rounds ((16, 2, 2, 1) at
+// k = 3, (16, 2, 2, 0) elsewhere) and the 32-channel forms of the exceptions could never be launched: they are not built.
+struct WinoInst {
+  int NS, dil, CPR, RH, TW, SHV;
+  int unit, OT, lds_bytes;  // WinoGeo's UNIT, OT, LDS_FLOATS
+  int (*launch)(const WinoArgs&, hipStream_t);
+};
+#define DISSC_W_INST(NS_, D_, CPR_, RH_, TW_, SHV_)                                                        \
+  {NS_, D_, CPR_, RH_, TW_, SHV_, WinoGeo<NS_, D_, CPR_, RH_, TW_>::UNIT, WinoGeo<NS_, D_, CPR_, RH_, TW_>::OT, \
+   WinoGeo<NS_, D_, CPR_, RH_, TW_>::LDS_FLOATS * (int)sizeof(float), &launch_wino_c<NS_, D_, CPR_, RH_, TW_, SHV_>}
+#define DISSC_W_SHAPE(NS_, D_)                                                                             \
+  DISSC_W_INST(NS_, D_, 16, 1, 1, 0), DISSC_W_INST(NS_, D_, 16, 1, 2, 0), DISSC_W_INST(NS_, D_, 16, 2, 1, 0), \
+  DISSC_W_INST(NS_, D_, (NS_ == 1 ? 32 : 16), 2, 2, 1), DISSC_W_INST(NS_, D_, ((NS_ == 4 && D_ == 5) ? 16 : 32), 2, 2, 0)
+static const WinoInst kWinoInst[] = {DISSC_W_SHAPE(1, 1), DISSC_W_SHAPE(1, 3), DISSC_W_SHAPE(1, 5),
+                                     DISSC_W_SHAPE(3, 1), DISSC_W_SHAPE(3, 3), DISSC_W_SHAPE(3, 5),
+                                     DISSC_W_SHAPE(4, 1), DISSC_W_SHAPE(4, 3), DISSC_W_SHAPE(4, 5)};
+#undef DISSC_W_SHAPE
+#undef DISSC_W_INST
+
+static int wino_find(int ns, int dil, int RH, int TW, int SHV) {
+  for (int i = 0; i < (int)(sizeof(kWinoInst) / sizeof(kWinoInst[0])); ++i) {
+    const WinoInst& t = kWinoInst[i];
+    if (t.NS == ns && t.dil == dil && t.RH == RH && t.TW == TW && t.SHV == SHV) return i;
+  }
+  return -1;
 }
 
 // launches with fewer 64 x 64-tile workgroups than this use 32 x 32 wave tiles
 constexpr int WINO_SMALL_GRID = 96;
 
-// option "wino_sv" (default 1): shared transform in the row-half form (C >= 128)
-template <int NS, int DIL>
-static int launch_wino_t(const WinoArgs& a, int B, int Lmax, hipStream_t stream) {
-  // Small grids (a short or single utterance: the reference's one-at-a-time mode) step down to 32 x 32 wave tiles: four
-  // times the workgroups.  Every output element sees the same MFMA sequence and the same transforms for either tile,
-  // so the result is bit-identical and an utterance's samples stay independent of the batch it runs in.
-  constexpr int D = DIL * NS;
-  const bool c64 = a.C % 128 != 0;
-  const int ot = 4 * D * (64 / D) * (c64 ? 2 : 1);
-  const long long nwg = (long long)((Lmax + ot - 1) / ot) * (c64 ? a.C / 64 : a.C / 128) * B;
-  const bool small = opts().small_grid && nwg < WINO_SMALL_GRID;
-  if (a.C == 32) return launch_wino_c<NS, DIL, 16, 1, 1>(a, B, Lmax, stream);  // diagnostics only (dissc_respair1d mode 2)
-  if (c64) {
-    if (small) return launch_wino_c<NS, DIL, 16, 1, 1>(a, B, Lmax, stream);  // 32 rows x 64 columns
-    return launch_wino_c<NS, DIL, 16, 1, 2>(a, B, Lmax, stream);            // 64 rows x 128 columns
+// The instance and grid of a launch, from (C, k, d, B, Lmax) and the options "small_grid" / "wino_sv" (default 1: shared
+// transform in the row-half form, C >= 128): host only, the one place that chooses (run_wino launches what this returns;
+// dissc_wino_info reports it).
+// Small grids (a short or single utterance: the reference's one-at-a-time mode) step down to 32 x 32 wave tiles: four times the
+// workgroups.  Every output element sees the same MFMA sequence and the same transforms for either tile, so the result is
+// bit-identical and an utterance's samples stay independent of the batch it runs in (tests/test_gpu_wino_tiles.py holds every
+// instance of a shape to the same bits).
+// C = 32 has no layer: the one instance mode 2 of dissc_respair1d runs as a diagnostic.
+int wino_plan(int C, int KS, int dil, int B, int Lmax, WinoPlan& p) {
+  const bool shape_ok = (KS == 3 || KS == 7 || KS == 11) && (dil == 1 || dil == 3 || dil == 5);
+  if (B <= 0 || Lmax <= 0 || !(wino_supported(C, C, KS, dil) || (C == 32 && shape_ok))) {
+    set_error("wino_plan: no instance (B %d, Lmax %d, C %d, k %d, d %d)", B, Lmax, C, KS, dil);
+    return DISSC_EINVAL;
   }
-  if (small) return launch_wino_c<NS, DIL, 16, 2, 1>(a, B, Lmax, stream);    // 64 rows x 32 columns
-  // 32 channels per barrier round where the chunks pair up (k = 11, d = 5 with 32 channels per round needs more registers
-  // than three waves per SIMD leave: 16 there)
-  const bool r32 = a.nchunk % 2 == 0 && !(NS == 4 && DIL == 5);
-  if (opts().wino_sv) {
-    // (with 32 channels per round the k = 7 / 11 instances spill a few registers; k = 3 has room)
-    if (NS == 1 && r32) return launch_wino_c<NS, DIL, 32, 2, 2, 1>(a, B, Lmax, stream);
-    return launch_wino_c<NS, DIL, 16, 2, 2, 1>(a, B, Lmax, stream);
+  const int ns = (KS + 2) / 3;
+  const bool c64 = C % 128 != 0;
+  int RH = c64 ? 1 : 2, TW = 2, SHV = (!c64 && opts().wino_sv) ? 1 : 0;
+  const int big = wino_find(ns, dil, RH, TW, SHV);  // the 64 x 64 wave tiles of the class
+  const long long nwg = big < 0 ? 0 : (long long)((Lmax + kWinoInst[big].OT - 1) / kWinoInst[big].OT) * (c64 ? C / 64 : C / 128) * B;
+  if (C == 32 || (opts().small_grid && nwg < WINO_SMALL_GRID)) { TW = 1; SHV = 0; }
+  const int i = wino_find(ns, dil, RH, TW, SHV);
+  if (i < 0) {
+    set_error("wino_plan: no instance of k = %d, dilation %d with %d row halves on %d x %d wave tiles", KS, dil, RH, 32 * TW, 32 * TW);
+    return DISSC_EINVAL;
   }
-  if (r32) return launch_wino_c<NS, DIL, 32, 2, 2>(a, B, Lmax, stream);
-  return launch_wino_c<NS, DIL, 16, 2, 2>(a, B, Lmax, stream);
+  const WinoInst& t = kWinoInst[i];
+  p.inst = i;
+  p.NS = ns; p.dil = dil; p.CPR = t.CPR; p.RH = RH; p.TW = TW; p.SHV = SHV;
+  p.unit = t.unit; p.OT = t.OT; p.lds_bytes = t.lds_bytes;
+  p.gx = (Lmax + t.OT - 1) / t.OT;
+  p.gy = C / (32 * TW * RH);
+  if ((C / KC) % (t.CPR / KC) != 0) {  // (no silent fallback to a 16-channel round: no supported C needs one)
+    set_error("wino_plan: %d channels are not a whole number of the %d-channel rounds of the instance", C, t.CPR);
+    return DISSC_EINVAL;
+  }
+  if (p.gy < 1 || 8 % p.gy != 0) {
+    set_error("wino_plan: %d row tiles do not divide the 8 XCDs", p.gy);
+    return DISSC_EINVAL;
+  }
+  if (t.lds_bytes > WINO_LDS_LIMIT) {
+    set_error("wino_plan: the instance needs %d bytes of LDS", t.lds_bytes);
+    return DISSC_EINVAL;
+  }
+  const int per = 8 / p.gy;
+  p.wgs = 8 * ((p.gx * B + per - 1) / per);
+  return DISSC_OK;
 }
 
 int run_wino(const DevConv& dc, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ldx, int ldo, float slope,
              hipStream_t stream) {
-  const int B = bt.B, Lmax = bt.Lmax;
   WinoArgs a;
   a.x = x; a.wpack = dc.wpack; a.bias = dc.bias; a.res = ep.res; a.out = out; a.acc = ep.acc;
   a.lengths = bt.lengths; a.len_default = bt.len_default; a.len_mul = bt.len_mul;
@@ -646,23 +704,17 @@ int run_wino(const DevConv& dc, const float* x, float* out, const Batch& bt, con
   a.ldx = ldx; a.ldo = ldo;
   a.x_bstride = (long long)dc.M * ldx; a.o_bstride = (long long)dc.M * ldo;
   a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi; a.dbg = opts().kernel_dbg;
+  a.gx = a.gy = a.B = 0;
   // the window staging, the residual / accumulator reads and the stores are 16-byte accesses
   if (ldx < 4 || ldx % 4 || ldo % 4 || misaligned16(x) || misaligned16(out) || misaligned16(ep.res) || misaligned16(ep.acc)) {
     set_error("run_wino: rows must be 16-byte aligned (ldx %d, ldo %d: multiples of 4 floats, ldx >= 4)", ldx, ldo);
     return DISSC_EINVAL;
   }
-  if (B <= 0 || Lmax <= 0) {
-    set_error("run_wino: empty batch (B %d, Lmax %d)", B, Lmax);
-    return DISSC_EINVAL;
-  }
-  const int ns = (dc.KS + 2) / 3;
-#define DISSC_WINO_CASE(NS_, D_) if (ns == NS_ && dc.dil == D_) return launch_wino_t<NS_, D_>(a, B, Lmax, stream);
-  DISSC_WINO_CASE(1, 1) DISSC_WINO_CASE(1, 3) DISSC_WINO_CASE(1, 5)
-  DISSC_WINO_CASE(3, 1) DISSC_WINO_CASE(3, 3) DISSC_WINO_CASE(3, 5)
-  DISSC_WINO_CASE(4, 1) DISSC_WINO_CASE(4, 3) DISSC_WINO_CASE(4, 5)
-#undef DISSC_WINO_CASE
-  set_error("run_wino: k = %d, dilation %d unsupported", dc.KS, dc.dil);
-  return DISSC_EINVAL;
+  WinoPlan p;
+  const int rc = wino_plan(dc.M, dc.KS, dc.dil, bt.B, bt.Lmax, p);
+  if (rc) return rc;
+  a.gx = p.gx; a.gy = p.gy; a.B = bt.B;
+  return kWinoInst[p.inst].launch(a, stream);
 }
 
 }  // namespace dissc

@@ -332,6 +332,20 @@ int dissc_wino8_info(int C, int k, int dilation, int R, int B, int Lmax, DisscWi
   return DISSC_OK;
 }
 
+// Diagnostics: the conv_wino_kernel instance and grid a C -> C conv of (k, dilation) launches in its six-point F(4,3) form on a batch of
+// B utterances of at most Lmax columns, under the current option defaults: wino_plan, which run_wino launches from.  Host only: no
+// HIP call.
+int dissc_wino_info(int C, int k, int dilation, int B, int Lmax, DisscWinoPlan* out) {
+  WinoPlan p;
+  const int rc = wino_plan(C, k, dilation, B, Lmax, p);
+  if (rc) return rc;
+  if (out) {
+    out->ns = p.NS; out->dilation = p.dil; out->cpr = p.CPR; out->rh = p.RH; out->tw = p.TW; out->shv = p.SHV;
+    out->unit = p.unit; out->ot = p.OT; out->gx = p.gx; out->gy = p.gy; out->wgs = p.wgs; out->lds_bytes = p.lds_bytes;
+  }
+  return DISSC_OK;
+}
+
 // Diagnostics: average ms of `iters` launches of one residual pair (modes as dissc_respair1d) on synthetic data.
 int dissc_pair_bench(int B, int C, int k, int dilation, int L, int epi, int iters, int mode, float* ms_out) {
   if (!ms_out || B <= 0 || L <= 0 || iters <= 0 || epi < EPI_RES || epi > EPI_MRF_DIV) {

@@ -26,7 +26,7 @@ using namespace dissc;
 extern "C" {
 
 const char* dissc_last_error(void) { return g_err; }
-int dissc_abi_version(void) { return 8; }
+int dissc_abi_version(void) { return 9; }
 
 int dissc_device_count(void) {
   int n = 0;

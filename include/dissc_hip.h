@@ -49,7 +49,8 @@ typedef struct {
 const char* dissc_last_error(void);
 /* ABI version of this header: bumped when a signature changes or a section is added (5: dissc_convgrad_*;
  * 6: dissc_conv_info, and dissc_get_option reads the tile-shape keys; 7: dissc_wino8_info; 8: the split-bf16 diagnostics
- * dissc_conv1d_prec, dissc_conv_transpose1d_prec, dissc_resblock1d_bf3, dissc_bf3_info and mode 5 of dissc_respair1d). */
+ * dissc_conv1d_prec, dissc_conv_transpose1d_prec, dissc_resblock1d_bf3, dissc_bf3_info and mode 5 of dissc_respair1d;
+ * 9: dissc_wino_info). */
 int dissc_abi_version(void);
 /* Number of HIP devices visible / name of device `dev` (for diagnostics). */
 int dissc_device_count(void);
@@ -309,6 +310,23 @@ typedef struct {
   int32_t unit, ot, cpr, gx, gy;
 } DisscWino8Plan;
 int dissc_wino8_info(int C, int k, int dilation, int R, int B, int Lmax, DisscWino8Plan* out);
+
+/* The conv_wino_kernel instance and grid that a C -> C conv of k taps and `dilation` launches in its six-point Toom-Cook form
+ * F(4,3) (what dissc_conv1d runs under "wino" = 2 with "wino8" below 2, both launches of mode 2 of dissc_respair1d, and the
+ * generator's ConvForm::f43 layers) on a batch of B utterances of at most Lmax columns, under the current option defaults
+ * ("small_grid", "wino_sv"): ns = ceil(k / 3) sub-filters, `cpr` input channels staged per barrier round, `rh` row halves (and
+ * 3 - rh column halves) of wave tiles of (32 tw) rows x (32 tw) columns, `shv` 1 = the transform shared between the waves;
+ * `unit` = 4 dilation ns outputs per tile unit, `ot` = unit * floor(32 tw / (dilation ns)) * (3 - rh) outputs per workgroup tile,
+ * gx = ceil(Lmax / ot) time tiles of the longest utterance, gy = C / (32 tw rh) row tiles (a divisor of 8), `wgs` workgroups in
+ * the grid, `lds_bytes` of dynamic LDS (at most 160 KB).  The answer is the launch path's own plan, the widths those of the
+ * instance itself.  C = 64 / 128 / 256 / 512, k = 3 / 7 / 11, dilation 1 / 3 / 5; C = 32 is answered too: no layer takes it, it is
+ * the diagnostic instance mode 2 of dissc_respair1d runs.  DISSC_EINVAL for any other shape, B < 1 or Lmax < 1.  Host only: no GPU
+ * is touched. */
+typedef struct {
+  int32_t ns, dilation, cpr, rh, tw, shv;
+  int32_t unit, ot, gx, gy, wgs, lds_bytes;
+} DisscWinoPlan;
+int dissc_wino_info(int C, int k, int dilation, int B, int Lmax, DisscWinoPlan* out);
 
 /* Diagnostics / tests: residual pairs [m0, m1) of ONE ResBlock1 (three pairs x_k += conv_1(lrelu(conv_d(lrelu(x_k)))), d =
  * dil3[0..2]) in split-bf16 arithmetic on resblock_bf3_kernel (csrc/resblock_bf3.hip), as the generator launches it under

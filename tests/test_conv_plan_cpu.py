@@ -93,7 +93,7 @@ def test_shipped_tables_and_families(lib):
         assert lib.get_option(f"conv32_cfg_bm{cls}") == cfg
     for cls, cfg in DEFAULT16.items():
         assert lib.get_option(f"conv_cfg_bm{cls}") == cfg
-    assert lib.lib.dissc_abi_version() == 8
+    assert lib.lib.dissc_abi_version() == 9
     assert one(lib, 16, 16, 11, 5, 32, 4000)["family"] == 16 and one(lib, 16, 1, 7, 1, 32, 4000)["cfg"] == 6
     assert one(lib, 32, 32, 3, 1, 32, 4000)["family"] == 32
     with options(lib, mfma32=0):

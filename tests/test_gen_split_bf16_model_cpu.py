@@ -131,7 +131,7 @@ def lib():
 def test_bf3_info_reports_the_launch_plans(lib):
     """the tile of conv_bf3_kernel by row class and the small-grid step-down (fewer than 256 x "small_grid" workgroups of the class
     tile), the windows of resblock_bf3_kernel (halo sum P2 (d + 1) over the pairs, rounded up to 4), and what has no instance"""
-    assert lib.lib.dissc_abi_version() == 8
+    assert lib.lib.dissc_abi_version() == 9
     before = lib.get_option("small_grid")
     try:
         lib.set_option("small_grid", 0)

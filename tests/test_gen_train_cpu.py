@@ -89,7 +89,7 @@ def test_embed_and_rowwise_entries_refuse_bad_arguments_on_the_host(nn):
 
 def test_wnorm_layout_and_abi(nn):
     from dissc_amd import lib
-    assert lib.dissc_abi_version() == 8
+    assert lib.dissc_abi_version() == 9
     assert nn.WNORM_WAVE_COLS == lib.dissc_wnorm_wave_cols() and nn.WNORM_WAVE_COLS >= 4
     for shapes in ([(1, 112), (16, 48), (512, 1799), (3, 1)], [(3, 1), (1, 112), (2, 3), (7, 1799)]):
         wn = nn.WeightNorm(shapes)

@@ -121,7 +121,7 @@ def test_abi_and_unit_grid_of_every_tile(lib):
     """Every OT is a whole number of units (every tile starts on the global unit grid, which is what makes the tiles of a shape
     agree bit for bit) and every F(6,3) OT a whole number of output quads (its epilogue stores aligned quads only); F(5,4) has
     tiles that are not (the shared-quad path)."""
-    assert lib.lib.dissc_abi_version() == 8
+    assert lib.lib.dissc_abi_version() == 9
     odd = 0
     for R, k, d, (MI, NI, WPS) in itertools.product(RS, (7, 11), DS, TILES):
         unit, ot, cpr = geometry(R, k, d, NI, WPS)
