@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 import mel_ref
+from mel_cases import FACTOR, ref_kwargs
 
 
 def mel_t(y, n_fft=1024, num_mels=80, sr=16000, hop=256, win=1024, fmin=0.0, fmax=None, log=True):
@@ -56,12 +57,32 @@ def model_vjp(w, cot, P, log):
     return y.grad.double().numpy()
 
 
+def noisy_of(waves):
+    rs = np.random.RandomState(7)
+    return [np.clip(w + 0.01 * rs.standard_normal(len(w)), -1, 1).astype(np.float32) for w in waves]
+
+
+class GradRef:
+    """float64 gradients of a set of signals for fixed cotangents, the float32 path's error on them, the bar"""
+
+    def __init__(self, waves, P, log, cots=None, seed=11):
+        kw, rs = ref_kwargs(P), np.random.RandomState(seed)
+        self.waves, self.P, self.log = waves, P, log
+        self.cots = cots or [rs.standard_normal((P["num_mels"], len(w) // P["hop_size"])).astype(np.float32) for w in waves]
+        self.g64 = [vjp(w, c, kw, torch.float64, log) for w, c in zip(waves, self.cots)]
+        g32 = [vjp(w, c, kw, torch.float32, log) for w, c in zip(waves, self.cots)]
+        self.e32 = max(self.err(i, g) for i, g in enumerate(g32))
+        self.bar = FACTOR * self.e32
+
+    def err(self, i, g):
+        return float(np.abs(np.asarray(g, np.float64) - self.g64[i]).max() / np.abs(self.g64[i]).max())
+
+
 if __name__ == "__main__":
     import os
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import test_gpu_mel as fwd
-    from test_gpu_mel_grad import GradRef, noisy_of
+    import mel_cases as fwd
     for name, P, kinds in (("shipped", fwd.SHIPPED, fwd.KINDS), ("narrow", fwd.NARROW, ("iid", "speech_like")),
                            ("hop250", fwd.ODD_HOP, ("speech_like",))):
         for kind in kinds:

@@ -1,15 +1,18 @@
 """What every test of the one-launch residual pairs y = x + conv_1(lrelu(conv_d(lrelu(x)))) (dissc_respair1d; reference
 sr/models.py:34-41) shares: the shipped option values and a context manager that restores them, data / float64 reference / launch,
-forms tied by dissc_pair_info to the kernel mode 3 builds, tile-edge lengths from that instance's own tile, the one check body, the
-one trained-like per-layer loop, and the trained-like context (float64 oracle taps) built once per process.
+forms tied by dissc_pair_info to the kernel mode 3 builds (and the pins of that entry), tile-edge lengths from that instance's own
+tile, the one check body, the one trained-like per-layer loop, and the trained-like context (float64 oracle taps) built once per
+process.
 `lib` is the dissc_amd._lib module throughout."""
-import contextlib
 import ctypes
 import functools
 from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
+
+import tile_harness
+import trained_like_cases as ttl
 
 DEV = "cuda:0"
 # the values the library ships with.  pair_f23: bit 0 C = 32, bit 1 C = 16 (4 / 8: their k = 3 pairs); pair_tc6: 1 C = 32 k = 7,
@@ -28,16 +31,10 @@ def shipped(lib):
     return {k: v for k, v in SHIPPED.items() if k != "pairw_chv" or experimental(lib)}
 
 
-@contextlib.contextmanager
 def options(lib, **kv):
-    """sets the given options; restores the SHIPPED values (not the previous ones) on exit"""
-    try:
-        for key, v in kv.items():
-            assert lib.lib.dissc_set_option(key.encode(), v) == 0, key
-        yield
-    finally:
-        for key, v in shipped(lib).items():
-            lib.lib.dissc_set_option(key.encode(), v)
+    """sets the given options; restores the SHIPPED values (not the previous ones, and nothing else) on exit.  Setting and
+    restoring both go through lib.set_option: a key the library refuses raises DisscError, on exit too"""
+    return tile_harness.options(lib, restore=shipped(lib), **kv)
 
 
 PairInfo = namedtuple("PairInfo", "form tile")
@@ -51,13 +48,43 @@ def pair_info(lib, C, k, d):
     return PairInfo(form.value, tile.value)
 
 
+# ---- the pins of dissc_pair_info (tests/test_pair_info.py holds the entry to them, tests/test_pair_info_c64_tc6.py holds them
+# untouched by "pair_tc6_c64") ----
+DILS = (1, 3, 5)
+# (C, k, options, form, tile at d = 1 / 3 / 5)
+PINS = [
+    (16, 11, {}, F23, (500, 492, 468)),
+    (32, 11, {}, TC6, (360, 360, 348)),
+    (32, 11, {"pair_tc6": 0}, F23, (500, 492, 468)),
+    (32, 11, {"pair_tc6": 1}, F23, (500, 492, 468)),  # (bit 0 is k = 7's)
+    (32, 7, {}, TC6, (376, 372, 352)),
+    (32, 7, {"pair_tc6": 1}, TC6, (376, 372, 352)),
+    (64, 3, {}, F23, (252, 248, 248)),
+]
+# DISSC_EXPERIMENTAL=1 builds: the k = 3 instances of the C = 32 / 16 F(2,3) kernels (bits 4 / 8 of "pair_f23"), and the F(4,3)
+# pair kernel (no constant outside its kernel file names its tile: 0) wherever the options leave no register-only form
+PINS_EXPERIMENTAL = [
+    (32, 3, {"pair_f23": 15}, F23, (508, 508, 508)),
+    (16, 3, {"pair_f23": 15}, F23, (508, 508, 508)),
+    (32, 7, {"pair_f23": 0}, F43, (0, 0, 0)),
+    (32, 11, {"pair_f23": 0}, F43, (0, 0, 0)),
+    (64, 3, {"pair_f23": 0}, F43, (0, 0, 0)),
+    (64, 3, {"pair_f23_c64": 0}, F43, (0, 0, 0)),
+]
+# no instance in a default build
+NONE_DEFAULT = [(32, 7, {"pair_f23": 0}), (32, 11, {"pair_f23": 0}), (64, 3, {"pair_f23": 0}), (64, 3, {"pair_f23_c64": 0}),
+                (32, 7, {"pair_f23": 2, "pair_tc6": 15}), (32, 3, {"pair_f23": 15}), (16, 3, {"pair_f23": 15})]
+# no instance in either build
+NONE_ANYWHERE = [(16, 11, {"pair_f23": 1}), (16, 7, {"pair_tc6": 15}), (32, 3, {}), (16, 3, {}), (128, 3, {}), (256, 11, {}), (32, 5, {})]
+
+
 class Form(namedtuple("Form", "name mode options expect_form", defaults=({}, None))):
     """one way through dissc_respair1d: its mode, the options it runs under and, for mode 3, the form that must come of them"""
 
 
 DIRECT_PAIR = Form("direct pair", 1)           # the fused direct pair (respair.hip)
 DIRECT_LAUNCHES = Form("direct launches", 0)   # two direct conv launches
-TL_DIRECT, TL_FUSED = Form("direct", 0), Form("fused", 1)  # the same two under the names of test_gpu_trained_like._check
+TL_DIRECT, TL_FUSED = Form("direct", 0), Form("fused", 1)  # the same two under the names of trained_like_cases._check
 
 
 def form_tile(lib, form, C, k, d):
@@ -182,7 +209,7 @@ def assert_no_instance(lib, C, k, opts):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# trained-like data (tests/test_gpu_trained_like.py: its rows, metrics and bars)
+# trained-like data (tests/trained_like_cases.py: the rows, metrics and bars of tests/test_gpu_trained_like.py)
 # ------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def tl_context():
@@ -222,8 +249,7 @@ def trained_like_pair_layer(tl, C, k, d, p, m, forms, plan_form, unit_widths, se
     """pair m (dilation d) of ResBlock p through every form, on its float64-oracle input (a) and on (b): the adversarial rows
     (bursts after silence at every offset modulo unit_widths, spikes, ragged lengths) and windows of the tap of the
     (first column, length) in extra_rows; at m == 2 also the MRF epilogues (2: store, 3: accumulate, 4: accumulate / 3) of the
-    chain's last pair.  Returns the broken bars of test_gpu_trained_like._check: TD_RMS for plan_form, TD_CH and LEAK for all."""
-    import test_gpu_trained_like as ttl  # (it imports this module)
+    chain's last pair.  Returns the broken bars of trained_like_cases._check: TD_RMS for plan_form, TD_CH and LEAK for all."""
     lib, folded = tl["_lib"], tl["folded"]
     w1, b1 = folded[f"{p}.convs1.{m}.weight"], folded[f"{p}.convs1.{m}.bias"]
     w2, b2 = folded[f"{p}.convs2.{m}.weight"], folded[f"{p}.convs2.{m}.bias"]

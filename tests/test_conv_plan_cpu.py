@@ -2,81 +2,14 @@
 conv_mfma_kernel's eleven), held to a Python statement of the documented rules -- the small-grid step-down, the clamps of the
 conv32_cfg_bm* / conv_cfg_bm* overrides, the phase grouping of ConvTranspose1d -- and the read-back of those options.  The GPU
 tests (tests/test_gpu_direct_conv_tiles.py) take their tile ids and tile-edge lengths from this entry."""
-import contextlib
 import itertools
 
 import pytest
 
 import conv_grad_ref as R
-
-# conv_mfma32.hip kCfgs32 / conv_mfma.hip kCfgs: id -> (BM, BN)
-TILES32 = {0: (256, 64), 1: (128, 128), 2: (64, 128), 3: (32, 256), 4: (32, 512), 5: (64, 256), 6: (256, 128), 7: (128, 256),
-           10: (64, 64), 11: (32, 128)}
-TILES16 = {0: (256, 64), 1: (128, 128), 2: (64, 256), 3: (32, 512), 4: (16, 512), 5: (32, 256), 6: (16, 256), 7: (64, 128),
-           8: (128, 64), 9: (256, 64), 10: (48, 256)}
-CLASSES32, CLASSES16 = (32, 64, 128, 256), (16, 32, 64, 128, 256)
-DEFAULT32 = {32: 3, 64: 2, 128: 1, 256: 0}
-DEFAULT16 = {16: 6, 32: 5, 64: 7, 128: 1, 256: 0}
-FALLBACK16 = {16: 4, 32: 3, 64: 2, 128: 1, 256: 0}  # what conv_cfg puts in place of an override whose BM exceeds the class
-STEPS = {32: (3, 11), 64: (2, 10), 128: (1, 2, 10), 256: (0, 2, 10)}  # conv32_pick_cfg: by class, largest tile first
-
-
-def cls32(M):
-    return 256 if M >= 256 else 128 if M >= 128 else 64 if M >= 64 else 32
-
-
-def cls16(M):
-    return 256 if M >= 256 else 128 if M >= 128 else 64 if M >= 64 else 32 if M >= 32 else 16
-
-
-def rule_pick(M, B, L, small_grid=1):
-    """the documented rule: the class's table entry, then the first tile of the class's step list that gives at least
-    256 * small_grid workgroups, otherwise the last one"""
-    steps = STEPS[cls32(M)]
-    if not small_grid:
-        return steps[0]
-    for cfg in steps:
-        bm, bn = TILES32[cfg]
-        if -(-L // bn) * -(-M // bm) * B >= 256 * small_grid:
-            return cfg
-    return steps[-1]
-
-
-def rule_override32(cls, cfg):
-    """conv32_set_cfg / conv32_cfg: ids 0..7 are taken, a tile taller than the class or id 4 outside class 32 is replaced by the
-    class default; anything else leaves the table as it was"""
-    if not 0 <= cfg < 8:
-        return DEFAULT32[cls]
-    if TILES32[cfg][0] > cls or (cfg == 4 and cls != 32):
-        return DEFAULT32[cls]
-    return cfg
-
-
-def rule_override16(cls, cfg):
-    if not 0 <= cfg < 10:  # (10, 48 x 256, belongs to the 48-row layers alone)
-        return DEFAULT16[cls]
-    return FALLBACK16[cls] if TILES16[cfg][0] > cls else cfg
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from dissc_amd import _lib
-    return _lib
-
-
-@contextlib.contextmanager
-def options(lib, **kv):
-    """sets options; restores the values read before (dissc_get_option)"""
-    before = {k: lib.get_option(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            lib.set_option(k, v)
-        yield
-    finally:
-        for k, v in before.items():
-            lib.set_option(k, v)
+from plan_rules import (CLASSES16, CLASSES32, DEFAULT16, DEFAULT32, STEPS, TILES16, TILES32, cls16, cls32, rule_override16,
+                        rule_override32, rule_pick)
+from tile_harness import lib, options  # noqa: F401  (lib: the module fixture)
 
 
 def one(lib, cin, cout, k, d, B, L):

@@ -9,8 +9,8 @@ from fractions import Fraction as Fr
 import numpy as np
 import pytest
 
-from test_tc6_model import _conv_direct, _fma32, _rms_errors
-from test_tc6_model import trained_like  # noqa: F401  (its fixture: the trained-like checkpoint and the oracle's conv inputs)
+from tc6_model import _conv_direct, _fma32, _rms_errors
+from tc6_model import trained_like  # noqa: F401  (its fixture: the trained-like checkpoint and the oracle's conv inputs)
 
 BT = [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]]
 AT = [[1, 1, 1, 0], [0, 1, -1, -1]]

@@ -4,7 +4,6 @@ beyond an utterance, and sit inside the float64 bars of tests/train_stage_cases.
 ConvTranspose epilogues (paired float2 stores and the scalar path), and the residual / MRF epilogues of two direct launches.
 Which shape runs is never assumed: dissc_conv_info (tests/test_conv_plan_cpu.py) is asked after every option change, and the set
 of ids that ran is asserted.  Measured ratios, ids and wall time: profiles/direct_conv_tiles.md."""
-import contextlib
 import ctypes
 import functools
 
@@ -15,11 +14,11 @@ import torch.nn.functional as F
 
 import conv_grad_ref as R
 import pair_harness as ph
+from plan_rules import cls16, cls32
+from tile_harness import (DEV, PAIRED, SENTINEL, SLOPE, UPS, beyond_mask, check_edges, check_pair_epilogues, edge_lengths, held, lib,  # noqa: F401
+                          make_x, options, pair_epilogues_every_setting, paired_store, run_conv, walk_case)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SENTINEL = -7.0
-SLOPE = 0.1
 
 # (Cin, Cout, k, dilation, input slope) by row class of the 32-row kernel
 SHAPES = [(20, 40, 7, 3, SLOPE),      # class 32: Cin no multiple of 16, M pads to 64
@@ -39,31 +38,7 @@ K_WHOLE, K_CH = R.K_WHOLE, R.K_CH
 
 
 def cls_of(M, family=32):
-    for c in (256, 128, 64, 32):
-        if M >= c:
-            return c
-    return 32 if family == 32 else 16
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from dissc_amd import _lib
-    return _lib
-
-
-@contextlib.contextmanager
-def options(lib, **kv):
-    """sets options for the stand-alone entries; restores the values read at the start"""
-    before = {k: lib.get_option(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            lib.set_option(k, v)
-        yield
-    finally:
-        for k, v in before.items():
-            lib.set_option(k, v)
+    return cls32(M) if family == 32 else cls16(M)
 
 
 def tile_settings(lib, key_fmt, classes, info, extra=None):
@@ -81,24 +56,9 @@ def tile_settings(lib, key_fmt, classes, info, extra=None):
     return out
 
 
-def edge_lengths(widths, pad):
-    ws = sorted(set(widths))
-    return sorted({0, 1, 2, pad, pad + 1} | {w + e for w in ws for e in (-1, 0, 1)}) + [2 * ws[-1] + 1]
-
-
-def make_x(rs, B, cin, ld, lengths):
-    x = torch.from_numpy(rs.randn(B, cin, ld).astype(np.float32))
-    x[torch.from_numpy(rs.rand(B, cin, ld) < 0.02)] = 0.0
-    for i, n in enumerate(lengths):
-        x[i, :, n:] = float("nan")  # never read
-    return x
-
-
-def beyond_mask(lengths, ld, mul=1):
-    m = torch.zeros(len(lengths), 1, ld, dtype=torch.bool)
-    for i, n in enumerate(lengths):
-        m[i, :, n * mul:] = True
-    return m
+def tile_edge_lengths(widths, pad):
+    """beside the first edge of every width, and one length past the second edge of the widest"""
+    return edge_lengths(widths, pad, multiples=(1,), extra=[2 * max(widths) + 1])
 
 
 @functools.lru_cache(maxsize=None)
@@ -112,7 +72,7 @@ def conv_case(lib, shape):
     for fam, key, extra in families:
         for _, forms in tile_settings(lib, key, [cls_of(cout, fam)], lambda: lib.conv_info(cin, cout, k, d, 1, 20, 1025), extra):
             widths |= {bn for _, _, bn in forms}
-    lengths = edge_lengths(widths, pad)
+    lengths = tile_edge_lengths(widths, pad)
     B, ld = len(lengths), (max(lengths) + 3) // 4 * 4
     rs = np.random.RandomState(1000 * cin + 10 * k + d)
     x = make_x(rs, B, cin, ld, lengths)
@@ -127,32 +87,6 @@ def conv_case(lib, shape):
         refs[dt] = r
     return dict(x=x.to(DEV), w=w, b=b, lengths=lengths, ld=ld, r64=refs[torch.float64], r32=refs[torch.float32],
                 beyond=beyond_mask(lengths, ld).to(DEV))
-
-
-def run_conv(lib, x, w, b, lengths, k, d, slope):
-    """dissc_conv1d on device x [B, Cin, ld] (ld a multiple of 4) into an output prefilled with the sentinel"""
-    B, cin, ld = x.shape
-    cout = w.shape[0]
-    assert ld % 4 == 0
-    y = torch.full((B, cout, ld), SENTINEL, device=DEV)
-    ln = torch.as_tensor(lengths, dtype=torch.int32, device=DEV)
-    lib.check(lib.lib.dissc_conv1d(x.data_ptr(), w.contiguous().data_ptr(), b.contiguous().data_ptr(), y.data_ptr(), ln.data_ptr(),
-                                   B, cin, cout, k, d, ld, ld, int(max(lengths)), ctypes.c_float(slope), None), "dissc_conv1d")
-    return y
-
-
-def check_edges(y, beyond, what):
-    """nothing written beyond an utterance (the sentinel is still there), nothing from beyond it inside (the input is NaN there)"""
-    b = beyond.expand_as(y)
-    assert (torch.where(b, y, torch.full_like(y, SENTINEL)) == SENTINEL).all(), ("wrote beyond an utterance", what)
-    assert torch.isfinite(torch.where(b, torch.zeros_like(y), y)).all(), ("a sample from beyond an utterance's length reached its output", what)
-
-
-def held(y, beyond):
-    """the output with the sentinel columns beyond each utterance (asserted untouched) as zeros, on the CPU"""
-    yb = torch.where(beyond.expand_as(y), y, torch.full_like(y, SENTINEL))
-    assert (yb == SENTINEL).all(), "wrote beyond an utterance"
-    return torch.where(beyond.expand_as(y), torch.zeros_like(y), y).cpu()
 
 
 def all_tiles(lib, case, shape, family):
@@ -213,42 +147,6 @@ def test_16_row_kernel_every_tile_shape(lib, shape):
         assert torch.equal(y32, y), "the 16-row and the 32-row kernel differ"
 
 
-def ragged_lengths(B, seed):
-    rs = np.random.RandomState(seed)
-    lengths = rs.randint(0, 301, B)
-    lengths[[3, 64, B - 1]] = 0
-    lengths[[0, 1, 63, 65, B - 2]] = [300, 77, 129, 1, 257]
-    return [int(n) for n in lengths]
-
-
-def walk_case(lib, shape, B, opts_list, alone):
-    cin, cout, k, d, slope = shape
-    lengths = ragged_lengths(B, seed=B)
-    ld = 300
-    rs = np.random.RandomState(B + cin)
-    x = make_x(rs, B, cin, ld, lengths).to(DEV)
-    w = torch.from_numpy((rs.uniform(-1, 1, (cout, cin, k)) / np.sqrt(cin * k)).astype(np.float32))
-    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32))
-    beyond = beyond_mask(lengths, ld).to(DEV)
-    first = None
-    for opts in opts_list:
-        with options(lib, **opts):
-            y = run_conv(lib, x, w, b, lengths, k, d, slope)
-        check_edges(y, beyond, opts)
-        first = y if first is None else first
-        assert torch.equal(y, first), opts
-    for i in alone:
-        n = lengths[i]
-        assert n > 0
-        one = run_conv(lib, x[i:i + 1].clone(), w, b, [n], k, d, slope)
-        assert torch.equal(one[0, :, :n], first[i, :, :n]), (i, n)
-    # against torch on a few rows (the bits above carry it to the rest)
-    for i in alone[:2]:
-        n = lengths[i]
-        ref = F.conv1d(F.leaky_relu(x[i:i + 1, :, :n].cpu().double(), slope), w.double(), b.double(), padding=(k - 1) * d // 2, dilation=d)
-        assert float((first[i, :, :n].cpu().double() - ref[0]).abs().max()) <= 2e-5
-
-
 @pytest.mark.parametrize("B", [70, 130])
 def test_ragged_walk_beyond_64_utterances(lib, B):
     """ragged_tile's prefix sum runs over 64 utterances at a time: a batch of two and three rounds, empty utterances at the
@@ -269,16 +167,6 @@ def test_ragged_walk_in_xcd_order(lib):
 
 
 # ---- ConvTranspose ------------------------------------------------------------------------------------------------------
-UPS = [(512, 256, 11, 5), (256, 128, 8, 4), (128, 64, 8, 4), (64, 32, 4, 2), (32, 16, 4, 2), (96, 80, 9, 3)]
-# where the paired float2 store of conv_epilogue32 runs (np, stride, p0 and the GEMM rows of every group all even)
-PAIRED = {(512, 256, 11, 5): False, (256, 128, 8, 4): True, (128, 64, 8, 4): True, (64, 32, 4, 2): True, (32, 16, 4, 2): True,
-          (96, 80, 9, 3): False}
-
-
-def paired_store(g, s):
-    return g["np"] % 2 == 0 and s % 2 == 0 and g["p0"] % 2 == 0 and g["rows"] % 2 == 0
-
-
 @pytest.mark.parametrize("cin,cout,k,s", UPS)
 def test_conv_transpose_every_tile_shape(lib, cin, cout, k, s):
     groups = lib.conv_info(cin, cout, k, 1, s, 16, 600)
@@ -287,7 +175,7 @@ def test_conv_transpose_every_tile_shape(lib, cin, cout, k, s):
     classes = sorted({cls_of(g["rows"]) for g in groups})
     settings = tile_settings(lib, "conv32_cfg_bm{}", classes, lambda: lib.conv_info(cin, cout, k, 1, s, 16, 600))
     widths = {bn for _, forms in settings for _, _, bn in forms}
-    lengths = edge_lengths(widths, max(g["pad_left"] for g in groups))
+    lengths = tile_edge_lengths(widths, max(g["pad_left"] for g in groups))
     B, ld, Lmax = len(lengths), (max(lengths) + 3) // 4 * 4, max(lengths)
     ldo = (s * Lmax + 3) // 4 * 4
     rs = np.random.RandomState(cin + k)
@@ -340,37 +228,20 @@ def test_residual_and_mrf_epilogues_every_tile_shape(lib, C, k, d):
     end in epi_store1's scalar tail.  Reference and bar: tests/pair_harness.py (float64 per utterance, max error 1e-5)."""
     settings = tile_settings(lib, "conv32_cfg_bm{}", [C], lambda: lib.conv_info(C, C, k, d, 1, 16, 600))
     widths = {bn for _, forms in settings for _, _, bn in forms}
-    lengths = [n for n in edge_lengths(widths, (k - 1) * d // 2) if n > 0]
+    lengths = [n for n in tile_edge_lengths(widths, (k - 1) * d // 2) if n > 0]
     assert {n % 4 for n in lengths} == {0, 1, 2, 3}
     ld, B = (max(lengths) + 3) // 4 * 4, len(lengths)
-    x, w1, b1, w2, b2 = ph.data(C, k, lengths, ld, seed=C + k)
-    ref = ph.reference(x, w1, b1, w2, b2, lengths, k, d)
+    pair = ph.data(C, k, lengths, ld, seed=C + k)
     acc0 = torch.rand(B, C, ld, device=DEV)
     beyond = beyond_mask(lengths, ld).to(DEV).expand(B, C, ld)
-    first, ran = {}, set()
-    for opts, _ in settings:
-        with options(lib, **opts):
-            ids = {lib.conv_info(C, C, k, dd, 1, B, max(lengths))[0]["cfg"] for dd in (d, 1)}
-            assert len(ids) == 1  # (both launches: the id depends on M, B and Lmax alone)
-            outs = {epi: ph.run_pair(lib, 0, x, w1, b1, w2, b2, lengths, k, d, epi=epi, acc=None if epi == 1 else acc0)
-                    for epi in (1, 2, 3, 4)}
-        ran |= ids
-        for epi, o in outs.items():
-            untouched = torch.full_like(o, -7.0) if epi == 1 else acc0
-            assert torch.equal(torch.where(beyond, o, untouched), untouched), (opts, epi, "wrote beyond an utterance")
-            assert torch.isfinite(torch.where(beyond, torch.zeros_like(o), o)).all(), (opts, epi, "read beyond an utterance")
-            first.setdefault(epi, o)
-            assert torch.equal(o, first[epi]), (opts, ids, epi)
+    ran = set()
+
+    def ids_in_force(opts):
+        ids = {lib.conv_info(C, C, k, dd, 1, B, max(lengths))[0]["cfg"] for dd in (d, 1)}
+        assert len(ids) == 1, (opts, ids)  # (both launches: the id depends on M, B and Lmax alone)
+        ran.update(ids)
+        return ids
+
+    first = pair_epilogues_every_setting(lib, 0, pair, lengths, k, d, acc0, beyond, [opts for opts, _ in settings], ids_in_force)
     assert ran == IDS32[C], ran
-    y = first[1]
-    worst = 0.0
-    for i, n in enumerate(lengths):
-        assert torch.isfinite(y[i, :, :n]).all()
-        worst = max(worst, float((y[i, :, :n].double() - ref[i, :, :n]).abs().max()))
-        for epi in (2, 3, 4):
-            want = y[i, :, :n] if epi == 2 else acc0[i, :, :n] + y[i, :, :n]
-            if epi == 4:
-                want = (want.cpu() / 3.0).to(DEV)  # a true division, like the reference's xs / num_kernels (not x * (1 / 3))
-            assert torch.equal(first[epi][i, :, :n], want), (epi, i, n)
-    print(f"\nDT pair C {C} k {k} d {d}: ids {sorted(ran)}, max err {worst:.2e}, lengths {lengths}")
-    assert worst <= 1e-5
+    check_pair_epilogues(first, pair, lengths, k, d, acc0, beyond, f"DT pair C {C} k {k} d {d}: ids {sorted(ran)}, ")

@@ -12,6 +12,7 @@ halo for a block) of a tile boundary or an utterance end:
 The distance of a pair or block to the model itself is printed, not asserted.  Run with -s for one "GSB" line per case;
 profiles/gen_split_bf16_tiles.md is a copy of them."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -20,11 +21,11 @@ import torch.nn.functional as F
 
 import pair_harness as ph
 import split_bf16_model as sm
-from test_gpu_direct_conv_tiles import PAIRED, SENTINEL, UPS, beyond_mask, check_edges, held, make_x, options, paired_store
+import tile_harness as th
+from tile_harness import (DEV, PAIRED, SENTINEL, SLOPE, UPS, beyond_mask, check_edges, edge_columns, held, lib, make_x, options,  # noqa: F401
+                          paired_store)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SLOPE = 0.1
 
 # (Cin, Cout, k, dilation, input slope): one per row class of conv_bf3_kernel's table, and the awkward ones
 CONVS = [(257, 512, 7, 1, 1.0),      # conv_pre: Cin no multiple of 16, two M tiles
@@ -40,13 +41,9 @@ TILES_OF_CLASS = {0: {(0, 0)}, 1: {(1, 0)}, 2: {(2, 0), (1, 1)}, 3: {(3, 0), (1,
 BLOCKS = [(C, k, (1, 3, 5)) for C in (16, 32, 64) for k in (3, 7, 11)] + [(64, 11, (5, 5, 5))]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from dissc_amd import _lib
-    assert _lib.lib.dissc_abi_version() >= 8
-    return _lib
+@pytest.fixture(scope="module", autouse=True)
+def abi(lib):
+    assert lib.lib.dissc_abi_version() >= 8
 
 
 def bf3_class(M):
@@ -56,22 +53,11 @@ def bf3_class(M):
 def edge_lengths(widths, pad):
     """0, 1, 2, 3, pad, pad + 1, m W + e for every width in play (m = 1, 2; e = -1, 0, 1), two columns past the first edge of the
     narrowest (so that every residue modulo 4 ends beside an edge) and the row stride itself -> (lengths, ld)"""
-    ls = {0, 1, 2, 3, pad, pad + 1, min(widths) + 2} | {m * w + e for w in widths for m in (1, 2) for e in (-1, 0, 1)}
+    ls = th.edge_lengths(widths, pad, extra=(3, min(widths) + 2))
     ld = (max(ls) + 3) // 4 * 4
-    ls.add(ld)
-    ls = sorted(ls)
+    ls = sorted(set(ls) | {ld})
     assert {n % 4 for n in ls if any(0 < abs(n - m * w) <= 2 for w in widths for m in (1, 2))} == {1, 2, 3}
     return ls, ld
-
-
-def edge_columns(n, widths, reach, mul=1):
-    """the columns of [0, n * mul) within `reach` (* mul) of an utterance end or of a boundary of a tile of one of the widths"""
-    t = torch.arange(n * mul)
-    m = (t < reach * mul) | (t >= (n - reach) * mul)
-    for w in widths:
-        for e in range(w, n + reach, w):
-            m |= (t >= (e - reach) * mul) & (t < (e + reach) * mul)
-    return m
 
 
 class Worst:
@@ -121,15 +107,7 @@ def in_one_row(x, lengths, gap):
     return row, offs
 
 
-def run_conv(lib, x, w, b, lengths, k, d, slope, Lmax=None, prec=1):
-    """dissc_conv1d_prec on device x [B, Cin, ld] into a sentinel-filled output; lengths None: the uniform call (all Lmax long)"""
-    B, cin, ld = x.shape
-    y = torch.full((B, w.shape[0], ld), SENTINEL, device=DEV)
-    ln = None if lengths is None else torch.as_tensor(lengths, dtype=torch.int32, device=DEV)
-    lib.check(lib.lib.dissc_conv1d_prec(x.data_ptr(), w.contiguous().data_ptr(), b.contiguous().data_ptr(), y.data_ptr(),
-                                        None if ln is None else ln.data_ptr(), B, cin, w.shape[0], k, d, ld, ld,
-                                        int(max(lengths)) if Lmax is None else Lmax, ctypes.c_float(slope), prec, None), "dissc_conv1d_prec")
-    return y
+run_conv = functools.partial(th.run_conv, prec=1)  # dissc_conv1d_prec, split-bf16
 
 
 # ---- conv_bf3_kernel, every tile -----------------------------------------------------------------------------------------
@@ -202,22 +180,19 @@ def test_pair_epilogues_on_the_large_and_the_small_grid_tile(lib, C, k, d):
     pad = (k - 1) * d // 2
     lengths, ld = edge_lengths(widths, pad)
     B = len(lengths)
-    x, w1, b1, w2, b2 = ph.data(C, k, lengths, ld, seed=C + k)
+    x, w1, b1, w2, b2 = pair = ph.data(C, k, lengths, ld, seed=C + k)
     acc0 = torch.rand(B, C, ld, device=DEV)
     beyond = beyond_mask(lengths, ld).to(DEV).expand(B, C, ld)
-    first, ran = {}, set()
-    for sg in (0, 1):
-        with options(lib, small_grid=sg):
-            infos = [lib.bf3_conv_info(C, C, k, dd, B, max(lengths)) for dd in (d, 1)]
-            outs = {epi: ph.run_pair(lib, 5, x, w1, b1, w2, b2, lengths, k, d, epi=epi, acc=None if epi == 1 else acc0) for epi in (1, 2, 3, 4)}
-        assert infos[0] == infos[1] and infos[0]["small_grid"] == sg
-        ran.add((infos[0]["tile"], sg))
-        for epi, o in outs.items():
-            untouched = torch.full_like(o, -7.0) if epi == 1 else acc0
-            assert torch.equal(torch.where(beyond, o, untouched), untouched), (sg, epi, "wrote beyond an utterance")
-            assert torch.isfinite(torch.where(beyond, torch.zeros_like(o), o)).all(), (sg, epi, "read beyond an utterance")
-            first.setdefault(epi, o)
-            assert torch.equal(o, first[epi]), (sg, epi, "the small-grid tile differs from the class tile")
+    ran = set()
+
+    def tile_in_force(opts):
+        infos = [lib.bf3_conv_info(C, C, k, dd, B, max(lengths)) for dd in (d, 1)]
+        assert infos[0] == infos[1] and infos[0]["small_grid"] == opts["small_grid"], (opts, infos)
+        ran.add((infos[0]["tile"], opts["small_grid"]))
+        return infos[0]
+
+    # (the small-grid tile gives the bits of the class tile)
+    first = th.pair_epilogues_every_setting(lib, 5, pair, lengths, k, d, acc0, beyond, [dict(small_grid=0), dict(small_grid=1)], tile_in_force)
     assert ran == TILES_OF_CLASS[bf3_class(C)], ran
     xc, a0 = x.cpu(), acc0.cpu()
     got = {epi: o.cpu() for epi, o in first.items()}

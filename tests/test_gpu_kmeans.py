@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_oracle_golden import kmeans_f32, kmeans_tie_cases
+from kmeans_cases import kmeans_f32, kmeans_tie_cases
 
 pytestmark = pytest.mark.gpu
 

@@ -24,9 +24,10 @@ import numpy as np
 import pytest
 import torch
 
+import mel_cases as fwd
 import mel_grad_ref
-import test_gpu_mel as fwd
-from test_gpu_mel import FACTOR, KINDS, NARROW, ODD_HOP, SHIPPED, batch_of, ref_kwargs
+from mel_cases import FACTOR, KINDS, NARROW, ODD_HOP, SHIPPED, batch_of, ref_kwargs
+from mel_grad_ref import GradRef, noisy_of
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -37,27 +38,6 @@ def melmod():
     from dissc_amd import mel
     assert mel.GRAD_TILE_FRAMES == mel.TILE_FRAMES == 64  # else: add one sample either side of the gradient's own tile
     return mel
-
-
-def noisy_of(waves):
-    rs = np.random.RandomState(7)
-    return [np.clip(w + 0.01 * rs.standard_normal(len(w)), -1, 1).astype(np.float32) for w in waves]
-
-
-class GradRef:
-    """float64 gradients of a set of signals for fixed cotangents, the float32 path's error on them, the bar"""
-
-    def __init__(self, waves, P, log, cots=None, seed=11):
-        kw, rs = ref_kwargs(P), np.random.RandomState(seed)
-        self.waves, self.P, self.log = waves, P, log
-        self.cots = cots or [rs.standard_normal((P["num_mels"], len(w) // P["hop_size"])).astype(np.float32) for w in waves]
-        self.g64 = [mel_grad_ref.vjp(w, c, kw, torch.float64, log) for w, c in zip(waves, self.cots)]
-        g32 = [mel_grad_ref.vjp(w, c, kw, torch.float32, log) for w, c in zip(waves, self.cots)]
-        self.e32 = max(self.err(i, g) for i, g in enumerate(g32))
-        self.bar = FACTOR * self.e32
-
-    def err(self, i, g):
-        return float(np.abs(np.asarray(g, np.float64) - self.g64[i]).max() / np.abs(self.g64[i]).max())
 
 
 _refs = {}

@@ -15,7 +15,7 @@ import sys
 import pytest
 import torch
 
-from test_gpu_pipeline import ROOT, _free_port, _run, _sweep_jobs, _write_models, _write_wavs, models  # noqa: F401
+from pipeline_cases import ROOT, _free_port, _run, _sweep_jobs, _write_models, _write_wavs, models  # noqa: F401
 
 # DISSC_MULTIGPU_REHEARSAL=gloo: run this file's code on a ONE-GPU box with two gloo ranks sharing the device (what the other test
 # files do for the product path) -- a rehearsal of the TESTS themselves, so that their first execution on a multi-GPU box is not

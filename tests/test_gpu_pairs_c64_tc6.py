@@ -11,9 +11,9 @@ import pytest
 import torch
 
 import pair_harness as ph
-import test_gpu_trained_like as ttl
-from test_gpu_generator import FP32_GUARD_RMS, _generator_with, _pair_cases, _rms
-from test_gpu_trained_like import tl  # noqa: F401  (its module fixture: trained-like checkpoint and the float64 oracle's layer taps)
+import trained_like_cases as ttl
+from generator_cases import FP32_GUARD_RMS, _generator_with, _pair_cases, _rms
+from trained_like_cases import tl  # noqa: F401  (its module fixture: trained-like checkpoint and the float64 oracle's layer taps)
 
 pytestmark = pytest.mark.gpu
 C = 64

@@ -8,9 +8,9 @@ import pytest
 import torch
 
 import pair_harness as ph
-import test_gpu_trained_like as ttl
-from test_gpu_generator import _generator_with, _pair_cases
-from test_gpu_trained_like import tl  # noqa: F401  (its module fixture: trained-like checkpoint and the float64 oracle's layer taps)
+import trained_like_cases as ttl
+from generator_cases import _generator_with, _pair_cases
+from trained_like_cases import tl  # noqa: F401  (its module fixture: trained-like checkpoint and the float64 oracle's layer taps)
 
 pytestmark = pytest.mark.gpu
 SIX = ph.Form("six-point", 3, {}, ph.TC6)

@@ -18,7 +18,7 @@ from scipy.io import wavfile
 from scipy.stats import wasserstein_distance
 
 import eval_ref as er
-from test_yaapt import CASES, FS, _speech, voiced
+from yaapt_cases import CASES, FS, _speech, voiced
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

@@ -19,8 +19,7 @@ import torch
 
 from oracle import train_ref as TR
 from oracle import train_stages_ref as S
-from test_gpu_train import _flip_tolerant
-from test_train_oracle import BN_FED_BIASES
+from train_cases import BN_FED_BIASES, _flip_tolerant
 import train_stage_cases as C
 
 pytestmark = pytest.mark.gpu
@@ -117,7 +116,7 @@ def test_stages_at_full_size(kind, harsh):
 @pytest.mark.parametrize("kind", ["len", "new", "base"])
 def test_whole_step_at_full_size(kind):
     """the existing whole-step style at the new shapes: loss and gradients against float64 autograd (bars of
-    test_gpu_train._flip_tolerant), the same step twice from the same state gives identical bits, state_dict layout"""
+    train_cases._flip_tolerant), the same step twice from the same state gives identical bits, state_dict layout"""
     B, L = LARGE[kind]
     batch, hp = C.make_batch(kind, B, L, seed=100), C.hyper(kind)
     outs = []

@@ -13,7 +13,7 @@ import pytest
 import torch
 from scipy.io import wavfile
 
-from test_yaapt import CASES, FS, _speech, check_track, pulse_train, speech_track_is_plausible, voiced
+from yaapt_cases import CASES, FS, _speech, check_track, pulse_train, speech_track_is_plausible, voiced
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,25 +1,17 @@
 """dissc_pair_info without a GPU for the six-point pairs of the 64-channel stage (respair64_tc6_kernel; option "pair_tc6_c64":
 bit 1 = k = 7, bit 2 = k = 11): the form and the outputs a workgroup owns (Tc6Geo64::WOUT of csrc/respair_f23.h) under the options
-that select them, no instance without them, and the pins of tests/test_pair_info.py untouched by the option."""
+that select them, no instance without them, and the pins of tests/pair_harness.py (held by tests/test_pair_info.py) untouched by the option."""
 import contextlib
 import ctypes
 
 import pytest
 
 import pair_harness as ph
-import test_pair_info as tpi
+from tile_harness import lib  # noqa: F401  (the module fixture)
 
 C = 64
-DILS = (1, 3, 5)
+DILS = ph.DILS
 TILES = {7: (184, 172, 172), 11: (176, 176, 168)}  # 4 waves, 64 conv_d columns per workgroup
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from dissc_amd import _lib
-    return _lib
 
 
 @contextlib.contextmanager
@@ -56,12 +48,12 @@ def test_no_instance_without_the_bit_or_the_master_switch(lib, k):
 
 
 def test_the_option_changes_no_other_shape(lib):
-    """every pin and refusal of tests/test_pair_info.py with both bits set; the k = 3 pairs of the stage keep F(2,3)"""
-    for Cx, k, opts, form, tiles in tpi.PINS:
+    """every pin and refusal of pair_harness.PINS / NONE_* with both bits set; the k = 3 pairs of the stage keep F(2,3)"""
+    for Cx, k, opts, form, tiles in ph.PINS:
         with c64_options(lib, 3, **opts):
             for d, tile in zip(DILS, tiles):
                 assert ph.pair_info(lib, Cx, k, d) == (form, tile), (Cx, k, d, opts)
-    for Cx, k, opts in tpi.NONE_ANYWHERE + ([] if ph.experimental(lib) else tpi.NONE_DEFAULT):
+    for Cx, k, opts in ph.NONE_ANYWHERE + ([] if ph.experimental(lib) else ph.NONE_DEFAULT):
         with c64_options(lib, 3, **opts):
             for d in DILS:
                 assert ph.pair_info(lib, Cx, k, d) is None, (Cx, k, d, opts)

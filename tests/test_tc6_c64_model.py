@@ -1,11 +1,11 @@
 """The six-point Toom-Cook form of the k = 7 / 11 residual pairs of the 64-channel stage (respair64_tc6_kernel, respair_f23.hip),
-checked without a GPU: the numpy model of tests/test_tc6_model.py (the kernel's fp32 arithmetic: ascending 16-channel chunks, then
+checked without a GPU: the numpy model of tests/tc6_model.py (the kernel's fp32 arithmetic: ascending 16-channel chunks, then
 sub-filter, then channel; one rounding per fused multiply-add) at C = 64 against float64, next to the direct-order fp32 model of the
 same pair.  The bar is the project's 3 x the direct-order model's rms error."""
 import numpy as np
 import pytest
 
-from test_tc6_model import _conv_tc6, _rms_errors, trained_like  # noqa: F401  (its module fixture: the trained-like checkpoint)
+from tc6_model import _conv_tc6, _rms_errors, trained_like  # noqa: F401  (its module fixture: the trained-like checkpoint)
 
 C = 64
 

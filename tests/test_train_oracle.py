@@ -8,18 +8,10 @@ import numpy as np
 import pytest
 import torch
 
-import synthdata as synth
 from oracle import train_ref as tr
+from train_cases import BN_FED_BIASES, compact, initial_state
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def compact(a):
-    a = np.asarray(a)
-    if a.size <= 4096:
-        return a.copy()
-    f = a.reshape(-1).astype(np.float64)
-    return np.concatenate([[f.sum(), np.abs(f).sum(), (f * f).sum()], f[::max(1, f.size // 509)]])
 
 
 def close(got, want, rtol, atol, what=""):
@@ -27,17 +19,6 @@ def close(got, want, rtol, atol, what=""):
     assert got.shape == want.shape, what
     scale = np.abs(want).max() if want.size else 0.0
     np.testing.assert_allclose(got, want, rtol=rtol, atol=atol + rtol * scale, err_msg=what)
-
-
-BN_FED_BIASES = {"len": {"cnn1.bias"} | {f"cnn1{i}.bias" for i in range(1, 7)},
-                 "new": {"cnn2.bias"},
-                 "base": {"cnn1.bias", "cnn_class1.bias", "cnn_reg1.bias"} | {f"cnn1{i}.bias" for i in range(1, 8)}}
-
-
-def initial_state(kind, n_spk=108):
-    if kind == "len":
-        return synth.synth_len_state_dict(100, n_spk)
-    return synth.synth_pitch_state_dict(kind, 100, n_spk)
 
 
 @pytest.mark.parametrize("kind", ["len", "new", "base"])

@@ -75,7 +75,7 @@ def test_chained_stages_equal_autograd_in_float64(kind):
 
 
 def BN_FED(kind):
-    from test_train_oracle import BN_FED_BIASES
+    from train_cases import BN_FED_BIASES
     return BN_FED_BIASES[kind]
 
 

@@ -133,7 +133,7 @@ def test_f0_is_normalised_by_the_source_speakers_statistics(cli, golden_dir, tmp
 @pytest.mark.gpu
 def test_validate_cli_equals_the_float64_oracle(cli, golden_dir, tmp_path, capsys):
     import mel_ref
-    from test_gpu_mel import SHIPPED, Ref
+    from mel_cases import SHIPPED, Ref
     from dissc_amd import AttrDict, CodeGenerator, formats
     td = str(tmp_path)
     cfg, names = setup_tree(td, golden_dir, checkpoints=(("g_00000001", 0), ("g_00000002", 1)))

@@ -4,85 +4,19 @@ that run_wino8 launches, held to a Python statement of the documented rules -- t
 instance -- and to the tile geometry as conv_wino8.hip's header comment and Wino8Geo define it.  Every plan must be launchable
 (the row tiles divide the 8 XCDs): C = 512 therefore stops at MI = 2.  The GPU tests (tests/test_gpu_wino8_tiles.py) take their
 tiles and tile-edge lengths from this entry."""
-import contextlib
 import ctypes
 import itertools
 
 import pytest
 
-TILES = [(1, 1, 4), (2, 1, 4), (2, 2, 4), (4, 2, 2), (2, 4, 2), (2, 2, 2)]  # (MI, NI, WPS) built per transform shape
-CS, KS, DS, RS = (64, 128, 256, 512), (3, 7, 11), (1, 3, 5), (3, 4)
-
-
-def geometry(R, k, d, NI, WPS):
-    """(unit width, OT, CPR) of a tile.  A unit is MO = 9 - R outputs in each of D = d NS phases, NS = ceil(k / R) sub-filters; a
-    tile of 32 NI columns (one per (unit, phase)) holds NTU = floor(32 NI / D) units -- as F(6,3) an odd D takes an even unit
-    count, so that the tile is a whole number of output quads; F(5,4) takes them all.  A round stages 16 channels, 8 in the
-    tiles built for two workgroups per CU (WPS = 4) or with 128 columns -- except the NI = 1 (latency) tiles, which stage 16."""
-    MO, NS = 9 - R, -(-k // R)
-    D = d * NS
-    ntu = 32 * NI // D
-    if R == 3 and D % 2 == 1 and ntu % 2 == 1:
-        ntu -= 1
-    cpr = 16 if NI == 1 else 8 if (NI == 4 or WPS == 4) else 16
-    return MO * D, MO * D * ntu, cpr
-
-
-def has_instance(C, k, d, R, experimental):
-    if C not in CS or k not in KS or d not in DS or R not in RS or (R == 4 and k == 3):
-        return False
-    return k != 3 or experimental or (C == 64 and d == 1)  # the default build carries one k = 3 instance
-
-
-def rule(C, k, d, R, B, Lmax, small_grid=1, wide=3, experimental=False):
-    """the documented tile choice.  C >= 128: 128 x 64 tiles; under "small_grid", with n = the workgroups those tiles would
-    make, n < 128 -> 64 x 64 on two workgroups per CU, n < 64 -> 64 x 32, n < 32 -> 32 x 32 -- but never below the tile whose row
-    tiles number 8 (they are pinned to the 8 XCDs and must divide them): C = 512 stops at MI = 2, on the same NI and so the
-    same bits.  C = 64: under "small_grid", fewer than 192 of the 64 x 64 tiles -> 64 x 32; otherwise "wino8_c64_wide": 1 = 64 x 128,
-    2 = 64 x 64 two per CU, 3 = 1 for k = 7 as F(6,3) and 2 otherwise, 4 = 1 for k = 7 and 2 otherwise, anything else 64 x 64 one
-    per CU.  k = 3 (default build): the one instance whatever the options say."""
-    if k == 3 and not experimental:
-        return (2, 2, 4)
-    if C >= 128:
-        n = -(-Lmax // geometry(R, k, d, 2, 2)[1]) * (C // 128) * B
-        if small_grid and n < 32:
-            return (2 if C // 32 > 8 else 1, 1, 4)
-        if small_grid and n < 64:
-            return (2, 1, 4)
-        if small_grid and n < 128:
-            return (2, 2, 4)
-        return (4, 2, 2)
-    n = -(-Lmax // geometry(R, k, d, 2, 4)[1]) * (C // 64) * B
-    if small_grid and n < 192:
-        return (2, 1, 4)
-    mode = ((1 if (k == 7 and R == 3) else 2) if wide == 3 else (1 if k == 7 else 2) if wide == 4 else wide)
-    return {1: (2, 4, 2), 2: (2, 2, 4)}.get(mode, (2, 2, 2))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from dissc_amd import _lib
-    return _lib
+from plan_rules import (DS, KS, RS, WINO8_CS as CS, WINO8_TILES as TILES, wino8_geometry as geometry, wino8_has_instance as has_instance,
+                        wino8_rule as rule)
+from tile_harness import lib, options  # noqa: F401  (lib: the module fixture)
 
 
 @pytest.fixture(scope="module")
 def exp_build(lib):
     return lib.get_option("experimental") == 1
-
-
-@contextlib.contextmanager
-def options(lib, **kv):
-    """sets options; restores the values read before (dissc_get_option)"""
-    before = {k: lib.get_option(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            lib.set_option(k, v)
-        yield
-    finally:
-        for k, v in before.items():
-            lib.set_option(k, v)
 
 
 def plan(lib, C, k, d, R, B, Lmax):

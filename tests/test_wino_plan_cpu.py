@@ -4,8 +4,8 @@ six-point F(4,3) conv, held to a Python statement of the documented rules -- C =
 "wino_sv", 32 channels per barrier round where the registers allow it -- and to the tile geometry as conv_wino.hip's header
 comment defines it.  Every plan must be launchable (the row tiles divide the 8 XCDs, the LDS fits the 160 KB the launch asks
 for), and the library must carry exactly the instances the rules can reach.  The GPU tests (tests/test_gpu_wino_tiles.py) take
-their instances and tile-edge lengths from this entry and their expected instance sets from `instances` below."""
-import contextlib
+their instances and tile-edge lengths from this entry and their expected instance sets from the same statement of the rules,
+`wino_instances` of tests/plan_rules.py."""
 import ctypes
 import itertools
 import re
@@ -14,66 +14,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-CS, KS, DS = (64, 128, 256, 512), (3, 7, 11), (1, 3, 5)
-SMALL_GRID = 96        # workgroups of the large tile below which a launch steps down
-LDS_LIMIT = 160 * 1024
+from plan_rules import (DS, KS, LDS_LIMIT, SMALL_GRID, WINO_CS as CS, wino_all_instances as all_instances, wino_geometry as geometry,
+                        wino_instances as instances, wino_rule as rule)
+from tile_harness import beyond_mask, edge_mask, lib, options  # noqa: F401  (lib: the module fixture)
+
 # outputs per workgroup tile for (k, d) = (3,1) (3,3) (3,5) (7,1) (7,3) (7,5) (11,1) (11,3) (11,5), worked by hand from
 # OT = 4 D floor(32 TW / D) (3 - RH), D = d ceil(k / 3): C >= 128 (RH = 2); C = 64 (RH = 1) has twice that
 OT_LARGE = (256, 252, 240, 252, 252, 240, 256, 240, 240)
 OT_SMALL = (128, 120, 120, 120, 108, 120, 128, 96, 80)
-
-
-def geometry(k, d, rh, tw):
-    """(unit, OT): a tile unit is 4 outputs in each of D = d NS phases, NS = ceil(k / 3) sub-filters; a wave's 32 TW columns (one
-    per (unit, phase)) hold floor(32 TW / D) units; a workgroup has RH row halves and 3 - RH column halves"""
-    D = d * -(-k // 3)
-    return 4 * D, 4 * D * (32 * tw // D) * (3 - rh)
-
-
-def rule(C, k, d, B, Lmax, small_grid=1, wino_sv=1):
-    """the documented choice (CPR, RH, TW, SHV)"""
-    if C == 32:  # the diagnostic instance: no layer takes it
-        return (16, 1, 1, 0)
-    rh = 1 if C == 64 else 2
-    n = -(-Lmax // geometry(k, d, rh, 2)[1]) * (1 if C == 64 else C // 128) * B
-    if small_grid and n < SMALL_GRID:
-        return (16, rh, 1, 0)
-    if C == 64:
-        return (16, 1, 2, 0)
-    if wino_sv:
-        return (32 if k == 3 else 16, 2, 2, 1)  # (with 32 channels per round the k = 7 / 11 instances spill)
-    return (16 if (k, d) == (11, 5) else 32, 2, 2, 0)  # (k = 11, d = 5 with 32 needs more registers than three waves per SIMD leave)
-
-
-def instances(C, k, d):
-    """the instances (NS, d, CPR, RH, TW, SHV) a supported layer of C channels can reach, by the rule"""
-    ns = -(-k // 3)
-    return {(ns, d) + rule(C, k, d, B, L, sg, sv) for B, L in ((1, 1), (4096, 4096)) for sg in (0, 1) for sv in (0, 1)}
-
-
-def all_instances():
-    return set().union(*(instances(C, k, d) for C in CS + (32,) for k in KS for d in DS))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from dissc_amd import _lib
-    return _lib
-
-
-@contextlib.contextmanager
-def options(lib, **kv):
-    """sets options; restores the values read before (dissc_get_option)"""
-    before = {k: lib.get_option(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            lib.set_option(k, v)
-        yield
-    finally:
-        for k, v in before.items():
-            lib.set_option(k, v)
 
 
 def plan(lib, C, k, d, B, Lmax):
@@ -197,7 +145,6 @@ def test_the_edge_column_bar_has_teeth():
     fp32 conv, the reference float64, the lengths and the edge columns those of the GPU test.  Two defects, each in ONE utterance at
     ONE tile boundary (the second tile of the width under test): (a) the first tap dropped where it reads the previous tile's
     columns (d columns), (b) one unit's columns shifted by D.  Either must miss the edge bar by more than 1 000 x; the clean model must sit inside it."""
-    import test_gpu_wino8_tiles as w8
     C, k, d, unit, widths = 64, 7, 3, 36, (216, 504)
     D, pad = unit // 4, (k - 1) * d // 2
     lengths = [1009, 215, 216, 217, 431, 432, 433, 35, 37, 503, 504, 505]
@@ -213,7 +160,7 @@ def test_the_edge_column_bar_has_teeth():
     direct = F.conv1d(xa, w, b, padding=pad, dilation=d)
     perm = torch.randperm(C, generator=g)
     clean = F.conv1d(xa[:, perm], w[:, perm], b, padding=pad, dilation=d)
-    valid = ~w8.dt.beyond_mask(lengths, ld).expand(B, C, ld)
+    valid = ~beyond_mask(lengths, ld).expand(B, C, ld)
     def rms(y, mask):
         return float((torch.where(mask, y.double() - r64, torch.zeros_like(r64)).pow(2).sum() / mask.sum()).sqrt())
 
@@ -223,7 +170,7 @@ def test_the_edge_column_bar_has_teeth():
         dropped[0, :, t0:t0 + d] -= torch.einsum("oc,ct->ot", w[:, :, 0], xa[0, :, t0 - pad:t0 - pad + d])
         shifted = clean.clone()  # (b) the first unit of that tile comes from D columns further on
         shifted[0, :, t0:t0 + unit] = clean[0, :, t0 + D:t0 + unit + D]
-        edge = w8.edge_mask(lengths, ld, unit, [wd]).expand(B, C, ld) & valid
+        edge = edge_mask(lengths, ld, unit, [wd]).expand(B, C, ld) & valid
         base = rms(direct, edge)
         ratios = {name: rms(y, edge) / base for name, y in (("clean", clean), ("tap dropped", dropped), ("unit shifted", shifted))}
         whole = {name: rms(y, valid) / rms(direct, valid) for name, y in (("tap dropped", dropped), ("unit shifted", shifted))}
