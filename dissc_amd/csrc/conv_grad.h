@@ -1,7 +1,10 @@
-// What the two differentiable conv layers share (conv_grad.hip: the stride-1 Conv1d; conv_grad_t.hip: ConvTranspose1d): the
-// partial plan of the weight gradient, the fixed-order sum over its partials, the bias gradient, and the host side of a layer
-// handle (base, argument checks, the backward's workspace layout, the tap-group dispatch).  Defined in conv_grad.hip.
+// What the three differentiable conv layers share (conv_grad.hip: the stride-1 Conv1d; conv_grad_t.hip: ConvTranspose1d;
+// conv_grad_s.hip: the strided Conv1d): the partial plan of the weight gradient, the fixed-order sum over its partials, the bias
+// gradient, the (plane, shift) table of a strided layer's taps, and the host side of a layer handle (base, argument checks, the
+// backward's workspace layout, the tap-group dispatch).  Defined in conv_grad.hip.
 #pragma once
+#include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -26,14 +29,36 @@ CgPlan cg_plan(int Cin, int Cout, int K, int B, int Lmax);
 
 inline size_t cg_rup(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
+// The two strided layers are phrased on the s phase planes of their long side, plane_p[c][q] = long[c][s q + p]: tap kk reads
+// long[s t + kk - pad] = plane_p[t + dl] with kk - pad = s dl + p, 0 <= p < s (ConvTranspose1d: pad = (k - s) / 2, the long side
+// is y / gy; strided Conv1d: pad = (k - 1) / 2, the long side is x).
+constexpr int CT_MAX_S = 8;
+struct CtTaps {
+  int p[CG_MAX_K], dl[CG_MAX_K];  // tap kk reads plane p[kk] at t + dl[kk]
+  int halo;                       // >= every |dl|, multiple of 4
+};
+inline CtTaps ct_taps(int k, int s, int pad) {
+  CtTaps t;
+  int m = 0;
+  for (int kk = 0; kk < CG_MAX_K; ++kk) {
+    const int o = (kk < k ? kk : k - 1) - pad;
+    t.p[kk] = ((o % s) + s) % s;
+    t.dl[kk] = (o - t.p[kk]) / s;  // exact
+    m = std::max(m, std::abs(t.dl[kk]));
+  }
+  t.halo = (m + 3) & ~3;
+  return t;
+}
+
 // out[i] = sum over the NP partials part[p][i], i < n, in a fixed order
 void cg_launch_reduce(const float* part, int NP, size_t n, float* out, hipStream_t st);
-// gb[co] = sum_b sum_{t < min(lengths[b] * len_mul, Lmax)} gy[b][co][t], in double; bpart: B * Cout doubles of workspace
+// gb[co] = sum_b sum_{t < min(ceil(lengths[b] * len_mul / len_div), Lmax)} gy[b][co][t], in double; bpart: B * Cout doubles of
+// workspace.  Lmax: positions of gy
 void cg_launch_bias(const float* gy, const int32_t* lengths, int len_mul, int B, int Cout, int Lmax, int ldo, double* bpart,
-                    float* gb, hipStream_t st);
+                    float* gb, hipStream_t st, int len_div = 1);
 
 // ---- the host side of a layer handle; `who` is the C entry that was called: every message starts with it ----
-struct CgLayer {  // the base of dissc_convgrad and dissc_convtgrad
+struct CgLayer {  // the base of dissc_convgrad, dissc_convtgrad and dissc_convsgrad
   Options opt;  // this handle's snapshot of the tuning options (common.h)
   int Cin = 0, Cout = 0, k = 0;
   bool ready = false;  // device buffers allocated (the first set_weights)
@@ -41,9 +66,9 @@ struct CgLayer {  // the base of dissc_convgrad and dissc_convtgrad
 
 // create: the out pointer and the channel range; kernel size, dilation and stride rules are each layer's own
 int cg_check_create(const char* who, const void* out, int Cin, int Cout);
-// a call on a handle: the arguments; then, with len_mul > 0 (1, or the stride: a row of y / gy holds len_mul * Lmax), the row
-// strides and "set_weights first"
-int cg_check_call(const CgLayer* h, const char* who, int B, int Lmax, int len_mul = 0, int ldx = 0, int ldo = 0);
+// a call on a handle: the arguments; then, with len_mul > 0 (1, or the stride: a row of y / gy holds len_mul * Lmax; with
+// len_div = the stride of a strided Conv1d: ceil(Lmax / len_div)), the row strides and "set_weights first"
+int cg_check_call(const CgLayer* h, const char* who, int B, int Lmax, int len_mul = 0, int ldx = 0, int ldo = 0, int len_div = 1);
 
 // the backward's workspace behind its 256-byte aligned base: partials at 0, the bias gradient's doubles at `bpart`; `bytes` is
 // what *_workspace_bytes promises

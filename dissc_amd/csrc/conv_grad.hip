@@ -197,13 +197,14 @@ __device__ __forceinline__ double cg_block_sum_d(double v, double* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// bpart[b][co] = sum_{t < len_b} gy[b][co][t], len_b = lengths[b] * len_mul (a ConvTranspose1d's rows are stride times its lengths)
+// bpart[b][co] = sum_{t < len_b} gy[b][co][t], len_b = ceil(lengths[b] * len_mul / len_div) (a ConvTranspose1d's rows are stride
+// times its lengths, a strided Conv1d's ceil(lengths / stride))
 __global__ void __launch_bounds__(256) convgrad_bias_part_kernel(const float* __restrict__ gy, const int32_t* __restrict__ lengths,
-                                                                 int len_mul, int Cout, int Lmax, int ldo,
+                                                                 int len_mul, int len_div, int Cout, int Lmax, int ldo,
                                                                  double* __restrict__ bpart) {
   __shared__ double red[4];
   const int co = blockIdx.x, b = blockIdx.y;
-  int len = lengths ? lengths[b] * len_mul : Lmax;
+  int len = lengths ? (lengths[b] * len_mul + len_div - 1) / len_div : Lmax;
   len = len < 0 ? 0 : (len > Lmax ? Lmax : len);
   const float* row = gy + ((size_t)b * Cout + co) * ldo;
   double s = 0.0;
@@ -288,8 +289,9 @@ void cg_launch_reduce(const float* part, int NP, size_t n, float* out, hipStream
 }
 
 void cg_launch_bias(const float* gy, const int32_t* lengths, int len_mul, int B, int Cout, int Lmax, int ldo, double* bpart,
-                    float* gb, hipStream_t st) {
-  hipLaunchKernelGGL(convgrad_bias_part_kernel, dim3(Cout, B), dim3(256), 0, st, gy, lengths, len_mul, Cout, Lmax, ldo, bpart);
+                    float* gb, hipStream_t st, int len_div) {
+  hipLaunchKernelGGL(convgrad_bias_part_kernel, dim3(Cout, B), dim3(256), 0, st, gy, lengths, len_mul, len_div, Cout, Lmax, ldo,
+                     bpart);
   hipLaunchKernelGGL(convgrad_bias_reduce_kernel, dim3((Cout + 63) / 64), dim3(64), 0, st, bpart, B, Cout, gb);
 }
 
@@ -305,18 +307,23 @@ int cg_check_create(const char* who, const void* out, int Cin, int Cout) {
   return DISSC_OK;
 }
 
-int cg_check_call(const CgLayer* h, const char* who, int B, int Lmax, int len_mul, int ldx, int ldo) {
+int cg_check_call(const CgLayer* h, const char* who, int B, int Lmax, int len_mul, int ldx, int ldo, int len_div) {
   if (!h || B <= 0 || Lmax <= 0 || B > 65535) {
     set_error("%s: bad argument (handle %p, B = %d, Lmax = %d)", who, (void*)h, B, Lmax);
     return DISSC_EINVAL;
   }
   if (len_mul <= 0) return DISSC_OK;  // a host-only query: no rows
-  if (ldx < Lmax || (long long)ldo < (long long)len_mul * Lmax || (ldx & 3) || (ldo & 3)) {
-    set_error("%s: row strides %d / %d must be multiples of 4 and >= Lmax = %d / %d x Lmax = %d", who, ldx, ldo, Lmax, len_mul,
-              len_mul * Lmax);
+  const long long need = ((long long)len_mul * Lmax + len_div - 1) / len_div;  // a row of y / gy
+  if (ldx < Lmax || (long long)ldo < need || (ldx & 3) || (ldo & 3)) {
+    if (len_div > 1)
+      set_error("%s: row strides %d / %d must be multiples of 4 and >= Lmax = %d / ceil(Lmax / %d) = %d", who, ldx, ldo, Lmax,
+                len_div, (int)need);
+    else
+      set_error("%s: row strides %d / %d must be multiples of 4 and >= Lmax = %d / %d x Lmax = %d", who, ldx, ldo, Lmax, len_mul,
+                len_mul * Lmax);
     return DISSC_EINVAL;
   }
-  if (!h->ready) {  // "dissc_conv[t]grad_" of the entry's own name
+  if (!h->ready) {  // "dissc_conv[t|s]grad_" of the entry's own name
     set_error("%s: %.*sset_weights first", who, (int)(strrchr(who, '_') + 1 - who), who);
     return DISSC_EINVAL;
   }

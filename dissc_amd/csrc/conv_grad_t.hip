@@ -36,28 +36,8 @@
 
 namespace dissc {
 
-constexpr int CT_MAX_S = 8;
 constexpr size_t CT_WG_LDS = 80 * 1024;  // weight gradient: two workgroups per CU, as conv_grad.hip
 constexpr size_t CT_DG_LDS = 40 * 1024;  // data gradient: the staged slab of gy
-
-struct CtTaps {
-  int p[CG_MAX_K], dl[CG_MAX_K];  // tap kk reads plane p[kk] at t + dl[kk]
-  int halo;                       // >= every |dl|, multiple of 4
-};
-
-static CtTaps ct_taps(int k, int s) {
-  CtTaps t;
-  const int pad = (k - s) / 2;
-  int m = 0;
-  for (int kk = 0; kk < CG_MAX_K; ++kk) {
-    const int o = (kk < k ? kk : k - 1) - pad;
-    t.p[kk] = ((o % s) + s) % s;
-    t.dl[kk] = (o - t.p[kk]) / s;  // exact
-    m = std::max(m, std::abs(t.dl[kk]));
-  }
-  t.halo = (m + 3) & ~3;
-  return t;
-}
 
 // ---- the weight gradient ------------------------------------------------------------------------------------------------
 struct WgradTArgs {
@@ -471,7 +451,7 @@ int dissc_convtgrad_backward(dissc_convtgrad_t h, const float* x, const float* g
   if ((rc = cg_backward_begin(who, p, B, h->Cout, x, gy, gx, gw || gb, workspace, workspace_bytes, &part, &bpart))) return rc;
   OptScope opt_scope(&h->opt);
   hipStream_t st = (hipStream_t)stream;
-  const CtTaps tp = ct_taps(h->k, h->s);
+  const CtTaps tp = ct_taps(h->k, h->s, (h->k - h->s) / 2);
   if (gw) {
     WgradTArgs a;
     a.gy = gy; a.x = x; a.lengths = lengths; a.part = part;

@@ -1,9 +1,11 @@
-"""Differentiable layers for training the vocoder's generator on the MI355X (C ABI ``dissc_convgrad_*``,
-csrc/conv_grad.hip, and ``dissc_convtgrad_*``, csrc/conv_grad_t.hip).
+"""Differentiable layers for training the vocoder on the MI355X (C ABI ``dissc_convgrad_*``, csrc/conv_grad.hip,
+``dissc_convtgrad_*``, csrc/conv_grad_t.hip, and ``dissc_convsgrad_*`` / ``dissc_period_fold_*``, csrc/conv_grad_s.hip).
 
     y = nn.conv1d(x, weight, bias, lengths=lengths, dilation=d, in_slope=0.1, add=res)   # a torch.autograd.Function
     y = nn.resblock1(x, weights, k)                                                       # reference sr/models.py:34-41
     y = nn.conv_transpose1d(x, weight, bias, stride=u, lengths=lengths, in_slope=0.1)     # the upsamplers ups[i]
+    y = nn.conv1d_strided(x, weight, bias, stride=3, lengths=lengths, in_slope=0.1)       # the period discriminator's layers
+    score, fmaps, lens = nn.discriminator_p(wav, weights, period, lengths)                # reference sr/models.py:228-260
 
 ``conv1d`` is the stride-1 "same" Conv1d that 92 of the generator's 97 conv layers are, with dissc_conv1d's conventions:
 the leaky ReLU of the INPUT is applied on load (``in_slope``; 1.0 = none), ``add`` is a residual added in the epilogue,
@@ -12,9 +14,9 @@ MFMA conv kernels, the weight gradient on its own MFMA kernel with fixed-order p
 The weights are a DEVICE tensor and are packed on the device on every call, because they change every step in training.
 No torch compute op on the hot path, no CPU fallback.  First order only.
 
-The two conv layers are one core: a ``_Kind`` describes each (its C entries, the weight layout, the rows of y per row of x),
-and one handle cache, one set of checks, ``_forward`` and ``_backward`` work on that description; the two autograd Functions
-differ in their argument lists only.
+The three conv layers are one core: a ``_Kind`` describes each (its C entries, the weight layout, the row length of y for a
+row length of x), and one handle cache, one set of checks, ``_forward`` and ``_backward`` work on that description; the three
+autograd Functions differ in their argument lists only.
 """
 import ctypes
 
@@ -32,12 +34,13 @@ _ENTRIES = ("create", "destroy", "set_weights", "forward", "partials", "workspac
 
 
 class _Kind:
-    """one differentiable conv layer kind: its C entries, how (Cin, Cout, k) are read from the weight's shape, the rows of y per
-    row of x as a function of the layer's own parameter p (dilation or stride), and the names its messages use"""
+    """one differentiable conv layer kind: its C entries, how (Cin, Cout, k) are read from the weight's shape, the outputs
+    nout(p, ld) of a row of ld inputs as a function of the layer's own parameter p (dilation or stride), and the names its
+    messages use"""
 
-    def __init__(self, who, prefix, layout, dims, mul, fwd_args):
+    def __init__(self, who, prefix, layout, dims, nout, fwd_args):
         vp, i32, sz, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
-        self.who, self.prefix, self.layout, self.dims, self.mul = who, prefix, layout, dims, mul
+        self.who, self.prefix, self.layout, self.dims, self.nout = who, prefix, layout, dims, nout
         self.names = {e: f"{prefix}_{e}" for e in _ENTRIES}
         for e, name in self.names.items():
             setattr(self, e, getattr(lib, name))
@@ -49,11 +52,18 @@ class _Kind:
         self.workspace_bytes.argtypes, self.workspace_bytes.restype = [vp, i32, i32], sz
         self.backward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]
 
+    def ldo(self, p, ld):
+        """the row length of y: the outputs, rounded up to 4"""
+        return (self.nout(p, ld) + 3) // 4 * 4
 
-# weight [Cout, Cin, k], p = dilation, forward(h, x, add, ...)  /  weight [Cin, Cout, k], p = stride, forward(h, x, ...)
-CONV1D = _Kind("nn.conv1d", "dissc_convgrad", "[Cout, {}, k]", lambda s: (s[1], s[0], s[2]), lambda p: 1, [ctypes.c_void_p] * 3)
-CONV_TRANSPOSE1D = _Kind("nn.conv_transpose1d", "dissc_convtgrad", "[{}, Cout, k]", lambda s: (s[0], s[1], s[2]), lambda p: p,
-                         [ctypes.c_void_p] * 2)
+
+# weight [Cout, Cin, k], p = dilation, forward(h, x, add, ...)  /  weight [Cin, Cout, k], p = stride, forward(h, x, ...)  /
+# weight [Cout, Cin, k], p = stride, forward(h, x, ...)
+CONV1D = _Kind("nn.conv1d", "dissc_convgrad", "[Cout, {}, k]", lambda s: (s[1], s[0], s[2]), lambda p, ld: ld, [ctypes.c_void_p] * 3)
+CONV_TRANSPOSE1D = _Kind("nn.conv_transpose1d", "dissc_convtgrad", "[{}, Cout, k]", lambda s: (s[0], s[1], s[2]),
+                         lambda p, ld: p * ld, [ctypes.c_void_p] * 2)
+CONV1D_STRIDED = _Kind("nn.conv1d_strided", "dissc_convsgrad", "[Cout, {}, k]", lambda s: (s[1], s[0], s[2]),
+                       lambda p, ld: -(-ld // p), [ctypes.c_void_p] * 2)
 
 _handles = {}     # (prefix, Cin, Cout, k, p, device) -> handle; device None: host-only queries
 _workspaces = {}  # device -> uint8 tensor, grown on demand (calls on one device are stream-ordered)
@@ -99,6 +109,18 @@ def workspace_bytes_transpose(B, Lmax, Cin, Cout, k, stride):
     return int(CONV_TRANSPOSE1D.workspace_bytes(_handle(CONV_TRANSPOSE1D, Cin, Cout, k, stride), int(B), int(Lmax)))
 
 
+def wgrad_partials_strided(B, Lmax, Cin, Cout, k, stride):
+    """wgrad_partials for conv1d_strided's weight gradient [Cout, Cin, k]: Lmax is in INPUT positions, the chunks are
+    WGRAD_CHUNK OUTPUT positions (stride * WGRAD_CHUNK columns of x), ceil(ceil(Lmax / stride) / WGRAD_CHUNK) per utterance.
+    A function of the shape only (host only)."""
+    return _partials(CONV1D_STRIDED, B, Lmax, Cin, Cout, k, stride)
+
+
+def workspace_bytes_strided(B, Lmax, Cin, Cout, k, stride):
+    """bytes of conv1d_strided's backward workspace (host only)"""
+    return int(CONV1D_STRIDED.workspace_bytes(_handle(CONV1D_STRIDED, Cin, Cout, k, stride), int(B), int(Lmax)))
+
+
 def _workspace(device, nbytes):
     ws = _workspaces.get(device)
     if ws is None or ws.numel() < nbytes:
@@ -139,15 +161,16 @@ def _ptr(t):
 
 
 def _forward(kind, ctx, x, weight, bias, lengths, p, in_slope, *add):
-    """set_weights, the output (zeros where lengths leave part of it unwritten), forward; saves x and weight, never y"""
+    """set_weights, the output (zeros where lengths, or a row longer than its outputs, leave part of it unwritten), forward;
+    saves x and weight, never y"""
     B, _, ld = x.shape
     Cin, Cout, k = kind.dims(weight.shape)
     h = _handle(kind, Cin, Cout, k, p, x.device)
     st = current_stream_ptr(x.device)
-    ldo = kind.mul(p) * ld
+    ldo = kind.ldo(p, ld)
     with torch.cuda.device(x.device):
         check(kind.set_weights(h, _ptr(weight), _ptr(bias), st), kind.names["set_weights"])
-        y = torch.zeros((B, Cout, ldo), dtype=torch.float32, device=x.device) if lengths is not None else \
+        y = torch.zeros((B, Cout, ldo), dtype=torch.float32, device=x.device) if lengths is not None or ldo != kind.nout(p, ld) else \
             torch.empty((B, Cout, ldo), dtype=torch.float32, device=x.device)
         check(kind.forward(h, _ptr(x), *map(_ptr, add), _ptr(y), _ptr(lengths), B, ld, ldo, ld, in_slope, st), kind.names["forward"])
     ctx.save_for_backward(x, weight)
@@ -179,7 +202,7 @@ def _backward(kind, ctx, gy):
             if need_w or need_b:
                 nws = int(kind.workspace_bytes(h, B, ld))
                 ws = _workspace(x.device, nws)
-            check(kind.backward(h, _ptr(x), _ptr(gy), _ptr(ctx.lengths), B, ld, kind.mul(ctx.p) * ld, ld, ctx.in_slope,
+            check(kind.backward(h, _ptr(x), _ptr(gy), _ptr(ctx.lengths), B, ld, kind.ldo(ctx.p, ld), ld, ctx.in_slope,
                                 _ptr(gx), _ptr(gw), _ptr(gb), _ptr(ws), nws, st), kind.names["backward"])
     return gx, gw, gb, gy
 
@@ -237,6 +260,30 @@ def conv_transpose1d(x, weight, bias=None, stride=1, lengths=None, in_slope=1.0)
     return _ConvTranspose1dFn.apply(x, weight, bias, lengths, int(stride), float(in_slope))
 
 
+class _Conv1dStridedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, lengths, stride, in_slope):
+        return _forward(CONV1D_STRIDED, ctx, x, weight, bias, lengths, stride, in_slope)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return _backward(CONV1D_STRIDED, ctx, gy)[:3] + (None, None, None)
+
+
+def conv1d_strided(x, weight, bias=None, stride=2, lengths=None, in_slope=1.0):
+    """y = bias + Conv1d(lrelu(x, in_slope), weight, stride=stride, padding=(k - 1) // 2): the strided layers of the period
+    discriminator (reference sr/models.py:234-237 on period-major rows), the adjoint of conv_transpose1d.
+
+    x [B, Cin, ld]: contiguous fp32 device tensor, ld % 4 == 0; y [B, Cout, ceil4(ceil(ld / stride))].  weight: DEVICE tensor
+    [Cout, Cin, k], k odd, 3 <= k <= 11, 2 <= stride <= min(k, 8); bias [Cout] or None.  lengths: int32 [B] on the device (or
+    None = ld), INPUT lengths: utterance b has ceil(lengths[b] / stride) valid output positions (torch's count for that input),
+    x is read as zero from lengths[b] on, y is left zero beyond its length and the incoming gradient is read as zero there; the
+    gradient of x is zero from lengths[b] on.  Gradients flow to x, weight and bias; x and weight are saved, y is not."""
+    _check_layer(CONV1D_STRIDED, x, weight, bias, lengths)
+    return _Conv1dStridedFn.apply(x, weight, bias, lengths, int(stride), float(in_slope))
+
+
 def resblock1(x, weights, k, dilations=(1, 3, 5), lengths=None, taps=None):
     """ResBlock1 (reference sr/models.py:34-41): for each dilation d,  x = x + conv_1(lrelu(conv_d(lrelu(x)))), composed
     from six conv1d calls with the residual through ``add=``.  weights: {"convs1.<m>.weight" / ".bias",
@@ -252,6 +299,133 @@ def resblock1(x, weights, k, dilations=(1, 3, 5), lengths=None, taps=None):
         x = conv1d(xt, weights[f"convs2.{m}.weight"], weights.get(f"convs2.{m}.bias"), lengths=lengths, dilation=1,
                    in_slope=LRELU_SLOPE, add=x)
     return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The period discriminator (reference sr/models.py:228-260) on period-major rows: the fold (C ABI dissc_period_fold_*,
+# csrc/conv_grad_s.hip), four conv1d_strided, two conv1d.
+# ---------------------------------------------------------------------------------------------------------------------
+lib.dissc_period_fold_fwd.argtypes = lib.dissc_period_fold_bwd.argtypes = \
+    [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p]
+DISC_P_STRIDE, DISC_P_STRIDED_LAYERS = 3, 4  # reference sr/models.py:229, :234-237
+
+
+def _ceil4(n):
+    return (n + 3) // 4 * 4
+
+
+def _host_lengths(lengths, B, T, who):
+    """host int64 [B] from a list, an array or a tensor on either side; None: T"""
+    if lengths is None:
+        return np.full(B, T, dtype=np.int64)
+    ln = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+    if ln.shape[0] != B or (ln < 0).any() or (ln > T).any():
+        raise ValueError(f"{who}: lengths must be [B] counts within 0 .. {T}")
+    return ln
+
+
+def _check_reflect(ln, period, who):
+    """F.pad(..., "reflect") of n samples to a multiple of the period needs the padding, period - n % period, below n"""
+    for n in ln:
+        if n % period and n <= period - n % period:
+            raise ValueError(f"{who}: an utterance of {int(n)} samples cannot be reflect-padded to a multiple of the period {period}")
+
+
+class _PeriodFoldFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wav, period, lengths):
+        B, T = wav.shape[0], wav.shape[-1]
+        ldh = _ceil4(-(-T // period))
+        x0 = torch.zeros((B * period, 1, ldh), dtype=torch.float32, device=wav.device)
+        with torch.cuda.device(wav.device):
+            check(lib.dissc_period_fold_fwd(_ptr(wav), _ptr(lengths), B, T, period, T, ldh, _ptr(x0), current_stream_ptr(wav.device)),
+                  "dissc_period_fold_fwd")
+        ctx.lengths, ctx.period, ctx.shape = lengths, period, tuple(wav.shape)
+        return x0
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gx0):
+        gx0 = gx0.contiguous()
+        B, T = ctx.shape[0], ctx.shape[-1]
+        gwav = torch.empty(ctx.shape, dtype=torch.float32, device=gx0.device)
+        with torch.cuda.device(gx0.device):
+            check(lib.dissc_period_fold_bwd(_ptr(gx0), _ptr(ctx.lengths), B, T, ctx.period, T, gx0.shape[2], _ptr(gwav),
+                                            current_stream_ptr(gx0.device)), "dissc_period_fold_bwd")
+        return gwav, None, None
+
+
+def _check_wav(wav, who):
+    if not (wav.is_cuda and wav.dtype == torch.float32 and wav.is_contiguous() and wav.shape[-1] >= 1
+            and (wav.dim() == 2 or (wav.dim() == 3 and wav.shape[1] == 1))):
+        raise DisscError(f"{who}: wav must be a contiguous fp32 device tensor [B, 1, T] or [B, T]")
+
+
+def period_fold(wav, period, lengths=None):
+    """x0 [B * period, 1, ceil4(ceil(T / period))] from wav [B, 1, T] or [B, T] with lengths[b] valid samples (a list, an array
+    or a tensor on either side; None = T): the view(b, c, t // period, period) of reference sr/models.py:245-250, period-major.
+    Row b * period + w holds ypad_b[h * period + w] for h < ceil(lengths[b] / period), ypad_b = utterance b reflect-padded at
+    ITS OWN end to a multiple of the period, zero beyond.  Every row is an independent 1-D sequence.  ValueError where torch's
+    reflect pad raises (0 < n <= period - n % period with n % period != 0); n = 0 gives empty rows.  The gradient of wav sums
+    each sample's one or two contributions (no atomics) and is zero from lengths[b] on."""
+    who = "nn.period_fold"
+    _check_wav(wav, who)
+    period = int(period)
+    if not 1 <= period <= 65535:
+        raise DisscError(f"{who}: period {period} outside 1 .. 65535")
+    dev_len = lengths if isinstance(lengths, torch.Tensor) and lengths.is_cuda else None
+    if lengths is not None:
+        ln = _host_lengths(lengths, wav.shape[0], wav.shape[-1], who)
+        _check_reflect(ln, period, who)
+        if dev_len is None:
+            dev_len = torch.from_numpy(ln.astype(np.int32)).to(wav.device)
+    else:
+        _check_reflect([wav.shape[-1]], period, who)
+    if not _lengths_ok(dev_len, wav.shape[0]):
+        raise DisscError(f"{who}: device lengths must be a contiguous int32 tensor [B]")
+    return _PeriodFoldFn.apply(wav, period, dev_len)
+
+
+def discriminator_p(wav, weights, period, lengths=None):
+    """DiscriminatorP (reference sr/models.py:228-260) of wav [B, 1, T] or [B, T] with lengths[b] valid samples (host counts; a
+    device tensor is copied back) -> (score, fmaps, lens).
+
+    weights: {"convs.<i>.weight" / ".bias" (i = 0 .. 4), "conv_post.weight" / ".bias"}, device tensors with weight norm already
+    folded, Conv2d weights [Cout, Cin, k, 1] or [Cout, Cin, k].  Composed as period_fold, four conv1d_strided (k = 5, stride 3;
+    the first with in_slope = 1), conv1d (k = 5) and conv1d (k = 3) with in_slope = 0.1, on B * period rows: no torch compute op
+    on the path.  fmaps: the six feature maps [B * period, C, ld_l], PRE-ACTIVATION and zero beyond their lengths: where the
+    reference appends leaky_relu(conv) to fmap, every consumer here applies the leaky ReLU on load, as the next layer does (a
+    feature-matching loss reads lrelu(f, 0.1) of maps 0 .. 4 and map 5 as it is).  score: the last map, [B * period, 1, ld]
+    (row b * period + w, column h is the reference's flattened score[b][h * period + w]).  lens: the six maps' per-row device
+    lengths, int32 [B * period] each: ceil(n / period), divided by 3 (rounded up) once per strided layer."""
+    who = "nn.discriminator_p"
+    _check_wav(wav, who)
+    period = int(period)
+    B, T = wav.shape[0], wav.shape[-1]
+    ln = _host_lengths(lengths, B, T, who)
+    _check_reflect(ln, period, who)
+    rows = [np.repeat(-(-ln // period), period)]
+    for _ in range(DISC_P_STRIDED_LAYERS):
+        rows.append(-(-rows[-1] // DISC_P_STRIDE))
+    # the waveform's and every layer's lengths in one upload
+    flat = torch.from_numpy(np.concatenate([ln] + rows).astype(np.int32)).to(wav.device)
+    n = B * period
+    wav_len, lens = flat[:B], [flat[B + i * n:B + (i + 1) * n] for i in range(len(rows))]
+
+    def W(name):
+        w = weights[name + ".weight"]
+        return (w.view(w.shape[:3]) if w.dim() == 4 and w.shape[3] == 1 else w), weights.get(name + ".bias")
+
+    x = _PeriodFoldFn.apply(wav, period, wav_len)
+    fmaps = []
+    for i in range(DISC_P_STRIDED_LAYERS):
+        x = conv1d_strided(x, *W(f"convs.{i}"), stride=DISC_P_STRIDE, lengths=lens[i], in_slope=LRELU_SLOPE if i else 1.0)
+        fmaps.append(x)
+    x = conv1d(x, *W(f"convs.{DISC_P_STRIDED_LAYERS}"), lengths=lens[-1], in_slope=LRELU_SLOPE)
+    fmaps.append(x)
+    x = conv1d(x, *W("conv_post"), lengths=lens[-1], in_slope=LRELU_SLOPE)
+    fmaps.append(x)
+    return x, fmaps, lens[1:] + [lens[-1], lens[-1]]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

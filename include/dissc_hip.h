@@ -805,6 +805,58 @@ int dissc_convtgrad_backward(dissc_convtgrad_t h, const float* x, const float* g
                              size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * A differentiable, ragged, STRIDED Conv1d layer (csrc/conv_grad_s.hip): the four Conv2d((5,1), stride (3,1)) layers of every
+ * DiscriminatorP (reference sr/models.py:228-260) on the period-major rows of dissc_period_fold_fwd, the layers neither section
+ * above can run.  Added without an ABI bump, as those were.
+ *   y[b,co,q] = bias[co] + sum_{ci,kk} w[co,ci,kk] lrelu(x, in_slope)[b,ci,stride q + kk - pad],  pad = (k - 1) / 2
+ *   x f32 [B][Cin][ldx], y / gy f32 [B][Cout][ldo], 16-byte aligned, ldx and ldo multiples of 4, ldx >= Lmax and
+ *   ldo >= ceil(Lmax / stride).  lengths i32 [B] on the device or NULL (= Lmax) and Lmax are INPUT positions: utterance b has
+ *   ceil(lengths[b] / stride) valid output positions (torch's own count for an input of lengths[b]: the last window reaches at
+ *   most lengths[b] + 1, inside the conv's zero padding); input at and beyond lengths[b] is read as zero, y is never written at
+ *   or beyond the output length and gy is read as zero there.
+ * dissc_convsgrad_create: HOST ONLY.  k odd, 3 <= k <= 11, 2 <= stride <= min(k, 8), 1 <= Cin, Cout <= 65535; anything else is
+ *   DISSC_EINVAL with a message that names the rule.
+ * dissc_convsgrad_set_weights: w_dev f32 [Cout][Cin][k] and bias_dev f32 [Cout] (NULL = no bias) are DEVICE pointers; one kernel
+ *   packs the A fragments of the forward and of the data gradient.  Call it again whenever the weights changed.
+ * dissc_convsgrad_packed: the packings, for tests.  which = 0: the forward's, [ceil(Cout / 32)][k][ceil(Cin / 32) * 4][64][4]
+ *   floats, element (blk, kk, c8, lane, e) = w[co = 32 blk + lane % 32][ci = 8 c8 + 2 e + lane / 32][kk]; which = 1: the data
+ *   gradient's, [ceil(Cin / 32)][k][ceil(Cout / 32) * 4][64][4], = w[co = 8 c8 + 2 e + lane / 32][ci = 32 blk + lane % 32][kk];
+ *   zero outside the weights.  Returns the number of floats (HOST ONLY with dst_dev NULL), after copying them to dst_dev
+ *   otherwise; negative on error.
+ * dissc_convsgrad_forward: one implicit-GEMM kernel on v_mfma_f32_32x32x2_f32 (Cin = 1 included, on zero-padded tiles).
+ * dissc_convsgrad_partials / _workspace_bytes: HOST ONLY, as dissc_convgrad_*: Lmax in INPUT positions, chunks of
+ *   DISSC_CONVGRAD_CHUNK OUTPUT positions, ceil(ceil(Lmax / stride) / chunk) per utterance.
+ * dissc_convsgrad_backward: gx f32 [B][Cin][ldx] (times the leaky ReLU's derivative, torch's rule at x = 0; zero from
+ *   lengths[b] to ldx), gw f32 [Cout][Cin][k], gb f32 [Cout]; each may be NULL and its kernels are skipped.  No atomics, fixed
+ *   summation orders: bit-reproducible, and an utterance's y and gx depend neither on the batch it is in nor on the row strides.
+ *
+ * The period fold in front of the first layer (reference sr/models.py:245-250, period-major: every row is an independent 1-D
+ * sequence, so the Conv2d stack over [B, C, H, p] is plain Conv1d layers on B p rows).
+ * dissc_period_fold_fwd: wav f32 [B][ldw] with lengths[b] (i32 on the device, or NULL = T) valid samples -> x0 f32 [B p][ldh],
+ *   x0[b p + w][h] = ypad_b[h p + w] for h < ceil(lengths[b] / p), ypad_b = utterance b reflect-padded at its own end
+ *   (ypad[n + i] = y[n - 2 - i]); nothing is written beyond.  ldw >= T, ldh >= ceil(T / p).  The caller refuses the lengths
+ *   torch's reflect pad refuses (0 < n <= p - n % p with n % p != 0).
+ * dissc_period_fold_bwd: gwav [B][ldw] = the gather form, each sample its own place plus, where it is a reflect source, the
+ *   padded place; zero from lengths[b] to ldw.  No atomics.
+ * ------------------------------------------------------------------------- */
+typedef struct dissc_convsgrad* dissc_convsgrad_t;
+int dissc_convsgrad_create(int Cin, int Cout, int k, int stride, dissc_convsgrad_t* out);
+void dissc_convsgrad_destroy(dissc_convsgrad_t h);
+int dissc_convsgrad_set_weights(dissc_convsgrad_t h, const float* w_dev, const float* bias_dev, void* stream);
+long long dissc_convsgrad_packed(dissc_convsgrad_t h, int which, float* dst_dev, void* stream);
+int dissc_convsgrad_forward(dissc_convsgrad_t h, const float* x, float* y, const int32_t* lengths, int B, int ldx, int ldo,
+                            int Lmax_in, float in_slope, void* stream);
+int dissc_convsgrad_partials(dissc_convsgrad_t h, int B, int Lmax_in, int* P, int* pairs_per_partial);
+size_t dissc_convsgrad_workspace_bytes(dissc_convsgrad_t h, int B, int Lmax_in);
+int dissc_convsgrad_backward(dissc_convsgrad_t h, const float* x, const float* gy, const int32_t* lengths, int B, int ldx,
+                             int ldo, int Lmax_in, float in_slope, float* gx, float* gw, float* gb, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int dissc_period_fold_fwd(const float* wav, const int32_t* lengths, int B, int T, int period, int ldw, int ldh, float* x0,
+                          void* stream);
+int dissc_period_fold_bwd(const float* gx0, const int32_t* lengths, int B, int T, int period, int ldw, int ldh, float* gwav,
+                          void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The rest of the generator's training step (csrc/gen_train.hip; composed in dissc_amd/nn.py's CodeGenerator): weight norm
  * of every layer at once, the embeddings, the MRF mean, the tanh tail.  Added without an ABI bump, as the sections above.
  * All device pointers f32 unless said otherwise; no atomics, fixed summation orders: bit-reproducible.

@@ -18,6 +18,13 @@ The same for the differentiable ConvTranspose1d (nn.conv_transpose1d, csrc/conv_
 upsamplers against torch's conv_transpose1d autograd (leaky_relu + conv_transpose1d; aten.convolution_backward, transposed,
 one output mask each): the table of profiles/conv_transpose_grad.md.  Its TFLOP/s are of the direct form's MACs,
 Cin Cout k per input position (the forward's phase groups execute some zero taps on top).
+
+    python tools/conv_grad_bench.py --strided [--batch 32] [--samples 8960] [--periods 2,11] [--markdown]
+
+The same for the strided Conv1d (nn.conv1d_strided, csrc/conv_grad_s.hip) on the four strided layers of DiscriminatorP at the
+trainer's shape, 32 segments of 8 960 samples folded to 32 p rows of ceil(8 960 / p) columns, against torch's leaky_relu +
+conv1d(stride=3) autograd on the rows' valid part: the table of profiles/conv_strided_grad.md.  TFLOP/s of the direct form's
+MACs, Cin Cout k per OUTPUT position (Cin = 1 executes 8 channels in the forward and 32 in the gradients).
 """
 import argparse
 import ctypes
@@ -58,19 +65,21 @@ def executed_flops(cin, cout, k, positions):
 
 
 def bench_layer(a, kind, cin, cout, k, p_, L):
-    """one layer through its nn layer kind (nn.CONV1D: p_ = dilation; nn.CONV_TRANSPOSE1D: p_ = stride) and through torch"""
+    """one layer through its nn layer kind (nn.CONV1D: p_ = dilation; nn.CONV_TRANSPOSE1D, nn.CONV1D_STRIDED: p_ = stride) and
+    through torch"""
     from dissc_amd import nn
     from dissc_amd._lib import check, current_stream_ptr
     F = torch.nn.functional
     dev = torch.device("cuda:0")
-    tr = kind is nn.CONV_TRANSPOSE1D
-    s, d = (p_, 1) if tr else (1, p_)
+    tr, sd = kind is nn.CONV_TRANSPOSE1D, kind is nn.CONV1D_STRIDED
+    s, d = (p_, 1) if tr or sd else (1, p_)
     B, slope = a.batch, 0.1
     rs = np.random.RandomState(0)
     ld = rup(L, 4)
+    ldo, nout = kind.ldo(p_, ld), kind.nout(p_, L)  # the row of y / gy, and the outputs of L inputs
     x = torch.from_numpy(rs.standard_normal((B, cin, ld)).astype(np.float32)).to(dev)
-    gy = torch.from_numpy(rs.standard_normal((B, cout, s * ld)).astype(np.float32)).to(dev)
-    w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k) if tr else (cout, cin, k)) / np.sqrt(cin * k / s)).astype(np.float32)).to(dev)
+    gy = torch.from_numpy(rs.standard_normal((B, cout, ldo)).astype(np.float32)).to(dev)
+    w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k) if tr else (cout, cin, k)) / np.sqrt(cin * k / (s if tr else 1))).astype(np.float32)).to(dev)
     b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)).to(dev)
     lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
     y, gx, gw, gb = torch.zeros_like(gy), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
@@ -81,23 +90,25 @@ def bench_layer(a, kind, cin, cout, k, p_, L):
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
     check(kind.set_weights(h, p(w), p(b), st), "set_weights")
     pad = (k - s) // 2 if tr else (k - 1) * d // 2
-    add = () if tr else (None,)
+    add = () if tr or sd else (None,)
+    # torch runs the strided layer on the rows' valid part: ceil(L / s) outputs of L inputs
+    xt, gyt = (x[:, :, :L].contiguous(), gy[:, :, :nout].contiguous()) if sd else (x, gy)
 
     def ours_bwd(gx_, gw_, gb_):
-        check(kind.backward(h, p(x), p(gy), p(lengths), B, ld, s * ld, ld, slope, gx_, gw_, gb_, p(ws), nws, st), "backward")
+        check(kind.backward(h, p(x), p(gy), p(lengths), B, ld, ldo, ld, slope, gx_, gw_, gb_, p(ws), nws, st), "backward")
 
-    xa = F.leaky_relu(x, slope)
+    xa = F.leaky_relu(xt, slope)
     conv_bwd = torch.ops.aten.convolution_backward
 
     def torch_bwd(mask):
-        return conv_bwd(gy, xa, w, [cout], [s], [pad], [d], tr, [0], 1, mask)
+        return conv_bwd(gyt, xa, w, [cout], [s], [pad], [d], tr, [0], 1, mask)
 
     def torch_fwd():
-        xl = F.leaky_relu(x, slope)
-        return F.conv_transpose1d(xl, w, b, stride=s, padding=pad) if tr else F.conv1d(xl, w, b, padding=pad, dilation=d)
+        xl = F.leaky_relu(xt, slope)
+        return F.conv_transpose1d(xl, w, b, stride=s, padding=pad) if tr else F.conv1d(xl, w, b, stride=s, padding=pad, dilation=d)
 
     cases = {
-        "fwd": lambda: check(kind.forward(h, p(x), *add, p(y), p(lengths), B, ld, s * ld, ld, slope, st), "forward"),
+        "fwd": lambda: check(kind.forward(h, p(x), *add, p(y), p(lengths), B, ld, ldo, ld, slope, st), "forward"),
         "torch_fwd": torch_fwd,
         "dgrad": lambda: ours_bwd(p(gx), None, None),
         "torch_dgrad": lambda: torch_bwd([True, False, False]),
@@ -110,8 +121,13 @@ def bench_layer(a, kind, cin, cout, k, p_, L):
     tg = torch_bwd([True, True, True])
     rel = lambda u, v: float((u - v).norm() / v.norm())
     valid = (torch.arange(ld, device=dev) < L).float()
-    agree = {"y": rel(y[:, :, :s * L], torch_fwd()[:, :, :s * L]) if ld == L else None,
-             "gx": rel(gx, tg[0] * torch.where(x > 0, 1.0, slope) * valid), "gw": rel(gw, tg[1]), "gb": rel(gb, tg[2])}
+    if sd:
+        assert not gx[:, :, L:].any() and not y[:, :, nout:].any()
+        agree = {"y": rel(y[:, :, :nout], torch_fwd()), "gx": rel(gx[:, :, :L], tg[0] * torch.where(xt > 0, 1.0, slope)),
+                 "gw": rel(gw, tg[1]), "gb": rel(gb, tg[2])}
+    else:
+        agree = {"y": rel(y[:, :, :s * L], torch_fwd()[:, :, :s * L]) if ld == L else None,
+                 "gx": rel(gx, tg[0] * torch.where(x > 0, 1.0, slope) * valid), "gw": rel(gw, tg[1]), "gb": rel(gb, tg[2])}
     for fn in cases.values():
         timed(fn, 2)
     times = {n: [] for n in cases}
@@ -119,15 +135,15 @@ def bench_layer(a, kind, cin, cout, k, p_, L):
         for n, fn in cases.items():  # alternating
             times[n].append(timed(fn, a.iters))
     P, pairs = nn._partials(kind, B, ld, cin, cout, k, p_)
-    out = {"transpose": True} if tr else {}
-    out.update({"cin": cin, "cout": cout, "k": k, "stride" if tr else "dilation": p_, "L": L, "batch": B, "partials": P,
+    out = {"transpose": True} if tr else ({"strided": True} if sd else {})
+    out.update({"cin": cin, "cout": cout, "k": k, "stride" if tr or sd else "dilation": p_, "L": L, "batch": B, "partials": P,
                 "pairs_per_partial": pairs, "workspace_mb": round(nws / 2**20, 2),
                 "rel_diff_to_torch": {n: None if v is None else float(f"{v:.2e}") for n, v in agree.items()}})
     for n, v in times.items():
         out[n + "_ms"] = round(float(np.median(v)), 4)
         out[n + "_ms_spread"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
     # the transposed layer: the direct form's MACs, Cin Cout k per input position
-    flops = [2.0 * cin * cout * k * B * L] * 3 if tr else executed_flops(cin, cout, k, B * L)
+    flops = [2.0 * cin * cout * k * B * (nout if sd else L)] * 3 if tr or sd else executed_flops(cin, cout, k, B * L)
     for n, fl in zip(("fwd", "dgrad", "wgrad"), flops):
         out[n + "_tflops"] = round(fl / (out[n + "_ms"] * 1e-3) / 1e12, 2)
     print(json.dumps(out), flush=True)
@@ -155,6 +171,33 @@ def main_transpose(a):
     return rows
 
 
+def main_strided(a):
+    import conv_strided_ref as RS
+    from dissc_amd import nn
+    rows, batch = [], a.batch
+    for period in (int(v) for v in a.periods.split(",")):
+        L, a.batch = -(-a.samples // period), batch * period  # the fold: every utterance is `period` rows
+        for cin, cout, k, s in RS.DISC_P:
+            if not a.only or [cin, cout, k] == [int(v) for v in a.only.split(",")]:
+                rows.append(dict(bench_layer(a, nn.CONV1D_STRIDED, cin, cout, k, s, L), period=period))
+            L = -(-L // s)
+    a.batch = batch
+    if a.markdown:
+        print("| period | layer | rows x L in | fwd ms (torch) | dgrad ms (torch) | wgrad ms (torch) | TFLOP/s fwd / dgrad / wgrad | P | repack ms |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['period']} | {r['cin']} -> {r['cout']}, k = {r['k']}, s = {r['stride']} | {r['batch']} x {r['L']} | "
+                  f"{r['fwd_ms']:.3f} ({r['torch_fwd_ms']:.3f}) | {r['dgrad_ms']:.3f} ({r['torch_dgrad_ms']:.3f}) | "
+                  f"{r['wgrad_ms']:.3f} ({r['torch_wgrad_ms']:.3f}) | {r['fwd_tflops']} / {r['dgrad_tflops']} / {r['wgrad_tflops']} | "
+                  f"{r['partials']} | {r['repack_ms']:.3f} |")
+        tot = lambda n: sum(r[n] for r in rows)
+        print(f"\nsum over the listed layers, ours (torch): fwd {tot('fwd_ms'):.2f} ({tot('torch_fwd_ms'):.2f}), "
+              f"dgrad {tot('dgrad_ms'):.2f} ({tot('torch_dgrad_ms'):.2f}), wgrad {tot('wgrad_ms'):.2f} ({tot('torch_wgrad_ms'):.2f}) ms")
+        slower = [(r["period"], r["cin"], r["cout"], n) for r in rows for n in ("fwd", "dgrad", "wgrad") if r[n + "_ms"] > r["torch_" + n + "_ms"]]
+        print("slower than torch:", slower if slower else "none")
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -164,9 +207,14 @@ def main(argv=None):
     ap.add_argument("--only", default=None, help="CIN,COUT,K: that shape only")
     ap.add_argument("--markdown", action="store_true")
     ap.add_argument("--transpose", action="store_true", help="the five ConvTranspose1d upsamplers instead")
+    ap.add_argument("--strided", action="store_true", help="the four strided layers of DiscriminatorP instead")
+    ap.add_argument("--samples", type=int, default=8960, help="--strided: samples per segment")
+    ap.add_argument("--periods", default="2,11", help="--strided: the periods to fold to")
     a = ap.parse_args(argv)
     if a.transpose:
         return main_transpose(a)
+    if a.strided:
+        return main_strided(a)
     import conv_grad_ref as R
     from dissc_amd import nn
     seen, rows = set(), []
