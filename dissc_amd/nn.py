@@ -1,11 +1,14 @@
 """Differentiable layers for training the vocoder on the MI355X (C ABI ``dissc_convgrad_*``, csrc/conv_grad.hip,
-``dissc_convtgrad_*``, csrc/conv_grad_t.hip, and ``dissc_convsgrad_*`` / ``dissc_period_fold_*``, csrc/conv_grad_s.hip).
+``dissc_convtgrad_*``, csrc/conv_grad_t.hip, ``dissc_convsgrad_*`` / ``dissc_period_fold_*``, csrc/conv_grad_s.hip, and
+``dissc_ganloss_*``, csrc/gan_loss.hip).
 
     y = nn.conv1d(x, weight, bias, lengths=lengths, dilation=d, in_slope=0.1, add=res)   # a torch.autograd.Function
     y = nn.resblock1(x, weights, k)                                                       # reference sr/models.py:34-41
     y = nn.conv_transpose1d(x, weight, bias, stride=u, lengths=lengths, in_slope=0.1)     # the upsamplers ups[i]
     y = nn.conv1d_strided(x, weight, bias, stride=3, lengths=lengths, in_slope=0.1)       # the period discriminator's layers
     score, fmaps, lens = nn.discriminator_p(wav, weights, period, lengths)                # reference sr/models.py:228-260
+    out = nn.MultiPeriodDiscriminator()(y, y_hat, lengths)                                # reference sr/models.py:263-286
+    nn.discriminator_loss(out), nn.generator_loss(out), nn.feature_loss(out)              # reference sr/models.py:352-383
 
 ``conv1d`` is the stride-1 "same" Conv1d that 92 of the generator's 97 conv layers are, with dissc_conv1d's conventions:
 the leaky ReLU of the INPUT is applied on load (``in_slope``; 1.0 = none), ``add`` is a residual added in the epilogue,
@@ -913,3 +916,378 @@ class CodeGenerator:
         return tanh(x, lens[-1], self.hop * T)
 
     __call__ = forward
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The period half of the GAN step (reference sr/models.py:263-286, :352-383; sr/train.py:157-190): the fused ragged losses
+# (C ABI dissc_ganloss_*, csrc/gan_loss.hip) and nn.MultiPeriodDiscriminator, which runs y and y_hat as ONE batch of paired maps.
+# ---------------------------------------------------------------------------------------------------------------------
+def _bind_gan_loss():
+    vp, i32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    pi, pf, pp = ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(vp)
+    lib.dissc_ganloss_workspace_bytes.argtypes, lib.dissc_ganloss_workspace_bytes.restype = [i32, pi, pi, pi], sz
+    lib.dissc_ganloss_forward.argtypes = [i32, pp, pp, pi, pi, pi, pi, pf, vp, vp, sz, vp]
+    lib.dissc_ganloss_backward.argtypes = [i32, pp, pp, pi, pi, pi, pi, pf, vp, vp, pp, vp]
+
+
+_bind_gan_loss()
+
+GANLOSS_MAX_MAPS = 64                # DISSC_GANLOSS_MAX_MAPS
+GANLOSS_WG_UNITS = 1024              # float4s per half that one workgroup of the loss kernels takes
+FM, DISC, GEN = 0, 1, 2              # DISSC_GANLOSS_FM / _DISC / _GEN
+MPD_PERIODS = (2, 3, 5, 7, 11)       # reference sr/models.py:267
+_DISC_P_LAYERS = [("convs.0", 1, 32, 5), ("convs.1", 32, 128, 5), ("convs.2", 128, 512, 5), ("convs.3", 512, 1024, 5),
+                  ("convs.4", 1024, 1024, 5), ("conv_post", 1024, 1, 3)]  # (name, Cin, Cout, k), reference sr/models.py:233-239
+
+
+def _int_array(values):
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def ganloss_workspace_bytes(R, C, ld):
+    """bytes of the loss forward's workspace for maps of R[i] row pairs, C[i] channels and row stride ld[i]: a function of the
+    shapes only (host only, no GPU needed); DisscError where the entries would refuse the list"""
+    n = len(R)
+    if n < 1 or len(C) != n or len(ld) != n:
+        raise DisscError("nn.ganloss_workspace_bytes: R, C and ld must be lists of one length, at least 1")
+    nbytes = int(lib.dissc_ganloss_workspace_bytes(n, _int_array(R), _int_array(C), _int_array(ld)))
+    if nbytes == 0:
+        check(-1, "dissc_ganloss_workspace_bytes")
+    return nbytes
+
+
+class _GanLossArgs:
+    """the host arrays of one dissc_ganloss_* call"""
+
+    def __init__(self, ops, maps, lens, R, slopes):
+        n = len(maps)
+        self.n = n
+        self.maps = (ctypes.c_void_p * n)(*[m.data_ptr() for m in maps])
+        self.lens = (ctypes.c_void_p * n)(*[t.data_ptr() for t in lens])
+        self.R, self.C, self.ld = _int_array(R), _int_array([m.shape[1] for m in maps]), _int_array([m.shape[2] for m in maps])
+        self.ops, self.slopes = _int_array(ops), (ctypes.c_float * n)(*[float(s) for s in slopes])
+
+    def head(self):
+        return (self.n, self.maps, self.lens, self.R, self.C, self.ld, self.ops, self.slopes)
+
+
+class _GanLossFn(torch.autograd.Function):
+    """(total, vals [2, n]) of a list of paired maps in one forward and one backward call; the maps are saved (the layer that
+    reads a map saves it anyway)"""
+
+    @staticmethod
+    def forward(ctx, ops, lens, R, slopes, *maps):
+        n, dev = len(maps), maps[0].device
+        a = _GanLossArgs(ops, maps, lens, R, slopes)
+        nws = ganloss_workspace_bytes(R, [m.shape[1] for m in maps], [m.shape[2] for m in maps])
+        out = torch.empty(1 + 2 * n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ws = _workspace(dev, nws)
+            check(lib.dissc_ganloss_forward(*a.head(), _ptr(out), _ptr(ws), nws, current_stream_ptr(dev)), "dissc_ganloss_forward")
+        ctx.save_for_backward(*maps)
+        ctx.ops, ctx.lens, ctx.R, ctx.slopes = ops, lens, R, slopes
+        ctx.set_materialize_grads(False)
+        return out[0], out[1:].view(2, n)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_total, g_vals):
+        maps = ctx.saved_tensors
+        n, dev = len(maps), maps[0].device
+        if g_total is None and g_vals is None:
+            return (None,) * (4 + n)
+        a = _GanLossArgs(ctx.ops, maps, ctx.lens, ctx.R, ctx.slopes)
+        gmaps = [torch.empty_like(m) if ctx.needs_input_grad[4 + i] else None for i, m in enumerate(maps)]
+        pg = (ctypes.c_void_p * n)(*[None if g is None else g.data_ptr() for g in gmaps])
+        g_total = None if g_total is None else g_total.contiguous()
+        g_vals = None if g_vals is None else g_vals.contiguous()
+        with torch.cuda.device(dev):
+            check(lib.dissc_ganloss_backward(*a.head(), _ptr(g_total), _ptr(g_vals), pg, current_stream_ptr(dev)),
+                  "dissc_ganloss_backward")
+        return (None, None, None, None) + tuple(gmaps)
+
+
+def gan_loss(op, maps, lens, R, slopes=None):
+    """The fused ragged GAN losses over a list of PAIRED maps -> (total, vals [2, n]), device tensors with a grad_fn.
+
+    maps[i]: contiguous fp32 device tensor [2 R[i], C, ld], ld % 4 == 0, PRE-activation: rows 0 .. R - 1 the real half, rows
+    R .. 2 R - 1 the generated half.  lens[i]: int32 device tensor of at least R[i] per-row lengths (row r and row R + r share
+    lens[i][r]); positions at or beyond a length are never read for their value.  op: nn.FM, nn.DISC or nn.GEN, one for all maps
+    or one per map; slopes: the leaky ReLU FM applies on load, per map (default 1.0).  With N = C sum(lens[:R]):
+      FM    vals[0][i] = 2 / N sum |lrelu(real) - lrelu(gen)|
+      DISC  vals[0][i] = 1 / N sum (1 - real)^2,  vals[1][i] = 1 / N sum gen^2
+      GEN   vals[0][i] = 1 / N sum (1 - gen)^2
+    (vals[1] is zero for FM and GEN; N = 0: value and gradient 0.)  total = the sum of all values in index order.  One forward
+    launch pair and one backward launch for the whole list (at most nn.GANLOSS_MAX_MAPS maps); sums in double, no atomics: the
+    values are bit-reproducible and a map's do not depend on the list it is in.  The gradient reaches both halves of every map
+    that requires one and is exactly zero at and beyond the lengths."""
+    who = "nn.gan_loss"
+    maps, lens = list(maps), list(lens)
+    n = len(maps)
+    ops = [int(op)] * n if isinstance(op, int) else [int(o) for o in op]
+    R = [int(r) for r in R]
+    slopes = [1.0] * n if slopes is None else [float(s) for s in slopes]
+    if not 1 <= n <= GANLOSS_MAX_MAPS:
+        raise DisscError(f"{who}: {n} maps; one call takes 1 .. {GANLOSS_MAX_MAPS}")
+    if not (len(lens) == len(R) == len(ops) == len(slopes) == n):
+        raise DisscError(f"{who}: maps, lens, R, ops and slopes must have one entry per map")
+    for i, (m, t, r, o) in enumerate(zip(maps, lens, R, ops)):
+        _check_act(m, f"maps[{i}]", who=who)
+        if m.device != maps[0].device or r < 1 or m.shape[0] != 2 * r:
+            raise DisscError(f"{who}: maps[{i}] is {tuple(m.shape)} for R = {r}: a paired map has 2 R rows, on one device")
+        if not (t.is_cuda and t.device == m.device and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.numel() >= r):
+            raise DisscError(f"{who}: lens[{i}] must be a contiguous int32 device tensor of at least R = {r} lengths")
+        if o not in (FM, DISC, GEN):
+            raise DisscError(f"{who}: op {o} is none of nn.FM, nn.DISC, nn.GEN")
+    return _GanLossFn.apply(tuple(ops), tuple(lens), tuple(R), tuple(slopes), *maps)
+
+
+class _PairedFoldFn(torch.autograd.Function):
+    """x0 [2 B period, 1, ldh]: period_fold of y into the first half and of y_hat into the second, by two calls of
+    dissc_period_fold_fwd on the halves of one buffer (no concatenation); the backward runs dissc_period_fold_bwd on a half only
+    where that input requires a gradient"""
+
+    @staticmethod
+    def forward(ctx, y, y_hat, period, lengths):
+        B, T = y.shape[0], y.shape[-1]
+        ldh = _ceil4(-(-T // period))
+        x0 = torch.zeros((2 * B * period, 1, ldh), dtype=torch.float32, device=y.device)
+        half = 4 * B * period * ldh  # bytes; ldh % 4 == 0 keeps the second half 16-byte aligned
+        st = current_stream_ptr(y.device)
+        with torch.cuda.device(y.device):
+            for i, w in enumerate((y, y_hat)):
+                check(lib.dissc_period_fold_fwd(_ptr(w), _ptr(lengths), B, T, period, T, ldh, ctypes.c_void_p(x0.data_ptr() + i * half),
+                                                st), "dissc_period_fold_fwd")
+        ctx.lengths, ctx.period, ctx.shapes = lengths, period, (tuple(y.shape), tuple(y_hat.shape))
+        return x0
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gx0):
+        gx0 = gx0.contiguous()
+        B, T = ctx.shapes[0][0], ctx.shapes[0][-1]
+        ldh = gx0.shape[2]
+        half = 4 * B * ctx.period * ldh
+        st = current_stream_ptr(gx0.device)
+        grads = [None, None]
+        with torch.cuda.device(gx0.device):
+            for i in range(2):
+                if ctx.needs_input_grad[i]:
+                    grads[i] = torch.empty(ctx.shapes[i], dtype=torch.float32, device=gx0.device)
+                    check(lib.dissc_period_fold_bwd(ctypes.c_void_p(gx0.data_ptr() + i * half), _ptr(ctx.lengths), B, T, ctx.period, T,
+                                                    ldh, _ptr(grads[i]), st), "dissc_period_fold_bwd")
+        return grads[0], grads[1], None, None
+
+
+class MPDOutput:
+    """what nn.MultiPeriodDiscriminator returns: per period i, scores[i] (= fmaps[i][5]), the six paired PRE-activation maps
+    fmaps[i][j] [2 R[i], C_j, ld_j] (rows 0 .. R[i] - 1 from y, the rest from y_hat), their per-row device lengths lens[i][j]
+    (int32 [2 R[i]], the two halves alike) and R[i] = B * period"""
+
+    def __init__(self, scores, fmaps, lens, R):
+        self.scores, self.fmaps, self.lens, self.R = scores, fmaps, lens, R
+
+
+class MultiPeriodDiscriminator:
+    """The trainable MultiPeriodDiscriminator (reference sr/models.py:263-286) under the reference's checkpoint keys
+    ``discriminators.<i>.convs.<j>.{weight_g, weight_v, bias}`` (j = 0 .. 4) and ``discriminators.<i>.conv_post.{...}``, Conv2d
+    shapes (weight_v [Cout, Cin, k, 1], weight_g [Cout, 1, 1, 1]): the ``mpd`` entry of a reference ``do_*`` checkpoint.
+
+        D = nn.MultiPeriodDiscriminator().to("cuda:0"); D.load_state_dict(sd["mpd"])
+        out = D(y, y_hat.detach(), lengths); loss_d, r_losses, g_losses = nn.discriminator_loss(out); loss_d.backward()
+        out = D(y, y_hat, lengths, param_grads=False)
+        (nn.feature_loss(out) + nn.generator_loss(out)[0] + 45 * mel.l1_loss(y, y_hat)).backward()
+
+    parameters(): three flat leaves -- every weight_v, every weight_g, every bias of the 30 layers; their weight norm is one
+    launch in each direction.  y and y_hat run as ONE batch [y ; y_hat] per period: the weights are packed once for both and
+    every weight gradient is one pass over both.  No torch compute op on the path (allocation, views, autograd's own sums where a
+    map feeds a layer and a loss)."""
+
+    def __init__(self, periods=MPD_PERIODS):
+        self.periods = tuple(int(p) for p in periods)
+        if not self.periods or any(not 1 <= p <= 65535 for p in self.periods):
+            raise DisscError("nn.MultiPeriodDiscriminator: at least one period, each within 1 .. 65535")
+        if 6 * len(self.periods) > GANLOSS_MAX_MAPS:
+            raise DisscError(f"nn.MultiPeriodDiscriminator: {len(self.periods)} periods give more than {GANLOSS_MAX_MAPS} maps, "
+                             "the most one loss launch takes")
+        # (name, weight shape as the layers take it, bias length) in the reference's order
+        self.layers = [(f"discriminators.{i}.{name}", (cout, cin, k), cout) for i in range(len(self.periods))
+                       for name, cin, cout, k in _DISC_P_LAYERS]
+        self.wn = WeightNorm([(s[0], s[1] * s[2]) for _, s, _ in self.layers], [nb for _, _, nb in self.layers])
+        self.device = torch.device("cuda:0")
+        self.v_flat = self.g_flat = self.bias_flat = None
+
+    # -- nn.Module-like surface --------------------------------------------------------------------------------------
+    def to(self, device):
+        if isinstance(device, int):
+            device = f"cuda:{device}"
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise DisscError("dissc_amd.nn.MultiPeriodDiscriminator runs on an MI355X only (device='cuda:N')")
+        if device.index is None:
+            device = torch.device("cuda:0")
+        if self.v_flat is not None and device != self.device:
+            raise DisscError("nn.MultiPeriodDiscriminator: choose the device before load_state_dict()")
+        self.device = device
+        return self
+
+    def cuda(self, device=0):
+        return self.to(device)
+
+    def _keys(self):
+        keys = []
+        for name, _, _ in self.layers:
+            keys += [name + ".bias", name + ".weight_g", name + ".weight_v"]
+        return keys
+
+    def load_state_dict(self, sd, strict=True):
+        """the reference's layout: weight_g [Cout, 1, 1, 1] / weight_v [Cout, Cin, k, 1] / bias [Cout] per Conv2d"""
+        keys = self._keys()
+        missing = [k for k in keys if k not in sd]
+        unexpected = sorted(set(sd.keys()) - set(keys))
+        if missing or (strict and unexpected):
+            raise RuntimeError("Error(s) in loading state_dict for MultiPeriodDiscriminator: "
+                               f"missing {missing[:5]}, unexpected {unexpected[:5]}")
+        wn = self.wn
+        v, g, b = torch.zeros(wn.total), torch.zeros(wn.total_rows), torch.zeros(wn.bias_total)
+        for i, (name, shape, nb) in enumerate(self.layers):
+            tv, tg, tb = (sd[name + s].detach().to("cpu", torch.float32) for s in (".weight_v", ".weight_g", ".bias"))
+            if tuple(tv.shape) != shape + (1,) or tuple(tg.shape) != (shape[0], 1, 1, 1) or tuple(tb.shape) != (nb,):
+                raise RuntimeError(f"size mismatch for {name}: weight_v {tuple(tv.shape)}, weight_g {tuple(tg.shape)}, bias "
+                                   f"{tuple(tb.shape)}; expected {shape + (1,)}, {(shape[0], 1, 1, 1)}, {(nb,)}")
+            v[wn.off[i]:wn.off[i] + tv.numel()] = tv.reshape(-1)
+            g[wn.row_off[i]:wn.row_off[i] + shape[0]] = tg.reshape(-1)
+            b[wn.bias_off[i]:wn.bias_off[i] + nb] = tb.reshape(-1)
+        leaf = lambda t: t.to(self.device).contiguous().requires_grad_(True)
+        self.v_flat, self.g_flat, self.bias_flat = leaf(v), leaf(g), leaf(b)
+        return self
+
+    def _loaded(self):
+        if self.v_flat is None:
+            raise RuntimeError("load_state_dict() first")
+
+    def parameters(self):
+        """the three flat leaves: v_flat, g_flat, bias_flat"""
+        self._loaded()
+        return [self.v_flat, self.g_flat, self.bias_flat]
+
+    def zero_grad(self):
+        for p in self.parameters():
+            p.grad = None
+
+    def _named(self, v, g, b):
+        out = {}
+        wn = self.wn
+        for i, (name, shape, nb) in enumerate(self.layers):
+            n = shape[0] * shape[1] * shape[2]
+            out[name + ".bias"] = b[wn.bias_off[i]:wn.bias_off[i] + nb]
+            out[name + ".weight_g"] = g[wn.row_off[i]:wn.row_off[i] + shape[0]].view(shape[0], 1, 1, 1)
+            out[name + ".weight_v"] = v[wn.off[i]:wn.off[i] + n].view(shape + (1,))
+        return out
+
+    def named_grads(self):
+        """{reference key: a view of its leaf's .grad} after a backward"""
+        ps = self.parameters()
+        if any(p.grad is None for p in ps):
+            raise RuntimeError("named_grads(): run a backward first")
+        return self._named(*(p.grad for p in ps))
+
+    def state_dict(self):
+        """host copies under the reference's unfolded keys and Conv2d shapes"""
+        self._loaded()
+        return {k: t.clone() for k, t in self._named(*(p.detach().cpu() for p in self.parameters())).items()}
+
+    def folded(self, i):
+        """discriminator i's weights g v / ||v|| as the forward folds them, under nn.discriminator_p's keys (detached device
+        tensors [Cout, Cin, k] and [Cout])"""
+        self._loaded()
+        buf, _ = self.wn.forward(self.v_flat.detach(), self.g_flat.detach(), self.bias_flat.detach())
+        wn, out = self.wn, {}
+        for j, (name, _, _, _) in enumerate(_DISC_P_LAYERS):
+            l = 6 * i + j
+            shape, nb = self.layers[l][1], self.layers[l][2]
+            out[name + ".weight"] = buf[wn.off[l]:wn.off[l] + shape[0] * shape[1] * shape[2]].view(shape)
+            out[name + ".bias"] = buf[wn.total + wn.bias_off[l]:wn.total + wn.bias_off[l] + nb]
+        return out
+
+    # -- forward -------------------------------------------------------------------------------------------------------
+    def forward(self, y, y_hat, lengths=None, param_grads=True):
+        """y, y_hat: contiguous fp32 device tensors of ONE shape, [B, 1, T] or [B, T], with lengths[b] valid samples each (host
+        counts; a device tensor is copied back; None = T) -> MPDOutput.  ValueError where torch's reflect pad would raise for one
+        of the periods.  param_grads=False detaches the three leaves in front of the weight norm: a backward then reaches y_hat
+        (and y) only and skips every weight- and bias-gradient kernel -- the generator's step, whose discriminator gradients the
+        reference computes and throws away."""
+        who = "nn.MultiPeriodDiscriminator"
+        self._loaded()
+        _check_wav(y, who), _check_wav(y_hat, who)
+        if y.shape != y_hat.shape or y.device != y_hat.device or y.device != self.device:
+            raise DisscError(f"{who}: y {tuple(y.shape)} and y_hat {tuple(y_hat.shape)} must have one shape, on {self.device}")
+        B, T = y.shape[0], y.shape[-1]
+        ln = _host_lengths(lengths, B, T, who)
+        for p in self.periods:
+            _check_reflect(ln, p, who)
+        # the waveform's lengths and every period's every layer's row lengths (both halves) in one upload
+        parts, where = [ln], []
+        at = B
+        for p in self.periods:
+            rows = np.tile(np.repeat(-(-ln // p), p), 2)
+            per = []
+            for j in range(DISC_P_STRIDED_LAYERS + 1):
+                if j:
+                    rows = -(-rows // DISC_P_STRIDE)
+                parts.append(rows)
+                per.append(at)
+                at += rows.shape[0]
+            where.append(per)
+        flat = torch.from_numpy(np.concatenate(parts).astype(np.int32)).to(self.device)
+        wav_len = flat[:B]
+        n = len(self.layers)
+        leaves = (self.v_flat, self.g_flat, self.bias_flat) if param_grads else \
+            (self.v_flat.detach(), self.g_flat.detach(), self.bias_flat.detach())
+        wb = _WeightsFn.apply(*leaves, self.wn, [s for _, s, _ in self.layers])
+        scores, fmaps, lens, Rs = [], [], [], []
+        for i, p in enumerate(self.periods):
+            rows2 = 2 * B * p
+            ls = [flat[o:o + rows2] for o in where[i]]  # the fold's rows, then the four strided layers' outputs
+            W = lambda j: (wb[6 * i + j], wb[n + 6 * i + j])
+            x = _PairedFoldFn.apply(y, y_hat, p, wav_len)
+            fm = []
+            for j in range(DISC_P_STRIDED_LAYERS):
+                x = conv1d_strided(x, *W(j), stride=DISC_P_STRIDE, lengths=ls[j], in_slope=LRELU_SLOPE if j else 1.0)
+                fm.append(x)
+            x = conv1d(x, *W(DISC_P_STRIDED_LAYERS), lengths=ls[-1], in_slope=LRELU_SLOPE)
+            fm.append(x)
+            x = conv1d(x, *W(DISC_P_STRIDED_LAYERS + 1), lengths=ls[-1], in_slope=LRELU_SLOPE)
+            fm.append(x)
+            scores.append(x)
+            fmaps.append(fm)
+            lens.append(ls[1:] + [ls[-1], ls[-1]])
+            Rs.append(B * p)
+        return MPDOutput(scores, fmaps, lens, Rs)
+
+    __call__ = forward
+
+
+def discriminator_loss(out):
+    """reference sr/models.py:363-374 on an MPDOutput of D(y, y_hat.detach()) -> (loss, r_losses, g_losses): loss = the sum over
+    the discriminators of mean((1 - score_real)^2) + mean(score_gen^2) over the valid scores; r_losses / g_losses: device tensors
+    [number of periods] (no host copy, no sync).  One forward and one backward launch over the scores."""
+    total, vals = gan_loss(DISC, out.scores, [ls[5] for ls in out.lens], out.R)
+    return total, vals[0], vals[1]
+
+
+def generator_loss(out):
+    """reference sr/models.py:377-383 -> (loss, gen_losses): the sum over the discriminators of mean((1 - score_gen)^2)"""
+    total, vals = gan_loss(GEN, out.scores, [ls[5] for ls in out.lens], out.R)
+    return total, vals[0]
+
+
+def feature_loss(out):
+    """reference sr/models.py:352-360 -> loss = 2 * the sum over all 6 maps of every discriminator of mean |fmap_real - fmap_gen|
+    over the valid positions, fmap = the leaky ReLU (0.1) of maps 0 .. 4 and conv_post's output as it is.  One forward and one
+    backward launch over all maps."""
+    maps = [m for fm in out.fmaps for m in fm]
+    lens = [t for ls in out.lens for t in ls]
+    R = [r for r, fm in zip(out.R, out.fmaps) for _ in fm]
+    slopes = [LRELU_SLOPE if j < len(fm) - 1 else 1.0 for fm in out.fmaps for j in range(len(fm))]
+    return gan_loss(FM, maps, lens, R, slopes)[0]

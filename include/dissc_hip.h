@@ -918,6 +918,44 @@ int dissc_tanh_fwd(const float* x, float* y, const int32_t* lengths, int B, int 
 int dissc_tanh_bwd(const float* y, const float* gy, float* gx, const int32_t* lengths, int B, int C, int ldx, int ldy, int Lmax,
                    void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * The GAN losses on paired, ragged, pre-activation maps (csrc/gan_loss.hip; composed in dissc_amd/nn.py's
+ * MultiPeriodDiscriminator, discriminator_loss, generator_loss and feature_loss; reference sr/models.py:352-383).  Added without
+ * an ABI bump, as the sections above.
+ *   A paired map is f32 [2 R][C][ld], 16-byte aligned, ld a multiple of 4: rows 0 .. R - 1 the real half, rows R .. 2 R - 1 the
+ *   generated half, row r and row R + r with lengths[r] valid positions (i32 [R] on the device, clamped to 0 .. ld).  Positions at
+ *   or beyond a length are never read for their value.  With v the valid positions and N = C sum_r lengths[r], a map's values are
+ *     DISSC_GANLOSS_FM    2 / N sum_v |lrelu(real, slope) - lrelu(gen, slope)|            (feature_loss's term, times its 2)
+ *     DISSC_GANLOSS_DISC  1 / N sum_v (1 - real)^2   and   1 / N sum_v gen^2              (discriminator_loss's r and g terms)
+ *     DISSC_GANLOSS_GEN   1 / N sum_v (1 - gen)^2                                         (generator_loss's term)
+ *   torch.mean of the reference at equal lengths.  N = 0: value 0, gradient 0.
+ * All array arguments are HOST arrays of n entries (1 <= n <= DISSC_GANLOSS_MAX_MAPS), one per map: the map and lengths DEVICE
+ *   pointers, R, C, ld, the op and the leaky ReLU's slope (read by FM only).  The records travel in the kernels' arguments:
+ *   nothing is uploaded per call.  Anything else (a null pointer, n outside its range, R or C below 1, ld no positive multiple
+ *   of 4, a map above 2^30 float4s per half, an unknown op) is DISSC_EINVAL with a message, before any launch.
+ * dissc_ganloss_workspace_bytes: HOST ONLY, a function of the shapes alone (two doubles per workgroup of 1024 float4s per half,
+ *   rounded up to 256 bytes); 0 on a bad argument.
+ * dissc_ganloss_forward: out f32 [1 + 2 n] on the device: out[1 + m] and out[1 + n + m] are map m's first and second value
+ *   (the second is 0 unless DISC), out[0] the sum of all of them in index order.  Stage 1 leaves one partial per workgroup in the
+ *   workspace, stage 2 (one workgroup) sums each map's partials: lane l the partials l, l + 64, ... in index order, then a fixed
+ *   butterfly.  Sums in double, no atomics: bit-reproducible, and a map's values do not depend on the list it is in.
+ * dissc_ganloss_backward: gmaps[m] (DEVICE, [2 R][C][ld], or NULL = skip the map) receives the gradient with respect to the
+ *   pre-activation map, both halves, exact zeros at and beyond every length.  The cotangent of map m's values is
+ *   g_total[0] + g_vals[m] and g_total[0] + g_vals[n + m] (device pointers; either may be NULL = 0, not both).  The leaky ReLU's
+ *   derivative is the slope at 0 (torch's rule), sign(0) = 0 (torch's abs); one rounding per element.
+ * ------------------------------------------------------------------------- */
+#define DISSC_GANLOSS_MAX_MAPS 64
+#define DISSC_GANLOSS_FM 0
+#define DISSC_GANLOSS_DISC 1
+#define DISSC_GANLOSS_GEN 2
+size_t dissc_ganloss_workspace_bytes(int n, const int* R, const int* C, const int* ld);
+int dissc_ganloss_forward(int n, const float* const* maps, const int32_t* const* lengths, const int* R, const int* C,
+                          const int* ld, const int* ops, const float* slopes, float* out, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int dissc_ganloss_backward(int n, const float* const* maps, const int32_t* const* lengths, const int* R, const int* C,
+                           const int* ld, const int* ops, const float* slopes, const float* g_total, const float* g_vals,
+                           float* const* gmaps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,13 @@ to the bytes they must move (every operand read once, every result written once)
 Step: forward + 45 x mel L1 + backward of nn.CodeGenerator against the same model in eager torch (torch._weight_norm -- what
 weight_norm's hook evaluates --, F.embedding, F.conv1d / conv_transpose1d, F.l1_loss of torch log-mels) with the same weights,
 `--steps` steps each after a warm-up; and the number of GPU kernels one step of each launches (torch.profiler's device
-activities; null where the profiler gives none).  One JSON line per figure; --markdown adds the tables of profiles/gen_train.md."""
+activities; null where the profiler gives none).  One JSON line per figure; --markdown adds the tables of profiles/gen_train.md.
+
+    python tools/gen_train_bench.py --mpd [--batch 32] [--frames 28] [--launches 1000] [--steps 50] [--markdown]
+
+times the period half of the GAN step instead (mpd_bench below; profiles/mpd_train.md): the fused loss launches of
+csrc/gan_loss.hip on the 30 paired maps of nn.MultiPeriodDiscriminator, and the discriminator's and the generator's period-side
+steps against the reference's MultiPeriodDiscriminator and loss functions in eager torch."""
 import argparse
 import ctypes
 import json
@@ -23,6 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 DEV = "cuda:0"
+MIN_WINDOW_MS = 200.0  # --mpd: the least a timed window of loss launches covers
 
 
 def timed(fn, iters):
@@ -66,6 +73,142 @@ def torch_mel(y, basis, window, n_fft=1024, hop=256):
     return torch.log(torch.clamp(torch.matmul(basis, torch.sqrt(spec.pow(2).sum(-1) + 1e-9)), min=1e-5))
 
 
+def mpd_bench(a):
+    """--mpd: the period half of the GAN step at the trainer's shape (32 segments of 8 960 samples, the five periods): the two
+    fused loss launches on the 30 paired maps next to the bytes they must move, the discriminator's step and the generator's
+    period-side step (down to y_hat.grad, param_grads both ways) against eager torch on the same GPU with the same weights."""
+    import gan_loss_ref as GL
+    import mpd_cases as M
+    from dissc_amd import nn
+    from dissc_amd._lib import check, lib
+    F = torch.nn.functional
+    B, T = a.batch, 320 * a.frames
+    sd = M.mpd_state_dict(0)
+    D = nn.MultiPeriodDiscriminator().to(DEV)
+    D.load_state_dict(sd)
+    y, y_hat = (t.to(DEV) for t in M.wav_pair(1, B, T))
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    rows = []
+
+    # ---- the loss launches, straight through the C ABI on the maps of one forward ----
+    with torch.no_grad():
+        out = D(y, y_hat)
+    torch.cuda.synchronize()
+    fm_maps = [m for fm in out.fmaps for m in fm]
+    fm_lens = [t for ls in out.lens for t in ls]
+    fm_R = [r for r in out.R for _ in range(6)]
+    fm_slopes = [0.1 if j < 5 else 1.0 for _ in out.R for j in range(6)]
+    sc_lens = [ls[5] for ls in out.lens]
+
+    def launches(tag, op, maps, lens, R, slopes, halves_read):
+        n = len(maps)
+        args = nn._GanLossArgs([op] * n, maps, lens, R, slopes)
+        nws = nn.ganloss_workspace_bytes(R, [m.shape[1] for m in maps], [m.shape[2] for m in maps])
+        ws, res = torch.empty(nws, dtype=torch.uint8, device=DEV), torch.empty(1 + 2 * n, device=DEV)
+        gmaps = [torch.empty_like(m) for m in maps]
+        pg = (ctypes.c_void_p * n)(*[g.data_ptr() for g in gmaps])
+        one = torch.ones((), device=DEV)
+        fwd = lambda: check(lib.dissc_ganloss_forward(*args.head(), p(res), p(ws), nws, None))
+        bwd = lambda: check(lib.dissc_ganloss_backward(*args.head(), p(one), None, pg, None))
+        timed(fwd, 3), timed(bwd, 3)
+        # valid elements of ONE half: C sum(lens[:R]); the forward reads halves_read halves, the backward reads them and writes both
+        half = sum(m.shape[1] * int(l[:r].sum()) for m, l, r in zip(maps, lens, R))
+        for what, fn, mb in ((f"{tag} forward, {n} maps, stage 1 + stage 2", fwd, 4e-6 * halves_read * half),
+                             (f"{tag} backward, {n} maps, one launch", bwd, 4e-6 * (halves_read + 2) * half)):
+            calls = a.launches
+            ms = timed(fn, calls)
+            if ms * calls < MIN_WINDOW_MS:  # a launch of a few us: time enough of them to fill the window
+                calls = int(MIN_WINDOW_MS / ms) + 1
+                ms = timed(fn, calls)
+            rows.append(row(what, ms, mb, {"calls": calls, "window_ms": round(ms * calls, 1)}))
+
+    launches("feature_loss (FM)", nn.FM, fm_maps, fm_lens, fm_R, fm_slopes, 2)
+    launches("discriminator_loss (DISC)", nn.DISC, out.scores, sc_lens, out.R, [1.0] * 5, 2)
+    launches("generator_loss (GEN)", nn.GEN, out.scores, sc_lens, out.R, [1.0] * 5, 1)
+    del out, fm_maps
+
+    # ---- eager torch: the reference's MultiPeriodDiscriminator (sr/models.py:228-286) in its batch form, the same weights ----
+    P = {k: t.to(DEV).requires_grad_(True) for k, t in sd.items()}
+
+    def torch_mpd(wav, grads):
+        scores, fmaps = [], []
+        for i, period in enumerate(M.PERIODS):
+            x = wav
+            if T % period:
+                x = F.pad(x, (0, period - T % period), "reflect")
+            x = x.view(x.shape[0], 1, -1, period)
+            fm = []
+            for j, (name, _, _, k) in enumerate(M.LAYERS):
+                pre = f"discriminators.{i}.{name}"
+                v, g, b = (P[pre + s] if grads else P[pre + s].detach() for s in (".weight_v", ".weight_g", ".bias"))
+                x = F.conv2d(x, torch._weight_norm(v, g, 0), b, stride=(3, 1) if j < 4 else 1, padding=((k - 1) // 2, 0))
+                if j < 5:
+                    x = F.leaky_relu(x, 0.1)
+                fm.append(x)
+            scores.append(torch.flatten(x, 1, -1))
+            fmaps.append(fm)
+        return scores, fmaps
+
+    def torch_d_step():
+        for t in P.values():
+            t.grad = None
+        (s_r, _), (s_g, _) = torch_mpd(y, True), torch_mpd(y_hat, True)
+        loss = GL.literal_discriminator_loss(s_r, s_g)[0]
+        loss.backward()
+        return loss
+
+    def ours_d_step():
+        D.zero_grad()
+        loss = nn.discriminator_loss(D(y, y_hat))[0]
+        loss.backward()
+        return loss
+
+    yh_o, yh_t = y_hat.clone().requires_grad_(True), y_hat.clone().requires_grad_(True)
+
+    def torch_g_step(grads=True):
+        yh_t.grad = None
+        for t in P.values():
+            t.grad = None
+        (_, f_r), (s_g, f_g) = torch_mpd(y, grads), torch_mpd(yh_t, grads)
+        loss = GL.literal_feature_loss(f_r, f_g) + GL.literal_generator_loss(s_g)[0]
+        loss.backward()
+        return loss
+
+    def ours_g_step(param_grads=True):
+        yh_o.grad = None
+        D.zero_grad()
+        out = D(y, yh_o, param_grads=param_grads)
+        loss = nn.feature_loss(out) + nn.generator_loss(out)[0]
+        loss.backward()
+        return loss
+
+    steps = []
+    for tag, ours, ref in (("D step: D(y, y_hat.detach()), discriminator_loss, backward", ours_d_step, torch_d_step),
+                           ("G step, param_grads=True: D(y, y_hat), feature_loss + generator_loss, backward to y_hat", ours_g_step, torch_g_step),
+                           ("G step, param_grads=False (torch: detached parameters)", lambda: ours_g_step(False), lambda: torch_g_step(False))):
+        lo, lt = float(ours().detach()), float(ref().detach())
+        gd = None
+        if ours is not ours_d_step:
+            gd = float(f"{float((yh_o.grad - yh_t.grad).norm() / yh_t.grad.norm()):.2e}")
+        timed(ours, 3), timed(ref, 3)
+        ts = []
+        for _ in range(2):  # the two alternate: other work shares the machine
+            ts.append((timed(ours, a.steps), timed(ref, a.steps)))
+        s = {"what": tag, "batch": B, "samples": T, "ours_ms": round(min(t[0] for t in ts), 3), "torch_ms": round(min(t[1] for t in ts), 3),
+             "ours_ms_runs": [round(t[0], 3) for t in ts], "torch_ms_runs": [round(t[1], 3) for t in ts], "loss_ours": lo, "loss_torch": lt,
+             "y_hat_grad_rel_diff": gd, "ours_kernels": kernel_count(ours), "torch_kernels": kernel_count(ref)}
+        print(json.dumps(s), flush=True)
+        steps.append(s)
+    if a.markdown:
+        print("\n| launch | calls timed | us | MB moved | GB/s |\n|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['what']} | {r['calls']} | {r['us']} | {r['MB']} | {r['GBps']} |")
+        print("\n| step | ours ms | eager torch ms | ours / torch kernels |\n|---|---|---|---|")
+        for s in steps:
+            print(f"| {s['what']} | {s['ours_ms']} | {s['torch_ms']} | {s['ours_kernels']} / {s['torch_kernels']} |")
+    return rows, steps
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -73,9 +216,12 @@ def main(argv=None):
     ap.add_argument("--launches", type=int, default=1000)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--markdown", action="store_true")
+    ap.add_argument("--mpd", action="store_true", help="time the period half of the GAN step (nn.MultiPeriodDiscriminator and the losses)")
     a = ap.parse_args(argv)
     import __graft_entry__ as ge
     ge.build()
+    if a.mpd:
+        return mpd_bench(a)
     import dissc_amd
     import gen_train_ref as GT
     import synthdata as synth
