@@ -1,12 +1,16 @@
 """Differentiable layers for training the vocoder on the MI355X (C ABI ``dissc_convgrad_*``, csrc/conv_grad.hip,
-``dissc_convtgrad_*``, csrc/conv_grad_t.hip, ``dissc_convsgrad_*`` / ``dissc_period_fold_*``, csrc/conv_grad_s.hip, and
-``dissc_ganloss_*``, csrc/gan_loss.hip).
+``dissc_convtgrad_*``, csrc/conv_grad_t.hip, ``dissc_convsgrad_*`` / ``dissc_period_fold_*``, csrc/conv_grad_s.hip,
+``dissc_convggrad_*`` / ``dissc_mean_pool_*``, csrc/conv_grad_g.hip, and ``dissc_ganloss_*``, csrc/gan_loss.hip).
 
     y = nn.conv1d(x, weight, bias, lengths=lengths, dilation=d, in_slope=0.1, add=res)   # a torch.autograd.Function
     y = nn.resblock1(x, weights, k)                                                       # reference sr/models.py:34-41
     y = nn.conv_transpose1d(x, weight, bias, stride=u, lengths=lengths, in_slope=0.1)     # the upsamplers ups[i]
     y = nn.conv1d_strided(x, weight, bias, stride=3, lengths=lengths, in_slope=0.1)       # the period discriminator's layers
     score, fmaps, lens = nn.discriminator_p(wav, weights, period, lengths)                # reference sr/models.py:228-260
+    y = nn.conv1d_grouped(x, weight, bias, stride=4, groups=16, lengths=lengths, in_slope=0.1)  # the scale discriminator's layers
+    pooled, out_lengths = nn.mean_pool(wav, lengths)                                      # AvgPool1d(4, 2, padding=2)
+    score, fmaps, lens = nn.discriminator_s(wav, weights, lengths)                        # reference sr/models.py:285-307
+    nn.wgrad_partials_grouped(...), nn.workspace_bytes_grouped(...)                       # host-only plan queries
     out = nn.MultiPeriodDiscriminator()(y, y_hat, lengths)                                # reference sr/models.py:263-286
     nn.discriminator_loss(out), nn.generator_loss(out), nn.feature_loss(out)              # reference sr/models.py:352-383
 
@@ -17,9 +21,9 @@ MFMA conv kernels, the weight gradient on its own MFMA kernel with fixed-order p
 The weights are a DEVICE tensor and are packed on the device on every call, because they change every step in training.
 No torch compute op on the hot path, no CPU fallback.  First order only.
 
-The three conv layers are one core: a ``_Kind`` describes each (its C entries, the weight layout, the row length of y for a
-row length of x), and one handle cache, one set of checks, ``_forward`` and ``_backward`` work on that description; the three
-autograd Functions differ in their argument lists only.
+The four conv layers are one core: a ``_Kind`` describes each (its C entries, the weight layout, the row length of y for a
+row length of x, whether it has groups), and one handle cache, one set of checks, ``_forward`` and ``_backward`` work on that
+description; the four autograd Functions differ in their argument lists only.
 """
 import ctypes
 
@@ -41,13 +45,14 @@ class _Kind:
     nout(p, ld) of a row of ld inputs as a function of the layer's own parameter p (dilation or stride), and the names its
     messages use"""
 
-    def __init__(self, who, prefix, layout, dims, nout, fwd_args):
+    def __init__(self, who, prefix, layout, dims, nout, fwd_args, grouped=False):
         vp, i32, sz, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
         self.who, self.prefix, self.layout, self.dims, self.nout = who, prefix, layout, dims, nout
+        self.grouped = grouped  # one more create parameter, groups: dims() then reads Cin / groups from the weight
         self.names = {e: f"{prefix}_{e}" for e in _ENTRIES}
         for e, name in self.names.items():
             setattr(self, e, getattr(lib, name))
-        self.create.argtypes = [i32, i32, i32, i32, ctypes.POINTER(vp)]
+        self.create.argtypes = [i32] * (5 if grouped else 4) + [ctypes.POINTER(vp)]
         self.destroy.argtypes, self.destroy.restype = [vp], None
         self.set_weights.argtypes = [vp, vp, vp, vp]
         self.forward.argtypes = fwd_args + [vp, vp, i32, i32, i32, i32, f32, vp]  # ..., y, lengths, B, ldx, ldo, Lmax, slope, stream
@@ -61,30 +66,35 @@ class _Kind:
 
 
 # weight [Cout, Cin, k], p = dilation, forward(h, x, add, ...)  /  weight [Cin, Cout, k], p = stride, forward(h, x, ...)  /
-# weight [Cout, Cin, k], p = stride, forward(h, x, ...)
+# weight [Cout, Cin, k], p = stride, forward(h, x, ...)  /  weight [Cout, Cin / groups, k], p = stride, groups, forward(h, x, ...)
 CONV1D = _Kind("nn.conv1d", "dissc_convgrad", "[Cout, {}, k]", lambda s: (s[1], s[0], s[2]), lambda p, ld: ld, [ctypes.c_void_p] * 3)
 CONV_TRANSPOSE1D = _Kind("nn.conv_transpose1d", "dissc_convtgrad", "[{}, Cout, k]", lambda s: (s[0], s[1], s[2]),
                          lambda p, ld: p * ld, [ctypes.c_void_p] * 2)
 CONV1D_STRIDED = _Kind("nn.conv1d_strided", "dissc_convsgrad", "[Cout, {}, k]", lambda s: (s[1], s[0], s[2]),
                        lambda p, ld: -(-ld // p), [ctypes.c_void_p] * 2)
+CONV1D_GROUPED = _Kind("nn.conv1d_grouped", "dissc_convggrad", "[Cout, {} / groups, k]", lambda s: (s[1], s[0], s[2]),
+                       lambda p, ld: -(-ld // p), [ctypes.c_void_p] * 2, grouped=True)
 
-_handles = {}     # (prefix, Cin, Cout, k, p, device) -> handle; device None: host-only queries
+_handles = {}     # (prefix, Cin, Cout, k, p, device[, groups]) -> handle; device None: host-only queries
 _workspaces = {}  # device -> uint8 tensor, grown on demand (calls on one device are stream-ordered)
 
 
-def _handle(kind, Cin, Cout, k, p, device=None):
+def _handle(kind, Cin, Cout, k, p, device=None, groups=1):
+    """Cin: the layer's input channels (of all groups); groups is part of the key and of the create call of a grouped kind only"""
     key = (kind.prefix, int(Cin), int(Cout), int(k), int(p), None if device is None else torch.device(device))
+    extra = (int(groups),) if kind.grouped else ()
+    key += extra
     h = _handles.get(key)
     if h is None:
         h = ctypes.c_void_p()
-        check(kind.create(key[1], key[2], key[3], key[4], ctypes.byref(h)), kind.names["create"])
+        check(kind.create(key[1], key[2], key[3], key[4], *extra, ctypes.byref(h)), kind.names["create"])
         _handles[key] = h
     return h
 
 
-def _partials(kind, B, Lmax, Cin, Cout, k, p=1):
+def _partials(kind, B, Lmax, Cin, Cout, k, p=1, groups=1):
     P, pairs = ctypes.c_int(0), ctypes.c_int(0)
-    check(kind.partials(_handle(kind, Cin, Cout, k, p), int(B), int(Lmax), ctypes.byref(P), ctypes.byref(pairs)),
+    check(kind.partials(_handle(kind, Cin, Cout, k, p, groups=groups), int(B), int(Lmax), ctypes.byref(P), ctypes.byref(pairs)),
           kind.names["partials"])
     return P.value, pairs.value
 
@@ -124,6 +134,18 @@ def workspace_bytes_strided(B, Lmax, Cin, Cout, k, stride):
     return int(CONV1D_STRIDED.workspace_bytes(_handle(CONV1D_STRIDED, Cin, Cout, k, stride), int(B), int(Lmax)))
 
 
+def wgrad_partials_grouped(B, Lmax, Cin, Cout, k, stride, groups):
+    """wgrad_partials for conv1d_grouped's weight gradient [Cout, Cin / groups, k]: Lmax is in INPUT positions, the chunks are
+    WGRAD_CHUNK OUTPUT positions, ceil(ceil(Lmax / stride) / WGRAD_CHUNK) per utterance; the partials take at most 56 MB.
+    A function of the shape only (host only)."""
+    return _partials(CONV1D_GROUPED, B, Lmax, Cin, Cout, k, stride, groups)
+
+
+def workspace_bytes_grouped(B, Lmax, Cin, Cout, k, stride, groups):
+    """bytes of conv1d_grouped's backward workspace (host only)"""
+    return int(CONV1D_GROUPED.workspace_bytes(_handle(CONV1D_GROUPED, Cin, Cout, k, stride, groups=groups), int(B), int(Lmax)))
+
+
 def _workspace(device, nbytes):
     ws = _workspaces.get(device)
     if ws is None or ws.numel() < nbytes:
@@ -143,12 +165,14 @@ def _lengths_ok(lengths, B):
                                and tuple(lengths.shape) == (B,))
 
 
-def _check_layer(kind, x, weight, bias, lengths):
-    """the refusals both conv layers share; -> Cout"""
+def _check_layer(kind, x, weight, bias, lengths, groups=1):
+    """the refusals every conv layer shares; -> Cout"""
     _check_act(x, "x", who=kind.who)
     B, Cin, _ = x.shape
+    if groups < 1 or (groups != 1 and not kind.grouped):
+        raise DisscError(f"{kind.who}: groups = {groups}")
     if not (weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 3 and weight.is_contiguous()
-            and kind.dims(weight.shape)[0] == Cin):
+            and kind.dims(weight.shape)[0] * groups == Cin):
         raise DisscError(f"{kind.who}: weight must be a contiguous fp32 device tensor {kind.layout.format(Cin)}")
     Cout = kind.dims(weight.shape)[1]
     if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous()
@@ -163,12 +187,12 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def _forward(kind, ctx, x, weight, bias, lengths, p, in_slope, *add):
+def _forward(kind, ctx, x, weight, bias, lengths, p, in_slope, *add, groups=1):
     """set_weights, the output (zeros where lengths, or a row longer than its outputs, leave part of it unwritten), forward;
     saves x and weight, never y"""
-    B, _, ld = x.shape
-    Cin, Cout, k = kind.dims(weight.shape)
-    h = _handle(kind, Cin, Cout, k, p, x.device)
+    B, Cin, ld = x.shape
+    _, Cout, k = kind.dims(weight.shape)
+    h = _handle(kind, Cin, Cout, k, p, x.device, groups)
     st = current_stream_ptr(x.device)
     ldo = kind.ldo(p, ld)
     with torch.cuda.device(x.device):
@@ -177,21 +201,21 @@ def _forward(kind, ctx, x, weight, bias, lengths, p, in_slope, *add):
             torch.empty((B, Cout, ldo), dtype=torch.float32, device=x.device)
         check(kind.forward(h, _ptr(x), *map(_ptr, add), _ptr(y), _ptr(lengths), B, ld, ldo, ld, in_slope, st), kind.names["forward"])
     ctx.save_for_backward(x, weight)
-    ctx.lengths, ctx.p, ctx.in_slope, ctx.has_bias = lengths, p, in_slope, bias is not None
+    ctx.lengths, ctx.p, ctx.in_slope, ctx.has_bias, ctx.groups = lengths, p, in_slope, bias is not None, groups
     return y
 
 
 def _backward(kind, ctx, gy):
     """-> (gx, gw, gb, gy made contiguous) for the inputs 0 .. 2 that need a gradient, None for the others"""
     x, weight = ctx.saved_tensors
-    B, _, ld = x.shape
-    Cin, Cout, k = kind.dims(weight.shape)
+    B, Cin, ld = x.shape
+    _, Cout, k = kind.dims(weight.shape)
     need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
     need_b = ctx.has_bias and ctx.needs_input_grad[2]
     gy = gy.contiguous()
     gx = gw = gb = ws = None
     if need_x or need_w or need_b:
-        h = _handle(kind, Cin, Cout, k, ctx.p, x.device)
+        h = _handle(kind, Cin, Cout, k, ctx.p, x.device, ctx.groups)
         st = current_stream_ptr(x.device)
         with torch.cuda.device(x.device):
             if need_x:  # another layer sharing the handle may have run since the forward: pack again (device only)
@@ -285,6 +309,32 @@ def conv1d_strided(x, weight, bias=None, stride=2, lengths=None, in_slope=1.0):
     gradient of x is zero from lengths[b] on.  Gradients flow to x, weight and bias; x and weight are saved, y is not."""
     _check_layer(CONV1D_STRIDED, x, weight, bias, lengths)
     return _Conv1dStridedFn.apply(x, weight, bias, lengths, int(stride), float(in_slope))
+
+
+class _Conv1dGroupedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, lengths, stride, groups, in_slope):
+        return _forward(CONV1D_GROUPED, ctx, x, weight, bias, lengths, stride, in_slope, groups=groups)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return _backward(CONV1D_GROUPED, ctx, gy)[:3] + (None, None, None, None)
+
+
+def conv1d_grouped(x, weight, bias=None, stride=1, groups=1, lengths=None, in_slope=1.0):
+    """y = bias + Conv1d(lrelu(x, in_slope), weight, stride=stride, padding=(k - 1) // 2, groups=groups): the grouped, wide-tap
+    layers of the scale discriminator (reference sr/models.py:289-294).
+
+    x [B, Cin, ld]: contiguous fp32 device tensor, ld % 4 == 0; y [B, Cout, ceil4(ceil(ld / stride))].  weight: DEVICE tensor
+    [Cout, Cin / groups, k], k odd, 3 <= k <= 41, stride 1, 2 or 4, Cin / groups 1 or a multiple of 8 up to 64, Cout / groups a
+    multiple of 16 up to 128; bias [Cout] or None.  lengths: int32 [B] on the device (or None = ld), INPUT lengths: utterance b
+    has ceil(lengths[b] / stride) valid output positions (torch's count for that input), x is read as zero from lengths[b] on, y
+    is left zero beyond its length and the incoming gradient is read as zero there; the gradient of x is zero from lengths[b]
+    on.  Gradients flow to x, weight and bias; x and weight are saved, y is not."""
+    groups = int(groups)
+    _check_layer(CONV1D_GROUPED, x, weight, bias, lengths, groups)
+    return _Conv1dGroupedFn.apply(x, weight, bias, lengths, int(stride), groups, float(in_slope))
 
 
 def resblock1(x, weights, k, dilations=(1, 3, 5), lengths=None, taps=None):
@@ -427,6 +477,94 @@ def discriminator_p(wav, weights, period, lengths=None):
     x = conv1d(x, *W(f"convs.{DISC_P_STRIDED_LAYERS}"), lengths=lens[-1], in_slope=LRELU_SLOPE)
     fmaps.append(x)
     x = conv1d(x, *W("conv_post"), lengths=lens[-1], in_slope=LRELU_SLOPE)
+    fmaps.append(x)
+    return x, fmaps, lens[1:] + [lens[-1], lens[-1]]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The scale discriminator (reference sr/models.py:285-307): six conv1d_grouped, two conv1d; the average pool between the scales
+# (C ABI dissc_mean_pool_*, csrc/conv_grad_g.hip).
+# ---------------------------------------------------------------------------------------------------------------------
+lib.dissc_mean_pool_fwd.argtypes = lib.dissc_mean_pool_bwd.argtypes = \
+    [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+# (stride, groups) of convs.0 .. convs.5, reference sr/models.py:289-294; convs.6 and conv_post are plain conv1d layers
+DISC_S_GROUPED = [(1, 1), (2, 4), (2, 16), (4, 16), (4, 16), (1, 16)]
+
+
+class _MeanPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wav, lengths):
+        B, T = wav.shape[0], wav.shape[-1]
+        ldo = _ceil4(T // 2 + 1)
+        out = torch.zeros((B, 1, ldo), dtype=torch.float32, device=wav.device)
+        with torch.cuda.device(wav.device):
+            check(lib.dissc_mean_pool_fwd(_ptr(wav), _ptr(out), _ptr(lengths), B, 1, T, T, ldo, current_stream_ptr(wav.device)),
+                  "dissc_mean_pool_fwd")
+        ctx.lengths, ctx.shape = lengths, tuple(wav.shape)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = g.contiguous()
+        B, T = ctx.shape[0], ctx.shape[-1]
+        gwav = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            check(lib.dissc_mean_pool_bwd(_ptr(g), _ptr(gwav), _ptr(ctx.lengths), B, 1, T, T, g.shape[2], current_stream_ptr(g.device)),
+                  "dissc_mean_pool_bwd")
+        return gwav, None
+
+
+def mean_pool(wav, lengths=None):
+    """(pooled [B, 1, ceil4(T // 2 + 1)], out_lengths) from wav [B, 1, T] or [B, T] with lengths[b] valid samples (a list, an
+    array or a tensor on either side; None = T): AvgPool1d(4, 2, padding=2) between the scales (reference sr/models.py:315),
+    every utterance zero-padded at ITS OWN end.  pooled[b][j] = ((w[2j - 2] + w[2j - 1]) + (w[2j] + w[2j + 1])) / 4 for
+    j <= n // 2, zero beyond; out_lengths: host int64 [B], n // 2 + 1 (0 for n = 0).  The gradient of wav is the gather form (no
+    atomics) and is zero from lengths[b] on."""
+    who = "nn.mean_pool"
+    _check_wav(wav, who)
+    B, T = wav.shape[0], wav.shape[-1]
+    ln = _host_lengths(lengths, B, T, who)
+    dev_len = lengths if isinstance(lengths, torch.Tensor) and lengths.is_cuda else None
+    if lengths is not None and dev_len is None:
+        dev_len = torch.from_numpy(ln.astype(np.int32)).to(wav.device)
+    if not _lengths_ok(dev_len, B):
+        raise DisscError(f"{who}: device lengths must be a contiguous int32 tensor [B]")
+    return _MeanPoolFn.apply(wav, dev_len), np.where(ln > 0, ln // 2 + 1, 0)
+
+
+def discriminator_s(wav, weights, lengths=None):
+    """DiscriminatorS (reference sr/models.py:285-307) of wav [B, 1, T] or [B, T] with lengths[b] valid samples (host counts; a
+    device tensor is copied back) -> (score, fmaps, lens).
+
+    weights: {"convs.<i>.weight" / ".bias" (i = 0 .. 6), "conv_post.weight" / ".bias"}, device tensors with the norm (weight or
+    spectral) already folded.  Composed as six conv1d_grouped (k = 15, then k = 41 with strides 2, 2, 4, 4, 1 and 4, 16, 16, 16,
+    16 groups; the first with in_slope = 1), conv1d (k = 5) and conv1d (k = 3) with in_slope = 0.1: no torch compute op on the
+    path.  A waveform whose T is no multiple of 4 is copied once into a zeroed row of ceil4(T) samples (allocation and copy;
+    autograd slices the gradient back).  fmaps: the eight feature maps [B, C, ld_l], PRE-ACTIVATION and zero beyond their
+    lengths, the contract of discriminator_p's.  score: the last map, [B, 1, ld].  lens: the eight maps' device lengths, int32
+    [B] each: n, ceil(n / 2), ceil(/ 2), ceil(/ 4), ceil(/ 4), then unchanged three times."""
+    who = "nn.discriminator_s"
+    _check_wav(wav, who)
+    B, T = wav.shape[0], wav.shape[-1]
+    ln = _host_lengths(lengths, B, T, who)
+    rows = [ln]  # the input lengths of convs.0 .. convs.5, then of the three stride-1 layers behind them
+    for s, _ in DISC_S_GROUPED:
+        rows.append(-(-rows[-1] // s))
+    flat = torch.from_numpy(np.concatenate(rows).astype(np.int32)).to(wav.device)  # every layer's lengths in one upload
+    lens = [flat[i * B:(i + 1) * B] for i in range(len(rows))]
+    x = wav.reshape(B, 1, T)
+    if T % 4:
+        x = torch.zeros((B, 1, _ceil4(T)), dtype=torch.float32, device=wav.device)
+        x[:, :, :T] = wav.reshape(B, 1, T)
+    fmaps = []
+    for i, (s, g) in enumerate(DISC_S_GROUPED):
+        x = conv1d_grouped(x, weights[f"convs.{i}.weight"], weights.get(f"convs.{i}.bias"), stride=s, groups=g, lengths=lens[i],
+                           in_slope=LRELU_SLOPE if i else 1.0)
+        fmaps.append(x)
+    x = conv1d(x, weights["convs.6.weight"], weights.get("convs.6.bias"), lengths=lens[-1], in_slope=LRELU_SLOPE)
+    fmaps.append(x)
+    x = conv1d(x, weights["conv_post.weight"], weights.get("conv_post.bias"), lengths=lens[-1], in_slope=LRELU_SLOPE)
     fmaps.append(x)
     return x, fmaps, lens[1:] + [lens[-1], lens[-1]]
 

@@ -857,6 +857,58 @@ int dissc_period_fold_bwd(const float* gx0, const int32_t* lengths, int B, int T
                           void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * A differentiable, ragged, GROUPED, strided, wide-tap Conv1d layer (csrc/conv_grad_g.hip): the first six layers of every
+ * DiscriminatorS (reference sr/models.py:285-307; k = 15 and 41, stride 1, 2 or 4, up to 16 groups), which the three sections
+ * above cannot run.  Added without an ABI bump, as those were.
+ *   y[b,co,q] = bias[co] + sum_{ci in group(co)} sum_kk w[co,ci,kk] lrelu(x, in_slope)[b,ci,stride q + kk - pad],
+ *   pad = (k - 1) / 2: torch's F.conv1d(..., stride, padding=pad, groups).  Rows, lengths and strides as dissc_convsgrad_*: x f32
+ *   [B][Cin][ldx], y / gy f32 [B][Cout][ldo], 16-byte aligned, ldx and ldo multiples of 4, ldx >= Lmax, ldo >= ceil(Lmax /
+ *   stride); lengths i32 [B] on the device or NULL (= Lmax) and Lmax are INPUT positions, utterance b has ceil(lengths[b] /
+ *   stride) outputs; input at and beyond lengths[b] is read as zero, y is never written at or beyond the output length and gy
+ *   is read as zero there.
+ * dissc_convggrad_create: HOST ONLY.  Accepted: k odd, 3 <= k <= 41; stride 1, 2 or 4; groups >= 1 dividing Cin and Cout;
+ *   Cin / groups either 1 or a multiple of 8 up to 64; Cout / groups a multiple of 16 up to 128; 1 <= Cin, Cout <= 65535.
+ *   Anything else is DISSC_EINVAL with a message that starts with the entry's name and names the rule.
+ * dissc_convggrad_set_weights: w_dev f32 [Cout][Cin / groups][k] and bias_dev f32 [Cout] (NULL = no bias) are DEVICE pointers;
+ *   one kernel packs the A fragments of the forward and of the data gradient.  Call it again whenever the weights changed.
+ * dissc_convggrad_packed: the packings, for tests.  Taps are indexed by o' = kk - pad + PO, PO = pad rounded up to 4, four to a
+ *   float4.  which = 0: the forward's, [groups][Cout / groups / 16][ceil(Cin / groups / 4)][K4 = (PO + pad) / 4 + 1][64][4]
+ *   floats, element (g, rt, c4, k4, lane, e) = w[co = g cog + 16 rt + lane % 16][ci = 4 c4 + lane / 16][kk = 4 k4 + e - PO + pad];
+ *   which = 1: the data gradient's, [groups][ceil(Cin / groups / 16)][Cout / groups / 4][K4][64][4], = w[co = g cog + 4 c4 +
+ *   lane / 16][ci = 16 rt + lane % 16][kk]; zero outside the weights.  Returns the number of floats (HOST ONLY with dst_dev
+ *   NULL), after copying them to dst_dev otherwise; negative on error.
+ * dissc_convggrad_forward: one implicit-GEMM kernel per group on v_mfma_f32_16x16x4_f32, four accumulators per output added in a
+ *   fixed order (Cin / groups = 1 included, on zero-padded tiles).
+ * dissc_convggrad_partials / _workspace_bytes: HOST ONLY, as dissc_convsgrad_*: Lmax in INPUT positions, chunks of
+ *   DISSC_CONVGRAD_CHUNK OUTPUT positions; the partials take at most 56 MB.
+ * dissc_convggrad_backward: gx f32 [B][Cin][ldx] (times the leaky ReLU's derivative, torch's rule at x = 0; zero from
+ *   lengths[b] to ldx), gw f32 [Cout][Cin / groups][k], gb f32 [Cout]; each may be NULL and its kernels are skipped.  No
+ *   atomics, fixed summation orders: bit-reproducible, and an utterance's y and gx depend neither on the batch it is in nor on
+ *   the row strides.
+ *
+ * The average pool between the scales, AvgPool1d(4, 2, padding=2) with count_include_pad (reference sr/models.py:315-318), on
+ * B C rows x f32 [B][C][ldx] with lengths[b] (i32 on the device, or NULL = T) valid samples, each zero-padded at its own end.
+ * dissc_mean_pool_fwd: out[j] = ((x[2 j - 2] + x[2 j - 1]) + (x[2 j] + x[2 j + 1])) * 0.25f for j <= floor(n / 2) (n >= 1;
+ *   n = 0 has no output); nothing is written beyond.  ldx >= T, ldo >= T / 2 + 1, B C <= 65535.
+ * dissc_mean_pool_bwd: gx[i] = 0.25f * (gy[floor(i / 2)] + gy[floor(i / 2) + 1]), gy read as zero at and beyond the output
+ *   length; zero from lengths[b] to ldx.  The gather form: no atomics.
+ * ------------------------------------------------------------------------- */
+typedef struct dissc_convggrad* dissc_convggrad_t;
+int dissc_convggrad_create(int Cin, int Cout, int k, int stride, int groups, dissc_convggrad_t* out);
+void dissc_convggrad_destroy(dissc_convggrad_t h);
+int dissc_convggrad_set_weights(dissc_convggrad_t h, const float* w_dev, const float* bias_dev, void* stream);
+long long dissc_convggrad_packed(dissc_convggrad_t h, int which, float* dst_dev, void* stream);
+int dissc_convggrad_forward(dissc_convggrad_t h, const float* x, float* y, const int32_t* lengths, int B, int ldx, int ldo,
+                            int Lmax_in, float in_slope, void* stream);
+int dissc_convggrad_partials(dissc_convggrad_t h, int B, int Lmax_in, int* P, int* pairs_per_partial);
+size_t dissc_convggrad_workspace_bytes(dissc_convggrad_t h, int B, int Lmax_in);
+int dissc_convggrad_backward(dissc_convggrad_t h, const float* x, const float* gy, const int32_t* lengths, int B, int ldx,
+                             int ldo, int Lmax_in, float in_slope, float* gx, float* gw, float* gb, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int dissc_mean_pool_fwd(const float* x, float* out, const int32_t* lengths, int B, int C, int T, int ldx, int ldo, void* stream);
+int dissc_mean_pool_bwd(const float* gy, float* gx, const int32_t* lengths, int B, int C, int T, int ldx, int ldo, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The rest of the generator's training step (csrc/gen_train.hip; composed in dissc_amd/nn.py's CodeGenerator): weight norm
  * of every layer at once, the embeddings, the MRF mean, the tanh tail.  Added without an ABI bump, as the sections above.
  * All device pointers f32 unless said otherwise; no atomics, fixed summation orders: bit-reproducible.

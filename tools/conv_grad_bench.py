@@ -25,6 +25,14 @@ The same for the strided Conv1d (nn.conv1d_strided, csrc/conv_grad_s.hip) on the
 trainer's shape, 32 segments of 8 960 samples folded to 32 p rows of ceil(8 960 / p) columns, against torch's leaky_relu +
 conv1d(stride=3) autograd on the rows' valid part: the table of profiles/conv_strided_grad.md.  TFLOP/s of the direct form's
 MACs, Cin Cout k per OUTPUT position (Cin = 1 executes 8 channels in the forward and 32 in the gradients).
+
+    python tools/conv_grad_bench.py --grouped [--batch 64] [--samples 8960] [--scales 3] [--iters 50] [--markdown]
+
+The same for the grouped Conv1d (nn.conv1d_grouped, csrc/conv_grad_g.hip) on the six grouped layers of DiscriminatorS at the
+trainer's rows, 64 rows (32 segments x the real and the generated waveform) of 8 960 samples and of the two pooled scales
+(4 481, 2 241), against torch's leaky_relu + conv1d(stride, groups) autograd, and for the pool (nn.mean_pool) against
+F.avg_pool1d: the tables of profiles/conv_grouped_grad.md.  TFLOP/s of the direct form's MACs, (Cin / groups) Cout k per OUTPUT
+position; GB/s of the bytes that have to move (x, y and, for the data gradient, gy, x and gx) for convs.0 and the pool.
 """
 import argparse
 import ctypes
@@ -64,14 +72,15 @@ def executed_flops(cin, cout, k, positions):
     return direct(cout, cin), direct(cin, cout), 2.0 * rup(cout, 32) * 32 * -(-cin // 32) * ng * positions
 
 
-def bench_layer(a, kind, cin, cout, k, p_, L):
-    """one layer through its nn layer kind (nn.CONV1D: p_ = dilation; nn.CONV_TRANSPOSE1D, nn.CONV1D_STRIDED: p_ = stride) and
-    through torch"""
+def bench_layer(a, kind, cin, cout, k, p_, L, groups=1):
+    """one layer through its nn layer kind (nn.CONV1D: p_ = dilation; nn.CONV_TRANSPOSE1D, nn.CONV1D_STRIDED, nn.CONV1D_GROUPED:
+    p_ = stride) and through torch"""
     from dissc_amd import nn
     from dissc_amd._lib import check, current_stream_ptr
     F = torch.nn.functional
     dev = torch.device("cuda:0")
-    tr, sd = kind is nn.CONV_TRANSPOSE1D, kind is nn.CONV1D_STRIDED
+    tr, sd = kind is nn.CONV_TRANSPOSE1D, kind in (nn.CONV1D_STRIDED, nn.CONV1D_GROUPED)
+    cig = cin // groups
     s, d = (p_, 1) if tr or sd else (1, p_)
     B, slope = a.batch, 0.1
     rs = np.random.RandomState(0)
@@ -79,11 +88,11 @@ def bench_layer(a, kind, cin, cout, k, p_, L):
     ldo, nout = kind.ldo(p_, ld), kind.nout(p_, L)  # the row of y / gy, and the outputs of L inputs
     x = torch.from_numpy(rs.standard_normal((B, cin, ld)).astype(np.float32)).to(dev)
     gy = torch.from_numpy(rs.standard_normal((B, cout, ldo)).astype(np.float32)).to(dev)
-    w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k) if tr else (cout, cin, k)) / np.sqrt(cin * k / (s if tr else 1))).astype(np.float32)).to(dev)
+    w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k) if tr else (cout, cig, k)) / np.sqrt(cig * k / (s if tr else 1))).astype(np.float32)).to(dev)
     b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)).to(dev)
     lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
     y, gx, gw, gb = torch.zeros_like(gy), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
-    h = nn._handle(kind, cin, cout, k, p_, dev)
+    h = nn._handle(kind, cin, cout, k, p_, dev, groups)
     st = current_stream_ptr(dev)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
     nws = int(kind.workspace_bytes(h, B, ld))
@@ -101,11 +110,11 @@ def bench_layer(a, kind, cin, cout, k, p_, L):
     conv_bwd = torch.ops.aten.convolution_backward
 
     def torch_bwd(mask):
-        return conv_bwd(gyt, xa, w, [cout], [s], [pad], [d], tr, [0], 1, mask)
+        return conv_bwd(gyt, xa, w, [cout], [s], [pad], [d], tr, [0], groups, mask)
 
     def torch_fwd():
         xl = F.leaky_relu(xt, slope)
-        return F.conv_transpose1d(xl, w, b, stride=s, padding=pad) if tr else F.conv1d(xl, w, b, stride=s, padding=pad, dilation=d)
+        return F.conv_transpose1d(xl, w, b, stride=s, padding=pad) if tr else F.conv1d(xl, w, b, stride=s, padding=pad, dilation=d, groups=groups)
 
     cases = {
         "fwd": lambda: check(kind.forward(h, p(x), *add, p(y), p(lengths), B, ld, ldo, ld, slope, st), "forward"),
@@ -134,8 +143,10 @@ def bench_layer(a, kind, cin, cout, k, p_, L):
     for _ in range(a.blocks):
         for n, fn in cases.items():  # alternating
             times[n].append(timed(fn, a.iters))
-    P, pairs = nn._partials(kind, B, ld, cin, cout, k, p_)
+    P, pairs = nn._partials(kind, B, ld, cin, cout, k, p_, groups)
     out = {"transpose": True} if tr else ({"strided": True} if sd else {})
+    if kind.grouped:
+        out = {"grouped": True, "groups": groups}
     out.update({"cin": cin, "cout": cout, "k": k, "stride" if tr or sd else "dilation": p_, "L": L, "batch": B, "partials": P,
                 "pairs_per_partial": pairs, "workspace_mb": round(nws / 2**20, 2),
                 "rel_diff_to_torch": {n: None if v is None else float(f"{v:.2e}") for n, v in agree.items()}})
@@ -143,7 +154,7 @@ def bench_layer(a, kind, cin, cout, k, p_, L):
         out[n + "_ms"] = round(float(np.median(v)), 4)
         out[n + "_ms_spread"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
     # the transposed layer: the direct form's MACs, Cin Cout k per input position
-    flops = [2.0 * cin * cout * k * B * (nout if sd else L)] * 3 if tr or sd else executed_flops(cin, cout, k, B * L)
+    flops = [2.0 * cig * cout * k * B * (nout if sd else L)] * 3 if tr or sd else executed_flops(cin, cout, k, B * L)
     for n, fl in zip(("fwd", "dgrad", "wgrad"), flops):
         out[n + "_tflops"] = round(fl / (out[n + "_ms"] * 1e-3) / 1e12, 2)
     print(json.dumps(out), flush=True)
@@ -198,6 +209,85 @@ def main_strided(a):
     return rows
 
 
+def bench_pool(a, T):
+    """nn.mean_pool's two kernels through the C ABI against F.avg_pool1d(4, 2, padding=2) and its autograd"""
+    from dissc_amd import nn
+    from dissc_amd._lib import check, current_stream_ptr, lib
+    F = torch.nn.functional
+    dev = torch.device("cuda:0")
+    B, no = a.batch, T // 2 + 1
+    ldo = rup(no, 4)
+    rs = np.random.RandomState(1)
+    x = torch.from_numpy(rs.standard_normal((B, 1, T)).astype(np.float32)).to(dev)
+    g = torch.from_numpy(rs.standard_normal((B, 1, ldo)).astype(np.float32)).to(dev)
+    out, gx = torch.zeros_like(g), torch.empty_like(x)
+    st = current_stream_ptr(dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    xr = x.clone().requires_grad_(True)
+    yr = F.avg_pool1d(xr, 4, 2, padding=2)
+    gr = g[:, :, :no].contiguous()
+    cases = {
+        "fwd": lambda: check(lib.dissc_mean_pool_fwd(p(x), p(out), None, B, 1, T, T, ldo, st), "dissc_mean_pool_fwd"),
+        "torch_fwd": lambda: F.avg_pool1d(x, 4, 2, padding=2),
+        "bwd": lambda: check(lib.dissc_mean_pool_bwd(p(g), p(gx), None, B, 1, T, T, ldo, st), "dissc_mean_pool_bwd"),
+        "torch_bwd": lambda: torch.autograd.grad(yr, xr, gr, retain_graph=True),
+    }
+    cases["fwd"](), cases["bwd"]()
+    agree = {"out": float((out[:, :, :no] - cases["torch_fwd"]()).abs().max()), "gx": float((gx - cases["torch_bwd"]()[0]).abs().max())}
+    for fn in cases.values():
+        timed(fn, 2)
+    times = {n: [] for n in cases}
+    for _ in range(a.blocks):
+        for n, fn in cases.items():
+            times[n].append(timed(fn, a.iters))
+    r = {"pool": True, "T": T, "batch": B, "max_abs_diff_to_torch": agree}
+    for n, v in times.items():
+        r[n + "_ms"] = round(float(np.median(v)), 4)
+    nbytes = 4.0 * B * (T + no)
+    r["fwd_gbs"], r["bwd_gbs"] = (round(nbytes / (r[n] * 1e-3) / 1e9, 1) for n in ("fwd_ms", "bwd_ms"))
+    print(json.dumps(r), flush=True)
+    return r
+
+
+def main_grouped(a):
+    import conv_grouped_ref as RG
+    from dissc_amd import nn
+    rows, pools, T = [], [], a.samples
+    for scale in range(a.scales):
+        L = T
+        for i, (cin, cout, k, s, g) in enumerate(RG.DISC_S):
+            if not a.only or [cin, cout, k] == [int(v) for v in a.only.split(",")]:
+                r = dict(bench_layer(a, nn.CONV1D_GROUPED, cin, cout, k, s, L, g), scale=scale, layer=f"convs.{i}")
+                if i == 0:  # bandwidth bound: x and y forward; gy, x and gx in the data gradient
+                    r["fwd_gbs"] = round(4.0 * a.batch * L * (cin + cout) / (r["fwd_ms"] * 1e-3) / 1e9, 1)
+                    r["dgrad_gbs"] = round(4.0 * a.batch * L * (2 * cin + cout) / (r["dgrad_ms"] * 1e-3) / 1e9, 1)
+                rows.append(r)
+            L = -(-L // s)
+        if scale + 1 < a.scales:
+            pools.append(bench_pool(a, T))
+            T = T // 2 + 1
+    if a.markdown:
+        print("| scale | layer | rows x L in | fwd ms (torch) | dgrad ms (torch) | wgrad ms (torch) | TFLOP/s fwd / dgrad / wgrad | P | repack ms |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['scale']} | {r['layer']}: {r['cin']} -> {r['cout']}, k = {r['k']}, s = {r['stride']}, g = {r['groups']} | "
+                  f"{r['batch']} x {r['L']} | {r['fwd_ms']:.3f} ({r['torch_fwd_ms']:.3f}) | {r['dgrad_ms']:.3f} ({r['torch_dgrad_ms']:.3f}) | "
+                  f"{r['wgrad_ms']:.3f} ({r['torch_wgrad_ms']:.3f}) | {r['fwd_tflops']} / {r['dgrad_tflops']} / {r['wgrad_tflops']} | "
+                  f"{r['partials']} | {r['repack_ms']:.3f} |")
+        for r in rows:
+            if "fwd_gbs" in r:
+                print(f"\nscale {r['scale']} convs.0: forward {r['fwd_gbs']} GB/s, data gradient {r['dgrad_gbs']} GB/s")
+        for r in pools:
+            print(f"\npool {r['batch']} x {r['T']}: fwd {r['fwd_ms']:.4f} ms ({r['torch_fwd_ms']:.4f} torch), {r['fwd_gbs']} GB/s; "
+                  f"bwd {r['bwd_ms']:.4f} ms ({r['torch_bwd_ms']:.4f} torch), {r['bwd_gbs']} GB/s")
+        tot = lambda n: sum(r[n] for r in rows)
+        print(f"\nsum over the listed layers, ours (torch): fwd {tot('fwd_ms'):.2f} ({tot('torch_fwd_ms'):.2f}), "
+              f"dgrad {tot('dgrad_ms'):.2f} ({tot('torch_dgrad_ms'):.2f}), wgrad {tot('wgrad_ms'):.2f} ({tot('torch_wgrad_ms'):.2f}) ms")
+        slower = [(r["scale"], r["layer"], n) for r in rows for n in ("fwd", "dgrad", "wgrad") if r[n + "_ms"] > r["torch_" + n + "_ms"]]
+        print("slower than torch:", slower if slower else "none")
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -208,13 +298,17 @@ def main(argv=None):
     ap.add_argument("--markdown", action="store_true")
     ap.add_argument("--transpose", action="store_true", help="the five ConvTranspose1d upsamplers instead")
     ap.add_argument("--strided", action="store_true", help="the four strided layers of DiscriminatorP instead")
-    ap.add_argument("--samples", type=int, default=8960, help="--strided: samples per segment")
+    ap.add_argument("--grouped", action="store_true", help="the six grouped layers of DiscriminatorS and the pool instead")
+    ap.add_argument("--scales", type=int, default=3, help="--grouped: the scales (each pooled from the one before)")
+    ap.add_argument("--samples", type=int, default=8960, help="--strided, --grouped: samples per segment")
     ap.add_argument("--periods", default="2,11", help="--strided: the periods to fold to")
     a = ap.parse_args(argv)
     if a.transpose:
         return main_transpose(a)
     if a.strided:
         return main_strided(a)
+    if a.grouped:
+        return main_grouped(a)
     import conv_grad_ref as R
     from dissc_amd import nn
     seen, rows = set(), []
