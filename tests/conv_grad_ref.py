@@ -1,5 +1,7 @@
-"""Shared by tests/test_conv_grad_cpu.py and tests/test_gpu_conv_grad.py (not a test module): the float64 / float32 torch
-restatement of dissc_amd.nn's layers, the generator's layer shapes, and the bars the gradients are held to."""
+"""Shared by the tests of dissc_amd.nn's differentiable layers (not a test module): the float64 / float32 torch restatement of
+the four conv layers (one layer_ref over an Op, every utterance alone on its valid part), the row-length and mask helpers, the
+kernels' phase form of the strided and grouped layers (for seeding defects), the ResBlock chain, the generator's layer shapes,
+and the bars the gradients are held to."""
 import collections
 import math
 
@@ -28,25 +30,61 @@ def generator_layer_shapes(frames=28):
     return shapes
 
 
-Op = collections.namedtuple("Op", "apply mul cout_dim")  # apply(lrelu(x), w, b); rows of y per row of x; Cout's dim in w
+# apply(lrelu(x), w, b); out_len(n): the outputs of n valid inputs; Cout's dim in w
+Op = collections.namedtuple("Op", "apply out_len cout_dim")
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def ceil4(n):
+    return (n + 3) // 4 * 4
+
+
+def out_ld(ld, s):
+    """the row length of a stride-s layer's y for a row length ld of x"""
+    return ceil4(cdiv(ld, s))
 
 
 def conv_op(dilation):
-    """F.conv1d, "same" padding: w [Cout, Cin, k]"""
-    return Op(lambda xa, w, b: F.conv1d(xa, w, b, padding=(w.shape[2] - 1) * dilation // 2, dilation=dilation), 1, 0)
+    """F.conv1d, "same" padding: w [Cout, Cin, k], n outputs"""
+    return Op(lambda xa, w, b: F.conv1d(xa, w, b, padding=(w.shape[2] - 1) * dilation // 2, dilation=dilation), lambda n: n, 0)
 
 
 def conv_transpose_op(stride):
-    """F.conv_transpose1d, padding (k - stride) // 2: w [Cin, Cout, k], stride outputs per input"""
-    return Op(lambda xa, w, b: F.conv_transpose1d(xa, w, b, stride=stride, padding=(w.shape[2] - stride) // 2), stride, 1)
+    """F.conv_transpose1d, padding (k - stride) // 2: w [Cin, Cout, k], stride n outputs"""
+    return Op(lambda xa, w, b: F.conv_transpose1d(xa, w, b, stride=stride, padding=(w.shape[2] - stride) // 2),
+              lambda n: stride * n, 1)
 
 
-def _ragged(x, lengths, gy, cout, mul, fn):
-    """y [B, cout, mul ld]: fn(i, n, x_i) of every utterance alone on its valid part x_i = x[i:i + 1, :, :n] (n = lengths[i], or
-    ld), zero beyond mul n.  With gy (same dtype as x) the backward of sum(y gy) has run on return.  Returns (y, gx), gx zero
-    beyond n."""
+def strided_op(stride, groups=1):
+    """F.conv1d at a stride, padding (k - 1) // 2, in groups: w [Cout, Cin / groups, k], ceil(n / stride) outputs"""
+    return Op(lambda xa, w, b: F.conv1d(xa, w, b, stride=stride, padding=(w.shape[2] - 1) // 2, groups=groups),
+              lambda n: cdiv(n, stride), 0)
+
+
+def y_ld(ld, op):
+    """the row length of y for a row length ld of x: out_len(ld) rounded up to a multiple of 4, as the library allocates it (its
+    rows of x are multiples of 4; the float64 cases on other rows, CPU only, keep out_len(ld))"""
+    return ceil4(op.out_len(ld)) if ld % 4 == 0 else op.out_len(ld)
+
+
+def valid_masks(lengths, ld, op):
+    """([B, 1, ld], [B, 1, y_ld]) float masks of the valid input / output positions: n and out_len(n)"""
+    vi, vo = torch.zeros(len(lengths), 1, ld), torch.zeros(len(lengths), 1, y_ld(ld, op))
+    for i, n in enumerate(lengths):
+        vi[i, :, :n] = 1
+        vo[i, :, :op.out_len(n)] = 1
+    return vi, vo
+
+
+def _ragged(x, lengths, gy, cout, op, fn):
+    """y [B, cout, y_ld]: fn(i, n, x_i) of every utterance alone on its valid part x_i = x[i:i + 1, :, :n] (n = lengths[i], or
+    ld), zero beyond its op.out_len(n) outputs.  With gy (same dtype as x) the backward of sum(y gy) has run on return.  Returns
+    (y, gx), gx zero beyond n."""
     B, _, ld = x.shape
-    y = torch.zeros(B, cout, mul * ld, dtype=x.dtype)
+    y = torch.zeros(B, cout, y_ld(ld, op), dtype=x.dtype)
     gx = torch.zeros_like(x)
     loss, xs = 0, []
     for i in range(B):
@@ -57,10 +95,11 @@ def _ragged(x, lengths, gy, cout, mul, fn):
         xi = x[i:i + 1, :, :n].clone().requires_grad_(gy is not None)
         xs.append(xi)
         yi = fn(i, n, xi)
-        assert yi.shape[2] == mul * n
-        y[i, :, :mul * n] = yi[0].detach()
+        m = op.out_len(n)
+        assert yi.shape[2] == m
+        y[i, :, :m] = yi[0].detach()
         if gy is not None:
-            loss = loss + (yi * gy[i:i + 1, :, :mul * n]).sum()
+            loss = loss + (yi * gy[i:i + 1, :, :m]).sum()
     if torch.is_tensor(loss):
         loss.backward()
     for i, xi in enumerate(xs):
@@ -74,15 +113,57 @@ def _grad(t):
 
 
 def layer_ref(x, w, b, gy, lengths, op, in_slope, dtype):
-    """(y, gx, gw, gb) of y = b + op(lrelu(x, in_slope), w) by torch autograd, op = conv_op(dilation) or
-    conv_transpose_op(stride), per utterance on its valid INPUT length n (op.mul * n outputs); y and gx are zero beyond.
+    """(y, gx, gw, gb) of y = b + op(lrelu(x, in_slope), w) by torch autograd, op = conv_op(dilation), conv_transpose_op(stride)
+    or strided_op(stride, groups), per utterance on its valid INPUT length n (op.out_len(n) outputs); y and gx are zero beyond.
     b may be None (gb is then None)."""
     x = x.detach().to("cpu", dtype)
     gy = gy.detach().to("cpu", dtype)
     w = w.detach().to("cpu", dtype).requires_grad_(True)
     bb = None if b is None else b.detach().to("cpu", dtype).requires_grad_(True)
-    y, gx = _ragged(x, lengths, gy, w.shape[op.cout_dim], op.mul, lambda i, n, xi: op.apply(F.leaky_relu(xi, in_slope), w, bb))
+    y, gx = _ragged(x, lengths, gy, w.shape[op.cout_dim], op, lambda i, n, xi: op.apply(F.leaky_relu(xi, in_slope), w, bb))
     return y, gx, _grad(w), None if bb is None else _grad(bb)
+
+
+def taps(k, s, pad=None):
+    """[(plane, shift)] of tap kk of a stride-s layer: kk - pad = s * shift + plane, 0 <= plane < s"""
+    pad = (k - 1) // 2 if pad is None else pad
+    return [((kk - pad) % s, (kk - pad - (kk - pad) % s) // s) for kk in range(k)]
+
+
+def phase_layer(xa, w, b, gym, lengths, s, g=1, drop_tap=None, tap_shift=None, plane_shift=None, next_group=False, floor_len=False,
+                pad=None):
+    """(y, gw) of the strided / grouped layer in the kernels' phase form, a CPU stand-in: plane_p[ci][q] = xa[ci][s q + p], tap kk
+    reads plane_p(kk)[q + dl(kk)] of the channels [grp cig, (grp + 1) cig) of its group.  xa = lrelu(x) and gym = gy, both already
+    zero beyond the lengths.  Defects: drop_tap = kk (left out), tap_shift = (kk, n) (tap kk read n positions late), plane_shift =
+    (p, n) (plane p read n positions late), next_group (group grp reads the input channels of group grp + 1, the last one those
+    of group 0), floor_len (the output length taken as floor(n / s)), pad (the padding taken as this in place of (k - 1) / 2)."""
+    B, cin, ld = xa.shape
+    cout, cig, k = w.shape
+    cog = cout // g
+    assert cig * g == cin and cog * g == cout
+    Q, H = out_ld(ld, s), 24  # the halo: k = 41 at stride 1 shifts by 20, and a defect by one more
+    xp = F.pad(xa, (0, s * (Q + H) - ld))
+    y = torch.zeros(B, cout, Q, dtype=xa.dtype)
+    gw = torch.zeros_like(w)
+    vo = torch.zeros(B, 1, Q, dtype=xa.dtype)
+    for i, n in enumerate(lengths):
+        vo[i, :, :(n // s if floor_len else cdiv(n, s))] = 1
+    for kk, (p, dl) in enumerate(taps(k, s, pad)):
+        if kk == drop_tap:
+            continue
+        if tap_shift is not None and tap_shift[0] == kk:
+            dl += tap_shift[1]
+        if plane_shift is not None and plane_shift[0] == p:
+            dl += plane_shift[1]
+        pl = F.pad(xp[:, :, p::s], (H, 0))  # column c = position c - H
+        win = pl[:, :, H + dl:H + dl + Q]
+        for grp in range(g):
+            src = (grp + 1) % g if next_group else grp
+            wi = win[:, src * cig:(src + 1) * cig]
+            co = slice(grp * cog, (grp + 1) * cog)
+            y[:, co] += torch.einsum("oi,biq->boq", w[co, :, kk], wi)
+            gw[co, :, kk] = torch.einsum("boq,biq->oi", (gym * vo)[:, co], wi)
+    return (y + b.view(1, -1, 1)) * vo, gw
 
 
 def _lrelu(x, slope, mask):
@@ -125,7 +206,7 @@ def resblock1_ref(w, x, k, dilations, dtype, masks=None, lengths=None, gy=None, 
         tap = None if taps is None else (lambda j, t: taps[j][i, :, :n].copy_(t[0].detach()))
         return resblock_chain(xi, wd, k, dilations, mask_of(masks, i, n), tap)
 
-    y, gx = _ragged(x, lengths, None if gy is None else gy.detach().to("cpu", dtype), x.shape[1], 1, block)
+    y, gx = _ragged(x, lengths, None if gy is None else gy.detach().to("cpu", dtype), x.shape[1], conv_op(1), block)
     return y if gy is None else (y, gx, {n: _grad(t) for n, t in wd.items()})
 
 

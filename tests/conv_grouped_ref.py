@@ -1,13 +1,14 @@
-"""Shared by tests/test_conv_grouped_cpu.py and tests/test_gpu_conv_grouped.py (not a test module): the layer table of the scale
-discriminator, the float64 / float32 torch restatement of dissc_amd.nn.conv1d_grouped (F.conv1d(lrelu(x), w, b, stride=s,
-padding=(k - 1) // 2, groups=g), every utterance alone on its valid part), the phase form its kernels use (for seeding defects),
-the average pool, and DiscriminatorS restated both as torch's grouped Conv1d chain on one utterance and as the ragged
-composition the library runs.  The bars are conv_grad_ref's."""
+"""Shared by tests/test_conv_grouped_cpu.py and tests/test_gpu_conv_grouped.py (not a test module): what is nn.conv1d_grouped's,
+nn.mean_pool's and nn.discriminator_s's own -- the layer table of the scale discriminator, the average pool, and DiscriminatorS
+restated both as torch's grouped Conv1d chain on one utterance and as the ragged composition the library runs.  The float64 /
+float32 restatement of the layer (layer_ref with strided_op(stride, groups)), its phase form, the masks and the bars are
+conv_grad_ref's."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from conv_grad_ref import SLOPE, check, compare, k_cap, K_WHOLE, K_CH, _grad  # noqa: F401
+from conv_grad_ref import (SLOPE, check, compare, k_cap, K_WHOLE, K_CH, cdiv, ceil4, out_ld, layer_ref, strided_op,  # noqa: F401
+                           valid_masks, taps, phase_layer)
 
 # (Cin, Cout, k, stride, groups) of convs.0 .. convs.5, reference sr/models.py:289-294
 DISC_S = [(1, 128, 15, 1, 1), (128, 128, 41, 2, 4), (128, 256, 41, 2, 16), (256, 512, 41, 4, 16), (512, 1024, 41, 4, 16),
@@ -16,98 +17,6 @@ SMALL = [(16, 32, 7, 2, 2), (24, 48, 41, 4, 3), (1, 16, 3, 1, 1)]  # a short ker
 DISC_S_TAIL = [(1024, 1024, 5), (1024, 1, 3)]  # convs.6 and conv_post: plain stride-1 layers
 DISC_S_CHANNELS = [128, 128, 256, 512, 1024, 1024, 1024, 1]  # the eight maps
 TRAIN_L = [8960, 8960, 4480, 2240, 560, 140]  # the input rows of convs.0 .. convs.5 at the trainer's segment, scale 0
-
-
-def cdiv(a, b):
-    return -(-a // b)
-
-
-def ceil4(n):
-    return (n + 3) // 4 * 4
-
-
-def out_ld(ld, s):
-    """the row length of y for a row length ld of x"""
-    return ceil4(cdiv(ld, s))
-
-
-def valid_masks(lengths, ld, s):
-    """([B, 1, ld], [B, 1, out_ld]) float masks of the valid input / output positions: n and ceil(n / s)"""
-    vi, vo = torch.zeros(len(lengths), 1, ld), torch.zeros(len(lengths), 1, out_ld(ld, s))
-    for i, n in enumerate(lengths):
-        vi[i, :, :n] = 1
-        vo[i, :, :cdiv(n, s)] = 1
-    return vi, vo
-
-
-def layer_ref(x, w, b, gy, lengths, s, g, in_slope, dtype):
-    """(y, gx, gw, gb) of y = b + conv1d(lrelu(x, in_slope), w, stride=s, padding=(k - 1) // 2, groups=g) by torch autograd, every
-    utterance alone on its valid INPUT length n (ceil(n / s) outputs); y [B, Cout, out_ld] and gx are zero beyond.  b may be None."""
-    x = x.detach().to("cpu", dtype)
-    gy = gy.detach().to("cpu", dtype)
-    w = w.detach().to("cpu", dtype).requires_grad_(True)
-    bb = None if b is None else b.detach().to("cpu", dtype).requires_grad_(True)
-    B, _, ld = x.shape
-    k = w.shape[2]
-    y = torch.zeros(B, w.shape[0], out_ld(ld, s), dtype=dtype)
-    gx = torch.zeros_like(x)
-    loss, xs = 0, []
-    for i in range(B):
-        n = ld if lengths is None else int(lengths[i])
-        xs.append(None)
-        if n <= 0:
-            continue
-        xs[-1] = xi = x[i:i + 1, :, :n].clone().requires_grad_(True)
-        yi = F.conv1d(F.leaky_relu(xi, in_slope), w, bb, stride=s, padding=(k - 1) // 2, groups=g)
-        m = cdiv(n, s)
-        assert yi.shape[2] == m
-        y[i, :, :m] = yi[0].detach()
-        loss = loss + (yi * gy[i:i + 1, :, :m]).sum()
-    if torch.is_tensor(loss):
-        loss.backward()
-    for i, xi in enumerate(xs):
-        if xi is not None and xi.grad is not None:
-            gx[i, :, :xi.shape[2]] = xi.grad[0]
-    return y, gx, _grad(w), None if bb is None else _grad(bb)
-
-
-def taps(k, s, pad=None):
-    """[(plane, shift)] of tap kk: kk - pad = s * shift + plane, 0 <= plane < s"""
-    pad = (k - 1) // 2 if pad is None else pad
-    return [((kk - pad) % s, (kk - pad - (kk - pad) % s) // s) for kk in range(k)]
-
-
-def phase_layer(xa, w, b, gym, lengths, s, g, drop_tap=None, tap_shift=None, next_group=False, floor_len=False, pad=None):
-    """(y, gw) in the kernels' phase form, a CPU stand-in: plane_p[ci][q] = xa[ci][s q + p], tap kk reads plane_p(kk)[q + dl(kk)] of
-    the channels [grp cig, (grp + 1) cig) of its group.  xa = lrelu(x) and gym = gy, both already zero beyond the lengths.
-    Defects: drop_tap = kk (left out), tap_shift = (kk, n) (tap kk read n positions late), next_group (group grp reads the input
-    channels of group grp + 1, the last one those of group 0), floor_len (the output length taken as floor(n / s)), pad (the
-    padding taken as this in place of (k - 1) / 2)."""
-    B, cin, ld = xa.shape
-    cout, cig, k = w.shape
-    cog = cout // g
-    assert cig * g == cin and cog * g == cout
-    Q, H = out_ld(ld, s), 24
-    xp = F.pad(xa, (0, s * (Q + H) - ld))
-    y = torch.zeros(B, cout, Q, dtype=xa.dtype)
-    gw = torch.zeros_like(w)
-    vo = torch.zeros(B, 1, Q, dtype=xa.dtype)
-    for i, n in enumerate(lengths):
-        vo[i, :, :(n // s if floor_len else cdiv(n, s))] = 1
-    for kk, (p, dl) in enumerate(taps(k, s, pad)):
-        if kk == drop_tap:
-            continue
-        if tap_shift is not None and tap_shift[0] == kk:
-            dl += tap_shift[1]
-        pl = F.pad(xp[:, :, p::s], (H, 0))  # column c = position c - H
-        win = pl[:, :, H + dl:H + dl + Q]
-        for grp in range(g):
-            src = (grp + 1) % g if next_group else grp
-            wi = win[:, src * cig:(src + 1) * cig]
-            co = slice(grp * cog, (grp + 1) * cog)
-            y[:, co] += torch.einsum("oi,biq->boq", w[co, :, kk], wi)
-            gw[co, :, kk] = torch.einsum("boq,biq->oi", (gym * vo)[:, co], wi)
-    return (y + b.view(1, -1, 1)) * vo, gw
 
 
 # ---- the pool -----------------------------------------------------------------------------------------------------------

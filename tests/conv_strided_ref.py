@@ -1,103 +1,19 @@
-"""Shared by tests/test_conv_strided_grad_cpu.py and tests/test_gpu_conv_strided_grad.py (not a test module): the float64 /
-float32 torch restatement of dissc_amd.nn.conv1d_strided (F.conv1d(lrelu(x), w, b, stride=s, padding=(k - 1) // 2), every
-utterance alone on its valid part), the phase form its kernels use (for seeding defects), the period fold, and DiscriminatorP
-restated with Conv2d as reference sr/models.py:241-260 writes it, next to its period-major Conv1d composition.  The bars are
-conv_grad_ref's."""
+"""Shared by tests/test_conv_strided_grad_cpu.py and tests/test_gpu_conv_strided_grad.py (not a test module): what is
+nn.conv1d_strided's and nn.discriminator_p's own -- the layer tables, the period fold, and DiscriminatorP restated with Conv2d as
+reference sr/models.py:241-260 writes it, next to its period-major Conv1d composition.  The float64 / float32 restatement of the
+layer (layer_ref with strided_op(stride)), its phase form, the masks and the bars are conv_grad_ref's."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from conv_grad_ref import SLOPE, check, compare, k_cap, K_WHOLE, K_CH, _grad  # noqa: F401
+from conv_grad_ref import (SLOPE, check, compare, k_cap, K_WHOLE, K_CH, cdiv, ceil4, out_ld, layer_ref, strided_op,  # noqa: F401
+                           valid_masks, taps, phase_layer)
 
 DISC_P = [(1, 32, 5, 3), (32, 128, 5, 3), (128, 512, 5, 3), (512, 1024, 5, 3)]  # (Cin, Cout, k, stride), sr/models.py:234-237
 TAP_TABLE = [(16, 16, 7, 2), (8, 24, 7, 4)]  # other (k, stride): taps of two and three shifts, an even stride
 DISC_P_CHANNELS = [1, 32, 128, 512, 1024, 1024, 1]  # convs.0 .. convs.4, conv_post
 DISC_P_KERNELS = [5, 5, 5, 5, 5, 3]
 PERIODS = [2, 3, 5, 7, 11]  # sr/models.py:267
-
-
-def cdiv(a, b):
-    return -(-a // b)
-
-
-def ceil4(n):
-    return (n + 3) // 4 * 4
-
-
-def out_ld(ld, s):
-    """the row length of y for a row length ld of x"""
-    return ceil4(cdiv(ld, s))
-
-
-def valid_masks(lengths, ld, s):
-    """([B, 1, ld], [B, 1, out_ld]) float masks of the valid input / output positions: n and ceil(n / s)"""
-    vi, vo = torch.zeros(len(lengths), 1, ld), torch.zeros(len(lengths), 1, out_ld(ld, s))
-    for i, n in enumerate(lengths):
-        vi[i, :, :n] = 1
-        vo[i, :, :cdiv(n, s)] = 1
-    return vi, vo
-
-
-def layer_ref(x, w, b, gy, lengths, s, in_slope, dtype):
-    """(y, gx, gw, gb) of y = b + conv1d(lrelu(x, in_slope), w, stride=s, padding=(k - 1) // 2) by torch autograd, every utterance
-    alone on its valid INPUT length n (ceil(n / s) outputs); y [B, Cout, out_ld] and gx are zero beyond.  b may be None."""
-    x = x.detach().to("cpu", dtype)
-    gy = gy.detach().to("cpu", dtype)
-    w = w.detach().to("cpu", dtype).requires_grad_(True)
-    bb = None if b is None else b.detach().to("cpu", dtype).requires_grad_(True)
-    B, _, ld = x.shape
-    k = w.shape[2]
-    y = torch.zeros(B, w.shape[0], out_ld(ld, s), dtype=dtype)
-    gx = torch.zeros_like(x)
-    loss, xs = 0, []
-    for i in range(B):
-        n = ld if lengths is None else int(lengths[i])
-        xs.append(None)
-        if n <= 0:
-            continue
-        xs[-1] = xi = x[i:i + 1, :, :n].clone().requires_grad_(True)
-        yi = F.conv1d(F.leaky_relu(xi, in_slope), w, bb, stride=s, padding=(k - 1) // 2)
-        m = cdiv(n, s)
-        assert yi.shape[2] == m
-        y[i, :, :m] = yi[0].detach()
-        loss = loss + (yi * gy[i:i + 1, :, :m]).sum()
-    if torch.is_tensor(loss):
-        loss.backward()
-    for i, xi in enumerate(xs):
-        if xi is not None and xi.grad is not None:
-            gx[i, :, :xi.shape[2]] = xi.grad[0]
-    return y, gx, _grad(w), None if bb is None else _grad(bb)
-
-
-def taps(k, s):
-    """[(plane, shift)] of tap kk: kk - pad = s * shift + plane, 0 <= plane < s"""
-    pad = (k - 1) // 2
-    return [((kk - pad) % s, (kk - pad - (kk - pad) % s) // s) for kk in range(k)]
-
-
-def phase_layer(xa, w, b, gym, lengths, s, drop_tap=None, plane_shift=None, floor_len=False):
-    """(y, gw) in the kernels' phase form, a CPU stand-in: plane_p[ci][q] = xa[ci][s q + p], tap kk reads plane_p(kk)[q + dl(kk)].
-    xa = lrelu(x) and gym = gy, both already zero beyond the lengths.  Defects: drop_tap = kk (left out), plane_shift = (p, n)
-    (plane p read n positions late), floor_len (the output length taken as floor(n / s))."""
-    B, cin, ld = xa.shape
-    cout, _, k = w.shape
-    Q, H = out_ld(ld, s), 8
-    xp = F.pad(xa, (0, s * (Q + H) - ld))
-    y = torch.zeros(B, cout, Q, dtype=xa.dtype)
-    gw = torch.zeros_like(w)
-    vo = torch.zeros(B, 1, Q, dtype=xa.dtype)
-    for i, n in enumerate(lengths):
-        vo[i, :, :(n // s if floor_len else cdiv(n, s))] = 1
-    for kk, (p, dl) in enumerate(taps(k, s)):
-        if kk == drop_tap:
-            continue
-        pl = F.pad(xp[:, :, p::s], (H, 0))  # column c = position c - H
-        if plane_shift is not None and plane_shift[0] == p:
-            dl += plane_shift[1]
-        win = pl[:, :, H + dl:H + dl + Q]
-        y += torch.einsum("oi,biq->boq", w[:, :, kk], win)
-        gw[:, :, kk] = torch.einsum("boq,biq->oi", gym * vo, win)
-    return (y + b.view(1, -1, 1)) * vo, gw
 
 
 # ---- the period fold and DiscriminatorP ---------------------------------------------------------------------------------

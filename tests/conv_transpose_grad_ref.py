@@ -1,11 +1,11 @@
 """Shared by tests/test_conv_transpose_grad_cpu.py and tests/test_gpu_conv_transpose_grad.py (not a test module): what is
-nn.conv_transpose1d's own -- the generator's five upsamplers and the other shapes, the valid masks, the phase form of the weight
-gradient the kernel uses (for seeding defects) and one generator stage.  The float64 / float32 restatement of the layer
-(layer_ref with conv_transpose_op(stride)), the ResBlock chain and the bars are conv_grad_ref's."""
+nn.conv_transpose1d's own -- the generator's five upsamplers and the other shapes, the phase form of the weight gradient the
+kernel uses (for seeding defects) and one generator stage.  The float64 / float32 restatement of the layer (layer_ref with
+conv_transpose_op(stride)), the valid masks, the ResBlock chain and the bars are conv_grad_ref's."""
 import torch
 import torch.nn.functional as F
 
-from conv_grad_ref import (SLOPE, check, compare, k_cap, K_WHOLE, K_CH, layer_ref, conv_transpose_op,  # noqa: F401
+from conv_grad_ref import (SLOPE, check, compare, k_cap, K_WHOLE, K_CH, layer_ref, conv_transpose_op, valid_masks,  # noqa: F401
                            resblock_chain, mask_of, _ragged, _grad)
 
 # ups[i] of the reference generator (synthdata.VCTK_CONFIG): (Cin, Cout, k, stride), and the input length of each at 28 frames
@@ -26,15 +26,6 @@ def ups_from_config():
         out.append((ch, ch // 2, k, u))
         ch //= 2
     return out
-
-
-def valid_masks(lengths, ld, stride):
-    """([B, 1, ld], [B, 1, stride ld]) float masks of the valid input / output positions"""
-    vi, vo = torch.zeros(len(lengths), 1, ld), torch.zeros(len(lengths), 1, stride * ld)
-    for i, n in enumerate(lengths):
-        vi[i, :, :n] = 1
-        vo[i, :, :stride * n] = 1
-    return vi, vo
 
 
 def phase_wgrad(xa, gym, k, stride, drop_phase=None, swap=None, plane_shift=None):
@@ -75,5 +66,5 @@ def stage_ref(wt, bt, stride, w, x, k, dilations, dtype, masks, lengths, gy):
         h = up.apply(F.leaky_relu(xi, SLOPE), wd["ups.weight"], wd["ups.bias"])
         return resblock_chain(h, wd, k, dilations, mask_of(masks, i, stride * n))
 
-    y, gx = _ragged(x.detach().to("cpu", dtype), lengths, gy.detach().to("cpu", dtype), wt.shape[1], stride, stage)
+    y, gx = _ragged(x.detach().to("cpu", dtype), lengths, gy.detach().to("cpu", dtype), wt.shape[1], up, stage)
     return y, gx, {n: _grad(t) for n, t in wd.items()}

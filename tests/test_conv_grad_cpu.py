@@ -1,7 +1,8 @@
 """dissc_amd.nn without a GPU: what dissc_convgrad_create refuses and accepts, the partial plan of the weight gradient
 (a function of the shape only, inside 64 MB for the generator), and the reference of tests/test_gpu_conv_grad.py:
 conv_grad_ref.layer_ref agrees with finite differences in float64, the bars it is used with catch seeded defects, and the
-harness both GPU files call (conv_grad_harness.assert_layer_gradients) passes the reference and catches seeded defects."""
+harness the four conv-layer GPU files call (conv_grad_harness: lengths_for, assert_layer_gradients) keeps its pinned lengths,
+passes the reference for every kind and reports each seeded defect by the one assertion meant for it."""
 import ctypes
 
 import numpy as np
@@ -205,33 +206,65 @@ def test_resblock_ref_masks():
 
 
 # ---------------------------------------------------------------------------------------------------------
-# the harness of the two GPU files (tests/conv_grad_harness.py)
+# the harness of the four GPU files (tests/conv_grad_harness.py)
 # ---------------------------------------------------------------------------------------------------------
+def test_lengths_for_keeps_its_pinned_lists(nn):
+    """the measured ratios of profiles/*.md belong to these lengths: the widest strided layer at max_b = 4, and a grouped layer
+    whose plan (23 partials of 2 pairs over 15 x 3 chunks) puts partial boundaries inside utterances"""
+    assert H.lengths_for(nn, H.Spec("strided", 512, 1024, 5, 3), max_b=4) == ([4, 383, 192, 385], 388, (4, 3))
+    assert H.lengths_for(nn, H.Spec("grouped", 128, 128, 41, 2, 4)) == \
+        ([1, 2, 2, 3, 20, 21, 41, 129, 128, 129, 257, 256, 255, 128, 127], 260, (23, 2))
+
+
 def _stand_in(spec, defect=None):
     """conv_grad_harness.run's contract on the CPU: the float32 reference, with one seeded defect"""
-    def run(x, w, b, gy, lengths, slope, add=None, need=(True, True, True)):
+    calls = []
+
+    def run(x, w, b, gy, lengths, slope, add=None, need=(True, True, True), nan_workspace=False):
         y, gx, gw, gb = (t.clone() for t in R.layer_ref(x, w, b, gy, lengths, spec.op, slope, torch.float32))
-        vi, vo = H.valid_masks(lengths, x.shape[2], spec.mul)
+        vi, vo = R.valid_masks(lengths, x.shape[2], spec.op)
+        calls.append(lengths)
+        alone = len(lengths) == 1
         if add is not None:
             y += add * vo
-        if defect == "gx beyond a length" and len(lengths) > 1:
+        if defect == "gx beyond a length" and not alone:
             gx[1, 0, lengths[1]] = 1e-3
         if defect == "gw reads beyond the lengths":  # too small to move a bit of gw until the poison arrives
             gw.view(-1)[0] += 1e-12 * float((x * (1 - vi)).sum())
-        if defect == "one tap of gw zeroed":
+        if defect == "one tap of gw zeroed" or (defect == "one tap of gw zeroed in one utterance alone" and lengths == [4]):
             gw[:, :, 1] = 0
-        grads = [g if on else None for g, on in zip((gx, gw, gb), need)]
-        return [y] + grads + [None if add is None else gy.clone()]
+        if defect == "y differs on the second call" and len(calls) == 2:
+            y[0, 0, 0] += 1e-3
+        if defect == "the workspace is read before it is written" and nan_workspace:
+            gb[0] += 1e-3
+        if defect == "gw depends on whether gx is wanted" and not need[0]:
+            gw[0, 0, 0] += 1e-3
+        if defect == "alone y differs" and alone:
+            y[0, 0, 0] += 1e-3
+        if defect == "alone gx differs" and alone:
+            gx[0, 0, 0] += 1e-3
+        gadd = None if add is None else gy * (0.5 if defect == "the gradient of add is halved" else 1.0)
+        return [y] + [g if on else None for g, on in zip((gx, gw, gb), need)] + [gadd]
     return run
 
 
-@pytest.mark.parametrize("spec", [H.Spec(False, 3, 2, 3, 1), H.Spec(True, 3, 2, 4, 2)], ids=["conv1d", "conv_transpose1d"])
+SPECS = [H.Spec("conv1d", 3, 2, 3, 1), H.Spec("transposed", 3, 2, 4, 2), H.Spec("strided", 3, 2, 3, 2), H.Spec("grouped", 4, 4, 3, 2, 2)]
+DEFECTS = [("gx beyond a length", "beyond the lengths"), ("gw reads beyond the lengths", "poison beyond the lengths changes gw"),
+           ("one tap of gw zeroed", "batch gw"), ("y differs on the second call", "y is not bit-reproducible"),
+           ("the workspace is read before it is written", "a workspace full of NaNs changes gb"),
+           ("gw depends on whether gx is wanted", r"needs_input_grad \(False, True, True\): gw"),
+           ("alone gx differs", "alone gx differs from the batch's"),
+           ("one tap of gw zeroed in one utterance alone", r"^\[\('alone len 4 gw'")]
+
+
+@pytest.mark.parametrize("spec", SPECS, ids=["conv1d", "conv_transpose1d", "conv1d_strided", "conv1d_grouped"])
 def test_harness_passes_the_reference_and_catches_seeded_defects(spec):
-    """assert_layer_gradients, as both GPU files call it, passes the float32 reference and fails on each of three defects:
-    the merged harness kept the strictness of the two copies it replaces"""
+    """assert_layer_gradients, as the four GPU files call it, passes the float32 reference of every kind, and each of its
+    assertions reports the defect seeded for it -- and no other assertion does: the message is the first one raised"""
     lengths, ld = [9, 4, 1], 12
     H.assert_layer_gradients(_stand_in(spec), spec, lengths, ld, seed=5)
-    for defect, said in (("gx beyond a length", "beyond the lengths"), ("gw reads beyond the lengths", "poison beyond the lengths changes gw"),
-                         ("one tap of gw zeroed", "batch gw")):
+    own = [("the gradient of add is halved", "the gradient of add is gy itself")] if spec.kind == "conv1d" else \
+        [("alone y differs", "alone y differs from the batch's")]  # (the Conv1d's alone runs are made without add)
+    for defect, said in DEFECTS + own:
         with pytest.raises(AssertionError, match=said):
             H.assert_layer_gradients(_stand_in(spec, defect), spec, lengths, ld, seed=5)

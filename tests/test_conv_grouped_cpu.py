@@ -1,6 +1,6 @@
 """dissc_amd.nn.conv1d_grouped, nn.mean_pool and nn.discriminator_s without a GPU: what dissc_convggrad_create accepts and
 refuses, the partial plan of the weight gradient (a function of the shape only, at most 56 MB of partials) and the workspace, and
-the references of tests/test_gpu_conv_grouped.py: the kernels' phase form equals conv_grouped_ref.layer_ref in float64 for every
+the references of tests/test_gpu_conv_grouped.py: the kernels' phase form equals conv_grad_ref.layer_ref in float64 for every
 layer, pool_ref equals F.avg_pool1d, the length chain equals torch's output shapes, the restated DiscriminatorS is held to a
 golden recorded from the reference's own module (tests/golden/make_disc_s_golden.py), and the bars catch seeded defects."""
 import ctypes
@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_grad_harness as H
 import conv_grouped_ref as R
 
 LENGTHS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 513, 4481, 8960]
@@ -22,16 +23,6 @@ def nn():
     ge.build()
     from dissc_amd import nn
     return nn
-
-
-def _case(cin, cout, k, s, g, B, ld, seed, dtype=np.float32):
-    rs = np.random.RandomState(seed)
-    x = torch.from_numpy(rs.randn(B, cin, ld).astype(dtype))
-    x[torch.from_numpy(rs.rand(B, cin, ld) < 0.02)] = 0.0
-    w = torch.from_numpy((rs.uniform(-1, 1, (cout, cin // g, k)) / np.sqrt(cin // g * k)).astype(dtype))
-    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(dtype))
-    gy = torch.from_numpy(rs.randn(B, cout, R.out_ld(ld, s)).astype(dtype))
-    return x, w, b, gy
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -122,10 +113,10 @@ def test_partials_depend_on_the_shape_only_and_stay_under_56_mb(nn):
 # ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cin,cout,k,s,g", R.DISC_S + R.SMALL)
 def test_phase_form_equals_layer_ref_in_float64(cin, cout, k, s, g):
-    lengths = [44, 2 * s + 1, 1, 41]
-    x, w, b, gy = _case(cin, cout, k, s, g, len(lengths), 44, seed=cin + k + s, dtype=np.float64)
-    y64, _, gw64, _ = R.layer_ref(x, w, b, gy, lengths, s, g, 0.1, torch.float64)
-    vi, _ = R.valid_masks(lengths, 44, s)
+    lengths, spec = [44, 2 * s + 1, 1, 41], H.Spec("grouped", cin, cout, k, s, g)
+    x, w, b, gy = (t.double() for t in H.case(spec, len(lengths), 44, seed=cin + k + s))
+    y64, _, gw64, _ = R.layer_ref(x, w, b, gy, lengths, spec.op, 0.1, torch.float64)
+    vi, _ = R.valid_masks(lengths, 44, spec.op)
     y, gw = R.phase_layer(F.leaky_relu(x, 0.1) * vi.double(), w, b, gy, lengths, s, g)
     assert float((y - y64).abs().max()) <= 1e-12 * max(1.0, float(y64.abs().max()))
     assert float((gw - gw64).abs().max()) <= 1e-12 * max(1.0, float(gw64.abs().max()))
@@ -196,19 +187,18 @@ def test_restated_discriminator_s_is_held_to_the_reference_golden(golden_dir):
 # ---------------------------------------------------------------------------------------------------------
 # the bars
 # ---------------------------------------------------------------------------------------------------------
-def test_bars_catch_seeded_defects():
+def test_bars_catch_seeded_defects(nn):
     """an fp32 "kernel result" (torch on the CPU, in the kernels' phase form) with one seeded defect misses its K = 4 bar by at
-    least 10 x on the ragged case of tests/test_gpu_conv_grouped.py; the clean one passes"""
-    cin, cout, k, s, g, slope = 24, 48, 41, 4, 3, 0.1
-    T = 64 * s
-    lengths = [1, 2, s, s + 1, 20, 21, 41, T - 1, T, T + 1, 2 * T + 1] + [2 * T - r for r in range(s)]
-    ld = R.ceil4(2 * T + 1)
-    x, w, b, gy = _case(cin, cout, k, s, g, len(lengths), ld, seed=5)
-    r64 = R.layer_ref(x, w, b, gy, lengths, s, g, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, s, g, slope, torch.float32)
+    least 10 x on the ragged case tests/test_gpu_conv_grouped.py runs; the clean one passes"""
+    spec, slope = H.Spec("grouped", 24, 48, 41, 4, 3), 0.1
+    s, g = spec.p, spec.groups
+    lengths, ld, _ = H.lengths_for(nn, spec)
+    x, w, b, gy = H.case(spec, len(lengths), ld, seed=5)
+    r64 = R.layer_ref(x, w, b, gy, lengths, spec.op, slope, torch.float64)
+    r32 = R.layer_ref(x, w, b, gy, lengths, spec.op, slope, torch.float32)
     for name, kind, y, a, c in zip(("y", "gx", "gw", "gb"), ("act", "act", "weight", "vec"), r32, r64, r32):
         assert not R.check("clean " + name, kind, y.clone(), a, c)
-    vi, vo = R.valid_masks(lengths, ld, s)
+    vi, vo = R.valid_masks(lengths, ld, spec.op)
     xa = F.leaky_relu(x, slope) * vi
 
     def wide(tag, kind, y, a, c, margin=10.0):

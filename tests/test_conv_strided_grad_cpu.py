@@ -1,8 +1,8 @@
 """dissc_amd.nn.conv1d_strided and nn.discriminator_p without a GPU: what dissc_convsgrad_create accepts and refuses, the calls
 that return before any device is touched, the partial plan of the weight gradient (a function of the shape only) and the
-workspace, and the references of tests/test_gpu_conv_strided_grad.py: conv_strided_ref.layer_ref agrees with finite differences
-in float64, the bars it is used with catch seeded defects, and the Conv2d restatement of DiscriminatorP equals the period-major
-Conv1d composition the library runs."""
+workspace, and the references of tests/test_gpu_conv_strided_grad.py: conv_grad_ref.layer_ref with strided_op agrees with finite
+differences in float64, the bars it is used with catch seeded defects on the ragged lengths of the GPU file, and the Conv2d
+restatement of DiscriminatorP equals the period-major Conv1d composition the library runs."""
 import ctypes
 
 import numpy as np
@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_grad_harness as H
 import conv_strided_ref as R
 
 
@@ -121,13 +122,13 @@ def test_layer_ref_agrees_with_finite_differences():
     x = torch.from_numpy(rs.randn(B, cin, L))
     x = torch.where(x.abs() < 0.05, torch.full_like(x, 0.3), x)  # no kink inside a finite-difference step
     w, b, gy = (torch.from_numpy(rs.randn(*sh)) for sh in ((cout, cin, k), (cout,), (B, cout, R.out_ld(L, s))))
-    y, gx, gw, gb = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float64)
-    vi, vo = R.valid_masks(lengths, L, s)
+    y, gx, gw, gb = R.layer_ref(x, w, b, gy, lengths, R.strided_op(s), slope, torch.float64)
+    vi, vo = R.valid_masks(lengths, L, R.strided_op(s))
     assert not y[(vo == 0).expand_as(y)].any() and not gx[(vi == 0).expand_as(gx)].any()
     assert y[0, :, :3].abs().min() > 0 and y[1, :, :2].abs().min() > 0  # ceil(8 / 3) = 3 and ceil(4 / 3) = 2 outputs
 
     def loss(x_, w_, b_):
-        return float((R.layer_ref(x_, w_, b_, gy, lengths, s, slope, torch.float64)[0] * gy).sum())
+        return float((R.layer_ref(x_, w_, b_, gy, lengths, R.strided_op(s), slope, torch.float64)[0] * gy).sum())
 
     eps = 1e-6
     for t, g, arg in ((x, gx, 0), (w, gw, 1), (b, gb, 2)):
@@ -143,23 +144,20 @@ def test_layer_ref_agrees_with_finite_differences():
     assert not gx[1, :, 4:].any()
 
 
-def test_bars_catch_seeded_defects():
+def test_bars_catch_seeded_defects(nn):
     """an fp32 "kernel result" (torch on the CPU, in the kernels' phase form) with one seeded defect fails its bar by a wide
-    margin; the clean one passes"""
-    rs = np.random.RandomState(3)
-    B, cin, cout, k, s, L, slope = 3, 12, 10, 5, 3, 152, 0.1
-    lengths = [151, 70, 1]  # 151 = 3 x 50 + 1: floor and ceil differ
-    x = torch.from_numpy(rs.randn(B, cin, L).astype(np.float32))
-    x[torch.from_numpy(rs.rand(B, cin, L) < 0.05)] = 0.0
-    w = torch.from_numpy((rs.uniform(-1, 1, (cout, cin, k)) / np.sqrt(cin * k)).astype(np.float32))
-    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32))
-    gy = torch.from_numpy(rs.randn(B, cout, R.out_ld(L, s)).astype(np.float32))
-    r64 = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, s, slope, torch.float32)
+    margin on the ragged lengths tests/test_gpu_conv_strided_grad.py runs; the clean one passes"""
+    spec, slope = H.Spec("strided", 12, 10, 5, 3), 0.1
+    s = spec.p
+    lengths, ld, _ = H.lengths_for(nn, spec)
+    assert any(n % s for n in lengths)  # floor and ceil differ
+    x, w, b, gy = H.case(spec, len(lengths), ld, seed=3)
+    r64 = R.layer_ref(x, w, b, gy, lengths, spec.op, slope, torch.float64)
+    r32 = R.layer_ref(x, w, b, gy, lengths, spec.op, slope, torch.float32)
     for name, kind, y, a, c in zip(("y", "gx", "gw", "gb"), ("act", "act", "weight", "vec"), r32, r64, r32):
         assert not R.check("clean " + name, kind, y.clone(), a, c)
     assert R.taps(5, 3) == [(1, -1), (2, -1), (0, 0), (1, 0), (2, 0)]
-    vi, vo = R.valid_masks(lengths, L, s)
+    vi, vo = R.valid_masks(lengths, ld, spec.op)
     xa = F.leaky_relu(x, slope) * vi
 
     def wide(tag, kind, y, i, margin=10.0):

@@ -93,7 +93,7 @@ def test_layer_ref_agrees_with_finite_differences():
     x = torch.where(x.abs() < 0.05, torch.full_like(x, 0.3), x)  # no kink inside a finite-difference step
     w, b, gy = (torch.from_numpy(rs.randn(*sh)) for sh in ((cin, cout, k), (cout,), (B, cout, s * L)))
     y, gx, gw, gb = R.layer_ref(x, w, b, gy, lengths, R.conv_transpose_op(s), slope, torch.float64)
-    vi, vo = R.valid_masks(lengths, L, s)
+    vi, vo = R.valid_masks(lengths, L, R.conv_transpose_op(s))
     assert not y[(vo == 0).expand_as(y)].any() and not gx[(vi == 0).expand_as(gx)].any()
     assert y[1, :, :s * 4].abs().min() > 0
 
@@ -132,7 +132,7 @@ def test_bars_catch_seeded_defects():
     kinds = ("act", "act", "weight", "vec")
     for name, kind, y, a, c in zip(("y", "gx", "gw", "gb"), kinds, r32, r64, r32):
         assert not R.check("clean " + name, kind, y.clone(), a, c)
-    vi, vo = R.valid_masks(lengths, L, s)
+    vi, vo = R.valid_masks(lengths, L, R.conv_transpose_op(s))
     gym, xa = gy * vo, F.leaky_relu(x, slope) * vi
     mask = torch.where(x > 0, 1.0, slope) * vi
 
@@ -147,7 +147,7 @@ def test_bars_catch_seeded_defects():
     wide("two phases swapped in gw", "weight", R.phase_wgrad(xa, gym, k, s, swap=(0, 2)), 2)
     wide("one phase's plane offset by one in gw", "weight", R.phase_wgrad(xa, gym, k, s, plane_shift=(3, 1)), 2)
     # the mask one column long (t <= len): the column at len of x and the s columns from s len of gy take part
-    vi1, vo1 = R.valid_masks([n + 1 for n in lengths], L, s)
+    vi1, vo1 = R.valid_masks([n + 1 for n in lengths], L, R.conv_transpose_op(s))
     vi1, vo1 = vi1[:, :, :L], vo1[:, :, :s * L]
     wide("t <= len in the weight gradient", "weight", R.phase_wgrad(F.leaky_relu(x, slope) * vi1, gy * vo1, k, s), 2)
     plain = F.conv1d(gym, w, stride=s, padding=pad)  # the data gradient before the mask: a stride-s correlation with w[ci][co][kk]

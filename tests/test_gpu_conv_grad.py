@@ -41,7 +41,7 @@ def _conv1d_host(x, w, b, lengths, d, slope):
                                                 (16, 1, 7, 1, 0.01)])
 def test_device_packing_bit_for_bit(nn, cin, cout, k, d, slope):
     B, ld, lengths = 3, 100, [100, 37, 3]
-    spec = H.Spec(False, cin, cout, k, d)
+    spec = H.Spec("conv1d", cin, cout, k, d)
     x, w, b, gy = H.case(spec, B, ld, seed=cin + k)
     y, gx, _, _, _ = H.gpu_run(nn, spec)(x, w, b, gy, lengths, slope)
     assert torch.equal(y, _conv1d_host(x, w, b, lengths, d, slope))
@@ -57,10 +57,11 @@ LAYERS = [(16, 16, 3, 1), (16, 16, 11, 5), (32, 32, 7, 3), (64, 64, 11, 5), (128
 
 @pytest.mark.parametrize("cin,cout,k,d", LAYERS)
 def test_layer_gradients_against_float64(nn, cin, cout, k, d):
-    spec = H.Spec(False, cin, cout, k, d)
+    spec = H.Spec("conv1d", cin, cout, k, d)
     lengths, ld, plan = H.lengths_for(nn, spec)
     print(f"\nlayer {spec}: lengths {lengths}, ld {ld}, (P, pairs) {plan}")
-    H.assert_layer_gradients(H.gpu_run(nn, spec), spec, lengths, ld, 7 * cin + k + d, k_direct(cin * k), k_direct(cout * k))
+    H.assert_layer_gradients(H.gpu_run(nn, spec), spec, lengths, ld, 7 * cin + k + d, H.k_bars(K_DIRECT, "y", spec),
+                             H.k_bars(K_DIRECT, "gx", spec))
 
 
 # The one exception to K = 4 (tests/train_stage_cases.py's rule): the forward and the data gradient are the direct conv
@@ -73,14 +74,7 @@ def test_layer_gradients_against_float64(nn, cin, cout, k, d):
 #   n = 3 584 (data gradient of 257 -> 512, k = 7): 4.55 / 4.77 (ragged batch), 4.14 / 4.31 (B = 32)  -> 10 / 10 (cap 32)
 #   n = 2 816 (256 -> 256, k = 11, B = 32):          forward 3.11 / 4.70, data gradient 3.78 / 3.81  ->  4 / 10 (cap 32)
 #   n = 1 799 (forward of 257 -> 512, k = 7):        2.40 / 3.54 (ragged batch), 2.03 / 4.06 (B = 32) ->  4 / 9  (cap 32)
-K_DIRECT = {3584: (10.0, 10.0), 2816: (4.0, 10.0), 1799: (4.0, 9.0)}  # n -> (whole, worst channel)
-
-
-def k_direct(n):
-    kw, kc = K_DIRECT.get(n, (R.K_WHOLE, R.K_CH))
-    assert max(kw, kc) <= R.k_cap(n)
-    return kw, kc
-
+K_DIRECT = {3584: (10.0, 10.0), 2816: (4.0, 10.0), 1799: (4.0, 9.0)}  # n -> (whole, worst channel); the rule: H.k_bars
 
 TRAIN = [(16, 16, 11, 5, 8960), (256, 256, 11, 5, 140), (257, 512, 7, 1, 28)]
 
@@ -89,9 +83,10 @@ TRAIN = [(16, 16, 11, 5, 8960), (256, 256, 11, 5, 140), (257, 512, 7, 1, 28)]
 def test_training_shapes(nn, cin, cout, k, d, L):
     """B = 32 at the generator's own lengths (28 frames): the 286 720-long reduction of the narrowest stage, the widest
     ResBlock layer, conv_pre"""
-    spec = H.Spec(False, cin, cout, k, d)
-    print(f"\ntraining shape {spec} L {L}: plan {H.partials(nn, spec, 32, L)}")
-    H.assert_training_shape(H.gpu_run(nn, spec), spec, L, k_direct(cin * k), k_direct(cout * k))
+    spec = H.Spec("conv1d", cin, cout, k, d)
+    print(f"\ntraining shape {spec} L {L}: plan {spec.partials(nn, 32, L)}")
+    H.assert_training_shape(H.gpu_run(nn, spec), spec, H.training_lengths(32, L, (1, 5, 17, 31)), L, L + k,
+                            H.k_bars(K_DIRECT, "y", spec), H.k_bars(K_DIRECT, "gx", spec))
 
 
 @pytest.mark.parametrize("C,k", [(32, 7), (16, 11)])
@@ -124,8 +119,9 @@ def test_resblock1_against_float64_with_the_engines_masks(nn, C, k):
     R.resblock1_ref(w, x, k, dil, torch.float64, lengths=lengths, taps=own)
     differ = sum(int((((t > 0) != m) & valid).sum()) for t, m in zip(own, masks))
     print(f"\nresblock1 C {C} k {k}: mask positions where float64's own sign differs: {differ} of {6 * int(valid.sum()) * C}")
-    bad = R.check("block y", "act", y.detach(), y64, y32, *k_direct(C * k))
-    bad += R.check("block gx", "act", xd.grad, gx64, gx32, *k_direct(C * k))
+    block = H.Spec("conv1d", C, C, k, 1)  # every conv of the block: chains of C k products
+    bad = R.check("block y", "act", y.detach(), y64, y32, *H.k_bars(K_DIRECT, "y", block))
+    bad += R.check("block gx", "act", xd.grad, gx64, gx32, *H.k_bars(K_DIRECT, "gx", block))
     for n in sorted(w):
         bad += R.check("block grad " + n, "weight" if n.endswith("weight") else "vec", wd[n].grad, g64[n], g32[n])
     assert not bad, bad

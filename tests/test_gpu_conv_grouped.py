@@ -3,18 +3,17 @@ packing, every gradient of the layer against torch in float64 under the bars of 
 around the stride, the halo, the chunk and a partial boundary; the six grouped layers of DiscriminatorS at full channel count and
 three small shapes), the layers at the trainer's row lengths, the pool against its stated fp32 expression, and DiscriminatorS end
 to end against its float64 restatement.  Measured ratios: profiles/conv_grouped_grad.md."""
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+import conv_grad_harness as H
 import conv_grouped_ref as R
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+DEV = H.DEV
 
 
 @pytest.fixture(scope="module")
@@ -25,33 +24,8 @@ def nn():
     return nn
 
 
-def case(cin, cout, k, s, g, B, ld, seed, bias=True):
-    rs = np.random.RandomState(seed)
-    x = torch.from_numpy(rs.randn(B, cin, ld).astype(np.float32))
-    x[torch.from_numpy(rs.rand(B, cin, ld) < 0.02)] = 0.0  # exact zeros: the x = 0 branch is the slope
-    w = torch.from_numpy((rs.uniform(-1, 1, (cout, cin // g, k)) / np.sqrt(cin // g * k)).astype(np.float32))
-    b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)) if bias else None
-    gy = torch.from_numpy(rs.randn(B, cout, R.out_ld(ld, s)).astype(np.float32))
-    return x, w, b, gy
-
-
-def run(nn, s, g, x, w, b, gy, lengths, slope, need=(True, True, True), nan_workspace=False):
-    """one forward + backward of nn.conv1d_grouped on the device; returns [y, gx, gw, gb], None where there is none"""
-    xd = x.to(DEV).requires_grad_(need[0])
-    wd = w.to(DEV).requires_grad_(need[1])
-    bd = None if b is None else b.to(DEV).requires_grad_(need[2])
-    ln = None if lengths is None else torch.tensor(lengths, dtype=torch.int32, device=DEV)
-    y = nn.conv1d_grouped(xd, wd, bd, stride=s, groups=g, lengths=ln, in_slope=slope)
-    if nan_workspace:
-        for ws in nn._workspaces.values():
-            ws.fill_(255)  # every float of the workspace a NaN
-    y.backward(gy.to(DEV))
-    torch.cuda.synchronize()
-    return [y.detach().cpu()] + [None if t is None or t.grad is None else t.grad.cpu() for t in (xd, wd, bd)]
-
-
 # ---- the packings -------------------------------------------------------------------------------------------------------
-def _host_packing(w, g, which):
+def _host_packing(w, which, g):
     """include/dissc_hip.h, dissc_convggrad_packed"""
     cout, cig, k = w.shape
     cog, pad = cout // g, (k - 1) // 2
@@ -68,22 +42,7 @@ def _host_packing(w, g, which):
 
 @pytest.mark.parametrize("cin,cout,k,s,g", R.DISC_S[:4] + R.SMALL + [(40, 96, 5, 2, 1)])
 def test_device_packing_bit_for_bit(nn, cin, cout, k, s, g):
-    from dissc_amd import _lib
-    lib = _lib.lib
-    lib.dissc_convggrad_packed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    lib.dissc_convggrad_packed.restype = ctypes.c_longlong
-    x, w, b, gy = case(cin, cout, k, s, g, 1, 16, seed=cin + k)
-    h = nn._handle(nn.CONV1D_GROUPED, cin, cout, k, s, torch.device(DEV), g)
-    wd = w.to(DEV)
-    _lib.check(nn.CONV1D_GROUPED.set_weights(h, wd.data_ptr(), None, None), "dissc_convggrad_set_weights")
-    for which in (0, 1):
-        host = _host_packing(w, g, which)
-        n = lib.dissc_convggrad_packed(h, which, None, None)
-        assert n == host.size
-        dst = torch.full((n,), float("nan"), device=DEV)
-        assert lib.dissc_convggrad_packed(h, which, dst.data_ptr(), None) == n
-        torch.cuda.synchronize()
-        assert np.array_equal(dst.cpu().numpy().view(np.uint32), host.reshape(-1).view(np.uint32))
+    H.assert_device_packing(nn, H.Spec("grouped", cin, cout, k, s, g), functools.partial(_host_packing, g=g))
 
 
 # ---- the layer ----------------------------------------------------------------------------------------------------------
@@ -94,79 +53,16 @@ def test_device_packing_bit_for_bit(nn, cin, cout, k, s, g):
 # None is needed: the kernels keep four accumulators per output and add them in a fixed order, so the longest chain of one
 # output is 2 624 / 4 = 656 products (convs.5, y and gx), below the rule's 1 024; every measured ratio is in
 # profiles/conv_grouped_grad.md.
-K_EXC = {}
-
-
-def _k(tensor, cin, cout, k, s, g):
-    kw, kc = K_EXC.get((tensor, cin, cout, k, s, g), (R.K_WHOLE, R.K_CH))
-    n = cin // g * k if tensor == "y" else cout // g * R.cdiv(k, s)
-    assert tensor in ("y", "gx") and (max(kw, kc) <= 4 or (n >= 1024 and max(kw, kc) <= R.k_cap(n)))
-    return kw, kc
-
-
-def lengths_for(nn, cin, cout, k, s, g, max_b=None):
-    """INPUT lengths with T = 64 s (one chunk of the weight gradient): 1, 2, s, s + 1, 20, 21, 41 (the halo and the kernel), T - 1,
-    T, T + 1, 2 T + 1, one of each residue mod s next to 2 T, and, where the plan has one inside an utterance, a length on either
-    side of a partial boundary (placed in the utterance the boundary falls in), as test_gpu_conv_strided_grad.lengths_for does.
-    max_b = 4 (the two widest layers): s + 1, 2 T - 1 and the last two of the list."""
-    T = nn.WGRAD_CHUNK * s
-    lengths = [1, 2, s, s + 1, 20, 21, 41, T - 1, T, T + 1, 2 * T + 1] + [2 * T - r for r in range(s)] + [T, 2 * T + 1]
-    if max_b is not None:
-        assert max_b == 4
-        lengths = [s + 1, 2 * T - 1, T, 2 * T + 1]
-    B, ld = len(lengths), R.ceil4(2 * T + 1)
-    P, pairs = nn.wgrad_partials_grouped(B, ld, cin, cout, k, s, g)
-    nch = R.cdiv(R.cdiv(ld, s), nn.WGRAD_CHUNK)
-    inside = [divmod(p * pairs, nch) for p in range(1, P) if (p * pairs) % nch]
-    if inside:
-        b, c = inside[len(inside) // 2]
-        lengths[-2], lengths[-1] = c * T, c * T + 1  # c chunks of outputs exactly, and one output more
-        lengths[b], lengths[-1] = lengths[-1], lengths[b]  # this utterance's chunk c belongs to the next partial
-    return lengths, ld, (P, pairs)
-
-
-def assert_layer_gradients(run, cin, cout, k, s, g, lengths, ld, seed, k_y, k_gx, slope=0.1):
-    """the four bars on a ragged batch; nothing beyond the lengths; every result bit-reproducible, also behind a workspace full of
-    NaNs; poison beyond the lengths changes nothing; the five needs_input_grad combinations keep the others' bits; every utterance
-    alone has the batch's y and gx bits."""
-    B = len(lengths)
-    x, w, b, gy = case(cin, cout, k, s, g, B, ld, seed)
-    vi, vo = R.valid_masks(lengths, ld, s)
-    run = functools.partial(run, lengths=lengths, slope=slope)
-    y, gx, gw, gb = run(x, w, b, gy)
-    r64 = R.layer_ref(x, w, b, gy, lengths, s, g, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, s, g, slope, torch.float32)
-    bad = R.check("batch y", "act", y, r64[0], r32[0], *k_y)
-    bad += R.check("batch gx", "act", gx, r64[1], r32[1], *k_gx)
-    bad += R.check("batch gw", "weight", gw, r64[2], r32[2])
-    bad += R.check("batch gb", "vec", gb, r64[3], r32[3])
-    assert not gx[(vi == 0).expand_as(gx)].any() and not y[(vo == 0).expand_as(y)].any(), "written or propagated beyond the lengths"
-    for name, t, q in zip(("y", "gx", "gw", "gb"), (y, gx, gw, gb), run(x, w, b, gy)):
-        assert torch.equal(q, t), f"{name} is not bit-reproducible"
-    for name, t, q in zip(("y", "gx", "gw", "gb"), (y, gx, gw, gb), run(x, w, b, gy, nan_workspace=True)):
-        assert torch.equal(q, t), f"a workspace full of NaNs changes {name}"
-    xp, gyp = x.clone(), gy.clone()
-    xp[(vi == 0).expand_as(x)] = 1e30
-    gyp[(vo == 0).expand_as(gy)] = 1e30
-    for name, t, q in zip(("y", "gx", "gw", "gb"), (y, gx, gw, gb), run(xp, w, b, gyp)):
-        assert torch.equal(q, t), f"poison beyond the lengths changes {name}"
-    for need in ((False, True, True), (True, False, True), (True, True, False), (True, False, False), (False, False, True)):
-        for name, t, q, on in zip(("gx", "gw", "gb"), (gx, gw, gb), run(x, w, b, gy, need=need)[1:4], need):
-            assert (torch.equal(q, t) if on else q is None), f"needs_input_grad {need}: {name}"
-    for i, n in enumerate(lengths):
-        sl = slice(i, i + 1)
-        yi, gxi, _, _ = run(x[sl], w, b, gy[sl], lengths=[n])
-        assert torch.equal(gxi, gx[sl]), ("alone gx differs from the batch's", i, n)
-        assert torch.equal(yi, y[sl]), ("alone y differs from the batch's", i, n)
-    assert not bad, bad
+K_EXC = {}  # the rule: H.k_bars
 
 
 @pytest.mark.parametrize("cin,cout,k,s,g", R.DISC_S + R.SMALL)
 def test_layer_gradients_against_float64(nn, cin, cout, k, s, g):
-    lengths, ld, plan = lengths_for(nn, cin, cout, k, s, g, max_b=4 if cout >= 1024 else None)
-    print(f"\nlayer {cin} -> {cout} k {k} s {s} g {g}: lengths {lengths}, ld {ld}, (P, pairs) {plan}")
-    assert_layer_gradients(functools.partial(run, nn, s, g), cin, cout, k, s, g, lengths, ld, 7 * cin + k + s,
-                           _k("y", cin, cout, k, s, g), _k("gx", cin, cout, k, s, g))
+    spec = H.Spec("grouped", cin, cout, k, s, g)
+    lengths, ld, plan = H.lengths_for(nn, spec, max_b=4 if cout >= 1024 else None)
+    print(f"\nlayer {spec}: lengths {lengths}, ld {ld}, (P, pairs) {plan}")
+    H.assert_layer_gradients(H.gpu_run(nn, spec), spec, lengths, ld, 7 * cin + k + s, H.k_bars(K_EXC, "y", spec),
+                             H.k_bars(K_EXC, "gx", spec))
 
 
 @pytest.mark.parametrize("layer", range(6))
@@ -174,20 +70,10 @@ def test_training_shape(nn, layer):
     """2 x 2 rows at the layer's own scale-0 row length, two rows shorter: the kernels' tile walk over a long row; the four bars,
     every result bit-reproducible"""
     (cin, cout, k, s, g), L = R.DISC_S[layer], R.TRAIN_L[layer]
-    B, ld, slope = 4, R.ceil4(L), 0.1
-    lengths = [L, L // 2 + 1, L, max(1, L // 3)]
-    x, w, b, gy = case(cin, cout, k, s, g, B, ld, seed=L + k)
-    y, gx, gw, gb = run(nn, s, g, x, w, b, gy, lengths, slope)
-    r64 = R.layer_ref(x, w, b, gy, lengths, s, g, slope, torch.float64)
-    r32 = R.layer_ref(x, w, b, gy, lengths, s, g, slope, torch.float32)
-    print(f"\ntraining shape {cin} -> {cout} L {L}: plan {nn.wgrad_partials_grouped(B, ld, cin, cout, k, s, g)}")
-    bad = R.check("train y", "act", y, r64[0], r32[0], *_k("y", cin, cout, k, s, g))
-    bad += R.check("train gx", "act", gx, r64[1], r32[1], *_k("gx", cin, cout, k, s, g))
-    bad += R.check("train gw", "weight", gw, r64[2], r32[2])
-    bad += R.check("train gb", "vec", gb, r64[3], r32[3])
-    for name, t, q in zip(("y", "gx", "gw", "gb"), (y, gx, gw, gb), run(nn, s, g, x, w, b, gy, lengths, slope)):
-        assert torch.equal(q, t), f"{name} is not bit-reproducible"
-    assert not bad, bad
+    spec, lengths = H.Spec("grouped", cin, cout, k, s, g), [L, L // 2 + 1, L, max(1, L // 3)]
+    print(f"\ntraining shape {cin} -> {cout} L {L}: plan {spec.partials(nn, 4, R.ceil4(L))}")
+    H.assert_training_shape(H.gpu_run(nn, spec), spec, lengths, R.ceil4(L), L + k, H.k_bars(K_EXC, "y", spec),
+                            H.k_bars(K_EXC, "gx", spec))
 
 
 # ---- the pool -----------------------------------------------------------------------------------------------------------
@@ -249,16 +135,6 @@ def test_mean_pool(nn):
 
 
 # ---- DiscriminatorS end to end ------------------------------------------------------------------------------------------
-def _loss(maps, hats, mask):
-    """mean((1 - score)^2) over the valid scores + 2 sum_l mean |lrelu(f_l) - lrelu(fhat_l)| (the score map as it is), torch ops"""
-    score = maps[7]
-    loss = (((1 - score) ** 2) * mask[7]).sum() / mask[7].sum()
-    for j, (f, fh) in enumerate(zip(maps, hats)):
-        a, c = (f, fh) if j == 7 else (F.leaky_relu(f, R.SLOPE), F.leaky_relu(fh, R.SLOPE))
-        loss = loss + 2 * (a - c).abs().sum() / (mask[j].sum() * f.shape[1])
-    return loss
-
-
 def test_discriminator_s_end_to_end(nn):
     B, T, lengths = 2, 1028, [1028, 771]
     rs = np.random.RandomState(11)
@@ -271,7 +147,7 @@ def test_discriminator_s_end_to_end(nn):
     wavd = wav.to(DEV).requires_grad_(True)
     score, fmaps, lens = nn.discriminator_s(wavd, wd, lengths)
     assert score is fmaps[7] and len(fmaps) == 8 and len(lens) == 8
-    _loss(fmaps, [h.to(DEV) for h in hats], [m.to(DEV) for m in masks]).backward()
+    H.disc_loss(fmaps, [h.to(DEV) for h in hats], [m.to(DEV) for m in masks]).backward()
     torch.cuda.synchronize()
     for j, (ln, m) in enumerate(zip(lens, masks)):
         assert ln.cpu().tolist() == [R.map_lengths(n)[j] for n in lengths] == m[:, 0].sum(1).long().tolist()
@@ -281,7 +157,7 @@ def test_discriminator_s_end_to_end(nn):
         wr = {n: t.to(dtype).requires_grad_(True) for n, t in w.items()}
         wavr = wav.to(dtype).requires_grad_(True)
         maps = R.disc_s_ragged(wr, wavr, lengths)
-        _loss(maps, [h.to(dtype) for h in hats], [m.to(dtype) for m in masks]).backward()
+        H.disc_loss(maps, [h.to(dtype) for h in hats], [m.to(dtype) for m in masks]).backward()
         ref[dtype] = ([m.detach() for m in maps], wavr.grad, {n: t.grad for n, t in wr.items()})
     m64, gwav64, g64 = ref[torch.float64]
     m32, gwav32, g32 = ref[torch.float32]
