@@ -49,6 +49,10 @@ class DisscBf3Info(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("bm", "bn", "small_grid", "tile", "cols", "h4", "pad")]
 
 
+class DisscChainInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("wout", "span", "halo", "lds_bytes", "tiles_per_wave")]
+
+
 class DisscWino8Plan(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("mi", "ni", "wps", "r", "ns", "unit", "ot", "cpr", "gx", "gy")]
 
@@ -132,6 +136,11 @@ def _load():
     L.dissc_wino_info.argtypes = [i32] * 5 + [ctypes.POINTER(DisscWinoPlan)]
     L.dissc_resblock1d_bf3.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, ctypes.c_float, i32, ctypes.c_float, i32, i32, vp]
     L.dissc_bf3_info.argtypes = [i32] * 6 + [vp, i32, i32, ctypes.POINTER(DisscBf3Info)]
+    if hasattr(L, "dissc_reschain1d"):  # (an older build loaded through DISSC_HIP_LIB for an A/B, tools/lib_ab.sh, has none of the three)
+        # x, w6, b6, y, acc, lengths | B, C, k | dil3 | ld, Lmax | slope | epi | mrf_div | mode | stream
+        L.dissc_reschain1d.argtypes = [vp] * 6 + [i32] * 3 + [vp, i32, i32, ctypes.c_float, i32, ctypes.c_float, i32, vp]
+        L.dissc_chain_info.argtypes = [i32, i32, vp, ctypes.POINTER(DisscChainInfo)]
+        L.dissc_chain_bench.argtypes = [i32] * 6 + [ctypes.POINTER(ctypes.c_float)]
     L.dissc_respair1d.argtypes = [vp] * 8 + [i32] * 6 + [ctypes.c_float, i32, ctypes.c_float, i32, vp]
     L.dissc_wav_postprocess.argtypes = [vp, vp, i32, i32, vp]
     L.dissc_pitch_stats.argtypes = [vp, vp, i32, vp, vp, vp, vp]

@@ -54,7 +54,8 @@ void set_error(const char* fmt, ...);
   X(pair_f23, 3, "pair_f23") \
   X(pair_tc6, 3, "pair_tc6") \
   X(pair_f23_c64, 1, "pair_f23_c64") \
-  X(pair_tc6_c64, 1, "pair_tc6_c64")
+  X(pair_tc6_c64, 1, "pair_tc6_c64") \
+  X(chain_f23, 3, "chain_f23")
 // options of the kernels that only DISSC_EXPERIMENTAL=1 builds carry (experimental/csrc: gates failed, kept for the record)
 #define DISSC_OPTION_LIST_EXPERIMENTAL(X) \
   X(graphs, 0, "graphs") \
@@ -426,6 +427,17 @@ int make_pairw(const float* w1, const float* b1, const float* w2, const float* b
 void free_pairw(DevPairW& pw);
 int launch_respair_wino(const DevPairW& pw, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld, float slope,
                         hipStream_t stream);
+
+// a whole k = 3 ResBlock -- three pairs, dilations (1, 3, 5) -- per launch, every conv as register-only F(2,3), x_1 / x_2 kept on
+// the CU (reschain32_f23_kernel in respair_f23.hip, reschain16_f23_kernel in respair16_f23.hip; host side: pair_host.hip)
+struct ChainInfo { int wout, span, halo, lds_bytes, tiles_per_wave; };  // owned outputs, computed span, halo per side, LDS, column tiles
+bool chain_f23_supported(int C, int KS, const int* dil);
+bool chain_f23_info(int C, int KS, const int* dil, ChainInfo& ci);  // false: no instance
+// the six convs [C,C,3] and biases [C] (or nullptr) in execution order -> one device buffer each, in the kernels' fragment order
+int make_chain_f23(const float* const* w6, const float* const* b6, int C, float** dev_w, float** dev_b);
+// x_3 = the block's output: ep.epi = EPI_RES writes it to out, the MRF modes update ep.acc
+int launch_reschain_f23(const float* w, const float* bias, int C, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld,
+                        float slope, hipStream_t stream);
 
 // one residual pair y = x + conv_1(lrelu(conv_d(lrelu(x)))) per launch, exact fp32 (respair.hip)
 bool respair_supported(int C, int KS, int dil);

@@ -208,6 +208,127 @@ int dissc_respair1d(const float* x, const float* w1_host, const float* b1_host, 
   return drained(rc, (hipStream_t)stream);
 }
 
+// Diagnostics / tests: ONE k = 3 ResBlock -- three residual pairs, dilations dil3 -- on device data with host weights [C,C,k] and
+// biases [C] in execution order (c1_0, c2_0, c1_1, c2_1, c1_2, c2_2): y (EPI_RES) or acc (the MRF modes) = the block's output.
+// mode 0 = three launches, each pair in the one-launch form the generator gives it without "chain_f23" (the register-only form
+// pair_reg_form names, else the direct fused pair), x_1 / x_2 through scratch; mode 1 = the one-launch F(2,3) chain
+// (reschain32/16_f23_kernel), which refuses a shape without an instance before anything is packed or written.  Synchronous.
+struct ChainDiag {
+  DiagScope pair[3];
+  int pmode[3] = {0, 0, 0};
+  float *w = nullptr, *b = nullptr, *s1 = nullptr, *s2 = nullptr;
+  ~ChainDiag() {
+    for (float* q : {w, b, s1, s2})
+      if (q) (void)hipFree(q);
+  }
+};
+static int chain_make(int mode, const float* const* w6, const float* const* b6, int C, int k, const int* dil, size_t scratch_floats,
+                      ChainDiag& cd) {
+  if (mode == 1) {
+    if (!chain_f23_supported(C, k, dil)) {
+      set_error("chain mode 1: no instance for C = %d, k = %d, dilations (%d, %d, %d)", C, k, dil[0], dil[1], dil[2]);
+      return DISSC_EINVAL;
+    }
+    return make_chain_f23(w6, b6, C, &cd.w, &cd.b);
+  }
+  if (mode != 0) {
+    set_error("chain mode %d", mode);
+    return DISSC_EINVAL;
+  }
+  for (int m = 0; m < 3; ++m) {
+    cd.pmode[m] = pair_reg_form(C, k, dil[m]) ? 3 : 1;
+    if (cd.pmode[m] == 1 && !respair_supported(C, k, dil[m])) {
+      set_error("chain mode 0: no one-launch pair for C = %d, k = %d, dilation %d", C, k, dil[m]);
+      return DISSC_EINVAL;
+    }
+    const int rc = pair_make(cd.pmode[m], w6[2 * m], b6[2 * m], w6[2 * m + 1], b6[2 * m + 1], C, k, dil[m], cd.pair[m]);
+    if (rc) return rc;
+  }
+  if (hipMalloc(&cd.s1, scratch_floats * sizeof(float)) != hipSuccess || hipMalloc(&cd.s2, scratch_floats * sizeof(float)) != hipSuccess) {
+    set_error("chain mode 0: hipMalloc");
+    return DISSC_ENOMEM;
+  }
+  return DISSC_OK;
+}
+static int chain_run(int mode, const ChainDiag& cd, const float* x, float* y, const Batch& bt, const EpiSpec& ep, int C, int ld, float slope,
+                     hipStream_t st) {
+  if (mode == 1) return launch_reschain_f23(cd.w, cd.b, C, x, y, bt, ep, ld, slope, st);
+  int rc = pair_run(cd.pmode[0], cd.pair[0], x, nullptr, cd.s1, bt, epi_of(EPI_RES), C, ld, slope, st);
+  if (!rc) rc = pair_run(cd.pmode[1], cd.pair[1], cd.s1, nullptr, cd.s2, bt, epi_of(EPI_RES), C, ld, slope, st);
+  if (!rc) rc = pair_run(cd.pmode[2], cd.pair[2], cd.s2, nullptr, y, bt, ep, C, ld, slope, st);
+  return rc;
+}
+
+int dissc_reschain1d(const float* x, const float* const* w6_host, const float* const* b6_host, float* y, float* acc, const int32_t* lengths,
+                     int B, int C, int k, const int32_t* dil3, int ld, int Lmax, float slope, int epi, float mrf_div, int mode,
+                     void* stream) {
+  if (!x || !w6_host || !b6_host || !dil3 || B <= 0 || Lmax <= 0 || ld < Lmax || epi < EPI_RES || epi > EPI_MRF_DIV ||
+      (epi == EPI_RES ? !y || y == x : !acc || acc == x)) {
+    set_error("dissc_reschain1d: bad argument");
+    return DISSC_EINVAL;
+  }
+  for (int l = 0; l < 6; ++l)
+    if (!w6_host[l] || !b6_host[l]) {
+      set_error("dissc_reschain1d: weight or bias %d is null", l);
+      return DISSC_EINVAL;
+    }
+  const int dil[3] = {dil3[0], dil3[1], dil3[2]};
+  ChainDiag cd;
+  int rc = chain_make(mode, w6_host, b6_host, C, k, dil, (size_t)B * C * ld, cd);
+  if (!rc) rc = chain_run(mode, cd, x, y, batch_of(lengths, 1, B, Lmax), epi_of(epi, nullptr, acc, mrf_div), C, ld, slope, (hipStream_t)stream);
+  return drained(rc, (hipStream_t)stream);
+}
+
+// Diagnostics: the geometry of the one-launch chain of a (C, k, dil3) block.  Host only: no HIP call.
+int dissc_chain_info(int C, int k, const int32_t* dil3, DisscChainInfo* out) {
+  ChainInfo ci;
+  const int dil[3] = {dil3 ? dil3[0] : 0, dil3 ? dil3[1] : 0, dil3 ? dil3[2] : 0};
+  if (!chain_f23_info(C, k, dil, ci)) {
+    set_error("dissc_chain_info: no instance for C = %d, k = %d, dilations (%d, %d, %d)", C, k, dil[0], dil[1], dil[2]);
+    return DISSC_EINVAL;
+  }
+  if (out) {
+    out->wout = ci.wout; out->span = ci.span; out->halo = ci.halo; out->lds_bytes = ci.lds_bytes; out->tiles_per_wave = ci.tiles_per_wave;
+  }
+  return DISSC_OK;
+}
+
+// Diagnostics: average ms of `iters` launches of one k = 3, dilations (1, 3, 5) block (modes as dissc_reschain1d) on synthetic data.
+int dissc_chain_bench(int B, int C, int L, int epi, int iters, int mode, float* ms_out) {
+  if (!ms_out || B <= 0 || L <= 0 || iters <= 0 || epi < EPI_RES || epi > EPI_MRF_DIV) {
+    set_error("dissc_chain_bench: bad argument");
+    return DISSC_EINVAL;
+  }
+  const int k = 3, dil[3] = {1, 3, 5};
+  std::vector<float> w[6], bias(C, 0.1f);
+  const float *w6[6], *b6[6];
+  Lcg rnd;
+  for (int l = 0; l < 6; ++l) {
+    w[l].resize((size_t)C * C * k);
+    rnd.fill(w[l], 0.05f);
+    w6[l] = w[l].data();
+    b6[l] = bias.data();
+  }
+  const int ld = (L + 3) / 4 * 4;
+  const size_t n = (size_t)B * C * ld;
+  ChainDiag cd;
+  int rc = chain_make(mode, w6, b6, C, k, dil, n, cd);
+  if (rc) return rc;
+  DiagScope ds;
+  float *x = nullptr, *y = nullptr, *a = nullptr;
+  std::vector<float> hx(n);
+  rnd.fill(hx, 2.f);
+  if (ds.alloc(&x, n) != hipSuccess || ds.alloc(&y, n) != hipSuccess || ds.alloc(&a, n) != hipSuccess ||
+      hipMemcpy(x, hx.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemset(a, 0, n * 4) != hipSuccess ||
+      ds.events() != hipSuccess) {
+    set_error("dissc_chain_bench: allocation failed");
+    return DISSC_ENOMEM;
+  }
+  const Batch bt = batch_of(nullptr, 1, B, L);
+  const EpiSpec ep = epi_of(epi, nullptr, a, 3.f);
+  return time_launches(ds, iters, [&]() { return chain_run(mode, cd, x, y, bt, ep, C, ld, 0.1f, nullptr); }, ms_out);
+}
+
 // Diagnostics / tests: residual pairs [m0, m1) of ONE ResBlock1 in split-bf16 arithmetic on resblock_bf3_kernel, as the generator
 // launches it under "precision" = 1: the whole block (m0 = 0, m1 = 3) or a pair at a time, chained through EPI_STORE.  x / acc on
 // the device, the six weights [C,C,k] and biases [C] on the host in execution order (c1_0, c2_0, c1_1, c2_1, c1_2, c2_2).  Synchronous.

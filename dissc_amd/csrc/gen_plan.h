@@ -14,6 +14,7 @@ enum class ChainForm : uint8_t {
   pairs,      // three pair launches or launch pairs, each in its own PairForm
   bf3_block,  // split-bf16: the whole block in one launch (resblock_bf3.hip)
   bf3_pairs,  // split-bf16: the block as three pair launches of the same kernel
+  f23_chain,  // fp32: the k = 3 block in one register-only F(2,3) launch (reschain32/16_f23_kernel); pair[] = the plan without it
 };
 enum class PairForm : uint8_t {
   direct,      // two direct convs, t through the chain's TMP buffer
@@ -39,6 +40,7 @@ ConvForm td_conv_form(int C, int KS, int dil);  // the transform-domain form of 
 int pair_reg_form(int C, int KS, int dil);      // the register-only form of a pair (DevPairW::form: 1 F(2,3), 2 six points), or 0
 ChainPlan plan_chain(int C, int KS, const int* dil, int prec);
 double pair_macs(const PairPlan& p, int C, int KS, bool executed);  // multiply-adds per output position of one pair: algorithmic, or executed
+double chain_macs(const ChainPlan& cp, int C, int KS, bool executed);  // ... of a whole chain in its form
 int make_pair_conv(ConvForm f, const float* w, const float* b, int C, int KS, int dil, DevConv& dc);  // packed for its form
 // The MRF epilogue of chain j's last launch: xs = r_0; xs += r_j; x = (xs + r_last) / nk
 inline int mrf_epi(int j, int nk) { return j == nk - 1 ? EPI_MRF_DIV : j == 0 ? EPI_MRF_SET : EPI_MRF_ADD; }

@@ -63,6 +63,18 @@ ConvForm td_conv_form(int C, int KS, int dil) {
 //   810 / 869 / 950 us against 979 / 1 117 / 1 095 for the two launches, forward 31.89-32.06 -> 31.43-31.65 ms (five alternated
 //   runs); k = 11 1 210 / 1 307 / 1 465 against 1 251 / 1 318 / 1 317, forward slower with bit 2 than without: off
 //   (profiles/r10).
+// option "chain_f23" (default 3), a bit mask honoured only for fp32 handles while "wino" != 0, "pair_f23" != 0 and the stage is within
+//   "pair_max_c" (a chain is a one-launch form like the pairs it replaces): 1 = the
+//   k = 3, dilations (1, 3, 5) ResBlock of the 32-channel stage, 2 = that of the 16-channel stage runs as ONE register-only F(2,3)
+//   launch (reschain32_f23_kernel in respair_f23.hip, reschain16_f23_kernel in respair16_f23.hip): 2 C^2 products per output and
+//   conv where the three direct pairs it replaces execute 3 C^2, x_1 / x_2 and the residuals never leave the CU.  0 = three
+//   one-launch pairs in the forms pair_reg_form() gives.  A chain-level choice: it does not enter pair_reg_form or dissc_pair_info.
+//   Measurements: profiles/r14.
+static bool chain_f23_wanted(int C, int KS, const int* dil, int prec) {
+  const int bit = C == 32 ? 1 : C == 16 ? 2 : 0;
+  return prec == 0 && opts().wino && opts().pair_f23 && C <= opts().pair_max_c && (opts().chain_f23 & bit) && chain_f23_supported(C, KS, dil);
+}
+
 int pair_reg_form(int C, int KS, int dil) {
   if (C == 64) {
     if (opts().pair_f23 == 0) return 0;
@@ -128,7 +140,15 @@ ChainPlan plan_chain(int C, int KS, const int* dil, int prec) {
       p.form = PairForm::direct_dma;
     }
   }
+  if (chain_f23_wanted(C, KS, dil, prec)) cp.form = ChainForm::f23_chain;
   return cp;
+}
+
+double chain_macs(const ChainPlan& cp, int C, int KS, bool executed) {
+  if (executed && cp.form == ChainForm::f23_chain) return 3 * 2 * 2.0 * C * C;  // F(2,3): 4 products per 2 outputs, six convs
+  double macs = 0;
+  for (const PairPlan& p : cp.pair) macs += pair_macs(p, C, KS, executed);
+  return macs;
 }
 
 double pair_macs(const PairPlan& p, int C, int KS, bool executed) {

@@ -54,7 +54,8 @@ struct dissc_gen {
   std::vector<ChainPlan> plan;     // [stage*nk + j]: the kernel forms of ResBlock j of the stage
   std::vector<DevConv> rb1, rb2;  // [stage*nk*3 + j*3 + m]: conv_d / conv_1 of pair m (forms direct, direct_dma, td, fused)
   std::vector<DevPairW> pw;       // same index: the pair as ONE transform-domain launch (form fused_td)
-  std::vector<float*> fused_w, fused_b;  // [stage*nk + j]: 6 packed convs / biases of a split-bf16 ResBlock (bf3_* chains)
+  std::vector<float*> fused_w, fused_b;  // [stage*nk + j]: 6 packed convs / biases of a split-bf16 ResBlock (bf3_* chains) or of a
+                                         // one-launch F(2,3) chain (f23_chain)
   float* post_w = nullptr;
   float* post_b = nullptr;
   int post_C = 0, post_KS = 0;
@@ -218,6 +219,11 @@ int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, s
         snprintf(name, sizeof(name), "resblocks.%d.convs%d.%d.bias", (int)cj, 1 + l % 2, l / 2);
         if ((rc = get(name, {ch}, &b6[l]))) return fail(rc);
       }
+      if (cp.form == ChainForm::f23_chain) {  // the six convs transformed and packed together
+        const std::vector<const float*> wv(w6, w6 + 6), bv(b6, b6 + 6);
+        tasks.push_back([=]() { return make_chain_f23(wv.data(), bv.data(), ch, &g->fused_w[cj], &g->fused_b[cj]); });
+        continue;
+      }
       if (cp.form != ChainForm::pairs) {  // split-bf16: the six convs packed together
         std::vector<float> fw, fb;
         pack_resblock_bf3(ch, rk, w6, fw);
@@ -301,8 +307,7 @@ static double gen_macs(const dissc_gen* g, bool executed) {
     for (auto& c : g->ups[i]) macs += c.macs_per_t * mul;
     mul = g->stage_mul[i];
     for (int j = 0; j < nk; ++j)
-      for (const PairPlan& p : g->plan[(size_t)i * nk + j].pair)
-        macs += pair_macs(p, g->stage_C[i], g->cfg.resblock_kernel_sizes[j], executed) * mul;
+      macs += chain_macs(g->plan[(size_t)i * nk + j], g->stage_C[i], g->cfg.resblock_kernel_sizes[j], executed) * mul;
   }
   macs += (double)g->post_C * g->post_KS * mul;
   return macs;
@@ -462,6 +467,11 @@ static int gen_forward_body(dissc_gen_t g, const int64_t* code, const float* f0,
       };
       if (cp.form == ChainForm::bf3_block) {  // the whole ResBlock in one launch
         if ((rc = acc_turn()) || (rc = launch_resblock_bf3(bf3, X, bt, mrf, ld, 0.1f, 0, 3, sj))) return rc;
+        if (multi) DISSC_HIP_CHECK(hipEventRecord(g->ev_fin[j], sj));
+        continue;
+      }
+      if (cp.form == ChainForm::f23_chain) {  // the whole ResBlock in one launch, x_1 / x_2 on the CU
+        if ((rc = acc_turn()) || (rc = launch_reschain_f23(g->fused_w[cj], g->fused_b[cj], ch, X, nullptr, bt, mrf, ld, 0.1f, sj))) return rc;
         if (multi) DISSC_HIP_CHECK(hipEventRecord(g->ev_fin[j], sj));
         continue;
       }

@@ -3,6 +3,8 @@
 //           k = 3 pairs at C = 64 (respair64_f23_kernel, option "pair_f23_c64");
 //   form 2: the register-only six-point F(3,4) pairs (respair_f23.hip) -- the default for k = 7 / 11 at C = 32, and the
 //           k = 7 / 11 pairs at C = 64 (respair64_tc6_kernel, option "pair_tc6_c64");
+//   chains: the k = 3 ResBlocks of the 16- / 32-channel stages as ONE register-only F(2,3) launch (reschain16_f23_kernel,
+//           reschain32_f23_kernel; option "chain_f23"): make_chain_f23, launch_reschain_f23, chain_f23_info;
 //   form 0: the F(4,3) pair kernel with the Y exchange through LDS (experimental/csrc/respair_wino.hip: its gate FAILED in round 4,
 //           it is in DISSC_EXPERIMENTAL=1 builds only; experimental_stubs.hip answers for it otherwise).
 #include <string.h>
@@ -118,6 +120,52 @@ static int pack_pair_reg(const float* w, float** dev, int C, int KS, int form) {
   return upload(packed, dev);
 }
 
+// ---- the k = 3 chains (reschain32_f23_kernel, reschain16_f23_kernel): six convs and six biases in one buffer each ----
+bool chain_f23_supported(int C, int KS, const int* dil) {
+  return (C == 16 || C == 32) && KS == 3 && dil && dil[0] == 1 && dil[1] == 3 && dil[2] == 5;
+}
+
+bool chain_f23_info(int C, int KS, const int* dil, ChainInfo& ci) {
+  if (!chain_f23_supported(C, KS, dil)) return false;
+  auto fill = [&](auto geo) {
+    using G = decltype(geo);
+    ci.wout = G::WOUT; ci.span = G::NP; ci.halo = G::HALO; ci.lds_bytes = (int)sizeof(float) * G::C * G::XW; ci.tiles_per_wave = G::NI;
+  };
+  if (C == 32) fill(F23ChainGeo32());
+  else fill(F23ChainGeo16());
+  return true;
+}
+
+int make_chain_f23(const float* const* w6, const float* const* b6, int C, float** dev_w, float** dev_b) {
+  if (C != 16 && C != 32) {
+    set_error("make_chain_f23: no instance for C = %d", C);
+    return DISSC_EINVAL;
+  }
+  std::vector<float> packed, bias((size_t)6 * C, 0.f);
+  packed.reserve((size_t)6 * 4 * C * C);
+  for (int l = 0; l < 6; ++l) {
+    const std::vector<float> U = transform_taps(w6[l], C, 3, &kF23G[0][0], 4, 3);  // one sub-filter
+    auto u = [&](int p, int co, int ci) { return U[((size_t)p * C + co) * C + ci]; };
+    if (C == 16) {
+      // reschain16_f23_kernel: [conv 6][point 4][64 lanes][4 k-steps]; lane l, k-step cq -> U_p[l & 15][4 cq + (l >> 4)]
+      for (int p = 0; p < 4; ++p)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int cq = 0; cq < 4; ++cq) packed.push_back(u(p, lane & 15, 4 * cq + (lane >> 4)));
+    } else {
+      // reschain32_f23_kernel: [conv 6][8-channel step 4][point 4][64 lanes][4 k-steps]; lane l, k-step e ->
+      // U_p[l & 31][8 st + 2 e + (l >> 5)]
+      for (int st = 0; st < 4; ++st)
+        for (int p = 0; p < 4; ++p)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int e = 0; e < 4; ++e) packed.push_back(u(p, lane & 31, 8 * st + 2 * e + (lane >> 5)));
+    }
+    if (b6 && b6[l]) memcpy(bias.data() + (size_t)l * C, b6[l], C * sizeof(float));
+  }
+  int rc = upload(packed, dev_w);
+  if (!rc) rc = upload(bias, dev_b);
+  return rc;
+}
+
 int make_pairw(const float* w1, const float* b1, const float* w2, const float* b2, int C, int KS, int dil, int form, DevPairW& pw) {
   pw.form = form;
   if (!pair_form_supported(form, C, KS, dil)) {
@@ -202,6 +250,31 @@ int launch_respair_wino(const DevPairW& pw, const float* x, float* out, const Ba
 #undef DISSC_CASE
   set_error("launch_pair_f23: no instance of form %d for C = %d, k = %d, dilation %d", pw.form, pw.C, pw.KS, pw.dil);
   return DISSC_EINVAL;
+}
+
+template <class Geo, auto Kernel, auto KernelDbg>
+static int launch_chain(const PairArgs& a, int B, int Lmax, hipStream_t stream) {
+  dim3 grid((Lmax + Geo::WOUT - 1) / Geo::WOUT, B);
+  // (the instance with the knock-outs only while "kernel_dbg" asks for one; the buffer is below the 64 KB a kernel gets unasked)
+  hipLaunchKernelGGL(a.dbg ? KernelDbg : Kernel, grid, dim3(256), sizeof(float) * Geo::C * Geo::XW, stream, a);
+  DISSC_HIP_CHECK(hipGetLastError());
+  return DISSC_OK;
+}
+
+int launch_reschain_f23(const float* w, const float* bias, int C, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld,
+                        float slope, hipStream_t stream) {
+  const int B = bt.B, Lmax = bt.Lmax;
+  if (!w || !bias || !x || (C != 16 && C != 32) || ep.epi == EPI_STORE || (ep.epi == EPI_RES ? !out || x == out : !ep.acc || x == ep.acc) ||
+      ld < 4 || ld % 4 || misaligned16(x) || misaligned16(out) || misaligned16(ep.acc) || B <= 0 || Lmax <= 0) {
+    set_error("launch_reschain_f23: bad argument (C=%d ld=%d epi=%d)", C, ld, ep.epi);
+    return DISSC_EINVAL;
+  }
+  PairArgs a;
+  a.x = x; a.out = out; a.acc = ep.acc; a.w1 = w; a.w2 = nullptr; a.b1 = bias; a.b2 = nullptr;
+  a.lengths = bt.lengths; a.len_default = bt.len_default; a.len_mul = bt.len_mul; a.ld = ld;
+  a.bstride = (long long)C * ld; a.slope = slope; a.mrf_div = ep.mrf_div; a.epi = ep.epi; a.dbg = opts().kernel_dbg;
+  if (C == 32) return launch_chain<F23ChainGeo32, reschain32_f23_kernel<false>, reschain32_f23_kernel<true>>(a, B, Lmax, stream);
+  return launch_chain<F23ChainGeo16, reschain16_f23_kernel<false>, reschain16_f23_kernel<true>>(a, B, Lmax, stream);
 }
 
 }  // namespace dissc

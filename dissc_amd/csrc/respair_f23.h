@@ -126,6 +126,57 @@ template <int KS, int DIL> using F23Geo32 = F23Geo<32, 8, KS, DIL>;
 template <int KS, int DIL> using F23Geo16 = F23Geo<16, 16, KS, DIL>;
 template <int KS, int DIL> using F23Geo64 = F23Geo<64, 8, KS, DIL, 32>;
 
+// F(2,3) chains: reschain32_f23_kernel (C = 32, one 32-column tile per wave) and reschain16_f23_kernel (C = 16, four 16-column
+// tiles per wave) run the three pairs of a k = 3 ResBlock, dilations (1, 3, 5), in one launch.  Everything is in BUFFER
+// COORDINATES p <-> time o0 - HALO + p: the workgroup computes conv_1's outputs p in [0, NP) in every pair and owns
+// [HALO, HALO + WOUT); lrelu(x_k) sits at LDS column PADL + p (the staged window is p in [-PADL, XW - PADL)), T at PADL + 1 + p
+// (so conv_1's four samples of an output pair are two aligned 8-byte reads).  Pair m's conv_d produces T on
+// [t0(m), t0(m) + w1(m)): whole units of 2 d positions dealt over the NCOLS columns.  What a column outside a pair's valid range
+// computes is arbitrary but finite, stays inside the buffer and feeds no valid output: covers() walks the ranges.
+template <int C_, int PROWS, int WCOLS>
+struct F23ChainGeo {
+  static constexpr int C = C_, NW = 4, KS = 3, NI = WCOLS / (C_ == 16 ? 16 : 32);
+  static constexpr int NCOLS = WCOLS * NW, NP = 2 * NCOLS;  // pair-columns per conv and workgroup; computed span
+  static constexpr int HALO = 12, PADL = 4;                 // 2 + 4 + 6 per side: d for conv_d and 1 for conv_1 per pair
+  static constexpr int WOUT = NP - 2 * HALO;                // outputs a workgroup owns
+  static constexpr int XW = round32_16(PADL + NP + 8);      // row stride of the one LDS buffer (x window / T / x_k+1 / patches)
+  static constexpr int PW = 2 * WCOLS + 4;                  // patch row: a wave's 2 WCOLS outputs
+  static constexpr int dil(int m) { return 2 * m + 1; }
+  static constexpr int t0(int m) { return m == 0 ? 1 : m == 1 ? 3 : 4; }
+  static constexpr int nc1(int m) { return NCOLS / dil(m) * dil(m); }
+  static constexpr int w1(int m) { return 2 * nc1(m); }
+  // x_0 is valid on the whole staged window; T_m where its three samples are valid x_m; x_m+1 where its three samples are valid
+  // T_m, and only on [0, NP): what is written.  true: every read stays in the row and the owned outputs are valid x_3.
+  static constexpr bool covers() {
+    int a = -PADL, b = XW - PADL;
+    for (int m = 0; m < 3; ++m) {
+      const int d = dil(m), lo = t0(m), hi = t0(m) + w1(m);
+      if (lo - d < -PADL || hi + d > XW - PADL || hi + 1 > XW - PADL) return false;  // conv_d's reads, T's writes
+      const int tlo = lo > a + d ? lo : a + d, thi = hi < b - d ? hi : b - d;
+      a = tlo + 1 > 0 ? tlo + 1 : 0;
+      b = thi - 1 < NP ? thi - 1 : NP;
+    }
+    return a <= HALO && b >= HALO + WOUT;
+  }
+  static_assert(WOUT % 4 == 0 && HALO % 4 == 0 && PADL % 4 == 0, "owned quads are whole");
+  static_assert(PADL + NP + 3 <= XW, "conv_1's reads of T stay in the row");
+  static_assert(NW * PROWS * PW <= C * XW, "the epilogue patches fit the buffer");
+};
+using F23ChainGeo32 = F23ChainGeo<32, 8, 32>;
+using F23ChainGeo16 = F23ChainGeo<16, 16, 64>;
+static_assert(F23ChainGeo32::covers() && F23ChainGeo16::covers(), "each pair's valid range covers what the next pair reads");
+
+// Store tail of the chain kernels: x = conv + bias + residual is complete in registers; n of the quad's elements lie inside
+// the utterance.
+__device__ __forceinline__ void chain_store_tail(const PairArgs& a, int epi, size_t idx, const f32x4& x, int n) {
+  if (n >= 4) {
+    epi_store_res(epi, quad_at(a.out + idx), quad_at(a.acc + idx), x, [&] { return load_quad(a.acc + idx); }, a.mrf_div);
+  } else {
+    for (int e = 0; e < n; ++e)
+      epi_store_res(epi, a.out + idx + e, a.acc + idx + e, x[e], [&] { return a.acc[idx + e]; }, a.mrf_div);
+  }
+}
+
 // six points: respair32_tc6_kernel and respair64_tc6_kernel (the scheme is described in respair_f23.hip).  At C = 64 the two 32-row
 // blocks of a column tile go to a wave pair (RB = 2): wave w has column tile w / RB and row block w % RB, so a workgroup holds
 // NCT = 2 column tiles where C = 32 holds 4.
@@ -162,6 +213,10 @@ template <int KS, int DIL> __global__ void respair32_tc6_kernel(const PairArgs a
 template <int KS, int DIL> __global__ void respair16_f23_kernel(const PairArgs a);
 template <int KS, int DIL> __global__ void respair64_f23_kernel(const PairArgs a);
 template <int KS, int DIL> __global__ void respair64_tc6_kernel(const PairArgs a);
+// the k = 3, dilations (1, 3, 5) chains: a.w1 = the six transformed weights, a.b1 = the six biases [6][C], in execution order;
+// DBG = true: the instance that honours a.dbg (launched only while "kernel_dbg" != 0)
+template <bool DBG> __global__ void reschain32_f23_kernel(const PairArgs a);
+template <bool DBG> __global__ void reschain16_f23_kernel(const PairArgs a);
 #if DISSC_EXPERIMENTAL
 #define DISSC_PAIR_F23_SHAPES(X) X(11, 1) X(11, 3) X(11, 5) X(3, 1) X(3, 3) X(3, 5)
 #else

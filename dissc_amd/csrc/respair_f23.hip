@@ -16,7 +16,9 @@
 // LDS fragment reads where the direct form makes 6.  A wave's 64 columns are 128 outputs, the workgroup's 256 columns 512
 // (480 / 504 for d = 5 / 3, whose units of 2 D outputs do not divide 512).
 // fp32 operands, fp32 products, fp32 accumulation on v_mfma_f32_32x32x2_f32; not bit-identical to the direct pair.
-// Geometry (F23Geo32, F23Geo64, Tc6Geo) and what every pair kernel shares: respair_f23.h; weights, launch and dispatch: pair_host.hip.
+// Further down: the six-point pairs (respair32_tc6_kernel, respair64_tc6_kernel), the C = 64 F(2,3) pair (respair64_f23_kernel) and
+// reschain32_f23_kernel, the whole k = 3 ResBlock of this stage in one launch.
+// Geometry (F23Geo32, F23Geo64, F23ChainGeo, Tc6Geo) and what every pair kernel shares: respair_f23.h; weights, launch and dispatch: pair_host.hip.
 #include "common.h"
 #include "respair_f23.h"
 
@@ -558,6 +560,174 @@ __global__ void __launch_bounds__(256, 2) respair64_f23_kernel(const PairArgs a)
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// reschain32_f23_kernel: the WHOLE k = 3 ResBlock of the 32-channel stage -- three residual pairs, dilations (1, 3, 5) -- in one
+// launch, each conv in the F(2,3) scheme above (one sub-filter: a column is the output pair (t, t + d) of conv_d, (t, t + 1) of
+// conv_1).  x_1 and x_2 never leave the CU and the residual is read once:
+//   * a wave holds the four points of ONE 32-column tile (64 accumulators) and, in conv_1's accumulator layout, the raw x_k of
+//     its 64 outputs (32 registers): conv_1's column map does not depend on d, so a wave owns the same outputs in every pair;
+//   * x_k+1 = (A^T acc + b2) + x_k replaces those registers, and lrelu(x_k+1), zero outside the utterance, goes back into the
+//     one LDS buffer for the next pair's conv_d;
+//   * the computed span is the same 256 outputs in every pair, of which the middle 232 are valid after the third (F23ChainGeo);
+//   * the 16 KB of a conv's weights are fetched while the epilogue before it runs.
+// Per output and conv 2 C^2 products where three direct pairs execute 3 C^2, and one read of x plus one write of the result
+// where they make three reads of x_k, three of the residual and three writes.
+// ---------------------------------------------------------------------------------------------
+template <bool DBG>
+__global__ void __launch_bounds__(256, 2) reschain32_f23_kernel(const PairArgs a) {
+  using G = F23ChainGeo32;
+  constexpr int C = G::C, NW = G::NW, NT = 64 * NW, XW = G::XW, PADL = G::PADL, HALO = G::HALO, WOUT = G::WOUT, PW = G::PW;
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [C][XW]
+
+  int b, len, o0;
+  if (!pair_tile<WOUT>(a, gridDim.y, b, len, o0)) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, h = lane >> 5;
+  const int t00 = o0 - HALO;  // the time of buffer coordinate 0
+  const float slope = a.slope;
+  const int dbg = DBG ? a.dbg : 0;  // (the knock-out branches around the tap loops cost the instance without them registers: two instances)
+  const size_t ob = (size_t)b * a.bstride;
+  const float* xb = a.x + ob;
+  typedef float f32x16f __attribute__((ext_vector_type(16)));
+  typedef float f32x2f __attribute__((ext_vector_type(2)));
+
+  // a conv's weights: [8-channel step 4][point 4][64 lanes][4 k-steps], fetched one conv ahead
+  const __amdgpu_buffer_rsrc_t wr = wave_rsrc(a.w1, 0x7ffffff0u);  // scalar-base loads (common.h), constant offsets
+  const unsigned lane16 = lane * 16u;
+  f32x4 wv[4][4];
+  auto load_w = [&](int ci) __attribute__((always_inline)) {
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) wv[st][p] = rsrc_load16(wr, lane16, (unsigned)(((ci * 4 + st) * 4 + p) * 1024));
+  };
+  load_w(0);
+
+  pair_stage_window<C, XW, NT>(a, xb, xs, t00 - PADL, len, tid);
+
+  // the wave's outputs: column col <-> buffer coordinates pc, pc + 1; their raw x_0 in conv_1's accumulator layout
+  const int col = wave * 32 + l31, pc = 2 * col, tc0 = t00 + pc;
+  const bool in_e = tc0 >= 0 && tc0 < len, in_o = tc0 + 1 >= 0 && tc0 + 1 < len;
+  f32x2f res[16];
+  {
+    const int tcl = tc0 < 0 ? 0 : (tc0 > a.ld - 2 ? a.ld - 2 : tc0);  // (clamped: such outputs are neither stored nor fed on)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      res[r] = *reinterpret_cast<const f32x2f*>(xb + (size_t)((r & 3) + 8 * (r >> 2) + 4 * h) * a.ld + tcl);
+  }
+  f32x16f acc[4];
+  auto clear = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[p][e] = 0.f;
+  };
+  // one conv: 4 steps of 8 channels x 4 k-steps x 4 points = 64 MFMAs fed by 64 fragment reads (32 of 8 bytes where the samples
+  // are neighbours) and 64 additions
+  auto taps = [&](const float* src, int dunit) __attribute__((always_inline)) {
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float* q = src + (8 * st + 2 * e + h) * XW;
+        float x0, x1, x2, x3;
+        if (dunit == 1) {  // (src is even in floats: 8-byte aligned)
+          const f32x2f lo = *reinterpret_cast<const f32x2f*>(q), hi = *reinterpret_cast<const f32x2f*>(q + 2);
+          x0 = lo[0]; x1 = lo[1]; x2 = hi[0]; x3 = hi[1];
+        } else {
+          x0 = q[0]; x1 = q[dunit]; x2 = q[2 * dunit]; x3 = q[3 * dunit];
+        }
+        float bq[4];
+        bq[0] = x0 - x2;
+        bq[1] = x1 + x2;
+        bq[2] = x2 - x1;
+        bq[3] = x1 - x3;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[st][p][e], bq[p], acc[p], 0, 0, 0);
+      }
+  };
+
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    const int d = G::dil(m), T0 = G::t0(m), NC1 = G::nc1(m);
+    const int c1 = col < NC1 ? col : NC1 - 1;
+    const int pe = T0 + 2 * d * (c1 / d) + (c1 % d);  // conv_d's column: T at buffer coordinates pe, pe + d
+    __syncthreads();  // lrelu(x_m) is in place
+    clear();
+    if (!(dbg & 1)) taps(xs + PADL + pe - d, d);
+    load_w(2 * m + 1);
+
+    // ---- T = lrelu(conv_d + b1) inside the utterance, 0 outside, at LDS column PADL + 1 + p ----
+    __syncthreads();  // every wave is done reading lrelu(x_m)
+    if (col < NC1 && !(dbg & 2)) {
+      const int te = t00 + pe, to = te + d;
+      const bool ine = te >= 0 && te < len, ino = to >= 0 && to < len;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const float bz = a.b1[(2 * m) * C + row];
+        const float y0 = acc[0][r], y1 = acc[1][r], y2 = acc[2][r], y3 = acc[3][r];
+        float ve = (y0 + y1) + y2 + bz, vo = (y1 - y2) - y3 + bz;
+        ve = ve > 0.f ? ve : ve * slope;
+        vo = vo > 0.f ? vo : vo * slope;
+        xs[row * XW + PADL + 1 + pe] = ine ? ve : 0.f;
+        xs[row * XW + PADL + 1 + pe + d] = ino ? vo : 0.f;
+      }
+    }
+    __syncthreads();
+    clear();
+    if (!(dbg & 1)) taps(xs + PADL + pc, 1);  // (T of p - 1 .. p + 2)
+    if (m < 2) load_w(2 * m + 2);
+
+    // ---- x_m+1 = (conv_1 + b2) + x_m, in registers ----
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float bz = a.b1[(2 * m + 1) * C + (r & 3) + 8 * (r >> 2) + 4 * h];
+      const float y0 = acc[0][r], y1 = acc[1][r], y2 = acc[2][r], y3 = acc[3][r];
+      res[r][0] = (((y0 + y1) + y2) + bz) + res[r][0];
+      res[r][1] = (((y1 - y2) - y3) + bz) + res[r][1];
+    }
+    __syncthreads();  // every wave is done reading T
+    if (m < 2 && !(dbg & 2)) {  // lrelu(x_m+1), 0 outside the utterance, to the wave's own columns
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        f32x2f v;
+        v[0] = in_e ? (res[r][0] > 0.f ? res[r][0] : res[r][0] * slope) : 0.f;
+        v[1] = in_o ? (res[r][1] > 0.f ? res[r][1] : res[r][1] * slope) : 0.f;
+        *reinterpret_cast<f32x2f*>(xs + ((r & 3) + 8 * (r >> 2) + 4 * h) * XW + PADL + pc) = v;
+      }
+    }
+  }
+
+  // ---- epilogue: x_3 (or an MRF mode of it), 8 rows at a time through a wave-private patch [8][PW] -> 16 B per lane ----
+  if (dbg & 4) {
+    if (res[0][0] == 123.f && a.acc) a.acc[0] = 1.f;
+    return;
+  }
+  float* ep = xs + wave * (8 * PW);
+  const int prow = lane >> 4, pc4 = lane & 15;
+  const int pq = wave * 64 + 4 * pc4;  // this lane's quad in buffer coordinates
+  const int tq = t00 + pq;
+  const bool live = pq >= HALO && pq < HALO + WOUT && tq < len;
+  const int epi = a.epi;
+#pragma unroll
+  for (int mq = 0; mq < 4; ++mq) {  // rows 8 mq .. 8 mq + 7
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) *reinterpret_cast<f32x2f*>(ep + (r + 4 * h) * PW + 2 * l31) = res[4 * mq + r];
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int prw = 4 * p + prow;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(ep + prw * PW + 4 * pc4);
+      if (!live) continue;
+      chain_store_tail(a, epi, ob + (size_t)(8 * mq + prw) * a.ld + tq, v, len - tq);
+    }
+  }
+}
+
+template __global__ void reschain32_f23_kernel<false>(const PairArgs);
+template __global__ void reschain32_f23_kernel<true>(const PairArgs);
 #define DISSC_INSTANCE(K_, D_) template __global__ void respair32_f23_kernel<K_, D_>(const PairArgs);
 DISSC_PAIR_F23_SHAPES(DISSC_INSTANCE)
 #undef DISSC_INSTANCE

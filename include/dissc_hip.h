@@ -210,6 +210,13 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *                        transform-domain launches (k = 7: per launch -13...-22 %, forward 1.4 % faster; k = 11: slower at
  *                        d = 5 and in the forward, off); 0 = the two launches.  Not bit-identical to them; rounding within
  *                        1.6 x the direct launches' on trained-like data
+ *   chain_f23 (3)        read at dissc_gen_create, a bit mask honoured only for fp32 handles while wino != 0, pair_f23 != 0 and the
+ *                        stage is within pair_max_c:
+ *                        1 = the k = 3, dilations (1, 3, 5) ResBlock of the 32-channel stage, 2 = that of the 16-channel stage
+ *                        runs as ONE register-only F(2,3) launch (reschain32_f23_kernel in respair_f23.hip,
+ *                        reschain16_f23_kernel in respair16_f23.hip: x_1, x_2 and the residuals stay on the CU, 2 C^2
+ *                        products per output and conv instead of 3 C^2); 0 = three one-launch pairs.  Not bit-identical to
+ *                        them.  A chain-level choice: dissc_pair_info does not see it
  *   pair_dma (1)         read at dissc_gen_create: the two-launch direct residual pairs of the >= 32-channel stages hand their
  *                        intermediate over activated with zero tails, and the second conv stages its windows by LDS-DMA
  *   wino8 (1)            read at dissc_gen_create: 1 = the ResBlock convs selected by wino8_mask run on conv_wino8.hip's
@@ -339,6 +346,22 @@ int dissc_wino_info(int C, int k, int dilation, int B, int Lmax, DisscWinoPlan* 
 int dissc_resblock1d_bf3(const float* x, const float* const* w6_host, const float* const* b6_host, float* acc,
                          const int32_t* lengths, int B, int C, int k, const int32_t* dil3, int ld, int Lmax, float slope,
                          int epi, float mrf_div, int m0, int m1, void* stream);
+/* Diagnostics / tests: ONE k = 3 ResBlock1 -- three residual pairs of dilations dil3 -- on device data with host weights, as
+ * dissc_resblock1d_bf3 takes them; y (epi = 1, EPI_RES; must not alias x) or acc (the MRF modes 2 / 3 / 4) receives the block's
+ * output.  mode 0 = three launches, every pair in the one-launch form the generator gives it without "chain_f23", x_1 / x_2
+ * through scratch; mode 1 = the one-launch F(2,3) chain, DISSC_EINVAL (nothing written) where the shape has no instance
+ * (instances: C = 16 / 32, k = 3, dilations (1, 3, 5)).  dissc_reschain1d synchronises the stream; dissc_chain_bench times `iters`
+ * launches of a k = 3, dilations (1, 3, 5) block on synthetic data.  dissc_chain_info reports the chain kernel's geometry: the
+ * outputs a workgroup owns, the span it computes in every pair, the halo per side ((span - wout) / 2), its LDS bytes and the
+ * column tiles per wave.  Host only: no GPU is touched. */
+int dissc_reschain1d(const float* x, const float* const* w6_host, const float* const* b6_host, float* y, float* acc,
+                     const int32_t* lengths, int B, int C, int k, const int32_t* dil3, int ld, int Lmax, float slope, int epi,
+                     float mrf_div, int mode, void* stream);
+typedef struct {
+  int wout, span, halo, lds_bytes, tiles_per_wave;
+} DisscChainInfo;
+int dissc_chain_info(int C, int k, const int32_t* dil3, DisscChainInfo* out);
+int dissc_chain_bench(int B, int C, int L, int epi, int iters, int mode, float* ms_out);
 /* What the generator's split-bf16 kernels would launch, answered by the planning functions the launches themselves call.
  * dil3 == NULL: the conv_bf3_kernel tile of a Cin -> Cout conv of k taps and `dilation` (for a phase group of a ConvTranspose:
  * its GEMM rows and taps as dissc_conv_info reports them, dilation 1) on B utterances of at most Lmax columns under the current

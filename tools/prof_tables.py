@@ -25,10 +25,11 @@ RK = [3, 7, 11]
 DIL = [1, 3, 5]
 PAIR_MAX_C = 32
 PAIR_F23_C64 = 1  # option "pair_f23_c64": the k = 3 pairs of the 64-channel stage are one launch each (respair64_f23_kernel)
+CHAIN_F23 = 3  # option "chain_f23" (--chain-f23): bit 1 the C = 32, bit 2 the C = 16 stage runs its k = 3 ResBlock as one launch (reschain32/16_f23_kernel)
 PAIR_TC6_C64 = 1  # option "pair_tc6_c64" (--pair-tc6-c64): bit 1 its k = 7, bit 2 its k = 11 pairs are one launch each (respair64_tc6_kernel)
 
 
-def gen_layers(pair_tc6_c64=PAIR_TC6_C64):
+def gen_layers(pair_tc6_c64=PAIR_TC6_C64, chain_f23=CHAIN_F23):
     """(name, flops, algorithmic bytes) of every dissc:: launch of one generator forward, in launch order."""
     f4 = 4.0
     out = [("embed_concat", 0.0, B * 257 * T * f4)]
@@ -43,6 +44,9 @@ def gen_layers(pair_tc6_c64=PAIR_TC6_C64):
         L *= s
         act = B * ch * L * f4
         for rk in RK:
+            if rk == 3 and (chain_f23 & {32: 1, 16: 2}.get(ch, 0)):  # the whole block in one launch: read x, write the accumulator
+                out.append((f"s{i} C{ch} k{rk} d1-3-5 chain", 3 * 2 * 2.0 * ch * ch * rk * L * B, act * 2))
+                continue
             for m, d in enumerate(DIL):
                 fl = 2.0 * ch * ch * rk * L * B
                 last = m == 2
@@ -127,8 +131,9 @@ def main():
     ap.add_argument("--json")
     ap.add_argument("--skip", type=int, default=0)
     ap.add_argument("--pair-tc6-c64", type=int, default=PAIR_TC6_C64, help="the capture's \"pair_tc6_c64\" (0: a build before the option)")
+    ap.add_argument("--chain-f23", type=int, default=CHAIN_F23, help="the capture's \"chain_f23\" (0: a build before the option)")
     a = ap.parse_args()
-    layers = gen_layers(a.pair_tc6_c64) if a.what == "gen" else enc_layers()
+    layers = gen_layers(a.pair_tc6_c64, a.chain_f23) if a.what == "gen" else enc_layers()
     n = len(layers)
     rows = dissc_rows(a.trace)
     dur = fold([(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows], n, a.skip)
@@ -155,6 +160,8 @@ def main():
             fx = fl * 6.0 * ((k + 2) // 3) / (4.0 * k)
         if "respair32_f23_kernel" in names[i][0] or "respair16_f23_kernel" in names[i][0]:  # register-only F(2,3) pairs (k = 11: four sub-filters): 8 products per output
             fx = fl * 8.0 / 11.0
+        if "reschain32_f23_kernel" in names[i][0] or "reschain16_f23_kernel" in names[i][0]:  # k = 3 chains, one sub-filter: 2 products per output
+            fx = fl * 2.0 / 3.0
         if "respair64_f23_kernel" in names[i][0]:  # k = 3, one sub-filter: 2 products per output
             fx = fl * 2.0 / 3.0
         if "respair32_tc6_kernel" in names[i][0] or "respair64_tc6_kernel" in names[i][0]:
