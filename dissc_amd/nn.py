@@ -1,6 +1,7 @@
 """Differentiable layers for training the vocoder on the MI355X (C ABI ``dissc_convgrad_*``, csrc/conv_grad.hip,
 ``dissc_convtgrad_*``, csrc/conv_grad_t.hip, ``dissc_convsgrad_*`` / ``dissc_period_fold_*``, csrc/conv_grad_s.hip,
-``dissc_convggrad_*`` / ``dissc_mean_pool_*``, csrc/conv_grad_g.hip, and ``dissc_ganloss_*``, csrc/gan_loss.hip).
+``dissc_convggrad_*`` / ``dissc_mean_pool_*``, csrc/conv_grad_g.hip, ``dissc_ganloss_*``, csrc/gan_loss.hip, and
+``dissc_snorm_*``, csrc/spectral_norm.hip).
 
     y = nn.conv1d(x, weight, bias, lengths=lengths, dilation=d, in_slope=0.1, add=res)   # a torch.autograd.Function
     y = nn.resblock1(x, weights, k)                                                       # reference sr/models.py:34-41
@@ -12,6 +13,7 @@
     score, fmaps, lens = nn.discriminator_s(wav, weights, lengths)                        # reference sr/models.py:285-307
     nn.wgrad_partials_grouped(...), nn.workspace_bytes_grouped(...)                       # host-only plan queries
     out = nn.MultiPeriodDiscriminator()(y, y_hat, lengths)                                # reference sr/models.py:263-286
+    out = nn.MultiScaleDiscriminator()(y, y_hat, lengths)                                 # reference sr/models.py:310-333
     nn.discriminator_loss(out), nn.generator_loss(out), nn.feature_loss(out)              # reference sr/models.py:352-383
 
 ``conv1d`` is the stride-1 "same" Conv1d that 92 of the generator's 97 conv layers are, with dissc_conv1d's conventions:
@@ -553,10 +555,23 @@ def discriminator_s(wav, weights, lengths=None):
         rows.append(-(-rows[-1] // s))
     flat = torch.from_numpy(np.concatenate(rows).astype(np.int32)).to(wav.device)  # every layer's lengths in one upload
     lens = [flat[i * B:(i + 1) * B] for i in range(len(rows))]
+    fmaps = _disc_s_layers(_wav_rows4(wav), weights, lens)
+    return fmaps[-1], fmaps, lens[1:] + [lens[-1], lens[-1]]
+
+
+def _wav_rows4(wav):
+    """wav as [B, 1, T]; a T that is no multiple of 4 is copied once into zeroed rows of ceil4(T) samples"""
+    B, T = wav.shape[0], wav.shape[-1]
     x = wav.reshape(B, 1, T)
     if T % 4:
         x = torch.zeros((B, 1, _ceil4(T)), dtype=torch.float32, device=wav.device)
         x[:, :, :T] = wav.reshape(B, 1, T)
+    return x
+
+
+def _disc_s_layers(x, weights, lens):
+    """the eight maps of DiscriminatorS on x [rows, 1, ld] (ld % 4 == 0); lens: the device lengths of the inputs of convs.0 ..
+    convs.5 and of the stride-1 layers behind them (seven tensors)"""
     fmaps = []
     for i, (s, g) in enumerate(DISC_S_GROUPED):
         x = conv1d_grouped(x, weights[f"convs.{i}.weight"], weights.get(f"convs.{i}.bias"), stride=s, groups=g, lengths=lens[i],
@@ -566,7 +581,7 @@ def discriminator_s(wav, weights, lengths=None):
     fmaps.append(x)
     x = conv1d(x, weights["conv_post.weight"], weights.get("conv_post.bias"), lengths=lens[-1], in_slope=LRELU_SLOPE)
     fmaps.append(x)
-    return x, fmaps, lens[1:] + [lens[-1], lens[-1]]
+    return fmaps
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1407,25 +1422,455 @@ class MultiPeriodDiscriminator:
 
 
 def discriminator_loss(out):
-    """reference sr/models.py:363-374 on an MPDOutput of D(y, y_hat.detach()) -> (loss, r_losses, g_losses): loss = the sum over
-    the discriminators of mean((1 - score_real)^2) + mean(score_gen^2) over the valid scores; r_losses / g_losses: device tensors
-    [number of periods] (no host copy, no sync).  One forward and one backward launch over the scores."""
-    total, vals = gan_loss(DISC, out.scores, [ls[5] for ls in out.lens], out.R)
+    """reference sr/models.py:363-374 on an MPDOutput or MSDOutput of D(y, y_hat.detach()) -> (loss, r_losses, g_losses): loss =
+    the sum over the discriminators of mean((1 - score_real)^2) + mean(score_gen^2) over the valid scores; r_losses / g_losses:
+    device tensors [number of periods or scales] (no host copy, no sync).  One forward and one backward launch over the scores
+    (each discriminator's last map, with that map's lengths)."""
+    total, vals = gan_loss(DISC, out.scores, [ls[-1] for ls in out.lens], out.R)
     return total, vals[0], vals[1]
 
 
 def generator_loss(out):
     """reference sr/models.py:377-383 -> (loss, gen_losses): the sum over the discriminators of mean((1 - score_gen)^2)"""
-    total, vals = gan_loss(GEN, out.scores, [ls[5] for ls in out.lens], out.R)
+    total, vals = gan_loss(GEN, out.scores, [ls[-1] for ls in out.lens], out.R)
     return total, vals[0]
 
 
 def feature_loss(out):
-    """reference sr/models.py:352-360 -> loss = 2 * the sum over all 6 maps of every discriminator of mean |fmap_real - fmap_gen|
-    over the valid positions, fmap = the leaky ReLU (0.1) of maps 0 .. 4 and conv_post's output as it is.  One forward and one
-    backward launch over all maps."""
+    """reference sr/models.py:352-360 -> loss = 2 * the sum over all maps (6 a period, 8 a scale) of every discriminator of
+    mean |fmap_real - fmap_gen| over the valid positions, fmap = the leaky ReLU (0.1) of all but the last map and conv_post's
+    output as it is.  One forward and one backward launch over all maps."""
     maps = [m for fm in out.fmaps for m in fm]
     lens = [t for ls in out.lens for t in ls]
     R = [r for r, fm in zip(out.R, out.fmaps) for _ in fm]
     slopes = [LRELU_SLOPE if j < len(fm) - 1 else 1.0 for fm in out.fmaps for j in range(len(fm))]
     return gan_loss(FM, maps, lens, R, slopes)[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The scale half of the GAN step (reference sr/models.py:285-333): spectral norm of a list of matrices (C ABI dissc_snorm_*,
+# csrc/spectral_norm.hip) and nn.MultiScaleDiscriminator.  Discriminator 0 is spectrally normalised, and torch's spectral_norm runs
+# one power iteration in EVERY training-mode forward of a wrapped conv: the reference's d(y) and d(y_hat) see W / sigma_1 and
+# W / sigma_2, two different weights.  Scale 0 therefore runs as two chains of B rows; scales 1 and 2 run paired, as the periods do.
+# ---------------------------------------------------------------------------------------------------------------------
+def _bind_snorm():
+    vp, i32, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    pll = ctypes.POINTER(ll)
+    lib.dissc_snorm_create.argtypes = [i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp)]
+    lib.dissc_snorm_destroy.argtypes, lib.dissc_snorm_destroy.restype = [vp], None
+    lib.dissc_snorm_offsets.argtypes = [vp, pll, pll, pll, pll, pll, pll, pll]
+    for name in ("chunk_rows", "span_cols", "wave_cols", "flat_span"):
+        getattr(lib, "dissc_snorm_" + name).argtypes = []
+    lib.dissc_snorm_forward.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.dissc_snorm_backward.argtypes = [vp, vp, vp, ctypes.POINTER(vp), vp, vp]
+
+
+_bind_snorm()
+
+SNORM_CHUNK_ROWS = int(lib.dissc_snorm_chunk_rows())  # rows per partial chunk of W^T u
+SNORM_SPAN_COLS = int(lib.dissc_snorm_span_cols())    # columns per workgroup span of W^T u and v
+SNORM_WAVE_COLS = int(lib.dissc_snorm_wave_cols())    # rows of up to this many columns: one wave; longer: one workgroup
+SNORM_FLAT_SPAN = int(lib.dissc_snorm_flat_span())    # elements per workgroup of the passes over a tensor as a flat array
+# (name, Cout, Cin / groups, k) of DiscriminatorS's eight layers, reference sr/models.py:289-295
+_DISC_S_LAYERS = [("convs.0", 128, 1, 15), ("convs.1", 128, 32, 41), ("convs.2", 256, 8, 41), ("convs.3", 512, 16, 41),
+                  ("convs.4", 1024, 32, 41), ("convs.5", 1024, 64, 41), ("convs.6", 1024, 1024, 5), ("conv_post", 1, 1024, 3)]
+
+
+def _aligned_offsets(sizes):
+    """([offset of each entry, 16-byte aligned], total floats)"""
+    offs, at = [], 0
+    for n in sizes:
+        at = (at + 3) & ~3
+        offs.append(at)
+        at += n
+    return offs, (at + 3) & ~3
+
+
+class SpectralNorm:
+    """torch.nn.utils.spectral_norm's weight for a whole list of matrices at once (dissc_snorm_*): ``shapes`` are the tensors'
+    (rows, cols) = weight_orig seen as [Cout, Cin / groups * k].  ``off[i]`` places tensor i in the flat layout of ``total``
+    floats (weight_orig, w, its gradient), ``u_off[i]`` / ``v_off[i]`` its power-iteration vectors in ``u_total`` / ``v_total``
+    floats; every entry 16-byte aligned.  A state is one tensor [u | v | sigma per tensor] of ``state_total`` floats."""
+
+    def __init__(self, shapes):
+        n = len(shapes)
+        rows = (ctypes.c_int * max(n, 1))(*[int(r) for r, _ in shapes])
+        cols = (ctypes.c_int * max(n, 1))(*[int(c) for _, c in shapes])
+        self._h = ctypes.c_void_p()
+        check(lib.dissc_snorm_create(n, rows, cols, ctypes.byref(self._h)), "dissc_snorm_create")
+        self.n, self.shapes = n, [(int(r), int(c)) for r, c in shapes]
+        off, uoff, voff = ((ctypes.c_longlong * n)() for _ in range(3))
+        tot, ut, vt, st = (ctypes.c_longlong(0) for _ in range(4))
+        check(lib.dissc_snorm_offsets(self._h, off, uoff, voff, ctypes.byref(tot), ctypes.byref(ut), ctypes.byref(vt), ctypes.byref(st)),
+              "dissc_snorm_offsets")
+        self.off, self.u_off, self.v_off = list(off), list(uoff), list(voff)
+        self.total, self.u_total, self.v_total, self.state_total = tot.value, ut.value, vt.value, st.value
+        self.has_gaps = self.total != sum(r * c for r, c in self.shapes)
+
+    def __del__(self):
+        try:
+            lib.dissc_snorm_destroy(self._h)
+        except Exception:
+            pass
+
+    def split(self, state):
+        """(u [u_total], v [v_total], sigma [n]): views of a state"""
+        a, b = self.u_total, self.u_total + self.v_total
+        return state[:a], state[a:b], state[b:b + self.n]
+
+    def forward(self, w_flat, u_flat, v_flat, iterate=True, out=None, state=None):
+        """-> (w, state): w = weight_orig / sigma in the flat layout, state = [u | v | sigma] as this call used them: after one
+        power iteration from (u_flat, v_flat) with ``iterate``, else (u_flat, v_flat) themselves.  New tensors whose alignment
+        gaps are zero, or ``out`` / ``state``; the inputs are never written."""
+        who = "SpectralNorm.forward"
+        _f32(w_flat, "w_flat", who), _f32(u_flat, "u_flat", who), _f32(v_flat, "v_flat", who)
+        if w_flat.numel() != self.total or u_flat.numel() != self.u_total or v_flat.numel() != self.v_total:
+            raise DisscError(f"{who}: w_flat / u_flat / v_flat must have {self.total} / {self.u_total} / {self.v_total} floats")
+        dev = w_flat.device
+        if out is None:
+            out = (torch.zeros if self.has_gaps else torch.empty)(self.total, dtype=torch.float32, device=dev)
+        if state is None:
+            state = torch.zeros(self.state_total, dtype=torch.float32, device=dev)
+        if _f32(out, "out", who).numel() != self.total or _f32(state, "state", who).numel() != self.state_total:
+            raise DisscError(f"{who}: out / state must have {self.total} / {self.state_total} floats")
+        with torch.cuda.device(dev):
+            check(lib.dissc_snorm_forward(self._h, _ptr(w_flat), _ptr(u_flat), _ptr(v_flat), 1 if iterate else 0, _ptr(out), _ptr(state),
+                                          current_stream_ptr(dev)), "dissc_snorm_forward")
+        return out, state
+
+    def backward(self, w_flat, state, gws, gw_out=None):
+        """gws: the tensors' own gradients (None = zero) -> the gradient of weight_orig in the flat layout, with the state's u, v
+        and sigma as constants"""
+        who = "SpectralNorm.backward"
+        _f32(w_flat, "w_flat", who), _f32(state, "state", who)
+        if w_flat.numel() != self.total or state.numel() != self.state_total or len(gws) != self.n:
+            raise DisscError(f"{who}: w_flat / state of {self.total} / {self.state_total} floats and {self.n} gradients expected")
+        for i, t in enumerate(gws):
+            if t is not None and _f32(t, f"gws[{i}]", who).numel() != self.shapes[i][0] * self.shapes[i][1]:
+                raise DisscError(f"{who}: gws[{i}] has {t.numel()} elements, expected {self.shapes[i]}")
+        dev = w_flat.device
+        pw = (ctypes.c_void_p * self.n)(*[None if t is None else t.data_ptr() for t in gws])
+        gw = gw_out if gw_out is not None else \
+            (torch.zeros if self.has_gaps else torch.empty)(self.total, dtype=torch.float32, device=dev)
+        if _f32(gw, "gw_out", who).numel() != self.total:
+            raise DisscError(f"{who}: gw_out must have {self.total} floats")
+        with torch.cuda.device(dev):
+            check(lib.dissc_snorm_backward(self._h, _ptr(w_flat), _ptr(state), pw, _ptr(gw), current_stream_ptr(dev)),
+                  "dissc_snorm_backward")
+        return gw
+
+
+class _SnWeightsFn(torch.autograd.Function):
+    """(weight_orig flat, bias flat) with the buffers (u, v) -> every layer's weight W / sigma and bias, views of buffers made
+    here, and the state [u | v | sigma] this call used (not differentiable; its u and v are the module's next buffers).  The
+    Function saves weight_orig and that very state: no later call can write what it saved.  The backward is three launches."""
+
+    @staticmethod
+    def forward(ctx, w_flat, bias_flat, u_flat, v_flat, sn, dims, bias_off, bias_sizes, iterate):
+        buf, state = sn.forward(w_flat, u_flat, v_flat, iterate)
+        ctx.save_for_backward(w_flat, state)
+        ctx.sn, ctx.bias_off, ctx.bias_sizes, ctx.nbias = sn, bias_off, bias_sizes, bias_flat.numel()
+        ws = [buf[o:o + r * c].view(d) for o, (r, c), d in zip(sn.off, sn.shapes, dims)]
+        bias = bias_flat.detach().clone()
+        bs = [bias[o:o + n] for o, n in zip(bias_off, bias_sizes)]
+        ctx.mark_non_differentiable(state)
+        return tuple(ws + bs + [state])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        w_flat, state = ctx.saved_tensors
+        n = ctx.sn.n
+        gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gw = ctx.sn.backward(w_flat, state, [None if t is None else t.contiguous() for t in grads[:n]])
+        if ctx.needs_input_grad[1]:
+            gb = torch.zeros(ctx.nbias, dtype=torch.float32, device=w_flat.device)
+            for o, nb, g in zip(ctx.bias_off, ctx.bias_sizes, grads[n:2 * n]):
+                if g is not None:
+                    gb[o:o + nb].copy_(g)
+        return (gw, gb) + (None,) * 7
+
+
+class _JoinFn(torch.autograd.Function):
+    """[a ; b] along dim 0 as one paired map: two device copies into the halves of one allocation; the backward hands out the two
+    contiguous row ranges of the gradient, no copy"""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        out = torch.empty((a.shape[0] + b.shape[0],) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
+        out[:a.shape[0]].copy_(a)
+        out[a.shape[0]:].copy_(b)
+        ctx.rows = a.shape[0]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = g.contiguous()
+        return g[:ctx.rows], g[ctx.rows:]
+
+
+class _PairedPoolFn(torch.autograd.Function):
+    """[2 B, 1, ldo]: mean_pool of y into the first half and of y_hat into the second, by two calls of dissc_mean_pool_fwd on the
+    halves of one buffer; the backward runs dissc_mean_pool_bwd on a half only where that input requires a gradient"""
+
+    @staticmethod
+    def forward(ctx, y, y_hat, lengths):
+        B, T = y.shape[0], y.shape[-1]
+        ldo = _ceil4(T // 2 + 1)
+        out = torch.zeros((2 * B, 1, ldo), dtype=torch.float32, device=y.device)
+        half = 4 * B * ldo  # bytes; ldo % 4 == 0 keeps the second half 16-byte aligned
+        st = current_stream_ptr(y.device)
+        with torch.cuda.device(y.device):
+            for i, w in enumerate((y, y_hat)):
+                check(lib.dissc_mean_pool_fwd(_ptr(w), ctypes.c_void_p(out.data_ptr() + i * half), _ptr(lengths), B, 1, T, T, ldo, st),
+                      "dissc_mean_pool_fwd")
+        ctx.lengths, ctx.shapes = lengths, (tuple(y.shape), tuple(y_hat.shape))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = g.contiguous()
+        B, T = ctx.shapes[0][0], ctx.shapes[0][-1]
+        ldo = g.shape[2]
+        half = 4 * B * ldo
+        st = current_stream_ptr(g.device)
+        grads = [None, None]
+        with torch.cuda.device(g.device):
+            for i in range(2):
+                if ctx.needs_input_grad[i]:
+                    grads[i] = torch.empty(ctx.shapes[i], dtype=torch.float32, device=g.device)
+                    check(lib.dissc_mean_pool_bwd(ctypes.c_void_p(g.data_ptr() + i * half), _ptr(grads[i]), _ptr(ctx.lengths), B, 1, T, T,
+                                                  ldo, st), "dissc_mean_pool_bwd")
+        return grads[0], grads[1], None
+
+
+def msd_row_lengths(ln):
+    """host only: [scale][7] int64 arrays of 2 B row lengths (the halves alike) for utterances of ln[b] samples -- per scale the
+    inputs of convs.0 .. convs.5 and then of the stride-1 layers behind them; scale i + 1's utterances have n // 2 + 1 samples
+    (AvgPool1d(4, 2, padding=2); 0 stays 0)"""
+    ln = np.asarray(ln, dtype=np.int64).reshape(-1)
+    out = []
+    for _ in range(3):
+        rows = [np.tile(ln, 2)]
+        for s, _ in DISC_S_GROUPED:
+            rows.append(-(-rows[-1] // s))
+        out.append(rows)
+        ln = np.where(ln > 0, ln // 2 + 1, 0)
+    return out
+
+
+class MSDOutput(MPDOutput):
+    """what nn.MultiScaleDiscriminator returns: MPDOutput's fields per scale i -- scores[i] (= fmaps[i][7]), the eight paired
+    PRE-activation maps fmaps[i][j] [2 B, C_j, ld_j] (rows 0 .. B - 1 from y, the rest from y_hat), their per-row device lengths
+    lens[i][j] (int32 [2 B], the two halves alike), R[i] = B -- and sigma, a device tensor [2, 8]: the sigmas of discriminator
+    0's eight layers as the real half (sigma[0]) and the generated half (sigma[1]) used them"""
+
+    def __init__(self, scores, fmaps, lens, R, sigma):
+        super().__init__(scores, fmaps, lens, R)
+        self.sigma = sigma
+
+
+class MultiScaleDiscriminator:
+    """The trainable MultiScaleDiscriminator (reference sr/models.py:310-333) under the reference's checkpoint keys: discriminator
+    0 is spectrally normalised, ``discriminators.0.convs.<j>.{bias, weight_orig, weight_u, weight_v}`` (j = 0 .. 6) and
+    ``discriminators.0.conv_post.{...}`` -- weight_u [Cout] and weight_v [Cin / groups * k] are the power iteration's BUFFERS --,
+    discriminators 1 and 2 are weight-normalised, ``{bias, weight_g [Cout, 1, 1], weight_v [Cout, Cin / groups, k]}``: the ``msd``
+    entry of a reference ``do_*`` checkpoint.
+
+        D = nn.MultiScaleDiscriminator().to("cuda:0"); D.load_state_dict(sd["msd"])
+        out = D(y, y_hat.detach(), lengths); loss_d, r_losses, g_losses = nn.discriminator_loss(out); loss_d.backward()
+        out = D(y, y_hat, lengths, param_grads=False)
+        (nn.feature_loss(out) + nn.generator_loss(out)[0]).backward()
+
+    parameters(): five flat leaves -- discriminator 0's eight weight_orig and its eight biases, and every weight_v, every
+    weight_g and every bias of the 16 layers of discriminators 1 and 2.  The two-sigma rule: a training-mode forward of the
+    reference calls d(y) and then d(y_hat), and each call runs one power iteration, so y sees W / sigma_1 and y_hat sees
+    W / sigma_2.  Scale 0 therefore runs as two chains of B rows with two folds, and its maps are joined by a copy; scales 1 and
+    2 run as ONE batch [y ; y_hat] of pooled rows (weights packed once, every weight gradient one pass over both halves).
+    state_dict() returns the current buffers: after n forwards, what torch's module holds after n forwards.  No torch compute
+    op on the path (allocation, copies, views, autograd's own sums)."""
+
+    def __init__(self):
+        shape = lambda cout, cig, k: (cout, cig, k)
+        self.layers0 = [(f"discriminators.0.{name}", shape(cout, cig, k), cout) for name, cout, cig, k in _DISC_S_LAYERS]
+        self.layers12 = [(f"discriminators.{i}.{name}", shape(cout, cig, k), cout) for i in (1, 2) for name, cout, cig, k in _DISC_S_LAYERS]
+        self.sn = SpectralNorm([(s[0], s[1] * s[2]) for _, s, _ in self.layers0])
+        self.bias0_sizes = [nb for _, _, nb in self.layers0]
+        self.bias0_off, self.bias0_total = _aligned_offsets(self.bias0_sizes)
+        self.wn = WeightNorm([(s[0], s[1] * s[2]) for _, s, _ in self.layers12], [nb for _, _, nb in self.layers12])
+        self.device = torch.device("cuda:0")
+        self.w_orig = self.bias0 = self.v_flat = self.g_flat = self.bias_flat = None  # the five leaves
+        self.u = self.v = None                                                        # discriminator 0's buffers, flat
+
+    # -- nn.Module-like surface --------------------------------------------------------------------------------------
+    def to(self, device):
+        if isinstance(device, int):
+            device = f"cuda:{device}"
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise DisscError("dissc_amd.nn.MultiScaleDiscriminator runs on an MI355X only (device='cuda:N')")
+        if device.index is None:
+            device = torch.device("cuda:0")
+        if self.w_orig is not None and device != self.device:
+            raise DisscError("nn.MultiScaleDiscriminator: choose the device before load_state_dict()")
+        self.device = device
+        return self
+
+    def cuda(self, device=0):
+        return self.to(device)
+
+    def _keys(self):
+        keys = []
+        for name, _, _ in self.layers0:
+            keys += [name + ".bias", name + ".weight_orig", name + ".weight_u", name + ".weight_v"]
+        for name, _, _ in self.layers12:
+            keys += [name + ".bias", name + ".weight_g", name + ".weight_v"]
+        return keys
+
+    def load_state_dict(self, sd, strict=True):
+        """the reference's layout: Conv1d shapes, weight_u [Cout] and weight_v [Cin / groups * k] for discriminator 0"""
+        keys = self._keys()
+        missing = [k for k in keys if k not in sd]
+        unexpected = sorted(set(sd.keys()) - set(keys))
+        if missing or (strict and unexpected):
+            raise RuntimeError("Error(s) in loading state_dict for MultiScaleDiscriminator: "
+                               f"missing {missing[:5]}, unexpected {unexpected[:5]}")
+        get = lambda k: sd[k].detach().to("cpu", torch.float32)
+
+        def expect(name, what, t, shape):
+            if tuple(t.shape) != tuple(shape):
+                raise RuntimeError(f"size mismatch for {name}.{what}: {tuple(t.shape)}, expected {tuple(shape)}")
+            return t.reshape(-1)
+
+        sn, wn = self.sn, self.wn
+        w, b0, u, v0 = torch.zeros(sn.total), torch.zeros(self.bias0_total), torch.zeros(sn.u_total), torch.zeros(sn.v_total)
+        for i, (name, shape, nb) in enumerate(self.layers0):
+            r, c = sn.shapes[i]
+            w[sn.off[i]:sn.off[i] + r * c] = expect(name, "weight_orig", get(name + ".weight_orig"), shape)
+            u[sn.u_off[i]:sn.u_off[i] + r] = expect(name, "weight_u", get(name + ".weight_u"), (r,))
+            v0[sn.v_off[i]:sn.v_off[i] + c] = expect(name, "weight_v", get(name + ".weight_v"), (c,))
+            b0[self.bias0_off[i]:self.bias0_off[i] + nb] = expect(name, "bias", get(name + ".bias"), (nb,))
+        v, g, b = torch.zeros(wn.total), torch.zeros(wn.total_rows), torch.zeros(wn.bias_total)
+        for i, (name, shape, nb) in enumerate(self.layers12):
+            v[wn.off[i]:wn.off[i] + shape[0] * shape[1] * shape[2]] = expect(name, "weight_v", get(name + ".weight_v"), shape)
+            g[wn.row_off[i]:wn.row_off[i] + shape[0]] = expect(name, "weight_g", get(name + ".weight_g"), (shape[0], 1, 1))
+            b[wn.bias_off[i]:wn.bias_off[i] + nb] = expect(name, "bias", get(name + ".bias"), (nb,))
+        leaf = lambda t: t.to(self.device).contiguous().requires_grad_(True)
+        self.w_orig, self.bias0, self.v_flat, self.g_flat, self.bias_flat = leaf(w), leaf(b0), leaf(v), leaf(g), leaf(b)
+        self.u, self.v = u.to(self.device), v0.to(self.device)
+        return self
+
+    def _loaded(self):
+        if self.w_orig is None:
+            raise RuntimeError("load_state_dict() first")
+
+    def parameters(self):
+        """the five flat leaves: discriminator 0's weight_orig and bias, discriminators 1 and 2's weight_v, weight_g and bias"""
+        self._loaded()
+        return [self.w_orig, self.bias0, self.v_flat, self.g_flat, self.bias_flat]
+
+    def zero_grad(self):
+        for p in self.parameters():
+            p.grad = None
+
+    def _named(self, w, b0, v, g, b):
+        out = {}
+        sn, wn = self.sn, self.wn
+        for i, (name, shape, nb) in enumerate(self.layers0):
+            out[name + ".bias"] = b0[self.bias0_off[i]:self.bias0_off[i] + nb]
+            out[name + ".weight_orig"] = w[sn.off[i]:sn.off[i] + shape[0] * shape[1] * shape[2]].view(shape)
+        for i, (name, shape, nb) in enumerate(self.layers12):
+            out[name + ".bias"] = b[wn.bias_off[i]:wn.bias_off[i] + nb]
+            out[name + ".weight_g"] = g[wn.row_off[i]:wn.row_off[i] + shape[0]].view(shape[0], 1, 1)
+            out[name + ".weight_v"] = v[wn.off[i]:wn.off[i] + shape[0] * shape[1] * shape[2]].view(shape)
+        return out
+
+    def named_grads(self):
+        """{reference key of a PARAMETER: a view of its leaf's .grad} after a backward"""
+        ps = self.parameters()
+        if any(p.grad is None for p in ps):
+            raise RuntimeError("named_grads(): run a backward first")
+        return self._named(*(p.grad for p in ps))
+
+    def state_dict(self):
+        """host copies under the reference's keys and Conv1d shapes, with discriminator 0's CURRENT weight_u / weight_v"""
+        self._loaded()
+        out = {k: t.clone() for k, t in self._named(*(p.detach().cpu() for p in self.parameters())).items()}
+        u, v = self.u.cpu(), self.v.cpu()
+        for i, (name, _, _) in enumerate(self.layers0):
+            r, c = self.sn.shapes[i]
+            out[name + ".weight_u"] = u[self.sn.u_off[i]:self.sn.u_off[i] + r].clone()
+            out[name + ".weight_v"] = v[self.sn.v_off[i]:self.sn.v_off[i] + c].clone()
+        return out
+
+    def _dict0(self, outs):
+        n = self.sn.n
+        return {f"{name}.{what}": outs[j + k * n] for j, (name, _, _, _) in enumerate(_DISC_S_LAYERS) for k, what in enumerate(("weight", "bias"))}
+
+    def folded(self, i):
+        """discriminator i's weights as a forward folds them, under nn.discriminator_s's keys (detached device tensors): for
+        i = 0, weight_orig / sigma at the CURRENT buffers with no power iteration (torch's eval())"""
+        self._loaded()
+        if i == 0:
+            with torch.no_grad():
+                outs = _SnWeightsFn.apply(self.w_orig.detach(), self.bias0.detach(), self.u, self.v, self.sn,
+                                          [s for _, s, _ in self.layers0], self.bias0_off, self.bias0_sizes, False)
+            return self._dict0(outs)
+        if i not in (1, 2):
+            raise DisscError("nn.MultiScaleDiscriminator.folded: the discriminators are 0, 1 and 2")
+        buf, _ = self.wn.forward(self.v_flat.detach(), self.g_flat.detach(), self.bias_flat.detach())
+        wn, out = self.wn, {}
+        for j, (name, _, _, _) in enumerate(_DISC_S_LAYERS):
+            l = 8 * (i - 1) + j
+            shape, nb = self.layers12[l][1], self.layers12[l][2]
+            out[name + ".weight"] = buf[wn.off[l]:wn.off[l] + shape[0] * shape[1] * shape[2]].view(shape)
+            out[name + ".bias"] = buf[wn.total + wn.bias_off[l]:wn.total + wn.bias_off[l] + nb]
+        return out
+
+    # -- forward -------------------------------------------------------------------------------------------------------
+    def forward(self, y, y_hat, lengths=None, param_grads=True, power_iteration=True):
+        """y, y_hat: contiguous fp32 device tensors of ONE shape, [B, 1, T] or [B, T], with lengths[b] valid samples each (host
+        counts; a device tensor is copied back; None = T) -> MSDOutput.  power_iteration=True is the reference's train() mode:
+        discriminator 0's buffers advance by one iteration in front of y's chain and by another in front of y_hat's;
+        False is its eval(): no iteration, both chains use weight_orig / sigma at the current buffers.  param_grads=False
+        detaches the five leaves in front of both norms: a backward then reaches y_hat (and y) only and skips every weight- and
+        bias-gradient kernel; the power iterations still run (the reference's generator step iterates too)."""
+        who = "nn.MultiScaleDiscriminator"
+        self._loaded()
+        _check_wav(y, who), _check_wav(y_hat, who)
+        if y.shape != y_hat.shape or y.device != y_hat.device or y.device != self.device:
+            raise DisscError(f"{who}: y {tuple(y.shape)} and y_hat {tuple(y_hat.shape)} must have one shape, on {self.device}")
+        B, T = y.shape[0], y.shape[-1]
+        ln = _host_lengths(lengths, B, T, who)
+        # every scale's every layer's row lengths (both halves) in one upload; a scale's first entry is also the lengths its input
+        # rows have for the pool behind it
+        flat = torch.from_numpy(np.concatenate([r for rows in msd_row_lengths(ln) for r in rows]).astype(np.int32)).to(self.device)
+        L = [[flat[(7 * i + j) * 2 * B:(7 * i + j + 1) * 2 * B] for j in range(7)] for i in range(3)]
+        leaves = self.parameters() if param_grads else [p.detach() for p in self.parameters()]
+        # scale 0: two folds, two chains of B rows, joined maps
+        lens0 = [t[:B] for t in L[0]]
+        halves, sigma = [], torch.empty((2, self.sn.n), dtype=torch.float32, device=self.device)
+        for h, wav in enumerate((y, y_hat)):
+            outs = _SnWeightsFn.apply(leaves[0], leaves[1], self.u, self.v, self.sn, [s for _, s, _ in self.layers0], self.bias0_off,
+                                      self.bias0_sizes, bool(power_iteration))
+            self.u, self.v, sg = self.sn.split(outs[-1])
+            sigma[h].copy_(sg)
+            halves.append(_disc_s_layers(_wav_rows4(wav), self._dict0(outs), lens0))
+        fmaps = [[_JoinFn.apply(a, b) for a, b in zip(*halves)]]
+        # scales 1 and 2: one weight-norm launch for their 16 layers, one paired chain of 2 B pooled rows each
+        n = len(self.layers12)
+        wb = _WeightsFn.apply(leaves[2], leaves[3], leaves[4], self.wn, [s for _, s, _ in self.layers12])
+        x = _PairedPoolFn.apply(y, y_hat, L[0][0][:B])
+        for i in (1, 2):
+            if i == 2:
+                x = _MeanPoolFn.apply(x, L[1][0])
+            W = {f"{name}.{what}": wb[k * n + 8 * (i - 1) + j] for j, (name, _, _, _) in enumerate(_DISC_S_LAYERS)
+                 for k, what in enumerate(("weight", "bias"))}
+            fmaps.append(_disc_s_layers(x, W, L[i]))
+        lens = [ls[1:] + [ls[-1], ls[-1]] for ls in L]
+        return MSDOutput([fm[-1] for fm in fmaps], fmaps, lens, [B, B, B], sigma)
+
+    __call__ = forward

@@ -1031,6 +1031,45 @@ int dissc_ganloss_backward(int n, const float* const* maps, const int32_t* const
                            const int* ld, const int* ops, const float* slopes, const float* g_total, const float* g_vals,
                            float* const* gmaps, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Spectral norm of a list of weight matrices (csrc/spectral_norm.hip; composed in dissc_amd/nn.py's SpectralNorm and
+ * MultiScaleDiscriminator; torch.nn.utils.spectral_norm as reference sr/models.py:288 applies it to discriminator 0 of the
+ * MultiScaleDiscriminator).  Added without an ABI bump, as the sections above.  Tensor i is weight_orig seen as rows[i] x cols[i]
+ * (cols = the product of every dim but 0), with the power iteration's vectors u (rows[i]) and v (cols[i]).
+ * dissc_snorm_create: HOST ONLY.  1 .. 128 tensors, rows and cols at least 1, at most 2^22 rows, 2^26 columns and 2^32 floats in
+ *   all; anything else is DISSC_EINVAL with a message.  It fixes three flat layouts, every entry 16-byte aligned: tensor i at the
+ *   float offset off[i] (W, w and gW share it), its u at u_off[i], its v at v_off[i].  The tensor table and a workspace of
+ *   doubles go to the device current at the first launch: a handle serves that device, and one stream at a time.
+ * dissc_snorm_offsets: HOST ONLY.  off / u_off / v_off: n entries each; the totals are the sizes of the three layouts (floats,
+ *   multiples of 4); state_floats = total_u + total_v + n rounded up to 4.  Each may be NULL.
+ * dissc_snorm_chunk_rows / _span_cols / _wave_cols / _flat_span: HOST ONLY, the sizes at which the kernels change their walk: rows
+ *   per partial chunk of W^T u; columns per workgroup span of W^T u and v; rows of up to wave_cols columns are reduced by one
+ *   wave, longer ones by a 256-thread workgroup; elements per workgroup of the passes over a tensor as a flat array.
+ * dissc_snorm_forward: with iterate = 1,  v = normalize(W^T u_in),  u = normalize(W v),  normalize(x) = x / max(||x||_2, 1e-12)
+ *   (torch's F.normalize); with iterate = 0, u = u_in and v = v_in.  Then sigma = u . (W v) and w_out = W / sigma (a division).
+ *   state_out = [u (total_u) | v (total_v) | sigma per tensor], freshly written; the alignment gaps of w_out and state_out are
+ *   left alone, the inputs are never written (w_out / state_out equal to an input is DISSC_EINVAL).  All pointers 16-byte aligned.
+ *   Six launches with an iteration, three without, whatever n.  Dots and norms in double, every sum in a fixed order, one rounding
+ *   to float for u, v and sigma; no atomics: bit-reproducible, and a tensor's results do not depend on the list it is in.
+ * dissc_snorm_backward: gw_orig (flat, as W) = gw / sigma - (sum gw o W / sigma^2) u v^T per tensor, u, v and sigma read from
+ *   `state` as the forward wrote it (they are constants of the gradient, as torch holds them).  gw_ptrs is a HOST array of n DEVICE
+ *   pointers, each tensor's own gradient [rows][cols], 16-byte aligned; NULL = a zero gradient (exact zeros are written).  The
+ *   pointers travel in the kernels' arguments.  Three launches.
+ * ------------------------------------------------------------------------- */
+typedef struct dissc_snorm* dissc_snorm_t;
+int dissc_snorm_create(int n, const int* rows, const int* cols, dissc_snorm_t* out);
+void dissc_snorm_destroy(dissc_snorm_t h);
+int dissc_snorm_offsets(dissc_snorm_t h, long long* off, long long* u_off, long long* v_off, long long* total_floats,
+                        long long* total_u, long long* total_v, long long* state_floats);
+int dissc_snorm_chunk_rows(void);
+int dissc_snorm_span_cols(void);
+int dissc_snorm_wave_cols(void);
+int dissc_snorm_flat_span(void);
+int dissc_snorm_forward(dissc_snorm_t h, const float* w_orig, const float* u_in, const float* v_in, int iterate, float* w_out,
+                        float* state_out, void* stream);
+int dissc_snorm_backward(dissc_snorm_t h, const float* w_orig, const float* state, const float* const* gw_ptrs, float* gw_orig,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,13 @@ activities; null where the profiler gives none).  One JSON line per figure; --ma
 
 times the period half of the GAN step instead (mpd_bench below; profiles/mpd_train.md): the fused loss launches of
 csrc/gan_loss.hip on the 30 paired maps of nn.MultiPeriodDiscriminator, and the discriminator's and the generator's period-side
-steps against the reference's MultiPeriodDiscriminator and loss functions in eager torch."""
+steps against the reference's MultiPeriodDiscriminator and loss functions in eager torch.
+
+    python tools/gen_train_bench.py --msd [--batch 32] [--frames 28] [--launches 200] [--steps 20] [--markdown]
+
+times the scale half (msd_bench below; profiles/msd_train.md): every dissc_snorm_* launch of csrc/spectral_norm.hip on the eight
+matrices of discriminator 0 next to the bytes it must move, the two joined-map copies per map of scale 0, and the discriminator's
+and the generator's scale-side steps against spectral_norm / weight_norm Conv1d modules in eager torch, in alternated runs."""
 import argparse
 import ctypes
 import json
@@ -209,6 +215,171 @@ def mpd_bench(a):
     return rows, steps
 
 
+def kernel_times(fn, iters):
+    """{kernel name: mean device us per call of fn} from torch.profiler, or {} where it records no device activity"""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            for _ in range(iters):
+                fn()
+            torch.cuda.synchronize()
+        out = {}
+        for e in prof.key_averages():
+            t = getattr(e, "self_device_time_total", None)
+            if t is None:
+                t = getattr(e, "self_cuda_time_total", 0.0)
+            if t and str(getattr(e, "device_type", "")).endswith("CUDA"):
+                out[e.key] = t / iters
+        return out
+    except Exception as e:  # a figure, not a requirement
+        print(f"# kernel times unavailable: {e}", file=sys.stderr)
+        return {}
+
+
+def msd_bench(a):
+    """--msd: the scale half of the GAN step at the trainer's shape (32 segments of 8 960 samples): the spectral norm launches on
+    discriminator 0's eight matrices next to the bytes they must move, the joined-map copies of scale 0, and both steps against
+    eager torch's spectral_norm / weight_norm modules on the same GPU with the same weights, alternated."""
+    import gan_loss_ref as GL
+    import msd_cases as M
+    from dissc_amd import nn
+    from dissc_amd._lib import check, lib
+    F = torch.nn.functional
+    B, T = a.batch, 320 * a.frames
+    sd = M.msd_state_dict(0)
+    D = nn.MultiScaleDiscriminator().to(DEV)
+    D.load_state_dict(sd)
+    y, y_hat = (t.to(DEV) for t in M.wav_pair(1, B, T))
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    rows = []
+
+    # ---- the spectral norm launches, straight through the C ABI ----
+    sn = D.sn
+    W, u, v = D.w_orig.detach(), D.u, D.v
+    w_out, state = torch.zeros(sn.total, device=DEV), torch.zeros(sn.state_total, device=DEV)
+    gws = [torch.randn(r, c, device=DEV) for r, c in sn.shapes]
+    pw = (ctypes.c_void_p * sn.n)(*[t.data_ptr() for t in gws])
+    gW = torch.zeros(sn.total, device=DEV)
+    fwd1 = lambda: check(lib.dissc_snorm_forward(sn._h, p(W), p(u), p(v), 1, p(w_out), p(state), None))
+    fwd0 = lambda: check(lib.dissc_snorm_forward(sn._h, p(W), p(u), p(v), 0, p(w_out), p(state), None))
+    bwd = lambda: check(lib.dissc_snorm_backward(sn._h, p(W), p(state), pw, p(gW), None))
+    for fn in (fwd1, fwd0, bwd):
+        timed(fn, 3)
+    mb = 4e-6 * sum(r * c for r, c in sn.shapes)  # one pass over the eight matrices
+    part_mb = 8e-6 * sum(-(-r // nn.SNORM_CHUNK_ROWS) * c for r, c in sn.shapes)  # the W^T u partials, doubles
+    small = 4e-6 * (sn.u_total + sn.v_total)
+    rows.append(row("dissc_snorm_forward, iterate = 1: six launches", timed(fwd1, a.launches), 4 * mb + 2 * part_mb))
+    rows.append(row("dissc_snorm_forward, iterate = 0: three launches", timed(fwd0, a.launches), 3 * mb))
+    rows.append(row("dissc_snorm_backward: three launches", timed(bwd, a.launches), 4 * mb))
+    must = {"snorm_wtu_kernel": mb + part_mb, "snorm_colsum_kernel": part_mb + 3 * small, "snorm_vnorm_kernel": 3 * small,
+            "snorm_rowdot_kernel": mb, "snorm_usigma_kernel": 3 * small, "snorm_scale_kernel": 2 * mb, "snorm_gdot_kernel": 2 * mb,
+            "snorm_coef_kernel": 0.03, "snorm_bwd_kernel": 2 * mb}
+    per = kernel_times(lambda: (fwd1(), bwd()), 20)
+    for name, need in must.items():
+        us = [t for k, t in per.items() if name in k]
+        if us:
+            rows.append(row(f"{name} (one launch, profiler)", 1e-3 * us[0], need))
+
+    # ---- the joined-map copies of scale 0: two device copies per map, eight maps ----
+    with torch.no_grad():
+        out = D(y, y_hat)
+    halves = [(m[:B].clone(), m[B:].clone()) for m in out.fmaps[0]]
+    join = lambda: [nn._JoinFn.apply(x, z) for x, z in halves]
+    timed(join, 3)
+    t_join = timed(join, max(20, a.launches // 10))
+    rows.append(row("scale 0: the eight joined maps (16 device copies)", t_join, 2 * 4e-6 * sum(m.numel() for m in out.fmaps[0])))
+    del out, halves
+
+    # ---- eager torch: spectral_norm / weight_norm Conv1d modules in train() mode (reference sr/models.py:285-333), the same weights ----
+    E = M.torch_msd(sd, torch.float32).to(DEV)
+    pools = [torch.nn.AvgPool1d(4, 2, padding=2), torch.nn.AvgPool1d(4, 2, padding=2)]
+
+    def disc(d, x):
+        fmap = []
+        for conv in d.convs:
+            x = F.leaky_relu(conv(x), 0.1)
+            fmap.append(x)
+        x = d.conv_post(x)
+        fmap.append(x)
+        return torch.flatten(x, 1, -1), fmap
+
+    def torch_msd(yr, yg):
+        s_r, s_g, f_r, f_g = [], [], [], []
+        for i, d in enumerate(E.discriminators):
+            if i:
+                yr, yg = pools[i - 1](yr), pools[i - 1](yg)
+            a_, b_ = disc(d, yr), disc(d, yg)
+            s_r.append(a_[0]), f_r.append(a_[1]), s_g.append(b_[0]), f_g.append(b_[1])
+        return s_r, s_g, f_r, f_g
+
+    def torch_d_step():
+        E.zero_grad(set_to_none=True)
+        s_r, s_g, _, _ = torch_msd(y, y_hat)
+        loss = GL.literal_discriminator_loss(s_r, s_g)[0]
+        loss.backward()
+        return loss
+
+    def ours_d_step():
+        D.zero_grad()
+        loss = nn.discriminator_loss(D(y, y_hat))[0]
+        loss.backward()
+        return loss
+
+    yh_o, yh_t = y_hat.clone().requires_grad_(True), y_hat.clone().requires_grad_(True)
+
+    def torch_g_step(grads=True):
+        yh_t.grad = None
+        E.zero_grad(set_to_none=True)
+        for q in E.parameters():
+            q.requires_grad_(grads)
+        _, s_g, f_r, f_g = torch_msd(y, yh_t)
+        loss = GL.literal_feature_loss(f_r, f_g) + GL.literal_generator_loss(s_g)[0]
+        loss.backward()
+        for q in E.parameters():
+            q.requires_grad_(True)
+        return loss
+
+    def ours_g_step(param_grads=True):
+        yh_o.grad = None
+        D.zero_grad()
+        out = D(y, yh_o, param_grads=param_grads)
+        loss = nn.feature_loss(out) + nn.generator_loss(out)[0]
+        loss.backward()
+        return loss
+
+    steps = []
+    for tag, ours, ref in (("D step: D(y, y_hat.detach()), discriminator_loss, backward", ours_d_step, torch_d_step),
+                           ("G step, param_grads=True: D(y, y_hat), feature_loss + generator_loss, backward to y_hat", ours_g_step, torch_g_step),
+                           ("G step, param_grads=False (torch: parameters without requires_grad)", lambda: ours_g_step(False), lambda: torch_g_step(False))):
+        # both sides advance their buffers at every call: reload them so that the two losses are of one state
+        D.load_state_dict(sd), E.load_state_dict(sd)
+        lo, lt = float(ours().detach()), float(ref().detach())
+        gd = None
+        if ours is not ours_d_step:
+            gd = float(f"{float((yh_o.grad - yh_t.grad).norm() / yh_t.grad.norm()):.2e}")
+        timed(ours, 2), timed(ref, 2)
+        ts = []
+        for _ in range(3):  # the two alternate: other work shares the machine
+            ts.append((timed(ours, a.steps), timed(ref, a.steps)))
+        s = {"what": tag, "batch": B, "samples": T, "ours_ms": round(min(t[0] for t in ts), 3), "torch_ms": round(min(t[1] for t in ts), 3),
+             "ours_ms_runs": [round(t[0], 3) for t in ts], "torch_ms_runs": [round(t[1], 3) for t in ts], "loss_ours": lo, "loss_torch": lt,
+             "y_hat_grad_rel_diff": gd, "join_ms": round(t_join, 3), "join_share_of_ours": round(t_join / min(t[0] for t in ts), 4),
+             "ours_kernels": kernel_count(ours), "torch_kernels": kernel_count(ref)}
+        print(json.dumps(s), flush=True)
+        steps.append(s)
+    if a.markdown:
+        print("\n| launch | us | MB moved | GB/s |\n|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['what']} | {r['us']} | {r['MB']} | {r['GBps']} |")
+        print("\n| step | ours ms (runs) | eager torch ms (runs) | joins ms (share) | ours / torch kernels |\n|---|---|---|---|---|")
+        for s in steps:
+            print(f"| {s['what']} | {s['ours_ms']} {s['ours_ms_runs']} | {s['torch_ms']} {s['torch_ms_runs']} | {s['join_ms']} "
+                  f"({100 * s['join_share_of_ours']:.1f} %) | {s['ours_kernels']} / {s['torch_kernels']} |")
+    return rows, steps
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -217,11 +388,14 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--markdown", action="store_true")
     ap.add_argument("--mpd", action="store_true", help="time the period half of the GAN step (nn.MultiPeriodDiscriminator and the losses)")
+    ap.add_argument("--msd", action="store_true", help="time the scale half of the GAN step (nn.SpectralNorm, nn.MultiScaleDiscriminator)")
     a = ap.parse_args(argv)
     import __graft_entry__ as ge
     ge.build()
     if a.mpd:
         return mpd_bench(a)
+    if a.msd:
+        return msd_bench(a)
     import dissc_amd
     import gen_train_ref as GT
     import synthdata as synth
