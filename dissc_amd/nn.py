@@ -15,6 +15,7 @@
     out = nn.MultiPeriodDiscriminator()(y, y_hat, lengths)                                # reference sr/models.py:263-286
     out = nn.MultiScaleDiscriminator()(y, y_hat, lengths)                                 # reference sr/models.py:310-333
     nn.discriminator_loss(out), nn.generator_loss(out), nn.feature_loss(out)              # reference sr/models.py:352-383
+    opt = nn.AdamW(D.parameters(), lr, betas); opt.step()                                 # torch.optim.AdamW, one launch (csrc/adamw.hip)
 
 ``conv1d`` is the stride-1 "same" Conv1d that 92 of the generator's 97 conv layers are, with dissc_conv1d's conventions:
 the leaky ReLU of the INPUT is applied on load (``in_slope``; 1.0 = none), ``add`` is a residual added in the epilogue,
@@ -617,6 +618,13 @@ def _f32(t, name, who):
     return t
 
 
+def _check_leaf_shaped(module, tensors):
+    shapes = module.leaf_shapes()
+    if len(tensors) != len(shapes) or any(tuple(t.shape) != s for t, s in zip(tensors, shapes)):
+        raise DisscError(f"{type(module).__name__}.named_views: tensors of the shapes {shapes} expected (parameters()'s), got "
+                         f"{[tuple(t.shape) for t in tensors]}")
+
+
 class WeightNorm:
     """w = g v / ||v|| over every dim but 0 for a whole list of tensors at once (dissc_wnorm_*): ``shapes`` are the tensors'
     (rows, cols), cols the product of every dim but 0.  ``off[i]`` / ``row_off[i]`` place tensor i in the flat layouts of
@@ -983,6 +991,28 @@ class CodeGenerator:
         return self._named(self.v_flat.grad, self.g_flat.grad, self.bias_flat.grad, self.dict_weight.grad,
                            None if self.spkr_weight is None else self.spkr_weight.grad)
 
+    def leaf_shapes(self):
+        """the shapes of parameters(), known before load_state_dict()"""
+        E = int(self.h.embedding_dim)
+        return [(self.wn.total,), (self.wn.total_rows,), (self.wn.bias_total,), (int(self.h.num_embeddings), E)] + \
+            ([(self.N_SPEAKERS, E)] if self.multispkr else [])
+
+    def named_views(self, *tensors):
+        """{reference key of a parameter: its view} of tensors shaped like parameters(), in that order and on any device (an
+        optimiser's moments, say); the order of the keys is the reference module's named_parameters()"""
+        _check_leaf_shaped(self, tensors)
+        return self._named(*tensors, *([] if self.multispkr else [None]))
+
+    def named_leaves(self):
+        """{reference key of a parameter: the index in parameters() of the leaf that holds it}, in named_views()'s order"""
+        out = {}
+        for name, _, _ in self.layers:
+            out.update({name + ".bias": 2, name + ".weight_g": 1, name + ".weight_v": 0})
+        out["dict.weight"] = 3
+        if self.multispkr:
+            out["spkr.weight"] = 4
+        return out
+
     def state_dict(self):
         """host copies under the reference's unfolded keys"""
         self._loaded()
@@ -1344,6 +1374,23 @@ class MultiPeriodDiscriminator:
         if any(p.grad is None for p in ps):
             raise RuntimeError("named_grads(): run a backward first")
         return self._named(*(p.grad for p in ps))
+
+    def leaf_shapes(self):
+        """the shapes of parameters(), known before load_state_dict()"""
+        return [(self.wn.total,), (self.wn.total_rows,), (self.wn.bias_total,)]
+
+    def named_views(self, *tensors):
+        """{reference key: its view, Conv2d shapes} of tensors shaped like parameters(), in that order and on any device (an
+        optimiser's moments, say); the order of the keys is the reference module's named_parameters()"""
+        _check_leaf_shaped(self, tensors)
+        return self._named(*tensors)
+
+    def named_leaves(self):
+        """{reference key: the index in parameters() of the leaf that holds it}, in named_views()'s order"""
+        out = {}
+        for name, _, _ in self.layers:
+            out.update({name + ".bias": 2, name + ".weight_g": 1, name + ".weight_v": 0})
+        return out
 
     def state_dict(self):
         """host copies under the reference's unfolded keys and Conv2d shapes"""
@@ -1795,6 +1842,26 @@ class MultiScaleDiscriminator:
             raise RuntimeError("named_grads(): run a backward first")
         return self._named(*(p.grad for p in ps))
 
+    def leaf_shapes(self):
+        """the shapes of parameters(), known before load_state_dict()"""
+        return [(self.sn.total,), (self.bias0_total,), (self.wn.total,), (self.wn.total_rows,), (self.wn.bias_total,)]
+
+    def named_views(self, *tensors):
+        """{reference key of a PARAMETER: its view} of tensors shaped like parameters(), in that order and on any device (an
+        optimiser's moments, say); discriminator 0's weight_u / weight_v are buffers and stay out.  The order of the keys is the
+        reference module's named_parameters()"""
+        _check_leaf_shaped(self, tensors)
+        return self._named(*tensors)
+
+    def named_leaves(self):
+        """{reference key of a PARAMETER: the index in parameters() of the leaf that holds it}, in named_views()'s order"""
+        out = {}
+        for name, _, _ in self.layers0:
+            out.update({name + ".bias": 1, name + ".weight_orig": 0})
+        for name, _, _ in self.layers12:
+            out.update({name + ".bias": 4, name + ".weight_g": 3, name + ".weight_v": 2})
+        return out
+
     def state_dict(self):
         """host copies under the reference's keys and Conv1d shapes, with discriminator 0's CURRENT weight_u / weight_v"""
         self._loaded()
@@ -1874,3 +1941,199 @@ class MultiScaleDiscriminator:
         return MSDOutput([fm[-1] for fm in fmaps], fmaps, lens, [B, B, B], sigma)
 
     __call__ = forward
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# nn.AdamW: torch.optim.AdamW's update over all leaves of an optimiser in one launch (dissc_adamw_step, csrc/adamw.hip), and the
+# conversion of its state to and from the reference's per-layer parameter list (the optim_g / optim_d of a do_* checkpoint).
+# ---------------------------------------------------------------------------------------------------------------------
+def _bind_adamw():
+    vp, i32, ll, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double
+    pp, pll = ctypes.POINTER(vp), ctypes.POINTER(ll)
+    lib.dissc_adamw_chunk.argtypes = lib.dissc_adamw_max_tensors.argtypes = []
+    lib.dissc_adamw_step.argtypes = [i32, pp, pp, pp, pp, pll, pll, f64, f64, f64, f64, f64, vp]
+
+
+_bind_adamw()
+
+ADAMW_CHUNK = int(lib.dissc_adamw_chunk())              # elements per workgroup
+ADAMW_MAX_TENSORS = int(lib.dissc_adamw_max_tensors())  # tensors per optimiser: one launch steps them all
+
+
+class AdamW:
+    """torch.optim.AdamW (amsgrad False, maximize False) over up to ADAMW_MAX_TENSORS float32 device leaves, one launch per step().
+
+        opt = nn.AdamW(D.parameters() + S.parameters(), lr=2e-4, betas=(0.8, 0.99)); loss.backward(); opt.step(); opt.lr *= 0.999
+
+    ``lr`` is a plain attribute read at each step.  A leaf whose .grad is None is skipped entirely, as torch skips it: no state,
+    no step count.  state_dict() / load_state_dict() use torch's format over the optimiser's own leaves (state[i] = {step: float32
+    scalar, exp_avg, exp_avg_sq}; one param group with torch's keys and ``initial_lr``): a torch.optim.AdamW over the same leaves
+    loads it, and this class loads torch's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        self.params = list(params)
+        if not 1 <= len(self.params) <= ADAMW_MAX_TENSORS:
+            raise DisscError(f"nn.AdamW: {len(self.params)} tensors; one launch steps 1 .. {ADAMW_MAX_TENSORS}")
+        for i, p in enumerate(self.params):
+            if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.is_leaf
+                    and p.numel() >= 1):
+                raise DisscError(f"nn.AdamW: params[{i}] must be a non-empty contiguous float32 CUDA leaf tensor")
+            if p.device != self.params[0].device:
+                raise DisscError(f"nn.AdamW: params[{i}] is on {p.device}, params[0] on {self.params[0].device}")
+        spans = sorted((p.data_ptr(), p.data_ptr() + 4 * p.numel(), i) for i, p in enumerate(self.params))
+        for (_, end, i), (start, _, j) in zip(spans, spans[1:]):
+            if start < end:
+                raise DisscError(f"nn.AdamW: params[{i}] and params[{j}] share memory; each element is stepped by one tensor")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        self.lr, self.initial_lr = float(lr), float(lr)
+        self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.state = {}  # index in params -> {"step": int, "exp_avg", "exp_avg_sq"}
+
+    def zero_grad(self):
+        for p in self.params:
+            p.grad = None
+
+    @torch.no_grad()
+    def step(self):
+        todo = [i for i, p in enumerate(self.params) if p.grad is not None]
+        for i in todo:
+            p, g = self.params[i], self.params[i].grad
+            if g.shape != p.shape or g.dtype != torch.float32 or g.device != p.device or not g.is_contiguous() or g.is_sparse:
+                raise DisscError(f"nn.AdamW: the grad of params[{i}] is {tuple(g.shape)} {g.dtype} on {g.device}; a contiguous "
+                                 f"float32 tensor of the shape {tuple(p.shape)} on {p.device} expected")
+        if not todo:
+            return
+        for i in todo:
+            if i not in self.state:
+                self.state[i] = {"step": 0, "exp_avg": torch.zeros_like(self.params[i]), "exp_avg_sq": torch.zeros_like(self.params[i])}
+        n = len(todo)
+        st = [self.state[i] for i in todo]
+        arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        numel = (ctypes.c_longlong * n)(*[self.params[i].numel() for i in todo])
+        t = (ctypes.c_longlong * n)(*[s["step"] + 1 for s in st])
+        dev = self.params[0].device
+        with torch.cuda.device(dev):
+            check(lib.dissc_adamw_step(n, arr([self.params[i] for i in todo]), arr([self.params[i].grad for i in todo]),
+                                       arr([s["exp_avg"] for s in st]), arr([s["exp_avg_sq"] for s in st]), numel, t, float(self.lr),
+                                       self.betas[0], self.betas[1], self.eps, self.weight_decay, current_stream_ptr(dev)),
+                  "dissc_adamw_step")
+        for s in st:
+            s["step"] += 1
+
+    def state_dict(self):
+        """torch's format; the moments are the optimiser's own tensors, as torch returns its own"""
+        state = {i: {"step": torch.tensor(float(s["step"]), dtype=torch.float32), "exp_avg": s["exp_avg"], "exp_avg_sq": s["exp_avg_sq"]}
+                 for i, s in sorted(self.state.items())}
+        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": True, "initial_lr": self.initial_lr, "params": list(range(len(self.params)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        groups = sd["param_groups"]
+        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(self.params))):
+            raise DisscError(f"nn.AdamW.load_state_dict: one param group over {len(self.params)} tensors expected")
+        g = groups[0]
+        if g.get("amsgrad", False) or g.get("maximize", False) or not g.get("decoupled_weight_decay", True):
+            raise DisscError("nn.AdamW.load_state_dict: amsgrad, maximize and coupled weight decay are not supported")
+        new = {}
+        for i, s in sd["state"].items():
+            i = int(i)
+            if not 0 <= i < len(self.params):
+                raise DisscError(f"nn.AdamW.load_state_dict: state[{i}] is outside the optimiser's {len(self.params)} tensors")
+            p = self.params[i]
+            if tuple(s["exp_avg"].shape) != tuple(p.shape) or tuple(s["exp_avg_sq"].shape) != tuple(p.shape):
+                raise DisscError(f"nn.AdamW.load_state_dict: state[{i}] has the shape {tuple(s['exp_avg'].shape)}, params[{i}] "
+                                 f"{tuple(p.shape)}")
+            step = float(s["step"])
+            if step != int(step) or step < 0:
+                raise DisscError(f"nn.AdamW.load_state_dict: state[{i}]['step'] = {step} is no step count")
+            own = lambda t: t.detach().to(p.device, torch.float32).contiguous().clone()
+            new[i] = {"step": int(step), "exp_avg": own(s["exp_avg"]), "exp_avg_sq": own(s["exp_avg_sq"])}
+        self.state = new
+        self.lr, self.betas, self.eps = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])
+        self.weight_decay, self.initial_lr = float(g["weight_decay"]), float(g.get("initial_lr", g["lr"]))
+
+
+def _module_leaf_ranges(modules):
+    out, at = [], 0
+    for m in modules:
+        n = len(m.leaf_shapes())
+        out.append((m, at, at + n))
+        at += n
+    return out, at
+
+
+def optimizer_state_to_reference(opt, modules):
+    """The state dictionary of an optimiser over the flat leaves of ``modules`` (their parameters() one after the other; ``opt``
+    is the optimiser or its state_dict(), ours or torch's) -> torch's dictionary over the reference's PER-LAYER parameter list:
+    indices 0 .. n - 1 in the order of the modules' named_views(), which is the reference modules' named_parameters() (optim_d:
+    [msd, mpd], reference sr/train.py chains msd.parameters() first), every moment with the shape of state_dict() at its key, every
+    parameter of one leaf with that leaf's step.  Host tensors out; works on CPU tensors."""
+    sd = opt.state_dict() if hasattr(opt, "state_dict") else opt
+    ranges, n_leaves = _module_leaf_ranges(modules)
+    groups = sd["param_groups"]
+    if len(groups) != 1 or list(groups[0]["params"]) != list(range(n_leaves)):
+        raise DisscError(f"optimizer_state_to_reference: one param group over the modules' {n_leaves} leaves expected")
+    state, k = {}, 0
+    for m, a, b in ranges:
+        present = [i for i in range(a, b) if i in sd["state"]]
+        zeros = [torch.zeros(shape) for shape in m.leaf_shapes()] if len(present) < b - a else None  # stand-ins of leaves without state
+        pick = lambda what: m.named_views(*[sd["state"][i][what].detach().cpu() if i in sd["state"] else zeros[i - a] for i in range(a, b)])
+        ms, vs = pick("exp_avg"), pick("exp_avg_sq")
+        for key, j in m.named_leaves().items():
+            if a + j in sd["state"]:
+                state[k] = {"step": torch.tensor(float(sd["state"][a + j]["step"]), dtype=torch.float32),
+                            "exp_avg": ms[key].clone(), "exp_avg_sq": vs[key].clone()}
+            k += 1
+    group = dict(groups[0])
+    group["params"] = list(range(k))
+    return {"state": state, "param_groups": [group]}
+
+
+def optimizer_state_from_reference(sd, modules):
+    """The inverse: torch's dictionary over the reference's per-layer parameters -> the dictionary over the modules' flat leaves
+    (host tensors; the alignment gaps of a leaf get zero moments).  Refused: a parameter count or a shape other than the modules',
+    and per-parameter steps that differ within one leaf -- a reference checkpoint never has them, all its parameters step
+    together."""
+    ranges, n_leaves = _module_leaf_ranges(modules)
+    groups = sd["param_groups"]
+    state, k = {}, 0
+    for m, a, b in ranges:
+        shapes = m.leaf_shapes()
+        ms, vs = [torch.zeros(s) for s in shapes], [torch.zeros(s) for s in shapes]
+        vm, vv, leaves = m.named_views(*ms), m.named_views(*vs), m.named_leaves()
+        steps = {}  # leaf -> {step or None of each of its parameters}
+        for key, view in vm.items():
+            leaf = a + leaves[key]
+            s = sd["state"].get(k, None)
+            steps.setdefault(leaf, set()).add(None if s is None else float(s["step"]))
+            if s is not None:
+                for what, dst in (("exp_avg", view), ("exp_avg_sq", vv[key])):
+                    if tuple(s[what].shape) != tuple(dst.shape):
+                        raise DisscError(f"optimizer_state_from_reference: parameter {k} ({key}) has {what} of the shape "
+                                         f"{tuple(s[what].shape)}, expected {tuple(dst.shape)}")
+                    dst.copy_(s[what].detach().to("cpu", torch.float32))
+            k += 1
+        for leaf, seen in steps.items():
+            if len(seen) != 1:
+                raise DisscError(f"optimizer_state_from_reference: the parameters of flat leaf {leaf} of {type(m).__name__} have "
+                                 f"different steps {sorted(seen, key=str)}; one leaf steps as a whole")
+            step = next(iter(seen))
+            if step is not None:
+                state[leaf] = {"step": torch.tensor(step, dtype=torch.float32), "exp_avg": ms[leaf - a], "exp_avg_sq": vs[leaf - a]}
+    if len(groups) != 1 or list(groups[0]["params"]) != list(range(k)):
+        raise DisscError(f"optimizer_state_from_reference: one param group over the modules' {k} parameters expected, got "
+                         f"{[len(g['params']) for g in groups]}")
+    group = dict(groups[0])
+    group["params"] = list(range(n_leaves))
+    return {"state": state, "param_groups": [group]}

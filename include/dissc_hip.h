@@ -1070,6 +1070,53 @@ int dissc_snorm_forward(dissc_snorm_t h, const float* w_orig, const float* u_in,
 int dissc_snorm_backward(dissc_snorm_t h, const float* w_orig, const float* state, const float* const* gw_ptrs, float* gw_orig,
                          void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * AdamW over every leaf of an optimiser in one launch (csrc/adamw.hip; composed in dissc_amd/nn.py's AdamW).  Added without an ABI
+ * bump, as the sections above.  The non-capturable single-tensor path of torch.optim.AdamW, amsgrad False, maximize False, per
+ * element and in this order, every product and sum rounded on its own (nothing contracted):
+ *   p *= 1 - lr wd;  m += (g - m)(1 - b1);  v = v b2 + ((1 - b2) g) g;  denom = sqrt(v) / sqrt(1 - b2^t) + eps;
+ *   p -= (lr / (1 - b1^t)) (m / denom)
+ * (m's line is torch's lerp_ for a weight 1 - b1 below 0.5, i.e. b1 > 0.5; at b1 <= 0.5 torch evaluates g - (g - m) b1, so the last
+ * bits can differ there.)
+ * Every scalar (1 - lr wd, 1 - b1, b2, 1 - b2, eps, lr / (1 - b1^t), sqrt(1 - b2^t)) is formed here in double and rounded once.
+ * dissc_adamw_step: all six array arguments are HOST arrays of n entries (1 <= n <= dissc_adamw_max_tensors() = 16): the DEVICE
+ *   pointers of p, g, m, v (four different f32 buffers of numel[i] >= 1 elements) and the step count t[i] >= 1 of THIS update,
+ *   per tensor.  They travel in the kernel's arguments: nothing is uploaded per step.  A tensor whose four pointers are 16-byte
+ *   aligned runs on float4s with a scalar tail, any other on scalars throughout; the bits are the same.  Workgroups take chunks of
+ *   dissc_adamw_chunk() elements.  No atomics, each element written by one thread: bit-reproducible, and a tensor's results do not
+ *   depend on the list it is in.  g is never written.  DISSC_EINVAL with a message before any launch: n outside its range, a null
+ *   or repeated pointer, numel or t below 1, more than 2^30 chunks, lr / eps / weight_decay negative or NaN, a beta outside [0, 1).
+ * ------------------------------------------------------------------------- */
+int dissc_adamw_chunk(void);
+int dissc_adamw_max_tensors(void);
+int dissc_adamw_step(int n, float* const* p, const float* const* g, float* const* m, float* const* v, const long long* numel,
+                     const long long* t, double lr, double b1, double b2, double eps, double weight_decay, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * The vocoder trainer's batch as one gather launch from a device-resident corpus (csrc/segment_gather.hip; composed in
+ * dissc_amd/gan_train.py's SegmentSampler; CodeDataset.__getitem__ with eval_mode False, reference sr/dataset.py:240-267 and
+ * 199-219).  Added without an ABI bump.
+ * dissc_segment_create: HOST arrays; uploads to the current device, which the handle then serves.  U >= 1 utterances of
+ *   frames[u] >= 1 frames after the trim, frames[u] hop < 2^31; packed one after the other: audio f32 (hop samples per frame),
+ *   codes i32 and f0 f32 (one per frame), spkr i32 [U].  The frame offsets stay in the handle on both sides.
+ * dissc_segment_interval_end: HOST ONLY.  The last legal start_step of an utterance at this segment, N' / hop - segment / hop with
+ *   N' = frames hop 2^j the length after the doublings that reach the segment.
+ * dissc_segment_gather: table is a HOST array of B (utterance, start_step) pairs of i32, 1 <= B <= dissc_segment_max_batch() =
+ *   256, passed by value to the kernel.  Writes y f32 [B, 1, segment], code i64 [B, F], f0 f32 [B, 1, F], spkr i64 [B, 1], F =
+ *   segment / hop, in one launch and nothing else: sample i of row b is sample (start_step hop + i) mod (frames hop) of its
+ *   utterance, frame j is frame (start_step + j) mod frames.  DISSC_EINVAL with a message naming the row, before any launch: an
+ *   utterance outside the corpus, a start_step outside [0, interval_end], B outside its range, a segment that is no positive
+ *   multiple of hop below 2^30, another current device.
+ * ------------------------------------------------------------------------- */
+typedef struct dissc_segment* dissc_segment_t;
+int dissc_segment_max_batch(void);
+int dissc_segment_create(int U, const long long* frames, int hop, const float* audio, const int32_t* codes, const float* f0,
+                         const int32_t* spkr, dissc_segment_t* out);
+void dissc_segment_destroy(dissc_segment_t h);
+int dissc_segment_interval_end(dissc_segment_t h, int utterance, int segment, long long* out);
+int dissc_segment_gather(dissc_segment_t h, const int32_t* table, int B, int segment, float* y, int64_t* code, float* f0,
+                         int64_t* spkr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

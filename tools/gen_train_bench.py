@@ -23,7 +23,12 @@ steps against the reference's MultiPeriodDiscriminator and loss functions in eag
 
 times the scale half (msd_bench below; profiles/msd_train.md): every dissc_snorm_* launch of csrc/spectral_norm.hip on the eight
 matrices of discriminator 0 next to the bytes it must move, the two joined-map copies per map of scale 0, and the discriminator's
-and the generator's scale-side steps against spectral_norm / weight_norm Conv1d modules in eager torch, in alternated runs."""
+and the generator's scale-side steps against spectral_norm / weight_norm Conv1d modules in eager torch, in alternated runs.
+
+    python tools/gen_train_bench.py --gan [--batch 32] [--frames 28] [--steps 20] [--blocks 3] [--markdown]
+
+times what the GAN trainer adds (gan_bench below; profiles/gan_train.md): nn.AdamW against torch.optim.AdamW on the same leaves,
+the gather launch against the host path, and GanTrainer.step against the same step in eager torch."""
 import argparse
 import ctypes
 import json
@@ -380,6 +385,207 @@ def msd_bench(a):
     return rows, steps
 
 
+def gan_bench(a):
+    """--gan: what the GAN trainer adds, at 32 x 8 960 samples with the shipped VCTK config's model (profiles/gan_train.md):
+    nn.AdamW.step() on optim_d's and optim_g's leaves against torch.optim.AdamW (default, foreach=True, fused=True) on copies of
+    the same leaves with the same grads, in alternating blocks; the gather launch against the host path that builds the same
+    batch and uploads it; GanTrainer.step against the same lines composed from eager torch modules and torch.optim.AdamW, from the same
+    weights on the same batch, in alternating blocks."""
+    import time
+
+    import numpy as np
+    import synthdata as synth
+    from dissc_amd import gan_train, nn
+    h = dict(synth.VCTK_CONFIG, learning_rate=2e-4, adam_b1=0.8, adam_b2=0.99, lr_decay=0.999, seed=1234, batch_size=a.batch,
+             segment_size=320 * a.frames, code_hop_size=320)
+    for k, v in dict(sampling_rate=16000, n_fft=1024, num_mels=80, hop_size=256, win_size=1024, fmin=0, fmax=8000, fmax_for_loss=None).items():
+        h.setdefault(k, v)
+    trainer = gan_train.GanTrainer(h, DEV).init(seed=0)
+    rows = []
+
+    # ---- 1. the optimiser: alternating blocks, every block shown ----
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    for name, leaves in (("optim_d", trainer.msd.parameters() + trainer.mpd.parameters()), ("optim_g", trainer.generator.parameters())):
+        n = sum(p.numel() for p in leaves)
+        grads = [torch.randn(p.shape, device=DEV, generator=gen) for p in leaves]
+        kw = dict(lr=2e-4, betas=(0.8, 0.99))
+
+        def make(ctor):
+            ps = [p.detach().clone().requires_grad_(True) for p in leaves]
+            for q, g in zip(ps, grads):
+                q.grad = g
+            return ctor(ps).step
+        variants = [("nn.AdamW", make(lambda ps: nn.AdamW(ps, **kw))), ("torch default", make(lambda ps: torch.optim.AdamW(ps, **kw))),
+                    ("torch foreach=True", make(lambda ps: torch.optim.AdamW(ps, foreach=True, **kw))),
+                    ("torch fused=True", make(lambda ps: torch.optim.AdamW(ps, fused=True, **kw)))]
+        for _, fn in variants:
+            timed(fn, 5)
+        blocks = {v: [] for v, _ in variants}
+        for _ in range(a.blocks):
+            for v, fn in variants:
+                blocks[v].append(timed(fn, a.steps))
+        for v, fn in variants:
+            ms = sorted(blocks[v])[len(blocks[v]) // 2]
+            rows.append(row(f"{name} ({n / 1e6:.1f} M floats, {len(leaves)} leaves): {v}", ms, 28e-6 * n,
+                            {"blocks_us": [round(1e3 * x, 1) for x in blocks[v]], "kernels": kernel_count(fn)}))
+        del variants, grads
+        torch.cuda.empty_cache()
+
+    # ---- 2. the batch: one gather launch against crops on the host and four uploads ----
+    rs = np.random.RandomState(0)
+    items = []
+    for u in range(4 * a.batch):
+        T = int(rs.randint(a.frames // 2, 12 * a.frames))
+        items.append(dict(name=f"u{u}", gt=rs.uniform(-1, 1, 320 * T).astype(np.float32), code=rs.randint(0, 100, T).astype(np.int64),
+                          f0=rs.uniform(-2, 2, T).astype(np.float32), spkr=int(rs.randint(0, 200))))
+    sampler = gan_train.SegmentSampler(h, items, seed=0, device=DEV)
+    tables = [sampler.draw(i % len(sampler)) for i in range(64)]
+
+    def ours(i):
+        return sampler.gather(tables[i % 64])
+
+    def host(i):
+        crops = [gan_train.crop_host(items[u], s, 320, h["segment_size"]) for u, s in tables[i % 64]]
+        return {"y": torch.from_numpy(np.stack([c[0] for c in crops])[:, None]).to(DEV), "code": torch.from_numpy(np.stack([c[1] for c in crops])).to(DEV),
+                "f0": torch.from_numpy(np.stack([c[2] for c in crops])[:, None]).to(DEV),
+                "spkr": torch.from_numpy(np.array([[items[u]["spkr"]] for u, _ in tables[i % 64]], np.int64)).to(DEV)}
+    assert all(torch.equal(x, y) for x, y in zip(ours(0).values(), host(0).values()))
+
+    def wall(fn, iters):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(iters):
+            fn(i)
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / iters
+    mb = 1e-6 * a.batch * (4 * h["segment_size"] * 2 + a.frames * (4 + 8 + 4 + 4))
+    wall(ours, 20), wall(host, 20)
+    blocks = {"gather launch (host table by value)": [], "host crops + four uploads": []}
+    for _ in range(a.blocks):
+        blocks["gather launch (host table by value)"].append(wall(ours, 200))
+        blocks["host crops + four uploads"].append(wall(host, 200))
+    for what, b in blocks.items():
+        rows.append(row(f"batch {a.batch} x {h['segment_size']}: {what}, wall per batch", sorted(b)[len(b) // 2], mb,
+                        {"blocks_us": [round(1e3 * x, 1) for x in b]}))
+    rows.append(row("gather, back-to-back calls between two device events", timed(lambda: ours(0), 200), mb))
+
+    # ---- 3. the whole alternation: GanTrainer.step against the same lines in eager torch (the generator of main() below, the
+    # period side of mpd_bench, the scale side of msd_bench, torch.optim.AdamW), from the same weights on the same batch ----
+    import gan_loss_ref as GL
+    import gen_train_ref as GT
+    import mpd_cases as MP
+    import msd_cases as MS
+    import dissc_amd
+    from oracle import generator_ref as G
+    F = torch.nn.functional
+    batch = sampler.batch(0)
+    y, T = batch["y"], h["segment_size"]
+    PG = {k: t.to(DEV).requires_grad_(True) for k, t in trainer.generator.state_dict().items()}
+    PP = {k: t.to(DEV).requires_grad_(True) for k, t in trainer.mpd.state_dict().items()}
+    E = MS.torch_msd(trainer.msd.state_dict(), torch.float32).to(DEV)  # spectral_norm / weight_norm Conv1d modules, train() mode
+    pools = [torch.nn.AvgPool1d(4, 2, padding=2), torch.nn.AvgPool1d(4, 2, padding=2)]
+    kw = dict(lr=float(h["learning_rate"]), betas=(h["adam_b1"], h["adam_b2"]))
+    eg, ed = torch.optim.AdamW(list(PG.values()), **kw), torch.optim.AdamW(list(E.parameters()) + list(PP.values()), **kw)
+    basis = torch.from_numpy(dissc_amd.mel.mel_filterbank(16000, 1024, 80)).float().to(DEV)
+    window = torch.hann_window(1024, device=DEV)
+    y_mel = torch_mel(y[:, 0], basis, window)  # the reference's loader hands the target's mel over with the batch
+
+    def eager_mpd(wav, grads):
+        scores, fmaps = [], []
+        for i, period in enumerate(MP.PERIODS):
+            x = wav
+            if T % period:
+                x = F.pad(x, (0, period - T % period), "reflect")
+            x = x.view(x.shape[0], 1, -1, period)
+            fm = []
+            for j, (name, _, _, k) in enumerate(MP.LAYERS):
+                pre = f"discriminators.{i}.{name}"
+                v, g, bb = (PP[pre + sfx] if grads else PP[pre + sfx].detach() for sfx in (".weight_v", ".weight_g", ".bias"))
+                x = F.conv2d(x, torch._weight_norm(v, g, 0), bb, stride=(3, 1) if j < 4 else 1, padding=((k - 1) // 2, 0))
+                if j < 5:
+                    x = F.leaky_relu(x, 0.1)
+                fm.append(x)
+            scores.append(torch.flatten(x, 1, -1))
+            fmaps.append(fm)
+        return scores, fmaps
+
+    def eager_disc_s(d, x):
+        fmap = []
+        for conv in d.convs:
+            x = F.leaky_relu(conv(x), 0.1)
+            fmap.append(x)
+        x = d.conv_post(x)
+        fmap.append(x)
+        return torch.flatten(x, 1, -1), fmap
+
+    def eager_msd(yr, yg):
+        s_r, s_g, f_r, f_g = [], [], [], []
+        for i, d in enumerate(E.discriminators):
+            if i:
+                yr, yg = pools[i - 1](yr), pools[i - 1](yg)
+            a_, b_ = eager_disc_s(d, yr), eager_disc_s(d, yg)
+            s_r.append(a_[0]), f_r.append(a_[1]), s_g.append(b_[0]), f_g.append(b_[1])
+        return s_r, s_g, f_r, f_g
+
+    def eager_step(d_grads_in_g_step):
+        """the reference's lines (sr/train.py:142-191); d_grads_in_g_step True is the reference as written (the discriminators'
+        parameters keep requires_grad in the generator's half, their gradients are computed and dropped), False detaches them
+        there, which is what GanTrainer's param_grads=False does"""
+        w = {}
+        for k, t in PG.items():
+            if k.endswith(".weight_g"):
+                w[k[:-2]] = torch._weight_norm(PG[k[:-2] + "_v"], t, 0)
+            elif not k.endswith(".weight_v"):
+                w[k] = t
+        y_hat = GT._forward(w, h, G.embed_concat(w, batch["code"], batch["f0"], batch["spkr"]), None, None)
+        ed.zero_grad()
+        yd = y_hat.detach()
+        loss_f = GL.literal_discriminator_loss(eager_mpd(y, True)[0], eager_mpd(yd, True)[0])[0]
+        s_r, s_g, _, _ = eager_msd(y, yd)
+        loss_d = GL.literal_discriminator_loss(s_r, s_g)[0] + loss_f
+        loss_d.backward()
+        ed.step()
+        eg.zero_grad()
+        loss_mel = F.l1_loss(y_mel, torch_mel(y_hat[:, 0], basis, window)) * 45
+        for q in E.parameters():
+            q.requires_grad_(d_grads_in_g_step)
+        (_, ff_r), (sf_g, ff_g) = eager_mpd(y, d_grads_in_g_step), eager_mpd(y_hat, d_grads_in_g_step)
+        _, ss_g, fs_r, fs_g = eager_msd(y, y_hat)
+        loss_g = GL.literal_generator_loss(ss_g)[0] + GL.literal_generator_loss(sf_g)[0] + GL.literal_feature_loss(fs_r, fs_g) + \
+            GL.literal_feature_loss(ff_r, ff_g) + loss_mel
+        loss_g.backward()
+        for q in E.parameters():
+            q.requires_grad_(True)
+        eg.step()
+        return loss_d.detach(), loss_g.detach()
+
+    # the first step of each from one state: the same losses
+    first = trainer.step(batch)
+    e_d, e_g = eager_step(False)
+    same = {"what": "first step from the same weights", "ours_loss_disc_all": float(first["loss_disc_all"]), "eager_loss_disc_all": float(e_d),
+            "ours_loss_gen_all": float(first["loss_gen_all"]), "eager_loss_gen_all": float(e_g)}
+    print(json.dumps(same), flush=True)
+    variants = [("GanTrainer.step", lambda i=0: trainer.step(batch)),
+                ("eager torch, discriminators detached in the generator's half", lambda i=0: eager_step(False)),
+                ("eager torch, the reference as written (discriminator gradients computed in both halves)", lambda i=0: eager_step(True))]
+    for _, fn in variants:
+        wall(fn, 3)
+    blocks = {v: [] for v, _ in variants}
+    for _ in range(a.blocks):
+        for v, fn in variants:
+            blocks[v].append(wall(fn, a.steps))
+    for v, fn in variants:
+        rows.append(row(f"whole alternation, wall per step: {v}", sorted(blocks[v])[len(blocks[v]) // 2], 0.0,
+                        {"blocks_ms": [round(x, 2) for x in blocks[v]], "kernels": kernel_count(fn)}))
+    opt = lambda i=0: (trainer.optim_d.step(), trainer.optim_g.step())
+    rows.append(row("  of GanTrainer.step: optim_d.step() + optim_g.step()", timed(opt, a.steps), 28e-6 * sum(p.numel() for o in (trainer.optim_d, trainer.optim_g) for p in o.params)))
+    if a.markdown:
+        print("\n| what | us | MB | GB/s | blocks | kernels |\n|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['what']} | {r['us']} | {r['MB']} | {r['GBps']} | {r.get('blocks_us', r.get('blocks_ms', ''))} | {r.get('kernels', '')} |")
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -389,6 +595,8 @@ def main(argv=None):
     ap.add_argument("--markdown", action="store_true")
     ap.add_argument("--mpd", action="store_true", help="time the period half of the GAN step (nn.MultiPeriodDiscriminator and the losses)")
     ap.add_argument("--msd", action="store_true", help="time the scale half of the GAN step (nn.SpectralNorm, nn.MultiScaleDiscriminator)")
+    ap.add_argument("--gan", action="store_true", help="time what the GAN trainer adds: nn.AdamW, the segment gather, GanTrainer.step")
+    ap.add_argument("--blocks", type=int, default=3, help="--gan: alternating blocks per variant")
     a = ap.parse_args(argv)
     import __graft_entry__ as ge
     ge.build()
@@ -396,6 +604,8 @@ def main(argv=None):
         return mpd_bench(a)
     if a.msd:
         return msd_bench(a)
+    if a.gan:
+        return gan_bench(a)
     import dissc_amd
     import gen_train_ref as GT
     import synthdata as synth
