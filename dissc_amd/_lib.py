@@ -78,6 +78,8 @@ def _load():
                                    ctypes.c_size_t, ctypes.POINTER(vp)]
     L.dissc_gen_create_ex.argtypes = [ctypes.POINTER(DisscGenConfig), ctypes.POINTER(DisscTensor),
                                       ctypes.c_size_t, i32, ctypes.POINTER(vp)]
+    L.dissc_gen_create_rb.argtypes = [ctypes.POINTER(DisscGenConfig), ctypes.POINTER(DisscTensor),
+                                      ctypes.c_size_t, i32, i32, ctypes.POINTER(vp)]
     L.dissc_gen_destroy.argtypes = [vp]
     L.dissc_gen_destroy.restype = None
     L.dissc_gen_hop.argtypes = [vp]
@@ -131,6 +133,9 @@ def _load():
     L.dissc_conv_s2_bench.argtypes = [i32] * 5 + [ctypes.POINTER(ctypes.c_float)]
     L.dissc_pair_bench.argtypes = [i32] * 8 + [ctypes.POINTER(ctypes.c_float)]
     L.dissc_pair_info.argtypes = [i32] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2
+    L.dissc_resblock2_bench.argtypes = [i32] * 9 + [ctypes.POINTER(ctypes.c_float)]
+    L.dissc_resblock2_info.argtypes = [i32] * 4 + [ctypes.POINTER(ctypes.c_int)] * 2
+    L.dissc_resblock2_1d.argtypes = [vp] * 8 + [i32] * 7 + [ctypes.c_float, i32, ctypes.c_float, i32, vp]
     L.dissc_conv_info.argtypes = [i32] * 7 + [ctypes.POINTER(DisscConvLaunch), i32, ctypes.POINTER(ctypes.c_int)]
     L.dissc_wino8_info.argtypes = [i32] * 6 + [ctypes.POINTER(DisscWino8Plan)]
     L.dissc_wino_info.argtypes = [i32] * 5 + [ctypes.POINTER(DisscWinoPlan)]

@@ -55,7 +55,8 @@ void set_error(const char* fmt, ...);
   X(pair_tc6, 3, "pair_tc6") \
   X(pair_f23_c64, 1, "pair_f23_c64") \
   X(pair_tc6_c64, 1, "pair_tc6_c64") \
-  X(chain_f23, 3, "chain_f23")
+  X(chain_f23, 3, "chain_f23") \
+  X(rb2_fused, 59, "rb2_fused")
 // options of the kernels that only DISSC_EXPERIMENTAL=1 builds carry (experimental/csrc: gates failed, kept for the record)
 #define DISSC_OPTION_LIST_EXPERIMENTAL(X) \
   X(graphs, 0, "graphs") \
@@ -250,6 +251,11 @@ struct ConvArgs {
 
 constexpr int MAX_TAP_SPAN = 60;    // (KS-1)*dil of the default instances (staging register budget)
 constexpr int WIDE_TAP_SPAN = 128;  // wide instance (HuBERT positional conv, k=128)
+// Widest span of a stride-1, ungrouped layer of ANY row count (ResBlock2 of HiFi-GAN V3: k = 7, d = 12).  Spans in
+// (MAX_TAP_SPAN, RB_TAP_SPAN] run on the wide instances' 256-column tiles, which walk the rows 16 or 32 at a time (untuned);
+// every span <= MAX_TAP_SPAN keeps its instance.
+constexpr int RB_TAP_SPAN = 72;
+constexpr int WIDE_TILE_BN = 256;   // time tile of every wide instance, both families
 
 // Pick a tile shape for M rows / Lmax columns and launch.  Returns a DISSC_* code.
 int launch_conv(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_t stream);
@@ -441,6 +447,11 @@ int launch_reschain_f23(const float* w, const float* bias, int C, const float* x
 
 // one residual pair y = x + conv_1(lrelu(conv_d(lrelu(x)))) per launch, exact fp32 (respair.hip)
 bool respair_supported(int C, int KS, int dil);
+// one ResBlock2 (two dilated convs, y1 on the CU) in one launch (resblock2.hip): the instances, the outputs a workgroup owns, the launch
+bool resblock2_supported(int C, int KS, int d0, int d1);
+int resblock2_tile(int KS, int d0, int d1);
+int launch_resblock2(const DevConv& c1, const DevConv& c2, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld,
+                     float slope, hipStream_t stream);
 int launch_respair(const DevConv& c1, const DevConv& c2, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ld,
                    float slope, hipStream_t stream);
 

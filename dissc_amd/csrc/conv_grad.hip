@@ -33,7 +33,9 @@ namespace dissc {
 
 constexpr int CG_HALO = 32;                 // largest |tap offset|, rounded up to 4 (MAX_TAP_SPAN / 2 = 30)
 constexpr int CG_LDD = CG_T + 1;            // odd row strides: a fragment read (32 rows x 1 column) is conflict-free
-constexpr int CG_LDA = CG_T + 2 * CG_HALO + 1;
+constexpr int CG_HALO_WIDE = 36;            // ... of the spans in (MAX_TAP_SPAN, RB_TAP_SPAN]: instances of their own, so that the
+                                            // LDS layout of every span <= MAX_TAP_SPAN stays what it was
+constexpr int cg_lda(int halo) { return CG_T + 2 * halo + 1; }
 constexpr size_t CG_PART_BUDGET = (size_t)56 << 20;  // bytes of partials (the workspace stays under 64 MB)
 constexpr int CG_TARGET_WG = 512;           // two workgroups per CU
 
@@ -71,8 +73,9 @@ struct WgradArgs {
   int WCI, WT, CIB, TS, nch, cpp;
 };
 
-template <int NG>
+template <int NG, int HALO = CG_HALO>
 __global__ void __launch_bounds__(256, 2) convgrad_wgrad_kernel(WgradArgs a) {
+  constexpr int CG_LDA = cg_lda(HALO);
   extern __shared__ float cg_lds[];
   float* ds = cg_lds;                 // gy  [32][CG_LDD]
   float* as = cg_lds + 32 * CG_LDD;   // lrelu(x) [32 WCI][CG_LDA], column c = position t0 - halo + c
@@ -113,8 +116,9 @@ __global__ void __launch_bounds__(256, 2) convgrad_wgrad_kernel(WgradArgs a) {
       for (int qq = 0; qq < 4; ++qq) ds[r * CG_LDD + 4 * v + qq] = (t + qq < len) ? g4[qq] : 0.f;
     }
     {
-      const int v = tid & 31, t = t0 - a.halo + 4 * v;
-      if (v < aw4)
+      // (a wide halo's rows are up to 34 float4 long: two passes of the 32 lanes that share a row)
+      for (int v = tid & 31; v < aw4; v += (HALO > CG_HALO ? 32 : aw4)) {
+        const int t = t0 - a.halo + 4 * v;
         for (int r = tid >> 5; r < nrows; r += 8) {
           f32x4 x4 = {0.f, 0.f, 0.f, 0.f};
           if (t >= 0 && t < len && ci0 + r < a.Cin) x4 = *reinterpret_cast<const f32x4*>(xb + (size_t)r * a.ldx + t);
@@ -124,6 +128,7 @@ __global__ void __launch_bounds__(256, 2) convgrad_wgrad_kernel(WgradArgs a) {
             as[r * CG_LDA + 4 * v + qq] = (t + qq < len) ? (xv > 0.f ? xv : xv * a.slope) : 0.f;  // (t < 0: loaded as zero)
           }
         }
+      }
     }
     __syncthreads();
     if (live) {
@@ -275,12 +280,13 @@ __global__ void convgrad_repack_kernel(const float* __restrict__ w, int Cout, in
   packed[idx] = v;
 }
 
-template <int NG>
+template <int NG, int HALO = CG_HALO>
 static int cg_launch_wgrad(const WgradArgs& a, const CgPlan& p, hipStream_t st) {
-  const size_t lds = ((size_t)32 * CG_LDD + (size_t)32 * p.WCI * CG_LDA) * sizeof(float);
+  const size_t lds = ((size_t)32 * CG_LDD + (size_t)32 * p.WCI * cg_lda(HALO)) * sizeof(float);
+  static_assert(((size_t)32 * CG_LDD + (size_t)32 * 4 * cg_lda(HALO)) * sizeof(float) <= 80 * 1024, "two workgroups per CU");
   static DeviceOnce attr_once;  // per device (common.h)
-  DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&convgrad_wgrad_kernel<NG>), 80 * 1024));
-  hipLaunchKernelGGL((convgrad_wgrad_kernel<NG>), dim3(p.coT, p.ciS, p.P), dim3(256), lds, st, a);
+  DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&convgrad_wgrad_kernel<NG, HALO>), 80 * 1024));
+  hipLaunchKernelGGL((convgrad_wgrad_kernel<NG, HALO>), dim3(p.coT, p.ciS, p.P), dim3(256), lds, st, a);
   return DISSC_OK;
 }
 
@@ -378,15 +384,15 @@ struct dissc_convgrad : CgLayer {
 
 extern "C" {
 
-int dissc_convgrad_create(int Cin, int Cout, int k, int dilation, dissc_convgrad_t* out) {
+static int convgrad_create(const char* who, int max_span, int Cin, int Cout, int k, int dilation, dissc_convgrad_t* out) {
   if (out) *out = nullptr;
-  if (int rc = cg_check_create("dissc_convgrad_create", out, Cin, Cout)) return rc;
+  if (int rc = cg_check_create(who, out, Cin, Cout)) return rc;
   if (k < 1 || k % 2 != 1 || k > CG_MAX_K) {
-    set_error("dissc_convgrad_create: kernel size %d (odd, at most %d)", k, CG_MAX_K);
+    set_error("%s: kernel size %d (odd, at most %d)", who, k, CG_MAX_K);
     return DISSC_EINVAL;
   }
-  if (dilation < 1 || (long long)(k - 1) * dilation > MAX_TAP_SPAN) {
-    set_error("dissc_convgrad_create: (k - 1) x dilation = %d x %d exceeds the tap span %d", k - 1, dilation, MAX_TAP_SPAN);
+  if (dilation < 1 || (long long)(k - 1) * dilation > max_span) {
+    set_error("%s: (k - 1) x dilation = %d x %d exceeds the tap span %d", who, k - 1, dilation, max_span);
     return DISSC_EINVAL;
   }
   dissc_convgrad* h = new dissc_convgrad();
@@ -394,6 +400,16 @@ int dissc_convgrad_create(int Cin, int Cout, int k, int dilation, dissc_convgrad
   h->Cin = Cin; h->Cout = Cout; h->k = k; h->dil = dilation;
   *out = h;
   return DISSC_OK;
+}
+
+int dissc_convgrad_create(int Cin, int Cout, int k, int dilation, dissc_convgrad_t* out) {
+  return convgrad_create("dissc_convgrad_create", MAX_TAP_SPAN, Cin, Cout, k, dilation, out);
+}
+
+// the same handle with the tap span of a ResBlock2 conv (k = 7, d = 12) admitted: what nn.conv1d creates
+int dissc_convgrad_create_wide(int Cin, int Cout, int k, int dilation, dissc_convgrad_t* out) {
+  static_assert(RB_TAP_SPAN / 2 <= CG_HALO_WIDE && CG_HALO_WIDE % 4 == 0, "the wide halo covers every admitted tap offset");
+  return convgrad_create("dissc_convgrad_create_wide", RB_TAP_SPAN, Cin, Cout, k, dilation, out);
 }
 
 void dissc_convgrad_destroy(dissc_convgrad_t h) { delete h; }
@@ -471,7 +487,10 @@ int dissc_convgrad_backward(dissc_convgrad_t h, const float* x, const float* gy,
     a.halo = (((h->k - 1) * h->dil) / 2 + 3) & ~3;
     a.slope = in_slope;
     a.WCI = p.WCI; a.WT = p.WT; a.CIB = p.CIB; a.TS = p.TS; a.nch = p.nch; a.cpp = p.cpp;
-    if ((rc = cg_dispatch_ng(p.NG, who, "tap groups", [&](auto ng) { return cg_launch_wgrad<decltype(ng)::value>(a, p, st); })))
+    if ((rc = cg_dispatch_ng(p.NG, who, "tap groups", [&](auto ng) {
+           return a.halo > CG_HALO ? cg_launch_wgrad<decltype(ng)::value, CG_HALO_WIDE>(a, p, st)
+                                   : cg_launch_wgrad<decltype(ng)::value>(a, p, st);
+         })))
       return rc;
     cg_launch_reduce(part, p.P * p.WT, p.gw, gw, st);
   }

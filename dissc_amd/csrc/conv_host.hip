@@ -200,7 +200,8 @@ int run_conv(const DevConv& dc, const float* x, float* out, const Batch& bt, con
   a.ragged_enum = 0;
   a.groups = dc.groups; a.nsub_group = dc.Mpad / (dc.m32 ? 32 : 16); a.act = dc.act; a.m32 = dc.m32; a.prec = dc.prec;
   a.cfg32 = conv_launch_cfg32(dc, bt.B, bt.Lmax);
-  a.XW = conv_xw(dc.M, dc.KS, dc.dil, dc.stride, dc.m32, a.cfg32 >= 0 ? conv32_cfg_bn(a.cfg32) : 0);
+  const bool wide = dc.stride == 1 && (dc.KS - 1) * dc.dil > MAX_TAP_SPAN;  // (every wide instance has the same time tile)
+  a.XW = conv_xw(dc.M, dc.KS, dc.dil, dc.stride, dc.m32, wide ? WIDE_TILE_BN : a.cfg32 >= 0 ? conv32_cfg_bn(a.cfg32) : 0);
   a.ldx = ldx; a.ldo = ldo;
   a.x_bstride = (long long)C_x * ldx;
   a.o_bstride = (long long)(dc.M * dc.groups / dc.up_np) * ldo;

@@ -385,6 +385,10 @@ int launch_conv(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_t 
     // wide taps (HuBERT positional conv k=128, 48 rows per group): 32x256 tile only
     if (span <= WIDE_TAP_SPAN && cfg == 5) return launch_t<2, 4, 1, 4, 1, WIDE_TAP_SPAN>(a, B, Lmax_out, stream);
     if (span <= WIDE_TAP_SPAN && cfg == 10) return launch_t<3, 4, 1, 4, 1, WIDE_TAP_SPAN>(a, B, Lmax_out, stream);
+    // spans up to RB_TAP_SPAN for any row count: the packed rows are a multiple of pick_bm(M), which the tile height divides
+    if (span <= RB_TAP_SPAN && a.groups == 1 && a.up == 1)
+      return pick_bm(a.M) == 16 ? launch_t<1, 4, 1, 4, 1, WIDE_TAP_SPAN>(a, B, Lmax_out, stream)
+                                : launch_t<2, 4, 1, 4, 1, WIDE_TAP_SPAN>(a, B, Lmax_out, stream);
     set_error("launch_conv: kernel %d x dilation %d unsupported for %d rows", a.KS, a.dil, a.M);
     return DISSC_EINVAL;
   }

@@ -416,7 +416,9 @@ int launch_conv32(const ConvArgs& a, int B, int Lmax_out, int stride, hipStream_
     return DISSC_EINVAL;
   }
   if (span > MAX_TAP_SPAN) {
-    if (span <= WIDE_TAP_SPAN && cfg == 3) return launch32_t<1, 2, 1, 4, 1, WIDE_TAP_SPAN>(a, B, Lmax_out, stream);
+    // (spans up to RB_TAP_SPAN take the same 32 x 256 instance for any row count: 32 rows divide every class's padded M)
+    if (span <= WIDE_TAP_SPAN && (cfg == 3 || (span <= RB_TAP_SPAN && a.groups == 1 && a.up == 1)))
+      return launch32_t<1, 2, 1, 4, 1, WIDE_TAP_SPAN>(a, B, Lmax_out, stream);
     set_error("launch_conv32: kernel %d x dilation %d unsupported for %d rows", a.KS, a.dil, a.M);
     return DISSC_EINVAL;
   }

@@ -208,6 +208,89 @@ int dissc_respair1d(const float* x, const float* w1_host, const float* b1_host, 
   return drained(rc, (hipStream_t)stream);
 }
 
+// Diagnostics / tests: ONE ResBlock2, y1 = x + conv_d0(lrelu(x)), y2 = y1 + conv_d1(lrelu(y1)), on device data with host weights
+// [C, C, k] and biases [C] packed per call: y (epi = EPI_RES) or acc (the MRF modes) = the block's output.  mode 0 = two direct
+// conv launches, y1 through scratch; mode 1 = the one-launch kernel (resblock2.hip), which refuses a shape without an instance
+// before anything is packed.  Synchronous.
+static int rb2_run(int mode, const DiagScope& d, const float* x, float* y1, float* y, const Batch& bt, const EpiSpec& ep, int C, int ld,
+                   float slope, hipStream_t st) {
+  if (mode == 1) return launch_resblock2(d.c1, d.c2, x, y, bt, ep, ld, slope, st);
+  if (int rc = run_conv(d.c1, x, y1, bt, epi_of(EPI_RES, x), C, ld, ld, slope, st)) return rc;
+  return run_conv(d.c2, y1, y, bt, epi_of(ep.epi, y1, ep.acc, ep.mrf_div), C, ld, ld, slope, st);
+}
+
+int dissc_resblock2_1d(const float* x, const float* w1_host, const float* b1_host, const float* w2_host, const float* b2_host, float* y,
+                       float* acc, const int32_t* lengths, int B, int C, int k, int d0, int d1, int ld, int Lmax, float slope, int epi,
+                       float mrf_div, int mode, void* stream) {
+  if (!x || !w1_host || !w2_host || !y || k % 2 != 1 || d0 < 1 || d1 < 1 || B <= 0 || C < 1 || epi < EPI_RES || epi > EPI_MRF_DIV ||
+      (epi != EPI_RES && !acc) || (mode != 0 && mode != 1) || (k - 1) * std::max(d0, d1) > RB_TAP_SPAN) {
+    set_error("dissc_resblock2_1d: bad argument (mode 0 = two launches, 1 = one launch; (k - 1) x dilation <= %d)", RB_TAP_SPAN);
+    return DISSC_EINVAL;
+  }
+  if (mode == 1 && !resblock2_supported(C, k, d0, d1)) {
+    set_error("dissc_resblock2_1d: no one-launch instance for C = %d, k = %d, dilations (%d, %d)", C, k, d0, d1);
+    return DISSC_EINVAL;
+  }
+  DiagScope ds;
+  float* y1 = nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  const Batch bt = batch_of(lengths, 1, B, Lmax);
+  int rc = make_conv(w1_host, b1_host, C, C, k, d0, ds.c1);
+  if (!rc) rc = make_conv(w2_host, b2_host, C, C, k, d1, ds.c2);
+  if (!rc && mode == 0 && ds.alloc(&y1, (size_t)B * C * ld) != hipSuccess) {
+    set_error("dissc_resblock2_1d: hipMalloc");
+    rc = DISSC_ENOMEM;
+  }
+  if (!rc) rc = rb2_run(mode, ds, x, y1, y, bt, epi_of(epi, nullptr, acc, mrf_div), C, ld, slope, st);
+  return drained(rc, st);
+}
+
+// Per-launch benchmark of one ResBlock2 in either form (dissc_resblock2_1d's modes) on B synthetic utterances of L columns:
+// dissc_pair_bench's method (two warm-up runs, then the average of `iters` runs between two events).  Synchronous.
+int dissc_resblock2_bench(int B, int C, int k, int d0, int d1, int L, int epi, int iters, int mode, float* ms_out) {
+  if (!ms_out || B <= 0 || L <= 0 || iters <= 0 || C < 1 || k % 2 != 1 || d0 < 1 || d1 < 1 || epi < EPI_RES || epi > EPI_MRF_DIV ||
+      (mode != 0 && mode != 1) || (k - 1) * std::max(d0, d1) > RB_TAP_SPAN || (mode == 1 && !resblock2_supported(C, k, d0, d1))) {
+    set_error("dissc_resblock2_bench: bad argument, or no one-launch instance for mode 1");
+    return DISSC_EINVAL;
+  }
+  std::vector<float> w1((size_t)C * C * k), w2((size_t)C * C * k), bias(C, 0.1f);
+  Lcg rnd;
+  rnd.fill(w1, 0.05f);
+  rnd.fill(w2, 0.05f);
+  DiagScope ds;
+  int rc = make_conv(w1.data(), bias.data(), C, C, k, d0, ds.c1);
+  if (!rc) rc = make_conv(w2.data(), bias.data(), C, C, k, d1, ds.c2);
+  if (rc) return rc;
+  const int ld = (L + 3) / 4 * 4;
+  const size_t n = (size_t)B * C * ld;
+  float *x = nullptr, *y = nullptr, *t = nullptr, *a = nullptr;
+  std::vector<float> hx(n);
+  rnd.fill(hx, 2.f);
+  if (ds.alloc(&x, n) != hipSuccess || ds.alloc(&y, n) != hipSuccess || ds.alloc(&t, n) != hipSuccess ||
+      ds.alloc(&a, n) != hipSuccess || hipMemcpy(x, hx.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(a, 0, n * 4) != hipSuccess || ds.events() != hipSuccess) {
+    set_error("dissc_resblock2_bench: allocation failed");
+    return DISSC_ENOMEM;
+  }
+  const Batch bt = batch_of(nullptr, 1, B, L);
+  const EpiSpec ep = epi_of(epi, nullptr, a, 3.f);
+  return time_launches(ds, iters, [&]() { return rb2_run(mode, ds, x, t, y, bt, ep, C, ld, 0.1f, nullptr); }, ms_out);
+}
+
+// Diagnostics: the form a (C; k; d0, d1) ResBlock2 takes in an fp32 generator handle created under the current option defaults
+// (0 = two direct conv launches, 1 = one launch) and, for the one-launch form, the outputs a workgroup owns (else 0); DISSC_EINVAL
+// for a block no handle takes.  Host only: no HIP call.
+int dissc_resblock2_info(int C, int k, int d0, int d1, int* form_out, int* tile_out) {
+  if (C < 1 || k < 1 || k % 2 != 1 || d0 < 1 || d1 < 1 || (k - 1) * std::max(d0, d1) > RB_TAP_SPAN) {
+    set_error("dissc_resblock2_info: C = %d, k = %d, dilations (%d, %d): k odd, (k - 1) x dilation within 0 .. %d", C, k, d0, d1, RB_TAP_SPAN);
+    return DISSC_EINVAL;
+  }
+  const int form = plan_resblock2(C, k, d0, d1, 0) == Rb2Form::fused ? 1 : 0;
+  if (form_out) *form_out = form;
+  if (tile_out) *tile_out = form ? resblock2_tile(k, d0, d1) : 0;
+  return DISSC_OK;
+}
+
 // Diagnostics / tests: ONE k = 3 ResBlock -- three residual pairs, dilations dil3 -- on device data with host weights [C,C,k] and
 // biases [C] in execution order (c1_0, c2_0, c1_1, c2_1, c1_2, c2_2): y (EPI_RES) or acc (the MRF modes) = the block's output.
 // mode 0 = three launches, each pair in the one-launch form the generator gives it without "chain_f23" (the register-only form

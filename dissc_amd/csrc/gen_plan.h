@@ -42,6 +42,12 @@ ChainPlan plan_chain(int C, int KS, const int* dil, int prec);
 double pair_macs(const PairPlan& p, int C, int KS, bool executed);  // multiply-adds per output position of one pair: algorithmic, or executed
 double chain_macs(const ChainPlan& cp, int C, int KS, bool executed);  // ... of a whole chain in its form
 int make_pair_conv(ConvForm f, const float* w, const float* b, int C, int KS, int dil, DevConv& dc);  // packed for its form
+// ---- a ResBlock2 chain (two dilated convs, x = x + conv_d(lrelu(x)) twice): decided once per handle like plan_chain ----
+enum class Rb2Form : uint8_t {
+  two_launch,  // two direct conv launches, x_1 through the chain's XK buffer, the second with the MRF epilogue
+  fused,       // one launch, x_1 in LDS (resblock2.hip)
+};
+Rb2Form plan_resblock2(int C, int KS, int d0, int d1, int prec);
 // The MRF epilogue of chain j's last launch: xs = r_0; xs += r_j; x = (xs + r_last) / nk
 inline int mrf_epi(int j, int nk) { return j == nk - 1 ? EPI_MRF_DIV : j == 0 ? EPI_MRF_SET : EPI_MRF_ADD; }
 

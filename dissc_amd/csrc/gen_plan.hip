@@ -144,6 +144,20 @@ ChainPlan plan_chain(int C, int KS, const int* dil, int prec) {
   return cp;
 }
 
+// option "rb2_fused" (default 59), a bit mask honoured only for fp32 handles: the ResBlock2 blocks of the 32-channel stage with
+//   k = 3 / 5 / 7 (bits 1 / 2 / 4) and of the 16-channel stage (bits 8 / 16 / 32) run as ONE launch each with x_1 in LDS
+//   (resblock2_32_kernel / resblock2_16_kernel; instances: HiFi-GAN V3's (3; 1, 2), (5; 2, 6), (7; 3, 12)), bit-identical to
+//   the two direct launches it replaces.  The mask holds the (C, k) whose one-launch form measured faster than its two launches
+//   by more than the spread between blocks of the same form (tools/resblock2_bench.py, B = 32 x 10 s, medians of seven alternated
+//   blocks, two launches -> one): C = 32: k = 3 584 -> 496 us, k = 5 709 -> 681, k = 7 877 -> 1 020 (it recomputes 72 of 256
+//   columns of the first conv: OFF); C = 16: k = 3 496 -> 313, k = 5 562 -> 404, k = 7 676 -> 570.  Forward of the V3-block VCTK
+//   model, 32 x 10 s: 14.23 ms all off, 13.80 all on.  profiles/resblock2.md.
+static int rb2_bit(int C, int KS) { return (KS == 3 ? 1 : KS == 5 ? 2 : KS == 7 ? 4 : 0) << (C == 16 ? 3 : 0); }
+Rb2Form plan_resblock2(int C, int KS, int d0, int d1, int prec) {
+  const bool fused = prec == 0 && (C == 16 || opts().use_mfma32) && resblock2_supported(C, KS, d0, d1) && (opts().rb2_fused & rb2_bit(C, KS));
+  return fused ? Rb2Form::fused : Rb2Form::two_launch;
+}
+
 double chain_macs(const ChainPlan& cp, int C, int KS, bool executed) {
   if (executed && cp.form == ChainForm::f23_chain) return 3 * 2 * 2.0 * C * C;  // F(2,3): 4 products per 2 outputs, six convs
   double macs = 0;

@@ -48,10 +48,13 @@ static hipStream_t shared_aux_stream(int chain, int prio) {
 struct dissc_gen {
   Options opt;  // this handle's snapshot of the tuning options (common.h): every entry point that works on the handle runs under it
   DisscGenConfig cfg;
+  int rb_type = 1;  // 1: ResBlock1, three (conv_d, conv_1) pairs per block (plan, rb1, rb2, pw, fused_*); 2: ResBlock2, two dilated
+                    // convs per block, rb1[stage*nk*3 + j*3 + m], m = 0, 1, run in the form plan2 gives
   int hop = 1;
   DevConv conv_pre;
   std::vector<std::vector<DevConv>> ups;  // per stage: one conv per phase group
   std::vector<ChainPlan> plan;     // [stage*nk + j]: the kernel forms of ResBlock j of the stage
+  std::vector<Rb2Form> plan2;      // ... of a ResBlock2 (rb_type 2)
   std::vector<DevConv> rb1, rb2;  // [stage*nk*3 + j*3 + m]: conv_d / conv_1 of pair m (forms direct, direct_dma, td, fused)
   std::vector<DevPairW> pw;       // same index: the pair as ONE transform-domain launch (form fused_td)
   std::vector<float*> fused_w, fused_b;  // [stage*nk + j]: 6 packed convs / biases of a split-bf16 ResBlock (bf3_* chains) or of a
@@ -110,6 +113,15 @@ int dissc_gen_create(const DisscGenConfig* cfg, const DisscTensor* weights, size
 
 int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, size_t n_weights, int precision,
                         dissc_gen_t* out) {
+  return dissc_gen_create_rb(cfg, weights, n_weights, precision, 1, out);
+}
+
+int dissc_gen_create_rb(const DisscGenConfig* cfg, const DisscTensor* weights, size_t n_weights, int precision, int resblock,
+                        dissc_gen_t* out) {
+  if (resblock != 1 && resblock != 2) {
+    set_error("dissc_gen_create_rb: resblock %d (use 1 = ResBlock1, 2 = ResBlock2)", resblock);
+    return DISSC_EINVAL;
+  }
   if (precision < -1 || precision > 1) {
     set_error("dissc_gen_create_ex: precision %d (use -1 = process option, 0 = fp32, 1 = split-bf16)", precision);
     return DISSC_EINVAL;
@@ -154,6 +166,7 @@ int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, s
   g->opt.precision = prec;
   OptScope opt_scope(&g->opt);
   g->cfg = *cfg;
+  g->rb_type = resblock;
   PrecScope prec_scope(prec);  // only the generator's layers may be packed for split-bf16
   int rc = DISSC_OK;
   const float *w = nullptr, *b = nullptr;
@@ -180,6 +193,7 @@ int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, s
   g->ups.resize(cfg->num_upsamples);
   const int nk = cfg->num_kernels;
   g->plan.resize((size_t)cfg->num_upsamples * nk);
+  g->plan2.assign((size_t)cfg->num_upsamples * nk, Rb2Form::two_launch);
   g->rb1.resize((size_t)cfg->num_upsamples * nk * 3);
   g->rb2.resize((size_t)cfg->num_upsamples * nk * 3);
   g->pw.resize((size_t)cfg->num_upsamples * nk * 3);
@@ -210,6 +224,23 @@ int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, s
       }
       const int* dl = cfg->resblock_dilations[j];
       const size_t cj = (size_t)i * nk + j;
+      if (resblock == 2) {  // each conv by make_conv's per-layer rule (fp32, or split-bf16 where that rule grants an instance)
+        for (int m = 0; m < 2; ++m) {
+          const int d = dl[m];
+          if (d < 1 || (rk - 1) * d > RB_TAP_SPAN) {
+            set_error("dissc_gen_create_rb: resblock_dilation_sizes[%d][%d] = %d with kernel size %d: (k - 1) x dilation must be in 0 .. %d",
+                      j, m, d, rk, RB_TAP_SPAN);
+            return fail(DISSC_EINVAL);
+          }
+          snprintf(name, sizeof(name), "resblocks.%d.convs.%d.weight", (int)cj, m);
+          if ((rc = get(name, {ch, ch, rk}, &w))) return fail(rc);
+          snprintf(name, sizeof(name), "resblocks.%d.convs.%d.bias", (int)cj, m);
+          if ((rc = get(name, {ch}, &b))) return fail(rc);
+          tasks.push_back([=]() { return make_conv(w, b, ch, ch, rk, d, g->rb1[cj * 3 + m]); });
+        }
+        g->plan2[cj] = plan_resblock2(ch, rk, dl[0], dl[1], prec);
+        continue;
+      }
       const ChainPlan& cp = g->plan[cj] = plan_chain(ch, rk, dl, prec);
       const float* w6[6];  // conv_d / conv_1 of the three pairs
       const float* b6[6];
@@ -306,8 +337,11 @@ static double gen_macs(const dissc_gen* g, bool executed) {
   for (int i = 0; i < g->cfg.num_upsamples; ++i) {
     for (auto& c : g->ups[i]) macs += c.macs_per_t * mul;
     mul = g->stage_mul[i];
-    for (int j = 0; j < nk; ++j)
-      macs += chain_macs(g->plan[(size_t)i * nk + j], g->stage_C[i], g->cfg.resblock_kernel_sizes[j], executed) * mul;
+    for (int j = 0; j < nk; ++j) {
+      const int C = g->stage_C[i], rk = g->cfg.resblock_kernel_sizes[j];
+      macs += (g->rb_type == 2 ? 2.0 * C * C * rk  // two direct convs: executed = algorithmic
+                               : chain_macs(g->plan[(size_t)i * nk + j], C, rk, executed)) * mul;
+    }
   }
   macs += (double)g->post_C * g->post_KS * mul;
   return macs;
@@ -465,6 +499,21 @@ static int gen_forward_body(dissc_gen_t g, const int64_t* code, const float* f0,
         if (multi && j > 0) DISSC_HIP_CHECK(hipStreamWaitEvent(sj, g->ev_fin[j - 1], 0));
         return DISSC_OK;
       };
+      if (g->rb_type == 2) {
+        // ResBlock2: x_1 = x + conv_d0(lrelu(x)) -> XK (a conv cannot run in place: its neighbours read the halo), then the
+        // block's output x_1 + conv_d1(lrelu(x_1)) goes straight into the MRF update
+        if (g->plan2[cj] == Rb2Form::fused) {  // the whole block in one launch, x_1 on the CU
+          if ((rc = acc_turn()) || (rc = launch_resblock2(g->rb1[cj * 3], g->rb1[cj * 3 + 1], X, nullptr, bt, mrf, ld, 0.1f, sj))) return rc;
+          if (multi) DISSC_HIP_CHECK(hipEventRecord(g->ev_fin[j], sj));
+          continue;
+        }
+        if ((rc = run_conv(g->rb1[cj * 3], X, XKc, bt, epi_of(EPI_RES, X), ch, ld, ld, 0.1f, sj))) return rc;
+        if ((rc = acc_turn()) ||
+            (rc = run_conv(g->rb1[cj * 3 + 1], XKc, TMPc, bt, epi_of(mrf.epi, XKc, ACC, (float)nk), ch, ld, ld, 0.1f, sj)))
+          return rc;
+        if (multi) DISSC_HIP_CHECK(hipEventRecord(g->ev_fin[j], sj));
+        continue;
+      }
       if (cp.form == ChainForm::bf3_block) {  // the whole ResBlock in one launch
         if ((rc = acc_turn()) || (rc = launch_resblock_bf3(bf3, X, bt, mrf, ld, 0.1f, 0, 3, sj))) return rc;
         if (multi) DISSC_HIP_CHECK(hipEventRecord(g->ev_fin[j], sj));

@@ -32,6 +32,43 @@ def fold_weight_norm(weight_g, weight_v):
     return torch._weight_norm(weight_v, weight_g, 0)
 
 
+def resblock_type(h):
+    """1 or 2 from the config's "resblock" key, read as the reference reads it (sr/models.py:80: '1' is ResBlock1, anything
+    else ResBlock2)"""
+    return 1 if str(h.get("resblock", "1")) == "1" else 2
+
+
+def resblock_conv_names(resblock, n):
+    """the conv layers of block n in the reference's parameter order: ResBlock1 convs1.0-2 then convs2.0-2, ResBlock2
+    convs.0-1 (reference sr/models.py:17-32, :50-58)"""
+    if resblock == 1:
+        return [f"resblocks.{n}.{grp}.{m}" for grp in ("convs1", "convs2") for m in range(3)]
+    return [f"resblocks.{n}.convs.{m}" for m in range(2)]
+
+
+RB2_TAP_SPAN = 72  # RB_TAP_SPAN (csrc/common.h): the widest (k - 1) * dilation of a ResBlock2 conv, HiFi-GAN V3's k = 7, d = 12
+
+
+def resblock_dilations(resblock, ds, k=None):
+    """the dilations one block reads from its resblock_dilation_sizes entry: ResBlock1 all three, ResBlock2 the first two (as
+    in the reference, further entries are ignored).  With its kernel size k, a ResBlock2 entry the kernels cannot run is
+    refused by the name of its config key."""
+    if resblock == 1:
+        if len(ds) != 3:
+            raise NotImplementedError("ResBlock1 needs 3 dilations per kernel size")
+        return [int(d) for d in ds]
+    if len(ds) < 2:
+        raise NotImplementedError(f"ResBlock2 needs 2 dilations per kernel size: resblock_dilation_sizes entry {list(ds)}")
+    ds = [int(d) for d in ds[:2]]
+    if k is not None:
+        if int(k) < 1 or int(k) % 2 != 1:
+            raise NotImplementedError(f"resblock_kernel_sizes: kernel size {k} (ResBlock2 needs an odd one)")
+        if min(ds) < 1 or (int(k) - 1) * max(ds) > RB2_TAP_SPAN:
+            raise NotImplementedError(f"resblock_dilation_sizes entry {ds} with kernel size {k}: (k - 1) * dilation must be "
+                                      f"within 0 .. {RB2_TAP_SPAN}")
+    return ds
+
+
 class CodeGenerator:
     """HiFi-GAN generator conditioned on units + F0 + speaker, on one MI355X."""
 
@@ -52,8 +89,10 @@ class CodeGenerator:
                 # VQ-VAE branches (reference sr/models.py:137-156) are not part of the
                 # shipped DISSC configs.
                 raise NotImplementedError(f"config option '{k}' (VQ-VAE branch) is not supported")
-        if str(self.h.get("resblock", "1")) != "1":
-            raise NotImplementedError("only resblock type '1' is supported")
+        self.resblock = resblock_type(self.h)
+        if self.resblock == 2:
+            for k, ds in zip(self.h.resblock_kernel_sizes, self.h.resblock_dilation_sizes):
+                resblock_dilations(2, ds, k)
         self.num_kernels = len(self.h.resblock_kernel_sizes)
         self.num_upsamples = len(self.h.upsample_rates)
         self.f0 = self.h.get("f0", None)
@@ -122,8 +161,7 @@ class CodeGenerator:
     def _conv_names(self):
         names = ["conv_pre"] + [f"ups.{i}" for i in range(self.num_upsamples)]
         for i in range(self.num_upsamples * self.num_kernels):
-            for grp in ("convs1", "convs2"):
-                names += [f"resblocks.{i}.{grp}.{m}" for m in range(3)]
+            names += resblock_conv_names(self.resblock, i)
         return names + ["conv_post"]
 
     # -- native handle ----------------------------------------------------------------
@@ -139,9 +177,7 @@ class CodeGenerator:
         c.num_kernels = self.num_kernels
         for j, (k, ds) in enumerate(zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes)):
             c.resblock_kernel_sizes[j] = int(k)
-            if len(ds) != 3:
-                raise NotImplementedError("ResBlock1 needs 3 dilations per kernel size")
-            for m, d in enumerate(ds):
+            for m, d in enumerate(resblock_dilations(self.resblock, ds)):
                 c.resblock_dilations[j][m] = int(d)
         c.num_embeddings = int(h.num_embeddings)
         c.embedding_dim = int(h.embedding_dim)
@@ -169,8 +205,8 @@ class CodeGenerator:
             hnd = ctypes.c_void_p()
             # the handle's arithmetic is an argument of its constructor: no process-wide state is touched
             prec = -1 if self.precision is None else self._PRECISIONS[self.precision]
-            check(lib.dissc_gen_create_ex(ctypes.byref(cfg), table, len(keep), prec, ctypes.byref(hnd)),
-                  "dissc_gen_create_ex")
+            check(lib.dissc_gen_create_rb(ctypes.byref(cfg), table, len(keep), prec, self.resblock, ctypes.byref(hnd)),
+                  "dissc_gen_create_rb")
             self._handle = hnd
             self.hop = lib.dissc_gen_hop(hnd)
 

@@ -5,6 +5,7 @@
 
     y = nn.conv1d(x, weight, bias, lengths=lengths, dilation=d, in_slope=0.1, add=res)   # a torch.autograd.Function
     y = nn.resblock1(x, weights, k)                                                       # reference sr/models.py:34-41
+    y = nn.resblock2(x, weights, k, (d0, d1))                                             # reference sr/models.py:50-63
     y = nn.conv_transpose1d(x, weight, bias, stride=u, lengths=lengths, in_slope=0.1)     # the upsamplers ups[i]
     y = nn.conv1d_strided(x, weight, bias, stride=3, lengths=lengths, in_slope=0.1)       # the period discriminator's layers
     score, fmaps, lens = nn.discriminator_p(wav, weights, period, lengths)                # reference sr/models.py:228-260
@@ -48,11 +49,12 @@ class _Kind:
     nout(p, ld) of a row of ld inputs as a function of the layer's own parameter p (dilation or stride), and the names its
     messages use"""
 
-    def __init__(self, who, prefix, layout, dims, nout, fwd_args, grouped=False):
+    def __init__(self, who, prefix, layout, dims, nout, fwd_args, grouped=False, create="create"):
         vp, i32, sz, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
         self.who, self.prefix, self.layout, self.dims, self.nout = who, prefix, layout, dims, nout
         self.grouped = grouped  # one more create parameter, groups: dims() then reads Cin / groups from the weight
         self.names = {e: f"{prefix}_{e}" for e in _ENTRIES}
+        self.names["create"] = f"{prefix}_{create}"
         for e, name in self.names.items():
             setattr(self, e, getattr(lib, name))
         self.create.argtypes = [i32] * (5 if grouped else 4) + [ctypes.POINTER(vp)]
@@ -70,7 +72,8 @@ class _Kind:
 
 # weight [Cout, Cin, k], p = dilation, forward(h, x, add, ...)  /  weight [Cin, Cout, k], p = stride, forward(h, x, ...)  /
 # weight [Cout, Cin, k], p = stride, forward(h, x, ...)  /  weight [Cout, Cin / groups, k], p = stride, groups, forward(h, x, ...)
-CONV1D = _Kind("nn.conv1d", "dissc_convgrad", "[Cout, {}, k]", lambda s: (s[1], s[0], s[2]), lambda p, ld: ld, [ctypes.c_void_p] * 3)
+CONV1D = _Kind("nn.conv1d", "dissc_convgrad", "[Cout, {}, k]", lambda s: (s[1], s[0], s[2]), lambda p, ld: ld, [ctypes.c_void_p] * 3,
+               create="create_wide")  # (k - 1) * dilation up to 72
 CONV_TRANSPOSE1D = _Kind("nn.conv_transpose1d", "dissc_convtgrad", "[{}, Cout, k]", lambda s: (s[0], s[1], s[2]),
                          lambda p, ld: p * ld, [ctypes.c_void_p] * 2)
 CONV1D_STRIDED = _Kind("nn.conv1d_strided", "dissc_convsgrad", "[Cout, {}, k]", lambda s: (s[1], s[0], s[2]),
@@ -254,7 +257,7 @@ def conv1d(x, weight, bias=None, lengths=None, dilation=1, in_slope=1.0, add=Non
     """y = bias + conv(lrelu(x, in_slope), weight, dilation, padding "same") (+ add).
 
     x [B, Cin, ld], add / y [B, Cout, ld]: contiguous fp32 device tensors, ld % 4 == 0.  weight: DEVICE tensor
-    [Cout, Cin, k], k odd, k <= 11, (k - 1) * dilation <= 60; bias [Cout] or None.  lengths: int32 [B] on the device (or
+    [Cout, Cin, k], k odd, k <= 11, (k - 1) * dilation <= 72; bias [Cout] or None.  lengths: int32 [B] on the device (or
     None = ld): positions at and beyond lengths[b] are read as zero and left zero in y.  Gradients flow to x, weight,
     bias and add (the gradient of add is the incoming gradient itself, handed through unmasked: the cotangent of a position
     beyond lengths[b], which the forward never writes, is the caller's to keep zero); x and weight are saved, y is not."""
@@ -353,6 +356,20 @@ def resblock1(x, weights, k, dilations=(1, 3, 5), lengths=None, taps=None):
         if taps is not None:
             taps.append(xt)
         x = conv1d(xt, weights[f"convs2.{m}.weight"], weights.get(f"convs2.{m}.bias"), lengths=lengths, dilation=1,
+                   in_slope=LRELU_SLOPE, add=x)
+    return x
+
+
+def resblock2(x, weights, k, dilations=(1, 3), lengths=None, taps=None):
+    """ResBlock2 (reference sr/models.py:50-63, the light block of HiFi-GAN V3): for each of the two dilations d,
+    x = x + conv_d(lrelu(x)), composed from two conv1d calls with the residual through ``add=``.  weights:
+    {"convs.<m>.weight" / ".bias"} (device tensors, weight norm already folded).  taps: as in resblock1."""
+    if len(dilations) != 2:
+        raise DisscError(f"nn.resblock2: {len(dilations)} dilations (ResBlock2 has two convs)")
+    for m, d in enumerate(dilations):
+        if taps is not None:
+            taps.append(x)
+        x = conv1d(x, weights[f"convs.{m}.weight"], weights.get(f"convs.{m}.bias"), lengths=lengths, dilation=d,
                    in_slope=LRELU_SLOPE, add=x)
     return x
 
@@ -873,13 +890,12 @@ class CodeGenerator:
     N_SPEAKERS = 200  # nn.Embedding(200, ...), reference sr/models.py:133
 
     def __init__(self, h):
-        from .generator import AttrDict
+        from .generator import AttrDict, resblock_conv_names, resblock_dilations, resblock_type
         self.h = AttrDict(h)
         for k in self._UNSUPPORTED:
             if self.h.get(k, None):
                 raise NotImplementedError(f"config option '{k}' (VQ-VAE branch) is not supported")
-        if str(self.h.get("resblock", "1")) != "1":
-            raise NotImplementedError("only resblock type '1' is supported")
+        self.resblock = resblock_type(self.h)
         h = self.h
         self.num_kernels, self.num_upsamples = len(h.resblock_kernel_sizes), len(h.upsample_rates)
         if not 1 <= self.num_kernels <= 4:
@@ -899,10 +915,8 @@ class CodeGenerator:
         for i in range(self.num_upsamples):
             ch = c0 >> (i + 1)
             for j, (k, ds) in enumerate(zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes)):
-                if len(ds) != 3:
-                    raise NotImplementedError("ResBlock1 needs 3 dilations per kernel size")
-                for grp in ("convs1", "convs2"):
-                    L += [(f"resblocks.{i * self.num_kernels + j}.{grp}.{m}", (ch, ch, int(k)), ch) for m in range(3)]
+                resblock_dilations(self.resblock, ds, k if self.resblock == 2 else None)  # (refuses what cannot run, by its key)
+                L += [(name, (ch, ch, int(k)), ch) for name in resblock_conv_names(self.resblock, i * self.num_kernels + j)]
         L.append(("conv_post", (1, c0 >> self.num_upsamples, 7), 1))
         self.layers = L
         self._index = {name: i for i, (name, _, _) in enumerate(L)}
@@ -1025,8 +1039,8 @@ class CodeGenerator:
         """code [B, T] ids, f0 [B, 1, T'] or [B, T'] (with "f0" in the config), spkr [B, 1] (with "multispkr"), lengths [B]
         valid frames (default T) -> wav [B, 1, hop T] with a grad_fn, zero beyond hop lengths[b].  The shorter of the code and
         f0 streams is repeated up to the longer one, as in the reference.  taps: a list that receives every conv's input in
-        call order (conv_pre's, then per stage the upsampler's and its ResBlocks' as nn.resblock1 gives them, conv_post's)."""
-        from .generator import CodeGenerator as _Inference
+        call order (conv_pre's, then per stage the upsampler's and its ResBlocks' as nn.resblock1 / nn.resblock2 give them, conv_post's)."""
+        from .generator import CodeGenerator as _Inference, resblock_conv_names, resblock_dilations
         self._loaded()
         if extra:
             raise NotImplementedError(f"extra conditioning features {sorted(extra)} are not supported")
@@ -1090,10 +1104,10 @@ class CodeGenerator:
             for j, (k, ds) in enumerate(zip(self.h.resblock_kernel_sizes, self.h.resblock_dilation_sizes)):
                 pre = f"resblocks.{i * nk + j}."
                 wts = {}
-                for grp in ("convs1", "convs2"):
-                    for mm in range(3):
-                        wts[f"{grp}.{mm}.weight"], wts[f"{grp}.{mm}.bias"] = W(f"{pre}{grp}.{mm}")
-                rs.append(resblock1(x, wts, int(k), tuple(int(d) for d in ds), lengths=lens[i + 1], taps=taps))
+                for name in resblock_conv_names(self.resblock, i * nk + j):
+                    wts[name[len(pre):] + ".weight"], wts[name[len(pre):] + ".bias"] = W(name)
+                block = resblock1 if self.resblock == 1 else resblock2
+                rs.append(block(x, wts, int(k), tuple(resblock_dilations(self.resblock, ds)), lengths=lens[i + 1], taps=taps))
             x = mrf_mean(rs, lens[i + 1])
         x = conv1d(tap(x), *W("conv_post"), lengths=lens[-1], in_slope=POST_SLOPE)
         return tanh(x, lens[-1], self.hop * T)

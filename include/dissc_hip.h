@@ -50,7 +50,9 @@ const char* dissc_last_error(void);
 /* ABI version of this header: bumped when a signature changes or a section is added (5: dissc_convgrad_*;
  * 6: dissc_conv_info, and dissc_get_option reads the tile-shape keys; 7: dissc_wino8_info; 8: the split-bf16 diagnostics
  * dissc_conv1d_prec, dissc_conv_transpose1d_prec, dissc_resblock1d_bf3, dissc_bf3_info and mode 5 of dissc_respair1d;
- * 9: dissc_wino_info). */
+ * 9: dissc_wino_info).  ADDED since, without a bump (no signature changed; a binding that needs one checks for the symbol):
+ * dissc_gen_create_rb (the generator with ResBlock2 blocks), dissc_resblock2_1d, dissc_resblock2_info, dissc_convgrad_create_wide
+ * (tap spans up to 72). */
 int dissc_abi_version(void);
 /* Number of HIP devices visible / name of device `dev` (for diagnostics). */
 int dissc_device_count(void);
@@ -92,6 +94,14 @@ int dissc_gen_create(const DisscGenConfig* cfg, const DisscTensor* weights, size
 /* the same with the handle's arithmetic given explicitly instead of read from the process-wide "precision" option:
  * -1 = that option, 0 = exact fp32, 1 = split-bf16 (opt-in, see dissc_set_option) */
 int dissc_gen_create_ex(const DisscGenConfig* cfg, const DisscTensor* weights, size_t n_weights, int precision,
+                        dissc_gen_t* out);
+/* the same with the residual block type of the config's "resblock" key (reference sr/models.py:80): 1 = ResBlock1, what the two
+ * entries above build; 2 = ResBlock2 (HiFi-GAN V3): block n has TWO convs, "resblocks.{n}.convs.{m}.weight/.bias", m = 0, 1, and
+ * computes  for m: x = x + conv_{d_m}(lrelu(x, 0.1))  with d_m = resblock_dilations[j][m] (the third entry is not read), then
+ * the stage's MRF mean in the reference's order.  Each block runs as two direct conv launches, x_k through the chain's
+ * buffers, the second carrying the MRF epilogue, on the chain's side stream; (k - 1) d_m <= 72.  precision 1: every conv follows
+ * the per-layer rule of the other layers (split-bf16 where >= 32 rows and (k - 1) d_m <= 60 grant an instance, fp32 elsewhere). */
+int dissc_gen_create_rb(const DisscGenConfig* cfg, const DisscTensor* weights, size_t n_weights, int precision, int resblock,
                         dissc_gen_t* out);
 void dissc_gen_destroy(dissc_gen_t g);
 /* samples produced per input frame (= prod(upsample_rates) = 320) */
@@ -217,6 +227,11 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *                        reschain16_f23_kernel in respair16_f23.hip: x_1, x_2 and the residuals stay on the CU, 2 C^2
  *                        products per output and conv instead of 3 C^2); 0 = three one-launch pairs.  Not bit-identical to
  *                        them.  A chain-level choice: dissc_pair_info does not see it
+ *   rb2_fused (59)       read at dissc_gen_create_rb, a bit mask honoured only for fp32 handles: the ResBlock2 blocks of the 32-channel
+ *                        stage with k = 3 / 5 / 7 (bits 1 / 2 / 4) and of the 16-channel stage (bits 8 / 16 / 32) run as ONE launch each
+ *                        (csrc/resblock2.hip: x_1 in LDS; instances (k; d0, d1) = (3; 1, 2), (5; 2, 6), (7; 3, 12)) instead of two
+ *                        direct conv launches; same bits either way.  Default: every shape but C = 32, k = 7, where the one launch measured
+ *                        16 % slower (profiles/resblock2.md).  dissc_resblock2_info reports the form
  *   pair_dma (1)         read at dissc_gen_create: the two-launch direct residual pairs of the >= 32-channel stages hand their
  *                        intermediate over activated with zero tails, and the second conv stages its windows by LDS-DMA
  *   wino8 (1)            read at dissc_gen_create: 1 = the ResBlock convs selected by wino8_mask run on conv_wino8.hip's
@@ -289,6 +304,18 @@ int dissc_pair_bench(int B, int C, int k, int dilation, int L, int epi, int iter
  * outputs one workgroup of that instance owns (0 for form 0).  DISSC_EINVAL where mode 3 has no instance.  Host only: no GPU
  * is touched. */
 int dissc_pair_info(int C, int k, int dilation, int* form_out, int* tile_out);
+/* ONE ResBlock2 (y1 = x + conv_d0(lrelu(x)), y2 = y1 + conv_d1(lrelu(y1)); reference sr/models.py:50-65) on device data x [B][C][ld]
+ * with host weights [C][C][k] and biases [C], packed per call: epi 1 writes y2 to y, epi 2 / 3 / 4 (the MRF modes) update acc.
+ * mode 0 = two direct conv launches, mode 1 = the one-launch kernel (csrc/resblock2.hip; C = 32 / 16 and (k; d0, d1) = (3; 1, 2),
+ * (5; 2, 6), (7; 3, 12): DISSC_EINVAL for any other shape); the two are bit-identical.  Tests / diagnostics; synchronous. */
+int dissc_resblock2_1d(const float* x, const float* w1_host, const float* b1_host, const float* w2_host, const float* b2_host, float* y,
+                       float* acc, const int32_t* lengths, int B, int C, int k, int d0, int d1, int ld, int Lmax, float slope, int epi,
+                       float mrf_div, int mode, void* stream);
+/* per-launch time (ms, the average of `iters` runs after two warm-up runs) of one ResBlock2 in mode 0 / 1 on B synthetic utterances of L columns */
+int dissc_resblock2_bench(int B, int C, int k, int d0, int d1, int L, int epi, int iters, int mode, float* ms_out);
+/* HOST ONLY: the form a (C; k; d0, d1) ResBlock2 takes in an fp32 generator handle created under the current options -- 0 = two direct
+ * conv launches, 1 = one launch (option rb2_fused) -- and the outputs one workgroup of the one-launch form owns (0 for form 0). */
+int dissc_resblock2_info(int C, int k, int d0, int d1, int* form_out, int* tile_out);
 /* The launches dissc_conv1d (up = 1: Cin -> Cout, k taps, `dilation`) or dissc_conv_transpose1d (up > 1: k taps, stride `up`,
  * dilation 1) makes on a batch of B utterances of at most Lmax_out columns per launch (for a ConvTranspose: INPUT columns), under
  * the current option defaults: one for a conv, one per group of output phases for a ConvTranspose.  Per launch: the kernel
@@ -786,6 +813,10 @@ int dissc_mel_l1_grad(dissc_mel_t h, const float* a, int lda, const float* b, in
 #define DISSC_CONVGRAD_CHUNK 64
 typedef struct dissc_convgrad* dissc_convgrad_t;
 int dissc_convgrad_create(int Cin, int Cout, int k, int dilation, dissc_convgrad_t* out);
+/* the same handle with (k - 1) dilation <= 72 admitted (ResBlock2 of HiFi-GAN V3: k = 7, dilation 12): spans above 60 run the
+ * forward and the data gradient on the wide-span conv instances (256-column tiles for any row count) and the weight gradient on
+ * instances with a 36-column halo; every span <= 60 runs what dissc_convgrad_create's handle runs.  What nn.conv1d creates. */
+int dissc_convgrad_create_wide(int Cin, int Cout, int k, int dilation, dissc_convgrad_t* out);
 void dissc_convgrad_destroy(dissc_convgrad_t h);
 int dissc_convgrad_set_weights(dissc_convgrad_t h, const float* w_dev, const float* bias_dev, void* stream);
 int dissc_convgrad_forward(dissc_convgrad_t h, const float* x, const float* add, float* y, const int32_t* lengths, int B,
