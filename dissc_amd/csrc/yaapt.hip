@@ -13,8 +13,8 @@
 //                  analytically), then the candidate peak logic, one thread per frame
 //   nccf + peaks   normalised cross-correlation of every frame inside its own lag range (set by the spectral
 //                  track), then the candidate logic (cmp_rate), one workgroup per frame
-// The short sequential stages (median smoothing, the two dynamic-programming passes, interpolation) stay on
-// the host (dissc_amd/f0.py).
+// The short sequential stages (median smoothing, the two dynamic-programming passes, interpolation) are the two
+// one-workgroup-per-utterance kernels of yaapt_dp.hip; dissc_amd/f0.py keeps their numpy form for the tests.
 #include <math.h>
 
 #include "common.h"

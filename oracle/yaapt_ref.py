@@ -367,13 +367,17 @@ def dynamic(ref_pitch, ref_merit, energy, p=PARAMS):
 
 
 def yaapt(signal, fs=16000, p=PARAMS):
-    """float waveform -> per-frame F0 (Hz, 0 = unvoiced), one value per frame_space (pYAAPT samp_values)"""
+    """float waveform -> per-frame F0 (Hz, 0 = unvoiced), one value per frame_space (pYAAPT samp_values).
+    A signal with spectral frames but shorter than one time-domain frame gives an all-unvoiced track
+    [3P-unverified: what pYAAPT does there is unknown; the device stages return zeros, and so does this]."""
     x = np.asarray(signal, dtype=np.float64)
     filt = bandpass(x, fs, p)
     nl_filt = bandpass(x * x, fs, p)
     energy, vuv = nlfer(filt, fs, p)
     if len(energy) == 0:
         return np.zeros(0)
+    if tda_geometry(len(x), fs, len(energy), p)[2] <= 0:
+        return np.zeros(len(energy))
     spec_pitch, pitch_std, _ = spec_track(nl_filt, fs, vuv, p)
     tp1, tm1 = time_track(filt, fs, spec_pitch, pitch_std, p)
     tp2, tm2 = time_track(nl_filt, fs, spec_pitch, pitch_std, p)

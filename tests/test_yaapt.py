@@ -22,6 +22,7 @@ def test_oracle_pulse_train_and_voicing_decisions():
     f0 = yr.get_yaapt_f0(pulse_train(140.0, 24000))
     check_track(f0, np.full(24000, 140.0))
     assert not yr.get_yaapt_f0(np.zeros(24000)).any()                         # silence
+    assert [yr.get_yaapt_f0(voiced(np.full(n, 150.0))).tolist() for n in (1, 79)] == [[0.0], [0.0]]  # no time-domain frame
     noise = 0.1 * np.random.RandomState(0).standard_normal(24000)
     assert (yr.get_yaapt_f0(noise) > 0).mean() <= 0.1                        # white noise: (almost) all unvoiced
     x = np.concatenate([voiced(np.full(8000, 150.0)), 0.002 * np.random.RandomState(1).standard_normal(8000),
