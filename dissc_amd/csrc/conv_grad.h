@@ -50,6 +50,29 @@ inline CtTaps ct_taps(int k, int s, int pad) {
   return t;
 }
 
+// one launch of the stride-1 weight gradient (conv_grad.hip's fp32 kernel, conv_grad_bf3.hip's split-bf16 one)
+struct WgradArgs {
+  const float* gy;   // [B][Cout][ldo]
+  const float* x;    // [B][Cin][ldx], before the activation
+  const int32_t* lengths;
+  float* part;       // [P * WT][Cout][Cin][K]
+  int B, Cout, Cin, K, Lmax, ldo, ldx;
+  int off0, dstep;   // tap j reads x[t + off0 + j * dstep]
+  int halo;          // LDS window = [t0 - halo, t0 + CG_T + halo), halo % 4 == 0, >= every |tap offset|
+  float slope;
+  int WCI, WT, CIB, TS, nch, cpp;
+};
+
+// The split-bf16 weight gradient (conv_grad_bf3.hip).  cg_wgrad_bf3_takes: whether a handle of precision `prec` runs its weight
+// gradient there -- what dissc_convgrad_backward dispatches on and dissc_convgrad_precision_info reports.  The launch takes the
+// fp32 kernel's arguments and plan (same chunks, same partials, same partial layout) and rounds a.halo up itself.
+bool cg_wgrad_bf3_takes(int prec, int Cin, int Cout, int K, int dil);
+int cg_launch_wgrad_bf3(const WgradArgs& a, const CgPlan& p, hipStream_t st);
+// master weights [Cout][Cin][K] -> conv_bf3_kernel's A fragments (pack_conv_weights_bf3's order) of a layer of nsub 32-row
+// tiles; transposed: the data gradient's conv (rows = input channels, taps flipped)
+void cg_launch_repack_bf3(const float* w, int Cout, int Cin, int K, int nsub, int nchunk, int transposed, float* packed,
+                          hipStream_t st);
+
 // out[i] = sum over the NP partials part[p][i], i < n, in a fixed order
 void cg_launch_reduce(const float* part, int NP, size_t n, float* out, hipStream_t st);
 // gb[co] = sum_b sum_{t < min(ceil(lengths[b] * len_mul / len_div), Lmax)} gy[b][co][t], in double; bpart: B * Cout doubles of
@@ -94,7 +117,7 @@ int cg_dispatch_ng(int NG, const char* who, const char* unit, F&& launch) {
 }
 
 // set_weights' allocation of one direct conv: the zeros uploaded are the packing's padding (weights never leave the device); a
-// packing the device-side repack does not write is refused
-int cg_alloc_conv(const char* who, int rows, int cols, int taps, int dil, int pad_left, DevConv& dc);
+// packing the device-side repack does not write is refused (prec = 1: conv_bf3_kernel's split-bf16 fragments are admitted)
+int cg_alloc_conv(const char* who, int rows, int cols, int taps, int dil, int pad_left, DevConv& dc, int prec = 0);
 
 }  // namespace dissc

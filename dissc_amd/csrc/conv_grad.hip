@@ -21,6 +21,9 @@
 //   * Tap offsets are off_j = off0 + j dstep with |off_j| <= 32: nothing ties them to (k - 1) d / 2.  A ConvTranspose1d's
 //     weight gradient (a stride-1 correlation of x with the phase planes of gy) is conv_grad_t.hip's kernel: this one with a
 //     (plane, shift) per tap; it shares the plan, the reduction and the bias kernels below through conv_grad.h.
+// A handle of dissc_convgrad_create_prec(prec = 1) runs each direction that has an instance in split-bf16 arithmetic instead:
+// forward and backward-data on conv_bf3_kernel, the weight gradient on conv_grad_bf3.hip's kernel, both packings written by its
+// repack kernel; every other direction, and every prec = 0 handle, runs exactly what is described above.
 // The host side the two layers have in common is defined here too (conv_grad.h: CgLayer, the argument checks, the workspace
 // layout with the preamble that carves it, cg_alloc_conv).
 #include <string.h>
@@ -60,18 +63,6 @@ CgPlan cg_plan(int Cin, int Cout, int K, int B, int Lmax) {
   p.P = (int)((N + p.cpp - 1) / p.cpp);  // no empty partial
   return p;
 }
-
-struct WgradArgs {
-  const float* gy;   // [B][Cout][ldo]
-  const float* x;    // [B][Cin][ldx], before the activation
-  const int32_t* lengths;
-  float* part;       // [P * WT][Cout][Cin][K]
-  int B, Cout, Cin, K, Lmax, ldo, ldx;
-  int off0, dstep;   // tap j reads x[t + off0 + j * dstep]
-  int halo;          // LDS window = [t0 - halo, t0 + CG_T + halo), halo % 4 == 0, >= every |tap offset|
-  float slope;
-  int WCI, WT, CIB, TS, nch, cpp;
-};
 
 template <int NG, int HALO = CG_HALO>
 __global__ void __launch_bounds__(256, 2) convgrad_wgrad_kernel(WgradArgs a) {
@@ -359,10 +350,11 @@ int cg_backward_begin(const char* who, const CgPlan& p, int B, int Cout, const f
   return DISSC_OK;
 }
 
-int cg_alloc_conv(const char* who, int rows, int cols, int taps, int dil, int pad_left, DevConv& dc) {
+int cg_alloc_conv(const char* who, int rows, int cols, int taps, int dil, int pad_left, DevConv& dc, int prec) {
   std::vector<float> zeros((size_t)rows * cols * taps, 0.f);
+  PrecScope prec_scope(prec);  // 1: the split-bf16 packing where conv_geometry gives the layer one
   if (int rc = make_conv(zeros.data(), nullptr, rows, cols, taps, dil, dc, 1, 1, pad_left)) return rc;
-  if (dc.prec || dc.wino || dc.wpack2) {
+  if (dc.prec > prec || dc.wino || dc.wpack2) {
     set_error("%s: unexpected conv packing", who);
     return DISSC_EINVAL;
   }
@@ -375,6 +367,7 @@ using namespace dissc;
 
 struct dissc_convgrad : CgLayer {
   int dil = 1;
+  int prec = 0;  // 1: split-bf16 in every direction that has an instance (dissc_convgrad_create_prec)
   DevConv fwd, bwd;
   ~dissc_convgrad() {
     free_conv(fwd);
@@ -412,6 +405,35 @@ int dissc_convgrad_create_wide(int Cin, int Cout, int k, int dilation, dissc_con
   return convgrad_create("dissc_convgrad_create_wide", RB_TAP_SPAN, Cin, Cout, k, dilation, out);
 }
 
+int dissc_convgrad_create_prec(int Cin, int Cout, int k, int dilation, int prec, dissc_convgrad_t* out) {
+  if (prec != 0 && prec != 1) {
+    if (out) *out = nullptr;
+    set_error("dissc_convgrad_create_prec: prec %d (0 = fp32, 1 = split-bf16)", prec);
+    return DISSC_EINVAL;
+  }
+  if (int rc = convgrad_create("dissc_convgrad_create_prec", RB_TAP_SPAN, Cin, Cout, k, dilation, out)) return rc;
+  (*out)->prec = prec;
+  return DISSC_OK;
+}
+
+// forward and data gradient: conv_geometry under the handle's precision, the function make_conv packs by and run_conv launches
+// by; weight gradient: the test dissc_convgrad_backward dispatches on
+int dissc_convgrad_precision_info(dissc_convgrad_t h, int32_t split[3]) {
+  if (!h || !split) {
+    set_error("dissc_convgrad_precision_info: bad argument");
+    return DISSC_EINVAL;
+  }
+  OptScope opt_scope(&h->opt);
+  PrecScope prec_scope(h->prec);
+  DevConv f, b;
+  conv_geometry(f, h->Cout, h->Cin, h->k, h->dil, 1, 1, -1);
+  conv_geometry(b, h->Cin, h->Cout, h->k, h->dil, 1, 1, -1);
+  split[0] = f.prec == 1;
+  split[1] = b.prec == 1;
+  split[2] = cg_wgrad_bf3_takes(h->prec, h->Cin, h->Cout, h->k, h->dil);
+  return DISSC_OK;
+}
+
 void dissc_convgrad_destroy(dissc_convgrad_t h) { delete h; }
 
 int dissc_convgrad_set_weights(dissc_convgrad_t h, const float* w_dev, const float* bias_dev, void* stream) {
@@ -423,12 +445,16 @@ int dissc_convgrad_set_weights(dissc_convgrad_t h, const float* w_dev, const flo
   hipStream_t st = (hipStream_t)stream;
   int rc;
   if (!h->ready) {
-    if ((rc = cg_alloc_conv("dissc_convgrad_set_weights", h->Cout, h->Cin, h->k, h->dil, -1, h->fwd))) return rc;
-    if ((rc = cg_alloc_conv("dissc_convgrad_set_weights", h->Cin, h->Cout, h->k, h->dil, -1, h->bwd))) return rc;
+    if ((rc = cg_alloc_conv("dissc_convgrad_set_weights", h->Cout, h->Cin, h->k, h->dil, -1, h->fwd, h->prec))) return rc;
+    if ((rc = cg_alloc_conv("dissc_convgrad_set_weights", h->Cin, h->Cout, h->k, h->dil, -1, h->bwd, h->prec))) return rc;
     h->ready = true;
   }
   for (int tr = 0; tr < 2; ++tr) {
     DevConv& dc = tr ? h->bwd : h->fwd;
+    if (dc.prec == 1) {  // split-bf16 fragments (hi | lo), rounded on the device
+      cg_launch_repack_bf3(w_dev, h->Cout, h->Cin, h->k, dc.Mpad / 32, dc.nchunk, tr, dc.wpack, st);
+      continue;
+    }
     const int nsub = dc.Mpad / (dc.m32 ? 32 : 16);
     const size_t n = (size_t)nsub * dc.nchunk * h->k * (dc.m32 ? 512 : 256);
     hipLaunchKernelGGL(convgrad_repack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w_dev, h->Cout, h->Cin,
@@ -487,7 +513,9 @@ int dissc_convgrad_backward(dissc_convgrad_t h, const float* x, const float* gy,
     a.halo = (((h->k - 1) * h->dil) / 2 + 3) & ~3;
     a.slope = in_slope;
     a.WCI = p.WCI; a.WT = p.WT; a.CIB = p.CIB; a.TS = p.TS; a.nch = p.nch; a.cpp = p.cpp;
-    if ((rc = cg_dispatch_ng(p.NG, who, "tap groups", [&](auto ng) {
+    if (cg_wgrad_bf3_takes(h->prec, h->Cin, h->Cout, h->k, h->dil)) {
+      if ((rc = cg_launch_wgrad_bf3(a, p, st))) return rc;
+    } else if ((rc = cg_dispatch_ng(p.NG, who, "tap groups", [&](auto ng) {
            return a.halo > CG_HALO ? cg_launch_wgrad<decltype(ng)::value, CG_HALO_WIDE>(a, p, st)
                                    : cg_launch_wgrad<decltype(ng)::value>(a, p, st);
          })))

@@ -213,16 +213,19 @@ def scan_checkpoint(cp_dir, prefix):
 class GanTrainer:
     """The reference's training step (sr/train.py:142-191) on one MI355X: nn.CodeGenerator, nn.MultiPeriodDiscriminator and
     nn.MultiScaleDiscriminator, the fused losses, MelSpectrogram.l1_loss, and two nn.AdamW(lr=h.learning_rate, betas=(h.adam_b1,
-    h.adam_b2)) -- optim_g over the generator's leaves, optim_d over msd's and then mpd's, the reference's order."""
+    h.adam_b2)) -- optim_g over the generator's leaves, optim_d over msd's and then mpd's, the reference's order.
+    precision: "fp32" or "split_bf16", handed to the three modules (their nn.conv1d layers; nn.conv1d says what it means).  A
+    checkpoint does not record it: one written in either mode loads and resumes in the other."""
 
-    def __init__(self, h, device="cuda:0"):
+    def __init__(self, h, device="cuda:0", precision="fp32"):
         from .mel import MelSpectrogram
         self.h = AttrDict(h)
         refuse_unsupported(self.h)
         self.device = torch.device(device)
-        self.generator = nn.CodeGenerator(self.h).to(self.device)
-        self.mpd = nn.MultiPeriodDiscriminator().to(self.device)
-        self.msd = nn.MultiScaleDiscriminator().to(self.device)
+        self.precision = precision
+        self.generator = nn.CodeGenerator(self.h, precision=precision).to(self.device)
+        self.mpd = nn.MultiPeriodDiscriminator(precision=precision).to(self.device)
+        self.msd = nn.MultiScaleDiscriminator(precision=precision).to(self.device)
         self.mel = MelSpectrogram.from_config(self.h, for_loss=True).to(self.device)
         self.optim_g = self.optim_d = None
 

@@ -81,19 +81,40 @@ CONV1D_STRIDED = _Kind("nn.conv1d_strided", "dissc_convsgrad", "[Cout, {}, k]", 
 CONV1D_GROUPED = _Kind("nn.conv1d_grouped", "dissc_convggrad", "[Cout, {} / groups, k]", lambda s: (s[1], s[0], s[2]),
                        lambda p, ld: -(-ld // p), [ctypes.c_void_p] * 2, grouped=True)
 
-_handles = {}     # (prefix, Cin, Cout, k, p, device[, groups]) -> handle; device None: host-only queries
+lib.dissc_convgrad_create_prec.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_void_p)]
+lib.dissc_convgrad_precision_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+PRECISIONS = {"fp32": 0, "split_bf16": 1}  # the prec of dissc_convgrad_create_prec
+
+
+def _prec(precision, who):
+    """the C ABI's prec of a precision name; any other name is refused here, before any launch"""
+    if precision not in PRECISIONS:
+        raise DisscError(f"{who}: unknown precision {precision!r} (one of {', '.join(PRECISIONS)})")
+    return PRECISIONS[precision]
+
+
+_handles = {}     # (prefix, Cin, Cout, k, p, device[, groups][, "split_bf16"]) -> handle; device None: host-only queries
 _workspaces = {}  # device -> uint8 tensor, grown on demand (calls on one device are stream-ordered)
 
 
-def _handle(kind, Cin, Cout, k, p, device=None, groups=1):
-    """Cin: the layer's input channels (of all groups); groups is part of the key and of the create call of a grouped kind only"""
+def _handle(kind, Cin, Cout, k, p, device=None, groups=1, prec=0):
+    """Cin: the layer's input channels (of all groups); groups is part of the key and of the create call of a grouped kind only;
+    prec = 1 (nn.conv1d only): the split-bf16 handle of the shape, a handle of its own beside the fp32 one"""
     key = (kind.prefix, int(Cin), int(Cout), int(k), int(p), None if device is None else torch.device(device))
     extra = (int(groups),) if kind.grouped else ()
     key += extra
+    if prec:
+        if kind is not CONV1D:
+            raise DisscError(f"{kind.who}: fp32 only (split_bf16 is nn.conv1d's)")
+        key += ("split_bf16",)
     h = _handles.get(key)
     if h is None:
         h = ctypes.c_void_p()
-        check(kind.create(key[1], key[2], key[3], key[4], *extra, ctypes.byref(h)), kind.names["create"])
+        if prec:
+            check(lib.dissc_convgrad_create_prec(key[1], key[2], key[3], key[4], int(prec), ctypes.byref(h)),
+                  "dissc_convgrad_create_prec")
+        else:
+            check(kind.create(key[1], key[2], key[3], key[4], *extra, ctypes.byref(h)), kind.names["create"])
         _handles[key] = h
     return h
 
@@ -115,6 +136,22 @@ def wgrad_partials(B, Lmax, Cin, Cout, k):
 def workspace_bytes(B, Lmax, Cin, Cout, k):
     """bytes of the backward's workspace (host only)"""
     return int(CONV1D.workspace_bytes(_handle(CONV1D, Cin, Cout, k, 1), int(B), int(Lmax)))
+
+
+def conv1d_precision(Cin, Cout, k, dilation=1):
+    """(fwd, dgrad, wgrad): whether the forward, the data gradient and the weight gradient of
+    conv1d(..., precision="split_bf16") on a [Cout, Cin, k] layer run split-bf16 (True) or on the fp32 kernels, with the
+    default call's bits (False): dissc_convgrad_precision_info, answered by the functions the launches consult.  Host only."""
+    out = (ctypes.c_int32 * 3)()
+    check(lib.dissc_convgrad_precision_info(_handle(CONV1D, Cin, Cout, k, dilation, prec=1), out), "dissc_convgrad_precision_info")
+    return tuple(bool(v) for v in out)
+
+
+def _precision_report(precision, entries):
+    """a module's precision_report(): entries (layer name, (Cin, Cout, k, dilation) of a conv1d layer or None for any other
+    kind) -> {name: (fwd, dgrad, wgrad)}; the other kinds, and every layer of an fp32 module, are (False, False, False)"""
+    fp32 = (False, False, False)
+    return {name: conv1d_precision(*a) if a is not None and PRECISIONS[precision] else fp32 for name, a in entries}
 
 
 def wgrad_partials_transpose(B, Lmax, Cin, Cout, k, stride):
@@ -193,12 +230,12 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def _forward(kind, ctx, x, weight, bias, lengths, p, in_slope, *add, groups=1):
+def _forward(kind, ctx, x, weight, bias, lengths, p, in_slope, *add, groups=1, prec=0):
     """set_weights, the output (zeros where lengths, or a row longer than its outputs, leave part of it unwritten), forward;
     saves x and weight, never y"""
     B, Cin, ld = x.shape
     _, Cout, k = kind.dims(weight.shape)
-    h = _handle(kind, Cin, Cout, k, p, x.device, groups)
+    h = _handle(kind, Cin, Cout, k, p, x.device, groups, prec)
     st = current_stream_ptr(x.device)
     ldo = kind.ldo(p, ld)
     with torch.cuda.device(x.device):
@@ -207,7 +244,7 @@ def _forward(kind, ctx, x, weight, bias, lengths, p, in_slope, *add, groups=1):
             torch.empty((B, Cout, ldo), dtype=torch.float32, device=x.device)
         check(kind.forward(h, _ptr(x), *map(_ptr, add), _ptr(y), _ptr(lengths), B, ld, ldo, ld, in_slope, st), kind.names["forward"])
     ctx.save_for_backward(x, weight)
-    ctx.lengths, ctx.p, ctx.in_slope, ctx.has_bias, ctx.groups = lengths, p, in_slope, bias is not None, groups
+    ctx.lengths, ctx.p, ctx.in_slope, ctx.has_bias, ctx.groups, ctx.prec = lengths, p, in_slope, bias is not None, groups, prec
     return y
 
 
@@ -221,7 +258,7 @@ def _backward(kind, ctx, gy):
     gy = gy.contiguous()
     gx = gw = gb = ws = None
     if need_x or need_w or need_b:
-        h = _handle(kind, Cin, Cout, k, ctx.p, x.device, ctx.groups)
+        h = _handle(kind, Cin, Cout, k, ctx.p, x.device, ctx.groups, ctx.prec)
         st = current_stream_ptr(x.device)
         with torch.cuda.device(x.device):
             if need_x:  # another layer sharing the handle may have run since the forward: pack again (device only)
@@ -242,31 +279,37 @@ def _backward(kind, ctx, gy):
 
 class _Conv1dFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, add, lengths, dilation, in_slope):
+    def forward(ctx, x, weight, bias, add, lengths, dilation, in_slope, prec):
         ctx.has_add = add is not None
-        return _forward(CONV1D, ctx, x, weight, bias, lengths, dilation, in_slope, add)
+        return _forward(CONV1D, ctx, x, weight, bias, lengths, dilation, in_slope, add, prec=prec)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
         gx, gw, gb, gy = _backward(CONV1D, ctx, gy)
-        return gx, gw, gb, (gy if ctx.has_add and ctx.needs_input_grad[3] else None), None, None, None
+        return gx, gw, gb, (gy if ctx.has_add and ctx.needs_input_grad[3] else None), None, None, None, None
 
 
-def conv1d(x, weight, bias=None, lengths=None, dilation=1, in_slope=1.0, add=None):
+def conv1d(x, weight, bias=None, lengths=None, dilation=1, in_slope=1.0, add=None, precision="fp32"):
     """y = bias + conv(lrelu(x, in_slope), weight, dilation, padding "same") (+ add).
 
     x [B, Cin, ld], add / y [B, Cout, ld]: contiguous fp32 device tensors, ld % 4 == 0.  weight: DEVICE tensor
     [Cout, Cin, k], k odd, k <= 11, (k - 1) * dilation <= 72; bias [Cout] or None.  lengths: int32 [B] on the device (or
     None = ld): positions at and beyond lengths[b] are read as zero and left zero in y.  Gradients flow to x, weight,
     bias and add (the gradient of add is the incoming gradient itself, handed through unmasked: the cotangent of a position
-    beyond lengths[b], which the forward never writes, is the caller's to keep zero); x and weight are saved, y is not."""
+    beyond lengths[b], which the forward never writes, is the caller's to keep zero); x and weight are saved, y is not.
+
+    precision: "fp32" (the default) or "split_bf16": every operand v is split into hi = bf16(v), lo = bf16(v - hi) and every
+    product is hi*hi + hi*lo + lo*hi on the bf16 matrix cores with fp32 accumulation (~2^-17 relative per product), in each of
+    the three directions that has a split instance -- conv1d_precision(Cin, Cout, k, dilation) tells which; the others (fewer
+    than 32 rows, (k - 1) * dilation > 60) run the fp32 kernels with the default call's bits.  The bias gradient is fp32."""
+    prec = _prec(precision, "nn.conv1d")
     Cout = _check_layer(CONV1D, x, weight, bias, lengths)
     if add is not None:
         _check_act(add, "add", x.shape[0], x.shape[2])
         if add.shape[1] != Cout:
             raise DisscError("nn.conv1d: add must have Cout channels")
-    return _Conv1dFn.apply(x, weight, bias, add, lengths, int(dilation), float(in_slope))
+    return _Conv1dFn.apply(x, weight, bias, add, lengths, int(dilation), float(in_slope), prec)
 
 
 class _ConvTranspose1dFn(torch.autograd.Function):
@@ -343,34 +386,34 @@ def conv1d_grouped(x, weight, bias=None, stride=1, groups=1, lengths=None, in_sl
     return _Conv1dGroupedFn.apply(x, weight, bias, lengths, int(stride), groups, float(in_slope))
 
 
-def resblock1(x, weights, k, dilations=(1, 3, 5), lengths=None, taps=None):
+def resblock1(x, weights, k, dilations=(1, 3, 5), lengths=None, taps=None, precision="fp32"):
     """ResBlock1 (reference sr/models.py:34-41): for each dilation d,  x = x + conv_1(lrelu(conv_d(lrelu(x)))), composed
     from six conv1d calls with the residual through ``add=``.  weights: {"convs1.<m>.weight" / ".bias",
     "convs2.<m>.weight" / ".bias"} (device tensors, weight norm already folded).  taps: a list that receives the input
-    tensor of every conv1d call in order -- the engine's own pre-activations."""
+    tensor of every conv1d call in order -- the engine's own pre-activations.  precision: that of every conv1d call."""
     for m, d in enumerate(dilations):
         if taps is not None:
             taps.append(x)
         xt = conv1d(x, weights[f"convs1.{m}.weight"], weights.get(f"convs1.{m}.bias"), lengths=lengths, dilation=d,
-                    in_slope=LRELU_SLOPE)
+                    in_slope=LRELU_SLOPE, precision=precision)
         if taps is not None:
             taps.append(xt)
         x = conv1d(xt, weights[f"convs2.{m}.weight"], weights.get(f"convs2.{m}.bias"), lengths=lengths, dilation=1,
-                   in_slope=LRELU_SLOPE, add=x)
+                   in_slope=LRELU_SLOPE, add=x, precision=precision)
     return x
 
 
-def resblock2(x, weights, k, dilations=(1, 3), lengths=None, taps=None):
+def resblock2(x, weights, k, dilations=(1, 3), lengths=None, taps=None, precision="fp32"):
     """ResBlock2 (reference sr/models.py:50-63, the light block of HiFi-GAN V3): for each of the two dilations d,
     x = x + conv_d(lrelu(x)), composed from two conv1d calls with the residual through ``add=``.  weights:
-    {"convs.<m>.weight" / ".bias"} (device tensors, weight norm already folded).  taps: as in resblock1."""
+    {"convs.<m>.weight" / ".bias"} (device tensors, weight norm already folded).  taps, precision: as in resblock1."""
     if len(dilations) != 2:
         raise DisscError(f"nn.resblock2: {len(dilations)} dilations (ResBlock2 has two convs)")
     for m, d in enumerate(dilations):
         if taps is not None:
             taps.append(x)
         x = conv1d(x, weights[f"convs.{m}.weight"], weights.get(f"convs.{m}.bias"), lengths=lengths, dilation=d,
-                   in_slope=LRELU_SLOPE, add=x)
+                   in_slope=LRELU_SLOPE, add=x, precision=precision)
     return x
 
 
@@ -459,7 +502,7 @@ def period_fold(wav, period, lengths=None):
     return _PeriodFoldFn.apply(wav, period, dev_len)
 
 
-def discriminator_p(wav, weights, period, lengths=None):
+def discriminator_p(wav, weights, period, lengths=None, precision="fp32"):
     """DiscriminatorP (reference sr/models.py:228-260) of wav [B, 1, T] or [B, T] with lengths[b] valid samples (host counts; a
     device tensor is copied back) -> (score, fmaps, lens).
 
@@ -470,8 +513,10 @@ def discriminator_p(wav, weights, period, lengths=None):
     reference appends leaky_relu(conv) to fmap, every consumer here applies the leaky ReLU on load, as the next layer does (a
     feature-matching loss reads lrelu(f, 0.1) of maps 0 .. 4 and map 5 as it is).  score: the last map, [B * period, 1, ld]
     (row b * period + w, column h is the reference's flattened score[b][h * period + w]).  lens: the six maps' per-row device
-    lengths, int32 [B * period] each: ceil(n / period), divided by 3 (rounded up) once per strided layer."""
+    lengths, int32 [B * period] each: ceil(n / period), divided by 3 (rounded up) once per strided layer.  precision: that of
+    the two conv1d layers (convs.4, conv_post); the strided layers are fp32."""
     who = "nn.discriminator_p"
+    _prec(precision, who)
     _check_wav(wav, who)
     period = int(period)
     B, T = wav.shape[0], wav.shape[-1]
@@ -494,9 +539,9 @@ def discriminator_p(wav, weights, period, lengths=None):
     for i in range(DISC_P_STRIDED_LAYERS):
         x = conv1d_strided(x, *W(f"convs.{i}"), stride=DISC_P_STRIDE, lengths=lens[i], in_slope=LRELU_SLOPE if i else 1.0)
         fmaps.append(x)
-    x = conv1d(x, *W(f"convs.{DISC_P_STRIDED_LAYERS}"), lengths=lens[-1], in_slope=LRELU_SLOPE)
+    x = conv1d(x, *W(f"convs.{DISC_P_STRIDED_LAYERS}"), lengths=lens[-1], in_slope=LRELU_SLOPE, precision=precision)
     fmaps.append(x)
-    x = conv1d(x, *W("conv_post"), lengths=lens[-1], in_slope=LRELU_SLOPE)
+    x = conv1d(x, *W("conv_post"), lengths=lens[-1], in_slope=LRELU_SLOPE, precision=precision)
     fmaps.append(x)
     return x, fmaps, lens[1:] + [lens[-1], lens[-1]]
 
@@ -553,7 +598,7 @@ def mean_pool(wav, lengths=None):
     return _MeanPoolFn.apply(wav, dev_len), np.where(ln > 0, ln // 2 + 1, 0)
 
 
-def discriminator_s(wav, weights, lengths=None):
+def discriminator_s(wav, weights, lengths=None, precision="fp32"):
     """DiscriminatorS (reference sr/models.py:285-307) of wav [B, 1, T] or [B, T] with lengths[b] valid samples (host counts; a
     device tensor is copied back) -> (score, fmaps, lens).
 
@@ -563,8 +608,10 @@ def discriminator_s(wav, weights, lengths=None):
     path.  A waveform whose T is no multiple of 4 is copied once into a zeroed row of ceil4(T) samples (allocation and copy;
     autograd slices the gradient back).  fmaps: the eight feature maps [B, C, ld_l], PRE-ACTIVATION and zero beyond their
     lengths, the contract of discriminator_p's.  score: the last map, [B, 1, ld].  lens: the eight maps' device lengths, int32
-    [B] each: n, ceil(n / 2), ceil(/ 2), ceil(/ 4), ceil(/ 4), then unchanged three times."""
+    [B] each: n, ceil(n / 2), ceil(/ 2), ceil(/ 4), ceil(/ 4), then unchanged three times.  precision: that of the two conv1d
+    layers (convs.6, conv_post); the grouped layers are fp32."""
     who = "nn.discriminator_s"
+    _prec(precision, who)
     _check_wav(wav, who)
     B, T = wav.shape[0], wav.shape[-1]
     ln = _host_lengths(lengths, B, T, who)
@@ -573,7 +620,7 @@ def discriminator_s(wav, weights, lengths=None):
         rows.append(-(-rows[-1] // s))
     flat = torch.from_numpy(np.concatenate(rows).astype(np.int32)).to(wav.device)  # every layer's lengths in one upload
     lens = [flat[i * B:(i + 1) * B] for i in range(len(rows))]
-    fmaps = _disc_s_layers(_wav_rows4(wav), weights, lens)
+    fmaps = _disc_s_layers(_wav_rows4(wav), weights, lens, precision)
     return fmaps[-1], fmaps, lens[1:] + [lens[-1], lens[-1]]
 
 
@@ -587,7 +634,7 @@ def _wav_rows4(wav):
     return x
 
 
-def _disc_s_layers(x, weights, lens):
+def _disc_s_layers(x, weights, lens, precision="fp32"):
     """the eight maps of DiscriminatorS on x [rows, 1, ld] (ld % 4 == 0); lens: the device lengths of the inputs of convs.0 ..
     convs.5 and of the stride-1 layers behind them (seven tensors)"""
     fmaps = []
@@ -595,9 +642,10 @@ def _disc_s_layers(x, weights, lens):
         x = conv1d_grouped(x, weights[f"convs.{i}.weight"], weights.get(f"convs.{i}.bias"), stride=s, groups=g, lengths=lens[i],
                            in_slope=LRELU_SLOPE if i else 1.0)
         fmaps.append(x)
-    x = conv1d(x, weights["convs.6.weight"], weights.get("convs.6.bias"), lengths=lens[-1], in_slope=LRELU_SLOPE)
+    x = conv1d(x, weights["convs.6.weight"], weights.get("convs.6.bias"), lengths=lens[-1], in_slope=LRELU_SLOPE, precision=precision)
     fmaps.append(x)
-    x = conv1d(x, weights["conv_post.weight"], weights.get("conv_post.bias"), lengths=lens[-1], in_slope=LRELU_SLOPE)
+    x = conv1d(x, weights["conv_post.weight"], weights.get("conv_post.bias"), lengths=lens[-1], in_slope=LRELU_SLOPE,
+               precision=precision)
     fmaps.append(x)
     return fmaps
 
@@ -889,8 +937,10 @@ class CodeGenerator:
     _UNSUPPORTED = ("lambda_commit", "lambda_commit_code", "f0_quantizer_path")
     N_SPEAKERS = 200  # nn.Embedding(200, ...), reference sr/models.py:133
 
-    def __init__(self, h):
+    def __init__(self, h, precision="fp32"):
         from .generator import AttrDict, resblock_conv_names, resblock_dilations, resblock_type
+        _prec(precision, "nn.CodeGenerator")
+        self.precision = precision  # of the conv1d layers (conv_pre, the ResBlock convs, conv_post); the upsamplers are fp32
         self.h = AttrDict(h)
         for k in self._UNSUPPORTED:
             if self.h.get(k, None):
@@ -919,6 +969,13 @@ class CodeGenerator:
                 L += [(name, (ch, ch, int(k)), ch) for name in resblock_conv_names(self.resblock, i * self.num_kernels + j)]
         L.append(("conv_post", (1, c0 >> self.num_upsamples, 7), 1))
         self.layers = L
+        # each conv1d layer's dilation, for precision_report (the upsamplers have none)
+        self._dilation = {"conv_pre": 1, "conv_post": 1}
+        for n, (k, ds) in ((i * self.num_kernels + j, kd) for i in range(self.num_upsamples)
+                           for j, kd in enumerate(zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes))):
+            dl = resblock_dilations(self.resblock, ds)
+            for name, d in zip(resblock_conv_names(self.resblock, n), dl + [1] * len(dl) if self.resblock == 1 else dl):
+                self._dilation[name] = d
         self._index = {name: i for i, (name, _, _) in enumerate(L)}
         self.wn = WeightNorm([(s[0], s[1] * s[2]) for _, s, _ in L], [nb for _, _, nb in L])
         self.device = torch.device("cuda:0")
@@ -938,6 +995,12 @@ class CodeGenerator:
 
     def cuda(self, device=0):
         return self.to(device)
+
+    def precision_report(self):
+        """{layer name: (fwd, dgrad, wgrad)}: which directions of each layer run split-bf16 under this module's precision
+        (nn.conv1d_precision per conv1d layer; the upsamplers are fp32).  Host only."""
+        return _precision_report(self.precision, [(name, (s[1], s[0], s[2], self._dilation[name]) if name in self._dilation else None)
+                                                  for name, s, _ in self.layers])
 
     def _keys(self):
         keys = []
@@ -1096,7 +1159,7 @@ class CodeGenerator:
             return t
 
         x = embed_concat(self.dict_weight, self.spkr_weight, code, f0d, sp, lens[0], ld)
-        x = conv1d(tap(x), *W("conv_pre"), lengths=lens[0])
+        x = conv1d(tap(x), *W("conv_pre"), lengths=lens[0], precision=self.precision)
         nk = self.num_kernels
         for i, u in enumerate(self.h.upsample_rates):
             x = conv_transpose1d(tap(x), *W(f"ups.{i}"), stride=int(u), lengths=lens[i], in_slope=LRELU_SLOPE)
@@ -1107,9 +1170,10 @@ class CodeGenerator:
                 for name in resblock_conv_names(self.resblock, i * nk + j):
                     wts[name[len(pre):] + ".weight"], wts[name[len(pre):] + ".bias"] = W(name)
                 block = resblock1 if self.resblock == 1 else resblock2
-                rs.append(block(x, wts, int(k), tuple(resblock_dilations(self.resblock, ds)), lengths=lens[i + 1], taps=taps))
+                rs.append(block(x, wts, int(k), tuple(resblock_dilations(self.resblock, ds)), lengths=lens[i + 1], taps=taps,
+                                precision=self.precision))
             x = mrf_mean(rs, lens[i + 1])
-        x = conv1d(tap(x), *W("conv_post"), lengths=lens[-1], in_slope=POST_SLOPE)
+        x = conv1d(tap(x), *W("conv_post"), lengths=lens[-1], in_slope=POST_SLOPE, precision=self.precision)
         return tanh(x, lens[-1], self.hop * T)
 
     __call__ = forward
@@ -1300,7 +1364,9 @@ class MultiPeriodDiscriminator:
     every weight gradient is one pass over both.  No torch compute op on the path (allocation, views, autograd's own sums where a
     map feeds a layer and a loss)."""
 
-    def __init__(self, periods=MPD_PERIODS):
+    def __init__(self, periods=MPD_PERIODS, precision="fp32"):
+        _prec(precision, "nn.MultiPeriodDiscriminator")
+        self.precision = precision  # of convs.4 and conv_post, the conv1d layers; the strided layers are fp32
         self.periods = tuple(int(p) for p in periods)
         if not self.periods or any(not 1 <= p <= 65535 for p in self.periods):
             raise DisscError("nn.MultiPeriodDiscriminator: at least one period, each within 1 .. 65535")
@@ -1330,6 +1396,13 @@ class MultiPeriodDiscriminator:
 
     def cuda(self, device=0):
         return self.to(device)
+
+    def precision_report(self):
+        """{layer name: (fwd, dgrad, wgrad)}: which directions of each layer run split-bf16 under this module's precision
+        (nn.conv1d_precision for convs.4 and conv_post; the strided layers are fp32).  Host only."""
+        conv1d_layers = [name for name, _, _, _ in _DISC_P_LAYERS[DISC_P_STRIDED_LAYERS:]]
+        return _precision_report(self.precision, [(name, (s[1], s[0], s[2], 1) if name.split(".", 2)[2] in conv1d_layers else None)
+                                                  for name, s, _ in self.layers])
 
     def _keys(self):
         keys = []
@@ -1469,9 +1542,9 @@ class MultiPeriodDiscriminator:
             for j in range(DISC_P_STRIDED_LAYERS):
                 x = conv1d_strided(x, *W(j), stride=DISC_P_STRIDE, lengths=ls[j], in_slope=LRELU_SLOPE if j else 1.0)
                 fm.append(x)
-            x = conv1d(x, *W(DISC_P_STRIDED_LAYERS), lengths=ls[-1], in_slope=LRELU_SLOPE)
+            x = conv1d(x, *W(DISC_P_STRIDED_LAYERS), lengths=ls[-1], in_slope=LRELU_SLOPE, precision=self.precision)
             fm.append(x)
-            x = conv1d(x, *W(DISC_P_STRIDED_LAYERS + 1), lengths=ls[-1], in_slope=LRELU_SLOPE)
+            x = conv1d(x, *W(DISC_P_STRIDED_LAYERS + 1), lengths=ls[-1], in_slope=LRELU_SLOPE, precision=self.precision)
             fm.append(x)
             scores.append(x)
             fmaps.append(fm)
@@ -1754,7 +1827,9 @@ class MultiScaleDiscriminator:
     state_dict() returns the current buffers: after n forwards, what torch's module holds after n forwards.  No torch compute
     op on the path (allocation, copies, views, autograd's own sums)."""
 
-    def __init__(self):
+    def __init__(self, precision="fp32"):
+        _prec(precision, "nn.MultiScaleDiscriminator")
+        self.precision = precision  # of convs.6 and conv_post, the conv1d layers; the grouped layers are fp32
         shape = lambda cout, cig, k: (cout, cig, k)
         self.layers0 = [(f"discriminators.0.{name}", shape(cout, cig, k), cout) for name, cout, cig, k in _DISC_S_LAYERS]
         self.layers12 = [(f"discriminators.{i}.{name}", shape(cout, cig, k), cout) for i in (1, 2) for name, cout, cig, k in _DISC_S_LAYERS]
@@ -1782,6 +1857,13 @@ class MultiScaleDiscriminator:
 
     def cuda(self, device=0):
         return self.to(device)
+
+    def precision_report(self):
+        """{layer name: (fwd, dgrad, wgrad)}: which directions of each layer run split-bf16 under this module's precision
+        (nn.conv1d_precision for convs.6 and conv_post; the grouped layers are fp32).  Host only."""
+        conv1d_layers = [name for name, _, _, _ in _DISC_S_LAYERS[len(DISC_S_GROUPED):]]
+        return _precision_report(self.precision, [(name, (s[1], s[0], s[2], 1) if name.split(".", 2)[2] in conv1d_layers else None)
+                                                  for name, s, _ in self.layers0 + self.layers12])
 
     def _keys(self):
         keys = []
@@ -1939,7 +2021,7 @@ class MultiScaleDiscriminator:
                                       self.bias0_sizes, bool(power_iteration))
             self.u, self.v, sg = self.sn.split(outs[-1])
             sigma[h].copy_(sg)
-            halves.append(_disc_s_layers(_wav_rows4(wav), self._dict0(outs), lens0))
+            halves.append(_disc_s_layers(_wav_rows4(wav), self._dict0(outs), lens0, self.precision))
         fmaps = [[_JoinFn.apply(a, b) for a, b in zip(*halves)]]
         # scales 1 and 2: one weight-norm launch for their 16 layers, one paired chain of 2 B pooled rows each
         n = len(self.layers12)
@@ -1950,7 +2032,7 @@ class MultiScaleDiscriminator:
                 x = _MeanPoolFn.apply(x, L[1][0])
             W = {f"{name}.{what}": wb[k * n + 8 * (i - 1) + j] for j, (name, _, _, _) in enumerate(_DISC_S_LAYERS)
                  for k, what in enumerate(("weight", "bias"))}
-            fmaps.append(_disc_s_layers(x, W, L[i]))
+            fmaps.append(_disc_s_layers(x, W, L[i], self.precision))
         lens = [ls[1:] + [ls[-1], ls[-1]] for ls in L]
         return MSDOutput([fm[-1] for fm in fmaps], fmaps, lens, [B, B, B], sigma)
 

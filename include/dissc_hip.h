@@ -52,7 +52,7 @@ const char* dissc_last_error(void);
  * dissc_conv1d_prec, dissc_conv_transpose1d_prec, dissc_resblock1d_bf3, dissc_bf3_info and mode 5 of dissc_respair1d;
  * 9: dissc_wino_info).  ADDED since, without a bump (no signature changed; a binding that needs one checks for the symbol):
  * dissc_gen_create_rb (the generator with ResBlock2 blocks), dissc_resblock2_1d, dissc_resblock2_info, dissc_convgrad_create_wide
- * (tap spans up to 72). */
+ * (tap spans up to 72), dissc_convgrad_create_prec and dissc_convgrad_precision_info (the split-bf16 training layer). */
 int dissc_abi_version(void);
 /* Number of HIP devices visible / name of device `dev` (for diagnostics). */
 int dissc_device_count(void);
@@ -817,6 +817,21 @@ int dissc_convgrad_create(int Cin, int Cout, int k, int dilation, dissc_convgrad
  * forward and the data gradient on the wide-span conv instances (256-column tiles for any row count) and the weight gradient on
  * instances with a 36-column halo; every span <= 60 runs what dissc_convgrad_create's handle runs.  What nn.conv1d creates. */
 int dissc_convgrad_create_wide(int Cin, int Cout, int k, int dilation, dissc_convgrad_t* out);
+/* dissc_convgrad_create_wide's handle with a precision: prec = 0 is exactly that handle; prec = 1 is the split-bf16 ("bf16x3")
+ * layer: every fp32 operand v is split into hi = bf16(v), lo = bf16(v - hi) (round to nearest even) and every product is
+ * hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  Any other prec is DISSC_EINVAL.  HOST ONLY.  It
+ * takes every shape create_wide takes; each DIRECTION of a prec = 1 handle runs split where there is an instance for it:
+ *   forward        rows = Cout >= 32 and (k - 1) dilation <= 60 (conv_bf3_kernel; not the k = 1 layers of >= 256 rows and >= 128
+ *                  columns, which have their own fp32 instance);
+ *   data gradient  the same test with rows = Cin (conv_bf3_kernel on the transposed, tap-flipped weights, then the mask kernel);
+ *   weight gradient  Cin >= 32, Cout >= 32 and (k - 1) dilation <= 60 (convgrad_wgrad_bf3_kernel, csrc/conv_grad_bf3.hip);
+ * every other direction runs the fp32 kernels of the prec = 0 handle, with its bits.  The bias gradient is always the fp32
+ * handle's.  set_weights packs the split A fragments on the device (convgrad_repack_bf3_kernel).  partials, workspace_bytes and
+ * every contract of the backward (no atomics, fixed orders, gx independent of the batch) are those of the prec = 0 handle.
+ * dissc_convgrad_precision_info: HOST ONLY.  split[0 .. 2] = 1 where the forward, the data gradient, the weight gradient of the
+ * handle run split-bf16, 0 where they run fp32; answered by the functions the launches themselves consult. */
+int dissc_convgrad_create_prec(int Cin, int Cout, int k, int dilation, int prec, dissc_convgrad_t* out);
+int dissc_convgrad_precision_info(dissc_convgrad_t h, int32_t split[3]);
 void dissc_convgrad_destroy(dissc_convgrad_t h);
 int dissc_convgrad_set_weights(dissc_convgrad_t h, const float* w_dev, const float* bias_dev, void* stream);
 int dissc_convgrad_forward(dissc_convgrad_t h, const float* x, const float* add, float* y, const int32_t* lengths, int B,

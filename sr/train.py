@@ -4,12 +4,14 @@ out, in the reference's format both ways.
 
     python sr/train.py --checkpoint_path checkpoints/vctk_hubert --config CONFIG.json
            [--training_epochs 2000] [--training_steps 400000] [--stdout_interval 5] [--checkpoint_interval 10000]
-           [--summary_interval 100] [--validation_interval 1000]
+           [--summary_interval 100] [--validation_interval 1000] [--precision {fp32,split_bf16}]
 
 The reference's arguments with its defaults (``--fine_tuning``, ``--local_rank`` and the two ``--distributed-*`` ones are
 accepted); the config is copied to ``config.json`` in the checkpoint directory, ``id_to_spkr.pkl`` is written next to
 ``input_training_file``; the reference's epoch / step loop, its stdout line, checkpoints at ``steps % checkpoint_interval == 0 and
-steps != 0``, resume at ``steps = saved + 1`` and ``last_epoch = saved epoch`` from the latest ``g_*`` / ``do_*``.  The step itself
+steps != 0``, resume at ``steps = saved + 1`` and ``last_epoch = saved epoch`` from the latest ``g_*`` / ``do_*``.  ``--precision``
+(not the reference's; default ``fp32``) is ``GanTrainer``'s: ``split_bf16`` runs the ``nn.conv1d`` layers of the three modules on
+the bf16 matrix cores in split arithmetic; checkpoints do not record it, so a run may resume in either.  The step itself
 is ``dissc_amd.gan_train.GanTrainer``; the batches are ``SegmentSampler``'s (the corpus is prepared once by sr/validate.py's
 ``prepare_items`` and lives on the device).  As in the reference, ``--training_steps`` ends an epoch, not the run: every later
 epoch still takes one step, so give ``--training_epochs`` too for a short run.
@@ -65,6 +67,7 @@ def get_parser():
     parser.add_argument("--local_rank", default=0, type=int)
     parser.add_argument("--distributed-world-size", type=int)
     parser.add_argument("--distributed-port", type=int)
+    parser.add_argument("--precision", default="fp32", choices=("fp32", "split_bf16"))  # (this trainer's own)
     return parser
 
 
@@ -165,9 +168,11 @@ def train(a, h, trainer, train_items, val_items, log):
 
 
 def main(argv=None, make_trainer=None):
-    """make_trainer(h, device) -> the trainer (default: dissc_amd.gan_train.GanTrainer), as validate.main takes make_scorer"""
+    """make_trainer(h, device) -> the trainer (default: dissc_amd.gan_train.GanTrainer at --precision), as validate.main takes
+    make_scorer"""
     print("Initializing Training Process..")
     a = get_parser().parse_args(argv)
+    print("precision : ", a.precision)
     from dissc_amd import AttrDict, gan_train
     with open(a.config) as f:
         h = AttrDict(json.loads(f.read()))
@@ -176,7 +181,8 @@ def main(argv=None, make_trainer=None):
     train_items, val_items, _ = load_data(h)
     if len(train_items) < int(h["batch_size"]):
         raise ValueError(f"{len(train_items)} training items do not fill one batch of {h['batch_size']} (drop_last)")
-    trainer = (make_trainer or gan_train.GanTrainer)(h, f"cuda:{a.local_rank}")
+    trainer = make_trainer(h, f"cuda:{a.local_rank}") if make_trainer else \
+        gan_train.GanTrainer(h, f"cuda:{a.local_rank}", precision=a.precision)
     print("checkpoints directory : ", a.checkpoint_path)
     log = ScalarLog(os.path.join(a.checkpoint_path, "logs"))
     try:

@@ -12,6 +12,14 @@ blocks (ours, torch, ours, ...), each block `iters` calls between two device eve
 work: padded rows / channel chunks for the direct convs, padded 32 x 32 tiles x tap groups for the weight gradient.  One
 JSON line per shape; --markdown adds the table of profiles/conv_grad.md.
 
+    python tools/conv_grad_bench.py --precision split_bf16 [--mpd] [--markdown]
+
+adds, in the same alternating blocks, the three directions (and the repack) of the split-bf16 handle of each shape
+(nn.conv1d(..., precision="split_bf16"), csrc/conv_grad_bf3.hip) next to the fp32 handle's and torch's, with every block's figure
+kept in the JSON line ("*_ms_blocks"), the directions nn.conv1d_precision reports as split, and the split results' distance to
+torch; --mpd adds 1024 -> 1024, k = 5 at the period discriminators' rows (2 x batch x p rows for p = 2, 3, 5, 7, 11): the tables of
+profiles/conv1d_split_bf16.md.  The split TFLOP/s are of the same executed MACs (each as three bf16 MFMAs, not counted thrice).
+
     python tools/conv_grad_bench.py --transpose [--batch 32] [--frames 28] [--markdown]
 
 The same for the differentiable ConvTranspose1d (nn.conv_transpose1d, csrc/conv_grad_t.hip) on the generator's five
@@ -90,9 +98,13 @@ def bench_layer(a, kind, cin, cout, k, p_, L, groups=1):
     gy = torch.from_numpy(rs.standard_normal((B, cout, ldo)).astype(np.float32)).to(dev)
     w = torch.from_numpy((rs.uniform(-1, 1, (cin, cout, k) if tr else (cout, cig, k)) / np.sqrt(cig * k / (s if tr else 1))).astype(np.float32)).to(dev)
     b = torch.from_numpy(rs.uniform(-1, 1, cout).astype(np.float32)).to(dev)
+    if kind is nn.CONV1D and ld != L:  # (the MPD rows: torch runs on whole rows, so the columns the layer never reads are zero)
+        x[:, :, L:], gy[:, :, L:] = 0.0, 0.0
     lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
     y, gx, gw, gb = torch.zeros_like(gy), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
     h = nn._handle(kind, cin, cout, k, p_, dev, groups)
+    split = kind is nn.CONV1D and getattr(a, "precision", "fp32") == "split_bf16"
+    hs = nn._handle(kind, cin, cout, k, p_, dev, prec=1) if split else None  # (a handle of its own: both stay packed)
     st = current_stream_ptr(dev)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
     nws = int(kind.workspace_bytes(h, B, ld))
@@ -125,6 +137,18 @@ def bench_layer(a, kind, cin, cout, k, p_, L, groups=1):
         "torch_wgrad": lambda: torch_bwd([False, True, True]),
         "repack": lambda: check(kind.set_weights(h, p(w), p(b), st), "set_weights"),
     }
+    if split:
+        ys, gxs, gws, gbs = torch.zeros_like(gy), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
+        check(kind.set_weights(hs, p(w), p(b), st), "set_weights")
+        s_bwd = lambda gx_, gw_, gb_: check(kind.backward(hs, p(x), p(gy), p(lengths), B, ld, ldo, ld, slope, gx_, gw_, gb_, p(ws), nws, st),
+                                            "backward")
+        cases.update({
+            "split_fwd": lambda: check(kind.forward(hs, p(x), None, p(ys), p(lengths), B, ld, ldo, ld, slope, st), "forward"),
+            "split_dgrad": lambda: s_bwd(p(gxs), None, None),
+            "split_wgrad": lambda: s_bwd(None, p(gws), p(gbs)),
+            "split_repack": lambda: check(kind.set_weights(hs, p(w), p(b), st), "set_weights"),
+        })
+        cases["split_fwd"](), cases["split_dgrad"](), cases["split_wgrad"]()
     # agreement first (fp32 both sides)
     cases["fwd"](), cases["dgrad"](), cases["wgrad"]()
     tg = torch_bwd([True, True, True])
@@ -153,10 +177,18 @@ def bench_layer(a, kind, cin, cout, k, p_, L, groups=1):
     for n, v in times.items():
         out[n + "_ms"] = round(float(np.median(v)), 4)
         out[n + "_ms_spread"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
+        if split:
+            out[n + "_ms_blocks"] = [round(float(t), 4) for t in v]
+    if split:
+        out["split"] = dict(zip(("fwd", "dgrad", "wgrad"), nn.conv1d_precision(cin, cout, k, p_)))
+        out["split_rel_diff_to_torch"] = {"gx": float(f"{rel(gxs, tg[0] * torch.where(x > 0, 1.0, slope) * valid):.2e}"),
+                                          "gw": float(f"{rel(gws, tg[1]):.2e}"), "gb": float(f"{rel(gbs, tg[2]):.2e}")}
     # the transposed layer: the direct form's MACs, Cin Cout k per input position
     flops = [2.0 * cig * cout * k * B * (nout if sd else L)] * 3 if tr or sd else executed_flops(cin, cout, k, B * L)
     for n, fl in zip(("fwd", "dgrad", "wgrad"), flops):
         out[n + "_tflops"] = round(fl / (out[n + "_ms"] * 1e-3) / 1e12, 2)
+        if split:
+            out["split_" + n + "_tflops"] = round(fl / (out["split_" + n + "_ms"] * 1e-3) / 1e12, 2)
     print(json.dumps(out), flush=True)
     return out
 
@@ -302,6 +334,8 @@ def main(argv=None):
     ap.add_argument("--scales", type=int, default=3, help="--grouped: the scales (each pooled from the one before)")
     ap.add_argument("--samples", type=int, default=8960, help="--strided, --grouped: samples per segment")
     ap.add_argument("--periods", default="2,11", help="--strided: the periods to fold to")
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "split_bf16"), help="split_bf16: the split handle's columns too")
+    ap.add_argument("--mpd", action="store_true", help="also 1024 -> 1024, k = 5 at the period discriminators' rows")
     a = ap.parse_args(argv)
     if a.transpose:
         return main_transpose(a)
@@ -319,7 +353,35 @@ def main(argv=None):
             continue
         seen.add((cin, cout, k))
         rows.append(bench_layer(a, nn.CONV1D, cin, cout, k, d, L))
-    if a.markdown:
+    mpd_rows = []
+    if a.mpd:  # convs.4 of DiscriminatorP: 2 x batch x p rows (y and y_hat as one batch) of the fold's columns behind four stride-3 layers
+        batch = a.batch
+        for period in (2, 3, 5, 7, 11):
+            L = -(-a.samples // period)
+            for _ in range(4):
+                L = -(-L // 3)
+            a.batch = 2 * batch * period
+            mpd_rows.append(dict(bench_layer(a, nn.CONV1D, 1024, 1024, 5, 1, L), period=period))
+        a.batch = batch
+    if a.markdown and a.precision == "split_bf16":
+        print("| layer | rows x L | fwd ms fp32 / split (torch) | dgrad ms fp32 / split (torch) | wgrad ms fp32 / split (torch) | "
+              "split TFLOP/s fwd / dgrad / wgrad | split directions | repack ms fp32 / split |")
+        print("|---|---|---|---|---|---|---|---|")
+        for r in rows + mpd_rows:
+            tri = lambda n: f"{r[n + '_ms']:.3f} / {r['split_' + n + '_ms']:.3f} ({r['torch_' + n + '_ms']:.3f})"
+            print(f"| {r['cin']} -> {r['cout']}, k = {r['k']}{' (MPD p = %d)' % r['period'] if 'period' in r else ''} | {r['batch']} x {r['L']} | "
+                  f"{tri('fwd')} | {tri('dgrad')} | {tri('wgrad')} | {r['split_fwd_tflops']} / {r['split_dgrad_tflops']} / "
+                  f"{r['split_wgrad_tflops']} | {'/'.join(n for n, v in r['split'].items() if v) or 'none'} | "
+                  f"{r['repack_ms']:.3f} / {r['split_repack_ms']:.3f} |")
+        mult = lambda r: 6 if r["cin"] == r["cout"] else 1  # a ResBlock has six convs of its shape
+        for n in ("fwd", "dgrad", "wgrad") if rows else ():
+            nb = len(rows[0][n + "_ms_blocks"])
+            per = lambda key: [round(sum(r[key + "_ms_blocks"][i] * mult(r) for r in rows), 3) for i in range(nb)]
+            print(f"\nsum over the generator's 92 stride-1 layers, {n}, per block: fp32 {per(n)} split {per('split_' + n)} torch {per('torch_' + n)} ms")
+        slower = [(r["cin"], r["cout"], r["k"], r.get("period"), n) for r in rows + mpd_rows for n in ("fwd", "dgrad", "wgrad")
+                  if r["split"][n] and r["split_" + n + "_ms"] > r[n + "_ms"]]
+        print("split slower than fp32:", slower if slower else "none")
+    elif a.markdown:
         print("| layer | L | fwd ms (torch) | dgrad ms (torch) | wgrad ms (torch) | TFLOP/s fwd / dgrad / wgrad | P | repack ms |")
         print("|---|---|---|---|---|---|---|---|")
         for r in rows:

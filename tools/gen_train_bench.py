@@ -25,10 +25,11 @@ times the scale half (msd_bench below; profiles/msd_train.md): every dissc_snorm
 matrices of discriminator 0 next to the bytes it must move, the two joined-map copies per map of scale 0, and the discriminator's
 and the generator's scale-side steps against spectral_norm / weight_norm Conv1d modules in eager torch, in alternated runs.
 
-    python tools/gen_train_bench.py --gan [--batch 32] [--frames 28] [--steps 20] [--blocks 3] [--markdown]
+    python tools/gen_train_bench.py --gan [--batch 32] [--frames 28] [--steps 20] [--blocks 3] [--markdown] [--precision split_bf16]
 
 times what the GAN trainer adds (gan_bench below; profiles/gan_train.md): nn.AdamW against torch.optim.AdamW on the same leaves,
-the gather launch against the host path, and GanTrainer.step against the same step in eager torch."""
+the gather launch against the host path, and GanTrainer.step against the same step in eager torch; with --precision split_bf16 the
+whole-step blocks alternate GanTrainer.step with GanTrainer(precision="split_bf16").step instead (profiles/conv1d_split_bf16.md)."""
 import argparse
 import ctypes
 import json
@@ -568,6 +569,11 @@ def gan_bench(a):
     variants = [("GanTrainer.step", lambda i=0: trainer.step(batch)),
                 ("eager torch, discriminators detached in the generator's half", lambda i=0: eager_step(False)),
                 ("eager torch, the reference as written (discriminator gradients computed in both halves)", lambda i=0: eager_step(True))]
+    if a.precision == "split_bf16":  # the split step against the fp32 step of this session, by turns, from the same weights
+        split = gan_train.GanTrainer(h, DEV, precision="split_bf16").init(seed=0)
+        s_first = split.step(batch)
+        print(json.dumps({"what": "first step from the same weights, split_bf16", **{k: float(v) for k, v in s_first.items()}}), flush=True)
+        variants = [variants[0], ('GanTrainer(precision="split_bf16").step', lambda i=0: split.step(batch))]
     for _, fn in variants:
         wall(fn, 3)
     blocks = {v: [] for v, _ in variants}
@@ -597,6 +603,8 @@ def main(argv=None):
     ap.add_argument("--msd", action="store_true", help="time the scale half of the GAN step (nn.SpectralNorm, nn.MultiScaleDiscriminator)")
     ap.add_argument("--gan", action="store_true", help="time what the GAN trainer adds: nn.AdamW, the segment gather, GanTrainer.step")
     ap.add_argument("--blocks", type=int, default=3, help="--gan: alternating blocks per variant")
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "split_bf16"),
+                    help="--gan: split_bf16 times GanTrainer(precision=\"split_bf16\").step against the fp32 step in alternating blocks")
     a = ap.parse_args(argv)
     import __graft_entry__ as ge
     ge.build()
