@@ -138,6 +138,8 @@ def _load():
     L.dissc_resblock2_1d.argtypes = [vp] * 8 + [i32] * 7 + [ctypes.c_float, i32, ctypes.c_float, i32, vp]
     L.dissc_conv_info.argtypes = [i32] * 7 + [ctypes.POINTER(DisscConvLaunch), i32, ctypes.POINTER(ctypes.c_int)]
     L.dissc_wino8_info.argtypes = [i32] * 6 + [ctypes.POINTER(DisscWino8Plan)]
+    if hasattr(L, "dissc_wino8_form"):  # (an older build loaded through DISSC_HIP_LIB for an A/B has none)
+        L.dissc_wino8_form.argtypes = [i32] * 6 + [ctypes.POINTER(ctypes.c_int)]
     L.dissc_wino_info.argtypes = [i32] * 5 + [ctypes.POINTER(DisscWinoPlan)]
     L.dissc_resblock1d_bf3.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, ctypes.c_float, i32, ctypes.c_float, i32, i32, vp]
     L.dissc_bf3_info.argtypes = [i32] * 6 + [vp, i32, i32, ctypes.POINTER(DisscBf3Info)]
@@ -210,6 +212,14 @@ def wino8_info(C, k, dilation, R, B, Lmax):
     out = DisscWino8Plan()
     check(lib.dissc_wino8_info(C, k, dilation, R, B, Lmax, ctypes.byref(out)), "dissc_wino8_info")
     return {f: getattr(out, f) for f, _ in DisscWino8Plan._fields_}
+
+
+def wino8_form(C, k, dilation, R, B, Lmax):
+    """dissc_wino8_form: 1 where that launch shares one input transform between the waves of a workgroup ("wino8_sv"), 0 where
+    every wave forms its own tile.  Host only."""
+    out = ctypes.c_int(-1)
+    check(lib.dissc_wino8_form(C, k, dilation, R, B, Lmax, ctypes.byref(out)), "dissc_wino8_form")
+    return out.value
 
 
 def wino_info(C, k, dilation, B, Lmax):

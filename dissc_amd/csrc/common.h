@@ -43,6 +43,7 @@ void set_error(const char* fmt, ...);
   X(small_grid, 1, "small_grid") \
   X(kernel_dbg, 0, "kernel_dbg") \
   X(wino_sv, 1, "wino_sv") \
+  X(wino8_sv, 1, "wino8_sv") \
   X(wino8_c64_wide, 3, "wino8_c64_wide") \
   X(wino8_mask, 0450770550, "wino8_mask") \
   X(wino8_r4_mask, 0770770010, "wino8_r4_mask") \
@@ -404,6 +405,8 @@ int run_wino8(const DevConv& dc, const float* x, float* out, const Batch& bt, co
 // the longest utterance, gy row tiles; `inst` indexes conv_wino8.hip's instance table
 struct Wino8Plan { int inst, R, NS, MI, NI, WPS, unit, OT, CPR, gx, gy; };
 int wino8_plan(int C, int KS, int dil, int R, int B, int Lmax, Wino8Plan& p);
+// whether run_wino8 launches the plan's instance in its shared-transform form (option "wino8_sv"; dissc_wino8_form reports it)
+bool wino8_plan_shared(const Wino8Plan& p);
 
 // one residual pair per launch with BOTH convs in the Toom-Cook transform domain, t kept in LDS (respair_wino.hip)
 struct DevPairW {

@@ -26,6 +26,14 @@
 // 6 D (its 8-byte window reads are then only 4-byte aligned), G has a fourth column and A^T five rows.
 // Rounding: per layer 1.8x the F(4,3) form's error (numpy model of a C = 256 layer, k = 11: rms 1.5e-7 vs 8.3e-8 on O(0.3)
 // outputs, direct 9.3e-8); DESIGN.md section 4.
+// SHV (template flag; "wino8_sv" option, the 128 x 64 tile (MI, NI, WPS) = (4, 2, 2) of the k = 7 / 11 shapes only): with private
+// tiles every window sample is read from LDS by all eight waves, once per point, and all eight are in the transform at once, so
+// nothing on the CU covers it (knock-out: 9-17 % of a launch of the two wide stages).  Shared: wave w forms all eight points of
+// channel w of a sub-chunk -- one read of the window per workgroup, the same 16 V writes per lane, no switch on the point -- into
+// a double-buffered V [2][8 points][8][XV]; the tile of sub-chunk g + 1 is formed in front of the MFMAs of sub-chunk g, one
+// barrier per sub-chunk instead of one per round.  Same w8_bt expression per value, same MFMA sequence: the same bits; per launch
+// -5 ... -13 % (profiles/r15/wino8_sv_gate.txt).  The second V copy (28.7 KB) fits this tile only: the two-per-CU tiles have 80 KB,
+// the C = 64 wide tile a 240-float V row; the latency tiers (NI = 1) have their own loop.
 #include <string.h>
 
 #include <type_traits>
@@ -113,7 +121,8 @@ constexpr int w8_row_len(int D, int NTU, int need, int MO) {
 // WPS: waves per SIMD the instance is built for -- 2: one 8-wave workgroup per CU (up to 256 registers); 4: TWO workgroups
 // per CU (<= 128 registers and <= 80 KB of LDS each: windows of 8 channels, epilogue passes of 16 rows), whose phases overlap
 // R: taps per sub-filter (3: F(6,3), 4: F(5,4)); MO = 9 - R outputs per unit
-template <int NS, int DIL, int MI, int NI, int WPS = 2, int R = 3>
+// SHV: the shared-transform form of the (4, 2, 2) tile (the kernel's `if constexpr (SHV)` main loop): V is [2][8 points][8][XV]
+template <int NS, int DIL, int MI, int NI, int WPS = 2, int R = 3, bool SHV = false>
 struct Wino8Geo {
   static constexpr int NTH = 512;
   static constexpr int MO = 9 - R;
@@ -141,23 +150,24 @@ struct Wino8Geo {
   static constexpr int XV = (LAT && NTU * W <= 80) ? 80 : NTU * W <= 112 ? 112 : 240; // V row stride (% 32 == 16: the two k halves of a fragment read hit different banks)
   static constexpr int YS = NCW + 4;
   static constexpr int WIN_FLOATS = 2 * CPR * CHF;
-  static constexpr int V_FLOATS = 8 * 8 * XV * (LAT ? 2 : 1);  // (latency form: two V tiles per wave)
+  static constexpr int V_FLOATS = 8 * 8 * XV * ((LAT || SHV) ? 2 : 1);  // (latency form: two V tiles per wave; shared form: two per workgroup)
   static constexpr int Y_FLOATS = 8 * RPP * YS;
   static constexpr int OS = w8_rup(OT, 4) + 4;          // row stride of the epilogue's output tile (16-byte aligned rows)
   static constexpr int EPI_FLOATS = Y_FLOATS + RPP * OS;
   static constexpr int LDS_FLOATS = (WIN_FLOATS + V_FLOATS) > EPI_FLOATS ? (WIN_FLOATS + V_FLOATS) : EPI_FLOATS;
   static_assert(NTU >= 1 && NTU * W <= XV && RL % 2 == 0, "tile geometry");
   static_assert(LDS_FLOATS * 4 <= ((WPS == 4 && !LAT) ? 80 : 160) * 1024, "LDS");
+  static_assert(!SHV || (MI == 4 && NI == 2 && WPS == 2 && NS > 1 && CG == 1 && CPR == 16), "the shared transform is built for the (4, 2, 2) tile");
 };
 
-template <int NS, int DIL, int MI, int NI, int WPS = 2, int R = 3>
+template <int NS, int DIL, int MI, int NI, int WPS = 2, int R = 3, bool SHV = false>
 __global__ void __launch_bounds__(512, (NI == 1 ? 2 : WPS)) conv_wino8_kernel(const Wino8Args a) {
-  using G = Wino8Geo<NS, DIL, MI, NI, WPS, R>;
+  using G = Wino8Geo<NS, DIL, MI, NI, WPS, R, SHV>;
   constexpr bool LAT = G::LAT;
   constexpr int NTH = G::NTH, D = G::D, W = G::W, NCOL = G::NCOL, OT = G::OT, NV = G::NV, RL = G::RL, MO = G::MO,
                 CHF = G::CHF, CPR = G::CPR, XV = G::XV, YS = G::YS, OFF = G::OFF, RPP = G::RPP, CG = G::CG;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* const vbuf = lds + G::WIN_FLOATS;  // [8 waves][8][XV]
+  float* const vbuf = lds + G::WIN_FLOATS;  // [8 waves][8][XV] (SHV: [2][8 points][8][XV])
 
   // 1-D grid, XCD-aware (conv_wino.hip): row tiles pinned to XCD groups, time tiles / utterances spread inside a group
   const int per = 8 / a.gy;
@@ -439,14 +449,14 @@ __global__ void __launch_bounds__(512, (NI == 1 ? 2 : WPS)) conv_wino8_kernel(co
   }
 
   int blk = 0;
-  auto run_taps = [&]() __attribute__((always_inline)) {
+  auto run_taps = [&](const float* vsrc) __attribute__((always_inline)) {  // vsrc: this point's V tile [8][XV]
     if (a.dbg & 2) {
       blk += NS;
       return;
     }
     const float* bj[NI];
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni) bj[ni] = vp + voff[ni];
+    for (int ni = 0; ni < NI; ++ni) bj[ni] = vsrc + voff[ni];
 #pragma unroll
     for (int j = 0; j < NS; ++j, ++blk) {
       const int bn = (blk + 1 < nblk) ? blk + 1 : nblk - 1;
@@ -473,6 +483,61 @@ __global__ void __launch_bounds__(512, (NI == 1 ? 2 : WPS)) conv_wino8_kernel(co
 
   // One barrier per round: at the top of round rd the window of round rd + 1 goes into the other buffer (every wave finished
   // reading it before the barrier that closed round rd - 1) and the loads of round rd + 2 are issued
+  if constexpr (SHV) {
+    // ---- shared transform ("wino8_sv"; conv_wino.hip's SHV form on eight waves): wave w forms ALL EIGHT points of channel w of
+    // a sub-chunk -- every window sample is read from LDS once per workgroup instead of once per wave, the same 16 V writes per
+    // lane, no switch on the point -- into a double-buffered V [2][8 points][8][XV]: the tile of sub-chunk g + 1 is formed in
+    // front of the MFMAs of sub-chunk g, one barrier per sub-chunk.  Every V value is w8_bt<P> of the same eight samples as in
+    // the private form, and the MFMA sequence per accumulator is the same: bit-identical.
+    constexpr int VSZ = 8 * 8 * XV;
+    auto transform_sv = [&](const float* raw8, float* vdst) __attribute__((always_inline)) {  // channel p of raw8's eight
+      const float* rw = raw8 + p * CHF + toff[0];
+      float* const vd = vdst + p * XV;
+      f32x2a q0, q1, q2, q3;
+      if constexpr (MO % 2 == 0) {
+        q0 = *reinterpret_cast<const f32x2a*>(rw); q1 = *reinterpret_cast<const f32x2a*>(rw + 2);
+        q2 = *reinterpret_cast<const f32x2a*>(rw + 4); q3 = *reinterpret_cast<const f32x2a*>(rw + 6);
+      } else {
+        q0[0] = rw[0]; q0[1] = rw[1]; q1[0] = rw[2]; q1[1] = rw[3]; q2[0] = rw[4]; q2[1] = rw[5]; q3[0] = rw[6]; q3[1] = rw[7];
+      }
+      const float r8 = rw[8];
+      auto point = [&](auto pc) __attribute__((always_inline)) {
+        constexpr int P = decltype(pc)::value;
+        const float v0 = w8_bt<P>(q0[0], q0[1], q1[0], q1[1], q2[0], q2[1], q3[0], q3[1]);
+        const float v1 = w8_bt<P>(q0[1], q1[0], q1[1], q2[0], q2[1], q3[0], q3[1], r8);
+        vd[P * (8 * XV) + e0[0]] = v0;
+        vd[P * (8 * XV) + e1[0]] = ok1[0] ? v1 : v0;
+      };
+      point(std::integral_constant<int, 0>{}); point(std::integral_constant<int, 1>{});
+      point(std::integral_constant<int, 2>{}); point(std::integral_constant<int, 3>{});
+      point(std::integral_constant<int, 4>{}); point(std::integral_constant<int, 5>{});
+      point(std::integral_constant<int, 6>{}); point(std::integral_constant<int, 7>{});
+    };
+    const bool tr = !(a.dbg & 1);  // (the knock-out takes both halves: the first tile and the ones formed in the loop)
+    if (tr) transform_sv(lds, vbuf);
+    __syncthreads();
+    int g = 0;
+    for (int rd = 0; rd < nround; ++rd) {
+      const float* raw = lds + (rd & 1) * (CPR * CHF);
+      float* rawn = lds + ((rd + 1) & 1) * (CPR * CHF);
+      // window rd + 1 goes into the other buffer at the top of the round (its last readers -- the transforms in front of round
+      // rd - 1's sub-chunk 0 -- finished two barriers ago); the barrier of sub-chunk 0 publishes it before the transform in
+      // front of this round's last sub-chunk reads its first 8 channels.  The loop's last barrier separates the last V reads
+      // from the epilogue's reuse of LDS.
+      if (rd + 1 < nround) stage_store(rawn);
+      if (rd + 2 < nround) stage_load(rd + 2);
+#pragma unroll
+      for (int sc = 0; sc < CPR / 8; ++sc, ++g) {
+        float* vnxt = vbuf + ((g + 1) & 1) * VSZ;
+        if (tr) {
+          if (sc + 1 < CPR / 8) transform_sv(raw + (sc + 1) * 8 * CHF, vnxt);
+          else if (rd + 1 < nround) transform_sv(rawn, vnxt);
+        }
+        run_taps(vbuf + (g & 1) * VSZ + p * (8 * XV));
+        __syncthreads();
+      }
+    }
+  } else {
   for (int rd = 0; rd < (LAT ? 0 : nround); ++rd) {
     const float* raw = lds + (rd & 1) * (CPR * CHF);
     if (rd + 1 < nround) stage_store(lds + ((rd + 1) & 1) * (CPR * CHF));
@@ -480,9 +545,10 @@ __global__ void __launch_bounds__(512, (NI == 1 ? 2 : WPS)) conv_wino8_kernel(co
 #pragma unroll
     for (int sc = 0; sc < CPR / 8; ++sc) {
       transform8(raw + (sc * 8) * CHF);
-      run_taps();
+      run_taps(vp);
     }
     __syncthreads();
+  }
   }
 
   // ---- epilogue, 32 rows at a time: the 8 waves put their Y_p into LDS; one thread per (row, column) applies A^T -- all
@@ -662,17 +728,43 @@ static int launch_wino8_t(const Wino8Args& a, hipStream_t stream) {  // a.gx, a.
   return DISSC_OK;
 }
 
+// the shared-transform twin of the (4, 2, 2) tile: the same plan, grid and arguments
+template <int NS, int DIL, int R>
+static int launch_wino8_sv_t(const Wino8Args& a, hipStream_t stream) {
+  using G = Wino8Geo<NS, DIL, 4, 2, 2, R, true>;
+  static_assert(G::OT == Wino8Geo<NS, DIL, 4, 2, 2, R>::OT && G::CPR == Wino8Geo<NS, DIL, 4, 2, 2, R>::CPR, "one plan for both forms");
+  static DeviceOnce attr_once;
+  DISSC_HIP_CHECK(attr_once.max_lds(reinterpret_cast<const void*>(&conv_wino8_kernel<NS, DIL, 4, 2, 2, R, true>), 160 * 1024));
+  const int per = 8 / a.gy;
+  dim3 grid(8 * ((a.gx * a.B + per - 1) / per));
+  hipLaunchKernelGGL((conv_wino8_kernel<NS, DIL, 4, 2, 2, R, true>), grid, dim3(512), (size_t)G::LDS_FLOATS * sizeof(float), stream, a);
+  DISSC_HIP_CHECK(hipGetLastError());
+  return DISSC_OK;
+}
+// (4, 2, 2) with more than one sub-filter (k = 7 / 11) has such a twin; every other tile keeps private V tiles (LDS: header).
+// The exception is an instance that does not exist, so it is made here, where the instances are listed, and wino8_plan_shared
+// -- the one place that chooses a launch's form -- reads it as a null launch_sv: k = 7, d = 5 as F(6,3) (R = 3 with NS = 3 sub-filters;
+// k = 7 is the only kernel size of wino8_supported with ceil(k / 3) = 3), whose private twin already holds 255 registers -- the
+// shared form spilled one (8 bytes of scratch per lane, profiles/r15/resource_usage.txt) and is not built; the default plan runs
+// that shape as F(5,4).
+template <int NS, int DIL, int MI, int NI, int WPS, int R>
+constexpr auto w8_sv_launch() -> int (*)(const Wino8Args&, hipStream_t) {
+  if constexpr (MI == 4 && NI == 2 && WPS == 2 && NS > 1 && !(R == 3 && NS == 3 && DIL == 5)) return &launch_wino8_sv_t<NS, DIL, R>;
+  else return nullptr;
+}
+
 // The instances the library carries: the geometry of each comes from its own Wino8Geo, the launch is its own launch_wino8_t.
 // wino8_plan (and through it run_wino8 and dissc_wino8_info) reads widths and channel rounds from this table alone.
 struct Wino8Inst {
   int R, NS, dil, MI, NI, WPS;
   int unit, OT, CPR;  // Wino8Geo's MO * D, OT, CPR
   int (*launch)(const Wino8Args&, hipStream_t);
+  int (*launch_sv)(const Wino8Args&, hipStream_t);  // the shared-transform form of the same tile ("wino8_sv"), or nullptr
 };
 #define DISSC_W8_INST(R_, NS_, D_, MI_, NI_, WPS_)                                                                   \
   {R_, NS_, D_, MI_, NI_, WPS_, Wino8Geo<NS_, D_, MI_, NI_, WPS_, R_>::MO * Wino8Geo<NS_, D_, MI_, NI_, WPS_, R_>::D, \
    Wino8Geo<NS_, D_, MI_, NI_, WPS_, R_>::OT, Wino8Geo<NS_, D_, MI_, NI_, WPS_, R_>::CPR,                             \
-   &launch_wino8_t<NS_, D_, MI_, NI_, WPS_, R_>}
+   &launch_wino8_t<NS_, D_, MI_, NI_, WPS_, R_>, w8_sv_launch<NS_, D_, MI_, NI_, WPS_, R_>()}
 // the six tiles (MI, NI, WPS) of a transform shape: the four tiers of C >= 128, and (2, 1, 4) with the three "wino8_c64_wide" tiles of C = 64
 #define DISSC_W8_SHAPE(R_, NS_, D_)                                                                                    \
   DISSC_W8_INST(R_, NS_, D_, 1, 1, 4), DISSC_W8_INST(R_, NS_, D_, 2, 1, 4), DISSC_W8_INST(R_, NS_, D_, 2, 2, 4),       \
@@ -771,6 +863,11 @@ int wino8_plan(int C, int KS, int dil, int R, int B, int Lmax, Wino8Plan& p) {
   return DISSC_OK;
 }
 
+// option "wino8_sv" (default 1): the (4, 2, 2) tile of a k = 7 / 11 shape launches its shared-transform form (template flag SHV);
+// 0 = every tile with private V tiles.  Same bits either way.  The one place that chooses the form (run_wino8 launches what
+// this returns; dissc_wino8_form reports it).  A shape without a shared instance (w8_sv_launch) keeps its private tiles.
+bool wino8_plan_shared(const Wino8Plan& p) { return opts().wino8_sv != 0 && kW8Inst[p.inst].launch_sv != nullptr; }
+
 int run_wino8(const DevConv& dc, const float* x, float* out, const Batch& bt, const EpiSpec& ep, int ldx, int ldo, float slope,
               hipStream_t stream) {
   Wino8Args a;
@@ -789,7 +886,7 @@ int run_wino8(const DevConv& dc, const float* x, float* out, const Batch& bt, co
   const int rc = wino8_plan(dc.M, dc.KS, dc.dil, dc.wr == 4 ? 4 : 3, bt.B, bt.Lmax, p);
   if (rc) return rc;
   a.gx = p.gx; a.gy = p.gy; a.B = bt.B;
-  return kW8Inst[p.inst].launch(a, stream);
+  return wino8_plan_shared(p) ? kW8Inst[p.inst].launch_sv(a, stream) : kW8Inst[p.inst].launch(a, stream);
 }
 
 }  // namespace dissc

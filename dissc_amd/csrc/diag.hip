@@ -536,6 +536,16 @@ int dissc_wino8_info(int C, int k, int dilation, int R, int B, int Lmax, DisscWi
   return DISSC_OK;
 }
 
+// Diagnostics: which form of that instance the launch takes under the current option defaults ("wino8_sv"): 1 = the transform shared
+// between the waves (conv_wino8_kernel<.., SHV = true>), 0 = private V tiles.  wino8_plan_shared, which run_wino8 launches from.  Host only.
+int dissc_wino8_form(int C, int k, int dilation, int R, int B, int Lmax, int* shared_out) {
+  Wino8Plan p;
+  const int rc = wino8_plan(C, k, dilation, R, B, Lmax, p);
+  if (rc) return rc;
+  if (shared_out) *shared_out = wino8_plan_shared(p) ? 1 : 0;
+  return DISSC_OK;
+}
+
 // Diagnostics: the conv_wino_kernel instance and grid a C -> C conv of (k, dilation) launches in its six-point F(4,3) form on a batch of
 // B utterances of at most Lmax columns, under the current option defaults: wino_plan, which run_wino launches from.  Host only: no
 // HIP call.

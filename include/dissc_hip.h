@@ -243,6 +243,11 @@ int dissc_conv_s2_bench(int B, int C, int L, int form, int iters, float* ms_out)
  *                        wino8_r4 (1): the shapes of wino8_r4_mask (0770770010, same layout) run as F(5,4); 2 = dissc_conv1d too; 0 =
  *                        never.  wino8_c64_wide (3): C = 64 instances -- 1 = 64 x 128 tiles, 0 = 64 x 64, 2 = 64 x 64
  *                        built for two workgroups per CU, 3 = 1 for k = 7 as F(6,3) and 2 for everything else (k = 11; k = 7 as F(5,4))
+ *   wino8_sv (1)         conv_wino8.hip, the 128 x 64 tile of a k = 7 / 11 shape (C >= 128 on a full grid): the eight waves of a
+ *                        workgroup share the input transform -- each forms all eight points of one channel into a double-buffered
+ *                        V, one barrier per 8 channels -- instead of every wave forming its own point's tile from the same window
+ *                        samples; bit-identical (0 = private tiles).  k = 7, dilation 5 as F(6,3) has no shared instance and keeps
+ *                        private tiles.  dissc_wino8_form reports the form of a launch
  *   ragged_enum (1)      conv_mfma32_kernel on a ragged batch enumerates only the (time tile, utterance) pairs that exist (the
  *                        empty workgroups all sit at the end of the dispatch order); 0 = tile x utterance grid with early exits
  *   pair_wino (0)        [experimental] read at dissc_gen_create: 0 = off (default: the whole-forward gain is 0.2 %); 1 = the residual pairs this measured faster for (C = 32, k = 11, d = 1 / 3;
@@ -344,6 +349,11 @@ typedef struct {
   int32_t unit, ot, cpr, gx, gy;
 } DisscWino8Plan;
 int dissc_wino8_info(int C, int k, int dilation, int R, int B, int Lmax, DisscWino8Plan* out);
+/* Which form of that instance the same launch takes under the current option defaults ("wino8_sv"): *shared_out = 1 where the
+ * eight waves of a workgroup share one input transform (the 128 x 64 tile, mi = 4, ni = 2, wps = 2, of a k = 7 / 11 shape), 0 where
+ * every wave forms its own tile.  The answer is the launch path's own choice.  DISSC_EINVAL as dissc_wino8_info.  Host only: no GPU
+ * is touched.  (Added without a new ABI number: nothing that existed changed.) */
+int dissc_wino8_form(int C, int k, int dilation, int R, int B, int Lmax, int* shared_out);
 
 /* The conv_wino_kernel instance and grid that a C -> C conv of k taps and `dilation` launches in its six-point Toom-Cook form
  * F(4,3) (what dissc_conv1d runs under "wino" = 2 with "wino8" below 2, both launches of mode 2 of dissc_respair1d, and the

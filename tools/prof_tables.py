@@ -174,7 +174,7 @@ def main():
             # argument (3: F(6,3), 4: F(5,4))
             import re
             k = int(re.search(r" k(\d+) ", name + " ").group(1))
-            targs = [int(v) for v in re.search(r"conv_wino8_kernel<([^>]*)>", names[i][0]).group(1).split(",")]
+            targs = [int(v) for v in re.search(r"conv_wino8_kernel<([^>]*)>", names[i][0]).group(1).split(",")[:6]]  # (a seventh: SHV, a bool)
             R = targs[5] if len(targs) > 5 else 3
             fx = fl * 8.0 * ((k + R - 1) // R) / ((9.0 - R) * k)
         row = [str(i), name, names[i][0][:44], f"{d:.0f}", f"{fl / 1e9:.1f}", f"{fl / d / 1e6:.1f}" if fl else "-",
